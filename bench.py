@@ -10,10 +10,14 @@ N = 1 : configs[1] "G1 MSM 2^20 scalars on 1 MI355X".
 N > 1 : the same 2^20-pair MSM sharded by scalar index over N ranks (one process per GPU), one RCCL all-gather
         of the N partial sums (16 x u64 each) + host fold on every rank  ->  "scaling": "strong".
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel k_msm_accumulate, HIP events recorded by the
-library on its own launch stream) and `cpu_baseline` (the oracle's arkworks-shaped Pippenger on the host cores).
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints ONE JSON line on rank 0 with the
+headline only.  `--full` adds everything else to the line, all measured after the timed steps: the per-step check of every timed
+commitment against big-integer arithmetic, `value_uniform`, `latency_ms`, `roofline` (dominant kernel k_msm_accumulate, HIP events
+recorded by the library on its own launch stream), BASELINE config 4, the shard rehearsal, `secondary` and `cpu_baseline` (the oracle's
+arkworks-shaped Pippenger on the host cores).  `--dump-outputs DIR` writes the last timed step's commitment to DIR (see dump_outputs).
 """
 import argparse
+import contextlib
 import ctypes as C
 import hashlib
 import json
@@ -180,6 +184,16 @@ def blob_like_scalars(n, seed):
     return ints_to_wire(blob_like_canonical(n, seed))
 
 
+def dump_outputs(out_dir, commitment):
+    """`--dump-outputs DIR`: what a caller of the timed path receives from its last step -- the commitment, an affine G1 point as 8 u64
+    wire limbs (x || y, Montgomery form; the identity is all zeros) -- written as DIR/commitment.npy.  Every limb is split into its four
+    16-bit pieces, least significant first, so that float64 holds every bit: shape (8, 4), float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    limbs = np.asarray(commitment, dtype=np.uint64).reshape(8)
+    pieces = np.stack([(limbs >> np.uint64(16 * j)) & np.uint64(0xFFFF) for j in range(4)], axis=1).astype(np.float64)
+    np.save(os.path.join(out_dir, "commitment.npy"), pieces)
+
+
 def main_multi(args):
     """`bench.py --multi --gpus N`: one process, N devices behind one kzg_multi handle (csrc/multi.hip): device g holds SRS powers and
     scalars [g n / N, (g+1) n / N) resident, runs its own pipeline of partial MSMs on one host thread of the library, the host folds the
@@ -208,8 +222,12 @@ def main_multi(args):
     for d in set(ids):
         torch.cuda.synchronize(d)
     elapsed = time.perf_counter() - t0
-    wants = [expected_commitment(c, tau) for c in canon_sets]
-    exact = bool(all(np.array_equal(res[i], wants[i % N_BUFFERS]) for i in range(args.steps)))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res[-1])
+    exact = None
+    if args.full:
+        wants = [expected_commitment(c, tau) for c in canon_sets]
+        exact = bool(all(np.array_equal(res[i], wants[i % N_BUFFERS]) for i in range(args.steps)))
     out = {
         "metric": "G1-MSM (scalar,point) pairs/s = 2^%d x KZG coeff-form commitments/s, 2^%d-point SRS" % (LOG_N, LOG_N),
         "value": n * args.steps / elapsed, "unit": "pairs/s", "commitments_per_s": args.steps / elapsed,
@@ -218,16 +236,17 @@ def main_multi(args):
         "data": "synthetic: SRS P_i = tau^i G1 with known tau (generated on the devices); blob-like scalars < 2^248 (Scalars-A); seeded",
         "config": {"workload": "G1 MSM 2^%d scalars (KZG::commit_coeff_form), scalars resident in HBM; step k commits buffer k mod %d" % (LOG_N, N_BUFFERS),
                    "sharding": "--multi: ONE process, %d device(s) %s behind one kzg_multi handle (one host thread and one software pipeline per "
-                               "device, no collective; host fold of the partial sums)" % (args.gpus, ids),
-                   "bit_exact_vs_oracle": exact,
-                   "bit_exact_check": "every timed step's commitment == (sum_i c_i tau^i mod r) * G1 of its buffer (big integers + tests/pyref.py)"},
+                               "device, no collective; host fold of the partial sums)" % (args.gpus, ids)},
         "roofline": {"bound": "hbm", "achieved": BYTES_PER_PAIR * n * args.steps / elapsed / 1e9, "peak": HBM_PEAK_GBS * args.gpus, "unit": "GB/s",
                      "frac": BYTES_PER_PAIR * n * args.steps / elapsed / 1e9 / (HBM_PEAK_GBS * args.gpus), "traffic": None,
                      "kernel": "whole step (the per-kernel figures are in the default mode's line)"},
     }
+    if args.full:
+        out["config"]["bit_exact_vs_oracle"] = exact
+        out["config"]["bit_exact_check"] = "every timed step's commitment == (sum_i c_i tau^i mod r) * G1 of its buffer (big integers + tests/pyref.py)"
     print(json.dumps(out), flush=True)
     mk.close()
-    if not exact:
+    if exact is False:
         raise SystemExit("bench.py --multi: a commitment differs from the expected point")
 
 
@@ -387,12 +406,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary figures (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also check every timed commitment and measure everything "
+                    "beside the headline (uniform scalars, latency, kernel profile and roofline, config 4, shard rehearsal, replicas, secondary "
+                    "figures, CPU baselines); a plain run prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's commitment to DIR/commitment.npy "
+                    "(float64, see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary figures (profiling runs)")
     ap.add_argument("--test-child-cmd", default=None, help=argparse.SUPPRESS)      # tests only: the command the self-launcher starts per rank
     ap.add_argument("--multi", action="store_true", help="ONE process driving --gpus devices through kzg_multi_* (no torch.distributed, no "
                     "collective): the other partitioning of SURVEY.md 8e; the driver's contract (one rank per GPU over RCCL) is the default mode")
     args, _unknown = ap.parse_known_args()          # (a launcher may append arguments of its own, e.g. --local-rank: ignored)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.multi:
         return main_multi(args)
 
@@ -455,10 +481,11 @@ def main():
         sft = n // 2 + j
         canon_sets.append(canon_sets[j][-sft:] + canon_sets[j][:-sft]); wire_sets.append(np.roll(wire_sets[j], sft, axis=0))
     canon_a, scalars = canon_sets[0], wire_sets[0]
-    canon_b, scalars_b = uniform_scalars(n, seed0 + 1)                  # Scalars-B (seed + 1)
     d_sets = [torch.from_numpy(np.ascontiguousarray(w[sh.lo:sh.hi]).view(np.int64)).cuda() for w in wire_sets]
     d_scalars = d_sets[0]
-    d_scalars_b = torch.from_numpy(scalars_b[sh.lo:sh.hi].view(np.int64)).cuda()
+    if args.full:                                                       # Scalars-B (seed + 1): the figures beside the headline only
+        canon_b, scalars_b = uniform_scalars(n, seed0 + 1)
+        d_scalars_b = torch.from_numpy(scalars_b[sh.lo:sh.hi].view(np.int64)).cuda()
     rot_ptrs = [d.data_ptr() for d in d_sets]
     torch.cuda.synchronize()
 
@@ -545,14 +572,51 @@ def main():
     run_steps(cold_n, rot_ptrs, depth_used)
     torch.cuda.synchronize()
     cold_ms_per_step = (time.perf_counter() - t_cold) / max(1, cold_n) * 1e3
-    clocks = ClockSampler(local_rank)                                  # engine clock under this very load, sampled in the UNTIMED spin-up only:
-    with clocks:                                                        # inside a timed region the sysfs reads cost 4-10 % (1.15 -> 1.27 ms per step at 20 steps)
+    clocks = ClockSampler(local_rank)                                  # engine clock under this very load, sampled in the UNTIMED spin-up only (--full):
+    with clocks if args.full else contextlib.nullcontext():            # inside a timed region the sysfs reads cost 4-10 % (1.15 -> 1.27 ms per step at 20 steps)
         run_steps(spinup_steps - cold_n, rot_ptrs, depth_used)
     run_steps(args.warmup, rot_ptrs, depth_used)                        # the W untimed warm-up steps
     timed_results = []
     elapsed, result = timed(args.steps, rot_ptrs, depth_used, keep=timed_results)    # THE timed region: exactly --steps steps, step k on buffer k mod N_BUFFERS
     per_rank_ms = [e / args.steps * 1e3 for e in rank_elapsed]
     comm_ranks = dist.get_world_size() if multi else 1
+    ms_per_step = elapsed / args.steps * 1e3
+    headline = {
+        "metric": "G1-MSM (scalar,point) pairs/s = 2^%d x KZG coeff-form commitments/s, 2^%d-point SRS" % (LOG_N, LOG_N),
+        "value": n * args.steps / elapsed,
+        "unit": "pairs/s",
+        "commitments_per_s": args.steps / elapsed,
+        "n_gpus": world,
+        "rccl_ranks": comm_ranks, "exchange_backend": (backend if multi else None),
+        "ms_per_step_per_rank": per_rank_ms,
+        "launched_by": "bench.py itself (N child ranks)" if os.environ.get("KZG_BENCH_SELF_LAUNCHED") else ("external launcher" if world > 1 else "single process"),
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "int32x9 (29-bit limbs, 64-bit accumulate)",
+    }
+    config = {"workload": "G1 MSM 2^%d scalars (KZG::commit_coeff_form), scalars resident in HBM; step k commits buffer k mod %d "
+                          "(%d distinct resident scalar sets, %d MiB)" % (LOG_N, N_BUFFERS, N_BUFFERS, N_BUFFERS * 32 * n >> 20),
+              "sharding": "by scalar index over %d GPU(s); all-gather of XYZZ partials + host fold" % world,
+              "host_gc_in_timed_region": os.environ.get("KZG_BENCH_GC", "0") != "0",
+              "pipeline_depth": sh.group_depth(depth_used, GROUP), "steps_per_launch": GROUP,
+              "untimed_before_warmup": "set-up: %d steps (workspaces), the first device-wide synchronisation, %d steps (clock ramp); then the %d warm-up steps" % (depth_used, spinup_steps, args.warmup)}
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, result)
+    if not args.full:                                                   # a plain run: the headline, nothing measured or checked beside it
+        if rank == 0:
+            out = dict(headline, data="synthetic: SRS P_i = tau^i G1 with known tau (generated on device); blob-like scalars < 2^248 (Scalars-A); seeded",
+                       config=config)
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(out) + "\n").encode())
+        if gc_off:
+            gc.enable()
+        if multi:
+            dist.destroy_process_group()
+        return
     if multi:
         # every rank must hold the same folded commitment
         chk = torch.from_numpy(result.view(np.int64).copy())
@@ -860,8 +924,6 @@ def main():
                                       "per_rank": "uploads %.0f MiB, IFFT and quotient of all 2^%d elements on every rank, MSM over its slice; exchange: 128 B per rank" % (32.0 * n / 2 ** 20, LOG_N),
                                       "bit_exact_vs_big_integers": old_ok},
                     "bit_exact_check": "commitment == f^(tau) G1, y == f^(z), proof == ((f^(tau) - y) / (tau - z)) G1 with f^ by big-integer barycentric evaluation (bench.py eval_form_ground_truth)"})
-        ms_per_step = elapsed / args.steps * 1e3
-        pairs_per_s = n * args.steps / elapsed
         acc_ms = phase_alone[4]                                   # k_msm_accumulate, average launch duration, running alone
         achieved = BYTES_PER_PAIR * units_per_launch / (acc_ms * 1e-3) / 1e9 if acc_ms > 0 else 0.0
         traffic, traffic_src = pmc_traffic_bytes(LOG_N) if world == 1 else (None, "PMC passes are single-GPU")
@@ -869,37 +931,18 @@ def main():
         # table mode (two-level sort from the scalars): coarse histogram | scan + pass 1 | pass 2; other modes: digits | histogram + scan | scatter
         phase_names = ["digits_or_coarse_hist", "sort_pass1", "sort_pass2", "unused", "accumulate", "bucket_sums_reduce1", "reduce2", "device_total"]
         out = {
-            "metric": "G1-MSM (scalar,point) pairs/s = 2^%d x KZG coeff-form commitments/s, 2^%d-point SRS" % (LOG_N, LOG_N),
-            "value": pairs_per_s,
-            "unit": "pairs/s",
-            "commitments_per_s": args.steps / elapsed,
+            **headline,
             "value_uniform": n * side_steps / elapsed_b,
             "latency_ms": elapsed_lat / side_steps * 1e3,
-            "n_gpus": world,
-            "rccl_ranks": comm_ranks, "exchange_backend": (backend if multi else None),
-            "ms_per_step_per_rank": per_rank_ms,
-            "launched_by": "bench.py itself (N child ranks)" if os.environ.get("KZG_BENCH_SELF_LAUNCHED") else ("external launcher" if world > 1 else "single process"),
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "int32x9 (29-bit limbs, 64-bit accumulate)",
             "data": "synthetic: SRS P_i = tau^i G1 with known tau (generated on device); value: blob-like scalars < 2^248 (Scalars-A), "
                     "value_uniform: uniform scalars in [0, r) (Scalars-B, seed + 1); seeded",
-            "config": {"workload": "G1 MSM 2^%d scalars (KZG::commit_coeff_form), scalars resident in HBM; step k commits buffer k mod %d "
-                                   "(%d distinct resident scalar sets, %d MiB)" % (LOG_N, N_BUFFERS, N_BUFFERS, N_BUFFERS * 32 * n >> 20),
-                       "sharding": "by scalar index over %d GPU(s); all-gather of XYZZ partials + host fold" % world,
-                       "host_gc_in_timed_region": os.environ.get("KZG_BENCH_GC", "0") != "0",
-                       "pipeline_depth": sh.group_depth(depth_used, GROUP), "steps_per_launch": GROUP,
-                       "cold_start_ms_per_step": cold_ms_per_step,
-                       "cold_start_is": "the first %d steps after the idle set-up (engine clock not yet settled), this rank; untimed, reported only" % cold_n,
-                       "untimed_before_warmup": "set-up: %d steps (workspaces), the first device-wide synchronisation, %d steps (clock ramp); then the %d warm-up steps" % (depth_used, spinup_steps, args.warmup),
-                       "latency_ms_is": "one commitment at a time (depth 1, one exchange per step), %d steps" % side_steps,
-                       "bit_exact_vs_oracle": exact,
-                       "bit_exact_check": "EVERY timed step's folded commitment == (sum_i c_i tau^i mod r) * G1 of its buffer by big-integer arithmetic "
-                                          "+ one affine scalar multiplication (tests/pyref.py); likewise value_uniform and latency_ms; on rank 0 at every world size"},
+            "config": dict(config,
+                           cold_start_ms_per_step=cold_ms_per_step,
+                           cold_start_is="the first %d steps after the idle set-up (engine clock not yet settled), this rank; untimed, reported only" % cold_n,
+                           latency_ms_is="one commitment at a time (depth 1, one exchange per step), %d steps" % side_steps,
+                           bit_exact_vs_oracle=exact,
+                           bit_exact_check="EVERY timed step's folded commitment == (sum_i c_i tau^i mod r) * G1 of its buffer by big-integer arithmetic "
+                                           "+ one affine scalar multiplication (tests/pyref.py); likewise value_uniform and latency_ms; on rank 0 at every world size"),
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                          "kernel": "k_msm_accumulate", "avg_launch_ms": acc_ms,

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_emits_the_contract_line():
     env = dict(os.environ, KZG_BENCH_LOG_N="14")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--full"],
                          capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -75,6 +75,41 @@ def test_bench_emits_the_contract_line():
     assert clk is None or (200 < clk["sclk_mhz_min"] <= clk["sclk_mhz_mean"] <= clk["sclk_mhz_max"] < 4000 and clk["samples"] >= 1)
 
 
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_commitment(tmp_path):
+    """A plain run (no --full) prints the headline and nothing measured or checked beside it; --dump-outputs writes the last timed step's
+    commitment, which must be the commitment of that step's buffer (step k commits buffer k mod 8) by big-integer arithmetic."""
+    import hashlib
+    import numpy as np
+    import bench
+    log_n, steps = 14, 11
+    env = dict(os.environ, KZG_BENCH_LOG_N=str(log_n))
+    out_dir = tmp_path / "outputs"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2",
+                          "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{")
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert key in d, key
+    assert d["steps"] == steps and d["warmup"] == 2 and d["n_gpus"] == 1 and d["higher_is_better"] is True and d["unit"] == "pairs/s"
+    assert d["value"] > 0 and abs(d["value"] - (1 << log_n) * steps / (d["ms_per_step"] * steps * 1e-3)) / d["value"] < 1e-6
+    for key in ("value_uniform", "latency_ms", "roofline", "cpu_baseline", "cpu_baseline_ntt", "config4", "shard_rehearsal", "secondary",
+                "gpu_clock_under_load", "phases_ms_per_launch"):
+        assert key not in d, key
+    got = np.load(str(out_dir / "commitment.npy"))
+    assert got.dtype == np.float64 and got.shape == (8, 4)
+    wire = np.zeros(8, np.uint64)
+    for j in range(4):
+        wire |= got[:, j].astype(np.uint64) << np.uint64(16 * j)
+    buf = (steps - 1) % bench.N_BUFFERS                  # 2: the third independently drawn set, not rotated
+    assert buf < bench.N_BUFFERS // 2
+    seed0 = 0x4B5A472D424E3235 & 0x7FFFFFFF
+    tau = int.from_bytes(hashlib.sha256(b"kzg-bn254-mi355x/srs/v1").digest(), "big") % bench.FR
+    want = bench.expected_commitment(bench.blob_like_canonical(1 << log_n, seed0 if buf == 0 else seed0 + 1 + buf), tau)
+    assert np.array_equal(wire, want)
+
+
 def test_bench_n_gpus_without_launcher_starts_its_own_ranks():
     """`python bench.py --gpus 2` with NO launcher (no WORLD_SIZE) must produce the line: bench.py starts the two
     ranks itself before anything touches the GPU (one child process per rank, RANK / WORLD_SIZE / MASTER_* set), relays rank 0's JSON
@@ -82,7 +117,7 @@ def test_bench_n_gpus_without_launcher_starts_its_own_ranks():
     env = dict(os.environ, KZG_BENCH_LOG_N="16", KZG_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for key in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(key, None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-secondary"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--no-secondary"],
                          capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert res.returncode == 0, (res.stdout[-1500:], res.stderr[-3000:])
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -126,7 +161,7 @@ def test_bench_two_ranks_gloo_is_bit_exact():
     for key in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(key, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29631", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--no-secondary"]
+           "--master-port", "29631", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--full", "--no-secondary"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert res.returncode == 0, (res.stdout[-1500:], res.stderr[-3000:])
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -145,7 +180,7 @@ def test_bench_two_ranks_gloo_carries_config4():
     env = dict(os.environ, KZG_BENCH_LOG_N="15", KZG_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", KZG_BENCH_REPLICAS="0")
     for key in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(key, None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full"],
                          capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert res.returncode == 0, (res.stdout[-1500:], res.stderr[-3000:])
     d = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
@@ -167,7 +202,7 @@ def test_bench_one_rank_through_rccl_takes_the_multi_gpu_path():
     env = dict(os.environ, KZG_BENCH_LOG_N="17", KZG_BENCH_FORCE_EXCHANGE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for key in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "KZG_BENCH_BACKEND", "MASTER_PORT"):
         env.pop(key, None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3", "--no-secondary",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3", "--full", "--no-secondary",
                           "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert res.returncode == 0, (res.stdout[-1500:], res.stderr[-3000:])
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -185,7 +220,7 @@ def test_bench_multi_mode_two_contexts_on_one_gpu_is_bit_exact():
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, KZG_BENCH_LOG_N="17")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--multi", "--gpus", "2", "--steps", "9", "--warmup", "2"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--multi", "--gpus", "2", "--steps", "9", "--warmup", "2", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-400:] + r.stderr[-800:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -168,6 +168,21 @@ def test_bench_self_launch_takes_its_ranks_along_when_stopped():
         assert alive == "" or alive.startswith("Z"), (pid, alive)
 
 
+def test_bench_dump_outputs_keeps_every_bit_of_the_commitment(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the last timed commitment (8 u64 wire limbs) as float64: four exact 16-bit pieces per limb,
+    least significant first, from which the wire point comes back bit for bit."""
+    import bench
+    wire = pyref.point_to_wire(pyref.ec_mul(123456789, (1, 2)))
+    bench.dump_outputs(str(tmp_path / "out"), wire)
+    got = np.load(str(tmp_path / "out" / "commitment.npy"))
+    assert got.dtype == np.float64 and got.shape == (8, 4)
+    assert np.all(got == np.floor(got)) and got.min() >= 0 and got.max() <= 0xFFFF
+    back = np.zeros(8, np.uint64)
+    for j in range(4):
+        back |= got[:, j].astype(np.uint64) << np.uint64(16 * j)
+    assert np.array_equal(back, wire)
+
+
 def test_shard_steps_per_launch_by_world_size(k, monkeypatch):
     """How many steps of a commitment stream one launch carries (ShardedMsm.auto_group; host logic, the capacity rule is
     kzg_msm_batch_capacity): a 2^20-pair commitment over 1 / 2 / 4 / 8 ranks -> 1 / 2 / 2 / 4; every rank derives it from n // world, so
