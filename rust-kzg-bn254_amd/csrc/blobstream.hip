@@ -324,3 +324,8 @@ int32_t kzg_commit_and_prove_blob_end(kzg_ctx* ctx, int32_t job, uint64_t* out_c
 }
 
 }  // extern "C"
+
+#if defined(KZG_DEVICE_BOUND_CHECK)   // the device bound-check variant only (field29.h, `make boundcheck`)
+#include "field29.h"
+KZG_BOUND_CHECK_EXPORTS(blobstream)
+#endif

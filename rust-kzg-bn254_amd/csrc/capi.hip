@@ -1932,3 +1932,35 @@ int32_t kzg_verify_blob_kzg_proof_batch(kzg_ctx* ctx, const uint8_t* const* blob
 namespace kzg {
 int32_t srs_upload_plain(kzg_ctx* ctx, const uint64_t* g1_xy_mont, size_t n_points, kzg_srs** out) { return srs_upload_impl(ctx, g1_xy_mont, n_points, out, false); }
 }  // namespace kzg
+
+#if defined(KZG_DEVICE_BOUND_CHECK)
+#include "field29.h"
+KZG_BOUND_CHECK_EXPORTS(capi)
+// The variant library's totals over every translation unit: counts[site] summed, first[site] = the operand limbs kept by the first
+// translation unit (in the order below) whose counter of that site fired.  Not declared in include/kzg_bn254_mi355x.h.
+#define KZG_BC_UNITS(X) X(msm) X(ntt) X(poly) X(lagrange) X(srs) X(g1fft) X(capi) X(blobstream) X(multi) X(ubench)
+#define KZG_BC_DECLARE(name) extern "C" int kzg_bc_read_##name(unsigned long long*, int32_t*); extern "C" int kzg_bc_reset_##name();
+KZG_BC_UNITS(KZG_BC_DECLARE)
+extern "C" int kzg_bc_sites() { return kzg::KZG_SITES; }
+extern "C" int kzg_bc_read_all(unsigned long long* counts, int32_t* first) {
+    unsigned long long c[kzg::KZG_SITES];
+    int32_t f[kzg::KZG_SITES][kzg::NL];
+    for (int s = 0; s < kzg::KZG_SITES; ++s) counts[s] = 0;
+    int rc = 0;
+#define KZG_BC_READ(name)                                                                                            \
+    if (kzg_bc_read_##name(c, &f[0][0]) != 0) rc = -1;                                                               \
+    for (int s = 0; s < kzg::KZG_SITES; ++s) {                                                                       \
+        if (c[s] && !counts[s])                                                                                      \
+            for (int j = 0; j < kzg::NL; ++j) first[s * kzg::NL + j] = f[s][j];                                      \
+        counts[s] += c[s];                                                                                           \
+    }
+    KZG_BC_UNITS(KZG_BC_READ)
+    return rc;
+}
+extern "C" int kzg_bc_reset_all() {
+    int rc = 0;
+#define KZG_BC_RESET(name) if (kzg_bc_reset_##name() != 0) rc = -1;
+    KZG_BC_UNITS(KZG_BC_RESET)
+    return rc;
+}
+#endif

@@ -33,7 +33,6 @@
 #endif
 
 #if defined(KZG_BOUND_CHECK)
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #endif
@@ -49,35 +48,174 @@ struct Fe {
     int32_t l[NL];
 };
 
-#if defined(KZG_BOUND_CHECK)
+// ---------------------------------------------------------------------------------------------
+// The preconditions of the lazy formulas as predicates (true = inside the bound), in plain integer and double arithmetic so that
+// the host and the device evaluate the same code.  Nothing calls them in the product build.  Two builds turn them into checks:
+//   KZG_BOUND_CHECK         (host, g++: tests/hostcheck)  a violation prints its site and aborts;
+//   KZG_DEVICE_BOUND_CHECK  (device, `make boundcheck`)   a violation counts into a per-site array of the translation unit and the
+//                                                         first one per site keeps its operand limbs (never faults, never aborts).
+// ---------------------------------------------------------------------------------------------
+constexpr double KZG_MUL_LIMB_LIMIT = 7.3e17;           // max|a_j| max|b_j| < (2^63 - 9*2^58)/9 = 2^59.35 = 7.366e17, with margin
+constexpr double KZG_REDUCE_LIMIT = 169.0;              // |a| < 169 m: 2^261 / m = 169.27
+
 template <class F>
-inline long double fe_approx(const Fe<F>& a) {
-    long double v = 0;
-    for (int j = NL - 1; j >= 0; --j) v = v * 536870912.0L + (long double)a.l[j];
+KZG_HD double fe_value_approx(const Fe<F>& a) {          // sum l_j 2^(29 j), relative error < 2^-50
+    double v = 0;
+    for (int j = NL - 1; j >= 0; --j) v = v * 536870912.0 + (double)a.l[j];
     return v;
 }
 template <class F>
-inline long double fe_modulus_approx() {
-    long double v = 0;
-    for (int j = NL - 1; j >= 0; --j) v = v * 536870912.0L + (long double)F::P[j];
+KZG_HD double fe_modulus_approx() {
+    double v = 0;
+    for (int j = NL - 1; j >= 0; --j) v = v * 536870912.0 + (double)F::P[j];
     return v;
 }
 template <class F>
-inline void fe_check_mul_operands(const Fe<F>& a, const Fe<F>& b, const char* what) {
-    long double ma = 0, mb = 0;
+KZG_HD double fe_max_limb(const Fe<F>& a) {
+    double m = 0;
+    for (int j = 0; j < NL; ++j) { const double x = a.l[j] < 0 ? -(double)a.l[j] : (double)a.l[j]; m = x > m ? x : m; }
+    return m;
+}
+// fe_mul / fe_sqr / fe_mul2 / fe_sqr2 / fe_mul_ilp: |a_j| |b_j| < 2^59.35 for every limb pair, |a b| < 2^261 m
+template <class F>
+KZG_HD bool fe_bound_mul_limbs(const Fe<F>& a, const Fe<F>& b) { return fe_max_limb(a) * fe_max_limb(b) < KZG_MUL_LIMB_LIMIT; }
+template <class F>
+KZG_HD bool fe_bound_mul_value(const Fe<F>& a, const Fe<F>& b) {
+    const double va = fe_value_approx(a), vb = fe_value_approx(b);
+    return (va < 0 ? -va : va) * (vb < 0 ? -vb : vb) < 0x1p261 * fe_modulus_approx<F>() * (1.0 - 1e-12);   // 2^261 m, less the 2^-50 error of the doubles
+}
+// fe_mulsub: 9 (max|a||b| + max|c||d|) + 9 2^58 < 2^63 per column, |a b| + |c d| < 2^261 m
+template <class F>
+KZG_HD bool fe_bound_mulsub_limbs(const Fe<F>& a, const Fe<F>& b, const Fe<F>& c, const Fe<F>& d) {
+    return 9.0 * (fe_max_limb(a) * fe_max_limb(b) + fe_max_limb(c) * fe_max_limb(d)) + 9.0 * 288230376151711744.0 < 9223372036854775807.0;
+}
+template <class F>
+KZG_HD bool fe_bound_mulsub_value(const Fe<F>& a, const Fe<F>& b, const Fe<F>& c, const Fe<F>& d) {
+    const double va = fe_value_approx(a), vb = fe_value_approx(b), vc = fe_value_approx(c), vd = fe_value_approx(d);
+    const double ab = va * vb, cd = vc * vd;
+    return (ab < 0 ? -ab : ab) + (cd < 0 ? -cd : cd) < 0x1p261 * fe_modulus_approx<F>() * (1.0 - 1e-12);
+}
+// limbs 0..7 in [0, 2^29) (the top limb carries the sign)
+template <class F>
+KZG_HD bool fe_bound_normalised(const Fe<F>& a) {
+    bool ok = true;
+    for (int j = 0; j < NL - 1; ++j) ok &= a.l[j] >= 0 && a.l[j] <= (int32_t)LMASK;
+    return ok;
+}
+// a < b exactly, both normalised (lexicographic from the signed top limb down)
+template <class F>
+KZG_HD bool fe_normalised_less(const Fe<F>& a, const Fe<F>& b) {
+    for (int j = NL - 1; j >= 0; --j)
+        if (a.l[j] != b.l[j]) return a.l[j] < b.l[j];
+    return false;
+}
+// fe_is_zero_mod, fe_canon: normalised and in (-m, 2m), exactly
+template <class F>
+KZG_HD bool fe_bound_canon(const Fe<F>& a) {
+    if (!fe_bound_normalised(a)) return false;
+    Fe<F> lo, hi;                                        // -m and 2m, normalised
+    int64_t cl = 0, ch = 0;
     for (int j = 0; j < NL; ++j) {
-        ma = fmaxl(ma, fabsl((long double)a.l[j]));
-        mb = fmaxl(mb, fabsl((long double)b.l[j]));
+        cl += -(int64_t)F::P[j]; ch += 2 * (int64_t)F::P[j];
+        lo.l[j] = j < NL - 1 ? (int32_t)(cl & LMASK) : (int32_t)cl; hi.l[j] = j < NL - 1 ? (int32_t)(ch & LMASK) : (int32_t)ch;
+        cl >>= LB; ch >>= LB;
     }
-    const long double lim = 7.3e17L;              // (2^63 - 9*2^58)/9 = 2^59.35 = 7.366e17
-    if (ma * mb >= lim) { fprintf(stderr, "KZG_BOUND_CHECK: %s limb bound violated: %Lg * %Lg\n", what, ma, mb); abort(); }
-    long double m = fe_modulus_approx<F>();
-    long double prod = fabsl(fe_approx(a)) * fabsl(fe_approx(b));
-    if (prod >= ldexpl(1.0L, 261) * m) { fprintf(stderr, "KZG_BOUND_CHECK: %s value bound violated: |a*b| / (R m) = %Lg\n", what, prod / (ldexpl(1.0L, 261) * m)); abort(); }
+    return fe_normalised_less(lo, a) && fe_normalised_less(a, hi);
 }
-#define KZG_CHECK_MUL(a, b, what) fe_check_mul_operands(a, b, what)
+// fe_norm: no limb leaves int32 while the carries propagate
+template <class F>
+KZG_HD bool fe_bound_norm(const Fe<F>& a) {
+    int64_t c = 0;
+    bool ok = true;
+    for (int j = 0; j < NL; ++j) {
+        const int64_t v = (int64_t)a.l[j] + c;
+        ok &= v >= INT32_MIN && v <= INT32_MAX;
+        c = v >> LB;
+    }
+    return ok;
+}
+// fe_reduce, fe_reduce_small: |a| < 169 m, and the normalisation they start with stays inside int32
+template <class F>
+KZG_HD bool fe_bound_reduce(const Fe<F>& a) {
+    const double v = fe_value_approx(a);
+    return fe_bound_norm(a) && (v < 0 ? -v : v) < KZG_REDUCE_LIMIT * fe_modulus_approx<F>();
+}
+// fe_to_wire: normalised, |a| < 169 m
+template <class F>
+KZG_HD bool fe_bound_to_wire(const Fe<F>& a) { return fe_bound_normalised(a) && fe_bound_reduce(a); }
+// fe_pack: canonical limbs, value < 2^256
+template <class F>
+KZG_HD bool fe_bound_pack(const Fe<F>& a) { return fe_bound_normalised(a) && a.l[NL - 1] >= 0 && a.l[NL - 1] < (1 << 24); }
+// fe_add / fe_sub / fe_dbl: no limb overflows int32
+template <class F>
+KZG_HD bool fe_bound_add(const Fe<F>& a, const Fe<F>& b, int sign) {      // sign = +1: a + b, -1: a - b
+    bool ok = true;
+    for (int j = 0; j < NL; ++j) {
+        const int64_t v = (int64_t)a.l[j] + sign * (int64_t)b.l[j];
+        ok &= v >= INT32_MIN && v <= INT32_MAX;
+    }
+    return ok;
+}
+
+// Check sites: one counter each in the device variant (the index is the site's position here).
+enum KzgBoundSite {
+    KZG_SITE_MUL_LIMBS, KZG_SITE_MUL_VALUE, KZG_SITE_MULSUB_LIMBS, KZG_SITE_MULSUB_VALUE, KZG_SITE_IS_ZERO_MOD, KZG_SITE_CANON,
+    KZG_SITE_REDUCE, KZG_SITE_REDUCE_SMALL, KZG_SITE_TO_WIRE, KZG_SITE_PACK, KZG_SITE_ADD, KZG_SITE_SUB, KZG_SITE_DBL, KZG_SITE_NORM,
+    KZG_SITES
+};
+
+#if defined(KZG_BOUND_CHECK)
+static const char* const kzg_site_names[KZG_SITES] = {
+    "mul limb bound", "mul value bound", "fe_mulsub limb bound", "fe_mulsub value bound", "fe_is_zero_mod precondition",
+    "fe_canon precondition", "fe_reduce precondition", "fe_reduce_small precondition", "fe_to_wire precondition", "fe_pack precondition",
+    "fe_add int32 overflow", "fe_sub int32 overflow", "fe_dbl int32 overflow", "fe_norm int32 overflow"};
+template <class F>
+inline void kzg_bound_fail(int site, const char* what, const Fe<F>& a) {
+    fprintf(stderr, "KZG_BOUND_CHECK: %s: %s violated, operand limbs", what, kzg_site_names[site]);
+    for (int j = 0; j < NL; ++j) fprintf(stderr, " %d", a.l[j]);
+    fprintf(stderr, "\n");
+    abort();
+}
+#define KZG_REQUIRE(ok, site, what, a) do { if (!(ok)) kzg_bound_fail(site, what, a); } while (0)
+#elif defined(KZG_DEVICE_BOUND_CHECK) && defined(__HIPCC__)
+// Per translation unit (static): the violations per site and, for the first violation of a site, the limbs of its first operand.
+// KZG_BOUND_CHECK_EXPORTS(name) below gives the host its reader and reset.
+static __device__ unsigned long long kzg_bc_count[KZG_SITES];
+static __device__ int32_t kzg_bc_first[KZG_SITES][NL];
+template <class F>
+KZG_HD void kzg_bound_record(int site, const Fe<F>& a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (atomicAdd(&kzg_bc_count[site], 1ull) == 0ull)
+        for (int j = 0; j < NL; ++j) kzg_bc_first[site][j] = a.l[j];
 #else
-#define KZG_CHECK_MUL(a, b, what) ((void)0)
+    (void)site; (void)a;
+#endif
+}
+#define KZG_REQUIRE(ok, site, what, a) do { if (!(ok)) kzg_bound_record(site, a); } while (0)
+#else
+#define KZG_REQUIRE(ok, site, what, a) ((void)0)
+#endif
+#define KZG_CHECK_MUL(a, b, what) do { KZG_REQUIRE(fe_bound_mul_limbs(a, b), KZG_SITE_MUL_LIMBS, what, a); \
+                                       KZG_REQUIRE(fe_bound_mul_value(a, b), KZG_SITE_MUL_VALUE, what, a); } while (0)
+
+// Every .hip file of csrc/ ends with KZG_BOUND_CHECK_EXPORTS(<file>) under KZG_DEVICE_BOUND_CHECK: the host reader (counts and first
+// operands of this translation unit's sites) and reset; capi.hip's kzg_bc_read_all / kzg_bc_reset_all cover them all.  Empty in
+// every other build.
+#if defined(KZG_DEVICE_BOUND_CHECK) && defined(__HIPCC__)
+#define KZG_BOUND_CHECK_EXPORTS(name)                                                                                              \
+    extern "C" int kzg_bc_read_##name(unsigned long long* counts, int32_t* first) {                                                \
+        if (hipMemcpyFromSymbol(counts, HIP_SYMBOL(kzg::kzg_bc_count), sizeof(kzg::kzg_bc_count)) != hipSuccess) return -1;        \
+        if (hipMemcpyFromSymbol(first, HIP_SYMBOL(kzg::kzg_bc_first), sizeof(kzg::kzg_bc_first)) != hipSuccess) return -1;         \
+        return 0;                                                                                                                   \
+    }                                                                                                                               \
+    extern "C" int kzg_bc_reset_##name() {                                                                                         \
+        static const unsigned long long zc[kzg::KZG_SITES] = {};                                                                    \
+        static const int32_t zf[kzg::KZG_SITES][kzg::NL] = {};                                                                      \
+        if (hipMemcpyToSymbol(HIP_SYMBOL(kzg::kzg_bc_count), zc, sizeof(zc)) != hipSuccess) return -1;                              \
+        return hipMemcpyToSymbol(HIP_SYMBOL(kzg::kzg_bc_first), zf, sizeof(zf)) == hipSuccess ? 0 : -1;                             \
+    }
+#else
+#define KZG_BOUND_CHECK_EXPORTS(name)
 #endif
 
 // The compiler tracks known-non-negative limbs (anything masked with LMASK) and, for a product of such a limb with a
@@ -319,25 +457,8 @@ KZG_HD void fe_sqr2(Fe<F>& r1, const Fe<F>& a1, Fe<F>& r2, const Fe<F>& a2) {
 // Result normalised, in (-m, 2m).
 template <class F>
 KZG_HD void fe_mulsub(Fe<F>& r, const Fe<F>& a, const Fe<F>& b, const Fe<F>& c, const Fe<F>& d) {
-#if defined(KZG_BOUND_CHECK)
-    {
-        long double mx = 0;
-        for (int j = 0; j < NL; ++j) {
-            mx = fmaxl(mx, fmaxl(fabsl((long double)a.l[j]) * fabsl((long double)b.l[j]), 0.0L));
-        }
-        long double ma = 0, mb = 0, mc = 0, md = 0;
-        for (int j = 0; j < NL; ++j) {
-            ma = fmaxl(ma, fabsl((long double)a.l[j])); mb = fmaxl(mb, fabsl((long double)b.l[j]));
-            mc = fmaxl(mc, fabsl((long double)c.l[j])); md = fmaxl(md, fabsl((long double)d.l[j]));
-        }
-        if (9.0L * (ma * mb + mc * md) + 9.0L * 288230376151711744.0L >= 9223372036854775807.0L) {
-            fprintf(stderr, "KZG_BOUND_CHECK: fe_mulsub limb bound violated: %Lg %Lg %Lg %Lg\n", ma, mb, mc, md); abort();
-        }
-        long double m = fe_modulus_approx<F>();
-        long double prod = fabsl(fe_approx(a)) * fabsl(fe_approx(b)) + fabsl(fe_approx(c)) * fabsl(fe_approx(d));
-        if (prod >= ldexpl(1.0L, 261) * m) { fprintf(stderr, "KZG_BOUND_CHECK: fe_mulsub value bound violated\n"); abort(); }
-    }
-#endif
+    KZG_REQUIRE(fe_bound_mulsub_limbs(a, b, c, d), KZG_SITE_MULSUB_LIMBS, "fe_mulsub", a);
+    KZG_REQUIRE(fe_bound_mulsub_value(a, b, c, d), KZG_SITE_MULSUB_VALUE, "fe_mulsub", a);
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(KZG_NO_FE_ASM)
     {
         int32_t q[NL], nc[NL];
@@ -442,11 +563,13 @@ KZG_HD void fe_sqr(Fe<F>& r, const Fe<F>& a) {
 // ---------------------------------------------------------------------------------------------
 template <class F>
 KZG_HD void fe_add(Fe<F>& r, const Fe<F>& a, const Fe<F>& b) {
+    KZG_REQUIRE(fe_bound_add(a, b, 1), KZG_SITE_ADD, "fe_add", a);
 #pragma unroll
     for (int j = 0; j < NL; ++j) r.l[j] = a.l[j] + b.l[j];
 }
 template <class F>
 KZG_HD void fe_sub(Fe<F>& r, const Fe<F>& a, const Fe<F>& b) {
+    KZG_REQUIRE(fe_bound_add(a, b, -1), KZG_SITE_SUB, "fe_sub", a);
 #pragma unroll
     for (int j = 0; j < NL; ++j) r.l[j] = a.l[j] - b.l[j];
 }
@@ -464,6 +587,7 @@ KZG_HD void fe_cneg(Fe<F>& r, const Fe<F>& a, uint32_t neg) {
 }
 template <class F>
 KZG_HD void fe_dbl(Fe<F>& r, const Fe<F>& a) {
+    KZG_REQUIRE(fe_bound_add(a, a, 1), KZG_SITE_DBL, "fe_dbl", a);
 #pragma unroll
     for (int j = 0; j < NL; ++j) r.l[j] = a.l[j] * 2;
 }
@@ -485,6 +609,7 @@ KZG_HD void fe_select(Fe<F>& r, bool c, const Fe<F>& a, const Fe<F>& b) {   // r
 // Signed carry propagation: limbs 0..7 -> [0, 2^29), limb 8 keeps the sign.  Value unchanged.
 template <class F>
 KZG_HD void fe_norm(Fe<F>& a) {
+    KZG_REQUIRE(fe_bound_norm(a), KZG_SITE_NORM, "fe_norm", a);
 #pragma unroll
     for (int j = 0; j < NL - 1; ++j) {
         int32_t c = a.l[j] >> LB;
@@ -496,6 +621,7 @@ KZG_HD void fe_norm(Fe<F>& a) {
 // a is a NORMALISED value in (-m, 2m) (any fe_mul / fe_sqr result): a == 0 mod m  <=>  a in {0, m}
 template <class F>
 KZG_HD bool fe_is_zero_mod(const Fe<F>& a) {
+    KZG_REQUIRE(fe_bound_canon(a), KZG_SITE_IS_ZERO_MOD, "fe_is_zero_mod", a);
     uint32_t z0 = 0, zp = 0;
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
@@ -515,6 +641,7 @@ KZG_HD bool fe_is_literal_zero(const Fe<F>& a) {
 // normalised a in (-m, 2m)  ->  canonical [0, m)
 template <class F>
 KZG_HD void fe_canon(Fe<F>& a) {
+    KZG_REQUIRE(fe_bound_canon(a), KZG_SITE_CANON, "fe_canon", a);
     Fe<F> t;
     bool neg = a.l[NL - 1] < 0;
 #pragma unroll
@@ -532,17 +659,21 @@ KZG_HD void fe_canon(Fe<F>& a) {
 // any lazy value with |a| < 169 m  ->  normalised representative in (-m, 2m)  (mont_mul by R' mod m)
 template <class F>
 KZG_HD void fe_reduce(Fe<F>& a) {
+    KZG_REQUIRE(fe_bound_reduce(a), KZG_SITE_REDUCE, "fe_reduce", a);
     Fe<F> one;
     fe_set_one(one);
     fe_norm(a);
     fe_mul(a, a, one);
 }
 
-// The same reduction WITHOUT a Montgomery product (no factor involved): subtract q m with q = floor(top limb / (P[8] + 1)), an
-// under-estimate of a / m by less than 1.0001, so the result lies in [0, 1.0001 m): ~70 instructions instead of the 206 of fe_mul
-// (the last pass of the Fr NTT reduces every output once).  |a| < 169 m as for fe_reduce (the top limb stays inside int32).
+// The same reduction WITHOUT a Montgomery product (no factor involved): subtract q m with q = floor(top limb / (P[8] + 1)):
+// ~70 instructions instead of the 206 of fe_mul (the last pass of the Fr NTT reduces every output once, then fe_canon).  |a| < 169 m
+// as for fe_reduce (the top limb stays inside int32).  Result normalised, a - q m = q e + (the rest of a below q (P[8] + 1) 2^232)
+// with e = (P[8] + 1) 2^232 - m < 2^232: in [0, 1.0001 m) for a >= 0, but for a NEGATIVE a q over-estimates a / m and the result
+// can be below 0 by up to |q| e < 170 2^232 < 0.0001 m (a = -6 m - 1 gives -1).  So: (-0.0001 m, 1.0001 m), inside fe_canon's range.
 template <class F>
 KZG_HD void fe_reduce_small(Fe<F>& a) {
+    KZG_REQUIRE(fe_bound_reduce(a), KZG_SITE_REDUCE_SMALL, "fe_reduce_small", a);
     fe_norm(a);
     const int32_t D = (int32_t)F::P[NL - 1] + 1;
     const int32_t top = a.l[NL - 1];
@@ -570,6 +701,7 @@ KZG_HD void fe_unpack(Fe<F>& r, const uint32_t w[8]) {
 // a canonical (limbs in [0, 2^29), value < 2^256)
 template <class F>
 KZG_HD void fe_pack(uint32_t w[8], const Fe<F>& a) {
+    KZG_REQUIRE(fe_bound_pack(a), KZG_SITE_PACK, "fe_pack", a);
 #pragma unroll
     for (int k = 0; k < 8; ++k) w[k] = ((uint32_t)a.l[k] >> (3 * k)) | ((uint32_t)a.l[k + 1] << (29 - 3 * k));
 }
@@ -586,6 +718,7 @@ KZG_HD void fe_from_wire(Fe<F>& r, const uint32_t w[8]) {
 // internal (normalised, |a| < 169 m) -> wire words (canonical)
 template <class F>
 KZG_HD void fe_to_wire(uint32_t w[8], const Fe<F>& a) {
+    KZG_REQUIRE(fe_bound_to_wire(a), KZG_SITE_TO_WIRE, "fe_to_wire", a);
     Fe<F> t, k;
 #pragma unroll
     for (int j = 0; j < NL; ++j) k.l[j] = (int32_t)F::K_OUT[j];

@@ -505,3 +505,8 @@ void lag_abort(kzg_ctx* ctx, int slot) {
 }
 
 }  // namespace kzg
+
+#if defined(KZG_DEVICE_BOUND_CHECK)   // the device bound-check variant only (field29.h, `make boundcheck`)
+#include "field29.h"
+KZG_BOUND_CHECK_EXPORTS(lagrange)
+#endif

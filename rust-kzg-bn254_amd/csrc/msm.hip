@@ -916,3 +916,8 @@ int32_t msm_run_batch_tables(kzg_ctx* ctx, const MsmBases& bases, const void* d_
 }
 
 }  // namespace kzg
+
+#if defined(KZG_DEVICE_BOUND_CHECK)   // the device bound-check variant only (field29.h, `make boundcheck`)
+#include "field29.h"
+KZG_BOUND_CHECK_EXPORTS(msm)
+#endif

@@ -551,3 +551,8 @@ int32_t kzg_compute_proof_rccl_device(kzg_ctx* ctx, const kzg_srs* lagrange_shar
 }
 
 }  // extern "C"
+
+#if defined(KZG_DEVICE_BOUND_CHECK)   // the device bound-check variant only (field29.h, `make boundcheck`)
+#include "field29.h"
+KZG_BOUND_CHECK_EXPORTS(multi)
+#endif

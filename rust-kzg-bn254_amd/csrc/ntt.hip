@@ -562,3 +562,8 @@ int32_t ntt_run(kzg_ctx* ctx, void* d_data, size_t n, bool inverse, hipStream_t 
 }
 
 }  // namespace kzg
+
+#if defined(KZG_DEVICE_BOUND_CHECK)   // the device bound-check variant only (field29.h, `make boundcheck`)
+#include "field29.h"
+KZG_BOUND_CHECK_EXPORTS(ntt)
+#endif

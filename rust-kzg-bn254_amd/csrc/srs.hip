@@ -482,3 +482,8 @@ int32_t srs_download(kzg_ctx* ctx, const uint4* d_points, size_t n, uint64_t* ou
 }
 
 }  // namespace kzg
+
+#if defined(KZG_DEVICE_BOUND_CHECK)   // the device bound-check variant only (field29.h, `make boundcheck`)
+#include "field29.h"
+KZG_BOUND_CHECK_EXPORTS(srs)
+#endif

@@ -75,3 +75,8 @@ extern "C" int32_t kzg_ctx_measure_valu_rates(kzg_ctx* ctx, int32_t waves_per_si
     (void)hipFree(d);
     return rc;
 }
+
+#if defined(KZG_DEVICE_BOUND_CHECK)   // the device bound-check variant only (field29.h, `make boundcheck`)
+#include "field29.h"
+KZG_BOUND_CHECK_EXPORTS(ubench)
+#endif

@@ -8,8 +8,28 @@
 #include "curve.h"
 #include "naf.h"
 #include "fe_invert.h"
+#include "../devcheck/dc_prims.h"
 
 using namespace kzg;
+
+template <class F>
+static int predicate(int site, const Fe<F>& a, const Fe<F>& b, const Fe<F>& c, const Fe<F>& d) {
+    switch (site) {
+        case KZG_SITE_MUL_LIMBS: return fe_bound_mul_limbs(a, b);
+        case KZG_SITE_MUL_VALUE: return fe_bound_mul_value(a, b);
+        case KZG_SITE_MULSUB_LIMBS: return fe_bound_mulsub_limbs(a, b, c, d);
+        case KZG_SITE_MULSUB_VALUE: return fe_bound_mulsub_value(a, b, c, d);
+        case KZG_SITE_IS_ZERO_MOD: case KZG_SITE_CANON: return fe_bound_canon(a);
+        case KZG_SITE_REDUCE: case KZG_SITE_REDUCE_SMALL: return fe_bound_reduce(a);
+        case KZG_SITE_TO_WIRE: return fe_bound_to_wire(a);
+        case KZG_SITE_PACK: return fe_bound_pack(a);
+        case KZG_SITE_ADD: return fe_bound_add(a, b, 1);
+        case KZG_SITE_SUB: return fe_bound_add(a, b, -1);
+        case KZG_SITE_DBL: return fe_bound_add(a, a, 1);
+        case KZG_SITE_NORM: return fe_bound_norm(a);
+        default: return -1;
+    }
+}
 
 extern "C" {
 
@@ -138,5 +158,31 @@ void hc_reduce_small(int which, const uint32_t* a, int k, int negate, uint32_t* 
         for (int i = 0; i < k; ++i) { fe_add(v, v, v); fe_norm(v); }
         fe_reduce_small(v); fe_canon(v); fe_to_wire(out, v);
     }
+}
+// One primitive of tests/devcheck/dc_prims.h on n operand sets (36 int32 each -> 18 int32 each), bound-checked: the host third of
+// the device conformance test (tests/test_gpu_device_math.py), and the proof that every generated operand is legal.
+void hc_prim(int which, int op, const int32_t* in, int32_t* out, size_t n) {
+    for (size_t i = 0; i < n; ++i) {
+        if (which == 0) dc_apply<FqParams>(op, in + 36 * i, out + 18 * i);
+        else dc_apply<FrParams>(op, in + 36 * i, out + 18 * i);
+    }
+}
+// The bound predicates of field29.h evaluated without aborting (1 = inside the bound), site = KzgBoundSite: the positive control
+// that every check fires just outside its bound and stays quiet just inside.
+int hc_predicate(int which, int site, const int32_t* in) {
+    if (which == 0) {
+        Fq o[4]; memcpy(o, in, sizeof(o));
+        return predicate(site, o[0], o[1], o[2], o[3]);
+    }
+    Fr o[4]; memcpy(o, in, sizeof(o));
+    return predicate(site, o[0], o[1], o[2], o[3]);
+}
+int hc_sites() { return KZG_SITES; }
+// The point formulas and the NAF recoding of tests/devcheck/dc_prims.h on n rows (the host third of test_gpu_device_math.py)
+void hc_curve(int op, const uint32_t* in, uint32_t* out, size_t n) {
+    for (size_t i = 0; i < n; ++i) dc_curve(op, in + 33 * i, out + 32 * i);
+}
+void hc_naf_rows(const uint32_t* scalars, const int32_t* width, uint32_t* out, size_t n) {
+    for (size_t i = 0; i < n; ++i) { memset(out + 64 * i, 0, 256); dc_naf(scalars + 8 * i, width[i], out + 64 * i); }
 }
 }

@@ -29,7 +29,7 @@ u8p = C.POINTER(C.c_uint8)
 
 @pytest.fixture(scope="module")
 def hc():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("field29.h", "curve.h", "field_constants.h", "naf.h", "fe_invert.h")]
+    deps = [SRC, os.path.join(HERE, "devcheck", "dc_prims.h")] + [os.path.join(CSRC, f) for f in ("field29.h", "curve.h", "field_constants.h", "naf.h", "fe_invert.h")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-DKZG_BOUND_CHECK", "-Wno-unknown-pragmas", "-fPIC",
                                "-shared", "-I" + CSRC, "-o", SO, SRC])

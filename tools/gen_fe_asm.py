@@ -13,6 +13,7 @@ quotient digits m_0..m_8 during the first nine columns (m_j dies after column j 
 column accumulators in FIXED registers v[0:1], v[2:3] (listed as clobbers: the low word is needed on its own, and inline asm has
 no sub-register modifier), the modulus limbs and -m^-1 mod 2^29 in SGPRs, vcc as the unused carry-out.
 """
+import argparse
 import os
 
 NL = 9
@@ -132,7 +133,11 @@ def statement(name, sig, outs, ins, prods_fn, n_acc):
     return txt, n_instr
 
 
-def main():
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rust-kzg-bn254_amd", "csrc", "fe_asm.h"),
+                    help="where to write the header (default: the one the product includes)")
+    out = ap.parse_args(argv).out
     parts = []
     hdr = '''// fe_asm.h -- GENERATED by tools/gen_fe_asm.py, do not edit.  The Montgomery products of field29.h as one gfx950 inline-asm
 // statement each (see the generator's docstring for the why and the register plan).  Device pass only; limb arrays in and out.
@@ -173,7 +178,6 @@ namespace kzg {
     parts.append("constexpr int FE_ASM_INSTRUCTIONS_SQR = %d;\n" % n5)
     parts.append("constexpr int FE_ASM_INSTRUCTIONS_MUL2 = %d, FE_ASM_INSTRUCTIONS_SQR2 = %d, FE_ASM_INSTRUCTIONS_MULSUB = %d, FE_ASM_INSTRUCTIONS_MUL = %d;\n" % (n1, n2, n3, n4))
     parts.append("}  // namespace kzg\n#endif\n")
-    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rust-kzg-bn254_amd", "csrc", "fe_asm.h")
     open(out, "w").write("\n".join(parts))
     print("wrote", out, "instructions:", n1, n2, n3, n4)
 
