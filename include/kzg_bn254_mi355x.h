@@ -261,6 +261,22 @@ int32_t kzg_g1_ifft(kzg_ctx* ctx, const kzg_srs* srs, size_t n, uint64_t* out_xy
 int32_t kzg_srs_cache_lagrange(kzg_ctx* ctx, kzg_srs* srs, size_t n);
 int32_t kzg_srs_lagrange(kzg_ctx* ctx, const kzg_srs* srs, size_t n, kzg_srs** out);
 int32_t kzg_srs_drop_lagrange(kzg_ctx* ctx, kzg_srs* srs);
+/* Proofs for EVERY coset of the domain in one call (Feist-Khovratovich "FK20", eprint 2023/033): the generalisation of
+ * KZG::compute_proof_with_known_z_fr_index (prover/src/kzg.rs:187-234), which opens one point per call, to all of them in O(n log n).
+ * poly: n Fr elements (n x 4 u64), evaluations on the domain {w^i} (eval_form = 1; inverse-NTT'd on the device) or coefficients
+ * (eval_form = 0); w the library's primitive n-th root (kzg_calculate_roots_of_unity).  chunk_len = l, a power of two with
+ * 1 <= l <= n / 2, m = n / l.  Chunk k < m is the coset {w^(k + j m) : j < l}, i.e. evaluation indices k, k + m, k + 2m, ...; its
+ * proof is [q_k(tau)]_1 with q_k = f / (X^l - w^(k l)).  For l = 1 proof k is exactly kzg_compute_proof's proof at z = w^k.
+ * out_xy: m x 8 u64 affine wire points (the identity as zeros), out_is_infinity: m flags.
+ * The 2n points FFT_2m(S^(b)) of FK20 depend on (srs, n, l) only: the first call builds them and keeps them on `srs`
+ * (kzg_srs_cache_multiproof builds them up front; kzg_srs_drop_multiproof and kzg_srs_free release them).
+ * Errors: a null pointer, srs of another context, a Lagrange-basis handle, n = 1, l not a power of two or l > n / 2 ->
+ * KZG_ERR_INVALID_ARG; n = 0 or not a power of two -> KZG_ERR_NOT_POWER_OF_TWO; n > 2^24 -> KZG_ERR_DOMAIN; n > kzg_srs_len(srs) ->
+ * KZG_ERR_SRS_CAPACITY_EXCEEDED; a failed allocation -> KZG_ERR_DEVICE (kzg_ctx_last_error has the text). */
+int32_t kzg_compute_multiproofs(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, size_t n, int32_t eval_form,
+                                size_t chunk_len, uint64_t* out_xy_mont, uint8_t* out_is_infinity);
+int32_t kzg_srs_cache_multiproof(kzg_ctx* ctx, kzg_srs* srs, size_t n, size_t chunk_len);
+int32_t kzg_srs_drop_multiproof(kzg_ctx* ctx, kzg_srs* srs);
 /* KZG::compute_proof / compute_proof_impl (kzg.rs:128-178, :215-234, on-domain branch :237-260).
  * roots = KZG::expanded_roots_of_unity (n_roots entries); n != n_roots -> KZG_ERR_ROOTS_LENGTH.
  * out_y (optional, 4 u64) receives y = p(z) (helpers.rs:475-535). */

@@ -97,6 +97,9 @@ PROTOTYPES = {
     "kzg_srs_cache_lagrange": (i32, [vp, vp, sz]),
     "kzg_srs_lagrange": (i32, [vp, vp, sz, C.POINTER(vp)]),
     "kzg_srs_drop_lagrange": (i32, [vp, vp]),
+    "kzg_compute_multiproofs": (i32, [vp, vp, u64p, sz, i32, sz, u64p, u8p]),
+    "kzg_srs_cache_multiproof": (i32, [vp, vp, sz, sz]),
+    "kzg_srs_drop_multiproof": (i32, [vp, vp]),
     "kzg_blob_to_fr": (i32, [vp, u8p, sz, u64p, sz, C.POINTER(sz)]),
     "kzg_commit_blob": (i32, [vp, vp, u8p, sz, u64p, u8p]),
     "kzg_compute_proof": (i32, [vp, vp, u64p, sz, u64p, sz, u64p, u64p, u8p, u64p]),

@@ -181,6 +181,8 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
     ctx->ntt.release();
     for (auto& w : ctx->ntt_x) w.release();
     for (auto& ps : ctx->poly) ps.release();
+    for (auto& b : ctx->mp) b.release();
+    ctx->mp_ntt.release();
     ctx->rccl_buf.release();
     if (ctx->rccl_pinned) { (void)hipHostFree(ctx->rccl_pinned); ctx->rccl_pinned = nullptr; ctx->rccl_pinned_bytes = 0; }
     if (ctx->vb_pinned) { (void)hipHostFree(ctx->vb_pinned); ctx->vb_pinned = nullptr; ctx->vb_pinned_bytes = 0; }
@@ -450,6 +452,7 @@ void kzg_srs_free(kzg_srs* srs) {
     if (srs->d_small) { (void)hipSetDevice(srs->ctx->device); (void)hipFree(srs->d_small); }
     if (srs->d_bits) { (void)hipSetDevice(srs->ctx->device); (void)hipFree(srs->d_bits); }
     if (srs->d_t3) { (void)hipSetDevice(srs->ctx->device); (void)hipFree(srs->d_t3); }
+    if (!srs->multiproof.empty()) { (void)hipSetDevice(srs->ctx->device); multiproof_drop(srs); }
     delete srs;
 }
 
@@ -559,6 +562,43 @@ int32_t kzg_srs_drop_lagrange(kzg_ctx* ctx, kzg_srs* srs) {
     return KZG_OK;
 }
 
+
+// ---- FK20 multi-proofs (multiproof.hip) ---------------------------------------------------------------------------------------
+static int32_t multiproof_check(kzg_ctx* ctx, const kzg_srs* srs, size_t n, size_t chunk_len) {
+    if (!ctx || !srs || srs->ctx != ctx || srs->lagrange_of != 0) return KZG_ERR_INVALID_ARG;
+    if (n == 0 || (n & (n - 1)) != 0) return KZG_ERR_NOT_POWER_OF_TWO;
+    if (n == 1 || chunk_len == 0 || (chunk_len & (chunk_len - 1)) != 0 || chunk_len > n / 2) return KZG_ERR_INVALID_ARG;
+    if (n > ((size_t)1 << 24)) return KZG_ERR_DOMAIN;
+    if (n > srs->n) return KZG_ERR_SRS_CAPACITY_EXCEEDED;
+    return KZG_OK;
+}
+
+int32_t kzg_compute_multiproofs(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, size_t n, int32_t eval_form,
+                                size_t chunk_len, uint64_t* out_xy_mont, uint8_t* out_is_infinity) {
+    if (!poly_mont || !out_xy_mont || !out_is_infinity) return KZG_ERR_INVALID_ARG;
+    int32_t rc = multiproof_check(ctx, srs, n, chunk_len);
+    if (rc != KZG_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return multiproof_run(ctx, srs, poly_mont, n, eval_form != 0, chunk_len, out_xy_mont, out_is_infinity);
+}
+
+int32_t kzg_srs_cache_multiproof(kzg_ctx* ctx, kzg_srs* srs, size_t n, size_t chunk_len) {
+    int32_t rc = multiproof_check(ctx, srs, n, chunk_len);
+    if (rc != KZG_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint4* table = nullptr;
+    return multiproof_cache(ctx, srs, n, chunk_len, &table);
+}
+
+int32_t kzg_srs_drop_multiproof(kzg_ctx* ctx, kzg_srs* srs) {
+    if (!ctx || !srs || srs->ctx != ctx) return KZG_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    multiproof_drop(srs);
+    return KZG_OK;
+}
 
 // ---- MSM ------------------------------------------------------------------------------------------
 static int32_t stage_scalars(kzg_ctx* ctx, const uint64_t* scalars, size_t n, const void** d_out) {
@@ -1938,7 +1978,7 @@ int32_t srs_upload_plain(kzg_ctx* ctx, const uint64_t* g1_xy_mont, size_t n_poin
 KZG_BOUND_CHECK_EXPORTS(capi)
 // The variant library's totals over every translation unit: counts[site] summed, first[site] = the operand limbs kept by the first
 // translation unit (in the order below) whose counter of that site fired.  Not declared in include/kzg_bn254_mi355x.h.
-#define KZG_BC_UNITS(X) X(msm) X(ntt) X(poly) X(lagrange) X(srs) X(g1fft) X(capi) X(blobstream) X(multi) X(ubench)
+#define KZG_BC_UNITS(X) X(msm) X(ntt) X(poly) X(lagrange) X(srs) X(g1fft) X(capi) X(blobstream) X(multi) X(ubench) X(multiproof)
 #define KZG_BC_DECLARE(name) extern "C" int kzg_bc_read_##name(unsigned long long*, int32_t*); extern "C" int kzg_bc_reset_##name();
 KZG_BC_UNITS(KZG_BC_DECLARE)
 extern "C" int kzg_bc_sites() { return kzg::KZG_SITES; }

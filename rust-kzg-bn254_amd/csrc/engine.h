@@ -123,6 +123,8 @@ struct kzg_ctx {
     hipEvent_t last_sorted = nullptr;          // ev_sorted of the most recently enqueued MSM launch of this context ...
     hipStream_t last_sorted_stream = nullptr;  // ... and the stream it went to (msm.hip msm_enqueue)
     kzg::NttWorkspace& slot_ntt(int slot) { return slot ? ntt_x[slot - 1] : ntt; }
+    kzg::DeviceBuffer mp[6];                   // scratch of kzg_compute_multiproofs / kzg_srs_cache_multiproof (multiproof.hip), its own: slot 0's may be in flight
+    kzg::NttWorkspace mp_ntt;
 };
 
 struct kzg_srs {
@@ -151,6 +153,9 @@ struct kzg_srs {
     // the eval-form commitments of exactly m evaluations instead of IFFT + MSM over the monomial basis; owned by this SRS
     std::map<size_t, kzg_srs*> lagrange;
     size_t lagrange_of = 0;      // this handle IS a Lagrange basis of that many points (0: monomial SRS)
+    // FK20 multi-proofs (multiproof.hip): (n, chunk length l) -> FFT_2m(S^(b)) for b < l, m = n / l, as l x 2m affine points (device format,
+    // 2n points), built by kzg_srs_cache_multiproof or on first use and published under lazy_mu like `lagrange`; owned by this SRS
+    std::map<std::pair<size_t, size_t>, uint4*> multiproof;
 };
 
 namespace kzg {
@@ -248,6 +253,14 @@ int32_t srs_decompress(kzg_ctx* ctx, const uint8_t* bytes, size_t n, uint4* d_po
 // KZG::g1_ifft: Lagrange-basis SRS of size n (n a power of two <= srs->n), affine wire points to the host / left on the device
 int32_t g1_ifft_run(kzg_ctx* ctx, const kzg_srs* srs, size_t n, uint64_t* out_xy);
 int32_t g1_ifft_device(kzg_ctx* ctx, const kzg_srs* srs, size_t n, uint4* d_out, bool wire);
+// the generic G1 transform of XYZZ planes (g1fft.hip): forward or inverse, optional 1/n, input read with its own stride; and the
+// batched affine conversion of n planes.  Both enqueued on st.
+int32_t g1_fft_planes(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t n, int32_t* out, int32_t* tmp, bool inverse, bool scaled);
+int32_t g1fft_planes_to_affine(kzg_ctx* ctx, hipStream_t st, const int32_t* planes, size_t n, uint4* d_out, bool wire, int32_t* scratch);
+// FK20 multi-proofs (multiproof.hip): the cached FFT_2m(S^(b)) of (srs, n, l), built if absent; the proofs of every coset of l points
+int32_t multiproof_cache(kzg_ctx* ctx, kzg_srs* srs, size_t n, size_t l, const uint4** out);
+int32_t multiproof_run(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, size_t n, bool eval_form, size_t l, uint64_t* out_xy, uint8_t* out_inf);
+void multiproof_drop(kzg_srs* srs);
 
 int32_t set_error(kzg_ctx* ctx, hipError_t e, const char* where);
 // the context's high-priority auxiliary stream (lagrange.hip)

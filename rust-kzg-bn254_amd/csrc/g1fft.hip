@@ -20,6 +20,7 @@
 #include "curve_quad.h"
 #include "fe_invert.h"
 #include "naf.h"
+#include "glv.h"
 #include "host_curve.h"
 
 #include <algorithm>
@@ -56,126 +57,6 @@ __device__ __forceinline__ void fe_inverse_fermat(Fe<F>& out, const Fe<F>& a) {
     }
     out = acc;
 #endif
-}
-
-// ---- GLV: k P = k1 P + k2 phi(P), phi(x, y) = (beta x, y) = [lambda] P on BN254 G1, |k1|, |k2| < 2^127 ---------------------------
-// beta, lambda: the cube roots of unity of Fq / Fr with phi(G) = [lambda] G (checked with big integers: tools note in DESIGN.md 9);
-// lattice basis of {(x, y): x + y lambda = 0 mod r} from the extended Euclid on (r, lambda):
-//   (a1, b1) = (9931322734385697763, -147946756881789319000765030803803410728), (a2, b2) = (147946756881789319010696353538189108491, a1),
-// a1 b2 - a2 b1 = r.  c1 = floor(k g1 / 2^256), c2 = floor(k g2 / 2^256) with g1 = round(2^256 b2 / r), g2 = round(2^256 (-b1) / r);
-// k1 = k - c1 a1 - c2 a2, k2 = c1 |b1| - c2 b2  (2 10^5 random k and the edge values: both below 2^127 in magnitude).
-// Little-endian 32-bit words.
-__device__ const uint32_t GLV_G1[3] = {0xc7e0b3d7u, 0xd91d232eu, 0x00000002u};
-__device__ const uint32_t GLV_G2[5] = {0x391eb18eu, 0x7a7bd9d4u, 0xa773d2cfu, 0x4ccef014u, 0x00000002u};
-__device__ const uint32_t GLV_A1[2] = {0x94d213e3u, 0x89d32568u};                                   // = b2
-__device__ const uint32_t GLV_B1M[4] = {0x7d4f1128u, 0x8211bbebu, 0xeeb859fcu, 0x6f4d8248u};        // -b1
-__device__ const uint32_t GLV_A2[4] = {0x1221250bu, 0x0be4e154u, 0xeeb859fdu, 0x6f4d8248u};
-__device__ const uint32_t GLV_BETA[8] = {0x77fffffeu, 0x57634731u, 0xacdb5c4fu, 0xd4f263f1u, 0xa0d48bacu, 0x59e26bceu, 0u, 0u};   // plain integer
-
-// out[0 .. na+nb) = a * b (schoolbook, 32-bit words)
-template <int NA, int NB>
-__device__ __forceinline__ void glv_mul_words(uint32_t* out, const uint32_t* a, const uint32_t* b) {
-#pragma unroll
-    for (int i = 0; i < NA + NB; ++i) out[i] = 0;
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        uint64_t carry = 0;
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const uint64_t t = (uint64_t)a[i] * b[j] + out[i + j] + carry;
-            out[i + j] = (uint32_t)t;
-            carry = t >> 32;
-        }
-        out[i + NB] = (uint32_t)carry;
-    }
-}
-// 256-bit two's complement helpers
-__device__ __forceinline__ void glv_sub8(uint32_t* r, const uint32_t* a, const uint32_t* b, int nb) {   // r = a - b (b has nb <= 8 words)
-    uint64_t borrow = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const uint64_t bi = i < nb ? b[i] : 0u;
-        const uint64_t t = (uint64_t)a[i] - bi - borrow;
-        r[i] = (uint32_t)t;
-        borrow = (t >> 32) & 1u;
-    }
-}
-__device__ __forceinline__ uint32_t glv_abs8(uint32_t* v) {                                             // v = |v|, returns the sign
-    const uint32_t neg = v[7] >> 31;
-    if (neg) {
-        uint64_t carry = 1;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const uint64_t t = (uint64_t)(~v[i]) + carry; v[i] = (uint32_t)t; carry = t >> 32; }
-    }
-    return neg;
-}
-// k (canonical, < r) -> kk[0..3] = |k1|, kk[4..7] = |k2|, their signs in bit 31 of kk[3] / kk[7]
-__device__ __forceinline__ void glv_decompose(uint32_t kk[8], const uint32_t k[8]) {
-    uint32_t p1[11], p2[13];
-    glv_mul_words<8, 3>(p1, k, GLV_G1);
-    glv_mul_words<8, 5>(p2, k, GLV_G2);
-    const uint32_t c1[2] = {p1[8], p1[9]};                          // < 2^64  (p1[10] = 0: k g1 < 2^320)
-    const uint32_t c2[4] = {p2[8], p2[9], p2[10], p2[11]};          // < 2^128 (p2[12] = 0)
-    uint32_t t1[4], t2[8], t3[6], t4[6];
-    glv_mul_words<2, 2>(t1, c1, GLV_A1);
-    glv_mul_words<4, 4>(t2, c2, GLV_A2);
-    glv_mul_words<2, 4>(t3, c1, GLV_B1M);
-    glv_mul_words<4, 2>(t4, c2, GLV_A1);
-    uint32_t k1[8], k2[8], z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    glv_sub8(k1, k, t1, 4);
-    glv_sub8(k1, k1, t2, 8);
-    uint32_t t3w[8] = {t3[0], t3[1], t3[2], t3[3], t3[4], t3[5], 0, 0};
-    (void)z;
-    glv_sub8(k2, t3w, t4, 6);
-    const uint32_t s1 = glv_abs8(k1), s2 = glv_abs8(k2);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { kk[i] = k1[i]; kk[4 + i] = k2[i]; }
-    kk[3] |= s1 << 31;
-    kk[7] |= s2 << 31;
-}
-
-// r = [k] * p with k given as its GLV halves (glv_decompose): 127 doublings, each followed by ONE addition of +-P, +-phi(P) or their
-// sum selected per lane (a wave executes the addition whenever any of its lanes has a bit set, i.e. always: the plain
-// double-and-add paid 254 doublings AND 254 additions per wave)
-__device__ __forceinline__ void xyzz_scalar_mul(Xyzz& r, const Xyzz& p, const uint32_t kk[8]) {
-    if (p.inf) { xyzz_set_inf(r); return; }
-    const uint32_t s1 = kk[3] >> 31, s2 = kk[7] >> 31;
-    Fq beta, kin, bx, y1, y2;
-    {
-        uint32_t bw[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) bw[j] = GLV_BETA[j];
-        fe_unpack(beta, bw);
-#pragma unroll
-        for (int j = 0; j < NL; ++j) kin.l[j] = (int32_t)FqParams::K_PLAIN_IN[j];
-        fe_mul(beta, beta, kin);                                   // plain integer -> internal form
-    }
-    fe_mul(bx, p.x, beta);
-    fe_cneg(y1, p.y, s1);
-    fe_cneg(y2, p.y, s2);
-    Xyzz P1 = p, P2 = p, S;
-    P1.y = y1;
-    P2.x = bx; P2.y = y2;
-    xyzz_add<true>(S, P1, P2);
-    Xyzz acc;
-    xyzz_set_inf(acc);
-#pragma unroll 1
-    for (int i = 126; i >= 0; --i) {
-        Xyzz t;
-        xyzz_dbl_impl(t, acc);
-        acc = t;
-        const uint32_t b1 = (kk[i >> 5] >> (i & 31)) & 1u, b2 = (kk[4 + (i >> 5)] >> (i & 31)) & 1u;
-        Xyzz op;
-        const bool both = b1 & b2;
-        fe_select(op.x, both, S.x, b1 ? P1.x : P2.x);
-        fe_select(op.y, both, S.y, b1 ? P1.y : P2.y);
-        fe_select(op.zz, both, S.zz, p.zz);
-        fe_select(op.zzz, both, S.zzz, p.zzz);
-        op.inf = both ? S.inf : !(b1 | b2);
-        xyzz_add<true>(t, acc, op);
-        acc = t;
-    }
-    r = acc;
 }
 
 __device__ __forceinline__ void tw_load(Fr& w, const NttTables& tb, uint32_t E) {
@@ -864,16 +745,17 @@ k_g1fft_to_affine(const int32_t* __restrict__ planes, uint32_t n, uint4* __restr
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-struct ScalKey { int dev, log_n, scaled; bool operator<(const ScalKey& o) const { return dev != o.dev ? dev < o.dev : (log_n != o.log_n ? log_n < o.log_n : scaled < o.scaled); } };   // scaled: bit 0 = times 1/n, bit 1 = canonical (not GLV-split)
+struct ScalKey { int dev, log_n, scaled; bool operator<(const ScalKey& o) const { return dev != o.dev ? dev < o.dev : (log_n != o.log_n ? log_n < o.log_n : scaled < o.scaled); } };   // scaled: bit 0 = times 1/n, bits 1-2 = canon, bit 3 = forward (w^+e)
 static std::map<ScalKey, uint4*> g_scal;
 static std::mutex g_scal_mu;
-static int32_t get_scalars(kzg_ctx* ctx, int log_n, bool scaled, const uint4** out, int canon = 0) {     // canon: 0 GLV halves, 1 canonical integers, 2 wire words
+// forward: the scalars of w^+e (the forward transform of g1_fft_planes) instead of w^-e; the kernel reads whichever table it is given
+static int32_t get_scalars(kzg_ctx* ctx, int log_n, bool scaled, const uint4** out, int canon = 0, bool forward = false) {     // canon: 0 GLV halves, 1 canonical integers, 2 wire words
     std::lock_guard<std::mutex> lk(g_scal_mu);
-    ScalKey key{ctx->device, log_n, (scaled ? 1 : 0) | (canon << 1)};
+    ScalKey key{ctx->device, log_n, (scaled ? 1 : 0) | (canon << 1) | (forward ? 8 : 0)};
     auto it = g_scal.find(key);
     if (it != g_scal.end()) { *out = it->second; return KZG_OK; }
     NttTables tb{};
-    if (log_n > 0) { int32_t rc = ntt_get_tables(ctx, log_n, true, &tb); if (rc != KZG_OK) return rc; }
+    if (log_n > 0) { int32_t rc = ntt_get_tables(ctx, log_n, !forward, &tb); if (rc != KZG_OK) return rc; }
     const size_t n = (size_t)1 << log_n;
     uint4* p = nullptr;
     KZG_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&p), n * 32));
@@ -922,6 +804,33 @@ k_g1fft_planes_to_wire(const int32_t* __restrict__ planes, uint32_t n, uint32_t*
     xyzz_to_wire(w, v);
 #pragma unroll
     for (int j = 0; j < 32; j += 4) *reinterpret_cast<uint4*>(out_wire + (size_t)i * 32 + j) = make_uint4(w[j], w[j + 1], w[j + 2], w[j + 3]);
+}
+
+// Stage plan.  A stage is one scalar multiplication deep whatever it computes, so the plan minimises (number of stages) x (time of a
+// stage).  Measured stage times on MI355X (tools/time_g1ifft.py, round 3) while the stage fits ONE wave per SIMD (65536 lanes):
+// 1.25 ms with one lane per point, 0.83 ms on lane pairs; beyond that a stage is throughput bound and scales with its lanes (a lone
+// wave already issues most of what its SIMD can: two pair waves per SIMD took 1.44 ms).  Candidates:
+//   direct stages of radix 2^K (one lane or pair per (output, term): n 2^K lanes or pairs), K <= 5
+//   radix-2 butterflies (n / 2 lanes or pairs, work bound: one multiplication per two outputs)
+// *kmax = 0: radix-2 butterflies; else the largest radix bits of the direct stages.  (Shared by g1_ifft and g1_fft_planes.)
+static void g1fft_choose_plan(size_t n, int log_n, int* kmax_out, bool* pairs_out) {
+    int kmax = 0;
+    bool pairs = false;
+    const double t_lane = 1.25, t_pair = 0.83, cap = 65536.0;
+    double best = 1e300;
+    for (int mode = 0; mode < 2; ++mode) {                        // 0: one lane per point, 1: lane pairs
+        const double t1 = mode ? t_pair : t_lane, width = mode ? 2.0 : 1.0;
+        for (int K = 2; K <= 5 && K <= std::max(log_n, 2); ++K) {  // direct stages
+            const double lanes = (double)n * (double)(1u << K) * width;
+            const double cost = (double)((log_n + K - 1) / K) * t1 * std::max(1.0, lanes / cap);
+            if (cost < best) { best = cost; kmax = K; pairs = mode != 0; }
+        }
+        const double lanes2 = (double)n / 2.0 * width;             // radix-2 butterflies (+ the scaling multiplication of the last stage)
+        const double cost2 = (double)(log_n + 1) * t1 * std::max(1.0, lanes2 / cap);
+        if (cost2 < best) { best = cost2; kmax = 0; pairs = mode != 0; }
+    }
+    *kmax_out = kmax;
+    *pairs_out = pairs;
 }
 
 // The stages of the transform: *result_out = XYZZ planes (stride n) of the Lagrange basis of the first n SRS points, natural order
@@ -1038,29 +947,9 @@ static int32_t g1_ifft_stages(kzg_ctx* ctx, const kzg_srs* srs, size_t n, const 
         *result_out = src;
         return KZG_OK;
     }
-    // Stage plan.  A stage is one scalar multiplication deep whatever it computes, so the plan minimises (number of stages) x (time of a
-    // stage).  Measured stage times on MI355X (tools/time_g1ifft.py, round 3) while the stage fits ONE wave per SIMD (65536 lanes):
-    // 1.25 ms with one lane per point, 0.83 ms on lane pairs; beyond that a stage is throughput bound and scales with its lanes (a lone
-    // wave already issues most of what its SIMD can: two pair waves per SIMD took 1.44 ms).  Candidates:
-    //   direct stages of radix 2^K (one lane or pair per (output, term): n 2^K lanes or pairs), K <= 5
-    //   radix-2 butterflies (n / 2 lanes or pairs, work bound: one multiplication per two outputs)
     int kmax = 0;
     bool pairs = false;
-    {
-        const double t_lane = 1.25, t_pair = 0.83, cap = 65536.0;
-        double best = 1e300;
-        for (int mode = 0; mode < 2; ++mode) {                        // 0: one lane per point, 1: lane pairs
-            const double t1 = mode ? t_pair : t_lane, width = mode ? 2.0 : 1.0;
-            for (int K = 2; K <= 5 && K <= std::max(log_n, 2); ++K) {  // direct stages
-                const double lanes = (double)n * (double)(1u << K) * width;
-                const double cost = (double)((log_n + K - 1) / K) * t1 * std::max(1.0, lanes / cap);
-                if (cost < best) { best = cost; kmax = K; pairs = mode != 0; }
-            }
-            const double lanes2 = (double)n / 2.0 * width;             // radix-2 butterflies (+ the scaling multiplication of the last stage)
-            const double cost2 = (double)(log_n + 1) * t1 * std::max(1.0, lanes2 / cap);
-            if (cost2 < best) { best = cost2; kmax = 0; pairs = mode != 0; }
-        }
-    }
+    g1fft_choose_plan(n, log_n, &kmax, &pairs);
     if (log_n == 0) {
         hipLaunchKernelGGL(k_g1fft_load, dim3(gn), dim3(256), 0, st, srs->d_points, (uint32_t)n, bufA, 0);
     } else if (kmax >= 2) {
@@ -1128,6 +1017,90 @@ int32_t g1_ifft_device(kzg_ctx* ctx, const kzg_srs* srs, size_t n, uint4* d_out,
     const size_t lanes = std::max<size_t>(1, (n + AFF_PER - 1) / AFF_PER);
     const unsigned blocks = (unsigned)std::min<size_t>((lanes + 255) / 256, 4096);
     hipLaunchKernelGGL(k_g1fft_to_affine, dim3(blocks), dim3(256), 0, ctx->stream, result, (uint32_t)n, d_out, wire ? 1 : 0, ctx->poly[0].a.as<int32_t>());
+    KZG_HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+
+// ---- the generic transform (planes in, planes out): the FK20 multi-proofs of multiproof.hip --------------------------------------
+// dst[i] = src[j], j = i or bit-reversed i, 36 limb planes each (src: element j of limb plane k at src[k * src_stride + j])
+__global__ void __launch_bounds__(256)
+k_g1fft_gather_planes(const int32_t* __restrict__ src, size_t src_stride, uint32_t n, int32_t* __restrict__ dst, int bitrev_log) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t j = bitrev_log > 0 ? (__brev(i) >> (32 - bitrev_log)) : i;
+#pragma unroll
+    for (int k = 0; k < 4 * NL; ++k) dst[(size_t)k * n + i] = src[(size_t)k * src_stride + j];
+}
+
+// out = sum_j w^(+-ij) in[j] (times 1/n if scaled), natural order, n a power of two.  in: n points of XYZZ planes with stride in_stride
+// (in_stride > n: a slice of a longer plane set, read in place by the radix-2 path's bit reversal, copied once for the direct stages);
+// out, tmp: n points each, stride n, neither aliasing in.  The stage plan, the kernels and the scalar tables are g1_ifft's
+// (g1fft_choose_plan, the direct stages on lanes or pairs, radix-2 butterflies); forward transforms use the tables of w^+e.
+// Enqueued on st; no synchronisation.
+int32_t g1_fft_planes(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t n, int32_t* out, int32_t* tmp, bool inverse, bool scaled) {
+    int log_n = 0;
+    while (((size_t)1 << log_n) < n) ++log_n;
+    const unsigned gn = (unsigned)((n + 255) / 256);
+    if (log_n == 0) {                                                        // one point: the transform (and 1/1) is the identity
+        hipLaunchKernelGGL(k_g1fft_gather_planes, dim3(1), dim3(256), 0, st, in, in_stride, 1u, out, 0);
+        KZG_HIP_TRY(ctx, hipGetLastError());
+        return KZG_OK;
+    }
+    const uint4 *scal = nullptr, *scal_last = nullptr;
+    int32_t rc = get_scalars(ctx, log_n, false, &scal, 0, !inverse);
+    if (rc == KZG_OK) rc = scaled ? get_scalars(ctx, log_n, true, &scal_last, 0, !inverse) : KZG_OK;
+    if (rc != KZG_OK) return rc;
+    if (!scaled) scal_last = scal;
+    const int last_flag = scaled ? 1 : 0;                                    // the last stage multiplies every term (1/n folded in)
+    int kmax = 0;
+    bool pairs = false;
+    g1fft_choose_plan(n, log_n, &kmax, &pairs);
+    if (kmax >= 2) {
+        const int stages = (log_n + kmax - 1) / kmax;
+        const int32_t* src = in;
+        if (in_stride != n) {                                                // the direct stages read planes of stride n
+            int32_t* c = (stages & 1) ? tmp : out;
+            hipLaunchKernelGGL(k_g1fft_gather_planes, dim3(gn), dim3(256), 0, st, in, in_stride, (uint32_t)n, c, 0);
+            src = c;
+        }
+        int done = 0;
+        for (int i = 0; i < stages; ++i) {
+            const int K = (log_n - done + (stages - i) - 1) / (stages - i);   // balanced split of the remaining bits (as g1_ifft)
+            done += K;
+            const int log_s = log_n - done;
+            const bool last = i == stages - 1;
+            int32_t* dst = ((stages - 1 - i) & 1) ? tmp : out;              // ping-pong that ends in out
+            const size_t lanes = n << K;
+            if (pairs)
+                hipLaunchKernelGGL(k_g1fft_direct_pairs, dim3((unsigned)((2 * lanes + 255) / 256)), dim3(256), 0, st, src, dst, (uint32_t)n, log_n, K, log_s,
+                                   last ? scal_last : scal, last ? last_flag : 0);
+            else
+                hipLaunchKernelGGL(k_g1fft_direct, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, src, dst, (uint32_t)n, log_n, K, log_s,
+                                   last ? scal_last : scal, last ? last_flag : 0);
+            src = dst;
+        }
+    } else {
+        hipLaunchKernelGGL(k_g1fft_gather_planes, dim3(gn), dim3(256), 0, st, in, in_stride, (uint32_t)n, out, log_n);
+        for (int s = 1; s <= log_n; ++s) {
+            const bool last = s == log_n;
+            if (pairs)
+                hipLaunchKernelGGL(k_g1fft_stage_pairs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out, (uint32_t)n, log_n, s,
+                                   last ? scal_last : scal, last ? last_flag : 0);
+            else
+                hipLaunchKernelGGL(k_g1fft_stage, dim3((unsigned)((n / 2 + 255) / 256)), dim3(256), 0, st, out, (uint32_t)n, log_n, s,
+                                   last ? scal_last : scal, last ? last_flag : 0);
+        }
+    }
+    KZG_HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+
+// n XYZZ planes (stride n) -> n affine points (wire, or the device format of curve.h; identity = zeros), the batched conversion of
+// g1_ifft_device; scratch: n x NL words.  Enqueued on st.
+int32_t g1fft_planes_to_affine(kzg_ctx* ctx, hipStream_t st, const int32_t* planes, size_t n, uint4* d_out, bool wire, int32_t* scratch) {
+    const size_t lanes = std::max<size_t>(1, (n + AFF_PER - 1) / AFF_PER);
+    const unsigned blocks = (unsigned)std::min<size_t>((lanes + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_g1fft_to_affine, dim3(blocks), dim3(256), 0, st, planes, (uint32_t)n, d_out, wire ? 1 : 0, scratch);
     KZG_HIP_TRY(ctx, hipGetLastError());
     return KZG_OK;
 }

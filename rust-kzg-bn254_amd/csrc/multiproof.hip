@@ -1,0 +1,259 @@
+// multiproof.hip — the KZG proofs of EVERY coset of a domain in one call: Feist-Khovratovich, "Fast amortized KZG proofs" (eprint
+// 2023/033, "FK20").  The reference opens one point per call (`compute_proof_with_known_z_fr_index`, prover/src/kzg.rs:187-234); n
+// such calls are n full proofs, O(n^2).  FK20 computes all n / l coset proofs in O(n log n).
+//
+// f = f_0 .. f_{n-1} (n a power of two), w the library's primitive n-th root, chunk length l a power of two, 1 <= l <= n / 2, m = n / l.
+// Chunk k < m is the coset {w^(k + j m) : j < l} (evaluation indices k, k + m, k + 2m, ...), its vanishing polynomial X^l - w^(k l);
+// pi_k = [q_k(tau)]_1, q_k = f / (X^l - w^(k l)).  For l = 1, pi_k is the proof at z = w^k.
+//   1. F^(b) = (f_b, f_{l+b}, ..., f_{(m-1)l+b}, 0 x m), b < l                       (length 2m; l Fr NTTs of size 2m)
+//   2. S^(b)_t = [tau^((m-2-t) l + b)]_1, t <= m - 2, then the identity up to 2m      (gathered from the SRS)
+//   3. H_t = sum_b FFT_2m(F^(b))_t FFT_2m(S^(b))_t, t < 2m                             (k_fk20_lincomb: 2n scalar multiplications)
+//   4. h_u = IFFT_2m(H)[u + m - 1], u < m  (h_{m-1} = 0)                               (one inverse G1 FFT; the slice is read in place)
+//   5. pi = DFT_m(h) with the m-th root w^l, natural order                            (one forward G1 FFT)
+// FFT_2m(S^(b)) depends only on (SRS, n, l): 2n affine points (128 n bytes), cached on the SRS handle (kzg_srs::multiproof).
+//
+// Design choices (the G1 FFT is g1fft.hip's generic g1_fft_planes: its stage plan, lanes or pairs by the g1_ifft cost model, radix
+// 2^K direct stages while n 2^K lanes fit one wave per SIMD, radix-2 butterflies beyond):
+//   * the inverse 2m-point and the forward m-point transform are NOT fused: the slice [m - 1, 2m - 1) between them is read in place
+//     (pointer offset, stride 2m) by the second transform's first kernel.  Fusing them (a 4-step split of both) was not tried.
+//   * the linear combination is one lane per (frequency, term) with GLV scalars, G = min(l, 64) lanes of one wave per frequency folded by
+//     a shuffle tree, and for l > 64 up to 32 waves per frequency whose partial sums a second kernel adds; a lane adds l / (64 W) terms
+//     one after the other.  l = 1 is a kernel of its own: one scalar multiplication per frequency, no tree.  Lanes rather than pairs:
+//     the stage is one multiplication deep like an FFT stage, and the pair form's gain there (0.83 against 1.25 ms) was not measured here.
+//   * the Fr side: l NTTs of 2m points, one ntt_run each (a single batched launch was not written: at l = 16 they are 16 short launches).
+//   * the cache build transforms the l sequences one after the other (gather, forward FFT, affine conversion each).
+// Measured figures: README.md ("Multi-proofs") and profiles/multiproof.md.
+#include "engine.h"
+#include "glv.h"
+
+#include <algorithm>
+#include <map>
+#include <mutex>
+#include <utility>
+
+namespace kzg {
+
+// planes (stride 2m) of S^(b): t <= m - 2 -> SRS point (m - 2 - t) l + b (< n - l), else the identity
+__global__ void __launch_bounds__(256)
+k_fk20_gather_srs(const uint4* __restrict__ srs_points, uint32_t m, uint32_t l, uint32_t b, int32_t* __restrict__ planes) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, M = 2 * m;
+    if (t >= M) return;
+    Xyzz v;
+    Affine p;
+    if (t + 2 <= m && affine_load(p, srs_points + 4 * ((size_t)(m - 2 - t) * l + b))) xyzz_from_affine(v, p, 0);
+    else xyzz_set_inf(v);
+    xyzz_store(planes, M, t, v);
+}
+
+// coefficient rows: F[b][j] = f[j l + b] for j < m, 0 for m <= j < 2m (wire Fr, 32 B each)
+__global__ void __launch_bounds__(256)
+k_fk20_scatter_coeffs(const uint4* __restrict__ f, uint32_t m, uint32_t l, uint4* __restrict__ F) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, M = 2 * m;
+    if (i >= M * l) return;
+    const uint32_t b = i / M, j = i - b * M;
+    uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+    if (j < m) { const size_t s = (size_t)j * l + b; lo = f[2 * s]; hi = f[2 * s + 1]; }
+    F[2 * (size_t)i] = lo;
+    F[2 * (size_t)i + 1] = hi;
+}
+
+// [s] P with s a wire Fr scalar and P a device-format affine point (identity: zeros)
+__device__ __forceinline__ void fk20_term(Xyzz& r, const uint4* __restrict__ scalar, const uint4* __restrict__ point) {
+    Affine p;
+    if (!affine_load(p, point)) { xyzz_set_inf(r); return; }
+    const uint4 lo = scalar[0], hi = scalar[1];
+    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    uint32_t kc[8], kk[8];
+    fe_wire_to_canonical_words<FrParams>(kc, w);
+    glv_decompose(kk, kc);
+    Xyzz base;
+    xyzz_from_affine(base, p, 0);
+    xyzz_scalar_mul(r, base, kk);
+}
+
+// l = 1: H_t = Fhat_t Shat_t, one lane per frequency
+__global__ void __launch_bounds__(256)
+k_fk20_pointwise(const uint4* __restrict__ fhat, const uint4* __restrict__ shat, uint32_t M, int32_t* __restrict__ out) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= M) return;
+    Xyzz r;
+    fk20_term(r, fhat + 2 * (size_t)t, shat + 4 * (size_t)t);
+    xyzz_store(out, M, t, r);
+}
+
+// l > 1: slot (t, w) = sum of the terms b = (w tpl + i) G + g (g < G lanes, i < tpl) of frequency t; G = 2^log_g <= 64 consecutive lanes of
+// one wave per slot, folded by a shuffle tree; slot (t, w) at index t W + w of `out` (stride M W): H itself when W = 1
+__global__ void __launch_bounds__(256)
+k_fk20_lincomb(const uint4* __restrict__ fhat, const uint4* __restrict__ shat, uint32_t M, int log_g, uint32_t W, uint32_t tpl, int32_t* __restrict__ out) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
+    const uint32_t G = 1u << log_g, g = t & (G - 1), slot = t >> log_g;
+    const uint32_t o = slot / W, w = slot - o * W;
+    const bool active = o < M;                                    // no early return: every lane takes part in the tree
+    Xyzz acc;
+    xyzz_set_inf(acc);
+    if (active) {
+#pragma unroll 1
+        for (uint32_t i = 0; i < tpl; ++i) {
+            const size_t e = (size_t)((w * tpl + i) * G + g) * M + o;   // term b, frequency o of the l x M arrays
+            Xyzz term, s;
+            fk20_term(term, fhat + 2 * e, shat + 4 * e);
+            xyzz_add<true>(s, acc, term);
+            acc = s;
+        }
+    }
+#pragma unroll 1
+    for (int d = 1; d < (int)G; d <<= 1) {
+        Xyzz other, r;
+        const Fq* sp[4] = {&acc.x, &acc.y, &acc.zz, &acc.zzz};
+        Fq* tp[4] = {&other.x, &other.y, &other.zz, &other.zzz};
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int q = 0; q < NL; ++q) tp[c]->l[q] = __shfl_down(sp[c]->l[q], d, 64);
+        other.inf = __shfl_down((int)acc.inf, d, 64) != 0;
+        if ((lane & (2 * d - 1)) == 0) {
+            xyzz_add<true>(r, acc, other);
+            acc = r;
+        }
+    }
+    if (active && g == 0) xyzz_store(out, (size_t)M * W, slot, acc);
+}
+
+// H_t = sum of the W partial sums of frequency t (one lane per frequency)
+__global__ void __launch_bounds__(256)
+k_fk20_sum_partials(const int32_t* __restrict__ partial, uint32_t M, uint32_t W, int32_t* __restrict__ out) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= M) return;
+    Xyzz acc;
+    xyzz_load(acc, partial, (size_t)M * W, (size_t)t * W);
+#pragma unroll 1
+    for (uint32_t w = 1; w < W; ++w) {
+        Xyzz v, s;
+        xyzz_load(v, partial, (size_t)M * W, (size_t)t * W + w);
+        xyzz_add<true>(s, acc, v);
+        acc = s;
+    }
+    xyzz_store(out, M, t, acc);
+}
+
+// out_inf[i] = 1 where the point is the identity
+__global__ void __launch_bounds__(256)
+k_fk20_inf_flags(const int32_t* __restrict__ planes, uint32_t n, uint8_t* __restrict__ out_inf) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Xyzz v;
+    xyzz_load(v, planes, n, i);
+    out_inf[i] = v.inf ? 1 : 0;
+}
+
+static inline unsigned grid_of(size_t threads) { return (unsigned)((threads + 255) / 256); }
+
+// ---- the cache: FFT_2m(S^(b)) for b < l as l x 2m device-format affine points -------------------------------------------------
+static uint4* cached(const kzg_srs* srs, size_t n, size_t l) {
+    std::lock_guard<std::mutex> lk(srs->lazy_mu);
+    auto it = srs->multiproof.find(std::make_pair(n, l));
+    return it == srs->multiproof.end() ? nullptr : it->second;
+}
+
+// called under ctx->mu (one builder per context; only the SRS's own context builds); published complete under lazy_mu
+int32_t multiproof_cache(kzg_ctx* ctx, kzg_srs* srs, size_t n, size_t l, const uint4** out) {
+    if (uint4* c = cached(srs, n, l)) { *out = c; return KZG_OK; }
+    const size_t m = n / l, M = 2 * m;
+    hipStream_t st = ctx->stream;
+    KZG_HIP_TRY(ctx, ctx->mp[2].reserve(M * 36 * 4));
+    KZG_HIP_TRY(ctx, ctx->mp[3].reserve(M * 36 * 4));
+    KZG_HIP_TRY(ctx, ctx->mp[4].reserve(M * 36 * 4));
+    KZG_HIP_TRY(ctx, ctx->mp[5].reserve(M * NL * 4));
+    uint4* table = nullptr;
+    KZG_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&table), 2 * n * 64));
+    int32_t rc = KZG_OK;
+    for (size_t b = 0; b < l && rc == KZG_OK; ++b) {
+        hipLaunchKernelGGL(k_fk20_gather_srs, dim3(grid_of(M)), dim3(256), 0, st, srs->d_points, (uint32_t)m, (uint32_t)l, (uint32_t)b, ctx->mp[3].as<int32_t>());
+        rc = g1_fft_planes(ctx, st, ctx->mp[3].as<int32_t>(), M, M, ctx->mp[2].as<int32_t>(), ctx->mp[4].as<int32_t>(), false, false);
+        if (rc == KZG_OK) rc = g1fft_planes_to_affine(ctx, st, ctx->mp[2].as<int32_t>(), M, table + 4 * b * M, false, ctx->mp[5].as<int32_t>());
+    }
+    if (rc == KZG_OK) {
+        hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = set_error(ctx, e, "building the multi-proof cache");
+    }
+    if (rc != KZG_OK) { (void)hipFree(table); return rc; }
+    std::lock_guard<std::mutex> lk(srs->lazy_mu);
+    srs->multiproof[std::make_pair(n, l)] = table;
+    *out = table;
+    return KZG_OK;
+}
+
+void multiproof_drop(kzg_srs* srs) {
+    std::lock_guard<std::mutex> lk(srs->lazy_mu);
+    for (auto& kv : srs->multiproof) (void)hipFree(kv.second);
+    srs->multiproof.clear();
+}
+
+// ---- the proofs -------------------------------------------------------------------------------------------------------------------
+// called under ctx->mu with the arguments checked (capi.hip kzg_compute_multiproofs)
+int32_t multiproof_run(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, size_t n, bool eval_form, size_t l, uint64_t* out_xy, uint8_t* out_inf) {
+    RoctxRange range("kzg:multiproofs");
+    const uint4* shat = nullptr;
+    int32_t rc = multiproof_cache(ctx, srs, n, l, &shat);
+    if (rc != KZG_OK) return rc;
+    const size_t m = n / l, M = 2 * m;
+    hipStream_t st = ctx->stream;
+    // W waves per frequency when l > 64 (<= 32), a lane adding tpl terms
+    const int log_g = l >= 64 ? 6 : __builtin_ctzll(l);
+    const uint32_t W = l > 64 ? (uint32_t)std::min<size_t>(l / 64, 32) : 1u;
+    const uint32_t tpl = (uint32_t)(l / ((size_t)W << log_g));
+    KZG_HIP_TRY(ctx, ctx->mp[0].reserve(n * 32));
+    KZG_HIP_TRY(ctx, ctx->mp[1].reserve(2 * n * 32));
+    KZG_HIP_TRY(ctx, ctx->mp[2].reserve(M * W * 36 * 4));
+    KZG_HIP_TRY(ctx, ctx->mp[3].reserve(M * 36 * 4));
+    KZG_HIP_TRY(ctx, ctx->mp[4].reserve(M * 36 * 4));
+    KZG_HIP_TRY(ctx, ctx->mp[5].reserve(m * (64 + 1 + NL * 4)));
+    uint4* f = ctx->mp[0].as<uint4>();
+    uint4* F = ctx->mp[1].as<uint4>();
+    int32_t* P0 = ctx->mp[2].as<int32_t>();
+    int32_t* P1 = ctx->mp[3].as<int32_t>();
+    int32_t* P2 = ctx->mp[4].as<int32_t>();
+    uint4* d_aff = ctx->mp[5].as<uint4>();                                   // m x 64 B
+    int32_t* aff_scratch = reinterpret_cast<int32_t*>(ctx->mp[5].as<uint8_t>() + m * 64);   // m x NL words
+    uint8_t* d_inf = ctx->mp[5].as<uint8_t>() + m * (64 + NL * 4);
+    // 1. coefficients (eval form: inverse NTT on the device), the l rows F^(b) and their NTTs
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(f, poly_mont, n * 32, hipMemcpyHostToDevice, st));
+    if (eval_form) { rc = ntt_run(ctx, f, n, true, st, &ctx->mp_ntt); if (rc != KZG_OK) return rc; }
+    hipLaunchKernelGGL(k_fk20_scatter_coeffs, dim3(grid_of(M * l)), dim3(256), 0, st, f, (uint32_t)m, (uint32_t)l, F);
+    for (size_t b = 0; b < l; ++b) {
+        rc = ntt_run(ctx, F + 2 * b * M, M, false, st, &ctx->mp_ntt);
+        if (rc != KZG_OK) return rc;
+    }
+    // 2. H = sum_b Fhat^(b) o Shat^(b)
+    int32_t* H = W > 1 ? P1 : P0;
+    if (l == 1) {
+        hipLaunchKernelGGL(k_fk20_pointwise, dim3(grid_of(M)), dim3(256), 0, st, F, shat, (uint32_t)M, H);
+    } else {
+        hipLaunchKernelGGL(k_fk20_lincomb, dim3(grid_of((M * W) << log_g)), dim3(256), 0, st, F, shat, (uint32_t)M, log_g, W, tpl, P0);
+        if (W > 1) hipLaunchKernelGGL(k_fk20_sum_partials, dim3(grid_of(M)), dim3(256), 0, st, P0, (uint32_t)M, W, H);
+    }
+    KZG_HIP_TRY(ctx, hipGetLastError());
+    // 3. h = IFFT_2m(H)[m - 1, 2m - 1), 4. pi = DFT_m(h): the slice is read in place (offset m - 1, stride 2m)
+    int32_t* X = W > 1 ? P0 : P1;                                               // the plane set H is not in
+    rc = g1_fft_planes(ctx, st, H, M, M, X, P2, true, true);
+    if (rc != KZG_OK) return rc;
+    int32_t* Y = H;                                                              // free again: stride m
+    rc = g1_fft_planes(ctx, st, X + (m - 1), M, m, Y, P2, false, false);
+    if (rc != KZG_OK) return rc;
+    // 5. one batched affine conversion (wire form, identity = zeros) and the identity flags
+    rc = g1fft_planes_to_affine(ctx, st, Y, m, d_aff, true, aff_scratch);
+    if (rc != KZG_OK) return rc;
+    hipLaunchKernelGGL(k_fk20_inf_flags, dim3(grid_of(m)), dim3(256), 0, st, Y, (uint32_t)m, d_inf);
+    KZG_HIP_TRY(ctx, hipGetLastError());
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(out_xy, d_aff, m * 64, hipMemcpyDeviceToHost, st));
+    if (out_inf) KZG_HIP_TRY(ctx, hipMemcpyAsync(out_inf, d_inf, m, hipMemcpyDeviceToHost, st));
+    KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    return KZG_OK;
+}
+
+}  // namespace kzg
+
+#if defined(KZG_DEVICE_BOUND_CHECK)   // the device bound-check variant only (field29.h, `make boundcheck`)
+#include "field29.h"
+KZG_BOUND_CHECK_EXPORTS(multiproof)
+#endif

@@ -308,6 +308,46 @@ class KZG:
             raise GenericError("Root of unity not found")
         return self.compute_proof(polynomial, z, srs)
 
+    # kzg.rs:187-234, every point at once (FK20)
+    def compute_multiproofs(self, polynomial, srs, chunk_len: int = 1):
+        """The proofs of every coset of the n-point domain in one call (`kzg_compute_multiproofs`, Feist-Khovratovich "FK20").
+        Chunk k < m = n / chunk_len is the coset {w^(k + j m) : j < chunk_len}: evaluation indices k, k + m, k + 2m, ...; its proof is
+        [f / (X^chunk_len - w^(k chunk_len))](tau).  With chunk_len = 1, row k is `compute_proof_with_known_z_fr_index(polynomial, k)`.
+        Returns an (m, 8) uint64 array of wire points (the identity as zeros, as `compute_proof` returns it)."""
+        if isinstance(polynomial, PolynomialEvalForm):
+            data, eval_form = polynomial.evaluations(), 1
+        elif isinstance(polynomial, PolynomialCoeffForm):
+            data, eval_form = polynomial.coeffs(), 0
+        else:
+            raise TypeError("compute_multiproofs takes a PolynomialEvalForm or a PolynomialCoeffForm")
+        n = len(polynomial)
+        chunk_len = int(chunk_len)
+        if n < 2:
+            raise GenericError("multi-proofs need a polynomial of at least 2 elements")
+        if chunk_len <= 0 or (chunk_len & (chunk_len - 1)) != 0:
+            raise GenericError("chunk length is not a power of 2")
+        if chunk_len > n // 2:
+            raise GenericError("chunk length exceeds half the polynomial length")
+        if n > len(srs):
+            raise SrsCapacityExceeded(n, len(srs))
+        ctx = self._ctx()
+        data = _lib.as_u64(data, 4)
+        m = n // chunk_len
+        out = np.zeros((m, 8), dtype=np.uint64)
+        inf = np.zeros(m, dtype=np.uint8)
+        rc = _lib.load().kzg_compute_multiproofs(ctx.handle, srs.handle, _lib.ptr(data), n, eval_form, chunk_len, _lib.ptr(out),
+                                                 inf.ctypes.data_as(_lib.u8p))
+        if rc == _lib.ERR_NOT_POWER_OF_TWO:
+            raise FFTError("length provided is not a power of 2")
+        if rc == _lib.ERR_DOMAIN:
+            raise FFTError("Could not perform IFFT due to domain consturction error")
+        if rc == _lib.ERR_SRS_CAPACITY_EXCEEDED:
+            raise SrsCapacityExceeded(n, len(srs))
+        ctx.check_device(rc)
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+        return out
+
     # kzg.rs:237-260
     def compute_quotient_eval_on_domain(self, z_fr, eval_fr, value_fr):
         """sum over the stored roots w^i != z of (f_i - value) w^i / ((z - w^i) z): the quotient's evaluation at the domain point z, on the GPU

@@ -165,6 +165,19 @@ class SRS:
     def drop_lagrange(self):
         _lib.load().kzg_srs_drop_lagrange(self.ctx.handle, self.handle)
 
+    def cache_multiproof(self, n: int, chunk_len: int = 1):
+        """Build the 2n points FK20 needs for the multi-proofs of n-element polynomials in chunks of `chunk_len` and keep them on the
+        device (`kzg_srs_cache_multiproof`); `KZG.compute_multiproofs` otherwise builds them on its first call.  Several (n, chunk_len)
+        pairs can be cached at once."""
+        rc = _lib.load().kzg_srs_cache_multiproof(self.ctx.handle, self.handle, n, chunk_len)
+        self.ctx.check_device(rc)
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+
+    def drop_multiproof(self):
+        """Release every cache `cache_multiproof` / `KZG.compute_multiproofs` attached (`kzg_srs_drop_multiproof`)."""
+        _lib.load().kzg_srs_drop_multiproof(self.ctx.handle, self.handle)
+
     def lagrange(self, n: int) -> "SRS":
         """The Lagrange basis of the first n points as an SRS of its own (`kzg_srs_lagrange`)."""
         h = C.c_void_p()
