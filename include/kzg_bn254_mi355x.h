@@ -23,6 +23,7 @@
  *   KZG_NO_PRECOMPUTE=1, KZG_NO_NAF=1     SRS uploads without any tables / without the per-bit tables (read at every upload)
  *   KZG_HOST_THREADS_MAX, KZG_HOST_THREADS cap of (default min(48, hardware threads, the cgroup's CPU quota)) / exact width of the host pool
  *   KZG_VB_GROUP_BYTES, KZG_VB_CHUNK_BYTES, KZG_VB_TRACE   batch verification: bytes per GPU round / per upload chunk; phase times on stderr
+ *                                         (KZG_VB_TRACE also prints the phases of kzg_verify_multiproof_batch, which then synchronises between them)
  *   KZG_ROCTX=1                           roctx ranges around the host phases (rocprofv3 --marker-trace)
  *   KZG_NTT_TILE_LOG=10 / 11              one tile size of the Fr NTT at every transform size
  *   KZG_EXCHANGE_TIMEOUT_S, KZG_RCCL_LIB  the _rccl entries: seconds to wait for a collective (60); the RCCL to dlopen
@@ -568,6 +569,56 @@ int32_t kzg_evaluate_blobs_in_evaluation_form_batch(kzg_ctx* ctx, const uint8_t*
 int32_t kzg_verify_blob_kzg_proof_batch(kzg_ctx* ctx, const uint8_t* const* blobs, const size_t* blob_lens,
                                         const uint64_t* commitments_xy_mont, const uint64_t* proofs_xy_mont, size_t n,
                                         const uint64_t* g2_tau_mont, int32_t* out_ok);
+
+/* ---- verification of coset proofs (the proofs of kzg_compute_multiproofs; the reference has none) -------------------------------
+ * n = domain size, w its primitive n-th root, l = chunk_len, m = n / l.  Coset k < m is {w^(k + j m) : j < l}; its values
+ * ys[j] = f(w^(k + j m)) are evals[k::m], its proof pi_k = [f / (X^l - w^(k l))](tau) G1 is entry k of kzg_compute_multiproofs.  With
+ * I_k the polynomial of degree < l through the values, I_k(X) = sum_t w^(-k t) IFFT_l(ys)_t X^t (IFFT_l over the root w^m, natural
+ * order), one proof verifies iff e(pi_k, [tau^l]_2 - [w^(k l)]G2) = e(C - [I_k(tau)]_1, G2).  A batch of N items (item i: commitment
+ * row c_i of M commitments, coset k_i, l values, proof pi_i) with weights r_i is ONE pairing check whatever N is:
+ *     A_t = sum_i r_i w^(-k_i t) IFFT_l(ys_i)_t                                  (GPU, kzg_coset_interpolate_rlc)
+ *     e(sum_i r_i pi_i, [tau^l]_2) = e(sum_rows (sum_{i: c_i = row} r_i) C_row - sum_t A_t [tau^t]_1 + sum_i r_i w^(k_i l) pi_i, G2)
+ * (for l = 1 the equation of kzg_verify_kzg_proof_batch).  The verifier needs the first l G1 points of an SRS and one G2 point.
+ *
+ * kzg_coset_interpolate_rlc: out[t] = sum_i weights[i] * w^(-coset_indices[i] * t) * IFFT_l(ys_i)[t].  ys: count x chunk_len x 4 u64,
+ * coset_indices: count values < n / chunk_len, weights: count x 4 u64, out: chunk_len x 4 u64 (canonical wire words: equal inputs give
+ * equal bits whatever the launch geometry).  Device memory grows with count * chunk_len only, not with n.  count = 0 -> zeros.
+ * Errors: a null pointer (with count > 0) -> KZG_ERR_INVALID_ARG; n = 0 or not a power of two -> KZG_ERR_NOT_POWER_OF_TWO; n > 2^24 ->
+ * KZG_ERR_DOMAIN; n = 1, chunk_len not a power of two or > n / 2, a coset index >= n / chunk_len -> KZG_ERR_INVALID_ARG;
+ * count * chunk_len > 2^28 -> KZG_ERR_TOO_LARGE. */
+int32_t kzg_coset_interpolate_rlc(kzg_ctx* ctx, const uint64_t* ys_mont, const uint64_t* coset_indices, const uint64_t* weights_mont,
+                                  size_t count, size_t n, size_t chunk_len, uint64_t* out_coeffs_mont);
+/* The Fiat-Shamir weights [r^0 .. r^(count-1)] of a batch.  Host only.  This library's own transcript, built like the one of
+ * kzg_compute_r_powers but in two levels, so that the count x chunk_len x 32 bytes of values are hashed on the host pool:
+ *   d_i = SHA-256("KZGBN254_COSETITEM___V1_" || u64be(c_i) || u64be(k_i) || chunk_len x be32(ys_i[j]) || ark-compressed pi_i)
+ *   r   = SHA-256("KZGBN254_COSETBATCH__V1_" || u64be(n) || u64be(chunk_len) || u64be(n_commitments) || u64be(count) ||
+ *                 n_commitments x ark-compressed C || d_0 || .. || d_(count-1)) mod r
+ * (both tags 24 bytes; point and scalar encodings as in kzg_compute_r_powers).  count = 0 writes nothing.  A null pointer ->
+ * KZG_ERR_INVALID_ARG; count * chunk_len > 2^28 -> KZG_ERR_TOO_LARGE.  Points are serialised as given, not validated. */
+int32_t kzg_compute_multiproof_r_powers(const uint64_t* commitments_xy_mont, size_t n_commitments, const uint64_t* commitment_indices,
+                                        const uint64_t* coset_indices, const uint64_t* ys_mont, const uint64_t* proofs_xy_mont,
+                                        size_t count, size_t n, size_t chunk_len, uint64_t* out_r_powers_mont);
+/* The batch equation above: upload of values / indices / weights, kzg_coset_interpolate_rlc's kernels, an MSM of the l coefficients
+ * over srs[0 .. l) with the scalars left on the device, the two count-point combinations of the proofs and the n_commitments-point
+ * one of the commitments as batched MSMs (every uploaded point checked on the device), point sums and ONE pairing check on the host.
+ * r_powers_mont = NULL derives the weights with kzg_compute_multiproof_r_powers.  The same item may appear twice.  *out_ok = 1 iff the
+ * equation holds; a failed check is *out_ok = 0 with KZG_OK.  count = 0 -> *out_ok = 1.
+ * g2_tau_l_mont = [tau^l]_2 in the G2 wire format, checked to be on the twist (not its subgroup: see kzg_verify_proof); NULL is
+ * allowed for chunk_len = 1 only and then means consts::G2_TAU.  The identity (all-zero wire point) is a valid commitment and proof.
+ * Errors, in this order: a null pointer (with count > 0), NULL g2_tau_l_mont with chunk_len != 1, srs of another context or a
+ * Lagrange-basis handle -> KZG_ERR_INVALID_ARG; n = 0 or not a power of two -> KZG_ERR_NOT_POWER_OF_TWO; n > 2^24 -> KZG_ERR_DOMAIN;
+ * n = 1, chunk_len not a power of two or > n / 2 -> KZG_ERR_INVALID_ARG; chunk_len > kzg_srs_len(srs) ->
+ * KZG_ERR_SRS_CAPACITY_EXCEEDED; a coset index >= n / chunk_len or a commitment index >= n_commitments -> KZG_ERR_INVALID_ARG;
+ * count * chunk_len > 2^28 -> KZG_ERR_TOO_LARGE; a commitment or proof off the curve -> KZG_ERR_G1_NOT_ON_CURVE; then g2_tau_l_mont off
+ * the twist -> KZG_ERR_G2_TAU_NOT_ON_CURVE. */
+int32_t kzg_verify_multiproof_batch(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments,
+                                    const uint64_t* commitment_indices, const uint64_t* coset_indices, const uint64_t* ys_mont,
+                                    const uint64_t* proofs_xy_mont, size_t count, size_t n, size_t chunk_len,
+                                    const uint64_t* r_powers_mont, const uint64_t* g2_tau_l_mont, int32_t* out_ok);
+/* One proof: the batch of one item with weight 1 (ys: chunk_len x 4 u64).  Errors as above. */
+int32_t kzg_verify_multiproof(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t commitment_xy_mont[8], const uint64_t proof_xy_mont[8],
+                              uint64_t coset_index, const uint64_t* ys_mont, size_t n, size_t chunk_len,
+                              const uint64_t* g2_tau_l_mont, int32_t* out_ok);
 
 #ifdef __cplusplus
 }

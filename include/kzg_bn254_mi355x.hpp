@@ -635,6 +635,32 @@ inline bool verify_blob_kzg_proof(const Blob& blob, const G1Affine& commitment, 
     detail::check(kzg_verify_blob_kzg_proof(ctx.handle(), blob.data().data(), blob.len(), commitment.xy.data(), proof.xy.data(), g2_tau ? g2_tau->w.data() : nullptr, &ok), ctx.handle());
     return ok != 0;
 }
+// One coset proof of KZG.compute_multiproofs (kzg_verify_multiproof): ys = the l values of coset `coset_index` of the n-point domain,
+// g2_tau_l = [tau^l]G2 (nullptr is allowed for l = 1 only: consts::G2_TAU); srs needs its first l points.
+inline bool verify_multiproof(const G1Affine& commitment, const G1Affine& proof, uint64_t coset_index, const std::vector<Fr>& ys, size_t n, const SRS& srs,
+                              const G2Affine* g2_tau_l = nullptr) {
+    int32_t ok = 0;
+    detail::check(kzg_verify_multiproof(srs.context().handle(), srs.handle(), commitment.xy.data(), proof.xy.data(), coset_index,
+                                        ys.empty() ? nullptr : ys.data()->limbs.data(), n, ys.size(), g2_tau_l ? g2_tau_l->w.data() : nullptr, &ok),
+                  srs.context().handle());
+    return ok != 0;
+}
+// A batch of coset proofs in one pairing check (kzg_verify_multiproof_batch): item i = (commitments[commitment_indices[i]], coset
+// coset_indices[i], ys[i l .. (i + 1) l), proofs[i]); r_powers = nullptr derives the weights (kzg_compute_multiproof_r_powers).
+inline bool verify_multiproof_batch(const std::vector<G1Affine>& commitments, const std::vector<uint64_t>& commitment_indices,
+                                    const std::vector<uint64_t>& coset_indices, const std::vector<Fr>& ys, const std::vector<G1Affine>& proofs, size_t n,
+                                    size_t chunk_len, const SRS& srs, const G2Affine* g2_tau_l = nullptr, const std::vector<Fr>* r_powers = nullptr) {
+    const size_t count = proofs.size();
+    if (!(commitment_indices.size() == count && coset_indices.size() == count && ys.size() == count * chunk_len && (!r_powers || r_powers->size() == count)))
+        throw KzgError::GenericError("length's of the input are not the same");
+    int32_t ok = 0;
+    detail::check(kzg_verify_multiproof_batch(srs.context().handle(), srs.handle(), commitments.empty() ? nullptr : commitments.data()->xy.data(), commitments.size(),
+                                              commitment_indices.data(), coset_indices.data(), ys.empty() ? nullptr : ys.data()->limbs.data(),
+                                              proofs.empty() ? nullptr : proofs.data()->xy.data(), count, n, chunk_len,
+                                              r_powers && count ? r_powers->data()->limbs.data() : nullptr, g2_tau_l ? g2_tau_l->w.data() : nullptr, &ok),
+                  srs.context().handle());
+    return ok != 0;
+}
 }  // namespace verify
 namespace batch {
 inline bool verify_blob_kzg_proof_batch(const std::vector<Blob>& blobs, const std::vector<G1Affine>& commitments, const std::vector<G1Affine>& proofs,

@@ -163,6 +163,10 @@ PROTOTYPES = {
     "kzg_compute_proof_rccl_device": (i32, [vp, vp, sz, vp, sz, sz, u64p, vp, i32, u64p, u8p, u64p]),
     "kzg_verify_blob_kzg_proof": (i32, [vp, u8p, sz, u64p, u64p, u64p, C.POINTER(i32)]),
     "kzg_verify_blob_kzg_proof_batch": (i32, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), u64p, u64p, sz, u64p, C.POINTER(i32)]),
+    "kzg_coset_interpolate_rlc": (i32, [vp, u64p, u64p, u64p, sz, sz, sz, u64p]),
+    "kzg_compute_multiproof_r_powers": (i32, [u64p, sz, u64p, u64p, u64p, u64p, sz, sz, sz, u64p]),
+    "kzg_verify_multiproof_batch": (i32, [vp, vp, u64p, sz, u64p, u64p, u64p, u64p, sz, sz, sz, u64p, u64p, C.POINTER(i32)]),
+    "kzg_verify_multiproof": (i32, [vp, vp, u64p, u64p, C.c_uint64, u64p, sz, sz, u64p, C.POINTER(i32)]),
 }
 
 _lib = None

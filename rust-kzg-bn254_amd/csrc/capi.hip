@@ -5,6 +5,7 @@
 #include "host_sha256.h"
 #include "host_transcript.h"
 #include "host_lagrange.h"
+#include "host_fr.h"
 
 #include <algorithm>
 #include <atomic>
@@ -183,6 +184,8 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
     for (auto& ps : ctx->poly) ps.release();
     for (auto& b : ctx->mp) b.release();
     ctx->mp_ntt.release();
+    for (auto& b : ctx->mv) b.release();
+    ctx->mv_ntt.release();
     ctx->rccl_buf.release();
     if (ctx->rccl_pinned) { (void)hipHostFree(ctx->rccl_pinned); ctx->rccl_pinned = nullptr; ctx->rccl_pinned_bytes = 0; }
     if (ctx->vb_pinned) { (void)hipHostFree(ctx->vb_pinned); ctx->vb_pinned = nullptr; ctx->vb_pinned_bytes = 0; }
@@ -632,12 +635,9 @@ int32_t kzg_msm_g1(kzg_ctx* ctx, const uint64_t* bases_xy_mont, size_t n_bases, 
     return msm_run(ctx, b, d_scalars, n_bases, out_xy_mont, out_is_infinity, nullptr);
 }
 
-static int32_t msm_g1_batch_impl(kzg_ctx* ctx, const uint64_t* bases_xy_mont, const uint64_t* scalars_mont, size_t n, size_t batch,
-                                 uint64_t* out_xy_mont, uint8_t* out_is_infinity, uint32_t* off_curve) {
-    if (!ctx || !out_xy_mont || batch == 0 || batch > 64) return KZG_ERR_INVALID_ARG;
-    if (n && (!bases_xy_mont || !scalars_mont)) return KZG_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+// (the caller holds ctx->mu and has set the device)
+static int32_t msm_g1_batch_locked(kzg_ctx* ctx, const uint64_t* bases_xy_mont, const uint64_t* scalars_mont, size_t n, size_t batch,
+                                   uint64_t* out_xy_mont, uint8_t* out_is_infinity, uint32_t* off_curve) {
     if (off_curve) *off_curve = 0;
     if (n == 0) {
         for (size_t i = 0; i < batch; ++i) write_identity(out_xy_mont + 8 * i, out_is_infinity ? out_is_infinity + i : nullptr, nullptr);
@@ -652,6 +652,14 @@ static int32_t msm_g1_batch_impl(kzg_ctx* ctx, const uint64_t* bases_xy_mont, co
     rc = stage_scalars(ctx, scalars_mont, total, &d_scalars);
     if (rc != KZG_OK) return rc;
     return msm_run_batch(ctx, ctx->msm.bases.as<uint4>(), d_scalars, n, (uint32_t)batch, out_xy_mont, out_is_infinity);
+}
+static int32_t msm_g1_batch_impl(kzg_ctx* ctx, const uint64_t* bases_xy_mont, const uint64_t* scalars_mont, size_t n, size_t batch,
+                                 uint64_t* out_xy_mont, uint8_t* out_is_infinity, uint32_t* off_curve) {
+    if (!ctx || !out_xy_mont || batch == 0 || batch > 64) return KZG_ERR_INVALID_ARG;
+    if (n && (!bases_xy_mont || !scalars_mont)) return KZG_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return msm_g1_batch_locked(ctx, bases_xy_mont, scalars_mont, n, batch, out_xy_mont, out_is_infinity, off_curve);
 }
 int32_t kzg_msm_g1_batch(kzg_ctx* ctx, const uint64_t* bases_xy_mont, const uint64_t* scalars_mont, size_t n, size_t batch,
                          uint64_t* out_xy_mont, uint8_t* out_is_infinity) {
@@ -1911,6 +1919,214 @@ int32_t kzg_compute_r_powers(const uint64_t* commitments_xy_mont, const uint64_t
     return KZG_OK;
 }
 
+// ---- verification of FK20 coset proofs (multiverify.hip; the proofs: kzg_compute_multiproofs) ---------------------------------
+namespace {
+const char COSET_ITEM_DOMAIN[] = "KZGBN254_COSETITEM___V1_";     // 24 bytes each; this library's own transcript (the reference has no coset proofs)
+const char COSET_BATCH_DOMAIN[] = "KZGBN254_COSETBATCH__V1_";
+void put_u64be(uint8_t* p, uint64_t v) { for (int b = 0; b < 8; ++b) p[b] = (uint8_t)(v >> (8 * (7 - b))); }
+
+// Two levels: one SHA-256 per item over its index pair, its l values and its proof (host pool), one over the header, the commitments and the digests
+void multiproof_r_powers_host(const uint64_t* commitments, size_t n_commitments, const uint64_t* commitment_indices, const uint64_t* coset_indices,
+                              const uint64_t* ys, const uint64_t* proofs, size_t count, size_t n, size_t l, uint64_t* out) {
+    using namespace kzg_host;
+    const size_t head = 24 + 32 + 32 * n_commitments;
+    std::vector<uint8_t> data(head + 32 * count, 0);
+    memcpy(data.data(), COSET_BATCH_DOMAIN, 24);
+    put_u64be(data.data() + 24, (uint64_t)n);
+    put_u64be(data.data() + 32, (uint64_t)l);
+    put_u64be(data.data() + 40, (uint64_t)n_commitments);
+    put_u64be(data.data() + 48, (uint64_t)count);
+    for (size_t c = 0; c < n_commitments; ++c) g1_serialize_compressed_ark(g1_from_wire(commitments + 8 * c), data.data() + 56 + 32 * c);
+    const size_t per = std::max<size_t>(1, 1024 / l), jobs = (count + per - 1) / per;
+    auto body = [&](size_t j) {
+        std::vector<uint8_t> item(24 + 16 + 32 * l + 32);
+        memcpy(item.data(), COSET_ITEM_DOMAIN, 24);
+        for (size_t i = j * per; i < std::min(count, (j + 1) * per); ++i) {
+            put_u64be(item.data() + 24, commitment_indices[i]);
+            put_u64be(item.data() + 32, coset_indices[i]);
+            for (size_t t = 0; t < l; ++t) fr_wire_to_be_bytes(ys + 4 * (i * l + t), item.data() + 40 + 32 * t);
+            g1_serialize_compressed_ark(g1_from_wire(proofs + 8 * i), item.data() + 40 + 32 * l);
+            Sha256 sh;
+            sha256_init(sh);
+            sha256_update(sh, item.data(), item.size());
+            sha256_final(sh, data.data() + head + 32 * i);
+        }
+    };
+    if (jobs > 1) parallel_for(jobs, body); else if (jobs == 1) body(0);
+    Sha256 sh;
+    sha256_init(sh);
+    sha256_update(sh, data.data(), data.size());
+    uint8_t dig[32];
+    sha256_final(sh, dig);
+    uint64_t r[4], cur[4];
+    digest_to_fr_wire(dig, r);
+    const uint64_t one_int[4] = {1, 0, 0, 0};
+    fr_mul(FR_R2_WORDS, one_int, cur);
+    for (size_t i = 0; i < count; ++i) { memcpy(out + 4 * i, cur, 32); fr_mul(cur, r, cur); }   // helpers::compute_powers
+}
+
+// the domain / chunk table of kzg_compute_multiproofs, in the documented order
+int32_t coset_domain_check(size_t n, size_t chunk_len) {
+    if (n == 0 || (n & (n - 1)) != 0) return KZG_ERR_NOT_POWER_OF_TWO;
+    if (n > ((size_t)1 << 24)) return KZG_ERR_DOMAIN;
+    if (n == 1 || chunk_len == 0 || (chunk_len & (chunk_len - 1)) != 0 || chunk_len > n / 2) return KZG_ERR_INVALID_ARG;
+    return KZG_OK;
+}
+}  // namespace
+
+int32_t kzg_compute_multiproof_r_powers(const uint64_t* commitments_xy_mont, size_t n_commitments, const uint64_t* commitment_indices,
+                                        const uint64_t* coset_indices, const uint64_t* ys_mont, const uint64_t* proofs_xy_mont,
+                                        size_t count, size_t n, size_t chunk_len, uint64_t* out_r_powers_mont) {
+    if (count == 0) return KZG_OK;
+    if (!commitment_indices || !coset_indices || !ys_mont || !proofs_xy_mont || !out_r_powers_mont || (n_commitments && !commitments_xy_mont)) return KZG_ERR_INVALID_ARG;
+    if (chunk_len == 0 || count > ((size_t)1 << 28) / chunk_len) return chunk_len == 0 ? KZG_ERR_INVALID_ARG : KZG_ERR_TOO_LARGE;
+    multiproof_r_powers_host(commitments_xy_mont, n_commitments, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, count, n, chunk_len, out_r_powers_mont);
+    return KZG_OK;
+}
+
+int32_t kzg_coset_interpolate_rlc(kzg_ctx* ctx, const uint64_t* ys_mont, const uint64_t* coset_indices, const uint64_t* weights_mont,
+                                  size_t count, size_t n, size_t chunk_len, uint64_t* out_coeffs_mont) {
+    if (!ctx || !out_coeffs_mont) return KZG_ERR_INVALID_ARG;
+    if (count && (!ys_mont || !coset_indices || !weights_mont)) return KZG_ERR_INVALID_ARG;
+    int32_t rc = coset_domain_check(n, chunk_len);
+    if (rc != KZG_OK) return rc;
+    for (size_t i = 0; i < count; ++i) if (coset_indices[i] >= n / chunk_len) return KZG_ERR_INVALID_ARG;
+    if (count > ((size_t)1 << 28) / chunk_len) return KZG_ERR_TOO_LARGE;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t l = chunk_len;
+    KZG_HIP_TRY(ctx, ctx->mv[0].reserve(std::max<size_t>(count * l * 32, 32)));
+    KZG_HIP_TRY(ctx, ctx->mv[1].reserve(std::max<size_t>(count * 40, 64)));
+    KZG_HIP_TRY(ctx, ctx->mv[2].reserve(l * 32));
+    uint4* d_w = ctx->mv[1].as<uint4>();
+    uint64_t* d_k = reinterpret_cast<uint64_t*>(ctx->mv[1].as<uint8_t>() + count * 32);
+    if (count) {
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(ctx->mv[0].p, ys_mont, count * l * 32, hipMemcpyHostToDevice, ctx->stream));
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(d_w, weights_mont, count * 32, hipMemcpyHostToDevice, ctx->stream));
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(d_k, coset_indices, count * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = coset_interpolate_rlc_device(ctx, ctx->mv[0].as<uint4>(), d_k, d_w, count, n, l, ctx->mv[2].as<uint4>());
+    if (rc != KZG_OK) return rc;
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(out_coeffs_mont, ctx->mv[2].p, l * 32, hipMemcpyDeviceToHost, ctx->stream));
+    KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return KZG_OK;
+}
+
+// accept <=> e(sum_i r_i pi_i, [tau^l]_2) = e(sum_rows R_row C_row - sum_t A_t [tau^t]_1 + sum_i r_i w^(k_i l) pi_i, G2), from
+// pi_i tau^l = C - I_i(tau) + w^(k_i l) pi_i.  For l = 1 this is batch.rs:228-254.
+int32_t kzg_verify_multiproof_batch(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments,
+                                    const uint64_t* commitment_indices, const uint64_t* coset_indices, const uint64_t* ys_mont,
+                                    const uint64_t* proofs_xy_mont, size_t count, size_t n, size_t chunk_len,
+                                    const uint64_t* r_powers_mont, const uint64_t* g2_tau_l_mont, int32_t* out_ok) {
+    using namespace kzg_host;
+    if (!ctx || !srs || !out_ok) return KZG_ERR_INVALID_ARG;
+    if (count && (!commitments_xy_mont || !commitment_indices || !coset_indices || !ys_mont || !proofs_xy_mont)) return KZG_ERR_INVALID_ARG;
+    if (!g2_tau_l_mont && chunk_len != 1) return KZG_ERR_INVALID_ARG;                     // consts::G2_TAU is [tau]_2 only
+    if (srs->ctx != ctx || srs->lagrange_of != 0) return KZG_ERR_INVALID_ARG;
+    int32_t rc = coset_domain_check(n, chunk_len);
+    if (rc != KZG_OK) return rc;
+    const size_t l = chunk_len, m = n / l, N = count;
+    if (l > srs->n) return KZG_ERR_SRS_CAPACITY_EXCEEDED;
+    for (size_t i = 0; i < N; ++i) if (coset_indices[i] >= m || commitment_indices[i] >= n_commitments) return KZG_ERR_INVALID_ARG;
+    if (N > ((size_t)1 << 28) / l) return KZG_ERR_TOO_LARGE;
+    if (N == 0) { *out_ok = 1; return KZG_OK; }
+    const bool trace = opts().vb_trace != 0;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const auto t0 = now();
+    G2 g2_tau_l;
+    const bool g2_ok = load_g2_tau(g2_tau_l_mont, &g2_tau_l);                            // reported after an off-curve G1 point, as verify_batch_core does
+    std::vector<uint64_t> derived;
+    if (!r_powers_mont) {
+        RoctxRange range("kzg:multiproof_verify:r_powers (host)");
+        derived.resize(4 * N);
+        multiproof_r_powers_host(commitments_xy_mont, n_commitments, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, N, n, l, derived.data());
+        r_powers_mont = derived.data();
+    }
+    const auto t_rp = now();
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // 1. values, indices, weights -> the l coefficients A_t (left on the device)
+    KZG_HIP_TRY(ctx, ctx->mv[0].reserve(N * l * 32));
+    KZG_HIP_TRY(ctx, ctx->mv[1].reserve(N * 40));
+    KZG_HIP_TRY(ctx, ctx->mv[2].reserve(l * 32));
+    uint4* d_w = ctx->mv[1].as<uint4>();
+    uint64_t* d_k = reinterpret_cast<uint64_t*>(ctx->mv[1].as<uint8_t>() + N * 32);
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(ctx->mv[0].p, ys_mont, N * l * 32, hipMemcpyHostToDevice, ctx->stream));
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(d_w, r_powers_mont, N * 32, hipMemcpyHostToDevice, ctx->stream));
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(d_k, coset_indices, N * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (trace) KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const auto t_up = now();
+    rc = coset_interpolate_rlc_device(ctx, ctx->mv[0].as<uint4>(), d_k, d_w, N, n, l, ctx->mv[2].as<uint4>());
+    if (rc != KZG_OK) return rc;
+    if (trace) KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const auto t_ker = now();
+    // 2. [sum_i r_i I_i(tau)]_1: an MSM of the coefficients over srs[0 .. l)
+    uint64_t interp_xy[8];
+    uint8_t interp_inf = 0;
+    rc = msm_srs_locked(ctx, srs, 0, ctx->mv[2].p, true, l, interp_xy, &interp_inf, nullptr);
+    if (rc != KZG_OK) return rc;
+    const auto t_msm1 = now();
+    // 3. host scalars: r_i w^(k_i l) (w^l = w_m from a two-level power table) and the row sums of the weights
+    std::vector<uint64_t> bases(2 * N * 8), scalars(2 * N * 4), row_w(4 * n_commitments, 0);
+    {
+        const int log_m = __builtin_ctzll(m), lo_bits = (log_m + 1) / 2, hi_bits = log_m - lo_bits;
+        const uint64_t* wm = kzg::h_roots().w[log_m];
+        const uint64_t one_int[4] = {1, 0, 0, 0};
+        std::vector<uint64_t> lo(4 << lo_bits), hi(4 << hi_bits);
+        fr_mul(FR_R2_WORDS, one_int, lo.data());
+        for (size_t j = 1; j < ((size_t)1 << lo_bits); ++j) fr_mul(lo.data() + 4 * (j - 1), wm, lo.data() + 4 * j);
+        uint64_t step[4];
+        fr_mul(lo.data() + 4 * (((size_t)1 << lo_bits) - 1), wm, step);                  // w_m^(2^lo_bits)
+        memcpy(hi.data(), lo.data(), 32);
+        for (size_t j = 1; j < ((size_t)1 << hi_bits); ++j) fr_mul(hi.data() + 4 * (j - 1), step, hi.data() + 4 * j);
+        const size_t chunks = N >= 1024 ? 32 : 1, per = (N + chunks - 1) / chunks;
+        auto body = [&](size_t c) {
+            for (size_t i = c * per; i < std::min(N, (c + 1) * per); ++i) {
+                const uint64_t k = coset_indices[i];
+                uint64_t h[4];
+                fr_mul(lo.data() + 4 * (k & (((uint64_t)1 << lo_bits) - 1)), hi.data() + 4 * (k >> lo_bits), h);
+                fr_mul(r_powers_mont + 4 * i, h, scalars.data() + (N + i) * 4);
+            }
+        };
+        if (chunks > 1) parallel_for(chunks, body); else body(0);
+        for (size_t i = 0; i < N; ++i) { uint64_t* rw = row_w.data() + 4 * commitment_indices[i]; fr_add(rw, r_powers_mont + 4 * i, rw); }
+        memcpy(scalars.data(), r_powers_mont, N * 32);
+        memcpy(bases.data(), proofs_xy_mont, N * 64);
+        memcpy(bases.data() + N * 8, proofs_xy_mont, N * 64);
+    }
+    // 4. the two N-point combinations of the proofs and the M-point one of the commitments; every uploaded point is checked on the device
+    uint64_t sums[2 * 8], c_sum[8];
+    uint8_t infs[2], c_inf = 0;
+    uint32_t off_p = 0, off_c = 0;
+    rc = msm_g1_batch_locked(ctx, bases.data(), scalars.data(), N, 2, sums, infs, &off_p);
+    if (rc != KZG_OK) return rc;
+    rc = msm_g1_batch_locked(ctx, commitments_xy_mont, row_w.data(), n_commitments, 1, c_sum, &c_inf, &off_c);
+    if (rc != KZG_OK) return rc;
+    if (off_p || off_c) return KZG_ERR_G1_NOT_ON_CURVE;
+    if (!g2_ok) return KZG_ERR_G2_TAU_NOT_ON_CURVE;
+    const auto t_msm2 = now();
+    // 5. point sums and ONE pairing check
+    const G1 lhs = g1_from_wire(sums);
+    const G1 rhs = g1_add(g1_add(g1_from_wire(c_sum), g1_neg(g1_from_wire(interp_xy))), g1_from_wire(sums + 8));
+    *out_ok = pairings_verify_pooled(lhs, g2_tau_l, rhs, g2_generator()) ? 1 : 0;
+    if (trace)
+        fprintf(stderr, "kzg_verify_multiproof_batch N=%zu l=%zu M=%zu: r_powers %.3f ms, upload %.3f ms, interpolation kernel %.3f ms, coefficient MSM %.3f ms, "
+                "host scalars + proof / commitment MSMs %.3f ms, point sums + pairing %.3f ms, call %.3f ms\n", N, l, n_commitments, ms(t0, t_rp), ms(t_rp, t_up),
+                ms(t_up, t_ker), ms(t_ker, t_msm1), ms(t_msm1, t_msm2), ms(t_msm2, now()), ms(t0, now()));
+    return KZG_OK;
+}
+
+int32_t kzg_verify_multiproof(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t commitment_xy_mont[8], const uint64_t proof_xy_mont[8],
+                              uint64_t coset_index, const uint64_t* ys_mont, size_t n, size_t chunk_len,
+                              const uint64_t* g2_tau_l_mont, int32_t* out_ok) {
+    if (!commitment_xy_mont || !proof_xy_mont || !ys_mont) return KZG_ERR_INVALID_ARG;
+    const uint64_t zero = 0, one_int[4] = {1, 0, 0, 0};
+    uint64_t one_w[4];
+    kzg_host::fr_mul(FR_R2_WORDS, one_int, one_w);
+    return kzg_verify_multiproof_batch(ctx, srs, commitment_xy_mont, 1, &zero, &coset_index, ys_mont, proof_xy_mont, 1, n, chunk_len, one_w, g2_tau_l_mont, out_ok);
+}
+
 // verify::verify_blob_kzg_proof (verifier/src/verify.rs:76-98) in one call: validate both points, z = compute_challenge(blob, commitment),
 // y = p(z) (one batched-evaluation launch of one blob), then verify::verify_proof (verify.rs:10-72) on the host.
 int32_t kzg_verify_blob_kzg_proof(kzg_ctx* ctx, const uint8_t* blob_bytes, size_t len, const uint64_t commitment_xy_mont[8],
@@ -1978,7 +2194,7 @@ int32_t srs_upload_plain(kzg_ctx* ctx, const uint64_t* g1_xy_mont, size_t n_poin
 KZG_BOUND_CHECK_EXPORTS(capi)
 // The variant library's totals over every translation unit: counts[site] summed, first[site] = the operand limbs kept by the first
 // translation unit (in the order below) whose counter of that site fired.  Not declared in include/kzg_bn254_mi355x.h.
-#define KZG_BC_UNITS(X) X(msm) X(ntt) X(poly) X(lagrange) X(srs) X(g1fft) X(capi) X(blobstream) X(multi) X(ubench) X(multiproof)
+#define KZG_BC_UNITS(X) X(msm) X(ntt) X(poly) X(lagrange) X(srs) X(g1fft) X(capi) X(blobstream) X(multi) X(ubench) X(multiproof) X(multiverify)
 #define KZG_BC_DECLARE(name) extern "C" int kzg_bc_read_##name(unsigned long long*, int32_t*); extern "C" int kzg_bc_reset_##name();
 KZG_BC_UNITS(KZG_BC_DECLARE)
 extern "C" int kzg_bc_sites() { return kzg::KZG_SITES; }

@@ -125,6 +125,8 @@ struct kzg_ctx {
     kzg::NttWorkspace& slot_ntt(int slot) { return slot ? ntt_x[slot - 1] : ntt; }
     kzg::DeviceBuffer mp[6];                   // scratch of kzg_compute_multiproofs / kzg_srs_cache_multiproof (multiproof.hip), its own: slot 0's may be in flight
     kzg::NttWorkspace mp_ntt;
+    kzg::DeviceBuffer mv[4];                   // kzg_coset_interpolate_rlc / kzg_verify_multiproof_batch (multiverify.hip): values | indices + weights | coefficients | partial rows
+    kzg::NttWorkspace mv_ntt;
 };
 
 struct kzg_srs {
@@ -261,6 +263,8 @@ int32_t g1fft_planes_to_affine(kzg_ctx* ctx, hipStream_t st, const int32_t* plan
 int32_t multiproof_cache(kzg_ctx* ctx, kzg_srs* srs, size_t n, size_t l, const uint4** out);
 int32_t multiproof_run(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, size_t n, bool eval_form, size_t l, uint64_t* out_xy, uint8_t* out_inf);
 void multiproof_drop(kzg_srs* srs);
+// verification of coset proofs (multiverify.hip): d_out[t] = sum_i weights[i] w^(-ks[i] t) IFFT_l(ys_i)[t], enqueued on ctx->stream (d_ys is scratch when l > 1024)
+int32_t coset_interpolate_rlc_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, size_t count, size_t n, size_t l, uint4* d_out);
 
 int32_t set_error(kzg_ctx* ctx, hipError_t e, const char* where);
 // the context's high-priority auxiliary stream (lagrange.hip)

@@ -13,7 +13,7 @@ from .consts import (BYTES_PER_FIELD_ELEMENT, FIAT_SHAMIR_PROTOCOL_DOMAIN, FQ_MO
                      MAINNET_SRS_G1_SIZE, primitive_root_of_unity)
 from .errors import (DeserializationError, G2GeneratorNotAcceptedError, GenericError, InvalidFieldElement, InvalidInputLength, MsmError,
                      NotOnCurveError)
-from .fr import fq_to_int, fr_from_int, fr_to_int, frs_from_ints, frs_to_ints, g1_is_identity
+from .fr import fq_from_int, fq_to_int, fr_from_int, fr_to_int, frs_from_ints, frs_to_ints, g1_is_identity
 
 
 def get_num_element(data_len: int, symbol_size: int) -> int:
@@ -320,6 +320,88 @@ def g2_tau() -> np.ndarray:
 def g2_mul_generator(scalar) -> np.ndarray:
     out = np.zeros(16, dtype=np.uint64)
     _lib.load().kzg_g2_mul_generator(_lib.ptr(_lib.as_u64(scalar, 0).reshape(4)), _lib.ptr(out))
+    return out
+
+
+def _fq_sqrt(a: int):
+    r = pow(a, (FQ_MODULUS + 1) // 4, FQ_MODULUS)
+    return r if r * r % FQ_MODULUS == a % FQ_MODULUS else None
+
+
+def _fq2_sqrt(a0: int, a1: int):
+    """A square root of a0 + a1 u in Fq[u] / (u^2 + 1), or None."""
+    p = FQ_MODULUS
+    if a1 == 0:
+        r = _fq_sqrt(a0)
+        if r is not None:
+            return (r, 0)
+        r = _fq_sqrt(-a0 % p)
+        return None if r is None else (0, r)
+    alpha = _fq_sqrt((a0 * a0 + a1 * a1) % p)
+    if alpha is None:
+        return None
+    half = pow(2, -1, p)
+    x0 = _fq_sqrt((a0 + alpha) * half % p)
+    if x0 is None:
+        x0 = _fq_sqrt((a0 - alpha) * half % p)
+    if x0 is None or x0 == 0:
+        return None
+    return (x0, a1 * pow(2 * x0, -1, p) % p)
+
+
+def read_g2_powers_of_2(path) -> np.ndarray:
+    """The G2 wire points (k, 16) of a file of gnark-compressed points [tau^(2^i)]_2, 64 bytes each: X.A1 || X.A0 big-endian, the top
+    two bits of the first byte 0b10 = the smaller y, 0b11 = the larger (the format of the reference's mainnet `g2.point.powerOf2`).
+    Entry log2(l) is the `g2_tau_l` that `verifier.verify_multiproof*` needs for chunks of l points of that setup.  Host only; every
+    decoded point passes `example_validate_g2_point` (on the twist, not the identity, in the order-r subgroup) or the call raises."""
+    data = open(path, "rb").read()
+    if len(data) == 0 or len(data) % 64 != 0:
+        raise DeserializationError("a file of compressed G2 points is a positive multiple of 64 bytes")
+    p = FQ_MODULUS
+    inv82 = pow(82, -1, p)
+    b2 = (27 * inv82 % p, -3 * inv82 % p)                                            # 3 / (9 + u)
+    mul2 = lambda a, b: ((a[0] * b[0] - a[1] * b[1]) % p, (a[0] * b[1] + a[1] * b[0]) % p)      # noqa: E731
+    larger = lambda v: (v[1] > (p - 1) // 2) if v[1] else (v[0] > (p - 1) // 2)                # noqa: E731
+    out = np.zeros((len(data) // 64, 16), dtype=np.uint64)
+    for i in range(len(data) // 64):
+        ch = data[64 * i:64 * i + 64]
+        flag = ch[0] >> 6
+        if flag not in (2, 3):
+            raise DeserializationError("G2 point %d: flag bits %d are not a compressed finite point" % (i, flag))
+        x = (int.from_bytes(ch[32:64], "big"), int.from_bytes(bytes([ch[0] & 0x3F]) + ch[1:32], "big"))
+        if x[0] >= p or x[1] >= p:
+            raise DeserializationError("G2 point %d: coordinate not below the modulus" % i)
+        x3 = mul2(mul2(x, x), x)
+        y = _fq2_sqrt((x3[0] + b2[0]) % p, (x3[1] + b2[1]) % p)
+        if y is None:
+            raise NotOnCurveError("G2 point not on curve")
+        neg = (-y[0] % p, -y[1] % p)
+        y = (y if larger(y) else neg) if flag == 3 else (neg if larger(y) else y)
+        for j, v in enumerate((x[0], x[1], y[0], y[1])):
+            out[i, 4 * j:4 * j + 4] = fq_from_int(v)
+        example_validate_g2_point(out[i])
+    return out
+
+
+def coset_interpolate_rlc(ys, coset_indices, weights, n: int, ctx=None) -> np.ndarray:
+    """A_t = sum_i weights[i] w^(-coset_indices[i] t) IFFT_l(ys[i])_t for t < l (`kzg_coset_interpolate_rlc`, GPU): the coefficients of
+    sum_i weights[i] I_i(X), I_i the polynomial of degree < l through the l values ys[i] on the coset {w^(k_i + j n / l)}.
+    ys: (count, l, 4); returns (l, 4)."""
+    ys = np.ascontiguousarray(_lib.as_u64(ys, 0))
+    if ys.ndim != 3 or ys.shape[2] != 4:
+        raise InvalidInputLength()
+    count, l = ys.shape[0], ys.shape[1]
+    ks = np.ascontiguousarray([int(v) for v in coset_indices], dtype=np.uint64)
+    ws = np.ascontiguousarray(_lib.as_u64(weights, 0)).reshape(-1, 4)
+    if len(ks) != count or len(ws) != count:
+        raise InvalidInputLength()
+    ctx = ctx or _lib.default_context()
+    out = np.zeros((l, 4), dtype=np.uint64)
+    rc = _lib.load().kzg_coset_interpolate_rlc(ctx.handle, _lib.ptr(ys) if count else None, _lib.ptr(ks) if count else None,
+                                               _lib.ptr(ws) if count else None, count, int(n), l, _lib.ptr(out))
+    ctx.check_device(rc)
+    if rc != _lib.OK:
+        raise GenericError(_lib.status_message(rc))
     return out
 
 

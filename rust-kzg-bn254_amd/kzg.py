@@ -348,6 +348,20 @@ class KZG:
             raise GenericError(_lib.status_message(rc))
         return out
 
+    def cosets(self, polynomial_eval_form, chunk_len: int = 1) -> np.ndarray:
+        """The values that go with the proofs of `compute_multiproofs`: an (m, chunk_len, 4) array, m = n / chunk_len, whose row k is
+        evals[k::m], the evaluations on the coset {w^(k + j m) : j < chunk_len} -- what `verifier.verify_multiproof*` takes as `ys`."""
+        if not isinstance(polynomial_eval_form, PolynomialEvalForm):
+            raise TypeError("cosets takes a PolynomialEvalForm")
+        n = len(polynomial_eval_form)
+        chunk_len = int(chunk_len)
+        if chunk_len <= 0 or (chunk_len & (chunk_len - 1)) != 0:
+            raise GenericError("chunk length is not a power of 2")
+        if n < 2 or (n & (n - 1)) != 0 or chunk_len > n // 2:
+            raise GenericError("chunk length exceeds half the polynomial length")
+        ev = _lib.as_u64(polynomial_eval_form.evaluations(), 4).reshape(chunk_len, n // chunk_len, 4)     # [j][k] = evals[k + j m]
+        return np.ascontiguousarray(ev.transpose(1, 0, 2))
+
     # kzg.rs:237-260
     def compute_quotient_eval_on_domain(self, z_fr, eval_fr, value_fr):
         """sum over the stored roots w^i != z of (f_i - value) w^i / ((z - w^i) z): the quotient's evaluation at the domain point z, on the GPU

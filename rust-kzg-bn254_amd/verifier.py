@@ -160,3 +160,90 @@ def verify_blob_kzg_proof_batch_py(blobs, commitments, proofs, g2_tau=None, ctx=
     zs, ys = helpers.compute_challenges_and_evaluate_polynomial(blobs, commitments, ctx)
     lengths = [len(b.to_polynomial_eval_form()) for b in blobs]
     return verify_kzg_proof_batch(commitments, zs, ys, proofs, lengths, g2_tau, ctx)
+
+
+# ---- coset proofs (the proofs of KZG.compute_multiproofs; the reference has none) -------------------------------------------
+COSET_ITEM_DOMAIN = b"KZGBN254_COSETITEM___V1_"
+COSET_BATCH_DOMAIN = b"KZGBN254_COSETBATCH__V1_"
+
+
+def _multiproof_args(commitments, commitment_indices, coset_indices, ys, proofs):
+    ys = np.ascontiguousarray(_lib.as_u64(ys, 0))
+    if ys.ndim != 3 or ys.shape[2] != 4:
+        raise InvalidInputLength()
+    count = ys.shape[0]
+    cm, pf = _pack(commitments, 8), _pack(proofs, 8)
+    ci = np.ascontiguousarray([int(v) for v in commitment_indices], dtype=np.uint64)
+    ki = np.ascontiguousarray([int(v) for v in coset_indices], dtype=np.uint64)
+    if not (len(pf) == len(ci) == len(ki) == count):
+        raise GenericError("length's of the input are not the same")
+    return cm, ci, ki, ys, pf
+
+
+def compute_multiproof_r_powers(commitments, commitment_indices, coset_indices, ys, proofs, n: int) -> np.ndarray:
+    """The weights [r^0 .. r^(count-1)] of a batch of coset proofs (`kzg_compute_multiproof_r_powers`, host only): item digests
+    d_i = SHA-256(COSET_ITEM_DOMAIN || u64be(c_i) || u64be(k_i) || l x be32(ys_i[j]) || compressed proof_i), then
+    r = SHA-256(COSET_BATCH_DOMAIN || u64be(n) || u64be(l) || u64be(M) || u64be(count) || M x compressed C || d_0 || ..) mod r."""
+    cm, ci, ki, ys, pf = _multiproof_args(commitments, commitment_indices, coset_indices, ys, proofs)
+    count, l = ys.shape[0], ys.shape[1]
+    out = np.zeros((count, 4), dtype=np.uint64)
+    if count == 0:
+        return out
+    rc = _lib.load().kzg_compute_multiproof_r_powers(_lib.ptr(cm) if len(cm) else None, len(cm), _lib.ptr(ci), _lib.ptr(ki), _lib.ptr(ys),
+                                                     _lib.ptr(pf), count, int(n), l, _lib.ptr(out))
+    if rc != _lib.OK:
+        raise GenericError(_lib.status_message(rc))
+    return out
+
+
+def compute_multiproof_r_powers_py(commitments, commitment_indices, coset_indices, ys, proofs, n: int) -> np.ndarray:
+    """The same transcript assembled in Python (hashlib): an independent cross-check of the C path."""
+    ys = np.asarray(ys, dtype=np.uint64)
+    count, l = ys.shape[0], ys.shape[1]
+    parts = [COSET_BATCH_DOMAIN, int(n).to_bytes(8, "big"), int(l).to_bytes(8, "big"), len(commitments).to_bytes(8, "big"),
+             int(count).to_bytes(8, "big")]
+    parts += [helpers.serialize_compressed(c) for c in commitments]
+    for i in range(count):
+        item = COSET_ITEM_DOMAIN + int(commitment_indices[i]).to_bytes(8, "big") + int(coset_indices[i]).to_bytes(8, "big")
+        item += b"".join(fr_to_int(ys[i, j]).to_bytes(BYTES_PER_FIELD_ELEMENT, "big") for j in range(l))
+        item += helpers.serialize_compressed(proofs[i])
+        parts.append(hashlib.sha256(item).digest())
+    return helpers.compute_powers(helpers.hash_to_field_element(b"".join(parts)), count)
+
+
+def verify_multiproof_batch(commitments, commitment_indices, coset_indices, ys, proofs, n: int, srs, g2_tau_l=None, r_powers=None,
+                            ctx=None) -> bool:
+    """A batch of coset proofs in ONE pairing check (`kzg_verify_multiproof_batch`).  Item i: commitment `commitments[commitment_indices[i]]`,
+    coset `coset_indices[i]` of the n-point domain, its l values `ys[i]` (= evals[k::n // l], `KZG.cosets`) and `proofs[i]` (row k of
+    `KZG.compute_multiproofs`).  `srs` needs its first l points only; `g2_tau_l` = [tau^l]_2 (G2 wire point; None is allowed for l = 1
+    and means consts::G2_TAU); `r_powers=None` derives the weights with `compute_multiproof_r_powers`."""
+    cm, ci, ki, ys, pf = _multiproof_args(commitments, commitment_indices, coset_indices, ys, proofs)
+    count, l = ys.shape[0], ys.shape[1]
+    if g2_tau_l is None and l != 1:
+        raise GenericError("g2_tau_l = None (consts::G2_TAU) is [tau]_2: chunks of more than one point need [tau^l]_2")
+    ctx = ctx or getattr(srs, "ctx", None) or _lib.default_context()                   # the SRS's own context
+    rp = None if r_powers is None else np.ascontiguousarray(_lib.as_u64(r_powers, 0)).reshape(-1, 4)
+    if rp is not None and len(rp) != count:
+        raise GenericError("length's of the input are not the same")
+    ok = _lib.i32(0)
+    rc = _lib.load().kzg_verify_multiproof_batch(ctx.handle, srs.handle, _lib.ptr(cm) if len(cm) else None, len(cm),
+                                                 _lib.ptr(ci) if count else None, _lib.ptr(ki) if count else None,
+                                                 _lib.ptr(ys) if count else None, _lib.ptr(pf) if count else None, count, int(n), l,
+                                                 None if rp is None or count == 0 else _lib.ptr(rp), _g2_arg(g2_tau_l), C.byref(ok))
+    _raise_for(rc, ctx)
+    return bool(ok.value)
+
+
+def verify_multiproof(commitment, proof, coset_index: int, ys, n: int, srs, g2_tau_l=None, ctx=None) -> bool:
+    """One coset proof (`kzg_verify_multiproof`): e(proof, [tau^l]_2 - [w^(k l)]G2) = e(C - [I_k(tau)]_1, G2) with I_k the polynomial
+    through the l values `ys` on coset `coset_index`.  For l = 1 this is `verify_proof(commitment, proof, ys[0], w^k)`."""
+    ys = np.ascontiguousarray(_lib.as_u64(ys, 0)).reshape(-1, 4)
+    if g2_tau_l is None and len(ys) != 1:
+        raise GenericError("g2_tau_l = None (consts::G2_TAU) is [tau]_2: chunks of more than one point need [tau^l]_2")
+    ctx = ctx or getattr(srs, "ctx", None) or _lib.default_context()
+    ok = _lib.i32(0)
+    rc = _lib.load().kzg_verify_multiproof(ctx.handle, srs.handle, _lib.ptr(_lib.as_u64(commitment, 0).reshape(8)),
+                                           _lib.ptr(_lib.as_u64(proof, 0).reshape(8)), int(coset_index), _lib.ptr(ys), int(n), len(ys),
+                                           _g2_arg(g2_tau_l), C.byref(ok))
+    _raise_for(rc, ctx)
+    return bool(ok.value)
