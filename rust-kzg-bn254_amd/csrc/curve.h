@@ -110,7 +110,11 @@ KZG_HD void xyzz_madd_exceptional(Xyzz& acc, const Fq& x2, const Fq& y2s, const 
 }
 
 // acc += (neg ? -p : p), p affine and NOT the identity (callers skip identity bases).   madd-2008-s
-template <bool INLINE_SLOW = false>
+// CHECKED = false leaves the test for P == +-Q (PP == 0 mod m) out: the formulas then give ZZ3 = ZZ1 PP == 0, and since the field has
+// no zero divisors and a sum starts from ZZ = 1, the ZZ of a sum of such additions is == 0 mod m if and only if one of them met
+// P == +-Q.  The caller tests that once per finished sum (fe_is_zero_mod(acc.zz)) and recomputes the sum with the checked form
+// (k_msm_accumulate, msm_kernels.h); until then a tainted value must not be stored: a literally zero ZZ is the stored identity.
+template <bool INLINE_SLOW = false, bool CHECKED = true>
 KZG_HD void xyzz_madd(Xyzz& acc, const Affine& p, uint32_t neg) {
     if (acc.inf) { xyzz_from_affine(acc, p, neg); return; }
     Fq y2s, u2, s2, pp_, rr_, P, R, ppp, q, t, v;
@@ -129,7 +133,7 @@ KZG_HD void xyzz_madd(Xyzz& acc, const Affine& p, uint32_t neg) {
     fe_sqr(pp_, P);                            // 81 m^2 < 169 m^2
     fe_sqr(rr_, R);
 #endif
-    if (__builtin_expect(fe_is_zero_mod(pp_), 0)) { xyzz_madd_exceptional<INLINE_SLOW>(acc, p.x, y2s, rr_); return; }
+    if (CHECKED && __builtin_expect(fe_is_zero_mod(pp_), 0)) { xyzz_madd_exceptional<INLINE_SLOW>(acc, p.x, y2s, rr_); return; }
 #if defined(KZG_MADD_PAIRED)
     fe_mul2(ppp, P, pp_, q, acc.x, pp_);
 #else
@@ -208,6 +212,14 @@ KZG_HD void xyzz_store(int32_t* __restrict__ base, size_t stride, size_t i, cons
     for (int q = 0; q < 4; ++q)
 #pragma unroll
         for (int j = 0; j < NL; ++j) base[(size_t)(q * NL + j) * stride + i] = v.inf ? 0 : c[q]->l[j];
+}
+// the same for a value whose limbs are literal zeros whenever `inf` is set (xyzz_set_inf): no select per limb
+KZG_HD void xyzz_store_zeroed(int32_t* __restrict__ base, size_t stride, size_t i, const Xyzz& v) {
+    const Fq* c[4] = {&v.x, &v.y, &v.zz, &v.zzz};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int j = 0; j < NL; ++j) base[(size_t)(q * NL + j) * stride + i] = c[q]->l[j];
 }
 KZG_HD void xyzz_load(Xyzz& v, const int32_t* __restrict__ base, size_t stride, size_t i) {
     Fq* c[4] = {&v.x, &v.y, &v.zz, &v.zzz};

@@ -148,6 +148,10 @@ struct kzg_srs {
     int small_W = 0;
     // per-bit tables Bit_j[i] = 2^j P_i, j < 255, n points apart (srs.hip srs_build_bit_tables): the NAF mode of MSMs of >= SRS_NAF_MIN pairs; may be absent
     uint4* d_bits = nullptr;
+    // no point of this SRS is the identity (srs.hip srs_precompute counts them before it builds the tables; a doubled identity is the
+    // identity, so the one flag covers every table): the accumulate kernel of its MSMs then runs without the per-entry identity test.
+    // false = unknown or some: the test stays
+    bool identity_free = false;
     // 3 Bit_p[j] for p < 255, j < 256 (g1fft.hip: the x3 tables of the 64..256-point g1_ifft), built on first use; a cache, hence mutable
     mutable uint4* d_t3 = nullptr;
     mutable uint32_t t3_n = 0;           // points covered by d_t3: min(n, 2048)
@@ -171,6 +175,7 @@ struct MsmBases {
     int W = 0;
     bool bitsum = false;  // tiny MSM: `points` = the per-bit tables, summed directly (k_bitsum_level1 / 2, msm_kernels.h section 6e)
     bool naf = false;     // `points` = the per-bit tables (Bit_j[i] = 2^j P_i, j < 255, table_stride points apart): width-(c + 1) NAF digits
+    bool identity_free = false;   // known: none of the points (of any table) is the identity (kzg_srs::identity_free; caller bases: unknown)
 };
 constexpr int SRS_SMALL_C = 15;                       // window bits of the second table set
 constexpr size_t SRS_SMALL_MAX = (size_t)1 << 13;     // MSMs of up to this many pairs use it
@@ -195,6 +200,7 @@ inline MsmBases srs_bases(const kzg_srs* srs, size_t offset, size_t n, bool allo
     MsmBases b;
     std::lock_guard<std::mutex> lk(srs->lazy_mu);
     b.points = srs->d_points + 4 * offset;
+    b.identity_free = srs->identity_free;
     if (allow_tables && srs->pre_W > 0) {
         b.table_stride = (uint32_t)srs->n; b.c = srs->pre_c; b.W = srs->pre_W;
         if (srs->d_small && n <= SRS_SMALL_MAX) { b.points = srs->d_small + 4 * offset; b.c = srs->small_c; b.W = srs->small_W; }

@@ -477,8 +477,11 @@ static int32_t msm_enqueue(kzg_ctx* ctx, MsmWorkspace& ws, hipStream_t st, const
     const bool fused = p.tables && !p.naf && (double)entries <= 2.5 * (double)p.B;
     p.fused = fused;
     // (64- and 128-thread workgroups measured the same as 256)
-    if (!fused)
-        hipLaunchKernelGGL(k_msm_accumulate, dim3(p.nl / 256), dim3(256), 0, st, bases.points, ws.sorted.as<uint32_t>(), d_offs, p.G,
+    if (!fused && bases.identity_free)
+        hipLaunchKernelGGL(k_msm_accumulate<false>, dim3(p.nl / 256), dim3(256), 0, st, bases.points, ws.sorted.as<uint32_t>(), d_offs, p.G,
+                           ws.head.as<int32_t>(), (size_t)p.G, ws.cont.as<int32_t>(), (size_t)p.nl, p.idx_log, p.stride_adj);
+    else if (!fused)                                        // (a set with an identity point, or caller bases: every entry is tested)
+        hipLaunchKernelGGL(k_msm_accumulate<true>, dim3(p.nl / 256), dim3(256), 0, st, bases.points, ws.sorted.as<uint32_t>(), d_offs, p.G,
                            ws.head.as<int32_t>(), (size_t)p.G, ws.cont.as<int32_t>(), (size_t)p.nl, p.idx_log, p.stride_adj);
     KZG_MARK(5);
     phases.begin("kzg:msm:bucket reduction");
@@ -916,6 +919,16 @@ int32_t msm_run_batch_tables(kzg_ctx* ctx, const MsmBases& bases, const void* d_
 }
 
 }  // namespace kzg
+
+#if defined(KZG_TEST_HOOKS)           // libkzg_bn254_mi355x_hooks.so only (make hooks; tests/test_gpu_accumulate_replay.py)
+// partial sums that k_msm_accumulate recomputed with the checked addition since the last reset (device-wide; call with no MSM in flight)
+extern "C" int kzg_test_acc_replays(unsigned long long* out, int reset) {
+    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(kzg::g_acc_replays), sizeof(unsigned long long)) != hipSuccess) return -1;
+    const unsigned long long zero = 0;
+    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(kzg::g_acc_replays), &zero, sizeof(zero)) != hipSuccess) return -1;
+    return 0;
+}
+#endif
 
 #if defined(KZG_DEVICE_BOUND_CHECK)   // the device bound-check variant only (field29.h, `make boundcheck`)
 #include "field29.h"

@@ -779,6 +779,31 @@ __device__ __forceinline__ size_t acc_point_index(uint32_t ix, uint32_t idx_log,
 #ifndef KZG_ACC_WAVES
 #define KZG_ACC_WAVES 3        // waves per SIMD (<= 168 VGPRs); 4 (128 VGPRs, more spills) measured equal in round 1
 #endif
+#ifdef KZG_TEST_HOOKS          // hooks build only: partial sums recomputed by acc_replay (read and reset through kzg_test_acc_replays, msm.hip)
+__device__ unsigned long long g_acc_replays;
+#endif
+// The accumulate loop adds with the UNCHECKED mixed addition (curve.h xyzz_madd<.., false>): no test for P == +-Q per entry.  A partial
+// that met such a pair ends with ZZ == 0 mod m; flush() sees that once per finished partial and calls this: the same entries
+// [lo, hi) of the sorted array again, with the checked addition.  Out of line, plain loads: rare by construction (two equal or
+// opposite table points in one bucket of one lane), so its code and registers stay out of the loop.
+__device__ __noinline__ Xyzz acc_replay(const uint4* __restrict__ points, const uint32_t* __restrict__ sorted, uint32_t lo, uint32_t hi, uint32_t idx_log, uint32_t stride_adj) {
+    Xyzz r;
+    xyzz_set_inf(r);
+#pragma unroll 1
+    for (uint32_t e = lo; e < hi; ++e) {
+        const uint32_t v = sorted[e];
+        Affine p;
+        if (!affine_load(p, points + 4 * acc_point_index(KZG_ACC_IDX(v), idx_log, stride_adj))) continue;     // identity base
+        xyzz_madd<true>(r, p, v >> 31);
+    }
+#ifdef KZG_TEST_HOOKS
+    atomicAdd(&g_acc_replays, 1ull);
+#endif
+    return r;
+}
+// IDENTITY_BASES = false: the caller knows that no base point of the table set is the identity (recorded when the set was built:
+// kzg_srs::identity_free), so the per-entry test of the 16 gathered words is left out.
+template <bool IDENTITY_BASES>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KZG_ACC_WAVES, KZG_ACC_WAVES)))
 k_msm_accumulate(const uint4* __restrict__ points, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offs, uint32_t G,
                  int32_t* __restrict__ head, size_t head_stride, int32_t* __restrict__ cont, size_t cont_stride,
@@ -844,19 +869,29 @@ k_msm_accumulate(const uint4* __restrict__ points, const uint32_t* __restrict__ 
     uint32_t next2 = 0;                                // offs[g + 2], loaded ahead: no dependent load at a boundary
     if (active) next2 = offs[g + 2 <= G ? g + 2 : G];
     // the partial of bucket g is complete for this lane: `more` = the lane goes on into the next bucket
+    // In this kernel `acc.inf` implies that all limbs of acc are literal zeros (xyzz_set_inf at every start; the unchecked addition
+    // never sets inf; the checked one of acc_replay sets it through xyzz_set_inf), so a partial is parked / stored without selects.
     auto flush = [&](bool more) {
+        // a partial whose additions met P == +-Q (ZZ == 0 mod m, see acc_replay) is recomputed BEFORE it leaves the lane: in stored
+        // form a literally zero ZZ means the identity.  acc.zz is 1 or a product: normalised, in (-m, 2m)
+        if (__builtin_expect(!acc.inf && fe_is_zero_mod(acc.zz), 0)) {
+            const uint32_t o0 = offs[g], o1 = offs[g + 1];             // this lane's part of bucket g
+            acc = acc_replay(points, sorted, o0 > begin ? o0 : begin, o1 < end ? o1 : end, idx_log, stride_adj);
+        }
+        KZG_REQUIRE(!acc.inf || (fe_is_literal_zero(acc.x) && fe_is_literal_zero(acc.y) && fe_is_literal_zero(acc.zz) && fe_is_literal_zero(acc.zzz)),
+                    KZG_SITE_IS_ZERO_MOD, "k_msm_accumulate: inf without zero limbs", acc.zz);
         const bool as_cont = is_cont && g == g0;
         if (more && !parked) {
             const Fq* c4[4] = {&acc.x, &acc.y, &acc.zz, &acc.zzz};
 #pragma unroll
             for (int q = 0; q < 4; ++q)
 #pragma unroll
-                for (int j = 0; j < NL; ++j) park[(q * NL + j) * 256 + tl] = acc.inf ? 0 : c4[q]->l[j];
+                for (int j = 0; j < NL; ++j) park[(q * NL + j) * 256 + tl] = c4[q]->l[j];
             parked = true; parked_cont = as_cont; park_g = g;
         } else if (!as_cont) {
-            xyzz_store(head, head_stride, g, acc);
+            xyzz_store_zeroed(head, head_stride, g, acc);
         } else if (!long_run || more) {
-            xyzz_store(cont, cont_stride, t, acc);
+            xyzz_store_zeroed(cont, cont_stride, t, acc);
         } else {
             cont_in_regs = true;                       // kept in registers for the segmented scan below
         }
@@ -873,8 +908,10 @@ k_msm_accumulate(const uint4* __restrict__ points, const uint32_t* __restrict__ 
         const uint32_t last = end - 1;
         uint32_t v = sorted[begin];
         uint32_t v1 = sorted[begin + 1 < end ? begin + 1 : last];
-        const uint4* src = points + 4 * acc_point_index(KZG_ACC_IDX(v), idx_log, stride_adj);
-        uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4* const pts = reinterpret_cast<const u32x4*>(points);
+        const u32x4* src = pts + 4 * acc_point_index(KZG_ACC_IDX(v), idx_log, stride_adj);
+        u32x4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
         for (uint32_t e = begin; e < end; ++e) {
 #ifdef KZG_ACC_STAMPS
             const bool any_cross = __any(e == next);
@@ -892,6 +929,9 @@ k_msm_accumulate(const uint4* __restrict__ points, const uint32_t* __restrict__ 
             if (any_cross) { flush_ticks += __builtin_amdgcn_s_memrealtime() - f0; flush_events += 1; }
 #endif
             const uint32_t neg = v >> 31;
+            // the point of entry e as four whole 128-bit registers: without the identity test nothing reads the 16 words together, and the
+            // compiler would regroup the gather into five loads of 8-byte alignment (no instruction is emitted here)
+            asm("" : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3));
             uint32_t wx[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
             uint32_t wy[8] = {q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
             const uint32_t any = q0.x | q0.y | q0.z | q0.w | q1.x | q1.y | q1.z | q1.w | q2.x | q2.y | q2.z | q2.w | q3.x | q3.y | q3.z | q3.w;
@@ -899,11 +939,11 @@ k_msm_accumulate(const uint4* __restrict__ points, const uint32_t* __restrict__ 
             fe_unpack(p.x, wx);
             fe_unpack(p.y, wy);
             v = v1;                                    // entry e + 1 (the last iteration re-reads entry `last`: unused)
-            src = points + 4 * acc_point_index(KZG_ACC_IDX(v), idx_log, stride_adj);
+            src = pts + 4 * acc_point_index(KZG_ACC_IDX(v), idx_log, stride_adj);
             q0 = src[0]; q1 = src[1]; q2 = src[2]; q3 = src[3];
             v1 = sorted[e + 2 < end ? e + 2 : last];
-            if (any == 0) continue;                                                       // identity base
-            xyzz_madd<true>(acc, p, neg);
+            if (IDENTITY_BASES && any == 0) continue;                                     // identity base
+            xyzz_madd<true, false>(acc, p, neg);                                          // unchecked: flush() looks at ZZ
         }
         flush(false);
     }

@@ -343,6 +343,16 @@ k_points_device_to_wire(const uint4* __restrict__ in, uint4* __restrict__ out, s
     out[4 * i + 3] = make_uint4(o[12], o[13], o[14], o[15]);
 }
 
+// *count += the identity points (all 16 words zero) among n device-format points
+__global__ void __launch_bounds__(256)
+k_srs_count_identity(const uint4* __restrict__ in, size_t n, uint32_t* __restrict__ count) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4 a = in[4 * i], b = in[4 * i + 1], c = in[4 * i + 2], d = in[4 * i + 3];
+    const uint32_t any = a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w | c.x | c.y | c.z | c.w | d.x | d.y | d.z | d.w;
+    if (any == 0) atomicAdd(count, 1u);
+}
+
 int32_t srs_generate(kzg_ctx* ctx, const uint64_t tau[4], uint64_t first_power, size_t n, uint4* d_points) {
     if (n == 0) return KZG_OK;
     KZG_HIP_TRY(ctx, ctx->poly[0].a.reserve(n * 32 + 64));
@@ -361,8 +371,23 @@ int32_t srs_generate(kzg_ctx* ctx, const uint64_t tau[4], uint64_t first_power, 
 // Window tables T_w = 2^(c w) * SRS for w < W, contiguous after the SRS itself.  Spends HBM capacity (W x 64 B per
 // point: 0.94 GiB for 2^20 points at c = 17) to turn the MSM into W n mixed adds into a single bucket set.
 int32_t srs_precompute(kzg_ctx* ctx, kzg_srs* srs) {
-    if (opt_no_precompute()) return KZG_OK;
     const size_t n = srs->n;
+    if (n) {                                     // one pass over the points, once per SRS: kzg_srs::identity_free
+        uint32_t* d_count = nullptr;             // (its own word: the scratch of the slots may be in use by calls in flight)
+        uint32_t identities = 1;
+        KZG_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d_count), 4));
+        hipError_t e = hipMemsetAsync(d_count, 0, 4, ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_srs_count_identity, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, srs->d_points, n, d_count);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(&identities, d_count, 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        (void)hipFree(d_count);
+        if (e != hipSuccess) return set_error(ctx, e, "counting the identity points of the SRS");
+        srs->identity_free = identities == 0;
+    }
+    if (opt_no_precompute()) return KZG_OK;
     if (n < 128) return KZG_OK;
     int lg = 0;
     while ((n >> (lg + 1)) != 0) ++lg;
