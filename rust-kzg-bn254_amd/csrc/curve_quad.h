@@ -236,5 +236,56 @@ __device__ __forceinline__ void quad_shfl(QuadXyzz& r, const QuadXyzz& h, int sr
     r.inf = __shfl((int)h.inf, src, 64) != 0;
 }
 
+// ---- lane groups: what a kernel written once for both forms needs to know (msm_kernels.h section 6c) -----------------------------
+// One point per LANES adjacent lanes, GROUPS points per wave; `role` is what a lane holds of its point and goes to every primitive.
+// The kernel constants are those of the bucket-reduction kernels: 64 values per workgroup in both forms.
+#ifndef KZG_PAIR_WAVES
+#define KZG_PAIR_WAVES 3       // waves per SIMD of the pair kernels (3: <= 168 VGPRs, a wave fits beside two accumulate waves of the other MSM in flight)
+#endif
+#ifndef KZG_QUAD_SMALL_WAVES
+#define KZG_QUAD_SMALL_WAVES 4     // waves per SIMD the small quad launches are compiled for (128 VGPRs with a few spills; 2 = no spills measured the same or 5 % slower)
+#endif
+// the superset-sum transforms of 64 values (msm_kernels.h 6c, which defines them inline; declared plainly here for the units that never use them)
+__device__ void group_zeta64(HalfXyzz& v, uint32_t lane, uint32_t w, bool odd, int32_t* __restrict__ lds);
+__device__ void group_zeta64q(QuadXyzz& v, uint32_t lane, uint32_t w, uint32_t q, int32_t* __restrict__ lds);
+struct PairLanes {
+    using Point = HalfXyzz;
+    using Role = bool;                                   // odd lane
+    static constexpr uint32_t LANES = 2, GROUPS = 64 / LANES, LOG_GROUPS = 5;
+    static constexpr int THREADS = 128, WAVES = KZG_PAIR_WAVES;
+    static constexpr int ZETA_LDS_WORDS = 2 * NL * 64;
+    static constexpr uint32_t FUSED_HEAVY = 12;          // (24 while the groups held neighbouring buckets: the ~100 heavy buckets of a blob's top window then sat in two workgroups)
+    static __device__ __forceinline__ Role role(uint32_t lane) { return (lane & 1u) != 0; }
+    static __device__ __forceinline__ int affine_half(Role r) { return r ? 2 : 0; }           // the uint4 of an affine point (x: 0, y: 2) the lane's mixed addition takes
+    static __device__ __forceinline__ void set_inf(Point& h) { half_set_inf(h); }
+    static __device__ __forceinline__ void load(Point& h, const int32_t* __restrict__ base, size_t stride, size_t i, Role r) { half_load(h, base, stride, i, r); }
+    static __device__ __forceinline__ void store(int32_t* __restrict__ base, size_t stride, size_t i, const Point& h, Role r) { half_store(base, stride, i, h, r); }
+    static __device__ __forceinline__ void store_wire(uint32_t* __restrict__ out_wire, size_t i, const Point& h, Role r) { half_store_wire(out_wire, i, h, r); }
+    static __device__ __forceinline__ void add(Point& r, const Point& a, const Point& b, Role role) { pair_add(r, a, b, role); }
+    static __device__ __forceinline__ void madd(Point& r, const Point& acc, const Fq& c, uint32_t neg, Role role) { pair_madd(r, acc, c, neg, role); }
+    static __device__ __forceinline__ void shfl_down(Point& r, const Point& h, int d) { half_shfl_down(r, h, d); }
+    static __device__ __forceinline__ void shfl(Point& r, const Point& h, int src) { half_shfl(r, h, src); }
+    static constexpr auto& zeta64 = group_zeta64;        // zeta64(v, lane, w, role, lds).  The function itself, not a wrapper: one more level of inlining moved the kernels' code
+};
+struct QuadLanes {
+    using Point = QuadXyzz;
+    using Role = uint32_t;                               // lane & 3
+    static constexpr uint32_t LANES = 4, GROUPS = 64 / LANES, LOG_GROUPS = 4;
+    static constexpr int THREADS = 256, WAVES = KZG_QUAD_SMALL_WAVES;
+    static constexpr int ZETA_LDS_WORDS = (NL + 1) * 256;
+    static constexpr uint32_t FUSED_HEAVY = 8;           // 16 quads share a heavy bucket
+    static __device__ __forceinline__ Role role(uint32_t lane) { return lane & 3u; }
+    static __device__ __forceinline__ int affine_half(Role r) { return (r & 1u) ? 2 : 0; }
+    static __device__ __forceinline__ void set_inf(Point& h) { quad_set_inf(h); }
+    static __device__ __forceinline__ void load(Point& h, const int32_t* __restrict__ base, size_t stride, size_t i, Role r) { quad_load(h, base, stride, i, r); }
+    static __device__ __forceinline__ void store(int32_t* __restrict__ base, size_t stride, size_t i, const Point& h, Role r) { quad_store(base, stride, i, h, r); }
+    static __device__ __forceinline__ void store_wire(uint32_t* __restrict__ out_wire, size_t i, const Point& h, Role r) { quad_store_wire(out_wire, i, h, r); }
+    static __device__ __forceinline__ void add(Point& r, const Point& a, const Point& b, Role role) { quad_add(r, a, b, role); }
+    static __device__ __forceinline__ void madd(Point& r, const Point& acc, const Fq& c, uint32_t neg, Role role) { quad_madd(r, acc, c, neg, role); }
+    static __device__ __forceinline__ void shfl_down(Point& r, const Point& h, int d) { quad_shfl_down(r, h, d); }
+    static __device__ __forceinline__ void shfl(Point& r, const Point& h, int src) { quad_shfl(r, h, src); }
+    static constexpr auto& zeta64 = group_zeta64q;
+};
+
 }  // namespace kzg
 #endif

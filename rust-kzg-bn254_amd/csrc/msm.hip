@@ -471,7 +471,7 @@ static int32_t msm_enqueue(kzg_ctx* ctx, MsmWorkspace& ws, hipStream_t st, const
     phases.begin("kzg:msm:accumulate");
     // the two reduction levels run on lane pairs (curve_pair.h; one 128-thread workgroup per 64 buckets, then per two groups of 64 sums) or lane quads
     // sparse table-mode MSMs (at most 2.5 entries per bucket on average: commitments of <= 2^11 coefficients on
-    // the c = 15 tables): the first reduction level adds the entries itself (k_msm_bucket_bits1p_fused), there is no accumulate kernel and
+    // the c = 15 tables): the first reduction level adds the entries itself (k_msm_bucket_bits1_fused), there is no accumulate kernel and
     // there are no partial sums.  Measured (tools/phases_small.py, same box, device time of one commitment): 2^8 170 -> 125 us, 2^9 163 -> 128,
     // 2^10 165 -> 152, 2^11 199 -> 195; at 2^12 (4.25 per bucket) 206 -> 261: a wave waits for its fullest bucket, the equal split does not.
     const bool fused = p.tables && !p.naf && (double)entries <= 2.5 * (double)p.B;
@@ -488,17 +488,17 @@ static int32_t msm_enqueue(kzg_ctx* ctx, MsmWorkspace& ws, hipStream_t st, const
     uint32_t n_out;                       // wire XYZZ values copied to the host
     if (p.tables) {
         if (fused && p.quad)
-            hipLaunchKernelGGL(k_msm_bucket_bits1q_fused, dim3(G1), dim3(256), 0, st, bases.points, ws.sorted.as<uint32_t>(), d_offs, p.B, p.idx_log,
+            hipLaunchKernelGGL(k_msm_bucket_bits1_fused<QuadLanes>, dim3(G1), dim3(QuadLanes::THREADS), 0, st, bases.points, ws.sorted.as<uint32_t>(), d_offs, p.B, p.idx_log,
                                p.stride_adj, G1, ws.chunkS.as<int32_t>(), (size_t)7 * G1, d_out);
         else if (fused)
-            hipLaunchKernelGGL(k_msm_bucket_bits1p_fused, dim3(G1), dim3(128), 0, st, bases.points, ws.sorted.as<uint32_t>(), d_offs, p.B, p.idx_log,
+            hipLaunchKernelGGL(k_msm_bucket_bits1_fused<PairLanes>, dim3(G1), dim3(PairLanes::THREADS), 0, st, bases.points, ws.sorted.as<uint32_t>(), d_offs, p.B, p.idx_log,
                                p.stride_adj, G1, ws.chunkS.as<int32_t>(), (size_t)7 * G1, d_out);
         else if (p.quad && (G1 <= 512 || ctx->reduction_lanes == 4))
             // (at 2^16 buckets the level is 4 096 quad waves of ~11 000 instructions: throughput bound, 0.121 against 0.114 ms on pairs)
-            hipLaunchKernelGGL(k_msm_bucket_bits1q, dim3(G1), dim3(256), 0, st, d_offs, p.B, p.nl, ws.head.as<int32_t>(), (size_t)p.G,
+            hipLaunchKernelGGL(k_msm_bucket_bits1<QuadLanes>, dim3(G1), dim3(QuadLanes::THREADS), 0, st, d_offs, p.B, p.nl, ws.head.as<int32_t>(), (size_t)p.G,
                                ws.cont.as<int32_t>(), (size_t)p.nl, G1, ws.chunkS.as<int32_t>(), (size_t)7 * G1, d_out);
         else
-            hipLaunchKernelGGL(k_msm_bucket_bits1p, dim3(G1), dim3(128), 0, st, d_offs, p.B, p.nl, ws.head.as<int32_t>(), (size_t)p.G,
+            hipLaunchKernelGGL(k_msm_bucket_bits1<PairLanes>, dim3(G1), dim3(PairLanes::THREADS), 0, st, d_offs, p.B, p.nl, ws.head.as<int32_t>(), (size_t)p.G,
                                ws.cont.as<int32_t>(), (size_t)p.nl, G1, ws.chunkS.as<int32_t>(), (size_t)7 * G1, d_out);
         KZG_MARK(6);
         if (p.polys && p.c == 7) {

@@ -1016,12 +1016,15 @@ __device__ __forceinline__ BucketSpan bucket_span(const uint32_t* __restrict__ o
     s.np = 1 + (s.long_run ? 1 + (t2 / 64 - (s.t1 + 1) / 64) : r);
     return s;
 }
+// partial k >= 1 of a bucket is cont[] of this accumulate lane (partial 0 is head[g])
+__device__ __forceinline__ uint32_t bucket_cont_lane(const BucketSpan& s, uint32_t k) {
+    const uint32_t first = s.t1 + 1;
+    return !s.long_run ? s.t1 + k : (k == 1 ? first : (first / 64 + (k - 1)) * 64);
+}
 __device__ __forceinline__ void bucket_partial(Xyzz& v, const BucketSpan& s, uint32_t k, const int32_t* __restrict__ head, size_t head_stride,
                                                const int32_t* __restrict__ cont, size_t cont_stride) {
     if (k == 0) { xyzz_load(v, head, head_stride, s.g); return; }
-    const uint32_t first = s.t1 + 1;
-    const uint32_t t = !s.long_run ? s.t1 + k : (k == 1 ? first : (first / 64 + (k - 1)) * 64);
-    xyzz_load(v, cont, cont_stride, t);
+    xyzz_load(v, cont, cont_stride, bucket_cont_lane(s, k));
 }
 // Sum of all partials of this lane's bucket.  Buckets with up to NP_SERIAL partials are summed by their lane; heavier ones
 // (skewed scalars: few distinct digits) one after the other by the whole wave (lanes take partials round-robin, then a
@@ -1207,77 +1210,17 @@ __device__ __forceinline__ void xyzz_store_wire(uint32_t* __restrict__ out_wire,
     for (int j = 0; j < 32; j += 4) *reinterpret_cast<uint4*>(out_wire + i * 32 + j) = make_uint4(w[j], w[j + 1], w[j + 2], w[j + 3]);
 }
 // (the one-lane kernels of this form -- one wave per group of 64 buckets, X1[role * G1 + g]: role k < 6 = S_k, role 6 = T; then one launch that finishes
-// bits 0..5 and transforms the group totals -- were the round-1 reduction; the lane-pair and lane-quad kernels below replaced them: history section 4b)
+// bits 0..5 and transforms the group totals -- were the round-1 reduction; the lane-group kernels below replaced them: history section 4b)
 // -------------------------------------------------------------------------------------------------
-// 6c. the same two reduction levels on LANE PAIRS (curve_pair.h): one point per pair of lanes, 7 multiplications per lane and
-//     addition instead of 14; 64 values = one workgroup of two waves (32 pairs each).  Same inputs, same X1 / out_wire layout
-//     and the same group elements as the one-lane form of 6b.
+// 6c. the first of the same two reduction levels on LANE GROUPS: one point per LG::LANES adjacent lanes, written ONCE over the traits
+//     PairLanes / QuadLanes (end of curve_quad.h) and instantiated for both.  Same inputs, same X1 / out_wire layout and the same
+//     group elements as the one-lane form of 6b; 64 values = one workgroup either way.
+//       <PairLanes>  curve_pair.h: 7 multiplications per lane and addition instead of 14; two waves of 32 pairs.
+//       <QuadLanes>  curve_quad.h: four instead of seven, four waves of 16 quads: ~0.7 of the pair form's dependent instructions at
+//                    twice its lanes: used when no other MSM is in flight (then latency is everything and the SIMDs are idle anyway;
+//                    kzg_ctx_set_reduction_lanes(ctx, 2): always the pair kernels).
+//     Only the two superset-sum transforms are written per form (LG::zeta64 names them): their steps across waves differ.
 // -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void bucket_partial_half(HalfXyzz& v, const BucketSpan& s, uint32_t k, const int32_t* __restrict__ head, size_t head_stride,
-                                                    const int32_t* __restrict__ cont, size_t cont_stride, bool odd) {
-    if (k == 0) { half_load(v, head, head_stride, s.g, odd); return; }
-    const uint32_t first = s.t1 + 1;
-    const uint32_t t = !s.long_run ? s.t1 + k : (k == 1 ? first : (first / 64 + (k - 1)) * 64);
-    half_load(v, cont, cont_stride, t, odd);
-}
-// A heavy bucket (more than NP_SERIAL partials: skewed scalars, few distinct digits), summed by the 32 pairs of the wave: pair p
-// takes the partials p, p + 32, ..; then a 5-step tree; every lane returns the sum.  Out of line: rare, and its registers (a second
-// running sum) stay out of the kernel's budget.  ONE addition site for both phases.
-__device__ __noinline__ void bucket_sum_heavy_pairs(HalfXyzz& tot, uint32_t g, uint32_t t1, uint32_t np, uint32_t long_run, uint32_t lane,
-                                                    const int32_t* __restrict__ head, size_t head_stride, const int32_t* __restrict__ cont, size_t cont_stride) {
-    const uint32_t pair = lane >> 1;
-    const bool odd = (lane & 1u) != 0;
-    BucketSpan h;
-    h.g = g; h.t1 = t1; h.np = np; h.long_run = long_run != 0;
-    HalfXyzz part;
-    half_set_inf(part);
-    const uint32_t loads = (np + 31) / 32;
-#pragma unroll 1
-    for (uint32_t step = 0; step < loads + 5; ++step) {
-        HalfXyzz u;
-        bool on;
-        if (step < loads) {
-            const uint32_t k = pair + 32 * step;
-            on = k < np;
-            if (on) bucket_partial_half(u, h, k, head, head_stride, cont, cont_stride, odd);
-        } else {
-            const uint32_t d = 16u >> (step - loads);
-            half_shfl_down(u, part, (int)(2 * d));
-            on = pair < d;
-        }
-        if (on) {
-            HalfXyzz r;
-            pair_add(r, part, u, odd);
-            part = r;
-        }
-    }
-    half_shfl(tot, part, odd ? 1 : 0);                 // pair 0 holds the sum
-}
-// Sum of all partials of this PAIR's bucket (s is the same in both lanes of the pair).  Buckets with up to NP_SERIAL partials are
-// summed by their pair; heavier ones one after the other by the whole wave.  Every lane of the wave must call this.
-__device__ __forceinline__ void bucket_sum_pairs(HalfXyzz& acc, const BucketSpan& s, uint32_t lane, bool odd, const int32_t* __restrict__ head,
-                                                 size_t head_stride, const int32_t* __restrict__ cont, size_t cont_stride) {
-    half_set_inf(acc);
-    const bool heavy = s.np > NP_SERIAL;
-    if (!heavy) {
-#pragma unroll 1
-        for (uint32_t k = 0; k < s.np; ++k) {
-            HalfXyzz v, r;
-            bucket_partial_half(v, s, k, head, head_stride, cont, cont_stride, odd);
-            pair_add(r, acc, v, odd);
-            acc = r;
-        }
-    }
-    unsigned long long todo = __ballot(heavy && !odd);  // one bit per heavy pair (its even lane)
-    while (todo) {                                     // wave-uniform
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        HalfXyzz tot;
-        bucket_sum_heavy_pairs(tot, __shfl(s.g, src, 64), __shfl(s.t1, src, 64), __shfl(s.np, src, 64), (uint32_t)__shfl((int)s.long_run, src, 64), lane,
-                               head, head_stride, cont, cont_stride);
-        if ((int)(lane & ~1u) == src) acc = tot;
-    }
-}
 // Superset-sum transform over the 64 values of a two-wave group, value gp = 32 w + pair: afterwards gp = 0 holds the total and
 // gp = 2^k the sum over the values whose index has bit k set.  Steps 0..4 inside the wave, step 5 through LDS (wave 1 publishes,
 // wave 0 adds).  Called by every lane of both waves (one barrier inside).
@@ -1308,57 +1251,151 @@ __device__ __forceinline__ void group_zeta64(HalfXyzz& v, uint32_t lane, uint32_
         }
     }
 }
-#ifndef KZG_PAIR_WAVES
-#define KZG_PAIR_WAVES 3       // waves per SIMD of the pair kernels (3: <= 168 VGPRs, a wave fits beside two accumulate waves of the other MSM in flight)
-#endif
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(KZG_PAIR_WAVES, KZG_PAIR_WAVES)))
-k_msm_bucket_bits1p(const uint32_t* __restrict__ offs, uint32_t B, uint32_t nl, const int32_t* __restrict__ head, size_t head_stride,
-                    const int32_t* __restrict__ cont, size_t cont_stride, uint32_t G1, int32_t* __restrict__ x1, size_t x_stride,
-                    uint32_t* __restrict__ out_wire /* G1 == 1 only */) {
+// Superset-sum transform over the 64 values of a four-wave group, value gp = 16 w + quad: afterwards gp = 0 holds the total and
+// gp = 2^k the sum over the values whose index has bit k set.  Steps 0..3 inside the wave, steps 4 and 5 through LDS (the waves whose
+// index has the bit set publish, the others add).  Called by every lane of the four waves (four barriers inside).
+__device__ __forceinline__ void group_zeta64q(QuadXyzz& v, uint32_t lane, uint32_t w, uint32_t q, int32_t* __restrict__ lds /* (NL + 1) x 256 words */) {
+    const uint32_t quad = lane >> 2, tid = w * 64 + lane;
+#pragma unroll 1
+    for (int k = 0; k < 6; ++k) {                      // one addition site for the six steps
+        QuadXyzz u;
+        bool on;
+        if (k < 4) {
+            quad_shfl_down(u, v, 4 << k);
+            on = ((quad >> k) & 1u) == 0;
+        } else {
+            const uint32_t bit = 1u << (k - 4);
+            if (k == 5) __syncthreads();               // step 4's readers are done
+            if (w & bit) {
+#pragma unroll
+                for (int j = 0; j < NL; ++j) lds[j * 256 + tid] = v.c.l[j];
+                lds[NL * 256 + tid] = v.inf ? 1 : 0;
+            }
+            __syncthreads();
+            on = (w & bit) == 0;
+            const uint32_t src = tid + 64 * bit;
+            if (on) {
+#pragma unroll
+                for (int j = 0; j < NL; ++j) u.c.l[j] = lds[j * 256 + src];
+                u.inf = lds[NL * 256 + src] != 0;
+            }
+        }
+        if (on) {
+            QuadXyzz r;
+            quad_add(r, v, u, q);
+            v = r;
+        }
+    }
+}
+
+template <class LG>
+__device__ __forceinline__ void bucket_partial_lanes(typename LG::Point& v, const BucketSpan& s, uint32_t k, const int32_t* __restrict__ head, size_t head_stride,
+                                                     const int32_t* __restrict__ cont, size_t cont_stride, typename LG::Role role) {
+    if (k == 0) { LG::load(v, head, head_stride, s.g, role); return; }
+    LG::load(v, cont, cont_stride, bucket_cont_lane(s, k), role);
+}
+// A heavy bucket (more than NP_SERIAL partials: skewed scalars, few distinct digits), summed by the GROUPS lane groups of the wave: group p
+// takes the partials p, p + GROUPS, ..; then a log2(GROUPS)-step tree; every lane returns the sum.  Out of line: rare, and its registers (a
+// second running sum) stay out of the kernel's budget.  ONE addition site for both phases.
+template <class LG>
+__device__ __noinline__ void bucket_sum_heavy(typename LG::Point& tot, uint32_t g, uint32_t t1, uint32_t np, uint32_t long_run, uint32_t lane,
+                                              const int32_t* __restrict__ head, size_t head_stride, const int32_t* __restrict__ cont, size_t cont_stride) {
+    const uint32_t grp = lane / LG::LANES;
+    const typename LG::Role role = LG::role(lane);
+    BucketSpan h;
+    h.g = g; h.t1 = t1; h.np = np; h.long_run = long_run != 0;
+    typename LG::Point part;
+    LG::set_inf(part);
+    const uint32_t loads = (np + LG::GROUPS - 1) / LG::GROUPS;
+#pragma unroll 1
+    for (uint32_t step = 0; step < loads + LG::LOG_GROUPS; ++step) {
+        typename LG::Point u;
+        bool on;
+        if (step < loads) {
+            const uint32_t k = grp + LG::GROUPS * step;
+            on = k < np;
+            if (on) bucket_partial_lanes<LG>(u, h, k, head, head_stride, cont, cont_stride, role);
+        } else {
+            const uint32_t d = (LG::GROUPS / 2) >> (step - loads);
+            LG::shfl_down(u, part, (int)(LG::LANES * d));
+            on = grp < d;
+        }
+        if (on) {
+            typename LG::Point r;
+            LG::add(r, part, u, role);
+            part = r;
+        }
+    }
+    LG::shfl(tot, part, (int)(lane & (LG::LANES - 1)));     // group 0 holds the sum
+}
+// Sum of all partials of this lane GROUP's bucket (s is the same in all its lanes).  Buckets with up to NP_SERIAL partials are
+// summed by their group; heavier ones one after the other by the whole wave.  Every lane of the wave must call this.
+template <class LG>
+__device__ __forceinline__ void bucket_sum_lanes(typename LG::Point& acc, const BucketSpan& s, uint32_t lane, typename LG::Role role, const int32_t* __restrict__ head,
+                                                 size_t head_stride, const int32_t* __restrict__ cont, size_t cont_stride) {
+    LG::set_inf(acc);
+    const bool heavy = s.np > NP_SERIAL;
+    if (!heavy) {
+#pragma unroll 1
+        for (uint32_t k = 0; k < s.np; ++k) {
+            typename LG::Point v, r;
+            bucket_partial_lanes<LG>(v, s, k, head, head_stride, cont, cont_stride, role);
+            LG::add(r, acc, v, role);
+            acc = r;
+        }
+    }
+    unsigned long long todo = __ballot(heavy && (lane & (LG::LANES - 1)) == 0);   // one bit per heavy group (its first lane)
+    while (todo) {                                     // wave-uniform
+        const int src = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        typename LG::Point tot;
+        bucket_sum_heavy<LG>(tot, __shfl(s.g, src, 64), __shfl(s.t1, src, 64), __shfl(s.np, src, 64), (uint32_t)__shfl((int)s.long_run, src, 64), lane,
+                             head, head_stride, cont, cont_stride);
+        if ((int)(lane & ~(LG::LANES - 1)) == src) acc = tot;
+    }
+}
+template <class LG>
+__global__ void __launch_bounds__(LG::THREADS) __attribute__((amdgpu_waves_per_eu(LG::WAVES, LG::WAVES)))
+k_msm_bucket_bits1(const uint32_t* __restrict__ offs, uint32_t B, uint32_t nl, const int32_t* __restrict__ head, size_t head_stride,
+                   const int32_t* __restrict__ cont, size_t cont_stride, uint32_t G1, int32_t* __restrict__ x1, size_t x_stride,
+                   uint32_t* __restrict__ out_wire /* G1 == 1 only */) {
     latency_bound_kernel();
-    __shared__ int32_t lds[2 * NL * 64];
-    const uint32_t g = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63, gp = w * 32 + (lane >> 1);
-    const bool odd = (lane & 1u) != 0;
+    __shared__ int32_t lds[LG::ZETA_LDS_WORDS];
+    const uint32_t g = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63, gp = w * LG::GROUPS + lane / LG::LANES;
+    const typename LG::Role role = LG::role(lane);
     const uint32_t L = acc_seg_len(offs[B], nl);
     const uint32_t bkt = g * 64 + gp;
     BucketSpan s;
     s.g = bkt; s.t1 = 0; s.np = 0; s.long_run = false;
     if (bkt < B && L) s = bucket_span(offs, bkt, L);
-    HalfXyzz v;
-#ifdef KZG_PROBE_NOSUM          // diagnostic builds (tools/ab_reduce.sh): where does this kernel's time go
-    if (s.np) half_load(v, head, head_stride, s.g, odd); else half_set_inf(v);
-#else
-    bucket_sum_pairs(v, s, lane, odd, head, head_stride, cont, cont_stride);
-#endif
-#ifndef KZG_PROBE_NOZETA
-    group_zeta64(v, lane, w, odd, lds);
-#endif
-    const int role = zeta_role(gp);
-    if (role < 0) return;
-    if (G1 == 1) half_store_wire(out_wire, (size_t)role, v, odd);
-    else half_store(x1, x_stride, (size_t)role * G1 + g, v, odd);
+    typename LG::Point v;
+    bucket_sum_lanes<LG>(v, s, lane, role, head, head_stride, cont, cont_stride);
+    LG::zeta64(v, lane, w, role, lds);
+    const int zr = zeta_role(gp);
+    if (zr < 0) return;
+    if (G1 == 1) LG::store_wire(out_wire, (size_t)zr, v, role);
+    else LG::store(x1, x_stride, (size_t)zr * G1 + g, v, role);
 }
 // level 1 FUSED with the accumulation, for sparse MSMs (a few entries per bucket: commitments of <= 2^12 coefficients on the c = 15
-// tables): pair = bucket, it adds its own sorted entries with pair_madd (5 multiplications per lane and entry) -- no k_msm_accumulate,
-// no head / continuation partials to gather and sum -- then the zeta transform as above.  With ~2 entries per bucket the equal-split
-// accumulate kernel spent a binary search and 4 dependent one-lane mixed additions (57 us) to leave ~2 partials per bucket, which the
-// first level then added again (another ~30 us).
-// A HEAVY bucket of the fused level (more than FUSED_HEAVY entries: a short top window puts e.g. 256 of a 512-coefficient polynomial's
-// entries into one bucket of a small SRS's tables) is summed by the whole wave: pair p adds the entries hb + p, hb + p + 32, ..., a
-// five-level tree joins the 32 partial sums.  One pair walking it alone kept its wave -- and the launch -- waiting for 256 dependent
+// tables): lane group = bucket, it adds its own sorted entries with LG::madd (pairs: 5 multiplications per lane and entry) -- no
+// k_msm_accumulate, no head / continuation partials to gather and sum -- then the zeta transform as above.  With ~2 entries per bucket the
+// equal-split accumulate kernel spent a binary search and 4 dependent one-lane mixed additions (57 us) to leave ~2 partials per bucket,
+// which the first level then added again (another ~30 us).
+// A HEAVY bucket of the fused level (more than LG::FUSED_HEAVY entries: a short top window puts e.g. 256 of a 512-coefficient polynomial's
+// entries into one bucket of a small SRS's tables) is summed by the whole wave: group p adds the entries hb + p, hb + p + GROUPS, ..., a
+// tree joins the GROUPS partial sums.  One pair walking it alone kept its wave -- and the launch -- waiting for 256 dependent
 // additions (0.93 ms for a 512-coefficient commitment on a 512-point SRS; 0.07 ms for the level otherwise).  Every lane of the wave calls.
-constexpr uint32_t FUSED_HEAVY = 12;        // (24 while the groups held neighbouring buckets: the ~100 heavy buckets of a blob's top window then sat in two workgroups)
-constexpr uint32_t FUSED_HEAVY_QUADS = 8;   // lane-quad form: 16 quads share a heavy bucket
-__device__ __noinline__ void fused_heavy_bucket(HalfXyzz& tot, uint32_t hb, uint32_t he, uint32_t lane, const uint4* __restrict__ points,
+template <class LG>
+__device__ __noinline__ void fused_heavy_bucket(typename LG::Point& tot, uint32_t hb, uint32_t he, uint32_t lane, const uint4* __restrict__ points,
                                                 const uint32_t* __restrict__ sorted, uint32_t idx_log, uint32_t stride_adj) {
-    const uint32_t pair = lane >> 1;
-    const bool odd = (lane & 1u) != 0;
-    HalfXyzz part;
-    half_set_inf(part);
+    const uint32_t grp = lane / LG::LANES;
+    const typename LG::Role role = LG::role(lane);
+    typename LG::Point part;
+    LG::set_inf(part);
 #pragma unroll 1
-    for (uint32_t e = hb + pair; e < he; e += 32) {     // pair-uniform trip count
+    for (uint32_t e = hb + grp; e < he; e += LG::GROUPS) {     // group-uniform trip count
         const uint32_t cur = sorted[e];
-        const uint4* src = points + 4 * acc_point_index(cur & 0x7FFFFFFFu, idx_log, stride_adj) + (odd ? 2 : 0);
+        const uint4* src = points + 4 * acc_point_index(cur & 0x7FFFFFFFu, idx_log, stride_adj) + LG::affine_half(role);
         const uint4 q0 = src[0], q1 = src[1];
         const uint32_t w32[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
         int any = (q0.x | q0.y | q0.z | q0.w | q1.x | q1.y | q1.z | q1.w) != 0 ? 1 : 0;
@@ -1366,81 +1403,87 @@ __device__ __noinline__ void fused_heavy_bucket(HalfXyzz& tot, uint32_t hb, uint
         if (!any) continue;
         Fq c;
         fe_unpack(c, w32);
-        HalfXyzz r;
-        pair_madd(r, part, c, cur >> 31, odd);
+        typename LG::Point r;
+        LG::madd(r, part, c, cur >> 31, role);
         part = r;
     }
 #pragma unroll 1
-    for (int d = 16; d >= 1; d >>= 1) {
-        HalfXyzz u;
-        half_shfl_down(u, part, 2 * d);
-        if (pair < (uint32_t)d) {
-            HalfXyzz r;
-            pair_add(r, part, u, odd);
+    for (int d = LG::GROUPS / 2; d >= 1; d >>= 1) {
+        typename LG::Point u;
+        LG::shfl_down(u, part, (int)LG::LANES * d);
+        if (grp < (uint32_t)d) {
+            typename LG::Point r;
+            LG::add(r, part, u, role);
             part = r;
         }
     }
-    half_shfl(tot, part, odd ? 1 : 0);                  // pair 0 holds the sum
+    LG::shfl(tot, part, (int)(lane & (LG::LANES - 1)));      // group 0 holds the sum
 }
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(KZG_PAIR_WAVES, KZG_PAIR_WAVES)))
-k_msm_bucket_bits1p_fused(const uint4* __restrict__ points, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offs, uint32_t B,
-                          uint32_t idx_log, uint32_t stride_adj, uint32_t G1, int32_t* __restrict__ x1, size_t x_stride,
-                          uint32_t* __restrict__ out_wire /* G1 == 1 only */) {
+template <class LG>
+__global__ void __launch_bounds__(LG::THREADS) __attribute__((amdgpu_waves_per_eu(LG::WAVES, LG::WAVES)))      // (sparse MSMs: at most 256 workgroups)
+k_msm_bucket_bits1_fused(const uint4* __restrict__ points, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offs, uint32_t B,
+                         uint32_t idx_log, uint32_t stride_adj, uint32_t G1, int32_t* __restrict__ x1, size_t x_stride,
+                         uint32_t* __restrict__ out_wire /* G1 == 1 only */) {
     latency_bound_kernel();
-    __shared__ int32_t lds[2 * NL * 64];
-    const uint32_t g = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63, gp = w * 32 + (lane >> 1);
-    const bool odd = (lane & 1u) != 0;
+    __shared__ int32_t lds[LG::ZETA_LDS_WORDS];
+    const uint32_t g = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63, gp = w * LG::GROUPS + lane / LG::LANES;
+    const typename LG::Role role = LG::role(lane);
     const uint32_t bkt = gp * G1 + g;                   // strided: neighbouring buckets (the few heavy ones of a short top window) go to different workgroups
     uint32_t e = 0, end = 0;
     if (bkt < B) { e = offs[bkt]; end = offs[bkt + 1]; }
     const uint32_t hb = e, he = end;
-    const bool heavy = end - e > FUSED_HEAVY;
+    const bool heavy = end - e > LG::FUSED_HEAVY;
     if (heavy) end = e;                                 // summed by the whole wave below
-    HalfXyzz v;
-    half_set_inf(v);
+    typename LG::Point v;
+    LG::set_inf(v);
     // two-deep software pipeline as in k_msm_accumulate: entry e + 2 and the point of entry e + 1 are in flight while entry e is added
     // (clamped, unconditional prefetches: the dependent index -> point gather would otherwise be exposed in every iteration)
+    const uint32_t half = LG::affine_half(role);
     const uint32_t last = end ? end - 1 : 0;
     uint32_t ent = e < end ? sorted[e] : 0u;
     uint32_t ent1 = e < end ? sorted[e + 1 < end ? e + 1 : last] : 0u;
-    const uint4* src = points + 4 * acc_point_index(ent & 0x7FFFFFFFu, idx_log, stride_adj) + (odd ? 2 : 0);
+    const uint4* src = points + 4 * acc_point_index(ent & 0x7FFFFFFFu, idx_log, stride_adj) + half;
     uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0;
     if (e < end) { q0 = src[0]; q1 = src[1]; }          // even lane: x, odd lane: y
 #pragma unroll 1
-    for (; e < end; ++e) {                              // pair-uniform trip count
+    for (; e < end; ++e) {                              // group-uniform trip count
         const uint32_t cur = ent;
         const uint32_t w32[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
         int any = (q0.x | q0.y | q0.z | q0.w | q1.x | q1.y | q1.z | q1.w) != 0 ? 1 : 0;
         ent = ent1;
-        src = points + 4 * acc_point_index(ent & 0x7FFFFFFFu, idx_log, stride_adj) + (odd ? 2 : 0);
+        src = points + 4 * acc_point_index(ent & 0x7FFFFFFFu, idx_log, stride_adj) + half;
         q0 = src[0]; q1 = src[1];
         ent1 = sorted[e + 2 < end ? e + 2 : last];
         any |= pair_swap(any);
-        if (!any) continue;                             // identity base (pair-uniform)
+        if (!any) continue;                             // identity base (group-uniform)
         Fq c;
         fe_unpack(c, w32);
-        HalfXyzz r;
-        pair_madd(r, v, c, cur >> 31, odd);
+        typename LG::Point r;
+        LG::madd(r, v, c, cur >> 31, role);
         v = r;
     }
-    unsigned long long todo = __ballot(heavy && !odd);   // one bit per heavy pair (its even lane)
+    unsigned long long todo = __ballot(heavy && (lane & (LG::LANES - 1)) == 0);   // one bit per heavy group (its first lane)
     while (todo) {                                      // wave-uniform
         const int src_lane = __ffsll((long long)todo) - 1;
         todo &= todo - 1;
-        HalfXyzz tot;
-        fused_heavy_bucket(tot, __shfl(hb, src_lane, 64), __shfl(he, src_lane, 64), lane, points, sorted, idx_log, stride_adj);
-        if ((int)(lane & ~1u) == src_lane) v = tot;
+        typename LG::Point tot;
+        fused_heavy_bucket<LG>(tot, __shfl(hb, src_lane, 64), __shfl(he, src_lane, 64), lane, points, sorted, idx_log, stride_adj);
+        if ((int)(lane & ~(LG::LANES - 1)) == src_lane) v = tot;
     }
-    group_zeta64(v, lane, w, odd, lds);
-    const int role = zeta_role(gp);
-    if (role < 0) return;
-    if (G1 == 1) half_store_wire(out_wire, (size_t)role, v, odd);
-    else half_store(x1, x_stride, (size_t)role * G1 + g, v, odd);
+    LG::zeta64(v, lane, w, role, lds);
+    const int zr = zeta_role(gp);
+    if (zr < 0) return;
+    if (G1 == 1) LG::store_wire(out_wire, (size_t)zr, v, role);
+    else LG::store(x1, x_stride, (size_t)zr * G1 + g, v, role);
 }
 
+// -------------------------------------------------------------------------------------------------
+// 6d. the second level, written per lane form because the forms really differ here: the pair kernel carries TWO groups of 64 values
+//     through one dual transform, the quad kernel one group through LG::zeta64's transform.
+// -------------------------------------------------------------------------------------------------
 // Superset-sum transforms of TWO groups of 64 values at once on a two-wave workgroup, pair gp = 32 w + (lane >> 1).
 // (Used by the second level only.  On the first level it HALVES the waves of a kernel that runs two waves per SIMD at 2^16 buckets and
-// doubles the serial bucket sums of each: k_msm_bucket_bits1p went 0.123 -> 0.207 ms at 2^20 pairs, 77 -> 131 us at 2^11 (same box).)
+// doubles the serial bucket sums of each: k_msm_bucket_bits1<PairLanes> went 0.123 -> 0.207 ms at 2^20 pairs, 77 -> 131 us at 2^11 (same box).)
 // A zeta step k adds, for the pairs whose index has bit k CLEAR, the value of the pair 2^k further up -- the other half of the pairs
 // would idle while the wave pays the issue slots.  So the workgroup carries a second group B in complemented order (pair gp holds
 // B's value 63 - gp): B's step k is due exactly on the pairs whose bit k is SET, and its partner is the same pair gp ^ 2^k.  Every
@@ -1513,220 +1556,7 @@ k_red_bits2p(const int32_t* __restrict__ x1, size_t x_stride, uint32_t G1, uint3
         }
     }
 }
-
-// -------------------------------------------------------------------------------------------------
-// 6d. the same two reduction levels on LANE QUADS (curve_quad.h): one point per four lanes, four multiplications per lane and addition
-//     instead of seven; 64 values = one workgroup of four waves (16 quads each).  ~0.7 of the pair form's dependent instructions at
-//     twice its lanes: used when no other MSM is in flight (then latency is everything and the SIMDs are idle anyway).
-//     Same inputs, same X1 / out_wire layout, the same group elements (KZG_QUAD_REDUCE=0: always the pair kernels).
-// -------------------------------------------------------------------------------------------------
-#ifndef KZG_QUAD_SMALL_WAVES
-#define KZG_QUAD_SMALL_WAVES 4     // waves per SIMD the small quad launches are compiled for (128 VGPRs with a few spills; 2 = no spills measured the same or 5 % slower)
-#endif
-__device__ __forceinline__ void bucket_partial_quad(QuadXyzz& v, const BucketSpan& s, uint32_t k, const int32_t* __restrict__ head, size_t head_stride,
-                                                    const int32_t* __restrict__ cont, size_t cont_stride, uint32_t q) {
-    if (k == 0) { quad_load(v, head, head_stride, s.g, q); return; }
-    const uint32_t first = s.t1 + 1;
-    const uint32_t t = !s.long_run ? s.t1 + k : (k == 1 ? first : (first / 64 + (k - 1)) * 64);
-    quad_load(v, cont, cont_stride, t, q);
-}
-// a heavy bucket, summed by the 16 quads of the wave: quad p takes the partials p, p + 16, ..; then a 4-step tree
-__device__ __noinline__ void bucket_sum_heavy_quads(QuadXyzz& tot, uint32_t g, uint32_t t1, uint32_t np, uint32_t long_run, uint32_t lane,
-                                                    const int32_t* __restrict__ head, size_t head_stride, const int32_t* __restrict__ cont, size_t cont_stride) {
-    const uint32_t quad = lane >> 2, q = lane & 3u;
-    BucketSpan h;
-    h.g = g; h.t1 = t1; h.np = np; h.long_run = long_run != 0;
-    QuadXyzz part;
-    quad_set_inf(part);
-    const uint32_t loads = (np + 15) / 16;
-#pragma unroll 1
-    for (uint32_t step = 0; step < loads + 4; ++step) {
-        QuadXyzz u;
-        bool on;
-        if (step < loads) {
-            const uint32_t k = quad + 16 * step;
-            on = k < np;
-            if (on) bucket_partial_quad(u, h, k, head, head_stride, cont, cont_stride, q);
-        } else {
-            const uint32_t d = 8u >> (step - loads);
-            quad_shfl_down(u, part, (int)(4 * d));
-            on = quad < d;
-        }
-        if (on) {
-            QuadXyzz r;
-            quad_add(r, part, u, q);
-            part = r;
-        }
-    }
-    quad_shfl(tot, part, (int)q);                      // quad 0 holds the sum
-}
-// Sum of all partials of this QUAD's bucket (s is the same in the four lanes).  Every lane of the wave must call this.
-__device__ __forceinline__ void bucket_sum_quads(QuadXyzz& acc, const BucketSpan& s, uint32_t lane, uint32_t q, const int32_t* __restrict__ head,
-                                                 size_t head_stride, const int32_t* __restrict__ cont, size_t cont_stride) {
-    quad_set_inf(acc);
-    const bool heavy = s.np > NP_SERIAL;
-    if (!heavy) {
-#pragma unroll 1
-        for (uint32_t k = 0; k < s.np; ++k) {
-            QuadXyzz v, r;
-            bucket_partial_quad(v, s, k, head, head_stride, cont, cont_stride, q);
-            quad_add(r, acc, v, q);
-            acc = r;
-        }
-    }
-    unsigned long long todo = __ballot(heavy && q == 0);   // one bit per heavy quad (its lane 0)
-    while (todo) {                                     // wave-uniform
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        QuadXyzz tot;
-        bucket_sum_heavy_quads(tot, __shfl(s.g, src, 64), __shfl(s.t1, src, 64), __shfl(s.np, src, 64), (uint32_t)__shfl((int)s.long_run, src, 64), lane,
-                               head, head_stride, cont, cont_stride);
-        if ((int)(lane & ~3u) == src) acc = tot;
-    }
-}
-// Superset-sum transform over the 64 values of a four-wave group, value gp = 16 w + quad: afterwards gp = 0 holds the total and
-// gp = 2^k the sum over the values whose index has bit k set.  Steps 0..3 inside the wave, steps 4 and 5 through LDS (the waves whose
-// index has the bit set publish, the others add).  Called by every lane of the four waves (four barriers inside).
-__device__ __forceinline__ void group_zeta64q(QuadXyzz& v, uint32_t lane, uint32_t w, uint32_t q, int32_t* __restrict__ lds /* (NL + 1) x 256 words */) {
-    const uint32_t quad = lane >> 2, tid = w * 64 + lane;
-#pragma unroll 1
-    for (int k = 0; k < 6; ++k) {                      // one addition site for the six steps
-        QuadXyzz u;
-        bool on;
-        if (k < 4) {
-            quad_shfl_down(u, v, 4 << k);
-            on = ((quad >> k) & 1u) == 0;
-        } else {
-            const uint32_t bit = 1u << (k - 4);
-            if (k == 5) __syncthreads();               // step 4's readers are done
-            if (w & bit) {
-#pragma unroll
-                for (int j = 0; j < NL; ++j) lds[j * 256 + tid] = v.c.l[j];
-                lds[NL * 256 + tid] = v.inf ? 1 : 0;
-            }
-            __syncthreads();
-            on = (w & bit) == 0;
-            const uint32_t src = tid + 64 * bit;
-            if (on) {
-#pragma unroll
-                for (int j = 0; j < NL; ++j) u.c.l[j] = lds[j * 256 + src];
-                u.inf = lds[NL * 256 + src] != 0;
-            }
-        }
-        if (on) {
-            QuadXyzz r;
-            quad_add(r, v, u, q);
-            v = r;
-        }
-    }
-}
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KZG_QUAD_SMALL_WAVES, KZG_QUAD_SMALL_WAVES)))
-k_msm_bucket_bits1q(const uint32_t* __restrict__ offs, uint32_t B, uint32_t nl, const int32_t* __restrict__ head, size_t head_stride,
-                    const int32_t* __restrict__ cont, size_t cont_stride, uint32_t G1, int32_t* __restrict__ x1, size_t x_stride,
-                    uint32_t* __restrict__ out_wire /* G1 == 1 only */) {
-    latency_bound_kernel();
-    __shared__ int32_t lds[(NL + 1) * 256];
-    const uint32_t g = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63, gp = w * 16 + (lane >> 2), q = lane & 3u;
-    const uint32_t L = acc_seg_len(offs[B], nl);
-    const uint32_t bkt = g * 64 + gp;
-    BucketSpan s;
-    s.g = bkt; s.t1 = 0; s.np = 0; s.long_run = false;
-    if (bkt < B && L) s = bucket_span(offs, bkt, L);
-    QuadXyzz v;
-    bucket_sum_quads(v, s, lane, q, head, head_stride, cont, cont_stride);
-    group_zeta64q(v, lane, w, q, lds);
-    const int role = zeta_role(gp);
-    if (role < 0) return;
-    if (G1 == 1) quad_store_wire(out_wire, (size_t)role, v, q);
-    else quad_store(x1, x_stride, (size_t)role * G1 + g, v, q);
-}
-// level 1 FUSED with the accumulation (sparse MSMs; see k_msm_bucket_bits1p_fused): quad = bucket, entries added with quad_madd
-__device__ __noinline__ void fused_heavy_bucket_quads(QuadXyzz& tot, uint32_t hb, uint32_t he, uint32_t lane, const uint4* __restrict__ points,
-                                                      const uint32_t* __restrict__ sorted, uint32_t idx_log, uint32_t stride_adj) {
-    const uint32_t quad = lane >> 2, q = lane & 3u;
-    QuadXyzz part;
-    quad_set_inf(part);
-#pragma unroll 1
-    for (uint32_t e = hb + quad; e < he; e += 16) {     // quad-uniform trip count
-        const uint32_t cur = sorted[e];
-        const uint4* src = points + 4 * acc_point_index(cur & 0x7FFFFFFFu, idx_log, stride_adj) + ((q & 1u) ? 2 : 0);
-        const uint4 q0 = src[0], q1 = src[1];
-        const uint32_t w32[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-        int any = (q0.x | q0.y | q0.z | q0.w | q1.x | q1.y | q1.z | q1.w) != 0 ? 1 : 0;
-        any |= pair_swap(any);
-        if (!any) continue;
-        Fq c;
-        fe_unpack(c, w32);
-        QuadXyzz r;
-        quad_madd(r, part, c, cur >> 31, q);
-        part = r;
-    }
-#pragma unroll 1
-    for (int d = 8; d >= 1; d >>= 1) {
-        QuadXyzz u;
-        quad_shfl_down(u, part, 4 * d);
-        if (quad < (uint32_t)d) {
-            QuadXyzz r;
-            quad_add(r, part, u, q);
-            part = r;
-        }
-    }
-    quad_shfl(tot, part, (int)q);                       // quad 0 holds the sum
-}
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KZG_QUAD_SMALL_WAVES, KZG_QUAD_SMALL_WAVES)))      // (sparse MSMs: at most 256 workgroups)
-k_msm_bucket_bits1q_fused(const uint4* __restrict__ points, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offs, uint32_t B,
-                          uint32_t idx_log, uint32_t stride_adj, uint32_t G1, int32_t* __restrict__ x1, size_t x_stride,
-                          uint32_t* __restrict__ out_wire /* G1 == 1 only */) {
-    latency_bound_kernel();
-    __shared__ int32_t lds[(NL + 1) * 256];
-    const uint32_t g = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63, gp = w * 16 + (lane >> 2), q = lane & 3u;
-    const uint32_t bkt = gp * G1 + g;                   // strided, as in k_msm_bucket_bits1p_fused
-    uint32_t e = 0, end = 0;
-    if (bkt < B) { e = offs[bkt]; end = offs[bkt + 1]; }
-    const uint32_t hb = e, he = end;
-    const bool heavy = end - e > FUSED_HEAVY_QUADS;
-    if (heavy) end = e;                                 // summed by the whole wave below
-    QuadXyzz v;
-    quad_set_inf(v);
-    const uint32_t half = (q & 1u) ? 2 : 0;             // lanes 0, 2: x; lanes 1, 3: y
-    const uint32_t last = end ? end - 1 : 0;
-    uint32_t ent = e < end ? sorted[e] : 0u;
-    uint32_t ent1 = e < end ? sorted[e + 1 < end ? e + 1 : last] : 0u;
-    const uint4* src = points + 4 * acc_point_index(ent & 0x7FFFFFFFu, idx_log, stride_adj) + half;
-    uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0;
-    if (e < end) { q0 = src[0]; q1 = src[1]; }
-#pragma unroll 1
-    for (; e < end; ++e) {                              // quad-uniform trip count
-        const uint32_t cur = ent;
-        const uint32_t w32[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-        int any = (q0.x | q0.y | q0.z | q0.w | q1.x | q1.y | q1.z | q1.w) != 0 ? 1 : 0;
-        ent = ent1;
-        src = points + 4 * acc_point_index(ent & 0x7FFFFFFFu, idx_log, stride_adj) + half;
-        q0 = src[0]; q1 = src[1];
-        ent1 = sorted[e + 2 < end ? e + 2 : last];
-        any |= pair_swap(any);
-        if (!any) continue;                             // identity base (quad-uniform)
-        Fq c;
-        fe_unpack(c, w32);
-        QuadXyzz r;
-        quad_madd(r, v, c, cur >> 31, q);
-        v = r;
-    }
-    unsigned long long todo = __ballot(heavy && q == 0);
-    while (todo) {                                      // wave-uniform
-        const int src_lane = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        QuadXyzz tot;
-        fused_heavy_bucket_quads(tot, __shfl(hb, src_lane, 64), __shfl(he, src_lane, 64), lane, points, sorted, idx_log, stride_adj);
-        if ((int)(lane & ~3u) == src_lane) v = tot;
-    }
-    group_zeta64q(v, lane, w, q, lds);
-    const int role = zeta_role(gp);
-    if (role < 0) return;
-    if (G1 == 1) quad_store_wire(out_wire, (size_t)role, v, q);
-    else quad_store(x1, x_stride, (size_t)role * G1 + g, v, q);
-}
-// level 2: one four-wave workgroup per job of k_red_bits2
+// the quad form: one four-wave workgroup per job of k_red_bits2p
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KZG_QUAD_SMALL_WAVES, KZG_QUAD_SMALL_WAVES)))      // (at most 7 x 16 workgroups)
 k_red_bits2q(const int32_t* __restrict__ x1, size_t x_stride, uint32_t G1, uint32_t G1p, uint32_t* __restrict__ out_wire) {
     latency_bound_kernel();
@@ -1808,7 +1638,7 @@ k_bitsum_level1(const uint4* __restrict__ bits /* Bit_p[i] at (p stride + i) x 6
         const uint32_t w32[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
         int any = (q0.x | q0.y | q0.z | q0.w | q1.x | q1.y | q1.z | q1.w) != 0 ? 1 : 0;
         any |= pair_swap(any);
-        if (!any) continue;                             // identity base
+        if (!any) continue; // identity base
         Fq cxy;
         fe_unpack(cxy, w32);
         QuadXyzz r;

@@ -177,3 +177,43 @@ def test_srs_msm_over_degenerate_points(k, log_srs):
             assert pyref.point_from_wire(out) == pyref.ec_mul(sum(a * b for a, b in zip(c, s[off:])) % R_, G), (log_srs, name, "offset")
         finally:
             srs.close()
+
+
+def test_srs_msm_over_degenerate_points_on_pairs_and_quads(k):
+    """The same SRS MSM with the bucket reduction FORCED onto lane pairs and onto lane quads (ctx.set_reduction_lanes: the synchronous calls
+    of the test above only ever meet the automatic choice, quads), on the smallest carriers that reach each path: an SRS of 1 024 points
+    (below 2^11: window tables only, so every n goes through the buckets and the fused first level) and one of 2^15 points (per-bit tables
+    + NAF digits; n above the 4 096-pair sums of table points, so the accumulate kernel and both reduction levels run).  Equal points,
+    +-P pairs and identities in the buckets; expected value (sum_j c_j s_j) G by big integers."""
+    import ctypes as C
+    rnd = random.Random(7100)
+    ctx = k.default_context(); lib = k._lib.load()
+    small = [0, 1, R_ - 1, 2, R_ - 2, 5, 1, 1]
+    try:
+        for N, sizes, bit_tables in ((1024, (2, 100, 1024), 0), (1 << 15, (4097, 1 << 15), 1)):
+            for name, s in (("all equal", [1] * N), ("alternating +-G", [1 if j % 2 == 0 else R_ - 1 for j in range(N)]),
+                            ("few small multiples", [rnd.choice(small) for _ in range(N)])):
+                srs = k.SRS(pyref.points_to_wire([mult(v) for v in s]))             # one build per point set, shared by both lane forms
+                try:
+                    assert lib.kzg_srs_has_bit_tables(srs.handle, 0) == bit_tables
+                    for n in sizes:
+                        for kind in ("uniform", "equal", "pairs cancel"):
+                            if kind == "uniform":
+                                c = [rnd.randrange(R_) for _ in range(n)]
+                            elif kind == "equal":
+                                c = [rnd.randrange(R_)] * n
+                            else:
+                                half = [rnd.randrange(R_) for _ in range((n + 1) // 2)]
+                                c = [half[j // 2] for j in range(n)]             # c_2j = c_2j+1: cancels on the alternating set
+                            want = pyref.ec_mul(sum(a * b for a, b in zip(c, s)) % R_, G)
+                            c_mont = pyref.frs_to_mont(c)
+                            for lanes in (2, 4):
+                                ctx.set_reduction_lanes(lanes)
+                                out = np.zeros(8, np.uint64); inf = C.c_uint8(0)
+                                assert lib.kzg_msm_g1_srs(ctx.handle, srs.handle, 0, k._lib.ptr(c_mont), n, k._lib.ptr(out), C.byref(inf)) == 0
+                                assert pyref.point_from_wire(out) == want, (N, name, n, kind, lanes)
+                                assert bool(inf.value) == (want is None), (N, name, n, kind, lanes)
+                finally:
+                    srs.close()
+    finally:
+        ctx.set_reduction_lanes(0)

@@ -1,4 +1,5 @@
 #!/bin/bash
+# (the KZG_PROBE_NOSUM / KZG_PROBE_NOZETA builds of the pair kernel, measured beside this A/B, were last in commit 210c322: docs/history/DESIGN_rounds1-3.md)
 # same-box A/B of the two bucket-reduction levels: one-lane kernels (KZG_PAIR_REDUCE=0) against the lane-pair kernels
 # (curve_pair.h): phase times of the 2^20 MSM from bench.py, small commitments and shard-sized MSMs.
 set -o pipefail
