@@ -16,6 +16,7 @@
 #include "host_curve.h"
 #include "host_pairing.h"
 #include "host_sha256.h"
+#include "host_fiat_shamir.h"
 
 #include <atomic>
 #include <chrono>
@@ -25,16 +26,6 @@
 #include <thread>
 
 namespace kzg {
-
-// capi.hip
-void challenge_absorb_prefix(kzg_host::Sha256& sh, const uint8_t* blob, size_t len, size_t n_padded);
-void challenge_finish(kzg_host::Sha256& sh, const kzg_host::G1& commitment, uint64_t out_z_mont[4]);
-size_t blob_padded_len(size_t len);
-// poly.hip
-int32_t blob_to_fr_run(kzg_ctx* ctx, const uint8_t* bytes, size_t len, size_t n_padded, void** d_out, hipStream_t st, DeviceBuffer* d_bytes,
-                       DeviceBuffer* d_elems);
-int32_t proof_begin(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* evals, size_t n, const uint64_t z[4], int slot, const void* d_resident);
-int32_t proof_end(kzg_ctx* ctx, int slot, uint64_t out_xy[8], uint8_t* out_inf, uint64_t* out_y);
 
 enum BlobJobState { JOB_IDLE = 0, JOB_COMMIT, JOB_WAIT_HASH, JOB_PROOF, JOB_DONE, JOB_FAILED };
 
@@ -182,7 +173,7 @@ int32_t kzg_commit_and_prove_blob_begin(kzg_ctx* ctx, const kzg_srs* srs, const 
     if (!ctx || !srs || srs->ctx != ctx || (len && !blob_bytes) || job < 0 || job >= KZG_BLOB_JOBS) return KZG_ERR_INVALID_ARG;
     const size_t n_elems = (len + 31) / 32;
     if (n_elems > ((size_t)1 << 24)) return KZG_ERR_TOO_LARGE;                       // (the asynchronous forms stop at 2^24 elements)
-    const size_t n = blob_padded_len(len);
+    const size_t n = kzg_host::blob_padded_len(len);
     kzg_host::G1 given;
     if (commitment_xy_mont) {
         given = kzg_host::g1_from_wire(commitment_xy_mont);

@@ -108,7 +108,7 @@ struct kzg_ctx {
     kzg::NttWorkspace ntt;
     int32_t* ondomain_inv[13] = {};      // [log n] -> 1 / (w^k - 1), k < n <= 4096 (limb planes): proofs at a known domain point (poly.hip)
     kzg::NttWorkspace ntt_x[KZG_NUM_SLOTS - 1];   // slots 1.. of the asynchronous commitment / proof calls
-    void* vb_pinned = nullptr;           // pinned staging of the packed blobs of one batch verification (capi.hip), grown on demand
+    void* vb_pinned = nullptr;           // pinned staging of the packed blobs of one batch verification (capi_verify.hip), grown on demand
     size_t vb_pinned_bytes = 0;
     kzg::DeviceBuffer rccl_buf;          // this rank's partial + the gathered partials of kzg_rccl_allgather_fold (multi.hip)
     void* rccl_pinned = nullptr;         // pinned host staging of the same rows (row out | world rows in)
@@ -272,18 +272,51 @@ void multiproof_drop(kzg_srs* srs);
 // verification of coset proofs (multiverify.hip): d_out[t] = sum_i weights[i] w^(-ks[i] t) IFFT_l(ys_i)[t], enqueued on ctx->stream (d_ys is scratch when l > 1024)
 int32_t coset_interpolate_rlc_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, size_t count, size_t n, size_t l, uint4* d_out);
 
+// polynomial pipeline (poly.hip)
+int32_t proof_run(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* evals, size_t n, const uint64_t z[4],
+                  uint64_t out_xy[8], uint8_t* out_inf, uint64_t* out_y, bool want_proof, size_t coeff_lo, uint64_t* out_xyzz);
+int32_t proof_begin(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* evals, size_t n, const uint64_t z[4], int slot, const void* d_resident = nullptr);
+int32_t proof_end(kzg_ctx* ctx, int slot, uint64_t out_xy[8], uint8_t* out_inf, uint64_t* out_y);
+int32_t roots_run(kzg_ctx* ctx, uint64_t* out, size_t n);
+int32_t blob_to_fr_run(kzg_ctx* ctx, const uint8_t* bytes, size_t len, size_t n_padded, void** d_out,
+                       hipStream_t st = nullptr, DeviceBuffer* d_bytes = nullptr, DeviceBuffer* d_elems = nullptr);
+// the batched evaluations of batch verification (poly.hip k_vb_prep / k_vb_eval; meta_host: nb x {u64 off, u32 len, u32 log_n})
+int32_t vb_evaluate_setup(kzg_ctx* ctx, size_t packed_len, size_t nb);
+int32_t vb_evaluate_enqueue(kzg_ctx* ctx, const uint8_t* packed, const void* meta_host, size_t nb, size_t b0, size_t b1, const uint64_t* zs,
+                            uint8_t* small_pinned);
+int32_t vb_evaluate_finish(kzg_ctx* ctx, size_t nb, uint64_t* ys_out, uint8_t* fallback_out);
+// Lagrange-sharded proofs (lagrange.hip; the host folds lag_fold_y / lag_fold_proof: host_lagrange.h)
+int32_t lag_begin(kzg_ctx* ctx, const kzg_srs* shard, size_t base, const void* evals, bool on_device, size_t len, size_t n, const uint64_t z[4], int slot, int commit_slot);
+int32_t lag_partial_y(kzg_ctx* ctx, int slot, uint64_t out[8]);
+int32_t lag_continue(kzg_ctx* ctx, int slot, const uint64_t y[4]);
+int32_t lag_end(kzg_ctx* ctx, int slot, uint64_t out_part[32], uint64_t* out_commit);
+void lag_abort(kzg_ctx* ctx, int slot);
+int32_t lag_quotient_eval_on_domain(kzg_ctx* ctx, const uint64_t z[4], const uint64_t* evals, size_t n, const uint64_t value[4], uint64_t out[4]);
+
+// MSM front ends shared by the units of the C-ABI (capi.hip).  _locked: the caller holds ctx->mu (msm_g1_batch_locked: and has set the device).
+// off_curve != nullptr: the uploaded points are validated on the device, *off_curve = 1 if one fails (then no MSM runs over them)
+int32_t msm_srs_locked(kzg_ctx* ctx, const kzg_srs* srs, size_t offset, const void* scalars, bool on_device, size_t n,
+                       uint64_t out_xy[8], uint8_t* out_inf, uint64_t* out_xyzz);
+int32_t msm_g1_batch_locked(kzg_ctx* ctx, const uint64_t* bases_xy_mont, const uint64_t* scalars_mont, size_t n, size_t batch,
+                            uint64_t* out_xy_mont, uint8_t* out_is_infinity, uint32_t* off_curve);
+int32_t msm_g1_batch_impl(kzg_ctx* ctx, const uint64_t* bases_xy_mont, const uint64_t* scalars_mont, size_t n, size_t batch,
+                          uint64_t* out_xy_mont, uint8_t* out_is_infinity, uint32_t* off_curve);
+// wire points of the host -> device format at d_out through `staging`, synchronised on return (capi_srs.hip)
+int32_t upload_points(kzg_ctx* ctx, const uint64_t* xy, size_t n, uint4* d_out, DeviceBuffer& staging, uint32_t* off_curve = nullptr);
+
 int32_t set_error(kzg_ctx* ctx, hipError_t e, const char* where);
 // the context's high-priority auxiliary stream (lagrange.hip)
 int32_t ctx_aux_stream(kzg_ctx* ctx, hipStream_t fallback, hipStream_t* out);
 // the points only, no window / per-bit tables (set-up paths that need the points once: kzg_multi_cache_lagrange)
 int32_t srs_upload_plain(kzg_ctx* ctx, const uint64_t* g1_xy_mont, size_t n_points, kzg_srs** out);
 
-// job(i) for i < n on the library's persistent host pool (capi.hip HostPool; the calling thread takes part)
+// job(i) for i < n on the library's persistent host pool (host_pool.h HostPool, sized in runtime.hip; the calling thread takes part)
 void host_parallel_for(size_t n, const std::function<void(size_t)>& job);
+unsigned host_pool_threads(size_t jobs);   // threads such a call of `jobs` jobs runs on (traces)
 // joins the transcript threads and frees the buffers of the blob stream (kzg_ctx_destroy)
 void blob_stream_release(kzg_ctx* ctx);
 
-// Every environment variable the library reads (capi.hip opts(); header: "ENVIRONMENT").  Read once per process, except the two SRS switches,
+// Every environment variable the library reads (runtime.hip opts(); header: "ENVIRONMENT").  Read once per process, except the two SRS switches,
 // which are read at every upload so that a host can load one SRS with and one without tables (bench.py does).
 struct Opts {
     int host_threads_max = 0;        // KZG_HOST_THREADS_MAX: cap of the host pool (transcripts of batch verification); 0 = min(48, the cgroup's CPU quota)

@@ -199,7 +199,7 @@ KZG_HD void kzg_bound_record(int site, const Fe<F>& a) {
                                        KZG_REQUIRE(fe_bound_mul_value(a, b), KZG_SITE_MUL_VALUE, what, a); } while (0)
 
 // Every .hip file of csrc/ ends with KZG_BOUND_CHECK_EXPORTS(<file>) under KZG_DEVICE_BOUND_CHECK: the host reader (counts and first
-// operands of this translation unit's sites) and reset; capi.hip's kzg_bc_read_all / kzg_bc_reset_all cover them all.  Empty in
+// operands of this translation unit's sites) and reset; runtime.hip's kzg_bc_read_all / kzg_bc_reset_all cover them all.  Empty in
 // every other build.
 #if defined(KZG_DEVICE_BOUND_CHECK) && defined(__HIPCC__)
 #define KZG_BOUND_CHECK_EXPORTS(name)                                                                                              \

@@ -1,0 +1,137 @@
+// host_fiat_shamir.h — the Fiat-Shamir codec of the library, one of each piece: the byte encoders, digest -> Fr, the challenge of
+// helpers::compute_challenge (primitives/src/helpers.rs:411-472), and the two random-linear-combination transcripts (the reference's
+// batch verifier, verifier/src/batch.rs:76-168, and this library's own for FK20 coset proofs).  Pure host code (no HIP, no engine.h):
+// also compiled by g++ for tests/test_fiat_shamir_host.py.  The two transcripts fan their rows out through a parallel-for handed in by
+// the caller (the library: kzg::host_parallel_for).
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <functional>
+#include <vector>
+#include "host_fr.h"
+#include "host_pairing.h"
+#include "host_sha256.h"
+#include "host_transcript.h"
+
+namespace kzg_host {
+
+using ParallelFor = void (*)(size_t n, const std::function<void(size_t)>& job);   // job(i) for i < n, in any order, on any threads
+
+const char RC_BATCH_DOMAIN[] = "EIGENDA_RCKZGBATCH___V1_";       // primitives/src/consts.rs:11 (24 bytes)
+const char COSET_ITEM_DOMAIN[] = "KZGBN254_COSETITEM___V1_";     // 24 bytes each; this library's own transcript (the reference has no coset proofs)
+const char COSET_BATCH_DOMAIN[] = "KZGBN254_COSETBATCH__V1_";
+
+inline size_t next_pow2(size_t x) { size_t p = 1; while (p < x) p <<= 1; return p; }           // next_power_of_two(0) == 1
+inline size_t blob_padded_len(size_t len) { return next_pow2((len + 31) / 32); }               // elements of Blob::to_polynomial_eval_form
+inline void put_u64be(uint8_t* p, uint64_t v) { for (int b = 0; b < 8; ++b) p[b] = (uint8_t)(v >> (8 * (7 - b))); }
+inline void fr_wire_to_be_bytes(const uint64_t wire[4], uint8_t out[32]) {
+    uint64_t k[4];
+    fr_wire_to_canonical(wire, k);
+    for (int i = 0; i < 4; ++i) put_u64be(out + 8 * i, k[3 - i]);
+}
+inline void digest_to_fr_wire(const uint8_t dig[32], uint64_t out[4]) {            // hash_to_field_element (helpers.rs:382-390)
+    uint64_t w[4];
+    for (int i = 0; i < 4; ++i) { uint64_t v = 0; for (int b = 0; b < 8; ++b) v = (v << 8) | dig[8 * (3 - i) + b]; w[i] = v; }
+    while (fr_geq_r(w)) fr_sub_r(w);                                                // Fr::from_be_bytes_mod_order
+    fr_mul(w, FR_R2, out);                                                          // canonical -> Montgomery
+}
+// ark-serialize compressed G1Affine (helpers.rs:456-459): x little-endian, bit 7 of the last byte = y is the larger root, bit 6 = infinity
+inline void g1_serialize_compressed_ark(const G1& p, uint8_t out[32]) {
+    memset(out, 0, 32);
+    if (p.inf) { out[31] = 0x40; return; }
+    Fq one_plain = {{1, 0, 0, 0}};
+    Fq x = mul(p.x, one_plain), y = mul(p.y, one_plain);                             // Montgomery -> canonical
+    memcpy(out, x.l, 32);                                                            // little-endian host
+    Fq ny = sub(FQ_P, y);                                                            // -y (y != 0 on this curve)
+    bool larger = false;
+    for (int i = 3; i >= 0; --i) if (y.l[i] != ny.l[i]) { larger = y.l[i] > ny.l[i]; break; }
+    if (larger) out[31] |= 0x80;
+}
+
+// Absorbs  tag || u64be(n) || n x 32 bytes, the evaluations of Blob::to_polynomial_eval_form in to_byte_array form: every
+// 32-byte big-endian chunk of the blob reduced mod r (helpers.rs:40-57 -> :80-119), zero elements up to the next power of two.
+// Canonical chunks (the normal case) are hashed straight from the caller's buffer.
+inline void challenge_absorb_prefix(Sha256& sh, const uint8_t* blob, size_t len, size_t n_padded) {
+    TranscriptPrefix gen(blob, len, n_padded);                                       // host_transcript.h
+    sha256_absorb(sh, gen);
+}
+inline void challenge_finish(Sha256& sh, const G1& commitment, uint64_t out_z_mont[4]) {
+    uint8_t cb[32], dig[32];
+    g1_serialize_compressed_ark(commitment, cb);
+    sha256_update(sh, cb, 32);
+    sha256_final(sh, dig);
+    digest_to_fr_wire(dig, out_z_mont);
+}
+
+// helpers::compute_powers (helpers.rs:298-313): out[i] = r^i for i < n, wire form
+inline void powers_of(const uint64_t r[4], size_t n, uint64_t* out) {
+    uint64_t cur[4];
+    fr_one(cur);
+    for (size_t i = 0; i < n; ++i) { memcpy(out + 4 * i, cur, 32); fr_mul(cur, r, cur); }
+}
+// the tail of both transcripts: r = hash_to_field_element(data), then the n powers of r
+inline void hash_to_r_powers(const std::vector<uint8_t>& data, size_t n, uint64_t* out) {
+    Sha256 sh;
+    sha256_init(sh);
+    sha256_update(sh, data.data(), data.size());
+    uint8_t dig[32];
+    sha256_final(sh, dig);
+    uint64_t r[4];
+    digest_to_fr_wire(dig, r);
+    powers_of(r, n, out);
+}
+
+// batch.rs:76-168 on the host: 40 + 8 n + 128 n transcript bytes, one SHA-256, n - 1 field multiplications
+inline void r_powers_host(const uint64_t* commitments, const uint64_t* zs, const uint64_t* ys, const uint64_t* proofs, const uint64_t* lens_elems,
+                          size_t n, uint64_t* out, ParallelFor parallel_for) {
+    std::vector<uint8_t> data(40 + n * 8 + n * 128, 0);
+    memcpy(data.data(), RC_BATCH_DOMAIN, 24);                                          // bytes 24..31 stay zero (batch.rs:107-112)
+    put_u64be(data.data() + 32, (uint64_t)n);
+    for (size_t i = 0; i < n; ++i) put_u64be(data.data() + 40 + 8 * i, lens_elems[i]);
+    uint8_t* rows = data.data() + 40 + 8 * n;
+    const size_t per = 64, jobs = (n + per - 1) / per;
+    parallel_for(jobs, [&](size_t j) {
+        for (size_t i = j * per; i < std::min(n, (j + 1) * per); ++i) {
+            uint8_t* p = rows + 128 * i;
+            g1_serialize_compressed_ark(g1_from_wire(commitments + 8 * i), p);
+            fr_wire_to_be_bytes(zs + 4 * i, p + 32);
+            fr_wire_to_be_bytes(ys + 4 * i, p + 64);
+            g1_serialize_compressed_ark(g1_from_wire(proofs + 8 * i), p + 96);
+        }
+    });
+    hash_to_r_powers(data, n, out);
+}
+
+// Two levels: one SHA-256 per item over its index pair, its l values and its proof (host pool), one over the header, the commitments and the digests
+inline void multiproof_r_powers_host(const uint64_t* commitments, size_t n_commitments, const uint64_t* commitment_indices, const uint64_t* coset_indices,
+                                     const uint64_t* ys, const uint64_t* proofs, size_t count, size_t n, size_t l, uint64_t* out, ParallelFor parallel_for) {
+    const size_t head = 24 + 32 + 32 * n_commitments;
+    std::vector<uint8_t> data(head + 32 * count, 0);
+    memcpy(data.data(), COSET_BATCH_DOMAIN, 24);
+    put_u64be(data.data() + 24, (uint64_t)n);
+    put_u64be(data.data() + 32, (uint64_t)l);
+    put_u64be(data.data() + 40, (uint64_t)n_commitments);
+    put_u64be(data.data() + 48, (uint64_t)count);
+    for (size_t c = 0; c < n_commitments; ++c) g1_serialize_compressed_ark(g1_from_wire(commitments + 8 * c), data.data() + 56 + 32 * c);
+    const size_t per = std::max<size_t>(1, 1024 / l), jobs = (count + per - 1) / per;
+    auto body = [&](size_t j) {
+        std::vector<uint8_t> item(24 + 16 + 32 * l + 32);
+        memcpy(item.data(), COSET_ITEM_DOMAIN, 24);
+        for (size_t i = j * per; i < std::min(count, (j + 1) * per); ++i) {
+            put_u64be(item.data() + 24, commitment_indices[i]);
+            put_u64be(item.data() + 32, coset_indices[i]);
+            for (size_t t = 0; t < l; ++t) fr_wire_to_be_bytes(ys + 4 * (i * l + t), item.data() + 40 + 32 * t);
+            g1_serialize_compressed_ark(g1_from_wire(proofs + 8 * i), item.data() + 40 + 32 * l);
+            Sha256 sh;
+            sha256_init(sh);
+            sha256_update(sh, item.data(), item.size());
+            sha256_final(sh, data.data() + head + 32 * i);
+        }
+    };
+    if (jobs > 1) parallel_for(jobs, body); else if (jobs == 1) body(0);
+    hash_to_r_powers(data, count, out);
+}
+
+}  // namespace kzg_host

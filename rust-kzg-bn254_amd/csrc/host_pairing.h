@@ -14,6 +14,7 @@
 #include <system_error>
 #include <thread>
 #include "host_curve.h"
+#include "host_fr.h"           // Fr in wire form: product, sum, conversion to canonical integer words, the modulus
 #include "pairing_constants.h"
 
 namespace kzg_host {
@@ -21,42 +22,6 @@ namespace kzg_host {
 // ---- Fq helpers -------------------------------------------------------------------------------------------------
 inline Fq fq_zero() { Fq z; memset(&z, 0, sizeof z); return z; }
 inline Fq neg(const Fq& a) { return is_zero(a) ? a : sub(fq_zero(), a); }
-
-// ---- Fr (scalar field) in wire form: Montgomery product, sum, and conversion to canonical integer words --------------------------------
-static const uint64_t FR_INV = 0xc2e1f593efffffffULL;           // -r^-1 mod 2^64
-inline bool fr_geq_r(const uint64_t t[4]) {
-    for (int i = 3; i >= 0; --i) { if (t[i] != FR_MODULUS_WORDS[i]) return t[i] > FR_MODULUS_WORDS[i]; }
-    return true;
-}
-inline void fr_sub_r(uint64_t t[4]) {
-    uint64_t br = 0;
-    for (int i = 0; i < 4; ++i) { u128 d = (u128)t[i] - FR_MODULUS_WORDS[i] - br; t[i] = (uint64_t)d; br = (uint64_t)(d >> 64) & 1; }
-}
-inline void fr_mul(const uint64_t a[4], const uint64_t b[4], uint64_t out[4]) {
-    uint64_t t[5] = {0, 0, 0, 0, 0};
-    for (int i = 0; i < 4; ++i) {
-        u128 c = 0;
-        for (int j = 0; j < 4; ++j) { c += (u128)a[j] * b[i] + t[j]; t[j] = (uint64_t)c; c >>= 64; }
-        u128 top = (u128)t[4] + (uint64_t)c;
-        uint64_t m = t[0] * FR_INV;
-        c = ((u128)m * FR_MODULUS_WORDS[0] + t[0]) >> 64;
-        for (int j = 1; j < 4; ++j) { c += (u128)m * FR_MODULUS_WORDS[j] + t[j]; t[j - 1] = (uint64_t)c; c >>= 64; }
-        top += (uint64_t)c;
-        t[3] = (uint64_t)top; t[4] = (uint64_t)(top >> 64);
-    }
-    if (t[4] || fr_geq_r(t)) fr_sub_r(t);
-    memcpy(out, t, 32);
-}
-inline void fr_add(const uint64_t a[4], const uint64_t b[4], uint64_t out[4]) {
-    uint64_t t[4]; u128 c = 0;
-    for (int i = 0; i < 4; ++i) { c += (u128)a[i] + b[i]; t[i] = (uint64_t)c; c >>= 64; }
-    if (c || fr_geq_r(t)) fr_sub_r(t);
-    memcpy(out, t, 32);
-}
-inline void fr_wire_to_canonical(const uint64_t in[4], uint64_t out[4]) {    // x 2^-256: Montgomery product with the integer 1
-    const uint64_t one[4] = {1, 0, 0, 0};
-    fr_mul(in, one, out);
-}
 
 // ---- G1 affine (host) -----------------------------------------------------------------------------------------------------
 struct G1 { Fq x, y; bool inf; };

@@ -12,7 +12,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
-#include "host_pairing.h"
+#include "host_fr.h"             // the modulus words, fr_geq_r / fr_sub_r
 #include "host_sha256.h"
 
 namespace kzg_host {

@@ -265,7 +265,7 @@ int32_t lag_begin(kzg_ctx* ctx, const kzg_srs* shard, size_t base, const void* e
     lp.d_evals = on_device ? evals : nullptr;
     lp.grouped = grouped;
     lp.on_domain = h_is_one(zn);
-    if (lp.on_domain && !h_domain_index(z, log_n, &lp.m)) { ctx->last_error = "z^n = 1 but z is no power of the domain generator"; return KZG_ERR_ROOT_NOT_FOUND; }
+    if (lp.on_domain && !kzg_host::fr_domain_index(z, log_n, &lp.m)) { ctx->last_error = "z^n = 1 but z is no power of the domain generator"; return KZG_ERR_ROOT_NOT_FOUND; }
     memcpy(pin, z, 32);
     memset(pin + 64, 0, 96);
     if (len == 0) { lp.phase = 1; return KZG_OK; }             // an empty slice contributes zero sums and the identity (no commitment MSM is enqueued either)
@@ -482,9 +482,9 @@ int32_t lag_quotient_eval_on_domain(kzg_ctx* ctx, const uint64_t z[4], const uin
 #undef LAG_TRY
     uint64_t t[4], zi[4], prod[4];
     memcpy(t, pin + 128, 32);
-    h_fr_inv(z, zi);
-    h_fr_mul(t, zi, prod);
-    h_fr_sub(zero, prod, out);
+    kzg_host::fr_inv(z, zi);
+    kzg_host::fr_mul(t, zi, prod);
+    kzg_host::fr_sub(zero, prod, out);
     return KZG_OK;
 }
 

@@ -190,7 +190,7 @@ void multiproof_drop(kzg_srs* srs) {
 }
 
 // ---- the proofs -------------------------------------------------------------------------------------------------------------------
-// called under ctx->mu with the arguments checked (capi.hip kzg_compute_multiproofs)
+// called under ctx->mu with the arguments checked (capi_srs.hip kzg_compute_multiproofs)
 int32_t multiproof_run(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, size_t n, bool eval_form, size_t l, uint64_t* out_xy, uint8_t* out_inf) {
     RoctxRange range("kzg:multiproofs");
     const uint4* shat = nullptr;

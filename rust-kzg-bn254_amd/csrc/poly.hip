@@ -720,7 +720,7 @@ int32_t blob_to_fr_run(kzg_ctx* ctx, const uint8_t* bytes, size_t len, size_t n_
 // stream has been synchronised); the quotient's coefficients are left in ps_set.c.
 // skip_intt: the caller commits the quotient's EVALUATIONS over a Lagrange basis (prover/src/kzg.rs:96-100 applied to the quotient, exactly
 // what the reference's compute_proof_impl does: kzg.rs:176-177), so they stay in set.c as they are.
-// d_resident: the n evaluations (wire) already on the device in a buffer of the caller's (the blob stream's jobs, capi.hip); read in place
+// d_resident: the n evaluations (wire) already on the device in a buffer of the caller's (the jobs of blobstream.hip); read in place
 static int32_t proof_enqueue(kzg_ctx* ctx, PolySet& set, hipStream_t st, NttWorkspace* nttws, const uint64_t* evals, size_t n,
                              const uint64_t z[4], bool want_proof, bool skip_intt = false, const uint4* d_resident = nullptr) {
     RoctxRange range(want_proof ? "kzg:proof:inverses + y + quotient + intt" : "kzg:evaluate:inverses + y");
@@ -765,24 +765,24 @@ static int32_t proof_enqueue(kzg_ctx* ctx, PolySet& set, hipStream_t st, NttWork
     {
         uint64_t* zt = reinterpret_cast<uint64_t*>(pin + 1024);
         memcpy(zt, z, 32);
-        for (int a = 1; a <= log_n; ++a) h_fr_mul(zt + 4 * (a - 1), zt + 4 * (a - 1), zt + 4 * a);
+        for (int a = 1; a <= log_n; ++a) kzg_host::fr_mul(zt + 4 * (a - 1), zt + 4 * (a - 1), zt + 4 * a);
         const uint64_t one_int[4] = {1, 0, 0, 0};
         uint64_t one_w[4], den[4];
-        h_fr_mul(H_FR_R2, one_int, one_w);
-        h_fr_sub(one_w, zt + 4 * log_n, den);                // 1 - z^n (zero: z is on the domain, the device inverts what it needs itself)
+        kzg_host::fr_mul(kzg_host::FR_R2, one_int, one_w);
+        kzg_host::fr_sub(one_w, zt + 4 * log_n, den);                // 1 - z^n (zero: z is on the domain, the device inverts what it needs itself)
         uint64_t* top = zt + 4 * (log_n + 1);
         uint64_t* zit = zt + 4 * (log_n + 2);                // z^-(2^a), a <= log_n: only read when z is on the domain
         uint64_t* cst = zt + 4 * (2 * log_n + 3);            // 1/(i - 1), -1/2, 1/(-i - 1), i = w^(n/4) = 5^((r-1)/4)
         if ((den[0] | den[1] | den[2] | den[3]) == 0) {
             z_on_domain = true;
             memset(top, 0, 32);
-            h_fr_inv(zt, zit);
-            for (int a = 1; a <= log_n; ++a) h_fr_mul(zit + 4 * (a - 1), zit + 4 * (a - 1), zit + 4 * a);
+            kzg_host::fr_inv(zt, zit);
+            for (int a = 1; a <= log_n; ++a) kzg_host::fr_mul(zit + 4 * (a - 1), zit + 4 * (a - 1), zit + 4 * a);
         } else {
-            h_fr_inv(den, top);
+            kzg_host::fr_inv(den, top);
             memset(zit, 0, (size_t)(log_n + 1) * 32);
         }
-        memcpy(cst, h_on_domain_constants(), 96);
+        memcpy(cst, kzg_host::fr_on_domain_constants(), 96);
     }
     if (!ctx->poly_lds_attr_set) {
         KZG_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_poly_inv_small), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -792,15 +792,15 @@ static int32_t proof_enqueue(kzg_ctx* ctx, PolySet& set, hipStream_t st, NttWork
     // z = w^m on a domain of at most 4 096 points (compute_proof_with_known_z_fr_index at the reference's bench sizes): the host finds m,
     // the inverses come from the domain's table 1 / (w^k - 1) -- no inversion chain, no barycentric sum
     uint32_t m_known = NO_INDEX;
-    if (want_proof && z_on_domain && n >= 2 && n <= POLY_SMALL_MAX && h_domain_index(z, log_n, &m_known)) {
+    if (want_proof && z_on_domain && n >= 2 && n <= POLY_SMALL_MAX && kzg_host::fr_domain_index(z, log_n, &m_known)) {
         int32_t*& t1 = ctx->ondomain_inv[log_n];
         if (!t1) {                                           // once per domain size: the chain below at z = 1
             std::vector<uint64_t> z1((size_t)(2 * log_n + 6) * 4, 0);
             const uint64_t one_int[4] = {1, 0, 0, 0};
             uint64_t one_w[4];
-            h_fr_mul(H_FR_R2, one_int, one_w);
+            kzg_host::fr_mul(kzg_host::FR_R2, one_int, one_w);
             for (int a = 0; a <= log_n; ++a) { memcpy(&z1[4 * (size_t)a], one_w, 32); memcpy(&z1[4 * (size_t)(log_n + 2 + a)], one_w, 32); }
-            memcpy(&z1[4 * (size_t)(2 * log_n + 3)], h_on_domain_constants(), 96);
+            memcpy(&z1[4 * (size_t)(2 * log_n + 3)], kzg_host::fr_on_domain_constants(), 96);
             uint4* d_z1 = nullptr;
             KZG_HIP_TRY(ctx, hipMalloc(&d_z1, z1.size() * 8));
             hipError_t e1 = hipMalloc(&t1, (size_t)NL * n * 4);
@@ -960,7 +960,7 @@ int32_t proof_end(kzg_ctx* ctx, int slot, uint64_t out_xy[8], uint8_t* out_inf, 
 //                                                              path does not cover (z on the domain, more than 2^VB_MAX_LOG elements)
 // Slot 0's buffers and stream.
 int32_t vb_evaluate_setup(kzg_ctx* ctx, size_t packed_len, size_t nb) {
-    static_assert(sizeof(VbBlob) == 16, "VbBlob layout is part of the host interface (capi.hip)");
+    static_assert(sizeof(VbBlob) == 16, "VbBlob layout is part of the host interface (capi_verify.hip VbMeta)");
     PolySet& set = ctx->poly[0];
     NttTables tb;
     int32_t rc = ntt_get_tables(ctx, VB_MAX_LOG, false, &tb);

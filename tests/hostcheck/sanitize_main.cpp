@@ -130,12 +130,12 @@ int main() {
         CHECK(kzg::lag_fold_y(rows, 3, nn, z, y) == 0);
         uint64_t sum[4], zn[4], t[4], n_m[4], n_inv[4], want[4];
         const uint64_t n_plain[4] = {nn, 0, 0, 0};
-        kzg::h_fr_add(S[0], S[1], sum); kzg::h_fr_add(sum, S[2], sum);
+        kzg_host::fr_add(S[0], S[1], sum); kzg_host::fr_add(sum, S[2], sum);
         memcpy(zn, z, 32);
         for (int q = 0; q < 3; ++q) orc_f_mul(1, zn, zn, zn);        // z^8
-        kzg::h_fr_sub(zn, FR_ONE_M, t);
+        kzg_host::fr_sub(zn, FR_ONE_M, t);
         orc_f_mul(1, n_m, n_plain, FR_R2);
-        kzg::h_fr_inv(n_m, n_inv);
+        kzg_host::fr_inv(n_m, n_inv);
         orc_f_mul(1, want, sum, t); orc_f_mul(1, want, want, n_inv);
         CHECK(memcmp(y, want, 32) == 0);
         // the host inversion (binary Euclid) against the Fermat form on every scalar at hand, on 0, 1, r - 1 and on words above r; and the fold's
@@ -143,22 +143,22 @@ int main() {
         for (size_t i = 0; i + 4 <= sc.size() && i < 4 * 64; i += 4) {
             uint64_t a[4], i1[4], i2[4], back[4];
             orc_f_mul(1, a, sc.data() + i, FR_ONE_M);
-            kzg::h_fr_inv(a, i1); kzg::h_fr_inv_fermat(a, i2);
+            kzg_host::fr_inv(a, i1); kzg_host::fr_inv_fermat(a, i2);
             CHECK(memcmp(i1, i2, 32) == 0);
-            kzg::h_fr_mul(a, i1, back);
+            kzg_host::fr_mul(a, i1, back);
             CHECK((a[0] | a[1] | a[2] | a[3]) == 0 || memcmp(back, FR_ONE_M, 32) == 0);
         }
         {
             const uint64_t zero[4] = {0, 0, 0, 0}, big[4] = {~0ULL, ~0ULL, ~0ULL, ~0ULL};
             uint64_t i1[4], i2[4], m1[4];
-            kzg::h_fr_inv(zero, i1); CHECK((i1[0] | i1[1] | i1[2] | i1[3]) == 0);
-            kzg::h_fr_inv(FR_ONE_M, i1); CHECK(memcmp(i1, FR_ONE_M, 32) == 0);
-            kzg::h_fr_sub(zero, FR_ONE_M, m1);
-            kzg::h_fr_inv(m1, i1); CHECK(memcmp(i1, m1, 32) == 0);              // (-1)^-1 = -1
-            kzg::h_fr_inv(big, i1);                                              // 2^256 - 1 = some residue above r: the same inverse as its canonical form
+            kzg_host::fr_inv(zero, i1); CHECK((i1[0] | i1[1] | i1[2] | i1[3]) == 0);
+            kzg_host::fr_inv(FR_ONE_M, i1); CHECK(memcmp(i1, FR_ONE_M, 32) == 0);
+            kzg_host::fr_sub(zero, FR_ONE_M, m1);
+            kzg_host::fr_inv(m1, i1); CHECK(memcmp(i1, m1, 32) == 0);              // (-1)^-1 = -1
+            kzg_host::fr_inv(big, i1);                                              // 2^256 - 1 = some residue above r: the same inverse as its canonical form
             uint64_t canon[4]; memcpy(canon, big, 32);
-            while (kzg::h_geq_r(canon)) kzg::h_sub_r(canon);
-            kzg::h_fr_inv_fermat(canon, i2);
+            while (kzg_host::fr_geq_r(canon)) kzg_host::fr_sub_r(canon);
+            kzg_host::fr_inv_fermat(canon, i2);
             CHECK(memcmp(i1, i2, 32) == 0);
         }
         for (int lg = 0; lg <= 28; ++lg) {
@@ -168,10 +168,10 @@ int main() {
             CHECK(kzg::lag_fold_y(rows1, 1, (size_t)1 << lg, zz, yy) == 0);
             const uint64_t np[4] = {(uint64_t)1 << lg, 0, 0, 0};
             orc_f_mul(1, nm, np, FR_R2);
-            kzg::h_fr_inv_fermat(nm, ninv);
+            kzg_host::fr_inv_fermat(nm, ninv);
             memcpy(znn, zz, 32);
             for (int q = 0; q < lg; ++q) orc_f_mul(1, znn, znn, znn);
-            kzg::h_fr_sub(znn, FR_ONE_M, tt);
+            kzg_host::fr_sub(znn, FR_ONE_M, tt);
             orc_f_mul(1, want2, S[0], tt); orc_f_mul(1, want2, want2, ninv);
             CHECK(memcmp(yy, want2, 32) == 0);
         }
@@ -193,7 +193,7 @@ int main() {
         CHECK(kzg::lag_fold_proof(parts, 3, nn, FR_ONE_M, got, &ginf) == 0 && ginf == 0);
         // expectation through the oracle: P0 + P1 + P2 + [-(T0 + T1 + T2)] P5   (1/z = 1)
         uint64_t zero[4] = {0, 0, 0, 0}, negsum[4], term[8], bases2[4 * 8], ones[4 * 4], expect[8];
-        kzg::h_fr_sub(zero, sum, negsum);
+        kzg_host::fr_sub(zero, sum, negsum);
         for (int g2 = 0; g2 < 3; ++g2) { memcpy(bases2 + 8 * g2, pts.data() + 8 * g2, 64); memcpy(ones + 4 * g2, FR_ONE_M, 32); }
         memcpy(bases2 + 24, pts.data() + 8 * 5, 64); memcpy(ones + 12, negsum, 32);
         CHECK(orc_msm_naive(bases2, ones, 4, expect) == 0);

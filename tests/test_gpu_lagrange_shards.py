@@ -351,7 +351,7 @@ def test_randomised_soak_of_the_lagrange_shards():
 
 def test_large_host_buffer_commitments_in_two_parts(k):
     """One call at a time from HOST buffers, 2^19 elements: kzg_commit_coeff_form, and over a cached Lagrange basis kzg_commit_eval_form /
-    kzg_commit_blob, go in TWO parts on two slots (the second part's upload hidden behind the first part's kernels; capi.hip msm_srs_common).
+    kzg_commit_blob, go in TWO parts on two slots (the second part's upload hidden behind the first part's kernels; capi.hip msm_srs_locked).
     Coefficient form against sum_i c_i tau^i G1 by big integers; the eval / blob forms against the SAME calls on an SRS handle without the
     cached basis (IFFT + monomial MSM in one part: an independent path); a ragged blob whose tail falls into the second part."""
     n = 1 << 19

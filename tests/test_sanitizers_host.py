@@ -41,3 +41,13 @@ def test_transcript_generator_and_two_stream_sha_under_asan_ubsan(tmp_path):
     subprocess.check_call(["g++", "-std=c++17", *SAN, "-DTRANSCRIPT_SELF_CHECK", "-I" + CSRC, os.path.join(HERE, "hostcheck", "transcriptcheck.cpp"), "-o", exe])
     r = subprocess.run([exe], capture_output=True, text=True, env=ENV, timeout=600)
     assert r.returncode == 0 and "transcript self-check ok" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
+
+
+def test_host_pool_alone_under_thread_sanitizer(tmp_path):
+    """csrc/host_pool.h by itself (no GPU library around it) under ThreadSanitizer: n = 0 / 1 / fewer jobs than threads / 1000 jobs each run exactly once,
+    200 back-to-back runs on 2, 8, 3 threads in turn (late wakers of an old generation meet a run that wants fewer threads), two callers at once."""
+    exe = str(tmp_path / "poolcheck_tsan")
+    subprocess.check_call(["g++", "-std=c++17", "-fsanitize=thread", "-fno-omit-frame-pointer", "-g", "-O1", "-I" + CSRC,
+                           os.path.join(HERE, "hostcheck", "poolcheck.cpp"), "-lpthread", "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1:exitcode=66"), timeout=600)
+    assert r.returncode == 0 and r.stdout.strip() == "poolcheck ok" and "ThreadSanitizer" not in r.stderr, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
