@@ -8,6 +8,7 @@
 #include <mutex>
 #include <string>
 #include "../../include/kzg_bn254_mi355x.h"
+#include "msm_plan.h"      // MsmBasesShape, msm_batch_capacity
 
 namespace kzg {
 
@@ -100,7 +101,7 @@ struct kzg_ctx {
     bool profiling = false;
     bool lds_attr_set = false;
     bool poly_lds_attr_set = false;
-    uint32_t acc_wave_slots = 3 * 1024;   // resident waves of the accumulate kernel on this device: 3 per SIMD x 4 SIMDs x CUs (set at kzg_ctx_create; make_plan takes 2 of the 3 per SIMD where that pays)
+    uint32_t acc_wave_slots = 3 * 1024;   // resident waves of the accumulate kernel on this device: 3 per SIMD x 4 SIMDs x CUs (set at kzg_ctx_create; msm_plan.h make_plan takes 2 of the 3 per SIMD where that pays)
     kzg::MsmWorkspace msm;
     kzg::MsmWorkspace msm_x[KZG_NUM_SLOTS - 1];   // workspaces of slots 1.. of the asynchronous calls
     hipStream_t stream_x[KZG_NUM_SLOTS - 1] = {}; // one stream per slot (slot 0: `stream`), created on first use
@@ -121,7 +122,7 @@ struct kzg_ctx {
     kzg::MsmWorkspace& slot_msm(int slot) { return slot ? msm_x[slot - 1] : msm; }
     kzg::BlobStream* blob_stream = nullptr;    // kzg_commit_and_prove_blob_begin / _end: created on first use
     hipEvent_t last_sorted = nullptr;          // ev_sorted of the most recently enqueued MSM launch of this context ...
-    hipStream_t last_sorted_stream = nullptr;  // ... and the stream it went to (msm.hip msm_enqueue)
+    hipStream_t last_sorted_stream = nullptr;  // ... and the stream it went to (msm.hip enqueue_sort)
     kzg::NttWorkspace& slot_ntt(int slot) { return slot ? ntt_x[slot - 1] : ntt; }
     kzg::DeviceBuffer mp[6];                   // scratch of kzg_compute_multiproofs / kzg_srs_cache_multiproof (multiproof.hip), its own: slot 0's may be in flight
     kzg::NttWorkspace mp_ntt;
@@ -166,15 +167,9 @@ struct kzg_srs {
 
 namespace kzg {
 
-// Bases of one MSM: `points` = first base of the slice; table_stride > 0 selects the precomputed-table mode
-// (tables `table_stride` points apart, window bits c, W tables).
-struct MsmBases {
+// Bases of one MSM: `points` = first base of the slice; the shape (msm_plan.h) selects the mode.
+struct MsmBases : MsmBasesShape {
     const uint4* points = nullptr;
-    uint32_t table_stride = 0;
-    int c = 0;
-    int W = 0;
-    bool bitsum = false;  // tiny MSM: `points` = the per-bit tables, summed directly (k_bitsum_level1 / 2, msm_kernels.h section 6e)
-    bool naf = false;     // `points` = the per-bit tables (Bit_j[i] = 2^j P_i, j < 255, table_stride points apart): width-(c + 1) NAF digits
     bool identity_free = false;   // known: none of the points (of any table) is the identity (kzg_srs::identity_free; caller bases: unknown)
 };
 constexpr int SRS_SMALL_C = 15;                       // window bits of the second table set
@@ -231,7 +226,6 @@ int32_t msm_run_batch(kzg_ctx* ctx, const uint4* d_points, const void* d_scalars
 int32_t srs_precompute(kzg_ctx* ctx, kzg_srs* srs);
 int32_t srs_build_bit_tables(kzg_ctx* ctx, kzg_srs* srs, bool force);
 // `polys` commitments over the first n points of one SRS in one kernel sequence (bases: the SRS's per-bit tables; msm.hip)
-size_t msm_batch_capacity(size_t n);
 int32_t msm_begin_batch(kzg_ctx* ctx, int slot, const MsmBases& bases, const void* const* d_scalars, size_t n, size_t count);
 int32_t msm_end_batch(kzg_ctx* ctx, int slot, size_t count, uint64_t* out_xy, uint8_t* out_inf, uint64_t* out_xyzz);
 int32_t msm_run_batch_tables(kzg_ctx* ctx, const MsmBases& bases, const void* d_scalars, size_t n, size_t polys, uint64_t* out_xy, uint8_t* out_inf);

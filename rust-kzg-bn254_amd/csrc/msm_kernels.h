@@ -19,6 +19,7 @@
 #include "curve_pair.h"
 #include "curve_quad.h"
 #include "naf.h"
+#include "msm_limits.h"
 
 namespace kzg {
 
@@ -32,7 +33,6 @@ __device__ __forceinline__ void latency_bound_kernel() {
 }
 
 constexpr uint32_t DIGIT_NONE = 0xFFFFFFFFu;
-constexpr int RED_T = 512;          // chunks (= threads of the per-window scan block) per window
 
 // -------------------------------------------------------------------------------------------------
 // 1. scalars -> signed digits + histogram
@@ -72,9 +72,6 @@ k_msm_digits(const uint4* __restrict__ scalars, uint32_t n_total, uint32_t n, in
 // -------------------------------------------------------------------------------------------------
 // 2. exclusive scan of the bucket counts: offs[g] = first sorted entry of bucket g, offs[G] = E (entries)
 // -------------------------------------------------------------------------------------------------
-constexpr int SCAN_THREADS = 256;
-constexpr int SCAN_ITEMS = 8;
-constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
 
 // block-wide exclusive scan of one u32 per thread; returns the exclusive prefix, *total = block sum
 template <int T>
@@ -98,8 +95,6 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* total,
 // Every wave owns one contiguous range and walks it 256 counters (one 16-byte load per lane, coalesced) at a time, four such
 // loads in flight; a first walk gives the wave totals, the second one the offsets (the counters come from L2 then).  The
 // thread-per-chunk form before it read 256 B per thread with a stride of 256 B between lanes: 33 us for 2^16 counters.
-constexpr int SCAN1_THREADS = 1024;
-constexpr uint32_t SCAN1_MAX = 1u << 17;
 __device__ __forceinline__ uint4 scan1_load(const uint32_t* __restrict__ count, uint32_t g, uint32_t hi) {
     if (g + 4 <= hi) return *reinterpret_cast<const uint4*>(count + g);
     uint4 v = make_uint4(0, 0, 0, 0);
@@ -291,12 +286,6 @@ k_sort_small_scatter(const uint32_t* __restrict__ digits, uint32_t n_entries, ui
 //   k_sort2_scalars<false>  scalars -> digits -> coarse histogram per tile      k_sort2_scan     bin starts, large-bin tiles
 //   k_sort2_scalars<true>   scalars -> digits -> entries grouped by bin (tmp1)  k_sort2_bin      per bin: fine sort + bucket offsets
 //   k_sort2_hist2 / k_sort2_scatter2: the tiled pass 2 for LARGE bins only (their grids exit at once otherwise)
-constexpr int SORT2_LO_BITS = 7;
-constexpr uint32_t SORT2_LO = 1u << SORT2_LO_BITS;
-constexpr int SORT2_IDX_BITS = 24;
-constexpr uint32_t SORT2_IDX_MASK = (1u << SORT2_IDX_BITS) - 1u;
-constexpr uint32_t SORT2_CHUNK = 4096;          // entries per pass-2 tile of a LARGE bin
-constexpr uint32_t SORT2_MAX_BINS = 512;
 
 // Pass 1 works straight from the scalars: a tile is `tile_s` scalars (W entries each), and both kernels recompute the signed
 // digits instead of going through a W*n digit array (round 2 first half: digits kernel + hist1 + scatter1 moved 284 MB for the
@@ -364,7 +353,6 @@ k_sort2_scalars(const uint4* __restrict__ scalars, uint32_t n, int c, int W, uin
 // polynomial, whose seven sums k_batch_finish turns into the polynomial's commitment.
 // The polynomials of a batched launch may live in separate buffers (a stream of resident scalar sets): p[k] = polynomial k, or all null
 // = one contiguous array `scalars`.
-constexpr int MSM_BATCH_PTRS = 16;
 struct PolyPtrs { const uint4* p[MSM_BATCH_PTRS]; };
 template <int ND>
 __global__ void __launch_bounds__(256)
@@ -429,7 +417,6 @@ k_naf_digits(const uint4* __restrict__ scalars, uint32_t n, int c, uint32_t tile
 // consecutive words (~15 entries per bin and chunk) instead of 64 single words to 64 different lines.  The digits are computed
 // twice (count, place) rather than kept: W values per thread would not stay in registers.
 // LDS entry: bin << 22 | low key << 15 | sign << 14 | window << 9 | scalar index inside the chunk.
-constexpr int SORT2_P1_THREADS = 512;
 static_assert(SORT2_MAX_BINS <= 512 && SORT2_LO_BITS == 7, "LDS entry layout of k_sort2_scatter1_lds");
 template <class F>
 __device__ __forceinline__ void sort2_for_digits(uint32_t k[8], int c, int W, F&& f) {
@@ -564,7 +551,6 @@ k_sort2_scatter1_lds(const uint4* __restrict__ scalars, uint32_t n, int c, int W
 // The cap follows the load: a bin is LARGE above 5/4 of the average bin + 2 048 entries (at most SORT2_BIN_CAP): k_sort2_bin gives
 // every other bin to ONE workgroup, so a bin of twice the average is a tail of twice the kernel's time (NAF mode: the bins that hold
 // a heavy small-key bucket).  *cap_out tells k_sort2_bin.
-constexpr uint32_t SORT2_BIN_CAP = 65536;
 __global__ void __launch_bounds__(512)
 k_sort2_scan(const uint32_t* __restrict__ ccount, uint32_t Hb, uint32_t* __restrict__ cstart, uint32_t* __restrict__ tstart,
              uint32_t* __restrict__ tile_bin, uint32_t* __restrict__ count, uint32_t* __restrict__ cap_out) {
@@ -650,9 +636,6 @@ k_sort2_scatter2(const uint32_t* __restrict__ tmp1, const uint32_t* __restrict__
 // the fine counts that k_sort2_hist2 gathered into offsets; k_sort2_scatter2 then moves its entries.
 // The scatter goes through LDS: a chunk of SORT2_BIN_CHUNK entries is counting-sorted inside the workgroup first, so that a wave
 // writes runs of consecutive positions (lane-per-entry stores of 4 bytes to 64 different lines ran at 2 TB/s of requests).
-constexpr int SORT2_BIN_THREADS = 1024;
-constexpr int SORT2_BIN_PER = 8;                                        // entries per thread and chunk
-constexpr uint32_t SORT2_BIN_CHUNK = SORT2_BIN_THREADS * SORT2_BIN_PER;
 template <bool NAF = false>
 __global__ void __launch_bounds__(SORT2_BIN_THREADS)
 k_sort2_bin(const uint32_t* __restrict__ tmp1, const uint32_t* __restrict__ cstart, uint32_t Hb, const uint32_t* __restrict__ count,
@@ -1587,8 +1570,7 @@ k_red_bits2q(const int32_t* __restrict__ x1, size_t x_stride, uint32_t G1, uint3
 //     commitment is then ~19 dependent point additions deep instead of ~35 (bucket walk + two six-step transforms + the host's 14-bit
 //     double-and-add), and two launches instead of five.
 // -------------------------------------------------------------------------------------------------
-constexpr uint32_t BITSUM_MAX_N = 8192;     // what the kernels take; the default policy (engine.h srs_bases) uses them up to 4 096
-// CHUNK = bit positions per quad (8 / 16 / 32: 32 / 16 / 8 quads per scalar, at most 4 / 8 / 16 dependent mixed additions): chosen by n (msm.hip)
+// CHUNK = bit positions per quad (8 / 16 / 32: 32 / 16 / 8 quads per scalar, at most 4 / 8 / 16 dependent mixed additions): chosen by n (msm_plan.h)
 template <int CHUNK>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KZG_QUAD_SMALL_WAVES, KZG_QUAD_SMALL_WAVES)))
 k_bitsum_level1(const uint4* __restrict__ bits /* Bit_p[i] at (p stride + i) x 64 B */, uint32_t stride, const uint4* __restrict__ scalars, uint32_t n,

@@ -1,5 +1,5 @@
 """-m gpu: an SRS of 2^21 points, beyond the 24 index bits of the two-level sort: MSMs over it run as launches of 2^20 pairs with
-compact indices (msm.hip: msm_launch_len / make_plan, msm_kernels.h: acc_point_index), several launches per call on one stream.
+compact indices (msm_plan.h: msm_launch_len / make_plan, msm_kernels.h: acc_point_index), several launches per call on one stream.
 The reference takes SRS files of up to 2^28 points (prover/src/srs.rs:28-63).  Expected values: sum_i s_i tau^(offset+i) mod r by
 big integers, times G1 (known-tau SRS) -- never another run of the HIP path."""
 import ctypes as C

@@ -242,7 +242,7 @@ def test_eval_form_commitment_and_proofs_at_2_22_and_2_24(k, log_n):
 
 def test_naf_bucket_bits_follow_the_in_flight_state(k):
     """An MSM of 2^18 .. 2^19 - 1 pairs over the per-bit tables runs with 2^14 buckets when nothing else is in flight on its context and
-    with 2^15 when another MSM is (msm.hip make_plan; the reference's bench_kzg_commit_8mb shape is the lone case).  Both plans, at the
+    with 2^15 when another MSM is (msm_plan.h make_plan; the reference's bench_kzg_commit_8mb shape is the lone case).  Both plans, at the
     edges of the range and inside it, against sum_i c_i tau^i G1 by big integers."""
     ctx = k.default_context(); lib = k._lib.load()
     N = 1 << 19

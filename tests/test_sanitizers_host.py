@@ -51,3 +51,13 @@ def test_host_pool_alone_under_thread_sanitizer(tmp_path):
                            os.path.join(HERE, "hostcheck", "poolcheck.cpp"), "-lpthread", "-o", exe])
     r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1:exitcode=66"), timeout=600)
     assert r.returncode == 0 and r.stdout.strip() == "poolcheck ok" and "ThreadSanitizer" not in r.stderr, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
+
+
+def test_msm_planner_and_host_epilogue_under_asan_ubsan(tmp_path):
+    """csrc/msm_plan.h over the whole plan grid (every size threshold, every rejected launch) and csrc/host_msm_epilogue.h over every MSM form, as the
+    stand-alone programs of tests/test_msm_plan_host.py."""
+    for name, last in (("plancheck", "batch_capacity len=16777217 -> 0"), ("epiloguecheck", "epiloguecheck ok")):
+        exe = str(tmp_path / (name + "_san"))
+        subprocess.check_call(["g++", "-std=c++17", *SAN, "-Wno-unknown-pragmas", "-I" + CSRC, os.path.join(HERE, "hostcheck", name + ".cpp"), "-o", exe])
+        r = subprocess.run([exe], capture_output=True, text=True, env=ENV, timeout=600)
+        assert r.returncode == 0 and r.stdout.splitlines()[-1] == last, (name, r.stdout[-500:], r.stderr[-3000:])

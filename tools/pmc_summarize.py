@@ -17,7 +17,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the sources k_msm_accumulate is compiled from: the summary is stamped with their digest, and bench.py reports `roofline.traffic` as
 # stale (null + the reason) when the tree no longer matches -- the one figure of the line the run does not produce itself
-KERNEL_SOURCES = ("msm_kernels.h", "msm.hip", "curve.h", "field29.h", "fe_asm.h")
+KERNEL_SOURCES = ("msm_kernels.h", "msm_limits.h", "msm.hip", "msm_plan.h", "curve.h", "field29.h", "fe_asm.h")
 
 
 def kernel_sources_sha256(root=ROOT):
