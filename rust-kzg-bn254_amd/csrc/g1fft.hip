@@ -22,6 +22,7 @@
 #include "naf.h"
 #include "glv.h"
 #include "host_curve.h"
+#include "g1fft_plan.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -33,32 +34,6 @@
 
 namespace kzg {
 
-// the ONE inversion behind every batched affine conversion: Bernstein-Yang division steps (fe_invert.h: ~20 us on a lone lane) instead of
-// a^(m-2) (381 dependent products, ~175 us).  -DKZG_INVERT_FERMAT restores the exponentiation (A/B).
-template <class F>
-__device__ __forceinline__ void fe_inverse_fermat(Fe<F>& out, const Fe<F>& a) {
-#if !defined(KZG_INVERT_FERMAT)
-    fe_inverse_safegcd(out, a);
-#else
-    Fe<F> acc, base = a;
-    fe_set_one(acc);
-    uint32_t e[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) e[j] = F::P32[j];
-    e[0] -= 2u;
-    for (int w = 0; w < 8; ++w) {
-        uint32_t bits = e[w];
-        for (int b = 0; b < 32; ++b) {
-            if (w == 7 && b >= 30) break;
-            if (bits & 1u) fe_mul(acc, acc, base);
-            fe_sqr(base, base);
-            bits >>= 1;
-        }
-    }
-    out = acc;
-#endif
-}
-
 __device__ __forceinline__ void tw_load(Fr& w, const NttTables& tb, uint32_t E) {
 #pragma unroll
     for (int j = 0; j < NL; ++j) w.l[j] = tb.lo[(size_t)j * tb.lo_len + (E & (tb.lo_len - 1))];
@@ -69,6 +44,12 @@ __device__ __forceinline__ void tw_load(Fr& w, const NttTables& tb, uint32_t E) 
         for (int j = 0; j < NL; ++j) h.l[j] = tb.hi[(size_t)j * tb.hi_len + eh];
         fe_mul(w, w, h);
     }
+}
+
+// k = entry e of a scalar table (k_g1fft_scalars): eight words
+__device__ __forceinline__ void scal_load(uint32_t k[8], const uint4* __restrict__ scal, uint32_t e) {
+    const uint4 lo = scal[2 * (size_t)e], hi = scal[2 * (size_t)e + 1];
+    k[0] = lo.x; k[1] = lo.y; k[2] = lo.z; k[3] = lo.w; k[4] = hi.x; k[5] = hi.y; k[6] = hi.z; k[7] = hi.w;
 }
 
 // scal[e] = the GLV halves (glv_decompose) of the canonical integer of w^-e, or of w^-e / n (scaled != 0), e < n: the scalars of every stage
@@ -138,8 +119,8 @@ k_g1fft_direct(const int32_t* __restrict__ x, int32_t* __restrict__ y, uint32_t 
         if (e == 0 && !last) {
             term = v;
         } else {
-            const uint4 lo = scal[2 * (size_t)e], hi = scal[2 * (size_t)e + 1];
-            const uint32_t k[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+            uint32_t k[8];
+            scal_load(k, scal, e);
             xyzz_scalar_mul(term, v, k);
         }
     }
@@ -175,8 +156,8 @@ k_g1fft_stage(int32_t* __restrict__ planes, uint32_t n, int log_n, int s, const 
     xyzz_load(B, planes, n, i1);
     const uint32_t E = j << (log_n - s);                 // w_n^(-j n/m)
     if (last) {                                          // (A +- [w]B) / n = [1/n]A +- [w/n]B: both products in this stage
-        const uint4 l0 = scal[0], h0 = scal[1];
-        const uint32_t k0[8] = {l0.x, l0.y, l0.z, l0.w, h0.x, h0.y, h0.z, h0.w};
+        uint32_t k0[8];
+        scal_load(k0, scal, 0);
         Xyzz a2;
         xyzz_scalar_mul(a2, A, k0);
         A = a2;
@@ -184,8 +165,8 @@ k_g1fft_stage(int32_t* __restrict__ planes, uint32_t n, int log_n, int s, const 
     if (E == 0 && !last) {
         t = B;
     } else {
-        const uint4 lo = scal[2 * (size_t)E], hi = scal[2 * (size_t)E + 1];
-        const uint32_t k[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        uint32_t k[8];
+        scal_load(k, scal, E);
         xyzz_scalar_mul(t, B, k);
     }
     Xyzz r0, r1, tn = t;
@@ -264,8 +245,7 @@ k_g1fft_direct_pairs(const int32_t* __restrict__ x, int32_t* __restrict__ y, uin
         const uint32_t e = (uint32_t)(((unsigned long long)p * jp << log_s) + (unsigned long long)nr * j * jp) & (n - 1);
         half_load(term, x, n, (size_t)q + ((size_t)(R * p + jp) << log_s), odd);
         if (!(e == 0 && !last)) {
-            const uint4 lo = scal[2 * (size_t)e], hi = scal[2 * (size_t)e + 1];
-            k[0] = lo.x; k[1] = lo.y; k[2] = lo.z; k[3] = lo.w; k[4] = hi.x; k[5] = hi.y; k[6] = hi.z; k[7] = hi.w;
+            scal_load(k, scal, e);
             plain = false;
         }
     }
@@ -294,7 +274,7 @@ k_g1fft_direct_pairs(const int32_t* __restrict__ x, int32_t* __restrict__ y, uin
 // per step 3 + 3 + 4 per two bits); the products
 // [k] x of all (output, term) slots go to a partial array and k_g1fft_sum_partials adds the R = 2^K terms of an output (a wave holds 16 quads,
 // so the tree no longer fits the multiplying wave for R = 32).  r = [k] p, k as its GLV halves; every lane of a quad holds the same k.
-__device__ __forceinline__ void quad_scalar_mul(QuadXyzz& r, const QuadXyzz& p, const uint32_t kk[8], uint32_t q, int32_t* __restrict__ tab /* this lane's LDS column: word (entry 9 + limb) 256 */) {
+__device__ __forceinline__ void quad_scalar_mul(QuadXyzz& r, const QuadXyzz& p, const uint32_t kk[8], uint32_t q) {
     const uint32_t s1 = kk[3] >> 31, s2 = kk[7] >> 31;
     Fq beta, kin, bx, y1, y2;
     {
@@ -313,56 +293,18 @@ __device__ __forceinline__ void quad_scalar_mul(QuadXyzz& r, const QuadXyzz& p, 
     fe_select(P1.c, q == 1u, y1, p.c);
     fe_select(P2.c, q == 1u, y2, p.c);
     fe_select(P2.c, q == 0u, bx, P2.c);
-#if defined(KZG_G1FFT_QUAD_W1)
-    // one bit of each half per step: a doubling and an addition of P1, P2 or P1 + P2 (7 products deep per bit)
-    QuadXyzz S;
-    quad_add(S, P1, P2, q);
-    QuadXyzz acc;
-    quad_set_inf(acc);
-#pragma unroll 1
-    for (int i = 126; i >= 0; --i) {
-        QuadXyzz t;
-        quad_dbl_any(t, acc, q);
-        acc = t;
-        const uint32_t b1 = (kk[i >> 5] >> (i & 31)) & 1u, b2 = (kk[4 + (i >> 5)] >> (i & 31)) & 1u;
-        QuadXyzz op;
-        const bool both = b1 & b2;
-        fe_select(op.c, both, S.c, b1 ? P1.c : P2.c);
-        op.inf = p.inf || (both ? S.inf : !(b1 | b2));
-        quad_add(t, acc, op, q);
-        acc = t;
-    }
-    r = acc;
-#else
     // TWO bits of each half per step: two doublings and ONE addition of T[a + 4 b] = a P1 + b P2, a, b < 4 (3 + 3 + 4 = 10 products deep per two
     // bits instead of 14).  On a quad a point is nine words per lane, so the fifteen table points of a lane stay in registers (135 VGPRs)
-    // and the entry is picked with a v_cndmask tree.  -DKZG_G1FFT_QUAD_LDS keeps them in a 540-byte LDS column per lane instead (144 KiB per
-    // workgroup, nine ds_read_b32 per step issued ahead of the doublings): 195 instead of 288 VGPRs, the SAME time per stage (measured:
-    // 0.728 / 0.975 / 1.428 ms against 0.729 / 0.978 / 1.441 ms at 512 / 1 024 / 2 048 points) -- the selects are not what a stage waits for.
+    // and the entry is picked with a v_cndmask tree (keeping them in an LDS column per lane instead measured the same time per stage: docs/history).
     // No entry is the identity unless p is (a + b lambda != 0 mod r for these a, b): one flag for all.
     QuadXyzz t, u;
-#if !defined(KZG_G1FFT_QUAD_LDS)
     Fq T[16];                                                      // T[0] unused
-#define QTAB_PUT(e, v) T[e] = (v)
-#define QTAB_GET(dst, e) dst = T[e]
-#else
-    auto tab_put = [&](int e, const Fq& v) {
-#pragma unroll
-        for (int j = 0; j < NL; ++j) tab[(e * NL + j) * 256] = v.l[j];
-    };
-    auto tab_get = [&](Fq& v, uint32_t e) {
-#pragma unroll
-        for (int j = 0; j < NL; ++j) v.l[j] = tab[(e * NL + j) * 256];
-    };
-#define QTAB_PUT(e, v) tab_put(e, v)
-#define QTAB_GET(dst, e) tab_get(dst, e)
-#endif
-    QTAB_PUT(1, P1.c); QTAB_PUT(4, P2.c);
+    T[1] = P1.c; T[4] = P2.c;
     Fq p1x2, p1x3, p2x2, p2x3;
-    quad_dbl_any(t, P1, q); p1x2 = t.c; QTAB_PUT(2, t.c);
-    quad_add(u, t, P1, q); p1x3 = u.c; QTAB_PUT(3, u.c);
-    quad_dbl_any(t, P2, q); p2x2 = t.c; QTAB_PUT(8, t.c);
-    quad_add(u, t, P2, q); p2x3 = u.c; QTAB_PUT(12, u.c);
+    quad_dbl_any(t, P1, q); p1x2 = t.c; T[2] = t.c;
+    quad_add(u, t, P1, q); p1x3 = u.c; T[3] = u.c;
+    quad_dbl_any(t, P2, q); p2x2 = t.c; T[8] = t.c;
+    quad_add(u, t, P2, q); p2x3 = u.c; T[12] = u.c;
 #pragma unroll
     for (int bb = 1; bb < 4; ++bb)
 #pragma unroll
@@ -371,7 +313,7 @@ __device__ __forceinline__ void quad_scalar_mul(QuadXyzz& r, const QuadXyzz& p, 
             x.c = aa == 1 ? P1.c : aa == 2 ? p1x2 : p1x3; x.inf = p.inf;
             y.c = bb == 1 ? P2.c : bb == 2 ? p2x2 : p2x3; y.inf = p.inf;
             quad_add(t, x, y, q);
-            QTAB_PUT(aa + 4 * bb, t.c);
+            T[aa + 4 * bb] = t.c;
         }
     QuadXyzz acc;
     quad_set_inf(acc);
@@ -385,7 +327,6 @@ __device__ __forceinline__ void quad_scalar_mul(QuadXyzz& r, const QuadXyzz& p, 
         h1[0] <<= 2; h2[0] <<= 2;
         const uint32_t idx = a | (b << 2);
         QuadXyzz op;
-#if !defined(KZG_G1FFT_QUAD_LDS)
         // 16-way select as a binary tree over the index bits (entry 0 never used as a point: op.inf covers it)
         Fq s8[8], s4[4], s2[2];
 #pragma unroll
@@ -395,19 +336,13 @@ __device__ __forceinline__ void quad_scalar_mul(QuadXyzz& r, const QuadXyzz& p, 
 #pragma unroll
         for (int m = 0; m < 2; ++m) fe_select(s2[m], (idx & 4u) != 0, s4[2 * m + 1], s4[2 * m]);
         fe_select(op.c, (idx & 8u) != 0, s2[1], s2[0]);
-#else
-        QTAB_GET(op.c, idx ? idx : 1u);                            // issued before the doublings: the reads are back when the addition needs them
-#endif
         op.inf = p.inf || idx == 0u;
         quad_dbl_any(t, acc, q);
         quad_dbl_any(acc, t, q);
         quad_add(t, acc, op, q);
         acc = t;
     }
-#undef QTAB_PUT
-#undef QTAB_GET
     r = acc;
-#endif
 }
 
 // slot (o, j') of a direct stage of radix R = 2^K (the index rule of k_g1fft_direct_pairs): partial[o R + j'] = [w^-e (/ n)] x[input]
@@ -429,15 +364,13 @@ k_g1fft_mul_quads(const int32_t* __restrict__ x, int32_t* __restrict__ partial, 
         const uint32_t e = (uint32_t)(((unsigned long long)p * jp << log_s) + (unsigned long long)nr * j * jp) & (n - 1);
         quad_load(term, x, n, (size_t)qq + ((size_t)(R * p + jp) << log_s), q);
         if (!(e == 0 && !last)) {
-            const uint4 lo = scal[2 * (size_t)e], hi = scal[2 * (size_t)e + 1];
-            k[0] = lo.x; k[1] = lo.y; k[2] = lo.z; k[3] = lo.w; k[4] = hi.x; k[5] = hi.y; k[6] = hi.z; k[7] = hi.w;
+            scal_load(k, scal, e);
             plain = false;
         }
     }
-    extern __shared__ int32_t qtab[];                             // -DKZG_G1FFT_QUAD_LDS: 16 entries x 9 words x 256 lanes; unused (size 0) otherwise
     if (!__all(plain)) {                                          // wave-uniform: the multiplication runs for the whole wave or not at all
         QuadXyzz m;
-        quad_scalar_mul(m, term, k, q, qtab + threadIdx.x);
+        quad_scalar_mul(m, term, k, q);
         if (!plain) term = m;
     }
     if (active) quad_store(partial, (size_t)n * R, (size_t)o * R + jp, term, q);
@@ -457,8 +390,8 @@ k_g1fft_stage_pairs(int32_t* __restrict__ planes, uint32_t n, int log_n, int s, 
     if (!active) { half_set_inf(A); half_set_inf(B); }
     const uint32_t E = j << (log_n - s);
     if (last) {                                                   // (A +- [w]B) / n = [1/n]A +- [w/n]B
-        const uint4 l0 = scal[0], h0 = scal[1];
-        const uint32_t k0[8] = {l0.x, l0.y, l0.z, l0.w, h0.x, h0.y, h0.z, h0.w};
+        uint32_t k0[8];
+        scal_load(k0, scal, 0);
         HalfXyzz a2;
         pair_scalar_mul(a2, A, k0, odd);
         A = a2;
@@ -466,8 +399,8 @@ k_g1fft_stage_pairs(int32_t* __restrict__ planes, uint32_t n, int log_n, int s, 
     const bool plain = E == 0 && !last;
     tB = B;
     if (!__all(plain)) {
-        const uint4 lo = scal[2 * (size_t)E], hi = scal[2 * (size_t)E + 1];
-        const uint32_t k[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        uint32_t k[8];
+        scal_load(k, scal, E);
         HalfXyzz m;
         pair_scalar_mul(m, B, k, odd);
         if (!plain) tB = m;
@@ -510,8 +443,8 @@ k_g1fft_first_tables(const uint4* __restrict__ tables, uint32_t table_stride, in
     // signed c-bit digit number w of the canonical scalar (the MSM's digit rule: k_msm_digits)
     uint32_t mag = 0, neg = 0;
     {
-        const uint4 lo = scal_canon[2 * (size_t)e], hi = scal_canon[2 * (size_t)e + 1];
-        uint32_t k[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        uint32_t k[8];
+        scal_load(k, scal_canon, e);
         const uint32_t mask = (1u << c) - 1u, half = 1u << (c - 1);
         uint32_t carry = 0;
         for (uint32_t ww = 0; ww <= w; ++ww) {
@@ -566,7 +499,6 @@ k_g1fft_first_tables(const uint4* __restrict__ tables, uint32_t table_stride, in
 // (pair_madd, 5 multiplications per lane); a wave holds 32 slots of one output and leaves their sum; k_g1fft_sum_partials adds the
 // <= 32 waves of an output.  Same group elements as the staged transform.
 constexpr uint32_t NAF2_MAX = 128;                       // digit slots per scalar (width-4 NAF of a scalar < 2^254: at most 254 / 4 + 1 = 64)
-constexpr uint32_t G1FFT_T3_MAX = 2048;                  // the x3 tables cover the first min(SRS length, 2048) points: every point the table paths transform
 // The odd multiples 3, 5, 7 of Bit_p[j] as XYZZ planes: k_g1fft_to_affine turns them into the tables.  3 x 255 x t3_points points (100 MB at
 // 2 048), once per SRS (kzg_srs::d_t3, ::t3_n).
 __global__ void __launch_bounds__(256)
@@ -595,8 +527,8 @@ __global__ void __launch_bounds__(64)
 k_g1fft_naf2(const uint4* __restrict__ scal_canon, uint32_t n, uint16_t* __restrict__ list, uint32_t* __restrict__ cnt) {
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
-    const uint4 lo = scal_canon[2 * (size_t)e], hi = scal_canon[2 * (size_t)e + 1];
-    uint32_t k[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    uint32_t k[8];
+    scal_load(k, scal_canon, e);
     uint32_t m = 0;
     // width-4 NAF (round 4; width 3 before): digits +-1, +-3, +-5, +-7 (key = 0 .. 3), ~51 per scalar instead of ~64; a digit with key > 0
     // reads the table of that odd multiple.  Entry: position (8 bits) | key << 8 | sign << 15
@@ -728,7 +660,7 @@ k_g1fft_to_affine(const int32_t* __restrict__ planes, uint32_t n, uint4* __restr
         fe_mul(run, run, d);
     }
     Fq rinv;
-    fe_inverse_fermat(rinv, run);
+    fe_inverse_safegcd(rinv, run);                          // the ONE inversion behind every batched affine conversion: Bernstein-Yang division steps (fe_invert.h), ~20 us on a lone lane
     const uint32_t cnt = (n - 1 - t) / T + 1;
     for (uint32_t k = cnt; k-- > 0;) {                    // backward: inv_i = rinv * prefix_i; rinv *= d_i
         const uint32_t i = t + k * T;
@@ -748,10 +680,13 @@ k_g1fft_to_affine(const int32_t* __restrict__ planes, uint32_t n, uint4* __restr
 struct ScalKey { int dev, log_n, scaled; bool operator<(const ScalKey& o) const { return dev != o.dev ? dev < o.dev : (log_n != o.log_n ? log_n < o.log_n : scaled < o.scaled); } };   // scaled: bit 0 = times 1/n, bits 1-2 = canon, bit 3 = forward (w^+e)
 static std::map<ScalKey, uint4*> g_scal;
 static std::mutex g_scal_mu;
-// forward: the scalars of w^+e (the forward transform of g1_fft_planes) instead of w^-e; the kernel reads whichever table it is given
-static int32_t get_scalars(kzg_ctx* ctx, int log_n, bool scaled, const uint4** out, int canon = 0, bool forward = false) {     // canon: 0 GLV halves, 1 canonical integers, 2 wire words
+// key_bits (g1fft_plan.h): G1SCAL_SCALED, canon in bits 1-2 (0 GLV halves, 1 canonical integers, 2 wire words), G1SCAL_FORWARD: the scalars of w^+e
+// (the forward transform of g1_fft_planes) instead of w^-e; the kernel reads whichever table it is given
+static int32_t get_scalars(kzg_ctx* ctx, int log_n, int key_bits, const uint4** out) {
+    const bool scaled = (key_bits & G1SCAL_SCALED) != 0, forward = (key_bits & G1SCAL_FORWARD) != 0;
+    const int canon = (key_bits >> 1) & 3;
     std::lock_guard<std::mutex> lk(g_scal_mu);
-    ScalKey key{ctx->device, log_n, (scaled ? 1 : 0) | (canon << 1) | (forward ? 8 : 0)};
+    ScalKey key{ctx->device, log_n, key_bits};
     auto it = g_scal.find(key);
     if (it != g_scal.end()) { *out = it->second; return KZG_OK; }
     NttTables tb{};
@@ -772,7 +707,7 @@ struct Naf2Lists { uint16_t* list = nullptr; uint32_t* cnt = nullptr; };
 static std::map<std::tuple<int, int, int>, Naf2Lists> g_naf2;
 static int32_t get_naf2(kzg_ctx* ctx, int log_n, bool scaled, Naf2Lists* out) {
     const uint4* sc = nullptr;
-    int32_t rc = get_scalars(ctx, log_n, scaled, &sc, 1);            // canonical integers
+    int32_t rc = get_scalars(ctx, log_n, G1SCAL_CANON | (scaled ? G1SCAL_SCALED : 0), &sc);            // canonical integers
     if (rc != KZG_OK) return rc;
     std::lock_guard<std::mutex> lk(g_scal_mu);
     auto key = std::make_tuple(ctx->device, log_n, scaled ? 1 : 0);
@@ -806,222 +741,6 @@ k_g1fft_planes_to_wire(const int32_t* __restrict__ planes, uint32_t n, uint32_t*
     for (int j = 0; j < 32; j += 4) *reinterpret_cast<uint4*>(out_wire + (size_t)i * 32 + j) = make_uint4(w[j], w[j + 1], w[j + 2], w[j + 3]);
 }
 
-// Stage plan.  A stage is one scalar multiplication deep whatever it computes, so the plan minimises (number of stages) x (time of a
-// stage).  Measured stage times on MI355X (tools/time_g1ifft.py, round 3) while the stage fits ONE wave per SIMD (65536 lanes):
-// 1.25 ms with one lane per point, 0.83 ms on lane pairs; beyond that a stage is throughput bound and scales with its lanes (a lone
-// wave already issues most of what its SIMD can: two pair waves per SIMD took 1.44 ms).  Candidates:
-//   direct stages of radix 2^K (one lane or pair per (output, term): n 2^K lanes or pairs), K <= 5
-//   radix-2 butterflies (n / 2 lanes or pairs, work bound: one multiplication per two outputs)
-// *kmax = 0: radix-2 butterflies; else the largest radix bits of the direct stages.  (Shared by g1_ifft and g1_fft_planes.)
-static void g1fft_choose_plan(size_t n, int log_n, int* kmax_out, bool* pairs_out) {
-    int kmax = 0;
-    bool pairs = false;
-    const double t_lane = 1.25, t_pair = 0.83, cap = 65536.0;
-    double best = 1e300;
-    for (int mode = 0; mode < 2; ++mode) {                        // 0: one lane per point, 1: lane pairs
-        const double t1 = mode ? t_pair : t_lane, width = mode ? 2.0 : 1.0;
-        for (int K = 2; K <= 5 && K <= std::max(log_n, 2); ++K) {  // direct stages
-            const double lanes = (double)n * (double)(1u << K) * width;
-            const double cost = (double)((log_n + K - 1) / K) * t1 * std::max(1.0, lanes / cap);
-            if (cost < best) { best = cost; kmax = K; pairs = mode != 0; }
-        }
-        const double lanes2 = (double)n / 2.0 * width;             // radix-2 butterflies (+ the scaling multiplication of the last stage)
-        const double cost2 = (double)(log_n + 1) * t1 * std::max(1.0, lanes2 / cap);
-        if (cost2 < best) { best = cost2; kmax = 0; pairs = mode != 0; }
-    }
-    *kmax_out = kmax;
-    *pairs_out = pairs;
-}
-
-// The stages of the transform: *result_out = XYZZ planes (stride n) of the Lagrange basis of the first n SRS points, natural order
-static int32_t g1_ifft_stages(kzg_ctx* ctx, const kzg_srs* srs, size_t n, const int32_t** result_out) {
-    int log_n = 0;
-    while (((size_t)1 << log_n) < n) ++log_n;
-    hipStream_t st = ctx->stream;
-    const unsigned gn = (unsigned)((n + 255) / 256);
-    KZG_HIP_TRY(ctx, ctx->poly[0].b.reserve(n * 36 * 4 * 2));                 // two XYZZ plane sets (ping-pong)
-    KZG_HIP_TRY(ctx, ctx->poly[0].a.reserve(n * NL * 4));                     // prefix products of the affine conversion
-    int32_t* bufA = ctx->poly[0].b.as<int32_t>();
-    int32_t* bufB = bufA + n * 36;
-    const uint4 *scal = nullptr, *scal_n = nullptr;
-    int32_t rc = get_scalars(ctx, log_n, false, &scal);
-    if (rc == KZG_OK) rc = get_scalars(ctx, log_n, true, &scal_n);
-    if (rc != KZG_OK) return rc;
-    const int32_t* result = bufA;
-    // 64 .. 256 points of an SRS with per-bit tables: the whole transform as sums of table points (k_g1fft_bits);
-    // 512 .. 2048 points: the FIRST STAGE that way (radix 2^K0 over the SRS points: n 2^K0 x 64 mixed additions at the chip's throughput
-    // instead of a 127-step scalar-multiplication chain), the rest as one or two direct stages on lane quads
-    uint4* const d_bits = srs_bits(srs);
-    const bool whole_by_bits = d_bits && srs->lagrange_of == 0 && n >= 64 && n <= 256;
-    const bool first_by_bits = d_bits && srs->lagrange_of == 0 && n >= 512 && n <= G1FFT_T3_MAX;
-    uint4* d_t3 = nullptr;
-    uint32_t t3_points = 0;
-    if (whole_by_bits || first_by_bits) {
-        std::unique_lock<std::mutex> lazy(srs->lazy_mu);
-        if (!srs->d_t3) {                                                  // x3 tables of the first min(SRS length, 2048) points, once per SRS (<= 33 MB)
-            const uint32_t pts = (uint32_t)std::min<size_t>(srs->n, G1FFT_T3_MAX);
-            const uint32_t total = 3 * 255 * pts;                              // the x3, x5, x7 tables (100 MB at 2 048 points)
-            KZG_HIP_TRY(ctx, ctx->poly[0].c.reserve((size_t)total * 36 * 4));
-            KZG_HIP_TRY(ctx, ctx->poly[0].a.reserve((size_t)total * NL * 4));
-            uint4* t3 = nullptr;
-            KZG_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&t3), (size_t)total * 64));
-            hipError_t e = hipMemsetAsync(t3, 0, (size_t)total * 64, st);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_g1fft_t3_planes, dim3((total + 255) / 256), dim3(256), 0, st, d_bits, (uint32_t)srs->n, pts, total, ctx->poly[0].c.as<int32_t>());
-                const size_t lanes = (total + AFF_PER - 1) / AFF_PER;
-                hipLaunchKernelGGL(k_g1fft_to_affine, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, ctx->poly[0].c.as<int32_t>(), total, t3, 0, ctx->poly[0].a.as<int32_t>());
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) { (void)hipFree(t3); return set_error(ctx, e, "building the x3 tables of g1_ifft"); }
-            srs->d_t3 = t3;
-            srs->t3_n = pts;
-        }
-        d_t3 = srs->d_t3;
-        t3_points = srs->t3_n;
-    }
-    if (whole_by_bits) {
-        Naf2Lists nl;
-        rc = get_naf2(ctx, log_n, true, &nl);
-        if (rc != KZG_OK) return rc;
-        // slices per term: two waves per SIMD in all (n^2 Q / 32 = 2048 waves) -- more waves only add tree additions (every wave ends in a
-        // 5-level tree: a third of the work at 21 digits per pair), fewer leave lone waves at half the issue rate.  Measured: 256 points
-        // 0.71 ms with Q = 4, 0.66 with Q = 1; 128 points 0.28 -> 0.26 (tools/time_g1ifft.py).  The floor is the additions themselves:
-        // n^2 x 85 (5.6 M at 256 points = 0.36 ms of the chip).
-        const uint32_t Q = (uint32_t)std::max<size_t>(1, 65536 / (n * n)), wpo = (uint32_t)(n * Q / 32);
-        KZG_HIP_TRY(ctx, ctx->poly[0].c.reserve((size_t)n * wpo * 36 * 4));
-        int32_t* partial = ctx->poly[0].c.as<int32_t>();
-        hipLaunchKernelGGL(k_g1fft_bits, dim3((unsigned)((n * (size_t)wpo * 64 + 255) / 256)), dim3(256), 0, st, d_bits, (uint32_t)srs->n, d_t3, t3_points, (uint32_t)n,
-                           log_n, log_n, nl.list, nl.cnt, Q, wpo, partial);
-        hipLaunchKernelGGL(k_g1fft_sum_partials, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, st, partial, wpo, (uint32_t)n, bufA);
-        KZG_HIP_TRY(ctx, hipGetLastError());
-        *result_out = bufA;
-        return KZG_OK;
-    }
-    if (first_by_bits) {
-        // Plan (bits of the stages, first one through the per-bit tables): the later stages are one 127-step GLV chain deep each, pure latency
-        // while they fit one wave per SIMD (65 536 lanes = 16 384 quads = n 2^K <= 16 384).  512 = 2^4 . 2^5, 1024 = 2^6 . 2^4, 2048 = 2^5 . 2^3 . 2^3
-        // (measured against 5,4 / 3,3,3 / 5,5 / 4,3,3 / 6,5 / 7,4 and against the later stages on lane pairs: tools/time_g1ifft.py, profiles/r03d_quad.md).
-        int plan[4] = {0, 0, 0, 0}, np = 0;
-        if (log_n == 9) { plan[0] = 4; plan[1] = 5; np = 2; }
-        else if (log_n == 10) { plan[0] = 6; plan[1] = 4; np = 2; }
-        else { plan[0] = 5; plan[1] = 3; plan[2] = 3; np = 3; }
-        const int K0 = plan[0];
-#if !defined(KZG_G1FFT_QUAD_LDS) || defined(KZG_G1FFT_QUAD_W1)
-        constexpr size_t QUAD_TAB_LDS = 0;
-#else
-        constexpr size_t QUAD_TAB_LDS = (size_t)16 * NL * 256 * 4;     // entries 1 .. 15 of every lane (entry 0 unused): 144 KiB of the CU's 160
-        static bool quad_attr_set = false;
-        if (!quad_attr_set) {
-            KZG_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_g1fft_mul_quads), hipFuncAttributeMaxDynamicSharedMemorySize, (int)QUAD_TAB_LDS));
-            quad_attr_set = true;
-        }
-#endif
-        Naf2Lists nl;
-        rc = get_naf2(ctx, log_n, false, &nl);
-        if (rc != KZG_OK) return rc;
-        const size_t R0 = (size_t)1 << K0;
-        const uint32_t Q = (uint32_t)std::max<size_t>(std::max<size_t>(1, 32 / R0), 65536 / (n * R0)), wpo = (uint32_t)(R0 * Q / 32);
-        size_t part_points = (size_t)n * wpo;
-        for (int i = 1; i < np; ++i) part_points = std::max(part_points, n << plan[i]);
-        KZG_HIP_TRY(ctx, ctx->poly[0].c.reserve(part_points * 36 * 4));
-        int32_t* partial = ctx->poly[0].c.as<int32_t>();
-        int32_t* src = bufB;
-        int32_t* dst = bufA;
-        hipLaunchKernelGGL(k_g1fft_bits, dim3((unsigned)((n * (size_t)wpo * 64 + 255) / 256)), dim3(256), 0, st, d_bits, (uint32_t)srs->n, d_t3, t3_points, (uint32_t)n,
-                           log_n, K0, nl.list, nl.cnt, Q, wpo, partial);
-        hipLaunchKernelGGL(k_g1fft_sum_partials, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, st, partial, wpo, (uint32_t)n, src);
-        int done = K0;
-        for (int i = 1; i < np; ++i) {
-            const int K = plan[i];
-            done += K;
-            const int log_s = log_n - done;
-            const bool last = i == np - 1;
-            const size_t slots = n << K;
-            hipLaunchKernelGGL(k_g1fft_mul_quads, dim3((unsigned)((4 * slots + 255) / 256)), dim3(256), QUAD_TAB_LDS, st, src, partial, (uint32_t)n, log_n, K, log_s,
-                               last ? scal_n : scal, last ? 1 : 0);
-            hipLaunchKernelGGL(k_g1fft_sum_partials, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, st, partial, (uint32_t)1 << K, (uint32_t)n, dst);
-            std::swap(src, dst);
-        }
-        KZG_HIP_TRY(ctx, hipGetLastError());
-        *result_out = src;
-        return KZG_OK;
-    }
-    int kmax = 0;
-    bool pairs = false;
-    g1fft_choose_plan(n, log_n, &kmax, &pairs);
-    if (log_n == 0) {
-        hipLaunchKernelGGL(k_g1fft_load, dim3(gn), dim3(256), 0, st, srs->d_points, (uint32_t)n, bufA, 0);
-    } else if (kmax >= 2) {
-        const int stages = (log_n + kmax - 1) / kmax;
-        // the first stage through the SRS window tables when the SRS has them and the stage fits four waves per SIMD
-        // Prefers the narrow (c = 15) set: fewer double-and-add steps per digit.
-        const uint4* tab = nullptr; int tab_c = 0, tab_W = 0;
-        if (srs->lagrange_of == 0) {
-            if (srs->d_small) { tab = srs->d_small; tab_c = srs->small_c; tab_W = srs->small_W; }
-            else if (srs->pre_W > 0) { tab = srs->d_points; tab_c = srs->pre_c; tab_W = srs->pre_W; }
-        }
-        const int K0 = (log_n + stages - 1) / stages;                       // radix bits of the first stage (balanced split)
-        const uint32_t wpo = tab ? (uint32_t)((((size_t)1 << K0) * tab_W + 31) / 32) : 0;
-        const bool first_tables = tab && wpo <= 32 && n * (size_t)wpo <= 4096;
-        if (!first_tables) hipLaunchKernelGGL(k_g1fft_load, dim3(gn), dim3(256), 0, st, srs->d_points, (uint32_t)n, bufA, 0);
-        int done = 0;
-        int32_t* src = bufA;
-        int32_t* dst = bufB;
-        for (int i = 0; i < stages; ++i) {
-            const int K = (log_n - done + (stages - i) - 1) / (stages - i);   // balanced split of the remaining bits
-            done += K;
-            const int log_s = log_n - done;
-            const bool last = i == stages - 1;
-            const size_t lanes = n << K;
-            if (i == 0 && first_tables) {
-                const uint4* sc = nullptr;
-                rc = get_scalars(ctx, log_n, last, &sc, 1);                // canonical scalars (scaled by 1/n when this is also the last stage)
-                if (rc != KZG_OK) return rc;
-                KZG_HIP_TRY(ctx, ctx->poly[0].c.reserve((size_t)n * wpo * 36 * 4));
-                int32_t* partial = ctx->poly[0].c.as<int32_t>();
-                hipLaunchKernelGGL(k_g1fft_first_tables, dim3((unsigned)((n * (size_t)wpo * 64 + 255) / 256)), dim3(256), 0, st, tab, (uint32_t)srs->n, tab_c, tab_W,
-                                   (uint32_t)n, log_n, K, sc, wpo, partial);
-                hipLaunchKernelGGL(k_g1fft_sum_partials, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, st, partial, wpo, (uint32_t)n, dst);
-            } else if (pairs)
-                hipLaunchKernelGGL(k_g1fft_direct_pairs, dim3((unsigned)((2 * lanes + 255) / 256)), dim3(256), 0, st, src, dst, (uint32_t)n, log_n, K, log_s,
-                                   last ? scal_n : scal, last ? 1 : 0);
-            else
-                hipLaunchKernelGGL(k_g1fft_direct, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, src, dst, (uint32_t)n, log_n, K, log_s,
-                                   last ? scal_n : scal, last ? 1 : 0);
-            std::swap(src, dst);
-        }
-        result = src;
-    } else {
-        hipLaunchKernelGGL(k_g1fft_load, dim3(gn), dim3(256), 0, st, srs->d_points, (uint32_t)n, bufA, log_n);
-        for (int s = 1; s <= log_n; ++s) {
-            const bool last = s == log_n;
-            if (pairs)
-                hipLaunchKernelGGL(k_g1fft_stage_pairs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, bufA, (uint32_t)n, log_n, s,
-                                   last ? scal_n : scal, last ? 1 : 0);
-            else
-                hipLaunchKernelGGL(k_g1fft_stage, dim3((unsigned)((n / 2 + 255) / 256)), dim3(256), 0, st, bufA, (uint32_t)n, log_n, s,
-                                   last ? scal_n : scal, last ? 1 : 0);
-        }
-    }
-    KZG_HIP_TRY(ctx, hipGetLastError());
-    *result_out = result;
-    return KZG_OK;
-}
-
-// Lagrange basis of the first n SRS points -> d_out (n affine points: wire format, or the device format of curve.h)
-int32_t g1_ifft_device(kzg_ctx* ctx, const kzg_srs* srs, size_t n, uint4* d_out, bool wire) {
-    const int32_t* result = nullptr;
-    int32_t rc = g1_ifft_stages(ctx, srs, n, &result);
-    if (rc != KZG_OK) return rc;
-    const size_t lanes = std::max<size_t>(1, (n + AFF_PER - 1) / AFF_PER);
-    const unsigned blocks = (unsigned)std::min<size_t>((lanes + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_g1fft_to_affine, dim3(blocks), dim3(256), 0, ctx->stream, result, (uint32_t)n, d_out, wire ? 1 : 0, ctx->poly[0].a.as<int32_t>());
-    KZG_HIP_TRY(ctx, hipGetLastError());
-    return KZG_OK;
-}
-
-// ---- the generic transform (planes in, planes out): the FK20 multi-proofs of multiproof.hip --------------------------------------
 // dst[i] = src[j], j = i or bit-reversed i, 36 limb planes each (src: element j of limb plane k at src[k * src_stride + j])
 __global__ void __launch_bounds__(256)
 k_g1fft_gather_planes(const int32_t* __restrict__ src, size_t src_stride, uint32_t n, int32_t* __restrict__ dst, int bitrev_log) {
@@ -1032,69 +751,6 @@ k_g1fft_gather_planes(const int32_t* __restrict__ src, size_t src_stride, uint32
     for (int k = 0; k < 4 * NL; ++k) dst[(size_t)k * n + i] = src[(size_t)k * src_stride + j];
 }
 
-// out = sum_j w^(+-ij) in[j] (times 1/n if scaled), natural order, n a power of two.  in: n points of XYZZ planes with stride in_stride
-// (in_stride > n: a slice of a longer plane set, read in place by the radix-2 path's bit reversal, copied once for the direct stages);
-// out, tmp: n points each, stride n, neither aliasing in.  The stage plan, the kernels and the scalar tables are g1_ifft's
-// (g1fft_choose_plan, the direct stages on lanes or pairs, radix-2 butterflies); forward transforms use the tables of w^+e.
-// Enqueued on st; no synchronisation.
-int32_t g1_fft_planes(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t n, int32_t* out, int32_t* tmp, bool inverse, bool scaled) {
-    int log_n = 0;
-    while (((size_t)1 << log_n) < n) ++log_n;
-    const unsigned gn = (unsigned)((n + 255) / 256);
-    if (log_n == 0) {                                                        // one point: the transform (and 1/1) is the identity
-        hipLaunchKernelGGL(k_g1fft_gather_planes, dim3(1), dim3(256), 0, st, in, in_stride, 1u, out, 0);
-        KZG_HIP_TRY(ctx, hipGetLastError());
-        return KZG_OK;
-    }
-    const uint4 *scal = nullptr, *scal_last = nullptr;
-    int32_t rc = get_scalars(ctx, log_n, false, &scal, 0, !inverse);
-    if (rc == KZG_OK) rc = scaled ? get_scalars(ctx, log_n, true, &scal_last, 0, !inverse) : KZG_OK;
-    if (rc != KZG_OK) return rc;
-    if (!scaled) scal_last = scal;
-    const int last_flag = scaled ? 1 : 0;                                    // the last stage multiplies every term (1/n folded in)
-    int kmax = 0;
-    bool pairs = false;
-    g1fft_choose_plan(n, log_n, &kmax, &pairs);
-    if (kmax >= 2) {
-        const int stages = (log_n + kmax - 1) / kmax;
-        const int32_t* src = in;
-        if (in_stride != n) {                                                // the direct stages read planes of stride n
-            int32_t* c = (stages & 1) ? tmp : out;
-            hipLaunchKernelGGL(k_g1fft_gather_planes, dim3(gn), dim3(256), 0, st, in, in_stride, (uint32_t)n, c, 0);
-            src = c;
-        }
-        int done = 0;
-        for (int i = 0; i < stages; ++i) {
-            const int K = (log_n - done + (stages - i) - 1) / (stages - i);   // balanced split of the remaining bits (as g1_ifft)
-            done += K;
-            const int log_s = log_n - done;
-            const bool last = i == stages - 1;
-            int32_t* dst = ((stages - 1 - i) & 1) ? tmp : out;              // ping-pong that ends in out
-            const size_t lanes = n << K;
-            if (pairs)
-                hipLaunchKernelGGL(k_g1fft_direct_pairs, dim3((unsigned)((2 * lanes + 255) / 256)), dim3(256), 0, st, src, dst, (uint32_t)n, log_n, K, log_s,
-                                   last ? scal_last : scal, last ? last_flag : 0);
-            else
-                hipLaunchKernelGGL(k_g1fft_direct, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, src, dst, (uint32_t)n, log_n, K, log_s,
-                                   last ? scal_last : scal, last ? last_flag : 0);
-            src = dst;
-        }
-    } else {
-        hipLaunchKernelGGL(k_g1fft_gather_planes, dim3(gn), dim3(256), 0, st, in, in_stride, (uint32_t)n, out, log_n);
-        for (int s = 1; s <= log_n; ++s) {
-            const bool last = s == log_n;
-            if (pairs)
-                hipLaunchKernelGGL(k_g1fft_stage_pairs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out, (uint32_t)n, log_n, s,
-                                   last ? scal_last : scal, last ? last_flag : 0);
-            else
-                hipLaunchKernelGGL(k_g1fft_stage, dim3((unsigned)((n / 2 + 255) / 256)), dim3(256), 0, st, out, (uint32_t)n, log_n, s,
-                                   last ? scal_last : scal, last ? last_flag : 0);
-        }
-    }
-    KZG_HIP_TRY(ctx, hipGetLastError());
-    return KZG_OK;
-}
-
 // n XYZZ planes (stride n) -> n affine points (wire, or the device format of curve.h; identity = zeros), the batched conversion of
 // g1_ifft_device; scratch: n x NL words.  Enqueued on st.
 int32_t g1fft_planes_to_affine(kzg_ctx* ctx, hipStream_t st, const int32_t* planes, size_t n, uint4* d_out, bool wire, int32_t* scratch) {
@@ -1103,6 +759,163 @@ int32_t g1fft_planes_to_affine(kzg_ctx* ctx, hipStream_t st, const int32_t* plan
     hipLaunchKernelGGL(k_g1fft_to_affine, dim3(blocks), dim3(256), 0, st, planes, (uint32_t)n, d_out, wire ? 1 : 0, scratch);
     KZG_HIP_TRY(ctx, hipGetLastError());
     return KZG_OK;
+}
+
+// ---- the driver: plan (g1fft_plan.h), fetch the tables the plan names, reserve from its sizes, walk its stages -----------------------------------
+// what the stages of a plan read and write
+struct G1fftOperands {
+    const uint4* points = nullptr;                  // load: the SRS points
+    const int32_t* in = nullptr;                    // gather, or the first direct stage of an unstrided transform: the caller's planes
+    size_t in_stride = 0;
+    int32_t* buf[2] = {nullptr, nullptr};           // the two plane sets
+    int32_t* partial = nullptr;                     // partial sums (bits, first-tables, quad stages)
+    const uint4* scal[G1SCAL_KEYS] = {};            // scalar tables by key
+    uint32_t srs_n = 0;                             // SRS length: the stride of its tables
+    const uint4* d_bits = nullptr;                  // bits stage: per-bit tables, their x3 / x5 / x7 tables, the digit lists
+    const uint4* d_t3 = nullptr;
+    uint32_t t3_points = 0;
+    Naf2Lists nl;
+    const uint4* tab = nullptr;                     // first-tables stage: the window tables
+};
+
+static int32_t g1fft_fetch_scalars(kzg_ctx* ctx, const G1fftPlan& p, G1fftOperands& io) {
+    for (int i = 0; i < p.n_scal_keys; ++i) {
+        int32_t rc = get_scalars(ctx, p.log_n, p.scal_keys[i], &io.scal[p.scal_keys[i]]);
+        if (rc != KZG_OK) return rc;
+    }
+    return KZG_OK;
+}
+
+// every stage of the plan, enqueued on st
+static int32_t g1fft_launch(kzg_ctx* ctx, hipStream_t st, const G1fftPlan& p, const G1fftOperands& io) {
+    const uint32_t n = p.n;
+    const int log_n = p.log_n;
+    const dim3 block(256);
+    for (int i = 0; i < p.n_stages; ++i) {
+        const G1fftStage& s = p.stage[i];
+        const dim3 grid((unsigned)s.grid);
+        const int32_t* src = s.src == G1BUF_INPUT ? io.in : io.buf[s.src];
+        int32_t* dst = io.buf[s.dst];
+        const uint4* scal = s.scal >= 0 ? io.scal[s.scal] : nullptr;
+        const int last = s.last ? 1 : 0;
+        switch (s.kind) {
+        case G1S_LOAD: case G1S_LOAD_BITREV:
+            hipLaunchKernelGGL(k_g1fft_load, grid, block, 0, st, io.points, n, dst, s.kind == G1S_LOAD_BITREV ? log_n : 0);
+            break;
+        case G1S_GATHER: case G1S_GATHER_BITREV:
+            hipLaunchKernelGGL(k_g1fft_gather_planes, grid, block, 0, st, io.in, io.in_stride, n, dst, s.kind == G1S_GATHER_BITREV ? log_n : 0);
+            break;
+        case G1S_BITS:
+            hipLaunchKernelGGL(k_g1fft_bits, grid, block, 0, st, io.d_bits, io.srs_n, io.d_t3, io.t3_points, n, log_n, s.K, io.nl.list, io.nl.cnt, s.Q, s.wpo, io.partial);
+            break;
+        case G1S_FIRST_TABLES:
+            hipLaunchKernelGGL(k_g1fft_first_tables, grid, block, 0, st, io.tab, io.srs_n, p.tab_c, p.tab_W, n, log_n, s.K, scal, s.wpo, io.partial);
+            break;
+        case G1S_DIRECT:
+            hipLaunchKernelGGL(k_g1fft_direct, grid, block, 0, st, src, dst, n, log_n, s.K, s.log_s, scal, last);
+            break;
+        case G1S_DIRECT_PAIRS:
+            hipLaunchKernelGGL(k_g1fft_direct_pairs, grid, block, 0, st, src, dst, n, log_n, s.K, s.log_s, scal, last);
+            break;
+        case G1S_MUL_QUADS:
+            hipLaunchKernelGGL(k_g1fft_mul_quads, grid, block, 0, st, src, io.partial, n, log_n, s.K, s.log_s, scal, last);
+            break;
+        case G1S_RADIX2:
+            hipLaunchKernelGGL(k_g1fft_stage, grid, block, 0, st, dst, n, log_n, s.log_s, scal, last);
+            break;
+        case G1S_RADIX2_PAIRS:
+            hipLaunchKernelGGL(k_g1fft_stage_pairs, grid, block, 0, st, dst, n, log_n, s.log_s, scal, last);
+            break;
+        case G1S_KINDS:
+            break;
+        }
+        if (s.partials) hipLaunchKernelGGL(k_g1fft_sum_partials, dim3((unsigned)p.sum_grid), block, 0, st, io.partial, s.partials, n, dst);
+    }
+    KZG_HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+
+// The x3, x5, x7 tables of the first `pts` = min(SRS length, 2048) points, once per SRS (100 MB at 2 048 points), built and published under lazy_mu
+static int32_t g1fft_t3_tables(kzg_ctx* ctx, const kzg_srs* srs, const uint4* d_bits, uint32_t pts, G1fftOperands& io) {
+    std::unique_lock<std::mutex> lazy(srs->lazy_mu);
+    if (!srs->d_t3) {
+        hipStream_t st = ctx->stream;
+        const uint32_t total = 3 * 255 * pts;
+        KZG_HIP_TRY(ctx, ctx->poly[0].c.reserve((size_t)total * 36 * 4));
+        KZG_HIP_TRY(ctx, ctx->poly[0].a.reserve((size_t)total * NL * 4));
+        uint4* t3 = nullptr;
+        KZG_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&t3), (size_t)total * 64));
+        hipError_t e = hipMemsetAsync(t3, 0, (size_t)total * 64, st);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_g1fft_t3_planes, dim3((total + 255) / 256), dim3(256), 0, st, d_bits, (uint32_t)srs->n, pts, total, ctx->poly[0].c.as<int32_t>());
+            const size_t lanes = (total + AFF_PER - 1) / AFF_PER;
+            hipLaunchKernelGGL(k_g1fft_to_affine, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, ctx->poly[0].c.as<int32_t>(), total, t3, 0, ctx->poly[0].a.as<int32_t>());
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { (void)hipFree(t3); return set_error(ctx, e, "building the x3 tables of g1_ifft"); }
+        srs->d_t3 = t3;
+        srs->t3_n = pts;
+    }
+    io.d_t3 = srs->d_t3;
+    io.t3_points = srs->t3_n;
+    return KZG_OK;
+}
+
+// The stages of the transform: *result_out = XYZZ planes (stride n) of the Lagrange basis of the first n SRS points, natural order
+static int32_t g1_ifft_stages(kzg_ctx* ctx, const kzg_srs* srs, size_t n, const int32_t** result_out) {
+    G1fftOperands io;
+    io.d_bits = srs_bits(srs);
+    G1fftSrsShape shape;
+    shape.n = srs->n;
+    shape.monomial = srs->lagrange_of == 0;
+    shape.bit_tables = io.d_bits != nullptr;
+    if (srs->d_small) { shape.small_c = srs->small_c; shape.small_W = srs->small_W; }
+    shape.pre_c = srs->pre_c;
+    shape.pre_W = srs->pre_W;
+    const G1fftPlan p = g1fft_plan_ifft(n, shape);
+    int32_t rc = g1fft_fetch_scalars(ctx, p, io);
+    if (rc == KZG_OK && p.t3) rc = g1fft_t3_tables(ctx, srs, io.d_bits, p.t3_points, io);
+    if (rc == KZG_OK && p.naf) rc = get_naf2(ctx, p.log_n, p.naf == 2, &io.nl);
+    if (rc != KZG_OK) return rc;
+    KZG_HIP_TRY(ctx, ctx->poly[0].a.reserve(p.bytes_a));
+    KZG_HIP_TRY(ctx, ctx->poly[0].b.reserve(p.bytes_b));
+    KZG_HIP_TRY(ctx, ctx->poly[0].c.reserve(p.bytes_c));
+    io.points = srs->d_points;
+    io.srs_n = (uint32_t)srs->n;
+    io.tab = p.tab_small ? srs->d_small : srs->d_points;
+    io.buf[0] = ctx->poly[0].b.as<int32_t>();
+    io.buf[1] = io.buf[0] + n * 36;
+    io.partial = ctx->poly[0].c.as<int32_t>();
+    rc = g1fft_launch(ctx, ctx->stream, p, io);
+    *result_out = io.buf[p.result];
+    return rc;
+}
+
+// Lagrange basis of the first n SRS points -> d_out (n affine points: wire format, or the device format of curve.h)
+int32_t g1_ifft_device(kzg_ctx* ctx, const kzg_srs* srs, size_t n, uint4* d_out, bool wire) {
+    const int32_t* result = nullptr;
+    int32_t rc = g1_ifft_stages(ctx, srs, n, &result);
+    if (rc != KZG_OK) return rc;
+    return g1fft_planes_to_affine(ctx, ctx->stream, result, n, d_out, wire, ctx->poly[0].a.as<int32_t>());
+}
+
+// ---- the generic transform (planes in, planes out): the FK20 multi-proofs of multiproof.hip --------------------------------------
+// out = sum_j w^(+-ij) in[j] (times 1/n if scaled), natural order, n a power of two.  in: n points of XYZZ planes with stride in_stride
+// (in_stride > n: a slice of a longer plane set, read in place by the radix-2 path's bit reversal, copied once for the direct stages);
+// out, tmp: n points each, stride n, neither aliasing in.  The stage plan, the kernels and the scalar tables are g1_ifft's
+// (g1fft_plan.h: the direct stages on lanes or pairs, radix-2 butterflies); forward transforms use the tables of w^+e.
+// Enqueued on st; no synchronisation.
+int32_t g1_fft_planes(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t n, int32_t* out, int32_t* tmp, bool inverse, bool scaled) {
+    const G1fftPlan p = g1fft_plan_planes(n, inverse, scaled, in_stride != n);
+    G1fftOperands io;
+    int32_t rc = g1fft_fetch_scalars(ctx, p, io);
+    if (rc != KZG_OK) return rc;
+    io.in = in;
+    io.in_stride = in_stride;
+    io.buf[p.result] = out;                                                  // the plan's ping-pong ends in out
+    io.buf[1 - p.result] = tmp;
+    return g1fft_launch(ctx, st, p, io);
 }
 
 // Up to this many points the one inversion of the affine conversion runs on the HOST (Montgomery's trick over the n points, ~20 us):

@@ -517,17 +517,7 @@ k_vb_prep(const uint4* __restrict__ zs_wire, const VbBlob* __restrict__ meta, ui
     if (o.fallback) return;
     // 1 / den by division steps (fe_invert.h, round 4; a^(r-2) before: 380 dependent products on a lone lane)
     Fr acc;
-#if !defined(KZG_INVERT_FERMAT)
     fe_inverse_safegcd(acc, den);
-#else
-    acc = den;
-#pragma unroll 1
-    for (int bit = 252; bit >= 0; --bit) {
-        fe_sqr(acc, acc);
-        const uint32_t limb = FrParams::P[bit / LB] - (bit / LB == 0 ? 2u : 0u);
-        if ((limb >> (bit % LB)) & 1u) fe_mul(acc, acc, den);
-    }
-#endif
 #pragma unroll
     for (int j = 0; j < NL; ++j) o.tinv[j] = acc.l[j];
 }

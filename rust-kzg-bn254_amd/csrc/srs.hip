@@ -12,30 +12,6 @@
 
 namespace kzg {
 
-template <class F>
-__device__ __forceinline__ void fe_inverse(Fe<F>& out, const Fe<F>& a) {     // a^-1 (0 -> 0): division steps, fe_invert.h (round 4; was a^(m-2))
-#if !defined(KZG_INVERT_FERMAT)
-    fe_inverse_safegcd(out, a);
-#else
-    Fe<F> acc, base = a;
-    fe_set_one(acc);
-    uint32_t e[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) e[j] = F::P32[j];
-    e[0] -= 2u;                                   // both moduli end in ...7 / ...1 with low word >= 2
-    for (int w = 0; w < 8; ++w) {
-        uint32_t bits = e[w];
-        for (int b = 0; b < 32; ++b) {
-            if (w == 7 && b >= 30) break;
-            if (bits & 1u) fe_mul(acc, acc, base);
-            fe_sqr(base, base);
-            bits >>= 1;
-        }
-    }
-    out = acc;
-#endif
-}
-
 // scalars: n canonical 256-bit integers k_i (device, 8 u32 each); out: device affine format
 __global__ void __launch_bounds__(256)
 k_srs_powers(const uint4* __restrict__ scalars_canonical, uint4* __restrict__ out, uint32_t n) {
@@ -65,7 +41,7 @@ k_srs_powers(const uint4* __restrict__ scalars_canonical, uint4* __restrict__ ou
     } else {
         Fq zi, t, x, y;
         fe_mul(t, acc.zz, acc.zzz);
-        fe_inverse(zi, t);                        // 1 / (ZZ ZZZ)
+        fe_inverse_safegcd(zi, t);                // 1 / (ZZ ZZZ): a^-1 (0 -> 0) by division steps, fe_invert.h
         fe_mul(t, zi, acc.zzz);                   // 1 / ZZ
         fe_mul(x, acc.x, t);
         fe_mul(t, zi, acc.zz);                    // 1 / ZZZ
@@ -133,7 +109,7 @@ k_srs_window_step(const uint4* __restrict__ prev, uint4* __restrict__ next, size
         }
         Fq zi, t, x, y;
         fe_mul(t, acc.zz, acc.zzz);
-        fe_inverse(zi, t);
+        fe_inverse_safegcd(zi, t);
         fe_mul(t, zi, acc.zzz);
         fe_mul(x, acc.x, t);
         fe_mul(t, zi, acc.zz);
@@ -174,7 +150,7 @@ k_srs_double_batch(const uint4* __restrict__ prev, uint4* __restrict__ next, siz
         for (int j = 0; j < NL; ++j) pre[(q * NL + j) * 256 + tl] = run.l[j];
     }
     Fq inv;
-    fe_inverse(inv, run);                               // 1 / (product of the lane's denominators)
+    fe_inverse_safegcd(inv, run);                               // 1 / (product of the lane's denominators)
     for (int q = BITS_K - 1; q >= 0; --q) {
         const size_t i = i0 + (size_t)q * lanes;
         if (i >= n) continue;                           // (its denominator was 1)

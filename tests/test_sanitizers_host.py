@@ -61,3 +61,13 @@ def test_msm_planner_and_host_epilogue_under_asan_ubsan(tmp_path):
         subprocess.check_call(["g++", "-std=c++17", *SAN, "-Wno-unknown-pragmas", "-I" + CSRC, os.path.join(HERE, "hostcheck", name + ".cpp"), "-o", exe])
         r = subprocess.run([exe], capture_output=True, text=True, env=ENV, timeout=600)
         assert r.returncode == 0 and r.stdout.splitlines()[-1] == last, (name, r.stdout[-500:], r.stderr[-3000:])
+
+
+def test_g1fft_planner_under_asan_ubsan(tmp_path):
+    """csrc/g1fft_plan.h over the whole plan grid (every SRS shape, every size, every direction of the planes transform), as the stand-alone program of
+    tests/test_g1fft_plan_host.py."""
+    exe = str(tmp_path / "g1fft_plancheck_san")
+    subprocess.check_call(["g++", "-std=c++17", *SAN, "-I" + CSRC, os.path.join(HERE, "hostcheck", "g1fft_plancheck.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, env=ENV, timeout=600)
+    want = open(os.path.join(HERE, "golden", "g1fft_plans.txt")).read()
+    assert r.returncode == 0 and r.stdout == want, (r.stdout[-500:], r.stderr[-3000:])
