@@ -620,6 +620,31 @@ int32_t kzg_verify_multiproof(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t c
                               uint64_t coset_index, const uint64_t* ys_mont, size_t n, size_t chunk_len,
                               const uint64_t* g2_tau_l_mont, int32_t* out_ok);
 
+/* ---- erasure decoding: a polynomial from a subset of its cosets ------------------------------------------------------------------
+ * The cosets are those above: coset k < m = n / chunk_len is {w^(k + j m) : j < chunk_len}, its values ys[j] = f(w^(k + j m)) (row k
+ * of KZG.cosets).  Given `count` DISTINCT cosets -- ys_mont: count x chunk_len x 4 u64, item i being the coset coset_indices[i], in any
+ * order -- the call returns the unique polynomial f of degree < count * chunk_len through those values: out_poly_mont, n x 4 u64
+ * canonical wire words, its evaluations on {w^i} (eval_form = 1) or its n coefficients (eval_form = 0; those from count * chunk_len on
+ * are zero).  *out_consistent = 1 iff deg f < degree_bound, i.e. the values are those of a polynomial below that bound; a failed check
+ * is 0 with KZG_OK and f is still the interpolant.  degree_bound = 0 means count * chunk_len (the flag is then always 1);
+ * out_consistent may be NULL.  Synchronous, host buffers, no SRS.  Equal inputs give equal bits whatever the launch geometry and
+ * whatever the order of the items.
+ * Method: with M the missing cosets and Z(X) = prod_{k in M} (X^l - w^(l k)), f Z has degree < n and known values on the whole
+ * domain (0 on M), so it is one IFFT; f is its quotient by Z on the shifted domain {5 w^i}: four transforms of n points (three for
+ * coefficients), three pointwise passes, and the values of Z as DIRECT products, 2 m (m - count) field products.  That part is
+ * quadratic in m, hence the last error below; the cap leaves every (n, chunk_len) with m <= 2^16 unrestricted and admits a larger m
+ * with proportionally fewer missing cosets.  Device memory: n x 32 B of values, the transforms' workspace (n x 32 B above 2^10
+ * points, 2 n x 32 B above 2^20, which also stages the upload), at most 80 m bytes of indices and vanishing values, at most 9 MiB of partial
+ * products and 72 (2^10 + n / 2^10) bytes of powers of 5.  Nothing proportional to n is computed on the host.
+ * Errors, checked on the host before any kernel runs, in this order: 1. a null pointer -> KZG_ERR_INVALID_ARG; 2. n = 0 or not a
+ * power of two -> KZG_ERR_NOT_POWER_OF_TWO; 3. n > 2^24 -> KZG_ERR_DOMAIN; 4. n = 1, chunk_len not a power of two or > n / 2 ->
+ * KZG_ERR_INVALID_ARG; 5. count = 0 or count > m -> KZG_ERR_INVALID_ARG; 6. an index >= m or a duplicate index ->
+ * KZG_ERR_INVALID_ARG; 7. degree_bound > count * chunk_len (too few cosets) -> KZG_ERR_INVALID_ARG; 8. m * (m - count) > 2^32 ->
+ * KZG_ERR_TOO_LARGE.  After any error the context stays usable. */
+int32_t kzg_recover_from_cosets(kzg_ctx* ctx, const uint64_t* ys_mont, const uint64_t* coset_indices, size_t count, size_t n,
+                                size_t chunk_len, size_t degree_bound, int32_t eval_form, uint64_t* out_poly_mont,
+                                int32_t* out_consistent);
+
 #ifdef __cplusplus
 }
 #endif

@@ -460,7 +460,41 @@ public:
                       srs.context().handle(), (blob.len() + 31) / 32, srs.len());
         return out;
     }
+    // Erasure decoding (kzg_recover_from_cosets; the reference has none): the polynomial of degree < count * l through the values of `count` distinct
+    // cosets of the n-point domain, ys[i l .. (i + 1) l) being the values of coset coset_indices[i] (any order), l = ys.size() / count.  degree_bound = 0
+    // means count * l; values that are not those of a polynomial below the bound are a GenericError.  n evaluations / n coefficients.
+    PolynomialEvalForm recover_from_cosets(const std::vector<uint64_t>& coset_indices, const std::vector<Fr>& ys, size_t n, size_t degree_bound = 0,
+                                           const Context& ctx = Context::default_context()) const {
+        return PolynomialEvalForm::new_(recover_impl(coset_indices, ys, n, degree_bound, 1, ctx));
+    }
+    PolynomialCoeffForm recover_coeff_form_from_cosets(const std::vector<uint64_t>& coset_indices, const std::vector<Fr>& ys, size_t n, size_t degree_bound = 0,
+                                                       const Context& ctx = Context::default_context()) const {
+        return PolynomialCoeffForm::new_(recover_impl(coset_indices, ys, n, degree_bound, 0, ctx));
+    }
 private:
+    static std::vector<Fr> recover_impl(const std::vector<uint64_t>& coset_indices, const std::vector<Fr>& ys, size_t n, size_t degree_bound, int32_t eval_form,
+                                        const Context& ctx) {
+        const size_t count = coset_indices.size();
+        if (count == 0 || ys.empty() || ys.size() % count != 0) throw KzgError::GenericError("ys must hold the same number of values for every coset index");
+        const size_t l = ys.size() / count;
+        if (n < 2 || (n & (n - 1)) != 0) throw KzgError::FFTError("length provided is not a power of 2");
+        if ((l & (l - 1)) != 0) throw KzgError::GenericError("chunk length is not a power of 2");
+        if (l > n / 2) throw KzgError::GenericError("chunk length exceeds half the polynomial length");
+        const size_t m = n / l;
+        if (count > m) throw KzgError::GenericError("the number of cosets must be between 1 and n / chunk length");
+        std::vector<bool> seen(m, false);
+        for (uint64_t k : coset_indices) {
+            if (k >= m || seen[(size_t)k]) throw KzgError::GenericError("coset indices must be distinct and below n / chunk length");
+            seen[(size_t)k] = true;
+        }
+        if (degree_bound > count * l) throw KzgError::GenericError("too few cosets for the degree bound");
+        std::vector<Fr> out(n);
+        int32_t consistent = 0;
+        detail::check(kzg_recover_from_cosets(ctx.handle(), ys.data()->limbs.data(), coset_indices.data(), count, n, l, degree_bound, eval_form, out.data()->limbs.data(),
+                                              &consistent), ctx.handle());
+        if (!consistent) throw KzgError::GenericError("the cosets are not the values of a polynomial below the degree bound");
+        return out;
+    }
     std::vector<Fr> expanded_roots_of_unity_;
 };
 

@@ -167,6 +167,7 @@ PROTOTYPES = {
     "kzg_compute_multiproof_r_powers": (i32, [u64p, sz, u64p, u64p, u64p, u64p, sz, sz, sz, u64p]),
     "kzg_verify_multiproof_batch": (i32, [vp, vp, u64p, sz, u64p, u64p, u64p, u64p, sz, sz, sz, u64p, u64p, C.POINTER(i32)]),
     "kzg_verify_multiproof": (i32, [vp, vp, u64p, u64p, C.c_uint64, u64p, sz, sz, u64p, C.POINTER(i32)]),
+    "kzg_recover_from_cosets": (i32, [vp, u64p, u64p, sz, sz, sz, sz, i32, u64p, C.POINTER(i32)]),
 }
 
 _lib = None

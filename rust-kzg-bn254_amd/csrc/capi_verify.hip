@@ -454,6 +454,21 @@ int32_t kzg_coset_interpolate_rlc(kzg_ctx* ctx, const uint64_t* ys_mont, const u
     return KZG_OK;
 }
 
+// erasure decoding: every check on the host before the context is touched (host_recover.h), then recover.hip
+int32_t kzg_recover_from_cosets(kzg_ctx* ctx, const uint64_t* ys_mont, const uint64_t* coset_indices, size_t count, size_t n, size_t chunk_len,
+                                size_t degree_bound, int32_t eval_form, uint64_t* out_poly_mont, int32_t* out_consistent) {
+    RecoverPlan plan;
+    int32_t rc = recover_plan(!ctx || !ys_mont || !coset_indices || !out_poly_mont, coset_indices, count, n, chunk_len, degree_bound, &plan);
+    if (rc != KZG_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int32_t consistent = 0;
+    rc = recover_run(ctx, plan, ys_mont, eval_form != 0, out_poly_mont, &consistent);
+    if (rc != KZG_OK) return rc;
+    if (out_consistent) *out_consistent = consistent;
+    return KZG_OK;
+}
+
 // accept <=> e(sum_i r_i pi_i, [tau^l]_2) = e(sum_rows R_row C_row - sum_t A_t [tau^t]_1 + sum_i r_i w^(k_i l) pi_i, G2), from
 // pi_i tau^l = C - I_i(tau) + w^(k_i l) pi_i.  For l = 1 this is batch.rs:228-254.
 int32_t kzg_verify_multiproof_batch(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments,

@@ -9,6 +9,7 @@
 #include <string>
 #include "../../include/kzg_bn254_mi355x.h"
 #include "msm_plan.h"      // MsmBasesShape, msm_batch_capacity
+#include "host_recover.h"  // RecoverPlan
 
 namespace kzg {
 
@@ -128,6 +129,9 @@ struct kzg_ctx {
     kzg::NttWorkspace mp_ntt;
     kzg::DeviceBuffer mv[4];                   // kzg_coset_interpolate_rlc / kzg_verify_multiproof_batch (multiverify.hip): values | indices + weights | coefficients | partial rows
     kzg::NttWorkspace mv_ntt;
+    kzg::DeviceBuffer rc[3];                   // kzg_recover_from_cosets (recover.hip): work values | indices, vanishing values, partial products, flag | powers of g
+    int rc_gpow_log = -1;                      // rc[2] holds the factored tables of g^t and g^-t for t < 2^rc_gpow_log (-1: none yet)
+    kzg::NttWorkspace rc_ntt;                  // its `data` also stages the uploaded coset values (dead before the first transform)
 };
 
 struct kzg_srs {
@@ -265,6 +269,9 @@ int32_t multiproof_run(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, si
 void multiproof_drop(kzg_srs* srs);
 // verification of coset proofs (multiverify.hip): d_out[t] = sum_i weights[i] w^(-ks[i] t) IFFT_l(ys_i)[t], enqueued on ctx->stream (d_ys is scratch when l > 1024)
 int32_t coset_interpolate_rlc_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, size_t count, size_t n, size_t l, uint4* d_out);
+// erasure decoding (recover.hip): the polynomial of degree < count l through the values of the plan's cosets (ys: host, count x l wire values), as n
+// coefficients or evaluations on the host; *consistent = its coefficients from plan.degree_bound on are zero.  Called under ctx->mu, synchronised on return
+int32_t recover_run(kzg_ctx* ctx, const RecoverPlan& plan, const uint64_t* ys, bool eval_form, uint64_t* out_poly, int32_t* consistent);
 
 // polynomial pipeline (poly.hip)
 int32_t proof_run(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* evals, size_t n, const uint64_t z[4],

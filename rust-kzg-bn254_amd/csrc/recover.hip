@@ -1,0 +1,327 @@
+// recover.hip — erasure decoding (kzg_recover_from_cosets, capi_verify.hip): from the values of `count` of the m = n / l cosets
+// {w^(k + j m) : j < l} of the n-point domain to the polynomial f of degree < count l through them, as n coefficients or n evaluations.
+// The reference has no coset code; the conventions are those of multiproof.hip and multiverify.hip.
+//
+// With M the missing cosets, z(Y) = prod_{k in M} (Y - w^(l k)) (a polynomial over the m-th roots w^l) and Z(X) = z(X^l), Z vanishes
+// exactly on the missing cosets, so D_i = f(w^i) Z(w^i) is known everywhere: the value times z(w^(l k)) on a present coset k = i mod m,
+// zero on a missing one.  deg f Z < count l + l |M| = n, so IFFT_n(D) is f Z exactly, and f is its quotient by Z taken on the shifted
+// domain {g w^i}, g = 5, where Z(g w^i) = z(s w^(l i)), s = g^l, has no zero (s is not an m-th root of unity: g^n != 1):
+//   1. k_recover_vanish / k_recover_vanish_fold   z on the m points w^(l p) and on the m points s w^(l p); the latter inverted
+//   2. k_recover_scatter                          D (every position written once: no memset, no index of the caller reaches a store)
+//   3. ntt_run inverse                            P = f Z
+//   4. k_recover_scale<0>, ntt_run forward        P_t g^t -> P(g w^i)
+//   5. k_recover_scale<1>                         / z(s w^(l (i mod m)))  -> f(g w^i)
+//   6. ntt_run inverse, k_recover_scale<2>        g^-t -> the coefficients of f; a word of flags ORs "a coefficient from degree_bound on is not zero"
+//   7. ntt_run forward                            when evaluations are asked for
+// Shapes chosen:
+//   * the vanishing values are DIRECT products, 2 m |M| field products (no coefficient form of z, no product tree): one lane per output
+//     point keeps a running product over tiles of 256 roots, staged in LDS as 9 limb planes (every lane reads the same root: an LDS
+//     broadcast).  The roots w_n^(l k) come from the forward tables of the n-point domain (ntt_get_tables).  2 m / 256 workgroups do not
+//     fill the device below m = 2^17, so M is split across blockIdx.y into up to RC_TARGET_GROUPS workgroups in all and the fold multiplies
+//     the partial products: a field product, the same element whatever the split, and canonical words leave the call.
+//   * the m divisors are inverted once: Montgomery's trick per workgroup of 256 (product tree in LDS, one fe_inverse_safegcd), as lagrange.hip.
+//   * g^t and g^-t are factored like the twiddle tables, 2^10 + n / 2^10 entries each (one product per element from 2^10 on), kept per context.
+//   * values stay in the wire residue class a 2^256 between the kernels (the factors are internal Montgomery), as in ntt.hip; every kernel
+//     writes canonical words, so equal inputs give equal bits.
+// Lazy-reduction bounds are written at each site; the boundcheck build counts violations (tests/test_gpu_recover.py).
+// Not tried: the scale passes fused into the first load / last store of the transforms next to them, two running products per lane
+// (fe_mul2), a product tree for m > 2^16, the complement form z = (Y^m - 1) / prod_present.  Measured figures: profiles/recover.md.
+#include "poly_common.h"
+#include "fe_invert.h"
+
+#include <algorithm>
+
+namespace kzg {
+
+constexpr uint32_t RC_THREADS = 256;
+constexpr uint32_t RC_TILE = 256;                  // roots per LDS tile: one per lane to stage
+constexpr int RC_LO_BITS = 10;                     // g^t = glo[t & 1023] ghi[t >> 10]
+constexpr uint32_t RC_LO_LEN = 1u << RC_LO_BITS;
+constexpr uint32_t RC_TARGET_GROUPS = 1024;        // workgroups of k_recover_vanish in all: four waves per SIMD on 256 CUs
+
+struct RcPow { const int32_t* lo; const int32_t* hi; uint32_t hi_len; };
+
+// the 256-bit words of a wire element as limbs, no product: < 2^256 < 5.3 m, normalised
+__device__ __forceinline__ void rc_load_words(Fr& v, const uint4* __restrict__ p, size_t i) {
+    const uint4 lo = p[2 * i], hi = p[2 * i + 1];
+    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    fe_unpack(v, w);
+}
+// v normalised in (-m, 2m) -> canonical words
+__device__ __forceinline__ void rc_store_canon(uint4* __restrict__ p, size_t i, Fr& v) {
+    fe_canon(v);
+    uint32_t o[8];
+    fe_pack(o, v);
+    p[2 * i] = make_uint4(o[0], o[1], o[2], o[3]);
+    p[2 * i + 1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+// g^(+-t), t < 2^10 hi_len, from the factored table: in (-m, 2m), normalised
+__device__ __forceinline__ void rc_gpow(Fr& w, const RcPow& t, uint32_t e) {
+    pl_load(w, t.lo, RC_LO_LEN, e & (RC_LO_LEN - 1));
+    const uint32_t eh = e >> RC_LO_BITS;
+    if (eh != 0) {
+        Fr h;
+        pl_load(h, t.hi, t.hi_len, eh);
+        fe_mul(w, w, h);
+    }
+}
+
+// ---- the power tables: planes[9][len] of g^(t step) (inverse: g^-(t step)), internal form; once per context and size ----------------
+__global__ void __launch_bounds__(RC_THREADS)
+k_recover_gpow_table(int32_t* __restrict__ planes, uint32_t len, uint32_t step, int inverse) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= len) return;
+    Fr one, base, acc;
+    fe_set_one(one);
+    fe_add(base, one, one);                                       // 1 + 1, limbs < 2^30
+    fe_dbl(base, base);                                           // 4: limbs < 2^31
+    fe_norm(base);
+    fe_add(base, base, one);
+    fe_reduce(base);                                              // 5 in (-m, 2m) (|5 * 1| < 5 m)
+    if (inverse) { Fr b = base; fe_inverse_safegcd(base, b); }
+    fe_set_one(acc);
+    for (uint32_t e = t * step; e; e >>= 1) {                     // t step < 2^24
+        if (e & 1u) fe_mul(acc, acc, base);
+        fe_sqr(base, base);
+    }
+    pl_store(planes, len, t, acc);
+}
+
+// ---- 1. vanishing values ---------------------------------------------------------------------------------------------------------------
+struct RcVanishArgs {
+    const uint32_t* missing;    // |M| coset indices < m, ascending
+    uint32_t n_missing, per_split;
+    uint32_t m;
+    int log_l;
+    NttTables tb;               // forward tables of the n-point domain
+    RcPow gp;                   // g^t
+    int32_t* partial;           // gridDim.y rows of 9 planes of 2 m words
+};
+// lane p < 2 m of row blockIdx.y: prod over the row's slice of M of (x_p - w^(l k)), x_p = w^(l p) (p < m) or g^l w^(l (p - m)).  An empty
+// slice (M empty) gives 1.
+__global__ void __launch_bounds__(RC_THREADS)
+k_recover_vanish(RcVanishArgs a) {
+    __shared__ int32_t roots[NL * RC_TILE];
+    const uint32_t tid = threadIdx.x, p = blockIdx.x * RC_THREADS + tid, two_m = 2 * a.m;
+    const uint32_t first = blockIdx.y * a.per_split, last = min(a.n_missing, first + a.per_split);
+    Fr x, acc;
+    fe_set_one(acc);
+    fe_set_zero(x);
+    if (p < two_m) {
+        const uint32_t q = p < a.m ? p : p - a.m;
+        domain_elem(x, a.tb, q << a.log_l);                          // q l < n
+        if (p >= a.m) {
+            Fr s;
+            rc_gpow(s, a.gp, 1u << a.log_l);                         // l <= n / 2: inside the table
+            fe_mul(x, x, s);
+        }
+    }
+#pragma unroll 1
+    for (uint32_t base = first; base < last; base += RC_TILE) {      // uniform across the workgroup
+        const uint32_t cnt = min(RC_TILE, last - base);
+        if (tid < cnt) {
+            Fr w;
+            domain_elem(w, a.tb, a.missing[base + tid] << a.log_l);
+            pl_store(roots, RC_TILE, tid, w);
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (uint32_t r = 0; r < cnt; ++r) {
+            Fr w, d;
+            pl_load(w, roots, RC_TILE, r);
+            fe_sub(d, x, w);                                         // both normalised in (-m, 2m): limbs within +-2^29, |d| < 3 m
+            fe_mul(acc, acc, d);                                     // |acc d| < 2 m * 3 m
+        }
+        __syncthreads();                                             // the next tile overwrites the roots
+    }
+    if (p < two_m) pl_store(a.partial, (size_t)gridDim.y * two_m, (size_t)blockIdx.y * two_m + p, acc);
+}
+
+// lane p < 2 m: the product of its `rows` partial products; p < m: stored (zdom[p] = z(w^(l p))); p >= m: inverted, Montgomery's trick per
+// workgroup (product tree in LDS, one inversion, back down: lagrange.hip), zsinv[p - m] = 1 / z(s w^(l (p - m))).  No divisor is zero.
+__global__ void __launch_bounds__(RC_THREADS)
+k_recover_vanish_fold(const int32_t* __restrict__ partial, uint32_t rows, uint32_t m, int32_t* __restrict__ zdom, int32_t* __restrict__ zsinv) {
+    __shared__ int32_t tree[NL * 2 * RC_THREADS];                    // heap order: root 1, leaves RC_THREADS + t
+    constexpr uint32_t Lf = RC_THREADS, S = 2 * RC_THREADS;
+    const uint32_t t = threadIdx.x, p = blockIdx.x * RC_THREADS + t, two_m = 2 * m;
+    Fr v;
+    fe_set_one(v);
+    if (p < two_m) {
+        pl_load(v, partial, (size_t)rows * two_m, p);
+        for (uint32_t b = 1; b < rows; ++b) {
+            Fr u;
+            pl_load(u, partial, (size_t)rows * two_m, (size_t)b * two_m + p);
+            fe_mul(v, v, u);                                         // both in (-m, 2m)
+        }
+        if (p < m) pl_store(zdom, m, p, v);
+    }
+    if (blockIdx.x * RC_THREADS + RC_THREADS <= m) return;           // no divisor in this workgroup (uniform)
+    if (p < m || p >= two_m) fe_set_one(v);
+    pl_store(tree, S, Lf + t, v);
+    __syncthreads();
+    for (uint32_t s = Lf >> 1; s >= 1; s >>= 1) {                    // up-sweep: node = product of its two children
+        if (t < s) {
+            const uint32_t node = s + t;
+            Fr a, c, r;
+            pl_load(a, tree, S, 2 * node);
+            pl_load(c, tree, S, 2 * node + 1);
+            fe_mul(r, a, c);
+            pl_store(tree, S, node, r);
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        Fr root, ri;
+        pl_load(root, tree, S, 1);
+        fe_inverse_safegcd(ri, root);
+        pl_store(tree, S, 1, ri);
+    }
+    __syncthreads();
+    for (uint32_t s = 1; s < Lf; s <<= 1) {                          // down-sweep: inverse of a child = inverse of the node x its sibling
+        if (t < s) {
+            const uint32_t node = s + t;
+            Fr g, a, c, ia, ic;
+            pl_load(g, tree, S, node);
+            pl_load(a, tree, S, 2 * node);
+            pl_load(c, tree, S, 2 * node + 1);
+            fe_mul2(ia, g, c, ic, g, a);
+            pl_store(tree, S, 2 * node, ia);
+            pl_store(tree, S, 2 * node + 1, ic);
+        }
+        __syncthreads();
+    }
+    if (p >= m && p < two_m) {
+        pl_load(v, tree, S, Lf + t);
+        pl_store(zsinv, m, p - m, v);
+    }
+}
+
+// ---- 2. D_i = ys z(w^(l k)) on a present coset k = i mod m (entry j = i / m of its item), 0 on a missing one ------------------------------
+__global__ void __launch_bounds__(RC_THREADS)
+k_recover_scatter(const uint4* __restrict__ ys, const uint32_t* __restrict__ item_of, uint32_t n, uint32_t m, int log_m, int log_l,
+                  const int32_t* __restrict__ zdom, uint4* __restrict__ data) {
+    const uint32_t i = blockIdx.x * RC_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t k = i & (m - 1), j = i >> log_m, item = item_of[k];
+    Fr v;
+    fe_set_zero(v);
+    if (item != RECOVER_NO_ITEM) {                                   // item < count by construction (host_recover.h)
+        Fr z;
+        rc_load_words(v, ys, ((size_t)item << log_l) + j);           // < 5.3 m
+        pl_load(z, zdom, m, k);                                      // (-m, 2m)
+        fe_mul(v, v, z);                                             // |v z| < 5.3 m * 2 m
+    }
+    rc_store_canon(data, i, v);
+}
+
+// ---- 4, 5, 6: the pointwise passes.  MODE 0: entry t times g^t; 1: entry i times zsinv[i mod m]; 2: entry t times g^-t, and the flag --------
+template <int MODE>
+__global__ void __launch_bounds__(RC_THREADS)
+k_recover_scale(uint4* __restrict__ data, uint32_t n, RcPow gp, const int32_t* __restrict__ zsinv, uint32_t m, uint32_t degree_bound,
+                uint32_t* __restrict__ flag) {
+    const uint32_t i = blockIdx.x * RC_THREADS + threadIdx.x;
+    bool nonzero = false;
+    if (i < n) {
+        Fr v, f;
+        rc_load_words(v, data, i);                                   // < 5.3 m
+        if (MODE == 1) pl_load(f, zsinv, m, i & (m - 1));
+        else rc_gpow(f, gp, i);
+        fe_mul(v, v, f);                                             // |v f| < 5.3 m * 2 m
+        rc_store_canon(data, i, v);
+        if (MODE == 2) nonzero = i >= degree_bound && !fe_is_literal_zero(v);
+    }
+    if (MODE == 2) {
+        if (__syncthreads_or(nonzero) && threadIdx.x == 0) *flag = 1u;   // every writer stores the same word
+    }
+}
+
+// the factored tables of g^t and g^-t for t < 2^log_n in ctx->rc[2], built on ctx->stream when the context has none that long
+static int32_t recover_gpow_tables(kzg_ctx* ctx, int log_n, RcPow* fwd, RcPow* inv) {
+    const int have = ctx->rc_gpow_log;
+    const int log = std::max(log_n, have);
+    const uint32_t hi_len = log > RC_LO_BITS ? 1u << (log - RC_LO_BITS) : 1u;
+    const size_t set = (size_t)NL * (RC_LO_LEN + hi_len);            // words of one direction
+    if (log_n > have) {
+        ctx->rc_gpow_log = -1;
+        KZG_HIP_TRY(ctx, ctx->rc[2].reserve(2 * set * 4));
+    }
+    int32_t* base = ctx->rc[2].as<int32_t>();
+    fwd->lo = base; fwd->hi = base + (size_t)NL * RC_LO_LEN; fwd->hi_len = hi_len;
+    inv->lo = base + set; inv->hi = base + set + (size_t)NL * RC_LO_LEN; inv->hi_len = hi_len;
+    if (log_n > have) {
+        for (int d = 0; d < 2; ++d) {
+            const RcPow& t = d ? *inv : *fwd;
+            hipLaunchKernelGGL(k_recover_gpow_table, dim3(RC_LO_LEN / RC_THREADS), dim3(RC_THREADS), 0, ctx->stream, const_cast<int32_t*>(t.lo), RC_LO_LEN, 1u, d);
+            hipLaunchKernelGGL(k_recover_gpow_table, dim3((hi_len + RC_THREADS - 1) / RC_THREADS), dim3(RC_THREADS), 0, ctx->stream, const_cast<int32_t*>(t.hi), hi_len, RC_LO_LEN, d);
+        }
+        KZG_HIP_TRY(ctx, hipGetLastError());
+        ctx->rc_gpow_log = log;                                      // read by later work of the same stream only
+    }
+    return KZG_OK;
+}
+
+int32_t recover_run(kzg_ctx* ctx, const RecoverPlan& plan, const uint64_t* ys, bool eval_form, uint64_t* out_poly, int32_t* consistent) {
+    RoctxRange range("kzg:recover_from_cosets");
+    hipStream_t st = ctx->stream;
+    const size_t n = plan.n, l = plan.l, m = plan.m, count = plan.count, n_missing = plan.missing.size();
+    NttTables tb;
+    int32_t rc = ntt_get_tables(ctx, plan.log_n, false, &tb);
+    if (rc != KZG_OK) return rc;
+    RcPow gp, gpi;
+    rc = recover_gpow_tables(ctx, plan.log_n, &gp, &gpi);
+    if (rc != KZG_OK) return rc;
+    // vanishing values: 2 m / 256 column groups x `splits` slices of M
+    const uint32_t xgroups = (uint32_t)((2 * m + RC_THREADS - 1) / RC_THREADS);
+    const uint32_t tiles = (uint32_t)((n_missing + RC_TILE - 1) / RC_TILE);
+    const uint32_t splits = std::max(1u, std::min(RC_TARGET_GROUPS / xgroups, tiles));
+    const uint32_t per_split = std::max(1u, (tiles + splits - 1) / splits) * RC_TILE;
+    // rc[1]: item_of m | missing |M| (u32) | flag | zdom 9 m | zsinv 9 m | partial splits x 9 x 2 m (words)
+    const size_t w_item = 0, w_miss = w_item + m, w_flag = w_miss + n_missing, w_zdom = (w_flag + 1 + 3) & ~(size_t)3, w_zsinv = w_zdom + NL * m,
+                 w_part = w_zsinv + NL * m, w_end = w_part + (size_t)splits * NL * 2 * m;
+    KZG_HIP_TRY(ctx, ctx->rc[0].reserve(n * 32));
+    KZG_HIP_TRY(ctx, ctx->rc[1].reserve(w_end * 4));
+    KZG_HIP_TRY(ctx, ctx->rc_ntt.data.reserve(n * 32));              // the uploaded values now, the transforms' scratch afterwards
+    uint32_t* small = ctx->rc[1].as<uint32_t>();
+    int32_t* zdom = ctx->rc[1].as<int32_t>() + w_zdom;
+    int32_t* zsinv = ctx->rc[1].as<int32_t>() + w_zsinv;
+    uint4* d_ys = ctx->rc_ntt.data.as<uint4>();
+    uint4* data = ctx->rc[0].as<uint4>();
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(d_ys, ys, count * l * 32, hipMemcpyHostToDevice, st));
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(small + w_item, plan.item_of.data(), m * 4, hipMemcpyHostToDevice, st));
+    if (n_missing) KZG_HIP_TRY(ctx, hipMemcpyAsync(small + w_miss, plan.missing.data(), n_missing * 4, hipMemcpyHostToDevice, st));
+    KZG_HIP_TRY(ctx, hipMemsetAsync(small + w_flag, 0, 4, st));
+    RcVanishArgs va;
+    va.missing = small + w_miss; va.n_missing = (uint32_t)n_missing; va.per_split = per_split; va.m = (uint32_t)m; va.log_l = plan.log_l;
+    va.tb = tb; va.gp = gp; va.partial = ctx->rc[1].as<int32_t>() + w_part;
+    hipLaunchKernelGGL(k_recover_vanish, dim3(xgroups, splits), dim3(RC_THREADS), 0, st, va);
+    hipLaunchKernelGGL(k_recover_vanish_fold, dim3(xgroups), dim3(RC_THREADS), 0, st, va.partial, splits, (uint32_t)m, zdom, zsinv);
+    const dim3 ngrid((unsigned)((n + RC_THREADS - 1) / RC_THREADS));
+    hipLaunchKernelGGL(k_recover_scatter, ngrid, dim3(RC_THREADS), 0, st, d_ys, small + w_item, (uint32_t)n, (uint32_t)m, plan.log_m, plan.log_l, zdom, data);
+    KZG_HIP_TRY(ctx, hipGetLastError());
+    rc = ntt_run(ctx, data, n, true, st, &ctx->rc_ntt);              // f Z
+    if (rc != KZG_OK) return rc;
+    hipLaunchKernelGGL(k_recover_scale<0>, ngrid, dim3(RC_THREADS), 0, st, data, (uint32_t)n, gp, nullptr, (uint32_t)m, 0u, nullptr);
+    rc = ntt_run(ctx, data, n, false, st, &ctx->rc_ntt);             // (f Z)(g w^i)
+    if (rc != KZG_OK) return rc;
+    hipLaunchKernelGGL(k_recover_scale<1>, ngrid, dim3(RC_THREADS), 0, st, data, (uint32_t)n, gp, zsinv, (uint32_t)m, 0u, nullptr);
+    rc = ntt_run(ctx, data, n, true, st, &ctx->rc_ntt);              // f(g X)
+    if (rc != KZG_OK) return rc;
+    hipLaunchKernelGGL(k_recover_scale<2>, ngrid, dim3(RC_THREADS), 0, st, data, (uint32_t)n, gpi, nullptr, (uint32_t)m, (uint32_t)plan.degree_bound, small + w_flag);
+    KZG_HIP_TRY(ctx, hipGetLastError());
+    if (eval_form) {
+        rc = ntt_run(ctx, data, n, false, st, &ctx->rc_ntt);
+        if (rc != KZG_OK) return rc;
+    }
+    uint32_t flag = 0;
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(out_poly, data, n * 32, hipMemcpyDeviceToHost, st));
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(&flag, small + w_flag, 4, hipMemcpyDeviceToHost, st));
+    KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    *consistent = flag ? 0 : 1;
+    return KZG_OK;
+}
+
+}  // namespace kzg
+
+#if defined(KZG_DEVICE_BOUND_CHECK)   // the device bound-check variant only (field29.h, `make boundcheck`)
+KZG_BOUND_CHECK_EXPORTS(recover)
+#endif

@@ -362,6 +362,49 @@ class KZG:
         ev = _lib.as_u64(polynomial_eval_form.evaluations(), 4).reshape(chunk_len, n // chunk_len, 4)     # [j][k] = evals[k + j m]
         return np.ascontiguousarray(ev.transpose(1, 0, 2))
 
+    def recover_from_cosets(self, coset_indices, ys, n: int, degree_bound=None, eval_form: bool = True):
+        """Erasure decoding (`kzg_recover_from_cosets`): the polynomial of degree < count * chunk_len through the values of `count`
+        distinct cosets of the n-point domain.  `ys` is a (count, chunk_len, 4) array whose row i holds the values of coset
+        `coset_indices[i]` (row `coset_indices[i]` of `cosets`), in any order.  Returns a PolynomialEvalForm of n evaluations, or with
+        eval_form=False a PolynomialCoeffForm of n coefficients.  `degree_bound` (None or 0: count * chunk_len) is the degree bound the
+        polynomial is known to have: values that are not those of a polynomial below it raise GenericError."""
+        ys = np.ascontiguousarray(ys, dtype=np.uint64)
+        idx = np.ascontiguousarray(coset_indices, dtype=np.uint64).reshape(-1)
+        n = int(n)
+        if ys.ndim != 3 or ys.shape[2] != 4 or ys.shape[0] != len(idx):
+            raise GenericError("ys must have the shape (count, chunk_len, 4) with one row per coset index")
+        count, chunk_len = int(ys.shape[0]), int(ys.shape[1])
+        if n < 2 or (n & (n - 1)) != 0:
+            raise FFTError("length provided is not a power of 2")
+        if chunk_len <= 0 or (chunk_len & (chunk_len - 1)) != 0:
+            raise GenericError("chunk length is not a power of 2")
+        if chunk_len > n // 2:
+            raise GenericError("chunk length exceeds half the polynomial length")
+        m = n // chunk_len
+        if count == 0 or count > m:
+            raise GenericError("the number of cosets must be between 1 and n / chunk length")
+        seen = np.zeros(m, dtype=bool)
+        if int(idx.max()) < m:
+            seen[idx.astype(np.int64)] = True
+        if int(seen.sum()) != count:                                                          # an index >= m, or the same coset twice
+            raise GenericError("coset indices must be distinct and below n / chunk length")
+        bound = count * chunk_len if not degree_bound else int(degree_bound)               # None or 0: the default, as in the C-ABI
+        if bound < 0 or bound > count * chunk_len:
+            raise GenericError("too few cosets for the degree bound")
+        ctx = self._ctx()
+        out = np.zeros((n, 4), dtype=np.uint64)
+        consistent = C.c_int32(0)
+        rc = _lib.load().kzg_recover_from_cosets(ctx.handle, _lib.ptr(ys), _lib.ptr(idx), count, n, chunk_len, bound, 1 if eval_form else 0,
+                                                 _lib.ptr(out), C.byref(consistent))
+        if rc == _lib.ERR_DOMAIN:
+            raise FFTError("Could not perform IFFT due to domain consturction error")
+        ctx.check_device(rc)
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+        if not consistent.value:
+            raise GenericError("the cosets are not the values of a polynomial below the degree bound")
+        return PolynomialEvalForm(out) if eval_form else PolynomialCoeffForm(out)
+
     # kzg.rs:237-260
     def compute_quotient_eval_on_domain(self, z_fr, eval_fr, value_fr):
         """sum over the stored roots w^i != z of (f_i - value) w^i / ((z - w^i) z): the quotient's evaluation at the domain point z, on the GPU
