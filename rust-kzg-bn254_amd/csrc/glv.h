@@ -10,7 +10,15 @@ namespace kzg {
 // lattice basis of {(x, y): x + y lambda = 0 mod r} from the extended Euclid on (r, lambda):
 //   (a1, b1) = (9931322734385697763, -147946756881789319000765030803803410728), (a2, b2) = (147946756881789319010696353538189108491, a1),
 // a1 b2 - a2 b1 = r.  c1 = floor(k g1 / 2^256), c2 = floor(k g2 / 2^256) with g1 = round(2^256 b2 / r), g2 = round(2^256 (-b1) / r);
-// k1 = k - c1 a1 - c2 a2, k2 = c1 |b1| - c2 b2  (2 10^5 random k and the edge values: both below 2^127 in magnitude).
+// k1 = k - c1 a1 - c2 a2, k2 = c1 |b1| - c2 b2.  The chains below read exactly 127 bits of each half.  With e1 = r |g1 - 2^256 b2 / r| / 2^256
+// = 0.0818 and e2 likewise = 0.0665 (the rounding of g1, g2 scaled by k / 2^256 < r / 2^256), every canonical k has
+//   |k2| <= (1 + e1) |b1| + e2 b2 = 0.94064746 2^127   (reached: k = 0x30644e1a4d7a33b8b20680a578b2ce9067544f5b7d240c6cd2a77771c2cfd9d4),
+//   |k1| <= (1 + e1) a1 + (1 + e2) a2 = 0.92741129 2^127   (largest met: 0.86955288 2^127, a2 almost exactly),
+// i.e. 6 % of headroom: one word less in g1 or a constant off by one puts a half over 2^127.  Signs: g1 is rounded down and g2 up, so
+// k1 > -e2 a2 = -0.058 2^127 (> -2^123.9), and k2 <= 0 on every scalar of the tests (a positive k2 is at most b2 < 2^64); a decomposed
+// scalar therefore never has a positive second half or a large negative first one.  Callers that pass halves of their own may use both
+// signs of both.
+// Derived from the constants below and checked by tests/test_glv_host.py; the device results by tests/test_gpu_glv.py.
 // Little-endian 32-bit words.
 static __device__ const uint32_t GLV_G1[3] = {0xc7e0b3d7u, 0xd91d232eu, 0x00000002u};
 static __device__ const uint32_t GLV_G2[5] = {0x391eb18eu, 0x7a7bd9d4u, 0xa773d2cfu, 0x4ccef014u, 0x00000002u};
@@ -98,8 +106,8 @@ __device__ __forceinline__ void xyzz_scalar_mul(Xyzz& r, const Xyzz& p, const ui
         fe_mul(beta, beta, kin);                                   // plain integer -> internal form
     }
     fe_mul(bx, p.x, beta);
-    fe_cneg(y1, p.y, s1);
-    fe_cneg(y2, p.y, s2);
+    fe_cneg(y1, p.y, s1); fe_norm(y1);                             // stored form: the first addition to the identity returns P1 / P2 / S as it is
+    fe_cneg(y2, p.y, s2); fe_norm(y2);
     Xyzz P1 = p, P2 = p, S;
     P1.y = y1;
     P2.x = bx; P2.y = y2;

@@ -44,8 +44,9 @@ VARIANTS = (("dc_asm_", []), ("dc_cpp_", ["-DKZG_NO_FE_ASM", "-DDC_PREFIX=dc_cpp
 
 
 def build_devcheck(out=SO):
-    deps = [os.path.join(DC, f) for f in ("devcheck.hip", "dc_prims.h")] + [os.path.join(CSRC, f) for f in
-                                                                             ("field29.h", "fe_asm.h", "fe_invert.h", "field_constants.h", "curve.h", "naf.h")]
+    deps = [os.path.join(DC, f) for f in ("devcheck.hip", "dc_prims.h", "dc_glv.h")] + [os.path.join(CSRC, f) for f in
+                                                                                         ("field29.h", "fe_asm.h", "fe_invert.h", "field_constants.h", "curve.h", "naf.h",
+                                                                                          "curve_pair.h", "curve_quad.h", "glv.h", "glv_lanes.h")]
     if os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in deps):
         return out
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + CSRC]
@@ -75,6 +76,9 @@ def dc():
         getattr(lib, prefix + "ops").restype = C.c_int
         getattr(lib, prefix + "curve").restype = C.c_int
         getattr(lib, prefix + "naf").restype = C.c_int
+        getattr(lib, prefix + "glv").restype = C.c_int
+        getattr(lib, prefix + "smul").restype = C.c_int
+        getattr(lib, prefix + "lanes_curve").restype = C.c_int
         assert getattr(lib, prefix + "ops")() == len(F.NAMES)
     return lib
 
