@@ -17,6 +17,7 @@
 #include "host_pairing.h"
 #include "host_sha256.h"
 #include "host_fiat_shamir.h"
+#include "host_log2.h"
 
 #include <atomic>
 #include <chrono>
@@ -248,7 +249,7 @@ int32_t kzg_commit_and_prove_blob_begin(kzg_ctx* ctx, const kzg_srs* srs, const 
             if (e != hipSuccess) rc = set_error(ctx, e, "blob job: copy of the evaluations");
             if (rc == KZG_OK && n > 1) {
                 NttTables tb;
-                int log_n = 0; while (((size_t)1 << log_n) < n) ++log_n;
+                const int log_n = ilog2_ceil(n);
                 rc = ntt_get_tables(ctx, log_n, true, &tb);
                 if (rc == KZG_OK) rc = ntt_run(ctx, ws.scalars.p, n, true, st, &ctx->slot_ntt(slot));
             }

@@ -218,7 +218,7 @@ int32_t commit_begin_common(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* ev
     if (const kzg_srs* cached = srs_cached_lagrange(srs, n))                         // no IFFT: MSM over the cached Lagrange basis
         return msm_begin(ctx, slot, srs_bases(cached, 0, n, ctx->msm_c_override == 0), d, n);
     NttTables tb;                                                                    // make sure the tables exist before the slot stream reads them
-    int log_n = 0; while (((size_t)1 << log_n) < n) ++log_n;
+    const int log_n = ilog2_ceil(n);
     if (n > 1) { rc = ntt_get_tables(ctx, log_n, true, &tb); if (rc != KZG_OK) return rc; }
     rc = ntt_run(ctx, d, n, true, st, &ctx->slot_ntt(slot));
     if (rc != KZG_OK) return rc;

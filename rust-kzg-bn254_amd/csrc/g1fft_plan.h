@@ -8,6 +8,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "host_log2.h"
+
 namespace kzg {
 
 constexpr uint32_t G1FFT_T3_MAX = 2048;                  // the x3 tables cover the first min(SRS length, 2048) points: every point the table paths transform
@@ -75,7 +77,7 @@ struct G1fftPlan {
     int result;                    // the plane buffer (0 or 1) that holds the result
 };
 
-inline int g1fft_log2(size_t n) { int log_n = 0; while (((size_t)1 << log_n) < n) ++log_n; return log_n; }
+inline int g1fft_log2(size_t n) { return ilog2_ceil(n); }
 
 // Stage plan.  A stage is one scalar multiplication deep whatever it computes, so the plan minimises (number of stages) x (time of a
 // stage).  Measured stage times on MI355X (tools/time_g1ifft.py, round 3) while the stage fits ONE wave per SIMD (65536 lanes):

@@ -5,6 +5,7 @@
 // (primitives/src/helpers.rs:497-504, :529-532) and of KZG::compute_quotient_eval_on_domain (prover/src/kzg.rs:237-260).
 #pragma once
 #include "host_fr.h"
+#include "host_log2.h"
 #include "host_curve.h"
 #include "host_pairing.h"
 
@@ -13,7 +14,6 @@ namespace H = kzg_host;              // (qualified: curve.h has device-math type
 
 constexpr int32_t LAG_ERR_ROOT_NOT_FOUND = -12;      // = KZG_ERR_ROOT_NOT_FOUND of the C header
 
-inline int ilog2_sz(size_t n) { int k = 0; while (((size_t)1 << k) < n) ++k; return k; }
 // z^n (n = 2^log_n) in wire form
 inline void h_pow2k(const uint64_t z[4], int log_n, uint64_t out[4]) {
     memcpy(out, z, 32);
@@ -24,7 +24,7 @@ inline bool h_is_one(const uint64_t a[4]) { uint64_t o[4]; H::fr_one(o); return 
 
 // y from the gathered partials (count x 8 words: S_g | f_m): helpers.rs:497-504 (z on the domain: y = f_m) / :507-532
 inline int32_t lag_fold_y(const uint64_t* parts, size_t count, size_t n, const uint64_t z[4], uint64_t out_y[4]) {
-    const int log_n = ilog2_sz(n);
+    const int log_n = ilog2_ceil(n);
     uint64_t zn[4], s[4] = {0, 0, 0, 0}, fm[4] = {0, 0, 0, 0};
     h_pow2k(z, log_n, zn);
     for (size_t g = 0; g < count; ++g) { H::fr_add(s, parts + 8 * g, s); H::fr_add(fm, parts + 8 * g + 4, fm); }
@@ -52,7 +52,7 @@ inline int32_t lag_fold_proof(const uint64_t* parts, size_t count, size_t n, con
     H::Xyzz acc = H::xyzz_inf();
     for (size_t g = 0; g < count; ++g) { H::Xyzz p; memcpy(&p, parts + 32 * g, 128); acc = H::xyzz_add(acc, p); }
     uint64_t zn[4];
-    h_pow2k(z, ilog2_sz(n), zn);
+    h_pow2k(z, ilog2_ceil(n), zn);
     if (h_is_one(zn)) {
         uint64_t t[4] = {0, 0, 0, 0}, zinv[4], qm[4], zero[4] = {0, 0, 0, 0}, qm_int[4];
         const uint64_t* lm = nullptr;

@@ -253,7 +253,7 @@ int32_t lag_begin(kzg_ctx* ctx, const kzg_srs* shard, size_t base, const void* e
     hipStream_t st = nullptr;
     int32_t rc = msm_slot_stream(ctx, slot, &st);
     if (rc != KZG_OK) return rc;
-    const int log_n = ilog2_sz(n);
+    const int log_n = ilog2_ceil(n);
     PolySet& set = ctx->poly[slot];
     if (!set.pinned) KZG_HIP_TRY(ctx, hipHostMalloc(&set.pinned, 4096, hipHostMallocDefault));
     uint8_t* pin = static_cast<uint8_t*>(set.pinned);
@@ -366,7 +366,7 @@ int32_t lag_continue(kzg_ctx* ctx, int slot, const uint64_t y[4]) {
     uint8_t* pin = static_cast<uint8_t*>(set.pinned);
     uint8_t* small = set.small.as<uint8_t>();
     NttTables tb;
-    int32_t rc = ntt_get_tables(ctx, ilog2_sz(lp.n), false, &tb);
+    int32_t rc = ntt_get_tables(ctx, ilog2_ceil(lp.n), false, &tb);
     if (rc != KZG_OK) { lp = LagProof(); return rc; }
     auto fail = [&](hipError_t e, const char* where) { lp = LagProof(); (void)hipStreamSynchronize(st); return set_error(ctx, e, where); };
     memcpy(pin + 32, y, 32);
@@ -444,7 +444,7 @@ int32_t lag_quotient_eval_on_domain(kzg_ctx* ctx, const uint64_t z[4], const uin
     hipStream_t st = nullptr;
     int32_t rc = msm_slot_stream(ctx, slot, &st);
     if (rc != KZG_OK) return rc;
-    const int log_n = ilog2_sz(n);
+    const int log_n = ilog2_ceil(n);
     NttTables tb;
     rc = ntt_get_tables(ctx, log_n, false, &tb);
     if (rc != KZG_OK) return rc;

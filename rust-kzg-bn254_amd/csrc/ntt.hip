@@ -21,6 +21,7 @@
 //   Algorithmic traffic: 64 B per element; this implementation moves P x 64 B.
 #include "engine.h"
 #include "field29.h"
+#include "ntt_plan.h"      // the pass policy: constants, NttPassArgs, ntt_plan
 
 #include <algorithm>
 #include <map>
@@ -29,12 +30,7 @@
 
 namespace kzg {
 
-constexpr int NTT_KMAX = 10;
-constexpr int NTT_EPT = 4;                         // elements per thread in the load / store phases = one radix-4 butterfly per thread and step
-// Two tile sizes (round 4).  2 048 elements / 512 threads, one workgroup per CU: transforms of >= 2^19 elements (>= 256 tiles per pass).
-// 1 024 elements / 256 threads, two workgroups per CU: smaller transforms -- twice the workgroups (2^18: 256 instead of 128 on 256
-// CUs; one tile of a <= 1 024-point transform in half the threads) and two independent barrier domains per CU:
-// 2^12 / 2^16 / 2^18 0.052 / 0.062 / 0.073 -> 0.040 / 0.046 / 0.057 ms per call; at 2^20 the big tile stays ahead (0.140 against 0.147).
+// The two tile sizes (ntt_plan.h NTT_TILE_LOG_BIG / _SMALL) as the kernel sees them
 template <int TILE_LOG> struct NttTile {
     static constexpr int LOG = TILE_LOG;
     static constexpr int TILE = 1 << TILE_LOG;     // elements per workgroup tile
@@ -43,13 +39,6 @@ template <int TILE_LOG> struct NttTile {
     // column-major one (ntt_lds_pos) -> TILE + max(TILE / 16, 32) words
     static constexpr int PL = TILE + (TILE / 16 > 32 ? TILE / 16 : 32);
 };
-constexpr int NTT_TILE_LOG_BIG = 11, NTT_TILE_LOG_SMALL = 10;
-// measured per call, small / big tile (tools/archive/time_ntt_variants.py, KZG_NTT_TILE_LOG=10 / 11): 2^10 0.034 / 0.043, 2^14 0.045 / 0.058,
-// 2^17 0.055 / 0.067, 2^18 0.059 / 0.071, 2^19 0.086 / 0.082, 2^20 0.155 / 0.136, 2^21 0.280 / 0.297, 2^22 0.537 / 0.562, 2^23 1.195 /
-// 1.246, 2^24 2.46 / 2.52, 2^25 5.31 / 5.34, 2^26 12.1 / 11.1 ms
-// round 6: 2^25 moved to the small tile (its passes are 9 + 8 + 8 bits: the slim instantiation below, three workgroups per CU: 5.24 -> 4.95 ms; 2^26 stays: 10.9 against 11.5)
-inline bool ntt_small_tile_pays(int log_n) { return log_n <= 18 || (log_n >= 21 && log_n <= 25); }
-constexpr int NTT_LO_BITS = 10;
 
 // ---- twiddle tables: planes[9][len] of w^(t * step), internal Montgomery form -----------------------
 __device__ __forceinline__ void fr_pow_root(Fr& out, int log_n, bool inverse, uint32_t e) {
@@ -111,14 +100,6 @@ __global__ void __launch_bounds__(256)
 k_ntt_build_pass_twiddles(uint4* __restrict__ tw, int log_n, int next_K, int next_log_s,
                           const int32_t* __restrict__ tlo, uint32_t lo_len, int lo_bits, const int32_t* __restrict__ thi, uint32_t hi_len);
 
-struct NttPassArgs {
-    int log_n, K, log_s;          // this pass
-    int next_K, next_log_s;       // the pass after it (next_K = 0: this is the last pass)
-    int scale_log_n;              // last pass: >= 0 multiplies by (2^scale_log_n)^-1; -1: no factor left (forward transform, or the inverse's 1 / n
-                                  // folded into the twiddle array of the previous pass boundary): the outputs are only reduced (fe_reduce_small)
-    uint32_t n_tiles;
-};
-
 // global word index of element (uu, j) of tile `tile` on the INPUT side of the pass
 __device__ __forceinline__ size_t ntt_in_index(const NttPassArgs& a, int tile_log, uint32_t tile, uint32_t t, uint32_t& uu, uint32_t& j, bool& valid) {
     const int log_c = tile_log - a.K;
@@ -137,11 +118,7 @@ template <int TILE_LOG, int KMAX_T = NTT_KMAX>
 __global__ void __launch_bounds__(NttTile<TILE_LOG>::THREADS)
 k_ntt_pass(const uint4* __restrict__ in_words, uint4* __restrict__ out_words, NttPassArgs a,
            const int32_t* __restrict__ tlo, uint32_t lo_len, int lo_bits, const int32_t* __restrict__ thi, uint32_t hi_len,
-           const uint4* __restrict__ next_tw /* or nullptr: w_N^(E(idx)) of the next pass for every output index, canonical words of the internal form */
-#ifdef KZG_NTT_STAMPS
-           , unsigned long long* __restrict__ stamps /* diagnostic build (tools/ntt_stamps.py): 8 phase sums per workgroup, 100 MHz ticks */
-#endif
-           ) {
+           const uint4* __restrict__ next_tw /* or nullptr: w_N^(E(idx)) of the next pass for every output index, canonical words of the internal form */) {
     constexpr int NTT_TILE_LOG = TILE_LOG, NTT_TILE = NttTile<TILE_LOG>::TILE, NTT_PL = NttTile<TILE_LOG>::PL, NTT_THREADS = NttTile<TILE_LOG>::THREADS;
     __shared__ int32_t lds[NL * NTT_PL];
     constexpr int NTT_TW = 1 << (KMAX_T - 1);
@@ -179,15 +156,8 @@ k_ntt_pass(const uint4* __restrict__ in_words, uint4* __restrict__ out_words, Nt
             else { pre[k][0] = make_uint4(0, 0, 0, 0); pre[k][1] = make_uint4(0, 0, 0, 0); }
         }
     }
-#ifdef KZG_NTT_STAMPS
-    unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_prev = __builtin_amdgcn_s_memrealtime();
-#define KZG_NTT_STAMP(i) do { const unsigned long long t_now = __builtin_amdgcn_s_memrealtime(); ph[i] += t_now - t_prev; t_prev = t_now; } while (0)
-#else
-#define KZG_NTT_STAMP(i) do { } while (0)
-#endif
     for (uint32_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
         const uint32_t tile_u0 = tile << log_c;
-        KZG_NTT_STAMP(0);                                  // (set-up, or the previous tile's trailing barrier)
         // ---- registers -> LDS (bit-reversed rows) ----------------------------------------------
 #pragma unroll
         for (int k = 0; k < NTT_EPT; ++k) {
@@ -202,7 +172,6 @@ k_ntt_pass(const uint4* __restrict__ in_words, uint4* __restrict__ out_words, Nt
             for (int l = 0; l < NL; ++l) lds[l * NTT_PL + e] = v.l[l];
         }
         __syncthreads();
-        KZG_NTT_STAMP(1);                                  // wait for the tile's words + unpack + LDS fill
         // ---- this tile's inter-pass twiddle words (the STORE phase multiplies by them): with the 1 024-element tile they are issued now and are in
         // flight during the butterfly stages; fetched at the store they are a dependent global load in front of every output product.  Same-box A/B
         // (round 6, tools/time_ntt.py, ms per transform early / at the store): 2^12 0.0364 / 0.0386, 2^16 0.0425 / 0.0453, 2^18 0.0528 / 0.0551,
@@ -240,7 +209,6 @@ k_ntt_pass(const uint4* __restrict__ in_words, uint4* __restrict__ out_words, Nt
         // Radix-4 step over half-sizes h and 2h on rows i0, i0+h, i0+2h, i0+3h (same butterflies and twiddles as two radix-2
         // stages, so the results are identical): one LDS round trip, one barrier and four limb normalisations per four elements.
         uint32_t log_h = 0;
-        KZG_NTT_STAMP(2);                                  // issue of the prefetch
         for (; log_h + 1 < (uint32_t)K; log_h += 2) {
             const uint32_t h = 1u << log_h;
             for (uint32_t gt = tid; gt < (uint32_t)(NTT_TILE / 4); gt += NTT_THREADS) {
@@ -287,12 +255,7 @@ k_ntt_pass(const uint4* __restrict__ in_words, uint4* __restrict__ out_words, Nt
                     lds[l * NTT_PL + e3] = c3.l[l];
                 }
             }
-#ifdef KZG_NTT_PROBE_NOBARRIER   // timing probe only (wrong results): what do the barriers of the first four radix-4 steps cost
-            if (log_h >= 6) __syncthreads();
-#else
             __syncthreads();
-#endif
-            KZG_NTT_STAMP(3);                              // the radix-4 steps
         }
         if (log_h < (uint32_t)K) {
             const uint32_t h = 1u << log_h;
@@ -322,7 +285,6 @@ k_ntt_pass(const uint4* __restrict__ in_words, uint4* __restrict__ out_words, Nt
             }
             __syncthreads();
         }
-        KZG_NTT_STAMP(4);                                  // the odd radix-2 stage
         // ---- LDS -> global: rows j, C consecutive units each -------------------------------------------------
 #pragma unroll
         for (int k = 0; k < NTT_EPT; ++k) {
@@ -368,13 +330,8 @@ k_ntt_pass(const uint4* __restrict__ in_words, uint4* __restrict__ out_words, Nt
             out_words[2 * idx] = make_uint4(w32[0], w32[1], w32[2], w32[3]);
             out_words[2 * idx + 1] = make_uint4(w32[4], w32[5], w32[6], w32[7]);
         }
-        KZG_NTT_STAMP(5);                                  // LDS read + the store-side multiply + pack + global stores (issue)
         __syncthreads();                   // the tile's rows are read before the next tile overwrites them
     }
-#ifdef KZG_NTT_STAMPS
-    KZG_NTT_STAMP(6);
-    if (tid == 0 && stamps) for (int i = 0; i < 8; ++i) stamps[(size_t)blockIdx.x * 8 + i] = ph[i];
-#endif
 }
 
 __global__ void __launch_bounds__(256)
@@ -430,9 +387,7 @@ int32_t ntt_get_tables(kzg_ctx* ctx, int log_n, bool inverse, NttTables* out) {
     return KZG_OK;
 }
 
-// HBM capacity spent to remove work (like the MSM window tables): the inter-pass twiddle of every element as one 32-byte word,
-// 32 MiB per pass boundary at 2^20; kept per (device, log n, direction, boundary) for transforms of up to 2^22 elements.
-constexpr int NTT_FULL_TW_MAX_LOG = 22;
+// the inter-pass twiddle of every element as one 32-byte word (ntt_plan.h NTT_FULL_TW_MAX_LOG), kept per (device, log n, direction, boundary, scaled)
 struct PassTwKey { int dev, log_n, inverse, next_K, next_log_s, scaled; bool operator<(const PassTwKey& o) const { return std::tie(dev, log_n, inverse, next_K, next_log_s, scaled) < std::tie(o.dev, o.log_n, o.inverse, o.next_K, o.next_log_s, o.scaled); } };
 static std::map<PassTwKey, uint4*> g_pass_tw;
 static int32_t ntt_get_pass_twiddles(kzg_ctx* ctx, int log_n, bool inverse, int next_K, int next_log_s, const NttTables& tb, int lo_bits, const uint4** out,
@@ -465,97 +420,50 @@ void ntt_release_device_caches(int dev) {
     }
 }
 
-#ifdef KZG_NTT_STAMPS
-static unsigned long long* g_ntt_stamps = nullptr;
-}  // namespace kzg
-extern "C" int32_t kzg_debug_ntt_stamps(unsigned long long* out /* 4 x 1024 x 8 */) {
-    if (!kzg::g_ntt_stamps) return -1;
-    return hipMemcpy(out, kzg::g_ntt_stamps, 4 * 1024 * 8 * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
+// one pass of the plan: THE launch of k_ntt_pass, the switch over its instantiations
+static void ntt_launch_pass(const NttPlan& plan, int pi, const uint4* src, uint4* dst, const NttTables& tb, int lo_bits, const uint4* next_tw, hipStream_t st) {
+    const NttPass& s = plan.pass[pi];
+#define NTT_LAUNCH(...) hipLaunchKernelGGL((k_ntt_pass<__VA_ARGS__>), dim3(s.grid), dim3(plan.threads), 0, st, src, dst, s.args, tb.lo, tb.lo_len, lo_bits, tb.hi, tb.hi_len, next_tw)
+    switch (plan.kernel) {
+    case NTT_K_SLIM7: NTT_LAUNCH(NTT_TILE_LOG_SMALL, 7); break;
+    case NTT_K_SLIM8: NTT_LAUNCH(NTT_TILE_LOG_SMALL, 8); break;
+    case NTT_K_SLIM9: NTT_LAUNCH(NTT_TILE_LOG_SMALL, 9); break;
+    case NTT_K_SMALL: NTT_LAUNCH(NTT_TILE_LOG_SMALL); break;
+    default: NTT_LAUNCH(NTT_TILE_LOG_BIG); break;
+    }
+#undef NTT_LAUNCH
 }
-namespace kzg {
-#endif
+static_assert(NttTile<NTT_TILE_LOG_SMALL>::THREADS == (1 << NTT_TILE_LOG_SMALL) / NTT_EPT && NttTile<NTT_TILE_LOG_BIG>::THREADS == (1 << NTT_TILE_LOG_BIG) / NTT_EPT,
+              "NttPlan::threads is the workgroup size k_ntt_pass is bounded to");
+
+// the driver: plan (ntt_plan.h), tables, the reserves from the plan, then its passes
 int32_t ntt_run(kzg_ctx* ctx, void* d_data, size_t n, bool inverse, hipStream_t st, NttWorkspace* ws) {
     if (!st) st = ctx->stream;
     if (!ws) ws = &ctx->ntt;
     if (n == 0 || (n & (n - 1)) != 0) return KZG_ERR_NOT_POWER_OF_TWO;
-    if (n > ((size_t)1 << 28)) return KZG_ERR_DOMAIN;
+    if (n > ((size_t)1 << NTT_MAX_LOG)) return KZG_ERR_DOMAIN;
     if (n == 1) return KZG_OK;
     RoctxRange range(inverse ? "kzg:fr_intt" : "kzg:fr_ntt");
-    int log_n = 0;
-    while (((size_t)1 << log_n) < n) ++log_n;
+    const int log_n = ilog2_ceil(n);
     NttTables tb;
     int32_t rc = ntt_get_tables(ctx, log_n, inverse, &tb);
     if (rc != KZG_OK) return rc;
-    int lo_bits = log_n < NTT_LO_BITS ? log_n : NTT_LO_BITS;
-
-    int P = (log_n + NTT_KMAX - 1) / NTT_KMAX;
-    // (2^20 as THREE passes of 7 + 7 + 6 bits on slim workgroups: 0.1305 / 0.1322 ms against 0.1333 for 10 + 10 -- 1.5 % for 60 % more HBM traffic: not taken;
-    //  2^15 .. 2^19 lose 2 .. 13 % that way)
-    int Ks[4];
-    for (int pi = 0; pi < P; ++pi) Ks[pi] = log_n / P + (pi < log_n % P ? 1 : 0);
-    // buffers: data -> A -> (B ->) data; a single pass works in place (one tile holds the whole transform)
-    if (P > 1) KZG_HIP_TRY(ctx, ws->data.reserve(n * 32));
-    if (P > 2) KZG_HIP_TRY(ctx, ws->tmp.reserve(n * 32));
-    uint4* bufs[2] = {ws->data.as<uint4>(), ws->tmp.as<uint4>()};
+    const int lo_bits = log_n < NTT_LO_BITS ? log_n : NTT_LO_BITS;
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    const int tile_env = opts().ntt_tile_log;                       // KZG_NTT_TILE_LOG = 10 / 11: one tile size at every transform size (tests cover both kernels everywhere)
-    int kmax = 0;
-    for (int pi = 0; pi < P; ++pi) kmax = std::max(kmax, log_n / P + (pi < log_n % P ? 1 : 0));
-    // Round 6: the radix bits of the widest pass decide the per-workgroup twiddle table.  With K <= 9 a 1 024-element workgroup needs 41.5 / 43.8 / 48.4 KB of LDS
-    // instead of 57.6, THREE fit a CU and at 145 VGPRs run three waves per SIMD -- the instantiations k_ntt_pass<10, 7 / 8 / 9>; fill and drain of one tile then
-    // overlap the butterfly stages of two others.  Same-box A/B against the KMAX = 10 instantiation (two per CU, early twiddle read), ms per transform
-    // (tools/time_ntt.py): 2^8 0.0267 -> 0.0254, 2^12 0.0385 -> 0.0372, 2^16 0.0450 -> 0.0430, 2^18 0.0552 -> 0.0531, 2^21 0.2723 -> 0.2423, 2^22 0.5213 -> 0.4880,
-    // 2^23 1.168 -> 1.082, 2^24 2.430 -> 2.268, 2^25 5.24 (2 048-element tile) -> 4.95.  2^10, 2^19, 2^20 and 2^26 .. 2^30 have a 10-bit pass and stay as they were.
-    const bool small_tile = tile_env == NTT_TILE_LOG_SMALL || (tile_env != NTT_TILE_LOG_BIG && ntt_small_tile_pays(log_n));
-    const int slim = small_tile && kmax <= 9 ? std::max(kmax, 7) : 0;
-    const int tile_log = small_tile ? NTT_TILE_LOG_SMALL : NTT_TILE_LOG_BIG;
-    int log_ncur = 0;
-    bool scale_folded = false;      // the inverse transform's 1 / n went into the twiddle array of the last pass boundary
-    for (int pi = 0; pi < P; ++pi) {
-        NttPassArgs a;
-        a.log_n = log_n;
-        a.K = Ks[pi];
-        log_ncur += a.K;
-        a.log_s = log_n - log_ncur;
-        const bool last = pi == P - 1;
-        a.next_K = last ? 0 : Ks[pi + 1];
-        a.next_log_s = last ? 0 : log_n - (log_ncur + Ks[pi + 1]);
-        a.scale_log_n = (last && inverse && !scale_folded) ? log_n : -1;
-        const uint32_t n_units = (uint32_t)(n >> a.K);
-        const uint32_t C = 1u << (tile_log - a.K);
-        a.n_tiles = (n_units + C - 1) / C;
-        const uint4* src = pi == 0 ? reinterpret_cast<const uint4*>(d_data) : bufs[(pi - 1) & 1];
-        uint4* dst = last ? reinterpret_cast<uint4*>(d_data) : bufs[pi & 1];
-        // big tile: one workgroup per CU (97 KB of LDS); small tile: two (58 KB each); a workgroup walks its tiles with the next one's words prefetched
-        const uint32_t grid = std::min<uint32_t>(a.n_tiles, (uint32_t)cus * (slim ? 3u : small_tile ? 2u : 1u));
+    NttPlan plan = ntt_plan(log_n, inverse, cus, opts().ntt_tile_log);
+    if (plan.bytes_data) KZG_HIP_TRY(ctx, ws->data.reserve(plan.bytes_data));
+    if (plan.bytes_tmp) KZG_HIP_TRY(ctx, ws->tmp.reserve(plan.bytes_tmp));
+    uint4* const bufs[3] = {reinterpret_cast<uint4*>(d_data), ws->data.as<uint4>(), ws->tmp.as<uint4>()};      // by NttBuf
+    for (int pi = 0; pi < plan.n_passes; ++pi) {
+        const NttPass& s = plan.pass[pi];
         const uint4* next_tw = nullptr;
-        if (!last && log_n <= NTT_FULL_TW_MAX_LOG) {
-            const bool fold = inverse && pi == P - 2;          // the boundary in front of the last pass carries the scaling
-            rc = ntt_get_pass_twiddles(ctx, log_n, inverse, a.next_K, a.next_log_s, tb, lo_bits, &next_tw, fold);
+        if (s.tw) {
+            rc = ntt_get_pass_twiddles(ctx, log_n, inverse, s.args.next_K, s.args.next_log_s, tb, lo_bits, &next_tw, s.tw_scaled);
             if (rc != KZG_OK) return rc;
-            scale_folded = fold && next_tw != nullptr;
+            if (s.tw_scaled && !next_tw) ntt_plan_fold_missing(plan);
         }
-#ifdef KZG_NTT_STAMPS
-        static unsigned long long* d_stamps = nullptr;     // [pass][workgroup][8]; read back by kzg_debug_ntt_stamps
-        if (!d_stamps) KZG_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d_stamps), 4 * 1024 * 8 * 8));
-        g_ntt_stamps = d_stamps;
-        if (small_tile)
-            hipLaunchKernelGGL(k_ntt_pass<NTT_TILE_LOG_SMALL>, dim3(grid), dim3(NttTile<NTT_TILE_LOG_SMALL>::THREADS), 0, st, src, dst, a, tb.lo, tb.lo_len, lo_bits, tb.hi, tb.hi_len, next_tw, d_stamps + (size_t)pi * 1024 * 8);
-        else
-            hipLaunchKernelGGL(k_ntt_pass<NTT_TILE_LOG_BIG>, dim3(grid), dim3(NttTile<NTT_TILE_LOG_BIG>::THREADS), 0, st, src, dst, a, tb.lo, tb.lo_len, lo_bits, tb.hi, tb.hi_len, next_tw, d_stamps + (size_t)pi * 1024 * 8);
-#else
-        if (slim == 7)
-            hipLaunchKernelGGL((k_ntt_pass<NTT_TILE_LOG_SMALL, 7>), dim3(grid), dim3(NttTile<NTT_TILE_LOG_SMALL>::THREADS), 0, st, src, dst, a, tb.lo, tb.lo_len, lo_bits, tb.hi, tb.hi_len, next_tw);
-        else if (slim == 8)
-            hipLaunchKernelGGL((k_ntt_pass<NTT_TILE_LOG_SMALL, 8>), dim3(grid), dim3(NttTile<NTT_TILE_LOG_SMALL>::THREADS), 0, st, src, dst, a, tb.lo, tb.lo_len, lo_bits, tb.hi, tb.hi_len, next_tw);
-        else if (slim == 9)
-            hipLaunchKernelGGL((k_ntt_pass<NTT_TILE_LOG_SMALL, 9>), dim3(grid), dim3(NttTile<NTT_TILE_LOG_SMALL>::THREADS), 0, st, src, dst, a, tb.lo, tb.lo_len, lo_bits, tb.hi, tb.hi_len, next_tw);
-        else if (small_tile)
-            hipLaunchKernelGGL(k_ntt_pass<NTT_TILE_LOG_SMALL>, dim3(grid), dim3(NttTile<NTT_TILE_LOG_SMALL>::THREADS), 0, st, src, dst, a, tb.lo, tb.lo_len, lo_bits, tb.hi, tb.hi_len, next_tw);
-        else
-            hipLaunchKernelGGL(k_ntt_pass<NTT_TILE_LOG_BIG>, dim3(grid), dim3(NttTile<NTT_TILE_LOG_BIG>::THREADS), 0, st, src, dst, a, tb.lo, tb.lo_len, lo_bits, tb.hi, tb.hi_len, next_tw);
-#endif
+        ntt_launch_pass(plan, pi, bufs[s.src], bufs[s.dst], tb, lo_bits, next_tw, st);
     }
     KZG_HIP_TRY(ctx, hipGetLastError());
     return KZG_OK;

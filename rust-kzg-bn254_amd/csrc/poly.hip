@@ -15,6 +15,7 @@
 // Also: helpers::calculate_roots_of_unity (helpers.rs:553-589) as a kernel.
 #include "poly_common.h"
 #include "fe_invert.h"
+#include "proof_plan.h"    // the proof driver's policy, the staging layout (ProofStaging, ProofScalars) and the chain's scalar table
 
 #include <algorithm>
 #include <cstdlib>
@@ -23,13 +24,7 @@
 
 namespace kzg {
 
-
-struct ProofScalars {        // device-resident small state of one proof computation
-    uint32_t on_domain_index; // NO_INDEX if z is not a domain element
-    uint32_t pad[3];
-    int32_t y[NL];            // y = p(z), internal form, reduced
-    uint32_t y_wire[8];
-};
+static_assert(PROOF_NL == NL && PROOF_THREADS == POLY_THREADS, "proof_plan.h sizes the workspaces for these kernels");
 
 // ---- K0: the inverses 1 / (W^j - Z) on a small domain, one workgroup ----------------------------------------------
 // out[j] = 1 / (w^(j e) - z^e), j < N = 2^log_ns <= 4096, e = n / N; zt[a] = z^(2^a) (wire), zt[log_n + 1] = 1 / (1 - z^n).
@@ -41,7 +36,7 @@ struct ProofScalars {        // device-resident small state of one proof computa
 // constants: the host supplies z^-(2^a) and 1/(i-1), -1/2, 1/(-i-1) with the other scalars (zt[log_n+2 ..]).  The value such a lane
 // read from the coarser level was never valid and is not used.
 constexpr int POLY_SMALL_THREADS = 1024;
-constexpr uint32_t POLY_SMALL_MAX_LOG = 12;
+constexpr uint32_t POLY_SMALL_MAX_LOG = PROOF_SMALL_MAX_LOG;
 constexpr uint32_t POLY_SMALL_MAX = 1u << POLY_SMALL_MAX_LOG;
 __global__ void __launch_bounds__(POLY_SMALL_THREADS)
 k_poly_inv_small(const uint4* __restrict__ zt, int log_n, int log_ns, NttTables tb, int32_t* __restrict__ out /* planes, stride 2^log_ns */) {
@@ -50,13 +45,13 @@ k_poly_inv_small(const uint4* __restrict__ zt, int log_n, int log_ns, NttTables 
     const uint32_t t0 = threadIdx.x, N = 1u << log_ns;
     if (t0 == 0) {
         Fr top;
-        wire_load(top, zt, (size_t)log_n + 1);
+        wire_load(top, zt, (size_t)ProofStaging::zt_top(log_n));
 #pragma unroll
         for (int j = 0; j < NL; ++j) lds_inv[(size_t)j * N] = top.l[j];
     }
     if ((int)t0 < log_ns) {                                   // level log_s = t0 works on the 2^(t0+1)-point domain
         Fr z;
-        wire_load(z, zt, (size_t)(log_n - (int)t0 - 1));
+        wire_load(z, zt, (size_t)ProofStaging::zt_pow(log_n - (int)t0 - 1));
         fe_canon(z);
 #pragma unroll
         for (int j = 0; j < NL; ++j) zl[t0 * NL + j] = z.l[j];
@@ -95,8 +90,8 @@ k_poly_inv_small(const uint4* __restrict__ zt, int log_n, int log_ns, NttTables 
             const bool z0 = fe_is_literal_zero(d0[q]), z1 = fe_is_literal_zero(d1[q]);
             if (__builtin_expect(z0 || z1, 0)) {               // +-W^t = Z: the other denominator is -2 Z, its inverse (-1/2) Z^-1 from the host's table
                 Fr zi, c2, other;
-                wire_load(zi, zt, (size_t)(log_n + 2 + log_e));
-                wire_load(c2, zt, (size_t)(2 * log_n + 3 + 1));
+                wire_load(zi, zt, (size_t)ProofStaging::zt_inv_pow(log_n, log_e));
+                wire_load(c2, zt, (size_t)ProofStaging::zt_const(log_n, 1));
                 fe_mul(other, zi, c2);
                 fe_set_one(i0); fe_set_one(i1);
                 if (!z0) i0 = other;
@@ -140,13 +135,13 @@ __device__ __forceinline__ uint32_t inv4_group(Fr inv[4], const NttTables& tb, c
     for (uint32_t k = 0; k < 4; ++k) if (fe_is_literal_zero(d[k])) { zero_k = k; fe_set_one(d[k]); }
     if (__builtin_expect(zero_k != 4, 0)) {                    // d_k = Z (i^(k - k0) - 1): inverses = Z^-1 times the host's constants
         Fr zi;
-        wire_load(zi, zt, (size_t)(log_n + 2 + log_e));
+        wire_load(zi, zt, (size_t)ProofStaging::zt_inv_pow(log_n, log_e));
 #pragma unroll
         for (uint32_t k = 0; k < 4; ++k) {
             const uint32_t r = (k - zero_k) & 3u;
             if (r == 0) { fe_set_one(inv[k]); continue; }
             Fr c;
-            wire_load(c, zt, (size_t)(2 * log_n + 3 + (r - 1)));
+            wire_load(c, zt, (size_t)(ProofStaging::zt_const(log_n, 0) + (r - 1)));
             fe_mul(inv[k], zi, c);
         }
         return zero_k;
@@ -171,7 +166,7 @@ k_poly_inv_level(const uint4* __restrict__ zt, int log_n, int log_nl, NttTables 
     if (t >= T) return;
     const int log_e = log_n - log_nl;
     Fr z, inv[4];
-    wire_load(z, zt, (size_t)log_e);
+    wire_load(z, zt, (size_t)ProofStaging::zt_pow(log_e));
     fe_canon(z);
     inv4_group(inv, tb, zt, log_n, log_e, t, z, next, T);
 #pragma unroll
@@ -671,10 +666,8 @@ k_vb_eval(const uint8_t* __restrict__ bytes, const VbBlob* __restrict__ meta, co
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------
-static int ilog2_exact(size_t n) { int k = 0; while (((size_t)1 << k) < n) ++k; return k; }
-
 int32_t roots_run(kzg_ctx* ctx, uint64_t* out, size_t n) {
-    int log_n = ilog2_exact(n);
+    int log_n = ilog2_ceil(n);
     NttTables tb;
     int32_t rc = ntt_get_tables(ctx, log_n, false, &tb);
     if (rc != KZG_OK) return rc;
@@ -705,178 +698,175 @@ int32_t blob_to_fr_run(kzg_ctx* ctx, const uint8_t* bytes, size_t len, size_t n_
 }
 
 
+// The known-index form's table 1 / (w^k - 1), k < n <= 4096, once per domain size: the inversion chain at z = 1
+static int32_t proof_ondomain_table(kzg_ctx* ctx, int log_n, const NttTables& tb, hipStream_t st, const int32_t** out) {
+    int32_t*& t1 = ctx->ondomain_inv[log_n];
+    if (!t1) {
+        const size_t n = (size_t)1 << log_n;
+        uint64_t z1[ProofStaging::zt_count(PROOF_SMALL_MAX_LOG) * 4], one_w[4];
+        const size_t z1_bytes = (size_t)ProofStaging::zt_count(log_n) * 32;
+        bool on_domain;
+        kzg_host::fr_one(one_w);
+        proof_fill_scalars(one_w, log_n, z1, &on_domain);
+        uint4* d_z1 = nullptr;
+        KZG_HIP_TRY(ctx, hipMalloc(&d_z1, z1_bytes));
+        hipError_t e1 = hipMalloc(&t1, (size_t)NL * n * 4);
+        if (e1 == hipSuccess) e1 = hipMemcpy(d_z1, z1, z1_bytes, hipMemcpyHostToDevice);
+        if (e1 == hipSuccess) {
+            hipLaunchKernelGGL(k_poly_inv_small, dim3(1), dim3(POLY_SMALL_THREADS), (size_t)NL * n * 4, st, d_z1, log_n, log_n, tb, t1);
+            e1 = hipGetLastError();
+            if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
+        }
+        (void)hipFree(d_z1);
+        if (e1 != hipSuccess) { if (t1) { (void)hipFree(t1); t1 = nullptr; } KZG_HIP_TRY(ctx, e1); }
+    }
+    *out = t1;
+    return KZG_OK;
+}
+
+// What the steps of a plan work on
+struct ProofOperands {
+    const uint64_t* evals;        // host evaluations, or nullptr
+    const uint4* d_a;             // the n evaluations on the device: set.a or the caller's buffer
+    const int32_t* table;         // PROOF_FORM_TABLE: 1 / (w^k - 1)
+    uint32_t m_known;             // ... and the index of z
+    NttWorkspace* nttws;
+};
+// Walks the plan's steps: each kernel's launch, each copy and the join of the two streams are written here once
+static int32_t proof_launch(kzg_ctx* ctx, PolySet& set, hipStream_t st, const ProofPlan& plan, const NttTables& tb, const ProofOperands& op) {
+    const size_t n = (size_t)1 << plan.log_n;
+    const int log_n = plan.log_n;
+    const uint32_t blocks = plan.blocks;
+    uint8_t* small = set.small.as<uint8_t>();
+    uint8_t* pin = static_cast<uint8_t*>(set.pinned);
+    ProofScalars* ps = reinterpret_cast<ProofScalars*>(small + ProofStaging::IMAGE);
+    const uint4* d_zt = reinterpret_cast<const uint4*>(small + ProofStaging::ZT);      // its first element is z itself
+    int32_t* partial = reinterpret_cast<int32_t*>(small + ProofStaging::PARTIALS);
+    int32_t* d_inv = set.b.as<int32_t>();
+    int32_t* d_lvl = d_inv + n * NL;
+    uint4* d_q = set.c.as<uint4>();
+    auto lvl = [&](size_t off) { return off == PROOF_OUT_INV ? d_inv : d_lvl + off; };
+    hipStream_t sc = st;                                     // the chain's stream
+    if (plan.aux) {
+        int32_t rca = ctx_aux_stream(ctx, st, &sc);
+        if (rca != KZG_OK) return rca;
+    }
+    ProofScalars* ps_out = nullptr;                          // the table form's kernels write the read-back slot themselves
+    if (plan.form == PROOF_FORM_TABLE) {
+        void* ps_host_dev = nullptr;
+        KZG_HIP_TRY(ctx, hipHostGetDevicePointer(&ps_host_dev, pin + ProofStaging::Y_READBACK, 0));
+        ps_out = static_cast<ProofScalars*>(ps_host_dev);
+    }
+    bool unchecked = false;                                  // a kernel was launched since the last hipGetLastError
+    for (int i = 0; i < plan.n_steps; ++i) {
+        const ProofStep& s = plan.step[i];
+        if (unchecked && proof_step_collects_errors(s.kind)) {
+            KZG_HIP_TRY(ctx, hipGetLastError());
+            unchecked = false;
+        }
+        unchecked |= s.kind >= PS_FIRST_KERNEL;
+        switch (s.kind) {
+        case PS_UPLOAD_SCALARS:   // one upload for the scalar image and the chain's scalars right behind it
+            KZG_HIP_TRY(ctx, hipMemcpyAsync(small, pin, ProofStaging::upload_bytes(log_n), hipMemcpyHostToDevice, sc));
+            break;
+        case PS_UPLOAD_EVALS:
+            KZG_HIP_TRY(ctx, hipMemcpyAsync(set.a.p, op.evals, n * 32, hipMemcpyHostToDevice, st));
+            break;
+        case PS_INV_SMALL:
+            hipLaunchKernelGGL(k_poly_inv_small, dim3(1), dim3(POLY_SMALL_THREADS), plan.small_lds, sc, d_zt, log_n, plan.small_log_ns, tb, lvl(plan.small_out));
+            break;
+        case PS_INV_LEVEL: {
+            const ProofLevel& l = plan.level[s.level];
+            const uint32_t T = 1u << (l.log_l - 2);
+            hipLaunchKernelGGL(k_poly_inv_level, dim3((T + POLY_THREADS - 1) / POLY_THREADS), dim3(POLY_THREADS), 0, sc, d_zt, log_n, l.log_l, tb,
+                               (const int32_t*)lvl(s.level + 1 < plan.n_levels ? plan.level[s.level + 1].off : plan.small_out), lvl(l.off));
+            break;
+        }
+        case PS_RECORD_CHAIN:
+            if (!set.ev_chain) KZG_HIP_TRY(ctx, hipEventCreateWithFlags(&set.ev_chain, hipEventDisableTiming));
+            KZG_HIP_TRY(ctx, hipEventRecord(set.ev_chain, sc));
+            break;
+        case PS_JOIN_CHAIN:
+            KZG_HIP_TRY(ctx, hipStreamWaitEvent(st, set.ev_chain, 0));
+            break;
+        case PS_INVERSES:
+            hipLaunchKernelGGL(k_poly_inverses, dim3(blocks), dim3(POLY_THREADS), 0, st, op.d_a, (uint32_t)n, log_n, tb, d_zt,
+                               (const int32_t*)lvl(plan.next_off), plan.direct, d_inv, partial, ps, (int)plan.fused_y);
+            break;
+        case PS_FINISH_Y:
+            hipLaunchKernelGGL(k_poly_finish_y, dim3(1), dim3(POLY_THREADS), 0, st, op.d_a, (uint32_t)n, log_n, d_zt, partial, blocks, ps);
+            break;
+        case PS_READ_Y:
+            KZG_HIP_TRY(ctx, hipMemcpyAsync(pin + ProofStaging::Y_READBACK, ps, sizeof(ProofScalars), hipMemcpyDeviceToHost, st));
+            break;
+        case PS_QUOTIENT:
+            hipLaunchKernelGGL(k_poly_quotient, dim3(blocks), dim3(POLY_THREADS), 0, st, op.d_a, (uint32_t)n, tb, d_inv, ps, d_q, partial);
+            break;
+        case PS_QUOTIENT_ON_DOMAIN:
+            hipLaunchKernelGGL(k_poly_quotient_on_domain, dim3(1), dim3(POLY_THREADS), 0, st, (uint32_t)n, tb, partial, blocks, ps, d_q);
+            break;
+        case PS_QUOTIENT_TABLE:
+            hipLaunchKernelGGL(k_poly_quotient_table, dim3(blocks), dim3(POLY_THREADS), 0, st, op.d_a, (uint32_t)n, tb, op.table, op.m_known, d_q, partial, ps_out);
+            break;
+        case PS_QUOTIENT_KNOWN:
+            hipLaunchKernelGGL(k_poly_quotient_on_domain_known, dim3(1), dim3(POLY_THREADS), 0, st, op.d_a, (uint32_t)n, tb, partial, blocks, op.m_known, ps_out, d_q);
+            break;
+        case PS_INTT:
+            return ntt_run(ctx, set.c.p, n, true, st, op.nttws);
+        }
+    }
+    if (unchecked) KZG_HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+
 // Enqueue the O(n) part of a proof on `st` with the buffers of `ps_set`, without waiting: upload, denominators + batch
-// inversion, y, quotient (+ on-domain entry), IFFT of the quotient.  y is copied back into ps_set.pinned + 2048 (valid once the
-// stream has been synchronised); the quotient's coefficients are left in ps_set.c.
+// inversion, y, quotient (+ on-domain entry), IFFT of the quotient.  y is left in the read-back slot of ps_set.pinned (ProofStaging::Y_READBACK,
+// valid once the stream has been synchronised); the quotient's coefficients are left in ps_set.c.
 // skip_intt: the caller commits the quotient's EVALUATIONS over a Lagrange basis (prover/src/kzg.rs:96-100 applied to the quotient, exactly
 // what the reference's compute_proof_impl does: kzg.rs:176-177), so they stay in set.c as they are.
 // d_resident: the n evaluations (wire) already on the device in a buffer of the caller's (the jobs of blobstream.hip); read in place
+// evals == nullptr without d_resident: set.a already holds the n evaluations (blob proofs)
+// The driver: the chain's scalars (they say where z lies), plan (proof_plan.h), tables, the reserves from the plan, staging, the known-index
+// table, the plan's steps.
 static int32_t proof_enqueue(kzg_ctx* ctx, PolySet& set, hipStream_t st, NttWorkspace* nttws, const uint64_t* evals, size_t n,
                              const uint64_t z[4], bool want_proof, bool skip_intt = false, const uint4* d_resident = nullptr) {
     RoctxRange range(want_proof ? "kzg:proof:inverses + y + quotient + intt" : "kzg:evaluate:inverses + y");
-    int log_n = ilog2_exact(n);
+    const int log_n = ilog2_ceil(n);
+    uint64_t zt[ProofStaging::zt_count(PROOF_MAX_LOG) * 4];
+    bool z_on_domain = false;
+    proof_fill_scalars(z, log_n, zt, &z_on_domain);
+    ProofOperands op{};
+    op.evals = d_resident ? nullptr : evals;
+    op.nttws = nttws;
+    op.m_known = NO_INDEX;
+    const bool index_known = proof_table_eligible(log_n, want_proof, z_on_domain) && kzg_host::fr_domain_index(z, log_n, &op.m_known);
+    const ProofPlan plan = proof_plan(log_n, want_proof, skip_intt, z_on_domain, index_known,
+                                      d_resident ? PROOF_EVALS_RESIDENT : evals ? PROOF_EVALS_HOST : PROOF_EVALS_IN_SET);
     NttTables tb;
     int32_t rc = ntt_get_tables(ctx, log_n, false, &tb);
     if (rc != KZG_OK) return rc;
-    if (want_proof && n > 1 && !skip_intt) { NttTables tbi; rc = ntt_get_tables(ctx, log_n, true, &tbi); if (rc != KZG_OK) return rc; }
-    // lanes of the last level: 4 elements each (one coset), at least one block
-    const int per_lane = 4;           // = the coset size of the last inversion level (k_poly_inverses)
-    uint32_t blocks = (uint32_t)((n + (size_t)POLY_THREADS * per_lane - 1) / ((size_t)POLY_THREADS * per_lane));
-    if (blocks == 0) blocks = 1;
-    if (!d_resident) KZG_HIP_TRY(ctx, set.a.reserve(n * 32));                 // evaluations (wire)
-    if (d_resident) evals = nullptr;
-    const uint4* d_a = d_resident ? d_resident : set.a.as<uint4>();
-    // inverses (planes) | level scratch: the smaller domains' inverses, two ping-pong plane sets of the small kernel
-    // The one-workgroup kernel takes the chain up to 2^chain_small_log points, x4 levels on the whole chip go on from there: its late levels
-    // keep all 16 waves of one CU busy, a x4 launch over many CUs costs about one of them.  Chain lengths 2..12, off-domain proofs of
-    // 2^11 / 2^12 / 2^14 evaluations (tools/time_proof_sizes.py, same box): 12 -> 0.231 / 0.295 / 0.426 ms, 9 -> 0.226 / 0.281 / 0.414, 7 -> 0.230 / 0.286 / 0.422
-    constexpr int chain_small_log = 9;
-    static_assert(chain_small_log >= 2 && chain_small_log <= (int)POLY_SMALL_MAX_LOG, "the one-workgroup kernel holds the chain's first levels in LDS");
-    const size_t chain_small_max = (size_t)1 << chain_small_log;
-    const size_t n1 = n > chain_small_max ? n / 4 : 0;       // the level above the last one (0: the small kernel gives all n inverses)
-    const size_t lvl_words = n1 ? (n1 + n1 / 2) * NL + 64 : 0;          // sum over n/4, n/16, ... < n1 * 4/3
-    KZG_HIP_TRY(ctx, set.b.reserve((n * NL + lvl_words) * 4));
-    KZG_HIP_TRY(ctx, set.c.reserve(n * 32));                 // quotient (wire)
-    KZG_HIP_TRY(ctx, set.small.reserve(4096 + (size_t)blocks * NL * 4 * 2));
-    if (!set.pinned) KZG_HIP_TRY(ctx, hipHostMalloc(&set.pinned, 4096, hipHostMallocDefault));
-    uint8_t* small = set.small.as<uint8_t>();
-    ProofScalars* ps = reinterpret_cast<ProofScalars*>(small);
-    uint4* d_zt = reinterpret_cast<uint4*>(small + 1024);    // zt[a] = z^(2^a), a <= log_n; zt[log_n + 1] = 1 / (1 - z^n); then z^-(2^a) and three constants (on-domain z)
-    uint4* d_z = d_zt;
-    int32_t* partial = reinterpret_cast<int32_t*>(small + 4096);
-    int32_t* d_inv = set.b.as<int32_t>();
-    int32_t* d_lvl = d_inv + n * NL;
-
-    uint8_t* pin = static_cast<uint8_t*>(set.pinned);       // [0, 1024): init image, [1024, 3072): the scalars of the inversion chain (zt), [3072, ..): y readback
-    ProofScalars* init = reinterpret_cast<ProofScalars*>(pin);
-    memset(init, 0, sizeof *init);
-    init->on_domain_index = NO_INDEX;
-    bool z_on_domain = false;
-    {
-        uint64_t* zt = reinterpret_cast<uint64_t*>(pin + 1024);
-        memcpy(zt, z, 32);
-        for (int a = 1; a <= log_n; ++a) kzg_host::fr_mul(zt + 4 * (a - 1), zt + 4 * (a - 1), zt + 4 * a);
-        const uint64_t one_int[4] = {1, 0, 0, 0};
-        uint64_t one_w[4], den[4];
-        kzg_host::fr_mul(kzg_host::FR_R2, one_int, one_w);
-        kzg_host::fr_sub(one_w, zt + 4 * log_n, den);                // 1 - z^n (zero: z is on the domain, the device inverts what it needs itself)
-        uint64_t* top = zt + 4 * (log_n + 1);
-        uint64_t* zit = zt + 4 * (log_n + 2);                // z^-(2^a), a <= log_n: only read when z is on the domain
-        uint64_t* cst = zt + 4 * (2 * log_n + 3);            // 1/(i - 1), -1/2, 1/(-i - 1), i = w^(n/4) = 5^((r-1)/4)
-        if ((den[0] | den[1] | den[2] | den[3]) == 0) {
-            z_on_domain = true;
-            memset(top, 0, 32);
-            kzg_host::fr_inv(zt, zit);
-            for (int a = 1; a <= log_n; ++a) kzg_host::fr_mul(zit + 4 * (a - 1), zit + 4 * (a - 1), zit + 4 * a);
-        } else {
-            kzg_host::fr_inv(den, top);
-            memset(zit, 0, (size_t)(log_n + 1) * 32);
-        }
-        memcpy(cst, kzg_host::fr_on_domain_constants(), 96);
-    }
+    if (plan.intt && n > 1) { NttTables tbi; rc = ntt_get_tables(ctx, log_n, true, &tbi); if (rc != KZG_OK) return rc; }
+    if (plan.bytes_a) KZG_HIP_TRY(ctx, set.a.reserve(plan.bytes_a));
+    KZG_HIP_TRY(ctx, set.b.reserve(plan.bytes_b));
+    KZG_HIP_TRY(ctx, set.c.reserve(plan.bytes_c));
+    KZG_HIP_TRY(ctx, set.small.reserve(plan.bytes_small));
+    if (!set.pinned) KZG_HIP_TRY(ctx, hipHostMalloc(&set.pinned, ProofStaging::PINNED_BYTES, hipHostMallocDefault));
+    op.d_a = d_resident ? d_resident : set.a.as<uint4>();
+    // the staging image: the initial ProofScalars, zero fill, the chain's scalars
+    uint8_t* pin = static_cast<uint8_t*>(set.pinned);
+    memset(pin + ProofStaging::IMAGE, 0, ProofStaging::IMAGE_BYTES);
+    reinterpret_cast<ProofScalars*>(pin + ProofStaging::IMAGE)->on_domain_index = NO_INDEX;
+    memcpy(pin + ProofStaging::ZT, zt, (size_t)ProofStaging::zt_count(log_n) * 32);
     if (!ctx->poly_lds_attr_set) {
         KZG_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_poly_inv_small), hipFuncAttributeMaxDynamicSharedMemorySize,
                                              (int)(NL * POLY_SMALL_MAX * 4)));
         ctx->poly_lds_attr_set = true;
     }
-    // z = w^m on a domain of at most 4 096 points (compute_proof_with_known_z_fr_index at the reference's bench sizes): the host finds m,
-    // the inverses come from the domain's table 1 / (w^k - 1) -- no inversion chain, no barycentric sum
-    uint32_t m_known = NO_INDEX;
-    if (want_proof && z_on_domain && n >= 2 && n <= POLY_SMALL_MAX && kzg_host::fr_domain_index(z, log_n, &m_known)) {
-        int32_t*& t1 = ctx->ondomain_inv[log_n];
-        if (!t1) {                                           // once per domain size: the chain below at z = 1
-            std::vector<uint64_t> z1((size_t)(2 * log_n + 6) * 4, 0);
-            const uint64_t one_int[4] = {1, 0, 0, 0};
-            uint64_t one_w[4];
-            kzg_host::fr_mul(kzg_host::FR_R2, one_int, one_w);
-            for (int a = 0; a <= log_n; ++a) { memcpy(&z1[4 * (size_t)a], one_w, 32); memcpy(&z1[4 * (size_t)(log_n + 2 + a)], one_w, 32); }
-            memcpy(&z1[4 * (size_t)(2 * log_n + 3)], kzg_host::fr_on_domain_constants(), 96);
-            uint4* d_z1 = nullptr;
-            KZG_HIP_TRY(ctx, hipMalloc(&d_z1, z1.size() * 8));
-            hipError_t e1 = hipMalloc(&t1, (size_t)NL * n * 4);
-            if (e1 == hipSuccess) e1 = hipMemcpy(d_z1, z1.data(), z1.size() * 8, hipMemcpyHostToDevice);
-            if (e1 == hipSuccess) {
-                hipLaunchKernelGGL(k_poly_inv_small, dim3(1), dim3(POLY_SMALL_THREADS), (size_t)NL * n * 4, st, d_z1, log_n, log_n, tb, t1);
-                e1 = hipGetLastError();
-                if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
-            }
-            (void)hipFree(d_z1);
-            if (e1 != hipSuccess) { if (t1) { (void)hipFree(t1); t1 = nullptr; } KZG_HIP_TRY(ctx, e1); }
-        }
-        // (no upload of the ProofScalars image and no copy back: the kernels below only WRITE it, straight into the pinned read-back slot)
-        void* ps_host_dev = nullptr;
-        KZG_HIP_TRY(ctx, hipHostGetDevicePointer(&ps_host_dev, pin + 3072, 0));
-        ProofScalars* ps_out = static_cast<ProofScalars*>(ps_host_dev);
-        if (evals) KZG_HIP_TRY(ctx, hipMemcpyAsync(set.a.p, evals, n * 32, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_poly_quotient_table, dim3(blocks), dim3(POLY_THREADS), 0, st, d_a, (uint32_t)n, tb, t1, m_known,
-                           set.c.as<uint4>(), partial, ps_out);
-        if (blocks > 1)
-            hipLaunchKernelGGL(k_poly_quotient_on_domain_known, dim3(1), dim3(POLY_THREADS), 0, st, d_a, (uint32_t)n, tb, partial, blocks,
-                               m_known, ps_out, set.c.as<uint4>());
-        KZG_HIP_TRY(ctx, hipGetLastError());
-        return skip_intt ? KZG_OK : ntt_run(ctx, set.c.p, n, true, st, nttws);
+    if (plan.form == PROOF_FORM_TABLE) {
+        rc = proof_ondomain_table(ctx, log_n, tb, st, &op.table);
+        if (rc != KZG_OK) return rc;
     }
-    // one upload for the scalar image (pin[0, 1024) -> small[0, 1024)) and the chain's scalars right behind it (pin + 1024 -> small + 1024)
-    static_assert(sizeof(ProofScalars) <= 1024, "the ProofScalars image and the zt table are uploaded as one block");
-    memset(pin + sizeof(ProofScalars), 0, 1024 - sizeof(ProofScalars));
-    // The chain below needs z only, not the evaluations: for a proof from HOST evaluations it is enqueued FIRST, on the context's auxiliary stream, and
-    // runs while this thread is inside the pageable upload of the evaluations (0.6 ms at 2^20; the chain: six launches, ~0.09 ms of latency).
-    hipStream_t sc = st;
-    if (evals && n > chain_small_max) {
-        int32_t rca = ctx_aux_stream(ctx, st, &sc);
-        if (rca != KZG_OK) return rca;
-    }
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(small, pin, 1024 + (size_t)(2 * log_n + 6) * 32, hipMemcpyHostToDevice, sc));
-    if (evals && sc == st) KZG_HIP_TRY(ctx, hipMemcpyAsync(set.a.p, evals, n * 32, hipMemcpyHostToDevice, st));   // nullptr: set.a already holds the n evaluations (blob proofs)
-
-    // the chain of smaller domains, coarsest first: small kernel (<= 4096 points, in LDS), then x4 levels, then the last level
-    const int32_t* next = nullptr;
-    int direct = 0;
-    if (n <= chain_small_max) {
-        hipLaunchKernelGGL(k_poly_inv_small, dim3(1), dim3(POLY_SMALL_THREADS), (size_t)NL * n * 4, st, d_zt, log_n, log_n, tb, d_inv);
-        next = d_inv; direct = 1;
-    } else {
-        int log_l = log_n - 2;                               // sizes n/4, n/16, .. down to the first one <= 4096
-        std::vector<int> logs;
-        while (log_l > chain_small_log) { logs.push_back(log_l); log_l -= 2; }
-        std::vector<int32_t*> bufs;                          // level buffers inside d_lvl: size 2^logs[0] first
-        int32_t* cursor = d_lvl;
-        for (int l : logs) { bufs.push_back(cursor); cursor += ((size_t)NL << l); }
-        int32_t* small_out = cursor;                         // 2^log_l <= 4096 entries
-        hipLaunchKernelGGL(k_poly_inv_small, dim3(1), dim3(POLY_SMALL_THREADS), ((size_t)NL << log_l) * 4, sc, d_zt, log_n, log_l, tb, small_out);
-        const int32_t* prev = small_out;
-        for (int q = (int)logs.size() - 1; q >= 0; --q) {
-            const uint32_t T = 1u << (logs[q] - 2);
-            hipLaunchKernelGGL(k_poly_inv_level, dim3((T + POLY_THREADS - 1) / POLY_THREADS), dim3(POLY_THREADS), 0, sc, d_zt, log_n, logs[q], tb,
-                               prev, bufs[q]);
-            prev = bufs[q];
-        }
-        next = prev;
-        if (sc != st) {                                      // the upload of the evaluations now (the host sits in it while the chain runs), then join
-            KZG_HIP_TRY(ctx, hipGetLastError());
-            if (!set.ev_chain) KZG_HIP_TRY(ctx, hipEventCreateWithFlags(&set.ev_chain, hipEventDisableTiming));
-            KZG_HIP_TRY(ctx, hipEventRecord(set.ev_chain, sc));
-            KZG_HIP_TRY(ctx, hipMemcpyAsync(set.a.p, evals, n * 32, hipMemcpyHostToDevice, st));
-            KZG_HIP_TRY(ctx, hipStreamWaitEvent(st, set.ev_chain, 0));
-        }
-    }
-    const int fused_y = blocks == 1 && !z_on_domain;         // one workgroup holds the whole barycentric sum: no second launch for y
-    hipLaunchKernelGGL(k_poly_inverses, dim3(blocks), dim3(POLY_THREADS), 0, st, d_a, (uint32_t)n, log_n, tb, d_z,
-                       next, direct, d_inv, partial, ps, fused_y);
-    if (!fused_y)
-        hipLaunchKernelGGL(k_poly_finish_y, dim3(1), dim3(POLY_THREADS), 0, st, d_a, (uint32_t)n, log_n, d_z,
-                           partial, blocks, ps);
-    KZG_HIP_TRY(ctx, hipGetLastError());
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(pin + 3072, ps, sizeof(ProofScalars), hipMemcpyDeviceToHost, st));
-    if (!want_proof) return KZG_OK;
-    hipLaunchKernelGGL(k_poly_quotient, dim3(blocks), dim3(POLY_THREADS), 0, st, d_a, (uint32_t)n, tb, d_inv,
-                       ps, set.c.as<uint4>(), partial);
-    if (z_on_domain)                                         // (z off the domain: the kernel would return at once)
-        hipLaunchKernelGGL(k_poly_quotient_on_domain, dim3(1), dim3(POLY_THREADS), 0, st, (uint32_t)n, tb, partial, blocks, ps,
-                           set.c.as<uint4>());
-    KZG_HIP_TRY(ctx, hipGetLastError());
-    // commit_eval_form(quotient): coefficients = IFFT(q), then MSM over the monomial SRS (kzg.rs:176-177)
-    return skip_intt ? KZG_OK : ntt_run(ctx, set.c.p, n, true, st, nttws);
+    return proof_launch(ctx, set, st, plan, tb, op);
 }
 // The cached Lagrange basis of exactly n points, if the SRS carries one (without one: the IFFT + monomial-basis form)
 static const kzg_srs* proof_lagrange_basis(const kzg_srs* srs, size_t n) {
@@ -884,7 +874,7 @@ static const kzg_srs* proof_lagrange_basis(const kzg_srs* srs, size_t n) {
     return srs_cached_lagrange(srs, n);
 }
 static void proof_read_y(const PolySet& set, uint64_t* out_y) {
-    const ProofScalars* host = reinterpret_cast<const ProofScalars*>(static_cast<const uint8_t*>(set.pinned) + 3072);
+    const ProofScalars* host = reinterpret_cast<const ProofScalars*>(static_cast<const uint8_t*>(set.pinned) + ProofStaging::Y_READBACK);
     memcpy(out_y, host->y_wire, 32);
 }
 
@@ -902,22 +892,19 @@ int32_t proof_run(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* evals, size_
     if (rc != KZG_OK) { (void)hipStreamSynchronize(st); return rc; }
     if (lag) {
         rc = msm_run(ctx, srs_bases(lag, 0, n, ctx->msm_c_override == 0), set.c.p, n, out_xy, out_inf, out_xyzz);
-        if (rc == KZG_OK && out_y) proof_read_y(set, out_y);
-        return rc;
-    }
-    // the whole SRS commits the whole quotient; a shard holding powers [coeff_lo, coeff_lo + srs->n) commits its slice of it
-    if (!want_proof || coeff_lo >= n) {
+    } else if (want_proof && coeff_lo < n) {
+        // the whole SRS commits the whole quotient; a shard holding powers [coeff_lo, coeff_lo + srs->n) commits its slice of it
+        const size_t len = std::min(srs->n, n - coeff_lo);
+        rc = msm_run(ctx, srs_bases(srs, 0, len, ctx->msm_c_override == 0), set.c.as<uint4>() + 2 * coeff_lo, len, out_xy, out_inf, out_xyzz);
+    } else {
+        // nothing to commit: an evaluation only, or a shard past the quotient's end (its share is the identity)
         KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (out_y) proof_read_y(set, out_y);
         if (want_proof) {
             if (out_xyzz) memset(out_xyzz, 0, 128);
             if (out_xy) { memset(out_xy, 0, 64); if (out_inf) *out_inf = 1; }
         }
-        return KZG_OK;
     }
-    const size_t len = std::min(srs->n, n - coeff_lo);
-    rc = msm_run(ctx, srs_bases(srs, 0, len, ctx->msm_c_override == 0), set.c.as<uint4>() + 2 * coeff_lo, len, out_xy, out_inf, out_xyzz);
-    if (rc == KZG_OK && out_y) proof_read_y(set, out_y);      // msm_run has synchronised the stream
+    if (rc == KZG_OK && out_y) proof_read_y(set, out_y);      // the stream is synchronised: by msm_run, or just above
     return rc;
 }
 

@@ -71,3 +71,17 @@ def test_g1fft_planner_under_asan_ubsan(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, env=ENV, timeout=600)
     want = open(os.path.join(HERE, "golden", "g1fft_plans.txt")).read()
     assert r.returncode == 0 and r.stdout == want, (r.stdout[-500:], r.stderr[-3000:])
+
+
+def test_ntt_and_proof_planners_and_scalar_table_under_asan_ubsan(tmp_path):
+    """csrc/ntt_plan.h and csrc/proof_plan.h over their whole plan grids and proof_fill_scalars over its cases (tables of exactly 2 log n + 6 elements on
+    the heap), as the stand-alone programs of tests/test_ntt_plan_host.py, tests/test_proof_plan_host.py and tests/test_proof_scalars_host.py."""
+    for name, golden in (("ntt_plancheck", "ntt_plans.txt"), ("proof_plancheck", "proof_plans.txt"), ("proof_scalars", None)):
+        exe = str(tmp_path / (name + "_san"))
+        subprocess.check_call(["g++", "-std=c++17", *SAN, "-I" + CSRC, os.path.join(HERE, "hostcheck", name + ".cpp"), "-o", exe])
+        r = subprocess.run([exe], capture_output=True, text=True, env=ENV, timeout=600)
+        assert r.returncode == 0 and r.stderr == "", (name, r.stdout[-500:], r.stderr[-3000:])
+        if golden:
+            assert r.stdout == open(os.path.join(HERE, "golden", golden)).read(), name
+        else:
+            assert len(r.stdout.splitlines()) == 6 * 5 + 12, name
