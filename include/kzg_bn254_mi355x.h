@@ -278,6 +278,27 @@ int32_t kzg_compute_multiproofs(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly
                                 size_t chunk_len, uint64_t* out_xy_mont, uint8_t* out_is_infinity);
 int32_t kzg_srs_cache_multiproof(kzg_ctx* ctx, kzg_srs* srs, size_t n, size_t chunk_len);
 int32_t kzg_srs_drop_multiproof(kzg_ctx* ctx, kzg_srs* srs);
+/* The encoder of a data-availability scheme: a blob of d = poly_len coefficients, evaluated on the domain of n = r d points (rate 1/r)
+ * and handed out as the m = n / l cosets of l = chunk_len values, each with its proof -- kzg_compute_multiproofs aware of the degree
+ * bound deg f < d <= n.  The conventions are kzg_compute_multiproofs': w the library's primitive n-th root, coset k < m is
+ * {w^(k + j m) : j < l}, its proof [f / (X^l - w^(k l))](tau) G1.  Every quotient has degree < d - l, so the SRS needs d points, not n,
+ * and the FK20 table is the (d, l) entry that kzg_srs_cache_multiproof(srs, d, l) builds (2d points); only the last transform, m points
+ * of which m / r are not the identity, sees n.  With n = poly_len the proofs are those of kzg_compute_multiproofs.
+ * poly: d Fr elements, coefficients (eval_form = 0) or evaluations on the d-point domain {(w^r)^i} (eval_form = 1; inverse-NTT'd on
+ * the device).  out_ys: m x l x 4 u64 canonical wire words, ys[k][j] = f(w^(k + j m)), the rows kzg_verify_multiproof* and
+ * kzg_recover_from_cosets take.  out_proofs_xy: m x 8 u64 affine wire points (the identity as zeros), out_is_infinity: m flags, required
+ * when proofs are asked for.  Either output may be NULL (it is then not computed), not both.
+ * Errors, checked on the host before any kernel runs, in this order:
+ *   1. a null ctx, srs or poly; both outputs NULL; proofs without flags -> KZG_ERR_INVALID_ARG;
+ *   2. srs of another context, or a Lagrange-basis handle -> KZG_ERR_INVALID_ARG;
+ *   3. poly_len or n zero or not a power of two -> KZG_ERR_NOT_POWER_OF_TWO;
+ *   4. n > 2^24 -> KZG_ERR_DOMAIN;
+ *   5. poly_len > n, poly_len = 1, chunk_len not a power of two or > poly_len / 2 -> KZG_ERR_INVALID_ARG;
+ *   6. poly_len > kzg_srs_len(srs) -> KZG_ERR_SRS_CAPACITY_EXCEEDED.
+ * A failed allocation -> KZG_ERR_DEVICE (kzg_ctx_last_error has the text).  After any error the context stays usable. */
+int32_t kzg_encode_cosets(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, size_t poly_len /* d */, int32_t eval_form,
+                          size_t n, size_t chunk_len, uint64_t* out_ys_mont /* m x chunk_len x 4, may be NULL */,
+                          uint64_t* out_proofs_xy_mont /* m x 8, may be NULL */, uint8_t* out_is_infinity /* m */);
 /* KZG::compute_proof / compute_proof_impl (kzg.rs:128-178, :215-234, on-domain branch :237-260).
  * roots = KZG::expanded_roots_of_unity (n_roots entries); n != n_roots -> KZG_ERR_ROOTS_LENGTH.
  * out_y (optional, 4 u64) receives y = p(z) (helpers.rs:475-535). */

@@ -460,6 +460,16 @@ public:
                       srs.context().handle(), (blob.len() + 31) / 32, srs.len());
         return out;
     }
+    // The encoder (kzg_encode_cosets; the reference has none): d = polynomial.len() elements evaluated on the domain of n = r d points and cut
+    // into the m = n / chunk_len cosets, each with its proof.  ys: m x chunk_len values (row k = the values of coset k), proofs: m points; an
+    // output that is not asked for stays empty.  srs needs d points, not n.
+    struct EncodedCosets { std::vector<Fr> ys; std::vector<G1Affine> proofs; };
+    EncodedCosets encode_cosets(const PolynomialCoeffForm& polynomial, const SRS& srs, size_t n, size_t chunk_len = 1, bool values = true, bool proofs = true) const {
+        return encode_impl(polynomial.coeffs(), 0, srs, n, chunk_len, values, proofs);
+    }
+    EncodedCosets encode_cosets(const PolynomialEvalForm& polynomial, const SRS& srs, size_t n, size_t chunk_len = 1, bool values = true, bool proofs = true) const {
+        return encode_impl(polynomial.evaluations(), 1, srs, n, chunk_len, values, proofs);
+    }
     // Erasure decoding (kzg_recover_from_cosets; the reference has none): the polynomial of degree < count * l through the values of `count` distinct
     // cosets of the n-point domain, ys[i l .. (i + 1) l) being the values of coset coset_indices[i] (any order), l = ys.size() / count.  degree_bound = 0
     // means count * l; values that are not those of a polynomial below the bound are a GenericError.  n evaluations / n coefficients.
@@ -472,6 +482,26 @@ public:
         return PolynomialCoeffForm::new_(recover_impl(coset_indices, ys, n, degree_bound, 0, ctx));
     }
 private:
+    static EncodedCosets encode_impl(const std::vector<Fr>& poly, int32_t eval_form, const SRS& srs, size_t n, size_t l, bool values, bool proofs) {
+        const size_t d = poly.size();
+        if (!values && !proofs) throw KzgError::GenericError("encode_cosets needs values, proofs or both");
+        if (d == 0 || (d & (d - 1)) != 0 || n == 0 || (n & (n - 1)) != 0) throw KzgError::FFTError("length provided is not a power of 2");
+        if (n > ((size_t)1 << 24)) throw KzgError::FFTError("Could not perform IFFT due to domain consturction error");
+        if (d < 2) throw KzgError::GenericError("encode_cosets needs a polynomial of at least 2 elements");
+        if (d > n) throw KzgError::GenericError("the domain is shorter than the polynomial");
+        if (l == 0 || (l & (l - 1)) != 0) throw KzgError::GenericError("chunk length is not a power of 2");
+        if (l > d / 2) throw KzgError::GenericError("chunk length exceeds half the polynomial length");
+        if (d > srs.len()) throw KzgError::SrsCapacityExceeded(d, srs.len());
+        const size_t m = n / l;
+        EncodedCosets out;
+        if (values) out.ys.resize(n);
+        if (proofs) out.proofs.resize(m);
+        std::vector<uint8_t> inf(m);
+        detail::check(kzg_encode_cosets(srs.context().handle(), srs.handle(), poly.data()->limbs.data(), d, eval_form, n, l, values ? out.ys.data()->limbs.data() : nullptr,
+                                        proofs ? out.proofs.data()->xy.data() : nullptr, inf.data()),
+                      srs.context().handle(), d, srs.len());
+        return out;
+    }
     static std::vector<Fr> recover_impl(const std::vector<uint64_t>& coset_indices, const std::vector<Fr>& ys, size_t n, size_t degree_bound, int32_t eval_form,
                                         const Context& ctx) {
         const size_t count = coset_indices.size();

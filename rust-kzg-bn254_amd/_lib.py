@@ -98,6 +98,7 @@ PROTOTYPES = {
     "kzg_srs_lagrange": (i32, [vp, vp, sz, C.POINTER(vp)]),
     "kzg_srs_drop_lagrange": (i32, [vp, vp]),
     "kzg_compute_multiproofs": (i32, [vp, vp, u64p, sz, i32, sz, u64p, u8p]),
+    "kzg_encode_cosets": (i32, [vp, vp, u64p, sz, i32, sz, sz, u64p, u64p, u8p]),
     "kzg_srs_cache_multiproof": (i32, [vp, vp, sz, sz]),
     "kzg_srs_drop_multiproof": (i32, [vp, vp]),
     "kzg_blob_to_fr": (i32, [vp, u8p, sz, u64p, sz, C.POINTER(sz)]),

@@ -1,5 +1,5 @@
 // capi_srs.hip — the kzg_srs_* surface of the C-ABI: upload / generation / decompression of an SRS, the packed-SRS file, Lagrange bases
-// and their cache, the FK20 multi-proof tables and proofs.
+// and their cache, the FK20 multi-proof tables and proofs, the encoder (cosets of values with their proofs).
 #include "engine.h"
 #include "host_sha256.h"
 
@@ -339,6 +339,18 @@ int32_t kzg_compute_multiproofs(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly
     std::lock_guard<std::mutex> lk(ctx->mu);
     KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     return multiproof_run(ctx, srs, poly_mont, n, eval_form != 0, chunk_len, out_xy_mont, out_is_infinity);
+}
+
+int32_t kzg_encode_cosets(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, size_t poly_len, int32_t eval_form, size_t n, size_t chunk_len,
+                          uint64_t* out_ys_mont, uint64_t* out_proofs_xy_mont, uint8_t* out_is_infinity) {
+    const bool bad_pointers = !ctx || !srs || !poly_mont || (!out_ys_mont && !out_proofs_xy_mont) || (out_proofs_xy_mont && !out_is_infinity);
+    const bool bad_srs = !bad_pointers && (srs->ctx != ctx || srs->lagrange_of != 0);
+    int32_t rc = encode_check(bad_pointers, bad_srs, poly_len, n, chunk_len, srs ? srs->n : 0);
+    if (rc != KZG_OK) return rc;
+    const EncodePlan plan = encode_plan(poly_len, n, chunk_len, out_ys_mont != nullptr, out_proofs_xy_mont != nullptr);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return multiproof_encode(ctx, srs, poly_mont, eval_form != 0, plan, out_ys_mont, out_proofs_xy_mont, out_is_infinity);
 }
 
 int32_t kzg_srs_cache_multiproof(kzg_ctx* ctx, kzg_srs* srs, size_t n, size_t chunk_len) {

@@ -10,6 +10,7 @@
 #include "../../include/kzg_bn254_mi355x.h"
 #include "msm_plan.h"      // MsmBasesShape, msm_batch_capacity
 #include "host_recover.h"  // RecoverPlan
+#include "host_encode.h"   // EncodePlan
 
 namespace kzg {
 
@@ -262,11 +263,16 @@ int32_t g1_ifft_device(kzg_ctx* ctx, const kzg_srs* srs, size_t n, uint4* d_out,
 // the generic G1 transform of XYZZ planes (g1fft.hip): forward or inverse, optional 1/n, input read with its own stride; and the
 // batched affine conversion of n planes.  Both enqueued on st.
 int32_t g1_fft_planes(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t n, int32_t* out, int32_t* tmp, bool inverse, bool scaled);
+// the forward transform of an input that is the identity from point `nonzero` on (host_encode.h: the spread load of the radix-2 form)
+int32_t g1_fft_planes_padded(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t nonzero, size_t n, int32_t* out, int32_t* tmp);
 int32_t g1fft_planes_to_affine(kzg_ctx* ctx, hipStream_t st, const int32_t* planes, size_t n, uint4* d_out, bool wire, int32_t* scratch);
 // FK20 multi-proofs (multiproof.hip): the cached FFT_2m(S^(b)) of (srs, n, l), built if absent; the proofs of every coset of l points
 int32_t multiproof_cache(kzg_ctx* ctx, kzg_srs* srs, size_t n, size_t l, const uint4** out);
 int32_t multiproof_run(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, size_t n, bool eval_form, size_t l, uint64_t* out_xy, uint8_t* out_inf);
 void multiproof_drop(kzg_srs* srs);
+// kzg_encode_cosets (multiproof.hip): the m = n / l cosets of values and their proofs for d = plan.d coefficients or evaluations;
+// either output may be null.  Called under ctx->mu with the arguments checked, synchronised on return
+int32_t multiproof_encode(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, bool eval_form, const EncodePlan& plan, uint64_t* out_ys, uint64_t* out_xy, uint8_t* out_inf);
 // verification of coset proofs (multiverify.hip): d_out[t] = sum_i weights[i] w^(-ks[i] t) IFFT_l(ys_i)[t], enqueued on ctx->stream (d_ys is scratch when l > 1024)
 int32_t coset_interpolate_rlc_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, size_t count, size_t n, size_t l, uint4* d_out);
 // erasure decoding (recover.hip): the polynomial of degree < count l through the values of the plan's cosets (ys: host, count x l wire values), as n

@@ -24,6 +24,7 @@
 #include "glv_lanes.h"
 #include "host_curve.h"
 #include "g1fft_plan.h"
+#include "host_encode.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -638,6 +639,29 @@ k_g1fft_gather_planes(const int32_t* __restrict__ src, size_t src_stride, uint32
     for (int k = 0; k < 4 * NL; ++k) dst[(size_t)k * n + i] = src[(size_t)k * src_stride + j];
 }
 
+// ---- a zero-padded input (g1_fft_planes_padded): only the first `nonzero` points of src exist, the identity stands after them ----------
+// dst[i] = src[i] for i < nonzero, the identity (literal zeros) for nonzero <= i < n: the input copy of the direct stages
+__global__ void __launch_bounds__(256)
+k_g1fft_pad_planes(const int32_t* __restrict__ src, size_t src_stride, uint32_t nonzero, uint32_t n, int32_t* __restrict__ dst) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+#pragma unroll
+    for (int k = 0; k < 4 * NL; ++k) dst[(size_t)k * n + i] = i < nonzero ? src[(size_t)k * src_stride + i] : 0;
+}
+
+// The spread load: dst[i] = src[bitrev_{log_nonzero}(i >> log_r)], i < n = 2^(log_nonzero + log_r), one lane per output point.  In
+// bit-reversed order the non-zero inputs of the radix-2 form stand on the multiples of r = 2^log_r, and the stages 1 .. log_r are
+// butterflies (A, 0) -> (A, A): after them every run of r consecutive points holds one input, which is what this load writes.
+__global__ void __launch_bounds__(256)
+k_g1fft_spread_planes(const int32_t* __restrict__ src, size_t src_stride, uint32_t n, int log_nonzero, int log_r, int32_t* __restrict__ dst) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t q = i >> log_r;                                 // < 2^log_nonzero
+    const uint32_t j = log_nonzero > 0 ? (__brev(q) >> (32 - log_nonzero)) : 0;
+#pragma unroll
+    for (int k = 0; k < 4 * NL; ++k) dst[(size_t)k * n + i] = src[(size_t)k * src_stride + j];
+}
+
 // n XYZZ planes (stride n) -> n affine points (wire, or the device format of curve.h; identity = zeros), the batched conversion of
 // g1_ifft_device; scratch: n x NL words.  Enqueued on st.
 int32_t g1fft_planes_to_affine(kzg_ctx* ctx, hipStream_t st, const int32_t* planes, size_t n, uint4* d_out, bool wire, int32_t* scratch) {
@@ -663,6 +687,8 @@ struct G1fftOperands {
     uint32_t t3_points = 0;
     Naf2Lists nl;
     const uint4* tab = nullptr;                     // first-tables stage: the window tables
+    uint32_t nonzero = 0;                           // pad / spread load: the points the input has
+    int log_nonzero = 0;
 };
 
 static int32_t g1fft_fetch_scalars(kzg_ctx* ctx, const G1fftPlan& p, G1fftOperands& io) {
@@ -712,6 +738,12 @@ static int32_t g1fft_launch(kzg_ctx* ctx, hipStream_t st, const G1fftPlan& p, co
             break;
         case G1S_RADIX2_PAIRS:
             hipLaunchKernelGGL(k_g1fft_stage_pairs, grid, block, 0, st, dst, n, log_n, s.log_s, scal, last);
+            break;
+        case G1S_GATHER_PAD:
+            hipLaunchKernelGGL(k_g1fft_pad_planes, grid, block, 0, st, io.in, io.in_stride, io.nonzero, n, dst);
+            break;
+        case G1S_SPREAD_BITREV:
+            hipLaunchKernelGGL(k_g1fft_spread_planes, grid, block, 0, st, io.in, io.in_stride, n, io.log_nonzero, s.log_s, dst);
             break;
         case G1S_KINDS:
             break;
@@ -801,6 +833,25 @@ int32_t g1_fft_planes(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in
     io.in = in;
     io.in_stride = in_stride;
     io.buf[p.result] = out;                                                  // the plan's ping-pong ends in out
+    io.buf[1 - p.result] = tmp;
+    return g1fft_launch(ctx, st, p, io);
+}
+
+// The forward, unscaled transform of g1_fft_planes for an input whose points from `nonzero` on are the identity and are NOT read:
+// in holds `nonzero` points (a power of two, <= n) with stride in_stride.  The plan is host_encode.h's: the direct stages behind a
+// copy that pads, or the spread load and the radix-2 stages log2(n / nonzero) + 1 .. log2 n, on lanes or lane pairs as
+// g1fft_choose_plan says for n.  The same group elements as g1_fft_planes on the padded input.  Enqueued on st.
+int32_t g1_fft_planes_padded(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t nonzero, size_t n, int32_t* out, int32_t* tmp) {
+    const G1fftPaddedPlan pp = g1fft_plan_planes_padded(n, nonzero);
+    const G1fftPlan& p = pp.plan;
+    G1fftOperands io;
+    int32_t rc = g1fft_fetch_scalars(ctx, p, io);
+    if (rc != KZG_OK) return rc;
+    io.in = in;
+    io.in_stride = in_stride;
+    io.nonzero = pp.nonzero;
+    io.log_nonzero = pp.log_nonzero;
+    io.buf[p.result] = out;
     io.buf[1 - p.result] = tmp;
     return g1fft_launch(ctx, st, p, io);
 }

@@ -41,6 +41,8 @@ enum G1fftStageKind {
     G1S_DIRECT, G1S_DIRECT_PAIRS,  // k_g1fft_direct, k_g1fft_direct_pairs
     G1S_MUL_QUADS,                 // k_g1fft_mul_quads
     G1S_RADIX2, G1S_RADIX2_PAIRS,  // k_g1fft_stage, k_g1fft_stage_pairs
+    G1S_GATHER_PAD,                // k_g1fft_pad_planes: the first `nonzero` points of the input, the identity after them (host_encode.h)
+    G1S_SPREAD_BITREV,             // k_g1fft_spread_planes: the bit-reversed load and the first log_s radix-2 stages of a zero-padded input
     G1S_KINDS
 };
 // the key of a scalar table (get_scalars): bit 0 = times 1/n, bits 1-2 = canon (1: canonical integers), bit 3 = forward (w^+e)

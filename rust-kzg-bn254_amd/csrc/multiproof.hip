@@ -22,7 +22,13 @@
 //     the stage is one multiplication deep like an FFT stage, and the pair form's gain there (0.83 against 1.25 ms) was not measured here.
 //   * the Fr side: l NTTs of 2m points, one ntt_run each (a single batched launch was not written: at l = 16 they are 16 short launches).
 //   * the cache build transforms the l sequences one after the other (gather, forward FFT, affine conversion each).
-// Measured figures: README.md ("Multi-proofs") and profiles/multiproof.md.
+//
+// The encoder (multiproof_encode, kzg_encode_cosets): d coefficients evaluated on n = r d points, deg f < d.  Every quotient has degree
+// < d - l, so steps 1-4 run with d in the place of n (m' = d / l, transforms of 2m' points, the cache entry (d, l), d SRS points): fk20_h,
+// shared with multiproof_run.  Step 5 alone sees n: pi = DFT_m(h_0 .. h_{m'-1}, 0 x (m - m')), m = n / l, by g1_fft_planes_padded (g1fft.hip;
+// plan in host_encode.h: the spread load instead of the first log2 r radix-2 stages, the zeros never read).  The values are one Fr NTT of
+// the zero-extended coefficients, written coset-major (k_encode_gather_cosets).
+// Measured figures: README.md ("multi-proofs", "the encoder"), profiles/multiproof.md and profiles/encode.md.
 #include "engine.h"
 #include "glv.h"
 
@@ -190,35 +196,16 @@ void multiproof_drop(kzg_srs* srs) {
 }
 
 // ---- the proofs -------------------------------------------------------------------------------------------------------------------
-// called under ctx->mu with the arguments checked (capi_srs.hip kzg_compute_multiproofs)
-int32_t multiproof_run(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, size_t n, bool eval_form, size_t l, uint64_t* out_xy, uint8_t* out_inf) {
-    RoctxRange range("kzg:multiproofs");
-    const uint4* shat = nullptr;
-    int32_t rc = multiproof_cache(ctx, srs, n, l, &shat);
-    if (rc != KZG_OK) return rc;
-    const size_t m = n / l, M = 2 * m;
-    hipStream_t st = ctx->stream;
-    // W waves per frequency when l > 64 (<= 32), a lane adding tpl terms
-    const int log_g = l >= 64 ? 6 : __builtin_ctzll(l);
-    const uint32_t W = l > 64 ? (uint32_t)std::min<size_t>(l / 64, 32) : 1u;
-    const uint32_t tpl = (uint32_t)(l / ((size_t)W << log_g));
-    KZG_HIP_TRY(ctx, ctx->mp[0].reserve(n * 32));
-    KZG_HIP_TRY(ctx, ctx->mp[1].reserve(2 * n * 32));
-    KZG_HIP_TRY(ctx, ctx->mp[2].reserve(M * W * 36 * 4));
-    KZG_HIP_TRY(ctx, ctx->mp[3].reserve(M * 36 * 4));
-    KZG_HIP_TRY(ctx, ctx->mp[4].reserve(M * 36 * 4));
-    KZG_HIP_TRY(ctx, ctx->mp[5].reserve(m * (64 + 1 + NL * 4)));
-    uint4* f = ctx->mp[0].as<uint4>();
-    uint4* F = ctx->mp[1].as<uint4>();
-    int32_t* P0 = ctx->mp[2].as<int32_t>();
-    int32_t* P1 = ctx->mp[3].as<int32_t>();
-    int32_t* P2 = ctx->mp[4].as<int32_t>();
-    uint4* d_aff = ctx->mp[5].as<uint4>();                                   // m x 64 B
-    int32_t* aff_scratch = reinterpret_cast<int32_t*>(ctx->mp[5].as<uint8_t>() + m * 64);   // m x NL words
-    uint8_t* d_inf = ctx->mp[5].as<uint8_t>() + m * (64 + NL * 4);
-    // 1. coefficients (eval form: inverse NTT on the device), the l rows F^(b) and their NTTs
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(f, poly_mont, n * 32, hipMemcpyHostToDevice, st));
-    if (eval_form) { rc = ntt_run(ctx, f, n, true, st, &ctx->mp_ntt); if (rc != KZG_OK) return rc; }
+// Steps 1-4 for d coefficients on the device (f), shared by multiproof_run (d = n) and multiproof_encode (d <= n): the l rows F^(b)
+// and their NTTs, H = sum_b Fhat^(b) o Shat^(b), the inverse transform of H.  m = d / l, M = 2m; F: l x M wire values; P0 (M W points),
+// P1, P2 (M points each or more): plane sets.  *X_out = the planes that hold IFFT_2m(H) (stride M: h is its slice [m - 1, 2m - 1)),
+// *Y_out = the plane set that is free again (P2 stays scratch).  Enqueued on st.
+static int32_t fk20_h(kzg_ctx* ctx, hipStream_t st, const uint4* shat, const uint4* f, uint4* F, size_t d, size_t l, const Fk20Shape& sh,
+                      int32_t* P0, int32_t* P1, int32_t* P2, int32_t** X_out, int32_t** Y_out) {
+    const size_t m = d / l, M = 2 * m;
+    const int log_g = sh.log_g;
+    const uint32_t W = sh.W, tpl = sh.tpl;
+    int32_t rc = KZG_OK;
     hipLaunchKernelGGL(k_fk20_scatter_coeffs, dim3(grid_of(M * l)), dim3(256), 0, st, f, (uint32_t)m, (uint32_t)l, F);
     for (size_t b = 0; b < l; ++b) {
         rc = ntt_run(ctx, F + 2 * b * M, M, false, st, &ctx->mp_ntt);
@@ -233,20 +220,112 @@ int32_t multiproof_run(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, si
         if (W > 1) hipLaunchKernelGGL(k_fk20_sum_partials, dim3(grid_of(M)), dim3(256), 0, st, P0, (uint32_t)M, W, H);
     }
     KZG_HIP_TRY(ctx, hipGetLastError());
-    // 3. h = IFFT_2m(H)[m - 1, 2m - 1), 4. pi = DFT_m(h): the slice is read in place (offset m - 1, stride 2m)
+    // 3. h = IFFT_2m(H)[m - 1, 2m - 1): left in place for the next transform to read (offset m - 1, stride 2m)
     int32_t* X = W > 1 ? P0 : P1;                                               // the plane set H is not in
     rc = g1_fft_planes(ctx, st, H, M, M, X, P2, true, true);
     if (rc != KZG_OK) return rc;
-    int32_t* Y = H;                                                              // free again: stride m
-    rc = g1_fft_planes(ctx, st, X + (m - 1), M, m, Y, P2, false, false);
-    if (rc != KZG_OK) return rc;
-    // 5. one batched affine conversion (wire form, identity = zeros) and the identity flags
-    rc = g1fft_planes_to_affine(ctx, st, Y, m, d_aff, true, aff_scratch);
+    *X_out = X;
+    *Y_out = H;                                                                  // free again
+    return KZG_OK;
+}
+
+// 5. m points of planes Y -> wire affine points (identity = zeros) and identity flags in `work` (m x 64 B | m x NL words | m flags), copied out
+static int32_t fk20_emit(kzg_ctx* ctx, hipStream_t st, const int32_t* Y, size_t m, uint8_t* work, uint64_t* out_xy, uint8_t* out_inf) {
+    uint4* d_aff = reinterpret_cast<uint4*>(work);                               // m x 64 B
+    int32_t* aff_scratch = reinterpret_cast<int32_t*>(work + m * 64);            // m x NL words
+    uint8_t* d_inf = work + m * (64 + NL * 4);
+    int32_t rc = g1fft_planes_to_affine(ctx, st, Y, m, d_aff, true, aff_scratch);
     if (rc != KZG_OK) return rc;
     hipLaunchKernelGGL(k_fk20_inf_flags, dim3(grid_of(m)), dim3(256), 0, st, Y, (uint32_t)m, d_inf);
     KZG_HIP_TRY(ctx, hipGetLastError());
     KZG_HIP_TRY(ctx, hipMemcpyAsync(out_xy, d_aff, m * 64, hipMemcpyDeviceToHost, st));
     if (out_inf) KZG_HIP_TRY(ctx, hipMemcpyAsync(out_inf, d_inf, m, hipMemcpyDeviceToHost, st));
+    return KZG_OK;
+}
+
+// called under ctx->mu with the arguments checked (capi_srs.hip kzg_compute_multiproofs)
+int32_t multiproof_run(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, size_t n, bool eval_form, size_t l, uint64_t* out_xy, uint8_t* out_inf) {
+    RoctxRange range("kzg:multiproofs");
+    const uint4* shat = nullptr;
+    int32_t rc = multiproof_cache(ctx, srs, n, l, &shat);
+    if (rc != KZG_OK) return rc;
+    const size_t m = n / l, M = 2 * m;
+    hipStream_t st = ctx->stream;
+    const Fk20Shape sh = fk20_shape(l);                                          // W waves per frequency when l > 64 (<= 32), a lane adding tpl terms
+    KZG_HIP_TRY(ctx, ctx->mp[0].reserve(n * 32));
+    KZG_HIP_TRY(ctx, ctx->mp[1].reserve(2 * n * 32));
+    KZG_HIP_TRY(ctx, ctx->mp[2].reserve(M * sh.W * 36 * 4));
+    KZG_HIP_TRY(ctx, ctx->mp[3].reserve(M * 36 * 4));
+    KZG_HIP_TRY(ctx, ctx->mp[4].reserve(M * 36 * 4));
+    KZG_HIP_TRY(ctx, ctx->mp[5].reserve(m * (64 + 1 + NL * 4)));
+    uint4* f = ctx->mp[0].as<uint4>();
+    int32_t* P2 = ctx->mp[4].as<int32_t>();
+    // 1. coefficients (eval form: inverse NTT on the device), then steps 1-4
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(f, poly_mont, n * 32, hipMemcpyHostToDevice, st));
+    if (eval_form) { rc = ntt_run(ctx, f, n, true, st, &ctx->mp_ntt); if (rc != KZG_OK) return rc; }
+    int32_t *X = nullptr, *Y = nullptr;
+    rc = fk20_h(ctx, st, shat, f, ctx->mp[1].as<uint4>(), n, l, sh, ctx->mp[2].as<int32_t>(), ctx->mp[3].as<int32_t>(), P2, &X, &Y);
+    if (rc != KZG_OK) return rc;
+    // 4. pi = DFT_m(h): the slice is read in place (offset m - 1, stride 2m); Y: stride m
+    rc = g1_fft_planes(ctx, st, X + (m - 1), M, m, Y, P2, false, false);
+    if (rc != KZG_OK) return rc;
+    // 5. one batched affine conversion (wire form, identity = zeros) and the identity flags
+    rc = fk20_emit(ctx, st, Y, m, ctx->mp[5].as<uint8_t>(), out_xy, out_inf);
+    if (rc != KZG_OK) return rc;
+    KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    return KZG_OK;
+}
+
+// ---- the encoder: cosets of values and their proofs for d coefficients on a domain of n = r d points --------------------------------
+// ys[k l + j] = evals[k + j m]: the coset-major order of KZG.cosets (wire Fr, 32 B each)
+__global__ void __launch_bounds__(256)
+k_encode_gather_cosets(const uint4* __restrict__ evals, uint32_t n, int log_l, int log_m, uint4* __restrict__ ys) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t k = i >> log_l, j = i & ((1u << log_l) - 1);
+    const size_t s = (size_t)k + ((size_t)j << log_m);
+    ys[2 * (size_t)i] = evals[2 * s];
+    ys[2 * (size_t)i + 1] = evals[2 * s + 1];
+}
+
+static_assert(ENCODE_LIMBS == NL && G1FFT_POINT_BYTES == 4 * NL * 4, "host_encode.h sizes the workspaces from these");
+
+// called under ctx->mu with the arguments checked and planned (capi_srs.hip kzg_encode_cosets).  The FK20 steps 1-4 see d only (the
+// cache entry is (d, l)); step 5 is the m-point transform of h zero-padded (g1_fft_planes_padded); the values are one n-point NTT of the
+// zero-extended coefficients.
+int32_t multiproof_encode(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, bool eval_form, const EncodePlan& plan, uint64_t* out_ys, uint64_t* out_xy, uint8_t* out_inf) {
+    RoctxRange range("kzg:encode_cosets");
+    const size_t d = plan.d, n = plan.n, l = plan.l, m = plan.m, mp = plan.mp, M = plan.M;
+    const uint4* shat = nullptr;
+    int32_t rc = KZG_OK;
+    if (plan.proofs) { rc = multiproof_cache(ctx, srs, d, l, &shat); if (rc != KZG_OK) return rc; }
+    hipStream_t st = ctx->stream;
+    for (int i = 0; i < 6; ++i) KZG_HIP_TRY(ctx, ctx->mp[i].reserve(plan.bytes[i]));
+    uint4* f = ctx->mp[0].as<uint4>();
+    uint4* F = ctx->mp[1].as<uint4>();
+    // the d coefficients (eval form: inverse NTT of size d on the device)
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(f, poly_mont, d * 32, hipMemcpyHostToDevice, st));
+    if (eval_form) { rc = ntt_run(ctx, f, d, true, st, &ctx->mp_ntt); if (rc != KZG_OK) return rc; }
+    if (plan.proofs) {
+        int32_t* P2 = ctx->mp[4].as<int32_t>();
+        int32_t *X = nullptr, *Y = nullptr;
+        rc = fk20_h(ctx, st, shat, f, F, d, l, plan.lincomb, ctx->mp[2].as<int32_t>(), ctx->mp[3].as<int32_t>(), P2, &X, &Y);
+        if (rc != KZG_OK) return rc;
+        // pi = DFT_m(h_0 .. h_{m'-1}, 0 x (m - m')): the slice is read in place (offset m' - 1, stride 2m'), the zeros are never read
+        rc = g1_fft_planes_padded(ctx, st, X + (mp - 1), M, mp, m, Y, P2);
+        if (rc != KZG_OK) return rc;
+        rc = fk20_emit(ctx, st, Y, m, ctx->mp[5].as<uint8_t>(), out_xy, out_inf);
+        if (rc != KZG_OK) return rc;
+    }
+    if (plan.values) {
+        // the evaluations of the zero-extended coefficients, then coset-major into F (free: its last reader, the linear combination, is enqueued)
+        if (n > d) KZG_HIP_TRY(ctx, hipMemsetAsync(f + 2 * d, 0, (n - d) * 32, st));
+        rc = ntt_run(ctx, f, n, false, st, &ctx->mp_ntt);
+        if (rc != KZG_OK) return rc;
+        hipLaunchKernelGGL(k_encode_gather_cosets, dim3(grid_of(n)), dim3(256), 0, st, f, (uint32_t)n, plan.log_l, plan.log_m, F);
+        KZG_HIP_TRY(ctx, hipGetLastError());
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(out_ys, F, n * 32, hipMemcpyDeviceToHost, st));
+    }
     KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
     return KZG_OK;
 }

@@ -348,6 +348,57 @@ class KZG:
             raise GenericError(_lib.status_message(rc))
         return out
 
+    def encode_cosets(self, polynomial, srs, n: int, chunk_len: int = 1, values: bool = True, proofs: bool = True):
+        """The encoder (`kzg_encode_cosets`): a polynomial of d elements (a PolynomialCoeffForm, or a PolynomialEvalForm on the d-point
+        domain), evaluated on the domain of n = r d points and cut into the m = n / chunk_len cosets of `compute_multiproofs`, each
+        with its proof.  Returns (ys, proofs): ys an (m, chunk_len, 4) array whose row k is row k of `cosets` of the n evaluations,
+        proofs an (m, 8) array of wire points (the identity as zeros); `values=False` / `proofs=False` leaves that one out (None).
+        The quotients have degree < d - chunk_len: `srs` needs d points, not n, and the FK20 table is `srs.cache_multiproof(d,
+        chunk_len)`.  With n = d the proofs are those of `compute_multiproofs`."""
+        if isinstance(polynomial, PolynomialEvalForm):
+            data, eval_form = polynomial.evaluations(), 1
+        elif isinstance(polynomial, PolynomialCoeffForm):
+            data, eval_form = polynomial.coeffs(), 0
+        else:
+            raise TypeError("encode_cosets takes a PolynomialEvalForm or a PolynomialCoeffForm")
+        d = len(polynomial)
+        n = int(n)
+        chunk_len = int(chunk_len)
+        if not values and not proofs:
+            raise GenericError("encode_cosets needs values, proofs or both")
+        if d <= 0 or (d & (d - 1)) != 0 or n <= 0 or (n & (n - 1)) != 0:
+            raise FFTError("length provided is not a power of 2")
+        if n > 1 << 24:
+            raise FFTError("Could not perform IFFT due to domain consturction error")
+        if d < 2:
+            raise GenericError("encode_cosets needs a polynomial of at least 2 elements")
+        if d > n:
+            raise GenericError("the domain is shorter than the polynomial")
+        if chunk_len <= 0 or (chunk_len & (chunk_len - 1)) != 0:
+            raise GenericError("chunk length is not a power of 2")
+        if chunk_len > d // 2:
+            raise GenericError("chunk length exceeds half the polynomial length")
+        if d > len(srs):
+            raise SrsCapacityExceeded(d, len(srs))
+        ctx = self._ctx()
+        data = _lib.as_u64(data, 4)
+        m = n // chunk_len
+        ys = np.zeros((m, chunk_len, 4), dtype=np.uint64) if values else None
+        out = np.zeros((m, 8), dtype=np.uint64) if proofs else None
+        inf = np.zeros(m, dtype=np.uint8)
+        rc = _lib.load().kzg_encode_cosets(ctx.handle, srs.handle, _lib.ptr(data), d, eval_form, n, chunk_len,
+                                           _lib.ptr(ys) if values else None, _lib.ptr(out) if proofs else None, inf.ctypes.data_as(_lib.u8p))
+        if rc == _lib.ERR_NOT_POWER_OF_TWO:
+            raise FFTError("length provided is not a power of 2")
+        if rc == _lib.ERR_DOMAIN:
+            raise FFTError("Could not perform IFFT due to domain consturction error")
+        if rc == _lib.ERR_SRS_CAPACITY_EXCEEDED:
+            raise SrsCapacityExceeded(d, len(srs))
+        ctx.check_device(rc)
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+        return ys, out
+
     def cosets(self, polynomial_eval_form, chunk_len: int = 1) -> np.ndarray:
         """The values that go with the proofs of `compute_multiproofs`: an (m, chunk_len, 4) array, m = n / chunk_len, whose row k is
         evals[k::m], the evaluations on the coset {w^(k + j m) : j < chunk_len} -- what `verifier.verify_multiproof*` takes as `ys`."""
