@@ -666,6 +666,65 @@ int32_t kzg_recover_from_cosets(kzg_ctx* ctx, const uint64_t* ys_mont, const uin
                                 size_t chunk_len, size_t degree_bound, int32_t eval_form, uint64_t* out_poly_mont,
                                 int32_t* out_consistent);
 
+/* ---- G2 on the device: SRS handle, MSM, length commitment and length proof ---------------------------------------------------------
+ * The published blob header of the protocol is (commitment in G1, length commitment in G2, length proof in G2, length): with N the
+ * order of the setup (a power of two), d <= N the claimed length (a power of two) and f_0 .. f_(d-1) the coefficients,
+ *     C = sum f_i [tau^i]_1      C2 = sum f_i [tau^i]_2      pi2 = sum f_i [tau^(N-d+i)]_2
+ * and (C, C2, pi2, d) is accepted iff e(C, G2) = e(G1, C2) and e([tau^(N-d)]_1, C2) = e(G1, pi2); the second cannot hold for
+ * deg f >= d without a power of tau beyond N - 1.  Both G2 elements are multi-scalar multiplications over G2 powers of tau and run on
+ * the GPU (csrc/g2msm.hip: bucket method, signed windows, no tables); G2 wire format as above (16 u64, identity = zeros).
+ * Every call below is synchronous, uses slot 0's workspace and stream, and returns KZG_ERR_INVALID_ARG while a kzg_*_begin on slot 0
+ * is in flight.  All argument checks run on the host before any launch, in the order written; the context stays usable after any
+ * error.  Equal inputs give equal bits, on any context. */
+typedef struct kzg_g2srs kzg_g2srs;
+/* n_points wire points -> a device-resident G2 SRS (128 B per point).  Every point is checked on the device to be on the twist or
+ * the identity: the first one that is not -> KZG_ERR_NOT_ON_CURVE with *bad_index = its position (bad_index may be NULL).  The
+ * order-r subgroup is NOT checked, as documented for kzg_verify_proof. */
+int32_t kzg_g2srs_upload(kzg_ctx* ctx, const uint64_t* g2_mont, size_t n_points, kzg_g2srs** out, uint64_t* bad_index);
+/* [tau^(first_power + i)]_2 for i < n_points and a KNOWN tau (tests, custom setups), computed on the device. */
+int32_t kzg_g2srs_generate(kzg_ctx* ctx, const uint64_t tau_mont[4], uint64_t first_power, size_t n_points, kzg_g2srs** out);
+/* points [offset, offset + n) as wire points; a range outside the handle -> KZG_ERR_INVALID_ARG */
+int32_t kzg_g2srs_download(kzg_ctx* ctx, const kzg_g2srs* srs, size_t offset, size_t n, uint64_t* out_g2_mont);
+size_t kzg_g2srs_len(const kzg_g2srs* srs);
+void kzg_g2srs_free(kzg_g2srs* srs);
+/* sum_i scalars[i] bases[i] in G2 (`G2Projective::msm` + into_affine).  n_bases != n_scalars -> KZG_ERR_MSM_LENGTH_MISMATCH; a base
+ * off the twist -> KZG_ERR_NOT_ON_CURVE.  n = 0 gives the identity.  out_is_infinity may be NULL. */
+int32_t kzg_msm_g2(kzg_ctx* ctx, const uint64_t* bases_g2_mont, size_t n_bases, const uint64_t* scalars_mont, size_t n_scalars,
+                   uint64_t out_g2_mont[16], uint8_t* out_is_infinity);
+/* the same over srs[offset .. offset + n): offset + n > kzg_g2srs_len -> KZG_ERR_POLY_LENGTH.  _device: scalars already on the device. */
+int32_t kzg_msm_g2_srs(kzg_ctx* ctx, const kzg_g2srs* srs, size_t offset, const uint64_t* scalars_mont, size_t n,
+                       uint64_t out_g2_mont[16], uint8_t* out_is_infinity);
+int32_t kzg_msm_g2_srs_device(kzg_ctx* ctx, const kzg_g2srs* srs, size_t offset, const void* d_scalars_mont, size_t n,
+                              uint64_t out_g2_mont[16], uint8_t* out_is_infinity);
+/* sum f_i [tau^i]_2 from n coefficients: n > kzg_g2srs_len -> KZG_ERR_POLY_LENGTH. */
+int32_t kzg_commit_g2_coeff_form(kzg_ctx* ctx, const kzg_g2srs* srs, const uint64_t* coeffs_mont, size_t n,
+                                 uint64_t out_g2_mont[16], uint8_t* out_is_infinity);
+/* the same from n evaluations on the n-point domain: inverse Fr NTT on the device, then the MSM.  n not a power of two ->
+ * KZG_ERR_NOT_POWER_OF_TWO; n > kzg_g2srs_len -> KZG_ERR_SRS_CAPACITY_EXCEEDED (as kzg_commit_eval_form). */
+int32_t kzg_commit_g2_eval_form(kzg_ctx* ctx, const kzg_g2srs* srs, const uint64_t* evals_mont, size_t n,
+                                uint64_t out_g2_mont[16], uint8_t* out_is_infinity);
+/* The blob header of n coefficients with claimed length claimed_len over a setup of order srs_order: one scalar upload, the G1
+ * commitment over g1_srs, and the two G2 MSMs over ONE digit pass and sort (bit for bit what kzg_commit_coeff_form,
+ * kzg_commit_g2_coeff_form and kzg_msm_g2_srs return one by one).  g2_trailing holds [tau^(trailing_first_power + i)]_2; the proof is
+ * the MSM over its points from offset srs_order - claimed_len - trailing_first_power.  Errors, in order: 1. a null pointer ->
+ * KZG_ERR_INVALID_ARG; 2. srs_order or claimed_len not a power of two -> KZG_ERR_NOT_POWER_OF_TWO; 3. n > claimed_len or claimed_len >
+ * srs_order -> KZG_ERR_INVALID_ARG; 4. that window not inside g2_trailing (srs_order - claimed_len < trailing_first_power, or its end
+ * beyond the handle) -> KZG_ERR_SRS_CAPACITY_EXCEEDED; 5. n larger than g1_srs or g2_srs -> KZG_ERR_POLY_LENGTH. */
+int32_t kzg_commit_with_length_proof(kzg_ctx* ctx, const kzg_srs* g1_srs, const kzg_g2srs* g2_srs, const kzg_g2srs* g2_trailing,
+                                     uint64_t trailing_first_power, uint64_t srs_order, const uint64_t* coeffs_mont, size_t n,
+                                     uint64_t claimed_len, uint64_t out_commitment_xy[8], uint64_t out_length_commitment[16],
+                                     uint64_t out_length_proof[16]);
+/* The two pairing checks above, g1_tau_shift_xy = [tau^(N-d)]_1.  Host only: two calls of the pairing check, no random weight.  A
+ * failed check is *out_ok = 0 with KZG_OK.  A G1 input off the curve -> KZG_ERR_G1_NOT_ON_CURVE; a G2 input off the twist ->
+ * KZG_ERR_G2_TAU_NOT_ON_CURVE.  The subgroup of the G2 inputs is not checked (see kzg_verify_proof). */
+int32_t kzg_verify_length_proof(const uint64_t commitment_xy[8], const uint64_t length_commitment[16], const uint64_t length_proof[16],
+                                const uint64_t g1_tau_shift_xy[8], int32_t* out_ok);
+/* n_points gnark-compressed G2 points (64 bytes each: X.A1 || X.A0 big-endian, top two bits of the first byte 0b10 = the smaller y,
+ * 0b11 = the larger; the format of the reference's g2.point.powerOf2) -> wire points, on the library's host thread pool.  Flag bits
+ * not 0b10 / 0b11 or a coordinate not below the modulus -> KZG_ERR_DESERIALIZE; no point of that x on the twist, a point outside the
+ * order-r subgroup, or the generator itself -> KZG_ERR_NOT_ON_CURVE; *bad_index = the first such point (may be NULL).  Host only. */
+int32_t kzg_g2_decompress_be(const uint8_t* bytes, size_t n_points, uint64_t* out_g2_mont, uint64_t* bad_index);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,19 @@ PROTOTYPES = {
     "kzg_verify_multiproof_batch": (i32, [vp, vp, u64p, sz, u64p, u64p, u64p, u64p, sz, sz, sz, u64p, u64p, C.POINTER(i32)]),
     "kzg_verify_multiproof": (i32, [vp, vp, u64p, u64p, C.c_uint64, u64p, sz, sz, u64p, C.POINTER(i32)]),
     "kzg_recover_from_cosets": (i32, [vp, u64p, u64p, sz, sz, sz, sz, i32, u64p, C.POINTER(i32)]),
+    "kzg_g2srs_upload": (i32, [vp, u64p, sz, C.POINTER(vp), C.POINTER(C.c_uint64)]),
+    "kzg_g2srs_generate": (i32, [vp, u64p, C.c_uint64, sz, C.POINTER(vp)]),
+    "kzg_g2srs_download": (i32, [vp, vp, sz, sz, u64p]),
+    "kzg_g2srs_len": (sz, [vp]),
+    "kzg_g2srs_free": (None, [vp]),
+    "kzg_msm_g2": (i32, [vp, u64p, sz, u64p, sz, u64p, u8p]),
+    "kzg_msm_g2_srs": (i32, [vp, vp, sz, u64p, sz, u64p, u8p]),
+    "kzg_msm_g2_srs_device": (i32, [vp, vp, sz, vp, sz, u64p, u8p]),
+    "kzg_commit_g2_coeff_form": (i32, [vp, vp, u64p, sz, u64p, u8p]),
+    "kzg_commit_g2_eval_form": (i32, [vp, vp, u64p, sz, u64p, u8p]),
+    "kzg_commit_with_length_proof": (i32, [vp, vp, vp, vp, C.c_uint64, C.c_uint64, u64p, sz, C.c_uint64, u64p, u64p, u64p]),
+    "kzg_verify_length_proof": (i32, [u64p, u64p, u64p, u64p, C.POINTER(i32)]),
+    "kzg_g2_decompress_be": (i32, [u8p, sz, u64p, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

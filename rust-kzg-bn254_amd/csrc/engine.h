@@ -170,6 +170,13 @@ struct kzg_srs {
     std::map<std::pair<size_t, size_t>, uint4*> multiproof;
 };
 
+// A device-resident G2 SRS: n affine points on the twist in the device format of curve_g2.h, 128 B per point, no tables
+struct kzg_g2srs {
+    kzg_ctx* ctx = nullptr;
+    uint4* d_points = nullptr;
+    size_t n = 0;
+};
+
 namespace kzg {
 
 // Bases of one MSM: `points` = first base of the slice; the shape (msm_plan.h) selects the mode.
@@ -224,6 +231,10 @@ int32_t msm_slot_stream(kzg_ctx* ctx, int slot, hipStream_t* out);
 int32_t msm_begin(kzg_ctx* ctx, int slot, const MsmBases& bases, const void* d_scalars, size_t n);
 int32_t msm_end(kzg_ctx* ctx, int slot, uint64_t out_xy[8], uint8_t* out_inf, uint64_t* out_xyzz);
 void msm_drop_slots(kzg_ctx* ctx);
+// the pieces of the G1 driver the G2 driver (g2msm.hip) runs on: the pinned result buffer of a workspace, and the digits + counting sort of
+// one generic-mode scalar set (p: make_plan without tables, batch 1), which leave ws.sorted / ws.offs
+int32_t msm_pinned_out(kzg_ctx* ctx, MsmWorkspace& ws);
+int32_t msm_sort_generic(kzg_ctx* ctx, MsmWorkspace& ws, hipStream_t st, const uint4* d_scalars, const Plan& p);
 int32_t msm_run_batch(kzg_ctx* ctx, const uint4* d_points, const void* d_scalars, size_t n, uint32_t batch,
                       uint64_t* out_xy, uint8_t* out_inf);
 
@@ -255,6 +266,16 @@ int32_t ntt_run(kzg_ctx* ctx, void* d_data, size_t n, bool inverse, hipStream_t 
 // synthetic SRS P_i = tau^i * G1 written to d_points (device format); device SRS -> wire on the host
 int32_t srs_generate(kzg_ctx* ctx, const uint64_t tau_mont[4], uint64_t first_power, size_t n, uint4* d_points);
 int32_t srs_download(kzg_ctx* ctx, const uint4* d_points, size_t n, uint64_t* out_xy);
+int32_t fr_powers_canonical(kzg_ctx* ctx, const uint64_t tau_mont[4], uint64_t first_power, size_t n, const uint4** d_out);
+
+// G2 (g2msm.hip).  Called under ctx->mu with the device set; every one is synchronised on return.
+// the MSM of ONE scalar set (device, wire form) over nb <= 2 base sets (device format, 8 uint4 per point): digits and sort once, accumulate and
+// reduce per set; out: nb x 16 u64 affine wire points, out_inf: nb flags (may be null)
+int32_t g2_msm_run(kzg_ctx* ctx, const uint4* const* d_points, uint32_t nb, const void* d_scalars, size_t n, uint64_t* out_g2, uint8_t* out_inf);
+// n wire points of the host -> device format at d_out, every point checked on the twist (or the identity); *bad = index of the first one off it, or -1
+int32_t g2_upload_points(kzg_ctx* ctx, const uint64_t* g2_mont, size_t n, uint4* d_out, int64_t* bad);
+int32_t g2_generate_points(kzg_ctx* ctx, const uint64_t tau_mont[4], uint64_t first_power, size_t n, uint4* d_out);
+int32_t g2_download_points(kzg_ctx* ctx, const uint4* d_points, size_t n, uint64_t* out_g2_mont);
 int32_t srs_decompress(kzg_ctx* ctx, const uint8_t* bytes, size_t n, uint4* d_points, uint32_t* err_kind, uint32_t* err_index, bool ark_le = false);
 
 // KZG::g1_ifft: Lagrange-basis SRS of size n (n a power of two <= srs->n), affine wire points to the host / left on the device

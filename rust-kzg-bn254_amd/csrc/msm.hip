@@ -329,6 +329,32 @@ static PlanContext plan_context(const kzg_ctx* ctx) {
     return pc;
 }
 
+static DeviceBuffer* ws_buffer(MsmWorkspace& ws, int which) {
+    DeviceBuffer* const buffers[WS_BUFFERS] = {&ws.digits, &ws.sorted, &ws.count, &ws.sort_tmp, &ws.sort_key, &ws.sort_small, &ws.blockbase, &ws.offs, &ws.block_sums,
+                                               &ws.head, &ws.cont, &ws.bucket, &ws.chunkS, &ws.chunkTmp, &ws.chunkA};      // (the order of WsBuffer)
+    return buffers[which];
+}
+// the workspace's pinned result buffer (MSM_MAX_OUT G1 XYZZ values + the entry counts of profiled launches), allocated on first use
+int32_t msm_pinned_out(kzg_ctx* ctx, MsmWorkspace& ws) {
+    if (ws.pinned_out) return KZG_OK;
+    KZG_HIP_TRY(ctx, hipHostMalloc(&ws.pinned_out, (size_t)MSM_MAX_OUT * 32 * 4 + MSM_MAX_PARTS * 4, hipHostMallocDefault));
+    KZG_HIP_TRY(ctx, hipHostGetDevicePointer(&ws.pinned_out_dev, ws.pinned_out, 0));
+    return KZG_OK;
+}
+// Digits and counting sort of ONE generic-mode scalar set on `st` for the G2 driver (g2msm.hip), whose kernels add points of another
+// type: ws.sorted and ws.offs as enqueue_sort leaves them (entries index | sign << 31 grouped by bucket, p.G + 1 offsets).  p: a plan
+// of make_plan without tables and with batch 1; only the buffers of the sort are reserved.
+int32_t msm_sort_generic(kzg_ctx* ctx, MsmWorkspace& ws, hipStream_t st, const uint4* d_scalars, const Plan& p) {
+    if (p.tables || p.batch != 1 || p.bitsum) return KZG_ERR_INVALID_ARG;
+    for (int i : {WS_DIGITS, WS_SORTED, WS_COUNT, WS_BLOCKBASE, WS_OFFS, WS_BLOCK_SUMS}) KZG_HIP_TRY(ctx, ws_buffer(ws, i)->reserve(p.bytes[i]));
+    const MsmBases none;
+    const Launch L{ctx, ws, st, none, d_scalars, p, nullptr, false};
+    const int32_t rc = enqueue_sort(L, nullptr);
+    if (rc != KZG_OK) return rc;
+    KZG_HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+
 // Enqueue every kernel of one MSM (or batch) on `st`, using `ws`: plan, validate, reserve, sort, accumulate, reduce.
 static int32_t msm_enqueue(kzg_ctx* ctx, MsmWorkspace& ws, hipStream_t st, const MsmBases& bases, const uint4* d_scalars, size_t n,
                            uint32_t batch, Pending* pend, uint32_t out_off = 0, uint32_t out_cap = MSM_MAX_OUT, uint32_t polys = 0,
@@ -340,13 +366,8 @@ static int32_t msm_enqueue(kzg_ctx* ctx, MsmWorkspace& ws, hipStream_t st, const
         if (error) ctx->last_error = error;
         if (rc != KZG_OK) return rc;
     }
-    DeviceBuffer* const buffers[WS_BUFFERS] = {&ws.digits, &ws.sorted, &ws.count, &ws.sort_tmp, &ws.sort_key, &ws.sort_small, &ws.blockbase, &ws.offs, &ws.block_sums,
-                                               &ws.head, &ws.cont, &ws.bucket, &ws.chunkS, &ws.chunkTmp, &ws.chunkA};      // (the order of WsBuffer)
-    for (int i = 0; i < WS_BUFFERS; ++i) KZG_HIP_TRY(ctx, buffers[i]->reserve(p.bytes[i]));
-    if (!ws.pinned_out) {
-        KZG_HIP_TRY(ctx, hipHostMalloc(&ws.pinned_out, (size_t)MSM_MAX_OUT * 32 * 4 + MSM_MAX_PARTS * 4, hipHostMallocDefault));   // + entry counts of profiled launches
-        KZG_HIP_TRY(ctx, hipHostGetDevicePointer(&ws.pinned_out_dev, ws.pinned_out, 0));
-    }
+    for (int i = 0; i < WS_BUFFERS; ++i) KZG_HIP_TRY(ctx, ws_buffer(ws, i)->reserve(p.bytes[i]));
+    { const int32_t rc = msm_pinned_out(ctx, ws); if (rc != KZG_OK) return rc; }
     // The last kernel of the sequence stores the O(200) result points straight into the pinned host buffer (coherent host memory, read
     // after the event behind that kernel).  A device-to-host copy of them cost ~10 us per MSM -- and above ~16 KiB (208 points at 2^16
     // buckets: every batched launch) hipMemcpyAsync takes the SDMA path, whose set-up after a device-wide synchronisation blocked the

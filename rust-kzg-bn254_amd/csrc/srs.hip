@@ -329,8 +329,9 @@ k_srs_count_identity(const uint4* __restrict__ in, size_t n, uint32_t* __restric
     if (any == 0) atomicAdd(count, 1u);
 }
 
-int32_t srs_generate(kzg_ctx* ctx, const uint64_t tau[4], uint64_t first_power, size_t n, uint4* d_points) {
-    if (n == 0) return KZG_OK;
+// tau^(first_power + i) for i < n as canonical integers (8 u32 each) in the polynomial scratch of slot 0, enqueued on ctx->stream: the
+// scalars of the synthetic G1 SRS below and of the G2 one (g2msm.hip)
+int32_t fr_powers_canonical(kzg_ctx* ctx, const uint64_t tau[4], uint64_t first_power, size_t n, const uint4** d_out) {
     KZG_HIP_TRY(ctx, ctx->poly[0].a.reserve(n * 32 + 64));
     KZG_HIP_TRY(ctx, ctx->poly[0].small.reserve(4096));
     uint4* d_tau = ctx->poly[0].small.as<uint4>();
@@ -338,6 +339,14 @@ int32_t srs_generate(kzg_ctx* ctx, const uint64_t tau[4], uint64_t first_power, 
     const uint32_t per = 64;
     uint32_t lanes = (uint32_t)((n + per - 1) / per);
     hipLaunchKernelGGL(k_fr_powers, dim3((lanes + 255) / 256), dim3(256), 0, ctx->stream, d_tau, ctx->poly[0].a.as<uint4>(), first_power, (uint32_t)n, per);
+    *d_out = ctx->poly[0].a.as<uint4>();
+    return KZG_OK;
+}
+
+int32_t srs_generate(kzg_ctx* ctx, const uint64_t tau[4], uint64_t first_power, size_t n, uint4* d_points) {
+    if (n == 0) return KZG_OK;
+    const uint4* d_powers = nullptr;
+    { const int32_t rc = fr_powers_canonical(ctx, tau, first_power, n, &d_powers); if (rc != KZG_OK) return rc; }
     hipLaunchKernelGGL(k_srs_powers, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->poly[0].a.as<uint4>(), d_points, (uint32_t)n);
     KZG_HIP_TRY(ctx, hipGetLastError());
     KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

@@ -196,6 +196,26 @@ def g1_lincomb(points, scalars, ctx=None) -> np.ndarray:
     return out
 
 
+def msm_g2(points, scalars, ctx=None) -> np.ndarray:
+    """`G2Projective::msm` + into_affine over caller bases on the GPU (`kzg_msm_g2`): points (n, 16) wire G2, scalars (n, 4); returns the
+    (16,) wire point (zeros = the identity).  Every base is checked on the twist on the device."""
+    ctx = ctx or _lib.default_context()
+    pts = _lib.as_u64(points, 16)
+    sc = _lib.as_u64(scalars, 4)
+    out = np.zeros(16, dtype=np.uint64)
+    inf = C.c_uint8(0)
+    rc = _lib.load().kzg_msm_g2(ctx.handle, _lib.ptr(pts) if len(pts) else None, len(pts), _lib.ptr(sc) if len(sc) else None, len(sc),
+                                _lib.ptr(out), C.byref(inf))
+    if rc == _lib.ERR_MSM_LENGTH_MISMATCH:
+        raise MsmError(str(min(len(pts), len(sc))))
+    if rc == _lib.ERR_NOT_ON_CURVE:
+        raise NotOnCurveError("G2 point not on curve")
+    ctx.check_device(rc)
+    if rc != _lib.OK:
+        raise GenericError(_lib.status_message(rc))
+    return out
+
+
 def g1_lincomb_batch(points_list, scalars_list, ctx=None):
     """Several `g1_lincomb` calls of equal length in one kernel sequence (`kzg_msm_g1_batch`), e.g. the three MSMs of
     verifier/src/batch.rs:228,245,246.  Returns a list of affine wire points."""

@@ -76,6 +76,58 @@ class KZG:
             raise GenericError(_lib.status_message(rc))
         return out
 
+    # ---- G2: the length commitment and the length proof of the protocol's blob header (G2SRS; csrc/g2msm.hip) ------------------
+    def commit_g2_coeff_form(self, polynomial: PolynomialCoeffForm, g2_srs):
+        """sum f_i [tau^i]_2 (`kzg_commit_g2_coeff_form`): a (16,) wire G2 point."""
+        if len(polynomial) > len(g2_srs):
+            raise SerializationError("polynomial length is not correct")
+        ctx = self._ctx()
+        coeffs = _lib.as_u64(polynomial.coeffs(), 4)
+        out = np.zeros(16, dtype=np.uint64); inf = C.c_uint8(0)
+        rc = _lib.load().kzg_commit_g2_coeff_form(ctx.handle, g2_srs.handle, _lib.ptr(coeffs), len(coeffs), _lib.ptr(out), C.byref(inf))
+        ctx.check_device(rc)
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+        return out
+
+    def commit_g2_eval_form(self, polynomial: PolynomialEvalForm, g2_srs):
+        """The same from evaluations: inverse NTT on the device, then the G2 MSM (`kzg_commit_g2_eval_form`)."""
+        if len(polynomial) > len(g2_srs):
+            raise SrsCapacityExceeded(len(polynomial), len(g2_srs))
+        ctx = self._ctx()
+        evals = _lib.as_u64(polynomial.evaluations(), 4)
+        out = np.zeros(16, dtype=np.uint64); inf = C.c_uint8(0)
+        rc = _lib.load().kzg_commit_g2_eval_form(ctx.handle, g2_srs.handle, _lib.ptr(evals), len(evals), _lib.ptr(out), C.byref(inf))
+        if rc == _lib.ERR_NOT_POWER_OF_TWO:
+            raise FFTError("length provided is not a power of 2")
+        if rc == _lib.ERR_DOMAIN:
+            raise FFTError("Could not perform IFFT due to domain consturction error")
+        ctx.check_device(rc)
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+        return out
+
+    def commit_with_length_proof(self, polynomial: PolynomialCoeffForm, srs, g2_srs, g2_trailing, srs_order: int, claimed_len: int):
+        """The blob header (`kzg_commit_with_length_proof`): (commitment (8,), length commitment (16,), length proof (16,)) of the
+        coefficients for the claimed length d = claimed_len over a setup of order srs_order; g2_trailing holds
+        [tau^(g2_trailing.first_power + i)]_2 and must cover the powers srs_order - d .. srs_order - 1.  One scalar upload, the G1
+        commitment, and both G2 MSMs over one sort."""
+        ctx = self._ctx()
+        coeffs = _lib.as_u64(polynomial.coeffs(), 4)
+        c = np.zeros(8, dtype=np.uint64); c2 = np.zeros(16, dtype=np.uint64); pi2 = np.zeros(16, dtype=np.uint64)
+        rc = _lib.load().kzg_commit_with_length_proof(ctx.handle, srs.handle, g2_srs.handle, g2_trailing.handle, g2_trailing.first_power, srs_order,
+                                                      _lib.ptr(coeffs), len(coeffs), claimed_len, _lib.ptr(c), _lib.ptr(c2), _lib.ptr(pi2))
+        if rc == _lib.ERR_NOT_POWER_OF_TWO:
+            raise FFTError("length provided is not a power of 2")
+        if rc == _lib.ERR_SRS_CAPACITY_EXCEEDED:
+            raise SrsCapacityExceeded(int(claimed_len), len(g2_trailing))
+        if rc == _lib.ERR_POLY_LENGTH:
+            raise SerializationError("polynomial length is not correct")
+        ctx.check_device(rc)
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+        return c, c2, pi2
+
     # ---- batched commitments: many polynomials of one length against one SRS in one kernel sequence (no counterpart in the
     # reference, which commits one polynomial per call; same values as that many calls) -----------------------------------------
     def _commit_batch(self, rows, srs, eval_form):

@@ -43,6 +43,18 @@ def verify_proof(commitment, proof, value_fr, z_fr, g2_tau=None) -> bool:
     return bool(ok.value)
 
 
+def verify_length_proof(commitment, length_commitment, length_proof, g1_tau_shift) -> bool:
+    """The blob header's two pairing checks (`kzg_verify_length_proof`, host): e(C, G2) = e(G1, C2) and e([tau^(N-d)]_1, C2) = e(G1, pi2)
+    with g1_tau_shift = [tau^(N-d)]_1 for the claimed length d over a setup of order N.  False = a check failed."""
+    ok = _lib.i32(0)
+    rc = _lib.load().kzg_verify_length_proof(_lib.ptr(_lib.as_u64(commitment, 0).reshape(8)), _lib.ptr(_lib.as_u64(length_commitment, 0).reshape(16)),
+                                             _lib.ptr(_lib.as_u64(length_proof, 0).reshape(16)), _lib.ptr(_lib.as_u64(g1_tau_shift, 0).reshape(8)), C.byref(ok))
+    if rc == _lib.ERR_G2_TAU_NOT_ON_CURVE:
+        raise NotOnCurveError("G2 point not on curve")
+    _raise_for(rc)
+    return bool(ok.value)
+
+
 def verify_blob_kzg_proof(blob, commitment, proof, g2_tau=None, ctx=None) -> bool:
     """verify.rs:76-98 as ONE call of the C-ABI (`kzg_verify_blob_kzg_proof`)."""
     ctx = ctx or _lib.default_context()
