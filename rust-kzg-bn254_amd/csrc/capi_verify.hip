@@ -102,12 +102,10 @@ int32_t verify_batch_core(kzg_ctx* ctx, const uint64_t* commitments_xy_mont, con
 
 // ---- batch verification end to end (verifier/src/batch.rs:16-69, :76-168; primitives/src/helpers.rs:613-662) ---------------------
 constexpr size_t VB_GROUP_BYTES = (size_t)256 << 20;           // packed blob bytes per GPU round
-constexpr uint32_t VB_BATCH_MAX_LOG = 12;                      // = VB_MAX_LOG of poly.hip: larger blobs take the single-polynomial path
-struct VbMeta { uint64_t off; uint32_t len; uint32_t log_n; }; // = VbBlob of poly.hip
 
 // The data-parallel front end of verify_blob_kzg_proof_batch: z_i = compute_challenge(blob_i, C_i), y_i = p_i(z_i) for all n blobs.
 // Transcripts: n independent SHA-256 streams on a pool of host threads (each also packs its blob into the pinned staging buffer);
-// evaluations: two GPU launches for all blobs of up to 4096 elements (poly.hip k_vb_prep / k_vb_eval), the single-polynomial path
+// evaluations: two GPU launches for all blobs of up to 4096 elements (vbeval.hip k_vb_prep / k_vb_eval), the single-polynomial path
 // for the rest.  `validated` = the caller has already checked every commitment (batch.rs:29-37); otherwise compute_challenge's own
 // validate_g1_point (helpers.rs:413) is reported in blob order.
 // commitments == nullptr: zs are INPUTS (kzg_evaluate_blobs_in_evaluation_form_batch), nothing is hashed.
@@ -117,7 +115,7 @@ int32_t challenges_and_evaluations(kzg_ctx* ctx, const uint8_t* const* blobs, co
     // per-blob guards in the reference's order (helpers.rs:634-645): to_polynomial_eval_form (TOO_LARGE), compute_challenge
     // (validate_g1_point), evaluate_polynomial_in_evaluation_form -> calculate_roots_of_unity (ZERO_LENGTH)
     std::vector<int32_t> status(n, KZG_OK);
-    std::vector<VbMeta> meta(n);
+    std::vector<VbBlob> meta(n);
     std::vector<size_t> group_end;                            // blob index where each GPU round ends
     // (KZG_VB_GROUP_BYTES / KZG_VB_CHUNK_BYTES: staging granularity; tests shrink them so that small batches take the multi-round / multi-chunk paths)
     const size_t group_bytes = opts().vb_group_bytes ? opts().vb_group_bytes : VB_GROUP_BYTES;
@@ -126,12 +124,12 @@ int32_t challenges_and_evaluations(kzg_ctx* ctx, const uint8_t* const* blobs, co
     for (size_t i = 0; i < n; ++i) {
         const size_t elems = (lens[i] + 31) / 32;
         if (lens[i] && !blobs[i]) return KZG_ERR_INVALID_ARG;
-        if (elems > ((size_t)1 << 28)) { status[i] = KZG_ERR_TOO_LARGE; meta[i] = VbMeta{0, 0, 99}; continue; }
+        if (elems > ((size_t)1 << 28)) { status[i] = KZG_ERR_TOO_LARGE; meta[i] = VbBlob{0, 0, 99}; continue; }
         const uint32_t lg = (uint32_t)__builtin_ctzll(kzg_host::next_pow2(elems));
-        const bool batched = lens[i] != 0 && lg <= VB_BATCH_MAX_LOG;
+        const bool batched = lens[i] != 0 && lg <= (uint32_t)VB_MAX_LOG;
         const size_t span = batched ? elems * 32 : 0;
         if (off && off + span > group_bytes) { group_end.push_back(i); off = 0; }
-        meta[i] = VbMeta{(uint64_t)off, (uint32_t)(batched ? lens[i] : 0), batched ? lg : 99u};
+        meta[i] = VbBlob{(uint64_t)off, (uint32_t)(batched ? lens[i] : 0), batched ? lg : 99u};
         off += span;
     }
     group_end.push_back(n);

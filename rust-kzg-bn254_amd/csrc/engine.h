@@ -86,6 +86,7 @@ struct LagProof {
     uint32_t m = 0;
     bool msm_started = false;      // len > 0: an MSM is pending on the slot
     bool grouped = false;          // commitment and proof leave as ONE batched launch (two scalar sets) on this slot
+    bool owns_m() const { return on_domain && m >= base && m - base < len; }   // z = w^m and this slice holds f_m
 };
 }
 #ifndef KZG_NUM_SLOTS
@@ -308,9 +309,13 @@ int32_t proof_end(kzg_ctx* ctx, int slot, uint64_t out_xy[8], uint8_t* out_inf, 
 int32_t roots_run(kzg_ctx* ctx, uint64_t* out, size_t n);
 int32_t blob_to_fr_run(kzg_ctx* ctx, const uint8_t* bytes, size_t len, size_t n_padded, void** d_out,
                        hipStream_t st = nullptr, DeviceBuffer* d_bytes = nullptr, DeviceBuffer* d_elems = nullptr);
-// the batched evaluations of batch verification (poly.hip k_vb_prep / k_vb_eval; meta_host: nb x {u64 off, u32 len, u32 log_n})
+// the batched evaluations of batch verification (vbeval.hip k_vb_prep / k_vb_eval), one workgroup per blob of up to 2^VB_MAX_LOG elements;
+// larger blobs take the single-polynomial path.  VbBlob describes a blob to the host driver and to the kernels alike.
+constexpr int VB_MAX_LOG = 12;
+struct VbBlob { uint64_t off; uint32_t len; uint32_t log_n; };          // byte offset (32-byte aligned, zero-filled to the next chunk), byte length, log2(padded elements)
+static_assert(sizeof(VbBlob) == 16, "descriptors are uploaded as they are");
 int32_t vb_evaluate_setup(kzg_ctx* ctx, size_t packed_len, size_t nb);
-int32_t vb_evaluate_enqueue(kzg_ctx* ctx, const uint8_t* packed, const void* meta_host, size_t nb, size_t b0, size_t b1, const uint64_t* zs,
+int32_t vb_evaluate_enqueue(kzg_ctx* ctx, const uint8_t* packed, const VbBlob* meta, size_t nb, size_t b0, size_t b1, const uint64_t* zs,
                             uint8_t* small_pinned);
 int32_t vb_evaluate_finish(kzg_ctx* ctx, size_t nb, uint64_t* ys_out, uint8_t* fallback_out);
 // Lagrange-sharded proofs (lagrange.hip; the host folds lag_fold_y / lag_fold_proof: host_lagrange.h)

@@ -18,6 +18,7 @@
 #include "poly_common.h"
 #include "fe_invert.h"
 #include "host_lagrange.h"
+#include "proof_plan.h"    // ProofStaging: the whole-domain proofs stage in the same pinned page of a slot
 
 #include <algorithm>
 #include <cstdlib>
@@ -32,6 +33,8 @@ constexpr uint32_t LAG_BLOCK = POLY_THREADS * LAG_PER;      // elements per work
 // ---- L1: inverses of w^(base + i) - z over the slice + the slice's part of the barycentric sum ------------------------------------
 // lane t of workgroup b owns the slice elements i = 1024 b + t + 256 k, k < 4.  inv (limb planes, stride len) receives 1 / (w^(base+i) - z),
 // and 1 for the element with w^(base+i) = z (whose slice index goes to *on_domain).  partial[b] = -sum f_i w^i inv_i = sum f_i w^i / (z - w^i).
+// The tree is written out here, not taken from poly_common.h (lds_tree_invert): through the helper the compiler scheduled this kernel
+// differently and it measured 1.2-1.8 % slower, which a streamed 2^20-element slice shows (profiles/poly_helpers.md).
 __global__ void __launch_bounds__(POLY_THREADS)
 k_lag_inverses(const uint4* __restrict__ evals, uint32_t len, uint32_t base, NttTables tb, const uint4* __restrict__ z_wire,
                int32_t* __restrict__ inv, int32_t* __restrict__ partial /* NL x gridDim */, uint32_t* __restrict__ on_domain) {
@@ -158,16 +161,7 @@ __global__ void __launch_bounds__(POLY_THREADS)
 k_lag_sum(const int32_t* __restrict__ partial, uint32_t n_partial, uint4* __restrict__ out_wire) {
     __shared__ int32_t lds[NL * POLY_THREADS];
     Fr sum;
-    fe_set_zero(sum);
-    for (uint32_t i = threadIdx.x; i < n_partial; i += POLY_THREADS) {
-        Fr v;
-        pl_load(v, partial, n_partial, i);
-        fe_add(sum, sum, v);
-        fe_norm(sum);
-        if ((i / POLY_THREADS) % 32 == 31) fe_reduce(sum);
-    }
-    fe_reduce(sum);
-    block_sum(sum, lds);
+    sum_partials(sum, partial, n_partial, lds);
     if (threadIdx.x == 0) wire_store(out_wire, 0, sum);
 }
 
@@ -212,10 +206,39 @@ k_lag_quotient(const uint4* __restrict__ evals, uint32_t len, uint32_t base, Ntt
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
 namespace {
-// pinned layout of a slot's PolySet for this path: [0,32) z | [32,64) y | [64,96) S readback | [96,128) f_m readback | [128,160) T readback
-// device `small`:  [0,32) z | [32,64) y | [64,68) on-domain slice index | [128,160) S | [160,192) T | [4096, ..) per-workgroup partials
-constexpr size_t LAG_SMALL_PARTIALS = 4096;
+// Staging of one slice proof in a slot's PolySet: the pinned page (host) and `small` (device).  Scalars are 32-byte wire elements.
+struct LagStaging {
+    static constexpr size_t PIN_Z = 0, PIN_Y = 32;          // pinned: z and y, uploaded to Z, Y
+    static constexpr size_t PIN_S = 64;                     // pinned: read-back of S, the slice's part of the barycentric sum, ...
+    static constexpr size_t PIN_FM = 96;                    // ... of f_m (the owner of m only) ...
+    static constexpr size_t PIN_T = 128;                    // ... and of T = sum q_i w^i (z on the domain)
+    static constexpr size_t PIN_INDEX = 160;                // pinned: NO_INDEX going up, the slice index the kernel found coming back (4 bytes)
+    static constexpr size_t PINNED_BYTES = 4096;
+    static constexpr size_t Z = 0, Y = 32;                  // small: z, y
+    static constexpr size_t INDEX = 64;                     // small: slice index of the element with w^i = z (4 bytes)
+    static constexpr size_t S = 128, T = 160;               // small: the two sums of k_lag_sum
+    static constexpr size_t PARTIALS = 4096;                // small: per-workgroup partial sums, NL planes
+    static constexpr size_t small_bytes(uint32_t blocks) { return PARTIALS + (size_t)blocks * NL * 4 + 64; }
+};
+static_assert(LagStaging::PIN_Y == LagStaging::PIN_Z + 32 && LagStaging::Y == LagStaging::Z + 32, "z | y go up as one block");
+static_assert(LagStaging::PIN_S == LagStaging::PIN_Y + 32 && LagStaging::PIN_FM == LagStaging::PIN_S + 32 && LagStaging::PIN_T == LagStaging::PIN_FM + 32 &&
+              LagStaging::PIN_INDEX == LagStaging::PIN_T + 32, "S | f_m are handed out as one block; S | f_m | T are cleared as one");
+static_assert(LagStaging::PIN_INDEX + 4 <= LagStaging::PINNED_BYTES && LagStaging::PINNED_BYTES == ProofStaging::PINNED_BYTES,
+              "the fields fit the page, which either proof path may have allocated");
+static_assert(LagStaging::Y + 32 <= LagStaging::INDEX && LagStaging::INDEX + 4 <= LagStaging::S && LagStaging::S + 32 <= LagStaging::T &&
+              LagStaging::T + 32 <= LagStaging::PARTIALS, "the fields of small do not overlap");
+
+// the slot's device buffers for a slice of len elements in `blocks` workgroups
+hipError_t lag_reserve(PolySet& set, size_t len, uint32_t blocks) {
+    hipError_t e = set.a.reserve(len * 32 + 32);
+    if (e == hipSuccess) e = set.b.reserve(len * NL * 4 + 64);
+    if (e == hipSuccess) e = set.c.reserve(len * 32 + 32);
+    if (e == hipSuccess) e = set.small.reserve(LagStaging::small_bytes(blocks));
+    return e;
+}
 }  // namespace
+// every host function below has a `fail` that gives up what it has in flight
+#define LAG_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return fail(_e, #expr); } while (0)
 
 // The context's AUXILIARY stream (high priority, created on first use; engine.h ctx_aux_stream): short latency-bound kernel sequences that other
 // work waits for.  Phase 1 of every Lagrange-sharded proof of a context (upload, inverses, partial sum: ~0.1 ms on few waves) runs here, and so
@@ -255,7 +278,7 @@ int32_t lag_begin(kzg_ctx* ctx, const kzg_srs* shard, size_t base, const void* e
     if (rc != KZG_OK) return rc;
     const int log_n = ilog2_ceil(n);
     PolySet& set = ctx->poly[slot];
-    if (!set.pinned) KZG_HIP_TRY(ctx, hipHostMalloc(&set.pinned, 4096, hipHostMallocDefault));
+    if (!set.pinned) KZG_HIP_TRY(ctx, hipHostMalloc(&set.pinned, LagStaging::PINNED_BYTES, hipHostMallocDefault));
     uint8_t* pin = static_cast<uint8_t*>(set.pinned);
     // z on the domain?  z^n == 1; then m with w^m = z (one bit per step, ~log^2 n / 2 host products)
     uint64_t zn[4];
@@ -266,8 +289,8 @@ int32_t lag_begin(kzg_ctx* ctx, const kzg_srs* shard, size_t base, const void* e
     lp.grouped = grouped;
     lp.on_domain = h_is_one(zn);
     if (lp.on_domain && !kzg_host::fr_domain_index(z, log_n, &lp.m)) { ctx->last_error = "z^n = 1 but z is no power of the domain generator"; return KZG_ERR_ROOT_NOT_FOUND; }
-    memcpy(pin, z, 32);
-    memset(pin + 64, 0, 96);
+    memcpy(pin + LagStaging::PIN_Z, z, 32);
+    memset(pin + LagStaging::PIN_S, 0, LagStaging::PIN_INDEX - LagStaging::PIN_S);                        // S | f_m | T
     if (len == 0) { lp.phase = 1; return KZG_OK; }             // an empty slice contributes zero sums and the identity (no commitment MSM is enqueued either)
     NttTables tb;
     rc = ntt_get_tables(ctx, log_n, false, &tb);
@@ -282,26 +305,22 @@ int32_t lag_begin(kzg_ctx* ctx, const kzg_srs* shard, size_t base, const void* e
         if (commit_started) { uint64_t sink[16]; (void)msm_end(ctx, commit_slot, nullptr, nullptr, sink); }
         return set_error(ctx, e, where);
     };
-#define LAG_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return fail(_e, #expr); } while (0)
-    LAG_TRY(set.a.reserve(len * 32 + 32));
-    LAG_TRY(set.b.reserve(len * NL * 4 + 64));
-    LAG_TRY(set.c.reserve(len * 32 + 32));
-    LAG_TRY(set.small.reserve(LAG_SMALL_PARTIALS + (size_t)blocks * NL * 4 + 64));
+    LAG_TRY(lag_reserve(set, len, blocks));
     uint8_t* small = set.small.as<uint8_t>();
     const uint32_t no_index = NO_INDEX;
     rc = ctx_aux_stream(ctx, st, &s1);
     if (rc != KZG_OK) { lp = LagProof(); return rc; }
     if (!ctx->lag_phase1[slot]) LAG_TRY(hipEventCreateWithFlags(&ctx->lag_phase1[slot], hipEventDisableTiming));
-    memcpy(pin + 160, &no_index, 4);
-    LAG_TRY(hipMemcpyAsync(small, pin, 32, hipMemcpyHostToDevice, s1));
-    LAG_TRY(hipMemcpyAsync(small + 64, pin + 160, 4, hipMemcpyHostToDevice, s1));
+    memcpy(pin + LagStaging::PIN_INDEX, &no_index, 4);
+    LAG_TRY(hipMemcpyAsync(small + LagStaging::Z, pin + LagStaging::PIN_Z, 32, hipMemcpyHostToDevice, s1));
+    LAG_TRY(hipMemcpyAsync(small + LagStaging::INDEX, pin + LagStaging::PIN_INDEX, 4, hipMemcpyHostToDevice, s1));
     // Evaluations in HOST memory: the inverses need z only, so they are enqueued FIRST (auxiliary stream) and run while this thread sits in the pageable upload
     // (the slot's stream); the sum waits for both.  Per-rank proof of a 2^17-element slice, one call at a time: 0.63 -> 0.56 ms.
     const bool split = !on_device && s1 != st;
     if (split) {
         hipLaunchKernelGGL(k_lag_inverses, dim3(blocks), dim3(POLY_THREADS), 0, s1, static_cast<const uint4*>(nullptr), (uint32_t)len, (uint32_t)base, tb,
-                           reinterpret_cast<const uint4*>(small), set.b.as<int32_t>(), reinterpret_cast<int32_t*>(small + LAG_SMALL_PARTIALS),
-                           reinterpret_cast<uint32_t*>(small + 64));
+                           reinterpret_cast<const uint4*>(small + LagStaging::Z), set.b.as<int32_t>(), reinterpret_cast<int32_t*>(small + LagStaging::PARTIALS),
+                           reinterpret_cast<uint32_t*>(small + LagStaging::INDEX));
         LAG_TRY(hipGetLastError());
         if (!ctx->lag_uploaded[slot]) LAG_TRY(hipEventCreateWithFlags(&ctx->lag_uploaded[slot], hipEventDisableTiming));
         LAG_TRY(hipMemcpyAsync(set.a.p, evals, len * 32, hipMemcpyHostToDevice, st));
@@ -327,18 +346,16 @@ int32_t lag_begin(kzg_ctx* ctx, const kzg_srs* shard, size_t base, const void* e
         commit_started = true;
     }
     if (split)
-        hipLaunchKernelGGL(k_lag_bary, dim3(blocks), dim3(POLY_THREADS), 0, s1, d_ev, (uint32_t)len, (uint32_t)base, tb, set.b.as<int32_t>(),
-                           reinterpret_cast<int32_t*>(small + LAG_SMALL_PARTIALS));
+        hipLaunchKernelGGL(k_lag_bary, dim3(blocks), dim3(POLY_THREADS), 0, s1, d_ev, (uint32_t)len, (uint32_t)base, tb, set.b.as<int32_t>(), reinterpret_cast<int32_t*>(small + LagStaging::PARTIALS));
     else
         hipLaunchKernelGGL(k_lag_inverses, dim3(blocks), dim3(POLY_THREADS), 0, s1, d_ev, (uint32_t)len, (uint32_t)base, tb,
-                           reinterpret_cast<const uint4*>(small), set.b.as<int32_t>(), reinterpret_cast<int32_t*>(small + LAG_SMALL_PARTIALS),
-                           reinterpret_cast<uint32_t*>(small + 64));
-    hipLaunchKernelGGL(k_lag_sum, dim3(1), dim3(POLY_THREADS), 0, s1, reinterpret_cast<const int32_t*>(small + LAG_SMALL_PARTIALS), blocks,
-                       reinterpret_cast<uint4*>(small + 128));
+                           reinterpret_cast<const uint4*>(small + LagStaging::Z), set.b.as<int32_t>(), reinterpret_cast<int32_t*>(small + LagStaging::PARTIALS),
+                           reinterpret_cast<uint32_t*>(small + LagStaging::INDEX));
+    hipLaunchKernelGGL(k_lag_sum, dim3(1), dim3(POLY_THREADS), 0, s1, reinterpret_cast<int32_t*>(small + LagStaging::PARTIALS), blocks, reinterpret_cast<uint4*>(small + LagStaging::S));
     LAG_TRY(hipGetLastError());
-    LAG_TRY(hipMemcpyAsync(pin + 64, small + 128, 32, hipMemcpyDeviceToHost, s1));
-    if (lp.on_domain && lp.m >= base && lp.m - base < len)     // this slice owns f_m = y (helpers.rs:497-504)
-        LAG_TRY(hipMemcpyAsync(pin + 96, reinterpret_cast<const uint8_t*>(d_ev) + (size_t)(lp.m - base) * 32, 32, hipMemcpyDeviceToHost, s1));
+    LAG_TRY(hipMemcpyAsync(pin + LagStaging::PIN_S, small + LagStaging::S, 32, hipMemcpyDeviceToHost, s1));
+    if (lp.owns_m())                                            // f_m = y (helpers.rs:497-504)
+        LAG_TRY(hipMemcpyAsync(pin + LagStaging::PIN_FM, reinterpret_cast<const uint8_t*>(d_ev) + (size_t)(lp.m - base) * 32, 32, hipMemcpyDeviceToHost, s1));
     LAG_TRY(hipEventRecord(ctx->lag_phase1[slot], s1));            // phase 2 (the slot's stream) and lag_partial_y wait for THIS proof's phase 1 only
     lp.phase = 1;
     return KZG_OK;
@@ -350,7 +367,7 @@ int32_t lag_partial_y(kzg_ctx* ctx, int slot, uint64_t out[8]) {
     hipError_t e = lp.len ? hipEventSynchronize(ctx->lag_phase1[slot]) : hipSuccess;
     if (e != hipSuccess) { lp = LagProof(); return set_error(ctx, e, "lagrange proof: partial sum"); }
     const uint8_t* pin = static_cast<const uint8_t*>(ctx->poly[slot].pinned);
-    memcpy(out, pin + 64, 64);                                // S_g | f_m (zero unless this slice owns m)
+    memcpy(out, pin + LagStaging::PIN_S, LagStaging::PIN_T - LagStaging::PIN_S);               // S_g | f_m (zero unless this slice owns m)
     if (lp.on_domain) memset(out, 0, 32);                     // the barycentric sum is not used for a domain point (and holds a dummy term)
     lp.phase = 2;
     return KZG_OK;
@@ -369,24 +386,20 @@ int32_t lag_continue(kzg_ctx* ctx, int slot, const uint64_t y[4]) {
     int32_t rc = ntt_get_tables(ctx, ilog2_ceil(lp.n), false, &tb);
     if (rc != KZG_OK) { lp = LagProof(); return rc; }
     auto fail = [&](hipError_t e, const char* where) { lp = LagProof(); (void)hipStreamSynchronize(st); return set_error(ctx, e, where); };
-    memcpy(pin + 32, y, 32);
+    memcpy(pin + LagStaging::PIN_Y, y, 32);
     LAG_TRY(hipStreamWaitEvent(st, ctx->lag_phase1[slot], 0));     // the inverses (already complete: lag_partial_y waited for the event)
-    LAG_TRY(hipMemcpyAsync(small + 32, pin + 32, 32, hipMemcpyHostToDevice, st));
-    const bool owner = lp.on_domain && lp.m >= lp.base && lp.m - lp.base < lp.len;
-    const uint32_t m_slice = owner ? (uint32_t)(lp.m - lp.base) : NO_INDEX;
+    LAG_TRY(hipMemcpyAsync(small + LagStaging::Y, pin + LagStaging::PIN_Y, 32, hipMemcpyHostToDevice, st));
+    const uint32_t m_slice = lp.owns_m() ? (uint32_t)(lp.m - lp.base) : NO_INDEX;
     // same lanes-per-element shape as k_poly_quotient: four elements per lane
     uint32_t blocks = (uint32_t)((lp.len + LAG_BLOCK - 1) / LAG_BLOCK);
     const uint4* d_ev = lp.d_evals ? static_cast<const uint4*>(lp.d_evals) : set.a.as<uint4>();
     hipLaunchKernelGGL(k_lag_quotient, dim3(blocks), dim3(POLY_THREADS), 0, st, d_ev, (uint32_t)lp.len, (uint32_t)lp.base, tb,
-                       set.b.as<int32_t>(), reinterpret_cast<const uint4*>(small + 32), m_slice, lp.on_domain ? 1 : 0, set.c.as<uint4>(),
-                       reinterpret_cast<int32_t*>(small + LAG_SMALL_PARTIALS));
+                       set.b.as<int32_t>(), reinterpret_cast<const uint4*>(small + LagStaging::Y), m_slice, lp.on_domain ? 1 : 0, set.c.as<uint4>(), reinterpret_cast<int32_t*>(small + LagStaging::PARTIALS));
     if (lp.on_domain) {
-        hipLaunchKernelGGL(k_lag_sum, dim3(1), dim3(POLY_THREADS), 0, st, reinterpret_cast<const int32_t*>(small + LAG_SMALL_PARTIALS), blocks,
-                           reinterpret_cast<uint4*>(small + 160));
-        LAG_TRY(hipMemcpyAsync(pin + 128, small + 160, 32, hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(k_lag_sum, dim3(1), dim3(POLY_THREADS), 0, st, reinterpret_cast<int32_t*>(small + LagStaging::PARTIALS), blocks, reinterpret_cast<uint4*>(small + LagStaging::T));
+        LAG_TRY(hipMemcpyAsync(pin + LagStaging::PIN_T, small + LagStaging::T, 32, hipMemcpyDeviceToHost, st));
     }
     LAG_TRY(hipGetLastError());
-#undef LAG_TRY
     if (lp.grouped) {                                           // commitment (the evaluations) and proof (the quotient) as ONE launch, in that order
         MsmBases b;
         b.points = srs_bits(lp.shard); b.table_stride = (uint32_t)lp.shard->n; b.c = 7; b.W = 255; b.naf = true;
@@ -423,8 +436,8 @@ int32_t lag_end(kzg_ctx* ctx, int slot, uint64_t out_part[32], uint64_t* out_com
     if (rc != KZG_OK) return rc;
     if (!lp.on_domain) return KZG_OK;
     const uint8_t* pin = static_cast<const uint8_t*>(ctx->poly[slot].pinned);
-    memcpy(out_part + 16, pin + 128, 32);
-    if (lp.m >= lp.base && lp.m - lp.base < lp.len) {
+    memcpy(out_part + 16, pin + LagStaging::PIN_T, 32);
+    if (lp.owns_m()) {
         rc = srs_download(ctx, lp.shard->d_points + 4 * (lp.m - lp.base), 1, out_part + 20);
         if (rc != KZG_OK) return rc;
         out_part[28] = 1;
@@ -449,39 +462,33 @@ int32_t lag_quotient_eval_on_domain(kzg_ctx* ctx, const uint64_t z[4], const uin
     rc = ntt_get_tables(ctx, log_n, false, &tb);
     if (rc != KZG_OK) return rc;
     PolySet& set = ctx->poly[slot];
-    if (!set.pinned) KZG_HIP_TRY(ctx, hipHostMalloc(&set.pinned, 4096, hipHostMallocDefault));
+    if (!set.pinned) KZG_HIP_TRY(ctx, hipHostMalloc(&set.pinned, LagStaging::PINNED_BYTES, hipHostMallocDefault));
     uint8_t* pin = static_cast<uint8_t*>(set.pinned);
     const uint32_t blocks = (uint32_t)((n + LAG_BLOCK - 1) / LAG_BLOCK);
     auto fail = [&](hipError_t e, const char* where) { (void)hipStreamSynchronize(st); return set_error(ctx, e, where); };
-#define LAG_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return fail(_e, #expr); } while (0)
-    LAG_TRY(set.a.reserve(n * 32 + 32));
-    LAG_TRY(set.b.reserve(n * NL * 4 + 64));
-    LAG_TRY(set.c.reserve(n * 32 + 32));
-    LAG_TRY(set.small.reserve(LAG_SMALL_PARTIALS + (size_t)blocks * NL * 4 + 64));
+    LAG_TRY(lag_reserve(set, n, blocks));
     uint8_t* small = set.small.as<uint8_t>();
-    memcpy(pin, z, 32);
-    memcpy(pin + 32, value, 32);
+    memcpy(pin + LagStaging::PIN_Z, z, 32);
+    memcpy(pin + LagStaging::PIN_Y, value, 32);
     const uint32_t no_index = NO_INDEX;
-    memcpy(pin + 160, &no_index, 4);
-    LAG_TRY(hipMemcpyAsync(small, pin, 64, hipMemcpyHostToDevice, st));
-    LAG_TRY(hipMemcpyAsync(small + 64, pin + 160, 4, hipMemcpyHostToDevice, st));
+    memcpy(pin + LagStaging::PIN_INDEX, &no_index, 4);
+    LAG_TRY(hipMemcpyAsync(small + LagStaging::Z, pin + LagStaging::PIN_Z, LagStaging::PIN_S - LagStaging::PIN_Z, hipMemcpyHostToDevice, st));    // z | y
+    LAG_TRY(hipMemcpyAsync(small + LagStaging::INDEX, pin + LagStaging::PIN_INDEX, 4, hipMemcpyHostToDevice, st));
     LAG_TRY(hipMemcpyAsync(set.a.p, evals, n * 32, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_lag_inverses, dim3(blocks), dim3(POLY_THREADS), 0, st, set.a.as<uint4>(), (uint32_t)n, 0u, tb, reinterpret_cast<const uint4*>(small),
-                       set.b.as<int32_t>(), reinterpret_cast<int32_t*>(small + LAG_SMALL_PARTIALS), reinterpret_cast<uint32_t*>(small + 64));
-    LAG_TRY(hipMemcpyAsync(pin + 160, small + 64, 4, hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(k_lag_inverses, dim3(blocks), dim3(POLY_THREADS), 0, st, set.a.as<uint4>(), (uint32_t)n, 0u, tb, reinterpret_cast<const uint4*>(small + LagStaging::Z),
+                       set.b.as<int32_t>(), reinterpret_cast<int32_t*>(small + LagStaging::PARTIALS), reinterpret_cast<uint32_t*>(small + LagStaging::INDEX));
+    LAG_TRY(hipMemcpyAsync(pin + LagStaging::PIN_INDEX, small + LagStaging::INDEX, 4, hipMemcpyDeviceToHost, st));
     LAG_TRY(hipStreamSynchronize(st));                          // the index of the root equal to z, if any (found by the kernel)
     uint32_t m_slice = NO_INDEX;
-    memcpy(&m_slice, pin + 160, 4);
+    memcpy(&m_slice, pin + LagStaging::PIN_INDEX, 4);
     hipLaunchKernelGGL(k_lag_quotient, dim3(blocks), dim3(POLY_THREADS), 0, st, set.a.as<uint4>(), (uint32_t)n, 0u, tb, set.b.as<int32_t>(),
-                       reinterpret_cast<const uint4*>(small + 32), m_slice, 1, set.c.as<uint4>(), reinterpret_cast<int32_t*>(small + LAG_SMALL_PARTIALS));
-    hipLaunchKernelGGL(k_lag_sum, dim3(1), dim3(POLY_THREADS), 0, st, reinterpret_cast<const int32_t*>(small + LAG_SMALL_PARTIALS), blocks,
-                       reinterpret_cast<uint4*>(small + 160));
+                       reinterpret_cast<const uint4*>(small + LagStaging::Y), m_slice, 1, set.c.as<uint4>(), reinterpret_cast<int32_t*>(small + LagStaging::PARTIALS));
+    hipLaunchKernelGGL(k_lag_sum, dim3(1), dim3(POLY_THREADS), 0, st, reinterpret_cast<int32_t*>(small + LagStaging::PARTIALS), blocks, reinterpret_cast<uint4*>(small + LagStaging::T));
     LAG_TRY(hipGetLastError());
-    LAG_TRY(hipMemcpyAsync(pin + 128, small + 160, 32, hipMemcpyDeviceToHost, st));
+    LAG_TRY(hipMemcpyAsync(pin + LagStaging::PIN_T, small + LagStaging::T, 32, hipMemcpyDeviceToHost, st));
     LAG_TRY(hipStreamSynchronize(st));
-#undef LAG_TRY
     uint64_t t[4], zi[4], prod[4];
-    memcpy(t, pin + 128, 32);
+    memcpy(t, pin + LagStaging::PIN_T, 32);
     kzg_host::fr_inv(z, zi);
     kzg_host::fr_mul(t, zi, prod);
     kzg_host::fr_sub(zero, prod, out);
@@ -504,6 +511,7 @@ void lag_abort(kzg_ctx* ctx, int slot) {
     else if (st) (void)hipStreamSynchronize(st);
 }
 
+#undef LAG_TRY
 }  // namespace kzg
 
 #if defined(KZG_DEVICE_BOUND_CHECK)   // the device bound-check variant only (field29.h, `make boundcheck`)

@@ -12,15 +12,13 @@
 // host computes while it enqueues (one 254-bit exponentiation, ~15 us); the device only multiplies: ~3 products per element
 // and level.  (Round 1 / first half of round 2: one Fermat inversion per lane, 381 dependent multiplies = 213 us on the
 // critical path of every proof, whatever n.)  Results are identical field elements.
-// Also: helpers::calculate_roots_of_unity (helpers.rs:553-589) as a kernel.
+// Also: helpers::calculate_roots_of_unity (helpers.rs:553-589) and helpers::to_fr_array as kernels.  (The batched evaluations of batch
+// verification are vbeval.hip's.)
 #include "poly_common.h"
-#include "fe_invert.h"
 #include "proof_plan.h"    // the proof driver's policy, the staging layout (ProofStaging, ProofScalars) and the chain's scalar table
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
-#include <vector>
 
 namespace kzg {
 
@@ -173,6 +171,22 @@ k_poly_inv_level(const uint4* __restrict__ zt, int log_n, int log_nl, NttTables 
     for (uint32_t k = 0; k < 4; ++k) pl_store(out, N, t + k * T, inv[k]);
 }
 
+// y (reduced) into the proof's scalar image: the limbs for k_poly_quotient, the wire form for the read-back; one thread
+__device__ __forceinline__ void proof_store_y(ProofScalars* __restrict__ ps, const Fr& y) {
+#pragma unroll
+    for (int j = 0; j < NL; ++j) ps->y[j] = y.l[j];
+    fe_to_wire(ps->y_wire, y);
+}
+// 1/z = w^(n-m) for z = w^m
+__device__ __forceinline__ void proof_z_inverse(Fr& zinv, const NttTables& tb, uint32_t n, uint32_t m) { domain_elem(zinv, tb, (n - m) & (n - 1)); }
+// the on-domain element q_m = -(1/z) sum, sum = sum_{i != m} q_i w^i (kzg.rs:237-260); one thread
+__device__ __forceinline__ void proof_store_q_m(uint4* __restrict__ q_out, uint32_t m, const Fr& sum, const Fr& zinv) {
+    Fr q;
+    fe_mul(q, sum, zinv);
+    fe_neg(q, q);
+    fe_norm(q);
+    wire_store(q_out, m, q);
+}
 // y = (z^n - 1) / n * sum  for z off the domain (helpers.rs:529-532), into the proof's scalar image; one thread
 __device__ __forceinline__ void poly_store_y_off_domain(const Fr& sum, int log_n, const uint4* __restrict__ z_wire, ProofScalars* __restrict__ ps) {
     Fr y, z, zn, one, ninv;
@@ -186,8 +200,8 @@ __device__ __forceinline__ void poly_store_y_off_domain(const Fr& sum, int log_n
     fe_mul(y, sum, zn);
     fe_mul(y, y, ninv);
 #pragma unroll
-    for (int j = 0; j < NL; ++j) ps->y[j] = y.l[j];
-    fe_to_wire(ps->y_wire, y);
+    for (int j = 0; j < NL; ++j) ps->y[j] = y.l[j];          // as proof_store_y, written out: through the call k_poly_inverses came out with
+    fe_to_wire(ps->y_wire, y);                               // other registers, and a proof of 1 024 evaluations measured outside the parent's spread
 }
 
 // ---- K1: the last level (inverses of all n denominators) + barycentric partial sums ---------------------------------------
@@ -261,28 +275,16 @@ k_poly_finish_y(const uint4* __restrict__ evals, uint32_t n, int log_n, const ui
                 const int32_t* __restrict__ partial, uint32_t n_partial, ProofScalars* __restrict__ ps) {
     __shared__ int32_t lds[NL * POLY_THREADS];
     Fr sum;
-    fe_set_zero(sum);
-    for (uint32_t i = threadIdx.x; i < n_partial; i += POLY_THREADS) {
-        Fr v;
-        pl_load(v, partial, n_partial, i);
-        fe_add(sum, sum, v);
-        fe_norm(sum);
-        if ((i / POLY_THREADS) % 32 == 31) fe_reduce(sum);
-    }
-    fe_reduce(sum);
-    block_sum(sum, lds);
+    sum_partials(sum, partial, n_partial, lds);
     if (threadIdx.x != 0) return;
-    Fr y;
-    uint32_t m = ps->on_domain_index;
-    if (m != NO_INDEX) {
-        wire_load(y, evals, m);                   // helpers.rs:497-504
-    } else {
+    const uint32_t m = ps->on_domain_index;
+    if (m == NO_INDEX) {
         poly_store_y_off_domain(sum, log_n, z_wire, ps);
         return;
     }
-#pragma unroll
-    for (int j = 0; j < NL; ++j) ps->y[j] = y.l[j];
-    fe_to_wire(ps->y_wire, y);
+    Fr y;
+    wire_load(y, evals, m);                       // helpers.rs:497-504
+    proof_store_y(ps, y);
 }
 
 // ---- K3: quotient evaluations -----------------------------------------------------------------------------
@@ -329,23 +331,11 @@ k_poly_quotient_on_domain(uint32_t n, NttTables tb, const int32_t* __restrict__ 
     const uint32_t m = ps->on_domain_index;
     if (m == NO_INDEX) return;
     Fr sum;
-    fe_set_zero(sum);
-    for (uint32_t i = threadIdx.x; i < n_partial; i += POLY_THREADS) {
-        Fr v;
-        pl_load(v, partial, n_partial, i);
-        fe_add(sum, sum, v);
-        fe_norm(sum);
-        if ((i / POLY_THREADS) % 32 == 31) fe_reduce(sum);
-    }
-    fe_reduce(sum);
-    block_sum(sum, lds);
+    sum_partials(sum, partial, n_partial, lds);
     if (threadIdx.x != 0) return;
-    Fr zinv, q;
-    domain_elem(zinv, tb, (n - m) & (n - 1));
-    fe_mul(q, sum, zinv);
-    fe_neg(q, q);
-    fe_norm(q);
-    wire_store(q_out, m, q);
+    Fr zinv;
+    proof_z_inverse(zinv, tb, n, m);
+    proof_store_q_m(q_out, m, sum, zinv);
 }
 
 // ---- K3' / K4': z = w^m with m known on the host (compute_proof_with_known_z_fr_index, kzg.rs:237-260), n <= POLY_SMALL_MAX ---------
@@ -360,7 +350,7 @@ k_poly_quotient_table(const uint4* __restrict__ evals, uint32_t n, NttTables tb,
     Fr y, zinv;
     wire_load(y, evals, m);
     fe_reduce(y);
-    domain_elem(zinv, tb, (n - m) & (n - 1));             // w^-m
+    proof_z_inverse(zinv, tb, n, m);
     Fr sum;
     fe_set_zero(sum);
     uint32_t cnt = 0;
@@ -383,15 +373,9 @@ k_poly_quotient_table(const uint4* __restrict__ evals, uint32_t n, NttTables tb,
     block_sum(sum, lds);
     if (threadIdx.x != 0) return;
     if (gridDim.x > 1) { pl_store(partial, gridDim.x, blockIdx.x, sum); return; }
-    Fr q;                                                 // n <= 1 024: the only workgroup -- what k_poly_quotient_on_domain_known would do
-    fe_mul(q, sum, zinv);
-    fe_neg(q, q);
-    fe_norm(q);
-    wire_store(q_out, m, q);
+    proof_store_q_m(q_out, m, sum, zinv);                 // n <= 1 024: the only workgroup -- what k_poly_quotient_on_domain_known would do
     ps->on_domain_index = m;
-#pragma unroll
-    for (int j = 0; j < NL; ++j) ps->y[j] = y.l[j];
-    fe_to_wire(ps->y_wire, y);
+    proof_store_y(ps, y);
 }
 // as K4, and y = f_m for the read-back
 __global__ void __launch_bounds__(POLY_THREADS)
@@ -399,28 +383,14 @@ k_poly_quotient_on_domain_known(const uint4* __restrict__ evals, uint32_t n, Ntt
                                 uint32_t m, ProofScalars* __restrict__ ps, uint4* __restrict__ q_out) {
     __shared__ int32_t lds[NL * POLY_THREADS];
     Fr sum;
-    fe_set_zero(sum);
-    for (uint32_t i = threadIdx.x; i < n_partial; i += POLY_THREADS) {
-        Fr v;
-        pl_load(v, partial, n_partial, i);
-        fe_add(sum, sum, v);
-        fe_norm(sum);
-        if ((i / POLY_THREADS) % 32 == 31) fe_reduce(sum);
-    }
-    fe_reduce(sum);
-    block_sum(sum, lds);
+    sum_partials(sum, partial, n_partial, lds);
     if (threadIdx.x != 0) return;
-    Fr zinv, q, y;
-    domain_elem(zinv, tb, (n - m) & (n - 1));
-    fe_mul(q, sum, zinv);
-    fe_neg(q, q);
-    fe_norm(q);
-    wire_store(q_out, m, q);
+    Fr zinv, y;
+    proof_z_inverse(zinv, tb, n, m);
+    proof_store_q_m(q_out, m, sum, zinv);
     wire_load(y, evals, m);
     ps->on_domain_index = m;
-#pragma unroll
-    for (int j = 0; j < NL; ++j) ps->y[j] = y.l[j];
-    fe_to_wire(ps->y_wire, y);
+    proof_store_y(ps, y);
 }
 
 // ---- blob bytes -> Fr (helpers::to_fr_array, primitives/src/helpers.rs:40-57) ---------------------------------------
@@ -435,10 +405,7 @@ k_blob_to_fr(const uint8_t* __restrict__ bytes, size_t len, uint32_t n_elems, ui
     if (i < n_elems && (size_t)i * 32 + 32 <= len) {
         // a whole chunk (all but a ragged last one): two 16-byte loads and byte swaps instead of 32 single-byte loads -- 67 -> ~20 us at 2^20 elements
         // (the staging buffer comes from hipMalloc: 16-byte aligned)
-        const uint4* p = reinterpret_cast<const uint4*>(bytes + (size_t)i * 32);
-        const uint4 hi = p[0], lo = p[1];          // bytes 0..15 (most significant), 16..31
-        w32[7] = __builtin_bswap32(hi.x); w32[6] = __builtin_bswap32(hi.y); w32[5] = __builtin_bswap32(hi.z); w32[4] = __builtin_bswap32(hi.w);
-        w32[3] = __builtin_bswap32(lo.x); w32[2] = __builtin_bswap32(lo.y); w32[1] = __builtin_bswap32(lo.z); w32[0] = __builtin_bswap32(lo.w);
+        be_chunk_load(w32, bytes + (size_t)i * 32);
     } else if (i < n_elems) {
         const size_t base = (size_t)i * 32;
 #pragma unroll
@@ -475,196 +442,6 @@ k_poly_roots(uint4* __restrict__ out, uint32_t n, NttTables tb) {
     wire_store(out, i, w);
 }
 
-// ---- batch verification front end: all n barycentric evaluations of verify_blob_kzg_proof_batch in two launches ---------------
-// verifier/src/batch.rs:16-69 -> primitives/src/helpers.rs:613-662 evaluates y_i = p_i(z_i) blob after blob (n_i inversions each).
-// Here blob i (2^log_n <= 2^VB_MAX_LOG evaluations, read straight from its big-endian bytes) is one workgroup:
-//   k_vb_prep   one LANE per blob: z^n by squarings and the ONE inversion of the blob, 1 / (z^n - 1) = 1 / prod_j (z - w^j) (Fermat)
-//   k_vb_eval   one WORKGROUP per blob: lane t owns the denominators d_j = z - w^j, j = t + k Lf; a product tree over the lanes
-//               in LDS (up-sweep), seeded at the root with the inverse from k_vb_prep and walked down (inverse of a node =
-//               inverse of its parent x product of its sibling) leaves every lane the inverse of its own product; Montgomery's
-//               trick inside the lane; then sum_j f_j w^j / (z - w^j) and y = (z^n - 1) / n times that sum (helpers.rs:507-532).
-// z on the domain (1 - z^n == 0; the early return of helpers.rs:497-504) and blobs beyond 2^VB_MAX_LOG elements are flagged and evaluated by
-// the single-polynomial path (proof_run) on the host's request.
-constexpr int VB_MAX_LOG = 12;
-constexpr int VB_THREADS = 512;         // 8 waves: two per SIMD, 256 VGPRs each (the asm products keep inputs and outputs apart)
-struct VbBlob { uint64_t off; uint32_t len; uint32_t log_n; };          // byte offset (32-byte aligned, zero-filled to the next chunk), byte length, log2(padded elements)
-struct VbPrep { int32_t z[NL]; int32_t znm1[NL]; int32_t tinv[NL]; uint32_t fallback; };
-
-__global__ void __launch_bounds__(64)
-k_vb_prep(const uint4* __restrict__ zs_wire, const VbBlob* __restrict__ meta, uint32_t nb, VbPrep* __restrict__ prep) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nb) return;
-    const int log_n = (int)meta[i].log_n;
-    Fr z, zn, one, den;
-    wire_load(z, zs_wire, i);
-    zn = z;
-    for (int a = 0; a < log_n; ++a) fe_sqr(zn, zn);
-    fe_set_one(one);
-    fe_sub(den, zn, one);
-    fe_reduce(den);                                        // z^n - 1 in (-m, 2m)
-    Fr dc = den;
-    fe_canon(dc);
-    VbPrep& o = prep[i];
-    o.fallback = (fe_is_literal_zero(dc) || log_n > VB_MAX_LOG) ? 1u : 0u;
-    fe_canon(z);
-#pragma unroll
-    for (int j = 0; j < NL; ++j) { o.z[j] = z.l[j]; o.znm1[j] = den.l[j]; }
-    if (o.fallback) return;
-    // 1 / den by division steps (fe_invert.h, round 4; a^(r-2) before: 380 dependent products on a lone lane)
-    Fr acc;
-    fe_inverse_safegcd(acc, den);
-#pragma unroll
-    for (int j = 0; j < NL; ++j) o.tinv[j] = acc.l[j];
-}
-
-// raw big-endian chunk j of a packed blob as a plain integer < 2^256 in limbs (zero beyond the blob's elements)
-__device__ __forceinline__ void vb_load_raw(Fr& x, const uint8_t* __restrict__ base, uint32_t j, uint32_t n_elems) {
-    uint32_t w32[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (j < n_elems) {
-        const uint4* p = reinterpret_cast<const uint4*>(base + (size_t)j * 32);
-        const uint4 hi = p[0], lo = p[1];                  // bytes 0..15 (most significant), 16..31
-        w32[7] = __builtin_bswap32(hi.x); w32[6] = __builtin_bswap32(hi.y); w32[5] = __builtin_bswap32(hi.z); w32[4] = __builtin_bswap32(hi.w);
-        w32[3] = __builtin_bswap32(lo.x); w32[2] = __builtin_bswap32(lo.y); w32[1] = __builtin_bswap32(lo.z); w32[0] = __builtin_bswap32(lo.w);
-    }
-    fe_unpack(x, w32);
-}
-
-// lane t of a blob's workgroup: its M denominators, their product into the tree leaf (phase 1), and after the tree walk the M
-// barycentric terms (phase 2).  M = n / Lf in {1, 2, 4, 8}: a template parameter so that d[] / pre[] stay in registers.
-template <int M>
-struct VbLane {
-    Fr d[M], pre[M];
-    __device__ __forceinline__ void denominators(Fr& p, const Fr& z, const NttTables& tb, uint32_t t, uint32_t Lf, int sh) {
-#pragma unroll
-        for (int k = 0; k < M; ++k) {
-            Fr w;
-            domain_elem(w, tb, (t + (uint32_t)k * Lf) << sh);
-            fe_canon(w);
-            fe_sub(d[k], z, w);                            // canonical - canonical: limbs within +-2^29, |d| < m
-            if (k == 0) p = d[0];
-            else { pre[k] = p; fe_mul(p, p, d[k]); }
-        }
-    }
-    __device__ __forceinline__ void terms(Fr& sum, Fr inv_all, const NttTables& tb, const uint8_t* __restrict__ base, uint32_t n_elems, uint32_t t, uint32_t Lf, int sh) {
-#pragma unroll
-        for (int k = M - 1; k >= 0; --k) {
-            Fr inv;
-            if (k > 0) { fe_mul(inv, inv_all, pre[k]); fe_mul(inv_all, inv_all, d[k]); }
-            else inv = inv_all;
-            const uint32_t jdx = t + (uint32_t)k * Lf;
-            Fr x, w, term;
-            vb_load_raw(x, base, jdx, n_elems);
-            domain_elem(w, tb, jdx << sh);
-            fe_mul(term, x, w);                            // plain integer x internal form = plain residue f_j w^j
-            fe_mul(term, term, inv);
-            fe_add(sum, sum, term);
-            if (M > 4 && (k & 1) == 0) fe_norm(sum);       // at most four unnormalised 29-bit limbs fit an int32: keep the running sum normalised
-        }
-        fe_norm(sum);                                      // <= 8 terms of (-m, 2m)
-        fe_reduce(sum);
-    }
-};
-
-template <int M>
-__device__ __forceinline__ void vb_eval_body(int32_t* __restrict__ tree, const uint8_t* __restrict__ bytes, const VbBlob& b, const VbPrep& pr,
-                                             const NttTables& tb, uint4* __restrict__ ys_wire) {
-    const int log_n = (int)b.log_n;
-    const uint32_t n = 1u << log_n, Lf = n / (uint32_t)M, S = 2 * Lf;
-    const uint32_t t = threadIdx.x, n_elems = (b.len + 31) / 32;
-    const int sh = VB_MAX_LOG - log_n;                     // w_n^j = w_4096^(j << sh)
-    Fr z;
-#pragma unroll
-    for (int j = 0; j < NL; ++j) z.l[j] = pr.z[j];
-    VbLane<M> lane;
-    if (t < Lf) {
-        Fr p;
-        lane.denominators(p, z, tb, t, Lf, sh);
-#pragma unroll
-        for (int j = 0; j < NL; ++j) tree[j * S + Lf + t] = p.l[j];
-    }
-    __syncthreads();
-    for (uint32_t s = Lf >> 1; s >= 1; s >>= 1) {          // up-sweep: node = product of its two children
-        if (t < s) {
-            const uint32_t node = s + t;
-            Fr a, c, r;
-#pragma unroll
-            for (int j = 0; j < NL; ++j) { a.l[j] = tree[j * S + 2 * node]; c.l[j] = tree[j * S + 2 * node + 1]; }
-            fe_mul(r, a, c);
-#pragma unroll
-            for (int j = 0; j < NL; ++j) tree[j * S + node] = r.l[j];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-#pragma unroll
-        for (int j = 0; j < NL; ++j) tree[j * S + 1] = pr.tinv[j];                   // 1 / prod_j (z - w^j) = 1 / (z^n - 1)
-    }
-    __syncthreads();
-    for (uint32_t s = 1; s < Lf; s <<= 1) {                // down-sweep: inverse of a child = inverse of the node x its sibling
-        if (t < s) {
-            const uint32_t node = s + t;
-            Fr g, a, c, ia, ic;
-#pragma unroll
-            for (int j = 0; j < NL; ++j) { g.l[j] = tree[j * S + node]; a.l[j] = tree[j * S + 2 * node]; c.l[j] = tree[j * S + 2 * node + 1]; }
-            fe_mul2(ia, g, c, ic, g, a);
-#pragma unroll
-            for (int j = 0; j < NL; ++j) { tree[j * S + 2 * node] = ia.l[j]; tree[j * S + 2 * node + 1] = ic.l[j]; }
-        }
-        __syncthreads();
-    }
-    Fr sum;
-    fe_set_zero(sum);
-    if (t < Lf) {
-        Fr inv_all;
-#pragma unroll
-        for (int j = 0; j < NL; ++j) inv_all.l[j] = tree[j * S + Lf + t];
-        lane.terms(sum, inv_all, tb, bytes + b.off, n_elems, t, Lf, sh);
-    }
-    __syncthreads();                                       // the tree is dead: its planes carry the block sum
-    int level = 0;
-    for (uint32_t dd = VB_THREADS / 2; dd >= 1; dd >>= 1, ++level) {
-#pragma unroll
-        for (int j = 0; j < NL; ++j) tree[j * VB_THREADS + t] = sum.l[j];
-        __syncthreads();
-        if (t < dd) {
-            Fr u;
-#pragma unroll
-            for (int j = 0; j < NL; ++j) u.l[j] = tree[j * VB_THREADS + t + dd];
-            fe_add(sum, sum, u);
-            fe_norm(sum);
-            if (level % 4 == 3) fe_reduce(sum);            // 16 terms of (-m, 2m) since the last reduction
-        }
-        __syncthreads();
-    }
-    if (t != 0) return;
-    fe_reduce(sum);
-    Fr y, znm1, ninv, kraw;
-#pragma unroll
-    for (int j = 0; j < NL; ++j) { znm1.l[j] = pr.znm1[j]; ninv.l[j] = (int32_t)FrParams::NINV[log_n * NL + j]; kraw.l[j] = (int32_t)FrParams::K_RAW[j]; }
-    fe_mul(y, sum, znm1);
-    fe_mul(y, y, ninv);                                    // helpers.rs:529-532; y is a PLAIN residue here (the raw f_j carried no Montgomery factor)
-    fe_mul(y, y, kraw);                                    // -> wire form y 2^256
-    fe_canon(y);
-    uint32_t o[8];
-    fe_pack(o, y);
-    ys_wire[2 * (size_t)blockIdx.x] = make_uint4(o[0], o[1], o[2], o[3]);
-    ys_wire[2 * (size_t)blockIdx.x + 1] = make_uint4(o[4], o[5], o[6], o[7]);
-}
-
-__global__ void __launch_bounds__(VB_THREADS)
-k_vb_eval(const uint8_t* __restrict__ bytes, const VbBlob* __restrict__ meta, const VbPrep* __restrict__ prep, NttTables tb /* 2^VB_MAX_LOG domain */,
-          uint4* __restrict__ ys_wire) {
-    extern __shared__ int32_t tree[];                      // NL planes of 2 Lf nodes (heap order: root 1, leaves Lf + t)
-    const VbBlob b = meta[blockIdx.x];
-    const VbPrep& pr = prep[blockIdx.x];
-    if (pr.fallback) return;                               // uniform across the workgroup
-    const uint32_t n = 1u << b.log_n;
-    if (n <= (uint32_t)VB_THREADS) vb_eval_body<1>(tree, bytes, b, pr, tb, ys_wire);
-    else if (n == 2u * VB_THREADS) vb_eval_body<2>(tree, bytes, b, pr, tb, ys_wire);
-    else if (n == 4u * VB_THREADS) vb_eval_body<4>(tree, bytes, b, pr, tb, ys_wire);
-    else vb_eval_body<8>(tree, bytes, b, pr, tb, ys_wire);
-}
-
 // ---- host -----------------------------------------------------------------------------------------------------
 int32_t roots_run(kzg_ctx* ctx, uint64_t* out, size_t n) {
     int log_n = ilog2_ceil(n);
@@ -696,7 +473,6 @@ int32_t blob_to_fr_run(kzg_ctx* ctx, const uint8_t* bytes, size_t len, size_t n_
     *d_out = d_elems->p;
     return KZG_OK;
 }
-
 
 // The known-index form's table 1 / (w^k - 1), k < n <= 4096, once per domain size: the inversion chain at z = 1
 static int32_t proof_ondomain_table(kzg_ctx* ctx, int log_n, const NttTables& tb, hipStream_t st, const int32_t** out) {
@@ -924,98 +700,6 @@ int32_t proof_end(kzg_ctx* ctx, int slot, uint64_t out_xy[8], uint8_t* out_inf, 
     int32_t rc = msm_end(ctx, slot, out_xy, out_inf, nullptr);
     if (rc == KZG_OK && out_y) proof_read_y(ctx->poly[slot], out_y);
     return rc;
-}
-
-// Batched y_i = p_i(z_i) for `nb` blobs whose bytes sit packed in PINNED host memory `packed` (blob i at meta[i].off, 32-byte aligned,
-// zero-filled up to the next 32-byte chunk) with the challenges zs (wire).  Three steps so that the caller can overlap the uploads with
-// the hashing of later blobs:
-//   vb_evaluate_setup(ctx, packed_len, nb)                     buffers, the 4096-point domain table, kernel attribute
-//   vb_evaluate_enqueue(ctx, packed, meta, b0, b1, zs)         blobs [b0, b1): their bytes, challenges and descriptors go up and the two
-//                                                              kernels are enqueued on the context's stream; returns at once; may be called
-//                                                              from any host thread, chunks in any order (they touch disjoint ranges)
-//   vb_evaluate_finish(ctx, nb, ys_out, fallback_out)          waits; ys_out = nb wire elements; fallback_out[i] != 0 marks the blobs this
-//                                                              path does not cover (z on the domain, more than 2^VB_MAX_LOG elements)
-// Slot 0's buffers and stream.
-int32_t vb_evaluate_setup(kzg_ctx* ctx, size_t packed_len, size_t nb) {
-    static_assert(sizeof(VbBlob) == 16, "VbBlob layout is part of the host interface (capi_verify.hip VbMeta)");
-    PolySet& set = ctx->poly[0];
-    NttTables tb;
-    int32_t rc = ntt_get_tables(ctx, VB_MAX_LOG, false, &tb);
-    if (rc != KZG_OK) return rc;
-    KZG_HIP_TRY(ctx, set.c.reserve(packed_len + 64));
-    KZG_HIP_TRY(ctx, set.a.reserve(nb * 32 * 2 + 64));                                 // zs | ys
-    KZG_HIP_TRY(ctx, set.b.reserve(nb * (sizeof(VbBlob) + sizeof(VbPrep)) + 64));
-    KZG_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_vb_eval), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(NL * 2 * VB_THREADS * 4)));
-    KZG_HIP_TRY(ctx, hipMemsetAsync(set.a.as<uint4>() + 2 * nb, 0, nb * 32, ctx->stream));
-    // slot 1's stream carries the blob bytes: created HERE, on the calling thread under ctx->mu -- vb_evaluate_enqueue runs on the
-    // caller's worker threads, which must not create context state (two chunks finishing together raced on stream_x[0])
-    hipStream_t st_copy = nullptr;
-    return msm_slot_stream(ctx, 1, &st_copy);
-}
-// `small_pinned`: pinned staging of at least nb x 48 bytes for the chunk's challenges and descriptors (a copy from pageable memory would
-// make this call wait for everything queued on the stream before it)
-int32_t vb_evaluate_enqueue(kzg_ctx* ctx, const uint8_t* packed, const void* meta_host, size_t nb, size_t b0, size_t b1, const uint64_t* zs,
-                            uint8_t* small_pinned) {
-    if (b1 <= b0) return KZG_OK;
-    // worker threads of the caller's pool: errors travel in the return code only (ctx->last_error belongs to the thread holding ctx->mu)
-    hipEvent_t up = nullptr;
-#define VB_TRY(expr) do { if ((expr) != hipSuccess) { (void)hipGetLastError(); if (up) (void)hipEventDestroy(up); return KZG_ERR_DEVICE; } } while (0)
-    VB_TRY(hipSetDevice(ctx->device));
-    PolySet& set = ctx->poly[0];
-    hipStream_t st = ctx->stream, st_copy = ctx->stream_x[0] ? ctx->stream_x[0] : ctx->stream;   // slot 1's stream exists since vb_evaluate_setup
-    // the blob bytes go up on a second stream (slot 1's): k_vb_prep is one inversion deep (~0.2 ms on a few lone waves, whatever the
-    // chunk size) and needs the challenges only, so it runs while the chunk's bytes are still on the bus; k_vb_eval waits for them
-    NttTables tb;
-    int32_t rc = ntt_get_tables(ctx, VB_MAX_LOG, false, &tb);                          // cached by vb_evaluate_setup: a look-up
-    if (rc != KZG_OK) return rc;
-    const VbBlob* meta = static_cast<const VbBlob*>(meta_host);
-    uint4* d_zs = set.a.as<uint4>();
-    uint4* d_ys = d_zs + 2 * nb;
-    VbBlob* d_meta = set.b.as<VbBlob>();
-    VbPrep* d_prep = reinterpret_cast<VbPrep*>(d_meta + nb);
-    uint32_t max_log = 0;
-    size_t lo = SIZE_MAX, hi = 0;
-    for (size_t i = b0; i < b1; ++i) {
-        if (meta[i].log_n > (uint32_t)VB_MAX_LOG) continue;
-        max_log = std::max(max_log, meta[i].log_n);
-        lo = std::min<size_t>(lo, meta[i].off);
-        hi = std::max<size_t>(hi, meta[i].off + ((size_t)meta[i].len + 31) / 32 * 32);
-    }
-    const uint32_t max_lf = std::min<uint32_t>(1u << max_log, (uint32_t)VB_THREADS);
-    const size_t lds = std::max<size_t>((size_t)NL * 2 * max_lf, (size_t)NL * VB_THREADS) * 4;
-    if (hi > lo) {
-        VB_TRY(hipMemcpyAsync(set.c.as<uint8_t>() + lo, packed + lo, hi - lo, hipMemcpyHostToDevice, st_copy));
-        VB_TRY(hipEventCreateWithFlags(&up, hipEventDisableTiming));
-        VB_TRY(hipEventRecord(up, st_copy));
-    }
-    uint8_t* pz = small_pinned + b0 * 32;
-    uint8_t* pm = small_pinned + nb * 32 + b0 * sizeof(VbBlob);
-    memcpy(pz, zs + 4 * b0, (b1 - b0) * 32);
-    memcpy(pm, meta + b0, (b1 - b0) * sizeof(VbBlob));
-    VB_TRY(hipMemcpyAsync(d_zs + 2 * b0, pz, (b1 - b0) * 32, hipMemcpyHostToDevice, st));
-    VB_TRY(hipMemcpyAsync(d_meta + b0, pm, (b1 - b0) * sizeof(VbBlob), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_vb_prep, dim3((unsigned)((b1 - b0 + 63) / 64)), dim3(64), 0, st, d_zs + 2 * b0, d_meta + b0, (uint32_t)(b1 - b0), d_prep + b0);
-    if (up) {
-        VB_TRY(hipStreamWaitEvent(st, up, 0));
-        (void)hipEventDestroy(up);                                                     // released by the runtime once the wait has been satisfied
-    }
-    hipLaunchKernelGGL(k_vb_eval, dim3((unsigned)(b1 - b0)), dim3(VB_THREADS), lds, st, set.c.as<uint8_t>(), d_meta + b0, d_prep + b0, tb, d_ys + 2 * b0);
-    VB_TRY(hipGetLastError());
-#undef VB_TRY
-    return KZG_OK;
-}
-int32_t vb_evaluate_finish(kzg_ctx* ctx, size_t nb, uint64_t* ys_out, uint8_t* fallback_out) {
-    PolySet& set = ctx->poly[0];
-    hipStream_t st = ctx->stream;
-    uint4* d_ys = set.a.as<uint4>() + 2 * nb;
-    VbPrep* d_prep = reinterpret_cast<VbPrep*>(set.b.as<VbBlob>() + nb);
-    static thread_local std::vector<VbPrep> prep_host;
-    prep_host.resize(nb);
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(ys_out, d_ys, nb * 32, hipMemcpyDeviceToHost, st));
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(prep_host.data(), d_prep, nb * sizeof(VbPrep), hipMemcpyDeviceToHost, st));
-    KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    for (size_t i = 0; i < nb; ++i) fallback_out[i] = prep_host[i].fallback ? 1 : 0;
-    return KZG_OK;
 }
 
 }  // namespace kzg

@@ -1,6 +1,8 @@
-// poly_common.h -- helpers shared by the polynomial kernels (poly.hip: whole-domain proofs) and the evaluation-slice kernels of the
-// Lagrange-sharded proofs (lagrange.hip): limb-plane loads / stores, domain elements from the two-level twiddle tables, wire <-> internal
-// conversion, the workgroup sum, and host-side Fr arithmetic on wire words for the handful of scalars a proof needs on the host.
+// poly_common.h -- helpers shared by the polynomial kernels (poly.hip: whole-domain proofs; vbeval.hip: the batched evaluations of batch
+// verification; recover.hip) and the evaluation-slice kernels of the Lagrange-sharded proofs (lagrange.hip): limb-plane loads / stores, domain
+// elements from the two-level twiddle tables, wire <-> internal conversion, the big-endian chunk load, the workgroup sum and the sum of
+// per-workgroup partials, Montgomery's trick across a workgroup, and host-side Fr arithmetic on wire words for the handful of
+// scalars a proof needs on the host.
 #pragma once
 #include "engine.h"
 #include "field29.h"
@@ -60,6 +62,67 @@ __device__ __forceinline__ void block_sum(Fr& v, int32_t* lds /* NL * POLY_THREA
         __syncthreads();
     }
     if (t == 0) fe_reduce(v);
+}
+// sum of n_partial per-workgroup partials (limb planes, stride n_partial, values in (-m, 2m)) by ONE workgroup; result (reduced) valid in thread 0
+__device__ __forceinline__ void sum_partials(Fr& sum, const int32_t* partial, uint32_t n_partial, int32_t* lds /* NL * POLY_THREADS */) {
+    fe_set_zero(sum);
+    for (uint32_t i = threadIdx.x; i < n_partial; i += POLY_THREADS) {
+        Fr v;
+        pl_load(v, partial, n_partial, i);
+        fe_add(sum, sum, v);
+        fe_norm(sum);
+        if ((i / POLY_THREADS) % 32 == 31) fe_reduce(sum);
+    }
+    fe_reduce(sum);
+    block_sum(sum, lds);
+}
+// the 32 big-endian bytes at p (16-byte aligned) as eight little-endian words: two 16-byte loads and byte swaps
+__device__ __forceinline__ void be_chunk_load(uint32_t w32[8], const uint8_t* __restrict__ p) {
+    const uint4* q = reinterpret_cast<const uint4*>(p);
+    const uint4 hi = q[0], lo = q[1];              // bytes 0..15 (most significant), 16..31
+    w32[7] = __builtin_bswap32(hi.x); w32[6] = __builtin_bswap32(hi.y); w32[5] = __builtin_bswap32(hi.z); w32[4] = __builtin_bswap32(hi.w);
+    w32[3] = __builtin_bswap32(lo.x); w32[2] = __builtin_bswap32(lo.y); w32[1] = __builtin_bswap32(lo.z); w32[0] = __builtin_bswap32(lo.w);
+}
+// Montgomery's trick across a workgroup: lane t < Lf (a power of two) has stored its value at leaf Lf + t of `tree` (NL planes of 2 Lf
+// nodes, heap order: root 1) and finds its inverse there on return.  Called by every lane of the workgroup.  root_inverse(ri, r) gives
+// the inverse ri of the root product r on lane 0: the one inversion of the workgroup.  None of the values may be zero.
+template <typename RootInverse>
+__device__ __forceinline__ void lds_tree_invert(int32_t* tree, uint32_t Lf, uint32_t t, RootInverse root_inverse) {
+    const uint32_t S = 2 * Lf;
+    __syncthreads();
+    for (uint32_t s = Lf >> 1; s >= 1; s >>= 1) {            // up-sweep: node = product of its two children
+        if (t < s) {
+            const uint32_t node = s + t;
+            Fr a, c, r;
+#pragma unroll
+            for (int j = 0; j < NL; ++j) { a.l[j] = tree[j * S + 2 * node]; c.l[j] = tree[j * S + 2 * node + 1]; }
+            fe_mul(r, a, c);
+#pragma unroll
+            for (int j = 0; j < NL; ++j) tree[j * S + node] = r.l[j];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        Fr root, ri;
+#pragma unroll
+        for (int j = 0; j < NL; ++j) root.l[j] = tree[j * S + 1];
+        root_inverse(ri, root);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) tree[j * S + 1] = ri.l[j];
+    }
+    __syncthreads();
+    for (uint32_t s = 1; s < Lf; s <<= 1) {                  // down-sweep: inverse of a child = inverse of the node x its sibling
+        if (t < s) {
+            const uint32_t node = s + t;
+            Fr g, a, c, ia, ic;
+#pragma unroll
+            for (int j = 0; j < NL; ++j) { g.l[j] = tree[j * S + node]; a.l[j] = tree[j * S + 2 * node]; c.l[j] = tree[j * S + 2 * node + 1]; }
+            fe_mul2(ia, g, c, ic, g, a);
+#pragma unroll
+            for (int j = 0; j < NL; ++j) { tree[j * S + 2 * node] = ia.l[j]; tree[j * S + 2 * node + 1] = ic.l[j]; }
+        }
+        __syncthreads();
+    }
 }
 
 }  // namespace kzg

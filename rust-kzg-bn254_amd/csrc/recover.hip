@@ -19,7 +19,7 @@
 //     broadcast).  The roots w_n^(l k) come from the forward tables of the n-point domain (ntt_get_tables).  2 m / 256 workgroups do not
 //     fill the device below m = 2^17, so M is split across blockIdx.y into up to RC_TARGET_GROUPS workgroups in all and the fold multiplies
 //     the partial products: a field product, the same element whatever the split, and canonical words leave the call.
-//   * the m divisors are inverted once: Montgomery's trick per workgroup of 256 (product tree in LDS, one fe_inverse_safegcd), as lagrange.hip.
+//   * the m divisors are inverted once: Montgomery's trick per workgroup of 256 (product tree in LDS, one fe_inverse_safegcd: lds_tree_invert).
 //   * g^t and g^-t are factored like the twiddle tables, 2^10 + n / 2^10 entries each (one product per element from 2^10 on), kept per context.
 //   * values stay in the wire residue class a 2^256 between the kernels (the factors are internal Montgomery), as in ntt.hip; every kernel
 //     writes canonical words, so equal inputs give equal bits.
@@ -138,7 +138,7 @@ k_recover_vanish(RcVanishArgs a) {
 }
 
 // lane p < 2 m: the product of its `rows` partial products; p < m: stored (zdom[p] = z(w^(l p))); p >= m: inverted, Montgomery's trick per
-// workgroup (product tree in LDS, one inversion, back down: lagrange.hip), zsinv[p - m] = 1 / z(s w^(l (p - m))).  No divisor is zero.
+// workgroup (lds_tree_invert), zsinv[p - m] = 1 / z(s w^(l (p - m))).  No divisor is zero.
 __global__ void __launch_bounds__(RC_THREADS)
 k_recover_vanish_fold(const int32_t* __restrict__ partial, uint32_t rows, uint32_t m, int32_t* __restrict__ zdom, int32_t* __restrict__ zsinv) {
     __shared__ int32_t tree[NL * 2 * RC_THREADS];                    // heap order: root 1, leaves RC_THREADS + t
@@ -158,38 +158,7 @@ k_recover_vanish_fold(const int32_t* __restrict__ partial, uint32_t rows, uint32
     if (blockIdx.x * RC_THREADS + RC_THREADS <= m) return;           // no divisor in this workgroup (uniform)
     if (p < m || p >= two_m) fe_set_one(v);
     pl_store(tree, S, Lf + t, v);
-    __syncthreads();
-    for (uint32_t s = Lf >> 1; s >= 1; s >>= 1) {                    // up-sweep: node = product of its two children
-        if (t < s) {
-            const uint32_t node = s + t;
-            Fr a, c, r;
-            pl_load(a, tree, S, 2 * node);
-            pl_load(c, tree, S, 2 * node + 1);
-            fe_mul(r, a, c);
-            pl_store(tree, S, node, r);
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        Fr root, ri;
-        pl_load(root, tree, S, 1);
-        fe_inverse_safegcd(ri, root);
-        pl_store(tree, S, 1, ri);
-    }
-    __syncthreads();
-    for (uint32_t s = 1; s < Lf; s <<= 1) {                          // down-sweep: inverse of a child = inverse of the node x its sibling
-        if (t < s) {
-            const uint32_t node = s + t;
-            Fr g, a, c, ia, ic;
-            pl_load(g, tree, S, node);
-            pl_load(a, tree, S, 2 * node);
-            pl_load(c, tree, S, 2 * node + 1);
-            fe_mul2(ia, g, c, ic, g, a);
-            pl_store(tree, S, 2 * node, ia);
-            pl_store(tree, S, 2 * node + 1, ic);
-        }
-        __syncthreads();
-    }
+    lds_tree_invert(tree, Lf, t, [](Fr& ri, const Fr& root) { fe_inverse_safegcd(ri, root); });
     if (p >= m && p < two_m) {
         pl_load(v, tree, S, Lf + t);
         pl_store(zsinv, m, p - m, v);
