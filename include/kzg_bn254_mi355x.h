@@ -719,6 +719,51 @@ int32_t kzg_commit_with_length_proof(kzg_ctx* ctx, const kzg_srs* g1_srs, const 
  * KZG_ERR_G2_TAU_NOT_ON_CURVE.  The subgroup of the G2 inputs is not checked (see kzg_verify_proof). */
 int32_t kzg_verify_length_proof(const uint64_t commitment_xy[8], const uint64_t length_commitment[16], const uint64_t length_proof[16],
                                 const uint64_t g1_tau_shift_xy[8], int32_t* out_ok);
+/* ---- batches of blob headers ------------------------------------------------------------------------------------------------------
+ * A validator checks every header (C, C2, pi2, d) of every batch it signs; the two G2 elements come from an untrusted disperser.
+ * kzg_verify_length_proof_batch checks `count` headers with ONE product of pairings: with weights r_i and rho (derived from a
+ * transcript of all inputs, or supplied), W_g = sum_{i in g} r_i C2_i per claimed length g, Pi = sum r_i pi2_i, U = sum r_i C_i and
+ * S = sum_g W_g it accepts iff
+ *     e(U, G2) e(-G1, S + [rho]Pi) prod_g e([rho]T_g, W_g) = 1,      T_g = [tau^(N - shift_lens[g])]_1,
+ * which is sum r_i [e(C_i, G2) - e(G1, C2_i)] + rho sum r_i [e(T_(d_i), C2_i) - e(G1, pi2_i)] = 0: 2 + (non-empty groups) Miller loops
+ * and one final exponentiation whatever the count.  A batch with a bad header passes with probability about 2^-128 over the weights
+ * (independent r_i, one rho between the two equations).  On the device: the on-twist test, the order-r subgroup
+ * test of both G2 elements (one 63-bit chain per point, csrc/g2_chain.h), the chains [r_i]C2_i and [r_i]pi2_i with their sums
+ * (csrc/g2batch.hip) and the G1 MSM for U.  Locating the bad header of a rejected batch is the caller's (bisection). */
+/* host only: prod_k e(g1s[k], g2s[k]) == 1 (EIP-197's predicate), any count; identity inputs contribute 1.
+ * G1 off the curve -> KZG_ERR_G1_NOT_ON_CURVE, G2 off the twist -> KZG_ERR_G2_TAU_NOT_ON_CURVE (every G1 input is tested first). */
+int32_t kzg_pairings_product_verify(const uint64_t* g1s_xy, const uint64_t* g2s, size_t count, int32_t* out_ok);
+/* n wire points on the device: each the identity, or on the twist AND in the order-r subgroup.  The first that is not ->
+ * KZG_ERR_NOT_ON_CURVE with *bad_index (may be NULL).  n = 0 -> KZG_OK; n > 2^28 -> KZG_ERR_TOO_LARGE.  Synchronous, slot 0. */
+int32_t kzg_g2_check_subgroup(kzg_ctx* ctx, const uint64_t* g2_mont, size_t n_points, uint64_t* bad_index);
+/* host only: the count + 1 weights of a header batch (r_0 .. r_(count-1), rho), each below 2^128, as Fr wire words.  Two levels, item
+ * hashes on the host pool, both tags 24 bytes:
+ *   d_i  = SHA-256("KZGBN254_HEADERITEM__V1_" || u64be(claimed_len_i) || ark-compressed C_i || g2bytes(C2_i) || g2bytes(pi2_i))
+ *   seed = SHA-256("KZGBN254_HEADERBATCH_V1_" || u64be(count) || u64be(n_shifts) || n_shifts x (u64be(len) || ark-compressed shift) || d_0 .. d_(count-1))
+ *   r_i  = the first 16 bytes, read big-endian, of SHA-256(seed || u64be(i));  rho = the same with index `count`
+ * g2bytes = be32(x.c0) || be32(x.c1) || be32(y.c0) || be32(y.c1) on canonical integers, the identity 128 zero bytes.  Nothing is
+ * validated here. */
+int32_t kzg_compute_header_batch_weights(const uint64_t* commitments_xy, const uint64_t* length_commitments, const uint64_t* length_proofs,
+                                         const uint64_t* claimed_lens, size_t count, const uint64_t* shift_lens,
+                                         const uint64_t* g1_tau_shifts_xy, size_t n_shifts, uint64_t* out_weights_mont);
+/* shift_lens[g]: distinct powers of two, g1_tau_shifts_xy[g] = [tau^(N - shift_lens[g])]_1; header i belongs to the group whose length
+ * is claimed_lens[i].  weights_mont = NULL: the weights above; else (count + 1) x 4 u64, any Fr values (the chains run over the bit
+ * length of the largest r_i).  Errors, all checked before the equation, in this order:
+ *   1. a null pointer with count > 0, n_shifts = 0 with count > 0, n_shifts > 64, a duplicate shift_lens entry -> KZG_ERR_INVALID_ARG;
+ *   2. a shift_lens or claimed_lens entry that is not a power of two -> KZG_ERR_NOT_POWER_OF_TWO;
+ *   3. a claimed length that is not in shift_lens -> KZG_ERR_INVALID_ARG with *bad_index = i;
+ *   4. count > 2^20 -> KZG_ERR_TOO_LARGE;
+ *   5. a commitment or a shift off the curve -> KZG_ERR_G1_NOT_ON_CURVE (commitments first; a shift reports its position in the list);
+ *   6. a G2 input off the twist -> KZG_ERR_G2_TAU_NOT_ON_CURVE;
+ *   7. a G2 input outside the order-r subgroup -> KZG_ERR_NOT_ON_CURVE.
+ * 5-7 set *bad_index (may be NULL) to the header's index, the smallest one, C2 tested in front of pi2.  count = 0 -> *out_ok = 1.  A
+ * failed equation is *out_ok = 0 with KZG_OK.  Identity C, C2 and pi2 (the zero polynomial) form a valid header.  Synchronous, slot
+ * 0 (KZG_ERR_INVALID_ARG while a _begin on slot 0 is in flight); the context is usable after any error.  KZG_VB_TRACE=1 prints the
+ * phase times on stderr. */
+int32_t kzg_verify_length_proof_batch(kzg_ctx* ctx, const uint64_t* commitments_xy, const uint64_t* length_commitments,
+                                      const uint64_t* length_proofs, const uint64_t* claimed_lens, size_t count,
+                                      const uint64_t* shift_lens, const uint64_t* g1_tau_shifts_xy, size_t n_shifts,
+                                      const uint64_t* weights_mont /* NULL: derived */, int32_t* out_ok, uint64_t* bad_index);
 /* n_points gnark-compressed G2 points (64 bytes each: X.A1 || X.A0 big-endian, top two bits of the first byte 0b10 = the smaller y,
  * 0b11 = the larger; the format of the reference's g2.point.powerOf2) -> wire points, on the library's host thread pool.  Flag bits
  * not 0b10 / 0b11 or a coordinate not below the modulus -> KZG_ERR_DESERIALIZE; no point of that x on the twist, a point outside the

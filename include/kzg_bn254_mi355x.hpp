@@ -19,6 +19,7 @@
 #include <cstdint>
 #include <cstring>
 #include <fstream>
+#include <map>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -624,6 +625,13 @@ inline bool pairings_verify(const G1Affine& a1, const G2Affine& a2, const G1Affi
     detail::check(kzg_pairings_verify(a1.xy.data(), a2.w.data(), b1.xy.data(), b2.w.data(), &ok));
     return ok != 0;
 }
+// every point the identity, or on the twist and in the order-r subgroup (kzg_g2_check_subgroup: one 63-bit chain per point on the GPU)
+inline void check_g2_subgroup(const std::vector<G2Affine>& points, const Context& ctx = Context::default_context()) {
+    uint64_t bad = 0;
+    const int32_t rc = kzg_g2_check_subgroup(ctx.handle(), points.empty() ? nullptr : points.data()->w.data(), points.size(), &bad);
+    if (rc == KZG_ERR_NOT_ON_CURVE) throw KzgError::NotOnCurveError("G2 point " + std::to_string(bad) + " not on curve or not in the correct subgroup");
+    detail::check(rc, ctx.handle());
+}
 // helpers.rs:151-173: y > (p - 1) / 2, y given in Montgomery form
 inline bool lexicographically_largest(const std::array<uint64_t, 4>& y_mont) {
     using u128 = unsigned __int128;
@@ -723,6 +731,49 @@ inline bool verify_multiproof_batch(const std::vector<G1Affine>& commitments, co
                                               proofs.empty() ? nullptr : proofs.data()->xy.data(), count, n, chunk_len,
                                               r_powers && count ? r_powers->data()->limbs.data() : nullptr, g2_tau_l ? g2_tau_l->w.data() : nullptr, &ok),
                   srs.context().handle());
+    return ok != 0;
+}
+// prod_k e(g1s[k], g2s[k]) == 1 for any number of pairs (kzg_pairings_product_verify, host; EIP-197's predicate)
+inline bool pairings_product_verify(const std::vector<G1Affine>& g1s, const std::vector<G2Affine>& g2s) {
+    if (g1s.size() != g2s.size()) throw KzgError::GenericError("length's of the input are not the same");
+    int32_t ok = 0;
+    detail::check(kzg_pairings_product_verify(g1s.empty() ? nullptr : g1s.data()->xy.data(), g2s.empty() ? nullptr : g2s.data()->w.data(), g1s.size(), &ok));
+    return ok != 0;
+}
+// {d: [tau^(srs_order - d)]_1} for the claimed lengths in `lens`, read from a device-resident G1 SRS: the `shifts` of verify_length_proof_batch
+inline std::map<uint64_t, G1Affine> header_shifts(const SRS& srs, uint64_t srs_order, const std::vector<uint64_t>& lens) {
+    std::map<uint64_t, G1Affine> out;
+    for (uint64_t d : lens) {
+        if (out.count(d)) continue;
+        if (d == 0 || d > srs_order || srs_order - d >= srs.len()) throw KzgError::GenericError("the SRS has no point tau^(srs_order - d)");
+        G1Affine pt;
+        detail::check(kzg_srs_download(srs.context().handle(), srs.handle(), srs_order - d, 1, pt.xy.data()), srs.context().handle());
+        out[d] = pt;
+    }
+    return out;
+}
+// `count` blob headers (C_i, C2_i, pi2_i, d_i) in one product of pairings (kzg_verify_length_proof_batch): on-twist and subgroup tests of
+// the G2 elements and the weighted sums on the GPU.  weights = nullptr derives them; else count + 1 values r_0 .. r_(count-1), rho.
+inline bool verify_length_proof_batch(const std::vector<G1Affine>& commitments, const std::vector<G2Affine>& length_commitments,
+                                      const std::vector<G2Affine>& length_proofs, const std::vector<uint64_t>& claimed_lens,
+                                      const std::map<uint64_t, G1Affine>& shifts, const std::vector<Fr>* weights = nullptr,
+                                      const Context& ctx = Context::default_context()) {
+    const size_t count = commitments.size();
+    if (!(length_commitments.size() == count && length_proofs.size() == count && claimed_lens.size() == count && (!weights || weights->size() == count + 1)))
+        throw KzgError::GenericError("length's of the input are not the same");
+    std::vector<uint64_t> shift_lens;
+    std::vector<G1Affine> shift_pts;
+    for (const auto& kv : shifts) { shift_lens.push_back(kv.first); shift_pts.push_back(kv.second); }
+    int32_t ok = 0;
+    uint64_t bad = 0;
+    const int32_t rc = kzg_verify_length_proof_batch(ctx.handle(), count ? commitments.data()->xy.data() : nullptr, count ? length_commitments.data()->w.data() : nullptr,
+                                                     count ? length_proofs.data()->w.data() : nullptr, count ? claimed_lens.data() : nullptr, count,
+                                                     shift_lens.empty() ? nullptr : shift_lens.data(), shift_pts.empty() ? nullptr : shift_pts.data()->xy.data(),
+                                                     shift_lens.size(), weights ? weights->data()->limbs.data() : nullptr, &ok, &bad);
+    if (rc == KZG_ERR_G1_NOT_ON_CURVE) throw KzgError::NotOnCurveError("G1 point " + std::to_string(bad) + " not on curve");
+    if (rc == KZG_ERR_G2_TAU_NOT_ON_CURVE) throw KzgError::NotOnCurveError("G2 point of header " + std::to_string(bad) + " not on curve");
+    if (rc == KZG_ERR_NOT_ON_CURVE) throw KzgError::NotOnCurveError("G2 point of header " + std::to_string(bad) + " not in correct subgroup");
+    detail::check(rc, ctx.handle());
     return ok != 0;
 }
 }  // namespace verify

@@ -181,6 +181,10 @@ PROTOTYPES = {
     "kzg_commit_g2_eval_form": (i32, [vp, vp, u64p, sz, u64p, u8p]),
     "kzg_commit_with_length_proof": (i32, [vp, vp, vp, vp, C.c_uint64, C.c_uint64, u64p, sz, C.c_uint64, u64p, u64p, u64p]),
     "kzg_verify_length_proof": (i32, [u64p, u64p, u64p, u64p, C.POINTER(i32)]),
+    "kzg_pairings_product_verify": (i32, [u64p, u64p, sz, C.POINTER(i32)]),
+    "kzg_g2_check_subgroup": (i32, [vp, u64p, sz, C.POINTER(C.c_uint64)]),
+    "kzg_compute_header_batch_weights": (i32, [u64p, u64p, u64p, u64p, sz, u64p, u64p, sz, u64p]),
+    "kzg_verify_length_proof_batch": (i32, [vp, u64p, u64p, u64p, u64p, sz, u64p, u64p, sz, u64p, C.POINTER(i32), C.POINTER(C.c_uint64)]),
     "kzg_g2_decompress_be": (i32, [u8p, sz, u64p, C.POINTER(C.c_uint64)]),
 }
 

@@ -1,13 +1,18 @@
 // capi_g2.hip — the G2 part of the C-ABI (include/kzg_bn254_mi355x.h, "G2 on the device"): the device-resident G2 SRS handle, the G2
 // MSM over caller bases or a handle, G2 commitments, the blob header (commitment, length commitment, length proof) in one call, its
-// verification by two pairing checks, and the host decoder of gnark-compressed G2 points.  The kernels and their driver are
-// g2msm.hip; every argument check here runs before any launch.
+// verification by two pairing checks, the batched verification of headers (subgroup test and weighted sums on the device, one
+// product of pairings), and the host decoder of gnark-compressed G2 points.  The kernels and their drivers are g2msm.hip and
+// g2batch.hip; every argument check here runs before any launch.
 #include "engine.h"
 #include <new>
 #include "field29.h"
 #include "host_g2_decode.h"
+#include "host_fiat_shamir.h"
 
+#include <algorithm>
 #include <atomic>
+#include <chrono>
+#include <cstdio>
 #include <string>
 #include <vector>
 #include <cstring>
@@ -227,6 +232,200 @@ int32_t kzg_verify_length_proof(const uint64_t commitment_xy[8], const uint64_t 
     const G2 g2 = g2_generator();
     // e(C, G2) = e(G1, C2): the two commitments hold the same polynomial; e([tau^(N-d)]_1, C2) = e(G1, pi2): pi2 is its shift by N - d
     *out_ok = pairings_verify(c, g2, g1, c2) && pairings_verify(shift, c2, g1, pi2) ? 1 : 0;
+    return KZG_OK;
+}
+
+// ---- batches of blob headers ---------------------------------------------------------------------------------------------------
+int32_t kzg_pairings_product_verify(const uint64_t* g1s_xy, const uint64_t* g2s, size_t count, int32_t* out_ok) {
+    if (!out_ok || (count && (!g1s_xy || !g2s)) || count > ((size_t)1 << 30)) return KZG_ERR_INVALID_ARG;
+    using namespace kzg_host;
+    std::vector<G1> ps(count);
+    std::vector<G2> qs(count);
+    for (size_t k = 0; k < count; ++k) { ps[k] = g1_from_wire(g1s_xy + 8 * k); if (!g1_on_curve(ps[k])) return KZG_ERR_G1_NOT_ON_CURVE; }
+    for (size_t k = 0; k < count; ++k) { qs[k] = g2_from_wire(g2s + 16 * k); if (!g2_on_curve(qs[k])) return KZG_ERR_G2_TAU_NOT_ON_CURVE; }
+    *out_ok = pairings_product_is_one(ps.data(), qs.data(), (int)count, host_parallel_for) ? 1 : 0;
+    return KZG_OK;
+}
+
+int32_t kzg_g2_check_subgroup(kzg_ctx* ctx, const uint64_t* g2_mont, size_t n_points, uint64_t* bad_index) {
+    if (!ctx || (n_points && !g2_mont)) return KZG_ERR_INVALID_ARG;
+    if (n_points > ((size_t)1 << 28)) return KZG_ERR_TOO_LARGE;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (slot0_busy(ctx)) return KZG_ERR_INVALID_ARG;
+    if (n_points == 0) return KZG_OK;
+    KZG_HIP_TRY(ctx, ctx->msm.bases.reserve(n_points * 128));
+    int64_t off_twist = -1, outside = -1;
+    int32_t rc = g2_upload_points(ctx, g2_mont, n_points, ctx->msm.bases.as<uint4>(), &off_twist);
+    if (rc != KZG_OK) return rc;
+    // the chain has no meaning off the twist: the points in front of the first such point are tested, and the smaller index is reported
+    rc = g2_subgroup_check(ctx, ctx->msm.bases.as<uint4>(), off_twist >= 0 ? (size_t)off_twist : n_points, &outside);
+    if (rc != KZG_OK) return rc;
+    const int64_t bad = outside >= 0 ? outside : off_twist;
+    if (bad < 0) return KZG_OK;
+    if (bad_index) *bad_index = (uint64_t)bad;
+    ctx->last_error = "kzg_g2_check_subgroup: point " + std::to_string(bad) + (outside >= 0 ? " is not in the order-r subgroup" : " is not on the twist");
+    return KZG_ERR_NOT_ON_CURVE;
+}
+
+int32_t kzg_compute_header_batch_weights(const uint64_t* commitments_xy, const uint64_t* length_commitments, const uint64_t* length_proofs,
+                                         const uint64_t* claimed_lens, size_t count, const uint64_t* shift_lens,
+                                         const uint64_t* g1_tau_shifts_xy, size_t n_shifts, uint64_t* out_weights_mont) {
+    if (!out_weights_mont) return KZG_ERR_INVALID_ARG;
+    if (count && (!commitments_xy || !length_commitments || !length_proofs || !claimed_lens)) return KZG_ERR_INVALID_ARG;
+    if (n_shifts && (!shift_lens || !g1_tau_shifts_xy)) return KZG_ERR_INVALID_ARG;
+    kzg_host::header_batch_weights_host(commitments_xy, length_commitments, length_proofs, claimed_lens, count, shift_lens, g1_tau_shifts_xy, n_shifts,
+                                        out_weights_mont, host_parallel_for);
+    return KZG_OK;
+}
+
+int32_t kzg_verify_length_proof_batch(kzg_ctx* ctx, const uint64_t* commitments_xy, const uint64_t* length_commitments,
+                                      const uint64_t* length_proofs, const uint64_t* claimed_lens, size_t count,
+                                      const uint64_t* shift_lens, const uint64_t* g1_tau_shifts_xy, size_t n_shifts,
+                                      const uint64_t* weights_mont, int32_t* out_ok, uint64_t* bad_index) {
+    using namespace kzg_host;
+    using Clock = std::chrono::steady_clock;
+    auto ms = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    // 1. pointers and the shape of the shift list
+    if (!ctx || !out_ok) return KZG_ERR_INVALID_ARG;
+    if (count && (!commitments_xy || !length_commitments || !length_proofs || !claimed_lens || !shift_lens || !g1_tau_shifts_xy || n_shifts == 0)) return KZG_ERR_INVALID_ARG;
+    if (n_shifts > 64 || (n_shifts && (!shift_lens || !g1_tau_shifts_xy))) return KZG_ERR_INVALID_ARG;
+    for (size_t g = 0; g < n_shifts; ++g)
+        for (size_t h = 0; h < g; ++h) if (shift_lens[g] == shift_lens[h]) return KZG_ERR_INVALID_ARG;
+    // 2. powers of two
+    for (size_t g = 0; g < n_shifts; ++g) if (!is_pow2(shift_lens[g])) return KZG_ERR_NOT_POWER_OF_TWO;
+    for (size_t i = 0; i < count; ++i) if (!is_pow2(claimed_lens[i])) return KZG_ERR_NOT_POWER_OF_TWO;
+    // 3. every claimed length has its shift
+    int8_t group_of_log[64];
+    memset(group_of_log, -1, sizeof group_of_log);
+    for (size_t g = 0; g < n_shifts; ++g) group_of_log[__builtin_ctzll(shift_lens[g])] = (int8_t)g;
+    std::vector<uint8_t> group(count);
+    for (size_t i = 0; i < count; ++i) {
+        const int8_t g = group_of_log[__builtin_ctzll(claimed_lens[i])];
+        if (g < 0) { if (bad_index) *bad_index = (uint64_t)i; return KZG_ERR_INVALID_ARG; }
+        group[i] = (uint8_t)g;
+    }
+    // 4. size
+    if (count > ((size_t)1 << 20)) return KZG_ERR_TOO_LARGE;
+    if (count == 0) { *out_ok = 1; return KZG_OK; }
+    const auto t0 = Clock::now();
+    // 5. G1 inputs on the curve: the commitments (the header's index), then the shifts (the shift's position in the list)
+    {
+        std::atomic<uint64_t> first_bad{UINT64_MAX};
+        const size_t per = 256, jobs = (count + per - 1) / per;
+        auto body = [&](size_t j) {
+            for (size_t i = j * per; i < std::min(count, (j + 1) * per); ++i) {
+                if (g1_on_curve(g1_from_wire(commitments_xy + 8 * i))) continue;
+                uint64_t cur = first_bad.load();
+                while (i < cur && !first_bad.compare_exchange_weak(cur, (uint64_t)i)) {}
+                return;
+            }
+        };
+        if (jobs > 1) host_parallel_for(jobs, body); else body(0);
+        if (first_bad.load() != UINT64_MAX) { if (bad_index) *bad_index = first_bad.load(); return KZG_ERR_G1_NOT_ON_CURVE; }
+    }
+    std::vector<G1> shifts(n_shifts);
+    for (size_t g = 0; g < n_shifts; ++g) {
+        shifts[g] = g1_from_wire(g1_tau_shifts_xy + 8 * g);
+        if (!g1_on_curve(shifts[g])) { if (bad_index) *bad_index = (uint64_t)g; return KZG_ERR_G1_NOT_ON_CURVE; }
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (slot0_busy(ctx)) return KZG_ERR_INVALID_ARG;
+    // 6. G2 inputs on the twist: uploaded as C2_0, pi2_0, C2_1, pi2_1, ..: point j belongs to header j / 2, C2 in front of pi2
+    const size_t n_points = 2 * count;
+    std::vector<uint64_t> inter(n_points * 16);
+    for (size_t i = 0; i < count; ++i) { memcpy(inter.data() + 32 * i, length_commitments + 16 * i, 128); memcpy(inter.data() + 32 * i + 16, length_proofs + 16 * i, 128); }
+    KZG_HIP_TRY(ctx, ctx->msm.bases.reserve(n_points * 128));
+    const uint4* d_points = ctx->msm.bases.as<uint4>();
+    int64_t bad = -1;
+    int32_t rc = g2_upload_points(ctx, inter.data(), n_points, ctx->msm.bases.as<uint4>(), &bad);
+    if (rc != KZG_OK) return rc;
+    if (bad >= 0) {
+        if (bad_index) *bad_index = (uint64_t)bad / 2;
+        ctx->last_error = std::string("kzg_verify_length_proof_batch: the length ") + (bad & 1 ? "proof" : "commitment") + " of header " + std::to_string(bad / 2) + " is not on the twist";
+        return KZG_ERR_G2_TAU_NOT_ON_CURVE;
+    }
+    const auto t1 = Clock::now();
+    // 7. G2 inputs in the order-r subgroup
+    rc = g2_subgroup_check(ctx, d_points, n_points, &bad);
+    if (rc != KZG_OK) return rc;
+    if (bad >= 0) {
+        if (bad_index) *bad_index = (uint64_t)bad / 2;
+        ctx->last_error = std::string("kzg_verify_length_proof_batch: the length ") + (bad & 1 ? "proof" : "commitment") + " of header " + std::to_string(bad / 2) + " is not in the order-r subgroup";
+        return KZG_ERR_NOT_ON_CURVE;
+    }
+    const auto t2 = Clock::now();
+    // the weights r_0 .. r_(count-1), rho: wire form for the G1 MSM, canonical words for the G2 chains
+    std::vector<uint64_t> derived;
+    if (!weights_mont) {
+        derived.resize((count + 1) * 4);
+        header_batch_weights_host(commitments_xy, length_commitments, length_proofs, claimed_lens, count, shift_lens, g1_tau_shifts_xy, n_shifts, derived.data(), host_parallel_for);
+        weights_mont = derived.data();
+    }
+    std::vector<uint64_t> canon((count + 1) * 4);
+    int bits = 0;
+    for (size_t i = 0; i <= count; ++i) {
+        uint64_t* k = canon.data() + 4 * i;
+        fr_wire_to_canonical(weights_mont + 4 * i, k);
+        if (i == count) break;                                      // rho multiplies on the host
+        for (int w = 3; w >= 0; --w) if (k[w]) { bits = std::max(bits, 64 * w + 64 - __builtin_clzll(k[w])); break; }
+    }
+    // lanes: the C2 of every group in the list's order, each group padded to whole tiles of 64, then every pi2
+    std::vector<size_t> group_count(n_shifts, 0), tile_begin(n_shifts + 2, 0);
+    for (size_t i = 0; i < count; ++i) ++group_count[group[i]];
+    for (size_t g = 0; g < n_shifts; ++g) tile_begin[g + 1] = tile_begin[g] + (group_count[g] + 63) / 64;
+    tile_begin[n_shifts + 1] = tile_begin[n_shifts] + (count + 63) / 64;
+    const size_t tiles = tile_begin[n_shifts + 1];
+    std::vector<uint32_t> lanes(tiles * 64, 0xFFFFFFFFu);
+    {
+        std::vector<size_t> next(n_shifts);
+        for (size_t g = 0; g < n_shifts; ++g) next[g] = tile_begin[g] * 64;
+        for (size_t i = 0; i < count; ++i) { lanes[next[group[i]]++] = (uint32_t)(2 * i); lanes[tile_begin[n_shifts] * 64 + i] = (uint32_t)(2 * i + 1); }
+    }
+    std::vector<uint64_t> tile_sums(tiles * 16);
+    rc = g2_weighted_tile_sums(ctx, d_points, n_points, lanes.data(), lanes.size(), reinterpret_cast<const uint32_t*>(canon.data()), count, 1, bits, tile_sums.data());
+    if (rc != KZG_OK) return rc;
+    const auto t3 = Clock::now();
+    // U = sum r_i C_i: the variable-base G1 MSM of the batched verifiers
+    uint64_t u_xy[8];
+    uint8_t u_inf = 0;
+    rc = msm_g1_batch_locked(ctx, commitments_xy, weights_mont, count, 1, u_xy, &u_inf, nullptr);
+    if (rc != KZG_OK) return rc;
+    const auto t4 = Clock::now();
+    // W_g, Pi: the tiles of one sum added in Jacobian coordinates, one inversion per sum
+    auto sum_tiles = [&](size_t lo, size_t hi) {
+        G2Jac acc; acc.inf = true; acc.X = {fq_zero(), fq_zero()}; acc.Y = acc.X; acc.Z = acc.X;
+        for (size_t t = lo; t < hi; ++t) acc = g2j_madd(acc, g2_from_wire(tile_sums.data() + 16 * t));
+        if (acc.inf) return g2_inf();
+        const Fq2 zi = inv(acc.Z), zi2 = sqr(zi);
+        G2 r; r.inf = false;
+        r.x = mul(acc.X, zi2);
+        r.y = mul(acc.Y, mul(zi2, zi));
+        return r;
+    };
+    std::vector<G2> W(n_shifts);
+    G2 S = g2_inf();
+    for (size_t g = 0; g < n_shifts; ++g) { W[g] = sum_tiles(tile_begin[g], tile_begin[g + 1]); S = g2_add(S, W[g]); }
+    const G2 Pi = sum_tiles(tile_begin[n_shifts], tile_begin[n_shifts + 1]);
+    // e(U, G2) e(-G1, S + [rho]Pi) prod_g e([rho]T_g, W_g) == 1
+    const uint64_t* rho = canon.data() + 4 * count;
+    std::vector<G1> ps;
+    std::vector<G2> qs;
+    G1 g1; g1.x = FQ_ONE; g1.y = FQ_TWO; g1.inf = false;
+    G1 U = g1_from_wire(u_xy);
+    if (u_inf) U.inf = true;
+    ps.push_back(U); qs.push_back(g2_generator());
+    ps.push_back(g1_neg(g1)); qs.push_back(g2_add(S, g2_mul(Pi, rho)));
+    for (size_t g = 0; g < n_shifts; ++g) {
+        if (group_count[g] == 0) continue;
+        ps.push_back(g1_mul(shifts[g], rho)); qs.push_back(W[g]);
+    }
+    *out_ok = pairings_product_is_one(ps.data(), qs.data(), (int)ps.size(), host_parallel_for) ? 1 : 0;
+    if (opts().vb_trace) {
+        fprintf(stderr, "  verify_length_proof_batch count=%zu groups=%zu bits=%d: checks + upload + on-twist %.3f ms, subgroup %.3f ms, weights + weighted sums %.3f ms, G1 MSM %.3f ms, host sums + pairing %.3f ms\n",
+                count, n_shifts, bits, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4), ms(t4, Clock::now()));
+    }
     return KZG_OK;
 }
 

@@ -285,4 +285,17 @@ KZG_HD void g2_to_wire(uint32_t out[64], const G2Xyzz& v) {
     fq2_to_wire(out + 48, v.zzz);
 }
 
+#if defined(__HIPCC__)
+// a stored-form XYZZ value from another lane of the wave: lane + src_lane (down) or lane src_lane (g2msm.hip, g2batch.hip)
+__device__ __forceinline__ void g2_shfl(G2Xyzz& r, const G2Xyzz& v, int src_lane, bool down) {
+    const Fq* s[8] = {&v.x.c0, &v.x.c1, &v.y.c0, &v.y.c1, &v.zz.c0, &v.zz.c1, &v.zzz.c0, &v.zzz.c1};
+    Fq* d[8] = {&r.x.c0, &r.x.c1, &r.y.c0, &r.y.c1, &r.zz.c0, &r.zz.c1, &r.zzz.c0, &r.zzz.c1};
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+#pragma unroll
+        for (int j = 0; j < NL; ++j) d[q]->l[j] = down ? __shfl_down(s[q]->l[j], src_lane, 64) : __shfl(s[q]->l[j], src_lane, 64);
+    r.inf = (down ? __shfl_down((int)v.inf, src_lane, 64) : __shfl((int)v.inf, src_lane, 64)) != 0;
+}
+#endif
+
 }  // namespace kzg

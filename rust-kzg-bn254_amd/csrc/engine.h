@@ -277,6 +277,13 @@ int32_t g2_msm_run(kzg_ctx* ctx, const uint4* const* d_points, uint32_t nb, cons
 int32_t g2_upload_points(kzg_ctx* ctx, const uint64_t* g2_mont, size_t n, uint4* d_out, int64_t* bad);
 int32_t g2_generate_points(kzg_ctx* ctx, const uint64_t tau_mont[4], uint64_t first_power, size_t n, uint4* d_out);
 int32_t g2_download_points(kzg_ctx* ctx, const uint4* d_points, size_t n, uint64_t* out_g2_mont);
+// g2batch.hip: per-lane G2 chains over device-format points (g2_chain.h).  *bad = the smallest index of a point that is neither the identity nor in
+// the order-r subgroup, or -1 (the points are on the twist: g2_upload_points checks that)
+int32_t g2_subgroup_check(kzg_ctx* ctx, const uint4* d_points, size_t n, int64_t* bad);
+// Lane t multiplies point lanes[t] (0xFFFFFFFF: an idle lane) by weight lanes[t] >> weight_shift (8 canonical u32 words each, the low `bits` bits read) and
+// every tile of 64 lanes is summed: out_tiles_g2 = n_lanes / 64 affine wire points.  n_lanes is a multiple of 64.
+int32_t g2_weighted_tile_sums(kzg_ctx* ctx, const uint4* d_points, size_t n_points, const uint32_t* lanes, size_t n_lanes, const uint32_t* weights_canonical,
+                              size_t n_weights, uint32_t weight_shift, int bits, uint64_t* out_tiles_g2);
 int32_t srs_decompress(kzg_ctx* ctx, const uint8_t* bytes, size_t n, uint4* d_points, uint32_t* err_kind, uint32_t* err_index, bool ark_le = false);
 
 // KZG::g1_ifft: Lagrange-basis SRS of size n (n a power of two <= srs->n), affine wire points to the host / left on the device

@@ -77,15 +77,7 @@ k_g2_accumulate(const uint4* __restrict__ points, const uint32_t* __restrict__ s
 // -------------------------------------------------------------------------------------------------
 // 2. lane partials -> bucket sums
 // -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void g2_shfl(G2Xyzz& r, const G2Xyzz& v, int src_lane, bool down) {
-    const Fq* s[8] = {&v.x.c0, &v.x.c1, &v.y.c0, &v.y.c1, &v.zz.c0, &v.zz.c1, &v.zzz.c0, &v.zzz.c1};
-    Fq* d[8] = {&r.x.c0, &r.x.c1, &r.y.c0, &r.y.c1, &r.zz.c0, &r.zz.c1, &r.zzz.c0, &r.zzz.c1};
-#pragma unroll
-    for (int q = 0; q < 8; ++q)
-#pragma unroll
-        for (int j = 0; j < NL; ++j) d[q]->l[j] = down ? __shfl_down(s[q]->l[j], src_lane, 64) : __shfl(s[q]->l[j], src_lane, 64);
-    r.inf = (down ? __shfl_down((int)v.inf, src_lane, 64) : __shfl((int)v.inf, src_lane, 64)) != 0;
-}
+// (g2_shfl: curve_g2.h)
 // Bucket g of the G = W * B buckets is stored at a transposed position so that the reduction kernels, where lane t walks chunk t
 // (buckets t m .. t m + m - 1), read consecutive addresses across lanes.
 __device__ __forceinline__ size_t g2_bucket_pos(uint32_t g, uint32_t m, uint32_t n_chunks) { return (size_t)(g % m) * n_chunks + (g / m); }

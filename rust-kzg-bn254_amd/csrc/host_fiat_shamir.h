@@ -22,6 +22,8 @@ using ParallelFor = void (*)(size_t n, const std::function<void(size_t)>& job); 
 const char RC_BATCH_DOMAIN[] = "EIGENDA_RCKZGBATCH___V1_";       // primitives/src/consts.rs:11 (24 bytes)
 const char COSET_ITEM_DOMAIN[] = "KZGBN254_COSETITEM___V1_";     // 24 bytes each; this library's own transcript (the reference has no coset proofs)
 const char COSET_BATCH_DOMAIN[] = "KZGBN254_COSETBATCH__V1_";
+const char HEADER_ITEM_DOMAIN[] = "KZGBN254_HEADERITEM__V1_";    // 24 bytes each; this library's own transcript for batches of blob headers
+const char HEADER_BATCH_DOMAIN[] = "KZGBN254_HEADERBATCH_V1_";
 
 inline size_t next_pow2(size_t x) { size_t p = 1; while (p < x) p <<= 1; return p; }           // next_power_of_two(0) == 1
 inline size_t blob_padded_len(size_t len) { return next_pow2((len + 31) / 32); }               // elements of Blob::to_polynomial_eval_form
@@ -132,6 +134,74 @@ inline void multiproof_r_powers_host(const uint64_t* commitments, size_t n_commi
     };
     if (jobs > 1) parallel_for(jobs, body); else if (jobs == 1) body(0);
     hash_to_r_powers(data, count, out);
+}
+
+// G2 point as 128 bytes: be32(x.c0) || be32(x.c1) || be32(y.c0) || be32(y.c1) on canonical integers; the identity is 128 zero bytes
+inline void g2_serialize_be(const G2& p, uint8_t out[128]) {
+    memset(out, 0, 128);
+    if (p.inf) return;
+    const Fq one_plain = {{1, 0, 0, 0}};
+    const Fq* c[4] = {&p.x.c0, &p.x.c1, &p.y.c0, &p.y.c1};
+    for (int q = 0; q < 4; ++q) {
+        const Fq v = mul(*c[q], one_plain);                                             // Montgomery -> canonical
+        for (int i = 0; i < 4; ++i) put_u64be(out + 32 * q + 8 * i, v.l[3 - i]);
+    }
+}
+// The weights of a batch of blob headers (kzg_verify_length_proof_batch): count + 1 values below 2^128, wire form.  Two levels like
+// the coset transcript: d_i = SHA-256(item tag || u64be(len_i) || C_i || C2_i || pi2_i) on the host pool, seed = SHA-256(batch tag ||
+// u64be(count) || u64be(n_shifts) || n_shifts x (u64be(len) || shift) || d_0 .. d_(count-1)), and weight j = the first 16 bytes, read
+// big-endian, of SHA-256(seed || u64be(j)); j = count is rho, the weight between the two equations.
+inline void header_batch_weights_host(const uint64_t* commitments, const uint64_t* length_commitments, const uint64_t* length_proofs,
+                                      const uint64_t* claimed_lens, size_t count, const uint64_t* shift_lens, const uint64_t* shifts, size_t n_shifts,
+                                      uint64_t* out, ParallelFor parallel_for) {
+    const size_t head = 24 + 16 + 40 * n_shifts;
+    std::vector<uint8_t> data(head + 32 * count, 0);
+    memcpy(data.data(), HEADER_BATCH_DOMAIN, 24);
+    put_u64be(data.data() + 24, (uint64_t)count);
+    put_u64be(data.data() + 32, (uint64_t)n_shifts);
+    for (size_t g = 0; g < n_shifts; ++g) {
+        put_u64be(data.data() + 40 + 40 * g, shift_lens[g]);
+        g1_serialize_compressed_ark(g1_from_wire(shifts + 8 * g), data.data() + 48 + 40 * g);
+    }
+    const size_t per = 64, jobs = (count + per - 1) / per;
+    auto body = [&](size_t j) {
+        uint8_t item[24 + 8 + 32 + 128 + 128];
+        memcpy(item, HEADER_ITEM_DOMAIN, 24);
+        for (size_t i = j * per; i < std::min(count, (j + 1) * per); ++i) {
+            put_u64be(item + 24, claimed_lens[i]);
+            g1_serialize_compressed_ark(g1_from_wire(commitments + 8 * i), item + 32);
+            g2_serialize_be(g2_from_wire(length_commitments + 16 * i), item + 64);
+            g2_serialize_be(g2_from_wire(length_proofs + 16 * i), item + 192);
+            Sha256 sh;
+            sha256_init(sh);
+            sha256_update(sh, item, sizeof item);
+            sha256_final(sh, data.data() + head + 32 * i);
+        }
+    };
+    if (jobs > 1) parallel_for(jobs, body); else if (jobs == 1) body(0);
+    uint8_t seed[40];
+    {
+        Sha256 sh;
+        sha256_init(sh);
+        sha256_update(sh, data.data(), data.size());
+        sha256_final(sh, seed);
+    }
+    const size_t wjobs = (count + 1 + 255) / 256;
+    auto wbody = [&](size_t j) {
+        uint8_t msg[40], dig[32];
+        memcpy(msg, seed, 32);
+        for (size_t i = j * 256; i < std::min(count + 1, (j + 1) * 256); ++i) {
+            put_u64be(msg + 32, (uint64_t)i);
+            Sha256 sh;
+            sha256_init(sh);
+            sha256_update(sh, msg, 40);
+            sha256_final(sh, dig);
+            uint64_t w[4] = {0, 0, 0, 0};
+            for (int b = 0; b < 8; ++b) { w[1] = (w[1] << 8) | dig[b]; w[0] = (w[0] << 8) | dig[8 + b]; }
+            fr_mul(w, FR_R2, out + 4 * i);                                              // canonical (below 2^128 < r) -> Montgomery
+        }
+    };
+    if (wjobs > 1) parallel_for(wjobs, wbody); else wbody(0);
 }
 
 }  // namespace kzg_host

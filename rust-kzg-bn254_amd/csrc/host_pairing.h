@@ -11,8 +11,10 @@
 // and the one the library uses (shared projective Miller loop, (p^6-1)(p^2+1) easy part, base-p Straus hard part); the
 // self-check build compares them.
 #pragma once
+#include <functional>
 #include <system_error>
 #include <thread>
+#include <vector>
 #include "host_curve.h"
 #include "host_fr.h"           // Fr in wire form: product, sum, conversion to canonical integer words, the modulus
 #include "pairing_constants.h"
@@ -817,6 +819,40 @@ inline bool pairings_verify_tate(const G1& a1, const G2& a2, const G1& b1, const
 inline bool pairings_verify_reference(const G1& a1, const G2& a2, const G1& b1, const G2& b2) {
     Fq12 f = mul(miller_tate(a1, a2), miller_tate(g1_neg(b1), b2));
     return fq12_is_one(final_exponentiation(f));
+}
+
+// prod_k e(ps[k], qs[k]) == 1 for ANY number of pairs (EIP-197's predicate; pairs with an identity point contribute 1).
+// miller_ate_product takes at most 4 pairs, so the pairs are cut into chunks, the chunks' Miller values multiplied, and ONE final
+// exponentiation decides.  With a parallel-for (the library hands in its host pool) every pair is its own chunk: separate loops on
+// separate threads beat the shared loop (see pairings_verify); without one the chunks hold 4 pairs and run one after the other.
+// A degenerate addition step (a G2 input outside the order-r subgroup) -> false.
+using PairingParallelFor = void (*)(size_t n, const std::function<void(size_t)>& job);
+inline bool pairings_product_is_one(const G1* ps, const G2* qs, int count, PairingParallelFor parallel_for = nullptr) {
+    std::vector<G1> p1;
+    std::vector<G2> q2;
+    for (int k = 0; k < count; ++k) {
+        if (ps[k].inf || qs[k].inf) continue;
+        p1.push_back(ps[k]); q2.push_back(qs[k]);
+    }
+    const size_t m = p1.size();
+    if (m == 0) return true;
+    const size_t per = parallel_for && m > 1 ? 1 : 4, chunks = (m + per - 1) / per;
+    std::vector<Fq12> f(chunks);
+    std::vector<uint8_t> bad(chunks, 0);
+    auto body = [&](size_t c) {
+        bool d = false;
+        const size_t lo = c * per, len = m - lo < per ? m - lo : per;
+        f[c] = miller_ate_product(p1.data() + lo, q2.data() + lo, (int)len, &d);
+        bad[c] = d ? 1 : 0;
+    };
+    if (parallel_for && chunks > 1) parallel_for(chunks, body);
+    else for (size_t c = 0; c < chunks; ++c) body(c);
+    Fq12 prod = f[0];
+    for (size_t c = 0; c < chunks; ++c) {
+        if (bad[c]) return false;
+        if (c) prod = mul(prod, f[c]);
+    }
+    return fq12_is_one(final_exponentiation_x(prod));
 }
 
 }  // namespace kzg_host

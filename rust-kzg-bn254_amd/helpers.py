@@ -296,6 +296,20 @@ def example_validate_g2_point(point) -> None:
         raise G2GeneratorNotAcceptedError("G2 point cannot be the generator point")
 
 
+def check_g2_subgroup(points, ctx=None) -> None:
+    """Every point is the identity, or on the twist and in the order-r subgroup (`kzg_g2_check_subgroup`: one 63-bit chain per point
+    on the GPU).  NotOnCurveError names the first point that is not."""
+    ctx = ctx or _lib.default_context()
+    pts = np.ascontiguousarray(_lib.as_u64(points, 16)).reshape(-1, 16)
+    bad = C.c_uint64(0)
+    rc = _lib.load().kzg_g2_check_subgroup(ctx.handle, _lib.ptr(pts) if len(pts) else None, len(pts), C.byref(bad))
+    if rc == _lib.ERR_NOT_ON_CURVE:
+        raise NotOnCurveError("G2 point %d not on curve or not in the correct subgroup" % bad.value)
+    ctx.check_device(rc)
+    if rc != _lib.OK:
+        raise ValueError(_lib.status_message(rc))
+
+
 def compute_powers(base, count: int) -> np.ndarray:
     """helpers.rs:298-315: [base^0 .. base^(count-1)]."""
     b = fr_to_int(base)

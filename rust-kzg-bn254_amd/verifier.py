@@ -55,6 +55,93 @@ def verify_length_proof(commitment, length_commitment, length_proof, g1_tau_shif
     return bool(ok.value)
 
 
+def pairings_product_verify(g1s, g2s) -> bool:
+    """prod_k e(g1s[k], g2s[k]) == 1 for any number of pairs (`kzg_pairings_product_verify`, host; EIP-197's predicate).  Pairs with an
+    identity point contribute 1."""
+    p1 = np.ascontiguousarray(_lib.as_u64(g1s, 8)).reshape(-1, 8)
+    p2 = np.ascontiguousarray(_lib.as_u64(g2s, 16)).reshape(-1, 16)
+    if len(p1) != len(p2):
+        raise InvalidInputLength()
+    ok = _lib.i32(0)
+    rc = _lib.load().kzg_pairings_product_verify(_lib.ptr(p1) if len(p1) else None, _lib.ptr(p2) if len(p2) else None, len(p1), C.byref(ok))
+    if rc == _lib.ERR_G2_TAU_NOT_ON_CURVE:
+        raise NotOnCurveError("G2 point not on curve")
+    _raise_for(rc)
+    return bool(ok.value)
+
+
+def header_shifts(srs, srs_order: int, lens) -> dict:
+    """{d: [tau^(srs_order - d)]_1 for d in lens}, read from a device-resident G1 SRS (`kzg_srs_download` of point srs_order - d): the
+    `shifts` argument of verify_length_proof_batch.  d = srs_order gives the generator."""
+    out = {}
+    for d in sorted({int(d) for d in lens}):
+        if d <= 0 or d > srs_order or srs_order - d >= len(srs):
+            raise GenericError(f"the SRS of {len(srs)} points has no point tau^({srs_order} - {d})")
+        pt = np.zeros(8, dtype=np.uint64)
+        rc = _lib.load().kzg_srs_download(srs.ctx.handle, srs.handle, srs_order - d, 1, _lib.ptr(pt))
+        _raise_for(rc, srs.ctx)
+        out[d] = pt
+    return out
+
+
+def _header_args(commitments, length_commitments, length_proofs, claimed_lens, shifts):
+    c = np.ascontiguousarray(_lib.as_u64(commitments, 8)).reshape(-1, 8)
+    c2 = np.ascontiguousarray(_lib.as_u64(length_commitments, 16)).reshape(-1, 16)
+    p2 = np.ascontiguousarray(_lib.as_u64(length_proofs, 16)).reshape(-1, 16)
+    lens = np.ascontiguousarray([int(d) for d in claimed_lens], dtype=np.uint64)
+    if not (len(c) == len(c2) == len(p2) == len(lens)):
+        raise InvalidInputLength()
+    shift_lens = np.ascontiguousarray([int(d) for d in shifts], dtype=np.uint64)
+    shift_pts = np.ascontiguousarray([_lib.as_u64(shifts[d], 0).reshape(8) for d in shifts], dtype=np.uint64).reshape(-1, 8)
+    return c, c2, p2, lens, shift_lens, shift_pts
+
+
+def _opt(a):
+    return _lib.ptr(a) if a.size else None
+
+
+def compute_header_batch_weights(commitments, length_commitments, length_proofs, claimed_lens, shifts) -> np.ndarray:
+    """The count + 1 weights (r_0 .. r_(count-1), rho) verify_length_proof_batch derives: (count + 1, 4) Fr wire words, each below 2^128
+    (`kzg_compute_header_batch_weights`, host; the transcript is written out in the C header)."""
+    c, c2, p2, lens, shift_lens, shift_pts = _header_args(commitments, length_commitments, length_proofs, claimed_lens, shifts)
+    out = np.zeros((len(c) + 1, 4), dtype=np.uint64)
+    rc = _lib.load().kzg_compute_header_batch_weights(_opt(c), _opt(c2), _opt(p2), _opt(lens), len(c), _opt(shift_lens), _opt(shift_pts), len(shift_lens),
+                                                      _lib.ptr(out))
+    _raise_for(rc)
+    return out
+
+
+def verify_length_proof_batch(commitments, length_commitments, length_proofs, claimed_lens, shifts, weights=None, ctx=None) -> bool:
+    """`count` blob headers (C_i, C2_i, pi2_i, d_i) in ONE product of pairings (`kzg_verify_length_proof_batch`): the on-twist and
+    order-r subgroup tests of both G2 elements and the weighted sums run on the GPU.  shifts = {d: [tau^(N-d)]_1} for every claimed
+    length (header_shifts builds it from a G1 SRS); weights = None derives them from the transcript, else (count + 1, 4) Fr wire
+    words r_0 .. r_(count-1), rho.  False = the equation failed (some header is bad: bisect); NotOnCurveError names the first header
+    with an input off its curve or outside the subgroup."""
+    c, c2, p2, lens, shift_lens, shift_pts = _header_args(commitments, length_commitments, length_proofs, claimed_lens, shifts)
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(_lib.as_u64(weights, 4)).reshape(-1, 4)
+        if len(w) != len(c) + 1:
+            raise InvalidInputLength()
+    ctx = ctx or _lib.default_context()                             # (no context is created before the arguments pass)
+    ok = _lib.i32(0)
+    bad = C.c_uint64(0)
+    rc = _lib.load().kzg_verify_length_proof_batch(ctx.handle, _opt(c), _opt(c2), _opt(p2), _opt(lens), len(c), _opt(shift_lens), _opt(shift_pts),
+                                                   len(shift_lens), None if w is None else _lib.ptr(w), C.byref(ok), C.byref(bad))
+    if rc == _lib.ERR_G1_NOT_ON_CURVE:
+        raise NotOnCurveError("G1 point %d not on curve" % bad.value)
+    if rc == _lib.ERR_G2_TAU_NOT_ON_CURVE:
+        raise NotOnCurveError("G2 point of header %d not on curve" % bad.value)
+    if rc == _lib.ERR_NOT_ON_CURVE:
+        raise NotOnCurveError("G2 point of header %d not in correct subgroup" % bad.value)
+    if rc == _lib.ERR_NOT_POWER_OF_TWO:
+        raise GenericError("a claimed length is not a power of two")
+    if rc == _lib.ERR_INVALID_ARG and len(c) and len(shift_lens):
+        raise GenericError("a claimed length has no shift, a shift length is listed twice, more than 64 shifts, or slot 0 is in flight")
+    _raise_for(rc, ctx)
+    return bool(ok.value)
+
+
 def verify_blob_kzg_proof(blob, commitment, proof, g2_tau=None, ctx=None) -> bool:
     """verify.rs:76-98 as ONE call of the C-ABI (`kzg_verify_blob_kzg_proof`)."""
     ctx = ctx or _lib.default_context()
