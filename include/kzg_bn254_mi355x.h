@@ -769,6 +769,25 @@ int32_t kzg_verify_length_proof_batch(kzg_ctx* ctx, const uint64_t* commitments_
  * not 0b10 / 0b11 or a coordinate not below the modulus -> KZG_ERR_DESERIALIZE; no point of that x on the twist, a point outside the
  * order-r subgroup, or the generator itself -> KZG_ERR_NOT_ON_CURVE; *bad_index = the first such point (may be NULL).  Host only. */
 int32_t kzg_g2_decompress_be(const uint8_t* bytes, size_t n_points, uint64_t* out_g2_mont, uint64_t* bad_index);
+/* The same format decoded ON THE DEVICE (csrc/g2_decode.h, csrc/g2decode.hip: one lane per point, the square root in Fq2 with two
+ * exponentiations, the 63-bit subgroup chain of csrc/g2_chain.h): the host decoder above costs about a millisecond per point and thread.
+ * The bytes are staged in chunks through pinned memory the context already holds.  Per point, in this order: 1. flag bits not 0b10 /
+ * 0b11 -> KZG_ERR_DESERIALIZE; 2. a coordinate not below the modulus -> KZG_ERR_DESERIALIZE; 3. no point of that x on the twist ->
+ * KZG_ERR_NOT_ON_CURVE; 4. with KZG_G2_CHECK_SUBGROUP: not in the order-r subgroup -> KZG_ERR_NOT_ON_CURVE; 5. with
+ * KZG_G2_REJECT_GENERATOR: the generator itself -> KZG_ERR_NOT_ON_CURVE.  The status is that of the SMALLEST bad index, which goes to
+ * *bad_index (may be NULL).  Synchronous, slot 0. */
+#define KZG_G2_CHECK_SUBGROUP   1u
+#define KZG_G2_REJECT_GENERATOR 2u
+/* n_points compressed points (host bytes) -> wire points (host).  flags = 3: status, *bad_index and bits are those of
+ * kzg_g2_decompress_be on the same bytes; flags = 0: on the twist only.  Errors, in order: 1. a null pointer with n_points > 0, or a
+ * flag bit other than the two above -> KZG_ERR_INVALID_ARG; 2. n_points > 2^28 -> KZG_ERR_TOO_LARGE (nothing is allocated); 3. a
+ * kzg_*_begin in flight on slot 0 -> KZG_ERR_INVALID_ARG; 4. the points, as above: then out_g2_mont is not written.  n_points = 0 ->
+ * KZG_OK. */
+int32_t kzg_g2_decompress_be_device(kzg_ctx* ctx, const uint8_t* bytes, size_t n_points, uint32_t flags, uint64_t* out_g2_mont,
+                                    uint64_t* bad_index);
+/* The same into a device-resident G2 SRS, without a wire round trip.  Every point is subgroup-checked; the generator is accepted (a
+ * file of powers of tau starts with [tau^0]_2).  Errors as above (1. also: out NULL); on any error *out = NULL. */
+int32_t kzg_g2srs_load_compressed_be(kzg_ctx* ctx, const uint8_t* bytes, size_t n_points, kzg_g2srs** out, uint64_t* bad_index);
 
 #ifdef __cplusplus
 }

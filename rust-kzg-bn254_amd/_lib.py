@@ -40,6 +40,8 @@ ERR_TAU_EQUALS_Z = -19
 ERR_PEER = -20
 ERR_EXCHANGE_TIMEOUT = -21
 ERR_IO = -22
+G2_CHECK_SUBGROUP = 1                                            # KZG_G2_CHECK_SUBGROUP, KZG_G2_REJECT_GENERATOR of the header
+G2_REJECT_GENERATOR = 2
 
 u64p = C.POINTER(C.c_uint64)
 u8p = C.POINTER(C.c_uint8)
@@ -186,6 +188,8 @@ PROTOTYPES = {
     "kzg_compute_header_batch_weights": (i32, [u64p, u64p, u64p, u64p, sz, u64p, u64p, sz, u64p]),
     "kzg_verify_length_proof_batch": (i32, [vp, u64p, u64p, u64p, u64p, sz, u64p, u64p, sz, u64p, C.POINTER(i32), C.POINTER(C.c_uint64)]),
     "kzg_g2_decompress_be": (i32, [u8p, sz, u64p, C.POINTER(C.c_uint64)]),
+    "kzg_g2_decompress_be_device": (i32, [vp, u8p, sz, C.c_uint32, u64p, C.POINTER(C.c_uint64)]),
+    "kzg_g2srs_load_compressed_be": (i32, [vp, u8p, sz, C.POINTER(vp), C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

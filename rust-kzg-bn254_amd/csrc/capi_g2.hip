@@ -1,8 +1,8 @@
 // capi_g2.hip — the G2 part of the C-ABI (include/kzg_bn254_mi355x.h, "G2 on the device"): the device-resident G2 SRS handle, the G2
 // MSM over caller bases or a handle, G2 commitments, the blob header (commitment, length commitment, length proof) in one call, its
 // verification by two pairing checks, the batched verification of headers (subgroup test and weighted sums on the device, one
-// product of pairings), and the host decoder of gnark-compressed G2 points.  The kernels and their drivers are g2msm.hip and
-// g2batch.hip; every argument check here runs before any launch.
+// product of pairings), and the decoders of gnark-compressed G2 points: on the host, and on the device into wire points or a resident
+// handle.  The kernels and their drivers are g2msm.hip, g2batch.hip and g2decode.hip; every argument check here runs before any launch.
 #include "engine.h"
 #include <new>
 #include "field29.h"
@@ -444,6 +444,36 @@ int32_t kzg_g2_decompress_be(const uint8_t* bytes, size_t n_points, uint64_t* ou
     if (bad == UINT64_MAX) return KZG_OK;
     if (bad_index) *bad_index = bad;
     return status[bad];
+}
+
+int32_t kzg_g2_decompress_be_device(kzg_ctx* ctx, const uint8_t* bytes, size_t n_points, uint32_t flags, uint64_t* out_g2_mont, uint64_t* bad_index) {
+    if (!ctx || (n_points && (!bytes || !out_g2_mont)) || (flags & ~(KZG_G2_CHECK_SUBGROUP | KZG_G2_REJECT_GENERATOR))) return KZG_ERR_INVALID_ARG;
+    if (n_points > ((size_t)1 << 28)) return KZG_ERR_TOO_LARGE;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (slot0_busy(ctx)) return KZG_ERR_INVALID_ARG;
+    uint32_t bad = 0xFFFFFFFFu;
+    const int32_t rc = g2_decompress_run(ctx, bytes, n_points, flags, nullptr, out_g2_mont, &bad);
+    if (rc != KZG_OK) return rc;
+    return g2_decode_status(ctx, "kzg_g2_decompress_be_device", bad, bad_index);
+}
+
+int32_t kzg_g2srs_load_compressed_be(kzg_ctx* ctx, const uint8_t* bytes, size_t n_points, kzg_g2srs** out, uint64_t* bad_index) {
+    if (!ctx || !out || (n_points && !bytes)) return KZG_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (n_points > ((size_t)1 << 28)) return KZG_ERR_TOO_LARGE;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (slot0_busy(ctx)) return KZG_ERR_INVALID_ARG;
+    int32_t rc;
+    kzg_g2srs* s = new_handle(ctx, n_points, &rc);
+    if (!s) return rc;
+    uint32_t bad = 0xFFFFFFFFu;
+    rc = g2_decompress_run(ctx, bytes, n_points, KZG_G2_CHECK_SUBGROUP, s->d_points, nullptr, &bad);     // the generator is [tau^0]_2 of a file
+    if (rc == KZG_OK) rc = g2_decode_status(ctx, "kzg_g2srs_load_compressed_be", bad, bad_index);
+    if (rc != KZG_OK) { drop_handle(s); return rc; }
+    *out = s;
+    return KZG_OK;
 }
 
 }  // extern "C"

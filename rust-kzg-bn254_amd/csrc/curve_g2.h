@@ -179,12 +179,16 @@ KZG_HD void g2_add_into(G2Xyzz& acc, const G2Xyzz& v) {
     acc = r;
 }
 
+// the twist constant 3 / (9 + u), class F
+KZG_HD void g2_twist_b(Fq2& b) {
+    const uint32_t bw[16] = {0x77b802a8u, 0x3bf938e3u, 0x3633535du, 0x020b1b27u, 0x49755260u, 0x26b7edf0u, 0x4384a86du, 0x2514c632u,
+                             0xd1dcff67u, 0x38e7ecccu, 0x93ce0d3eu, 0x65f0b37du, 0x22ac00aau, 0xd749d0ddu, 0x4a688d4du, 0x0141b9ceu};   // wire form
+    fq2_from_wire(b, bw);
+}
 // y^2 == x^3 + 3 / (9 + u) for affine coordinates in class F
 KZG_HD bool g2_on_twist(const Fq2& x, const Fq2& y) {
-    const uint32_t bw[16] = {0x77b802a8u, 0x3bf938e3u, 0x3633535du, 0x020b1b27u, 0x49755260u, 0x26b7edf0u, 0x4384a86du, 0x2514c632u,
-                             0xd1dcff67u, 0x38e7ecccu, 0x93ce0d3eu, 0x65f0b37du, 0x22ac00aau, 0xd749d0ddu, 0x4a688d4du, 0x0141b9ceu};   // the twist constant, wire form
     Fq2 b, yy, xx, xxx, d;
-    fq2_from_wire(b, bw);
+    g2_twist_b(b);
     fq2_sqr(yy, y);                            // 4 * 4
     fq2_sqr(xx, x);
     fq2_mul(xxx, xx, x);                       // 4 * 4

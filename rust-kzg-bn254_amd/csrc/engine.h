@@ -284,6 +284,12 @@ int32_t g2_subgroup_check(kzg_ctx* ctx, const uint4* d_points, size_t n, int64_t
 // every tile of 64 lanes is summed: out_tiles_g2 = n_lanes / 64 affine wire points.  n_lanes is a multiple of 64.
 int32_t g2_weighted_tile_sums(kzg_ctx* ctx, const uint4* d_points, size_t n_points, const uint32_t* lanes, size_t n_lanes, const uint32_t* weights_canonical,
                               size_t n_weights, uint32_t weight_shift, int bits, uint64_t* out_tiles_g2);
+// g2decode.hip: n gnark-compressed points of the host decoded on the device (g2_decode.h; flags: KZG_G2_CHECK_SUBGROUP | KZG_G2_REJECT_GENERATOR) into
+// d_points (device format) or, with d_points == nullptr, as wire points to out_wire (host; written only when no point is refused).
+// *bad_word = index << 2 | kind (G2_BAD_* of g2_decode.h) of the smallest refused index, or 0xFFFFFFFF
+int32_t g2_decompress_run(kzg_ctx* ctx, const uint8_t* bytes, size_t n, uint32_t flags, uint4* d_points, uint64_t* out_wire, uint32_t* bad_word);
+// the status of such a bad word (KZG_OK for 0xFFFFFFFF), its index to *bad_index (may be null), a line for kzg_ctx_last_error
+int32_t g2_decode_status(kzg_ctx* ctx, const char* who, uint32_t bad_word, uint64_t* bad_index);
 int32_t srs_decompress(kzg_ctx* ctx, const uint8_t* bytes, size_t n, uint4* d_points, uint32_t* err_kind, uint32_t* err_index, bool ark_le = false);
 
 // KZG::g1_ifft: Lagrange-basis SRS of size n (n a power of two <= srs->n), affine wire points to the host / left on the device

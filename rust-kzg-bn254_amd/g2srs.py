@@ -58,14 +58,51 @@ class G2SRS:
             raise GenericError(_lib.status_message(rc))
         return out
 
+    @staticmethod
+    def _check_decoded(rc, bad, ctx):
+        if rc == _lib.ERR_DESERIALIZE:
+            raise DeserializationError("G2 point %d: not a compressed finite point below the modulus" % bad)
+        if rc == _lib.ERR_NOT_ON_CURVE:
+            raise NotOnCurveError("G2 point %d not on curve or not in the correct subgroup" % bad)
+        ctx.check_device(rc)
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+
+    @staticmethod
+    def decompress_device(data: bytes, check_subgroup: bool = True, reject_generator: bool = True, ctx=None) -> np.ndarray:
+        """gnark-compressed G2 points (64 bytes each) -> (n, 16) wire points, decoded on the GPU (`kzg_g2_decompress_be_device`).  With both
+        checks: the points, the exception and its index are those of `decompress`; with neither: only "on the twist"."""
+        if len(data) == 0 or len(data) % 64 != 0:
+            raise DeserializationError("a file of compressed G2 points is a positive multiple of 64 bytes")
+        ctx = ctx or _lib.default_context()
+        n = len(data) // 64
+        out = np.zeros((n, 16), dtype=np.uint64)
+        bad = C.c_uint64(0)
+        buf = np.frombuffer(data, dtype=np.uint8)
+        flags = (_lib.G2_CHECK_SUBGROUP if check_subgroup else 0) | (_lib.G2_REJECT_GENERATOR if reject_generator else 0)
+        rc = _lib.load().kzg_g2_decompress_be_device(ctx.handle, buf.ctypes.data_as(_lib.u8p), n, flags, _lib.ptr(out), C.byref(bad))
+        G2SRS._check_decoded(rc, bad.value, ctx)
+        return out
+
     @classmethod
-    def from_file(cls, path, points_to_load: int, first_power: int = 0, ctx=None):
-        """The first `points_to_load` gnark-compressed points of a file, decoded on the host pool and uploaded."""
+    def from_file(cls, path, points_to_load: int, first_power: int = 0, ctx=None, offset_points: int = 0):
+        """`points_to_load` gnark-compressed points of a file, from point `offset_points` on (a disperser loads the trailing window
+        [tau^(N-d) ..]_2 of the same file), decoded and subgroup-checked on the GPU straight into the handle
+        (`kzg_g2srs_load_compressed_be`).  The generator is accepted: a file of powers of tau starts with [tau^0]_2."""
+        ctx = ctx or _lib.default_context()
         with open(path, "rb") as f:
+            f.seek(64 * offset_points)
             data = f.read(64 * points_to_load)
         if len(data) != 64 * points_to_load:
             raise GenericError(f"Expected {points_to_load} points, only read {len(data) // 64}")
-        return cls.from_points(cls.decompress(data), first_power, ctx)
+        if len(data) == 0:
+            raise DeserializationError("a file of compressed G2 points is a positive multiple of 64 bytes")
+        h = C.c_void_p()
+        bad = C.c_uint64(0)
+        buf = np.frombuffer(data, dtype=np.uint8)
+        rc = _lib.load().kzg_g2srs_load_compressed_be(ctx.handle, buf.ctypes.data_as(_lib.u8p), points_to_load, C.byref(h), C.byref(bad))
+        cls._check_decoded(rc, bad.value, ctx)
+        return cls(h, points_to_load, ctx, first_power)
 
     @property
     def g2(self):
