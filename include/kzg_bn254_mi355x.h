@@ -27,7 +27,7 @@
  *   KZG_ROCTX=1                           roctx ranges around the host phases (rocprofv3 --marker-trace)
  *   KZG_NTT_TILE_LOG=10 / 11              one tile size of the Fr NTT at every transform size
  *   KZG_EXCHANGE_TIMEOUT_S, KZG_RCCL_LIB  the _rccl entries: seconds to wait for a collective (60); the RCCL to dlopen
- * Per-context settings are calls (kzg_ctx_set_msm_window, kzg_ctx_set_reduction_lanes).  Entry points marked MEASUREMENT ONLY below
+ * Per-context settings are calls (kzg_ctx_set_msm_window, kzg_ctx_set_reduction_lanes, kzg_ctx_set_transcript_device).  Entry points marked MEASUREMENT ONLY below
  * (kzg_ctx_set_profiling, kzg_ctx_get_msm_profile*, kzg_ctx_measure_valu_rates) exist for bench.py's roofline figures; a host binding can leave them out.
  */
 #ifndef KZG_BN254_MI355X_H
@@ -84,6 +84,16 @@ int32_t kzg_ctx_set_msm_window(kzg_ctx* ctx, int32_t c_bits, int32_t segment_len
 /* Lanes per point of the table-mode bucket-reduction kernels: 0 = automatic (lane quads for an MSM that runs alone, lane pairs
  * beside another MSM in flight), 2 = always pairs, 4 = always quads.  Results are identical; a test / measurement hook. */
 int32_t kzg_ctx_set_reduction_lanes(kzg_ctx* ctx, int32_t lanes);
+/* Where kzg_verify_multiproof_batch hashes the item digests of the weights it derives: 0 = automatic (on the device inside the envelope
+ * measured to win -- at least 4 096 items of at most 64 values and 2 MiB of values: profiles/fs_device.md --, on the host pool
+ * otherwise), 1 = always on the host, 2 = always on the device.
+ * Results are identical; a test / measurement hook.  Another mode -> KZG_ERR_INVALID_ARG. */
+int32_t kzg_ctx_set_transcript_device(kzg_ctx* ctx, int32_t mode);
+/* SHA-256 of `count` messages of row_len bytes each (msgs: count x row_len bytes, message i at msgs + i * row_len), one lane per message
+ * on the device (csrc/dev_sha256.h, csrc/fsdevice.hip): out_digests = count x 32 bytes.  Host buffers, synchronous.  count = 0 writes
+ * nothing; row_len = 0 hashes count empty messages.  A null pointer (msgs may be NULL when row_len = 0) -> KZG_ERR_INVALID_ARG;
+ * count > 2^28 or count * row_len > 2^31 -> KZG_ERR_TOO_LARGE. */
+int32_t kzg_sha256_rows(kzg_ctx* ctx, const uint8_t* msgs, size_t row_len, size_t count, uint8_t* out_digests);
 /* MEASUREMENT ONLY (bench.py's roofline): when enabled, every MSM launch is bracketed phase by phase with HIP events on the
  * context's launch stream.  phase_ms_out[0..7] = accumulated milliseconds of: digits, bucket scan, scatter,
  * segment map, bucket ACCUMULATE (the dominant kernel), bucket finalise, window reduction, whole device span;
@@ -619,10 +629,20 @@ int32_t kzg_coset_interpolate_rlc(kzg_ctx* ctx, const uint64_t* ys_mont, const u
 int32_t kzg_compute_multiproof_r_powers(const uint64_t* commitments_xy_mont, size_t n_commitments, const uint64_t* commitment_indices,
                                         const uint64_t* coset_indices, const uint64_t* ys_mont, const uint64_t* proofs_xy_mont,
                                         size_t count, size_t n, size_t chunk_len, uint64_t* out_r_powers_mont);
+/* The same weights, bit for bit, with the count item digests hashed on the device: values, indices and proofs are uploaded, one lane per
+ * item produces and hashes its 72 + 32 chunk_len bytes (csrc/coset_item_stream.h), the 32 count digest bytes come back, the one sequential
+ * batch hash runs on the host, and r^i is one product of two table entries per lane.  Inputs the host entry does not validate -- a value
+ * >= r, a coordinate >= p -- are detected on the device and that transcript is recomputed on the host, so every input gives the host entry's
+ * bits.  Arguments and errors as above; a null ctx -> KZG_ERR_INVALID_ARG. */
+int32_t kzg_compute_multiproof_r_powers_device(kzg_ctx* ctx, const uint64_t* commitments_xy_mont, size_t n_commitments,
+                                               const uint64_t* commitment_indices, const uint64_t* coset_indices, const uint64_t* ys_mont,
+                                               const uint64_t* proofs_xy_mont, size_t count, size_t n, size_t chunk_len,
+                                               uint64_t* out_r_powers_mont);
 /* The batch equation above: upload of values / indices / weights, kzg_coset_interpolate_rlc's kernels, an MSM of the l coefficients
  * over srs[0 .. l) with the scalars left on the device, the two count-point combinations of the proofs and the n_commitments-point
  * one of the commitments as batched MSMs (every uploaded point checked on the device), point sums and ONE pairing check on the host.
- * r_powers_mont = NULL derives the weights with kzg_compute_multiproof_r_powers.  The same item may appear twice.  *out_ok = 1 iff the
+ * r_powers_mont = NULL derives the weights of kzg_compute_multiproof_r_powers: on the host pool, or (kzg_ctx_set_transcript_device) on the
+ * device from the values uploaded for the interpolation, which then go up once.  The same item may appear twice.  *out_ok = 1 iff the
  * equation holds; a failed check is *out_ok = 0 with KZG_OK.  count = 0 -> *out_ok = 1.
  * g2_tau_l_mont = [tau^l]_2 in the G2 wire format, checked to be on the twist (not its subgroup: see kzg_verify_proof); NULL is
  * allowed for chunk_len = 1 only and then means consts::G2_TAU.  The identity (all-zero wire point) is a valid commitment and proof.

@@ -58,6 +58,8 @@ PROTOTYPES = {
     "kzg_ctx_last_error": (C.c_char_p, [vp]),
     "kzg_ctx_set_msm_window": (i32, [vp, i32, i32]),
     "kzg_ctx_set_reduction_lanes": (i32, [vp, i32]),
+    "kzg_ctx_set_transcript_device": (i32, [vp, i32]),
+    "kzg_sha256_rows": (i32, [vp, u8p, sz, sz, u8p]),
     "kzg_srs_upload": (i32, [vp, u64p, sz, C.POINTER(vp)]),
     "kzg_srs_load_compressed_be": (i32, [vp, u8p, sz, C.POINTER(vp), C.POINTER(C.c_uint64)]),
     "kzg_srs_load_compressed_ark_le": (i32, [vp, u8p, sz, C.POINTER(vp), C.POINTER(C.c_uint64)]),
@@ -168,6 +170,7 @@ PROTOTYPES = {
     "kzg_verify_blob_kzg_proof_batch": (i32, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), u64p, u64p, sz, u64p, C.POINTER(i32)]),
     "kzg_coset_interpolate_rlc": (i32, [vp, u64p, u64p, u64p, sz, sz, sz, u64p]),
     "kzg_compute_multiproof_r_powers": (i32, [u64p, sz, u64p, u64p, u64p, u64p, sz, sz, sz, u64p]),
+    "kzg_compute_multiproof_r_powers_device": (i32, [vp, u64p, sz, u64p, u64p, u64p, u64p, sz, sz, sz, u64p]),
     "kzg_verify_multiproof_batch": (i32, [vp, vp, u64p, sz, u64p, u64p, u64p, u64p, sz, sz, sz, u64p, u64p, C.POINTER(i32)]),
     "kzg_verify_multiproof": (i32, [vp, vp, u64p, u64p, C.c_uint64, u64p, sz, sz, u64p, C.POINTER(i32)]),
     "kzg_recover_from_cosets": (i32, [vp, u64p, u64p, sz, sz, sz, sz, i32, u64p, C.POINTER(i32)]),
@@ -265,6 +268,12 @@ class Context:
         """Lanes per point of the bucket-reduction kernels: 0 automatic, 2 pairs, 4 quads (same results; test / measurement hook)."""
         if load().kzg_ctx_set_reduction_lanes(self.handle, lanes) != OK:
             raise ValueError("lanes must be 0, 2 or 4")
+
+    def set_transcript_device(self, mode=0):
+        """Where `verify_multiproof_batch` hashes the item digests of derived weights: 0 automatic, 1 host, 2 device (same results; test /
+        measurement hook)."""
+        if load().kzg_ctx_set_transcript_device(self.handle, mode) != OK:
+            raise ValueError("mode must be 0, 1 or 2")
 
     def close(self):
         if self.handle:

@@ -356,6 +356,7 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
     for (auto& b : ctx->mp) b.release();
     ctx->mp_ntt.release();
     for (auto& b : ctx->mv) b.release();
+    for (auto& b : ctx->fs) b.release();
     ctx->mv_ntt.release();
     for (auto& b : ctx->rc) b.release();
     ctx->rc_ntt.release();
@@ -390,6 +391,12 @@ int32_t kzg_ctx_set_reduction_lanes(kzg_ctx* ctx, int32_t lanes) {
     if (!ctx || (lanes != 0 && lanes != 2 && lanes != 4)) return KZG_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
     ctx->reduction_lanes = lanes;
+    return KZG_OK;
+}
+
+int32_t kzg_ctx_set_transcript_device(kzg_ctx* ctx, int32_t mode) {
+    if (!ctx || mode < 0 || mode > 2) return KZG_ERR_INVALID_ARG;
+    ctx->transcript_device.store(mode, std::memory_order_relaxed);
     return KZG_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <vector>
 
 using namespace kzg;
@@ -298,25 +299,57 @@ int32_t coset_domain_check(size_t n, size_t chunk_len) {
     return KZG_OK;
 }
 
+// the upload alone: values -> ctx->mv[0], weights | indices -> ctx->mv[1] (weights == nullptr: their place is left for the caller to fill on the
+// device); room for the l coefficients in ctx->mv[2].  Enqueued on ctx->stream; the caller holds ctx->mu
+int32_t coset_upload(kzg_ctx* ctx, const uint64_t* ys, const uint64_t* coset_indices, const uint64_t* weights, size_t count, size_t l, uint4** d_w, uint64_t** d_k) {
+    KZG_HIP_TRY(ctx, ctx->mv[0].reserve(std::max<size_t>(count * l * 32, 32)));           // (count == 0: the kernels still get valid pointers)
+    KZG_HIP_TRY(ctx, ctx->mv[1].reserve(std::max<size_t>(count * 40, 64)));
+    KZG_HIP_TRY(ctx, ctx->mv[2].reserve(l * 32));
+    *d_w = ctx->mv[1].as<uint4>();
+    *d_k = reinterpret_cast<uint64_t*>(ctx->mv[1].as<uint8_t>() + count * 32);
+    if (count) {
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(ctx->mv[0].p, ys, count * l * 32, hipMemcpyHostToDevice, ctx->stream));
+        if (weights) KZG_HIP_TRY(ctx, hipMemcpyAsync(*d_w, weights, count * 32, hipMemcpyHostToDevice, ctx->stream));
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(*d_k, coset_indices, count * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return KZG_OK;
+}
 // values, weights and indices of `count` cosets -> ctx->mv[0] | mv[1], then their l coefficients sum_i weights[i] I_i into ctx->mv[2] (left on the
 // device, enqueued on ctx->stream).  The caller holds ctx->mu.  t_uploaded != nullptr (trace): the stream is drained behind the uploads, the time
 // taken there, and drained again behind the kernels, so that the caller's phase times are those of the GPU work.
 int32_t coset_upload_and_interpolate(kzg_ctx* ctx, const uint64_t* ys, const uint64_t* coset_indices, const uint64_t* weights, size_t count, size_t n, size_t l,
                                      Clock::time_point* t_uploaded) {
-    KZG_HIP_TRY(ctx, ctx->mv[0].reserve(std::max<size_t>(count * l * 32, 32)));           // (count == 0: the kernels still get valid pointers)
-    KZG_HIP_TRY(ctx, ctx->mv[1].reserve(std::max<size_t>(count * 40, 64)));
-    KZG_HIP_TRY(ctx, ctx->mv[2].reserve(l * 32));
-    uint4* d_w = ctx->mv[1].as<uint4>();
-    uint64_t* d_k = reinterpret_cast<uint64_t*>(ctx->mv[1].as<uint8_t>() + count * 32);
-    if (count) {
-        KZG_HIP_TRY(ctx, hipMemcpyAsync(ctx->mv[0].p, ys, count * l * 32, hipMemcpyHostToDevice, ctx->stream));
-        KZG_HIP_TRY(ctx, hipMemcpyAsync(d_w, weights, count * 32, hipMemcpyHostToDevice, ctx->stream));
-        KZG_HIP_TRY(ctx, hipMemcpyAsync(d_k, coset_indices, count * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
+    uint4* d_w = nullptr;
+    uint64_t* d_k = nullptr;
+    int32_t rc = coset_upload(ctx, ys, coset_indices, weights, count, l, &d_w, &d_k);
+    if (rc != KZG_OK) return rc;
     if (t_uploaded) { KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); *t_uploaded = Clock::now(); }
-    const int32_t rc = coset_interpolate_rlc_device(ctx, ctx->mv[0].as<uint4>(), d_k, d_w, count, n, l, ctx->mv[2].as<uint4>());
+    rc = coset_interpolate_rlc_device(ctx, ctx->mv[0].as<uint4>(), d_k, d_w, count, n, l, ctx->mv[2].as<uint4>());
     if (rc != KZG_OK) return rc;
     if (t_uploaded) KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return KZG_OK;
+}
+
+// The weights with the item digests hashed on the device: values and indices go up as for the interpolation (they stay in ctx->mv[0] / mv[1], the
+// weights land in mv[1] too), the weights come back to out.  Inputs that are not canonical give the host's bits: that transcript is
+// recomputed there and its weights uploaded.  The caller holds ctx->mu.  *on_host (may be null) = that fallback ran.
+int32_t coset_upload_and_derive_weights(kzg_ctx* ctx, const uint64_t* commitments, size_t n_commitments, const uint64_t* commitment_indices,
+                                        const uint64_t* coset_indices, const uint64_t* ys, const uint64_t* proofs, size_t count, size_t n, size_t l, uint64_t* out,
+                                        Clock::time_point* t_uploaded, bool* on_host) {
+    uint4* d_w = nullptr;
+    uint64_t* d_k = nullptr;
+    int32_t rc = coset_upload(ctx, ys, coset_indices, nullptr, count, l, &d_w, &d_k);
+    if (rc != KZG_OK) return rc;
+    if (t_uploaded) { KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); *t_uploaded = Clock::now(); }
+    bool fell_back = false;
+    rc = coset_r_powers_device(ctx, commitments, n_commitments, commitment_indices, ctx->mv[0].as<uint4>(), d_k, proofs, count, n, l, d_w, out, &fell_back);
+    if (rc != KZG_OK) return rc;
+    if (fell_back) {
+        multiproof_r_powers_host(commitments, n_commitments, commitment_indices, coset_indices, ys, proofs, count, n, l, out, host_parallel_for);
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(d_w, out, count * 32, hipMemcpyHostToDevice, ctx->stream));
+        KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (on_host) *on_host = fell_back;
     return KZG_OK;
 }
 
@@ -434,6 +467,29 @@ int32_t kzg_compute_multiproof_r_powers(const uint64_t* commitments_xy_mont, siz
     return KZG_OK;
 }
 
+int32_t kzg_compute_multiproof_r_powers_device(kzg_ctx* ctx, const uint64_t* commitments_xy_mont, size_t n_commitments, const uint64_t* commitment_indices,
+                                               const uint64_t* coset_indices, const uint64_t* ys_mont, const uint64_t* proofs_xy_mont,
+                                               size_t count, size_t n, size_t chunk_len, uint64_t* out_r_powers_mont) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    if (count == 0) return KZG_OK;
+    if (!commitment_indices || !coset_indices || !ys_mont || !proofs_xy_mont || !out_r_powers_mont || (n_commitments && !commitments_xy_mont)) return KZG_ERR_INVALID_ARG;
+    if (chunk_len == 0 || count > ((size_t)1 << 28) / chunk_len) return chunk_len == 0 ? KZG_ERR_INVALID_ARG : KZG_ERR_TOO_LARGE;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return coset_upload_and_derive_weights(ctx, commitments_xy_mont, n_commitments, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, count, n, chunk_len,
+                                           out_r_powers_mont, nullptr, nullptr);
+}
+
+int32_t kzg_sha256_rows(kzg_ctx* ctx, const uint8_t* msgs, size_t row_len, size_t count, uint8_t* out_digests) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    if (count == 0) return KZG_OK;
+    if (!out_digests || (row_len && !msgs)) return KZG_ERR_INVALID_ARG;
+    if (count > ((size_t)1 << 28) || (row_len && count > ((size_t)1 << 31) / row_len)) return KZG_ERR_TOO_LARGE;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return sha256_rows_run(ctx, msgs, row_len, count, out_digests);
+}
+
 int32_t kzg_coset_interpolate_rlc(kzg_ctx* ctx, const uint64_t* ys_mont, const uint64_t* coset_indices, const uint64_t* weights_mont,
                                   size_t count, size_t n, size_t chunk_len, uint64_t* out_coeffs_mont) {
     if (!ctx || !out_coeffs_mont) return KZG_ERR_INVALID_ARG;
@@ -490,19 +546,46 @@ int32_t kzg_verify_multiproof_batch(kzg_ctx* ctx, const kzg_srs* srs, const uint
     G2 g2_tau_l;
     const bool g2_ok = load_g2_tau(g2_tau_l_mont, &g2_tau_l);                            // reported after an off-curve G1 point, as verify_batch_core does
     std::vector<uint64_t> derived;
-    if (!r_powers_mont) {
-        RoctxRange range("kzg:multiproof_verify:r_powers (host)");
-        derived.resize(4 * N);
-        multiproof_r_powers_host(commitments_xy_mont, n_commitments, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, N, n, l, derived.data(), host_parallel_for);
-        r_powers_mont = derived.data();
+    const bool derive = !r_powers_mont;
+    if (derive) { derived.resize(4 * N); r_powers_mont = derived.data(); }
+    const bool on_device = derive && coset_transcript_on_device(ctx->transcript_device.load(std::memory_order_relaxed), N, l);   // (no lock: the host transcript never waits for the context)
+    std::unique_lock<std::mutex> lk(ctx->mu, std::defer_lock);
+    const char* rp_path = "";
+    double rp_ms = 0, up_ms = 0;
+    if (on_device) {
+        lk.lock();
+        // 0 + 1. values and indices go up ONCE; the item digests are hashed where they landed, the batch hash runs here, the weights are written where
+        // the interpolation reads them and come back for the host scalars of step 3
+        KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        auto t_up = t0;
+        bool on_host = false;
+        rc = coset_upload_and_derive_weights(ctx, commitments_xy_mont, n_commitments, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, N, n, l, derived.data(),
+                                             trace ? &t_up : nullptr, &on_host);
+        if (rc != KZG_OK) return rc;
+        const auto t_rp = Clock::now();
+        rp_path = on_host ? " (device, then host: an input is not canonical)" : " (device)";
+        up_ms = ms_between(t0, t_up);
+        rp_ms = ms_between(t_up, t_rp);
+        rc = coset_interpolate_rlc_device(ctx, ctx->mv[0].as<uint4>(), reinterpret_cast<uint64_t*>(ctx->mv[1].as<uint8_t>() + N * 32), ctx->mv[1].as<uint4>(), N, n, l,
+                                          ctx->mv[2].as<uint4>());
+        if (rc != KZG_OK) return rc;
+        if (trace) KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    } else {
+        if (derive) {                                                                    // (the host transcript needs no context)
+            RoctxRange range("kzg:multiproof_verify:r_powers (host)");
+            multiproof_r_powers_host(commitments_xy_mont, n_commitments, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, N, n, l, derived.data(), host_parallel_for);
+            rp_path = " (host)";
+        }
+        const auto t_rp = Clock::now();
+        lk.lock();
+        KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        // 1. values, indices, weights -> the l coefficients A_t (left on the device)
+        auto t_up = t_rp;
+        rc = coset_upload_and_interpolate(ctx, ys_mont, coset_indices, r_powers_mont, N, n, l, trace ? &t_up : nullptr);
+        if (rc != KZG_OK) return rc;
+        rp_ms = ms_between(t0, t_rp);
+        up_ms = ms_between(t_rp, t_up);
     }
-    const auto t_rp = Clock::now();
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // 1. values, indices, weights -> the l coefficients A_t (left on the device)
-    auto t_up = t_rp;
-    rc = coset_upload_and_interpolate(ctx, ys_mont, coset_indices, r_powers_mont, N, n, l, trace ? &t_up : nullptr);
-    if (rc != KZG_OK) return rc;
     const auto t_ker = Clock::now();
     // 2. [sum_i r_i I_i(tau)]_1: an MSM of the coefficients over srs[0 .. l)
     uint64_t interp_xy[8];
@@ -553,9 +636,9 @@ int32_t kzg_verify_multiproof_batch(kzg_ctx* ctx, const kzg_srs* srs, const uint
     const G1 rhs = g1_add(g1_add(g1_from_wire(c_sum), g1_neg(g1_from_wire(interp_xy))), g1_from_wire(sums + 8));
     *out_ok = pairings_verify_pooled(lhs, g2_tau_l, rhs, g2_generator()) ? 1 : 0;
     if (trace)
-        fprintf(stderr, "kzg_verify_multiproof_batch N=%zu l=%zu M=%zu: r_powers %.3f ms, upload %.3f ms, interpolation kernel %.3f ms, coefficient MSM %.3f ms, "
-                "host scalars + proof / commitment MSMs %.3f ms, point sums + pairing %.3f ms, call %.3f ms\n", N, l, n_commitments, ms_between(t0, t_rp), ms_between(t_rp, t_up),
-                ms_between(t_up, t_ker), ms_between(t_ker, t_msm1), ms_between(t_msm1, t_msm2), ms_between(t_msm2, Clock::now()), ms_between(t0, Clock::now()));
+        fprintf(stderr, "kzg_verify_multiproof_batch N=%zu l=%zu M=%zu: r_powers%s %.3f ms, upload %.3f ms, interpolation kernel %.3f ms, coefficient MSM %.3f ms, "
+                "host scalars + proof / commitment MSMs %.3f ms, point sums + pairing %.3f ms, call %.3f ms\n", N, l, n_commitments, rp_path, rp_ms, up_ms,
+                ms_between(t0, t_ker) - rp_ms - up_ms, ms_between(t_ker, t_msm1), ms_between(t_msm1, t_msm2), ms_between(t_msm2, Clock::now()), ms_between(t0, Clock::now()));
     return KZG_OK;
 }
 

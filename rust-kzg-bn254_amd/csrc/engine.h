@@ -2,6 +2,7 @@
 // device-resident SRS, reusable workspaces.  No torch types, no CPU fallback.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdint>
 #include <functional>
 #include <map>
@@ -101,6 +102,7 @@ struct kzg_ctx {
     int msm_c_override = 0;
     int msm_seg_override = 0;
     int reduction_lanes = 0;               // kzg_ctx_set_reduction_lanes: 0 automatic, 2 lane pairs, 4 lane quads
+    std::atomic<int> transcript_device{0}; // kzg_ctx_set_transcript_device: 0 automatic, 1 always host, 2 always device (the weights of kzg_verify_multiproof_batch)
     bool profiling = false;
     bool lds_attr_set = false;
     bool poly_lds_attr_set = false;
@@ -131,6 +133,7 @@ struct kzg_ctx {
     kzg::NttWorkspace mp_ntt;
     kzg::DeviceBuffer mv[4];                   // kzg_coset_interpolate_rlc / kzg_verify_multiproof_batch (multiverify.hip): values | indices + weights | coefficients | partial rows
     kzg::NttWorkspace mv_ntt;
+    kzg::DeviceBuffer fs[2];                   // the coset transcript on the device (fsdevice.hip): commitment rows | proofs, digests | power tables | flag; kzg_sha256_rows: messages, digests
     kzg::DeviceBuffer rc[3];                   // kzg_recover_from_cosets (recover.hip): work values | indices, vanishing values, partial products, flag | powers of g
     int rc_gpow_log = -1;                      // rc[2] holds the factored tables of g^t and g^-t for t < 2^rc_gpow_log (-1: none yet)
     kzg::NttWorkspace rc_ntt;                  // its `data` also stages the uploaded coset values (dead before the first transform)
@@ -310,6 +313,16 @@ void multiproof_drop(kzg_srs* srs);
 int32_t multiproof_encode(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, bool eval_form, const EncodePlan& plan, uint64_t* out_ys, uint64_t* out_xy, uint8_t* out_inf);
 // verification of coset proofs (multiverify.hip): d_out[t] = sum_i weights[i] w^(-ks[i] t) IFFT_l(ys_i)[t], enqueued on ctx->stream (d_ys is scratch when l > 1024)
 int32_t coset_interpolate_rlc_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, size_t count, size_t n, size_t l, uint4* d_out);
+// hashing on the device (fsdevice.hip).  Called under ctx->mu with the device set.
+// count messages of row_len bytes each (host, stride row_len) -> count SHA-256 digests (host); synchronised on return
+int32_t sha256_rows_run(kzg_ctx* ctx, const uint8_t* msgs, size_t row_len, size_t count, uint8_t* out_digests);
+// The weights r^0 .. r^(count-1) of the coset transcript (host_fiat_shamir.h multiproof_r_powers_host) from values and coset indices ALREADY on the
+// device (wire form): commitment rows and proofs go up, the item digests are hashed one lane per item and come back, the one batch hash runs on the
+// host, the powers are one product per lane into d_weights (count wire scalars) and are copied to out_r_powers (host).  *fell_back = an input was
+// not canonical (a value >= r, a coordinate >= p): nothing is written, the caller derives the weights on the host.  Synchronised on return
+int32_t coset_r_powers_device(kzg_ctx* ctx, const uint64_t* commitments, size_t n_commitments, const uint64_t* commitment_indices, const uint4* d_ys,
+                              const uint64_t* d_ks, const uint64_t* proofs, size_t count, size_t n, size_t l, uint4* d_weights, uint64_t* out_r_powers,
+                              bool* fell_back);
 // erasure decoding (recover.hip): the polynomial of degree < count l through the values of the plan's cosets (ys: host, count x l wire values), as n
 // coefficients or evaluations on the host; *consistent = its coefficients from plan.degree_bound on are zero.  Called under ctx->mu, synchronised on return
 int32_t recover_run(kzg_ctx* ctx, const RecoverPlan& plan, const uint64_t* ys, bool eval_form, uint64_t* out_poly, int32_t* consistent);

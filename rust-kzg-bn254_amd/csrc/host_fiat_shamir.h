@@ -74,14 +74,17 @@ inline void powers_of(const uint64_t r[4], size_t n, uint64_t* out) {
     for (size_t i = 0; i < n; ++i) { memcpy(out + 4 * i, cur, 32); fr_mul(cur, r, cur); }
 }
 // the tail of both transcripts: r = hash_to_field_element(data), then the n powers of r
-inline void hash_to_r_powers(const std::vector<uint8_t>& data, size_t n, uint64_t* out) {
+inline void hash_to_r(const std::vector<uint8_t>& data, uint64_t r[4]) {
     Sha256 sh;
     sha256_init(sh);
     sha256_update(sh, data.data(), data.size());
     uint8_t dig[32];
     sha256_final(sh, dig);
-    uint64_t r[4];
     digest_to_fr_wire(dig, r);
+}
+inline void hash_to_r_powers(const std::vector<uint8_t>& data, size_t n, uint64_t* out) {
+    uint64_t r[4];
+    hash_to_r(data, r);
     powers_of(r, n, out);
 }
 
@@ -106,17 +109,33 @@ inline void r_powers_host(const uint64_t* commitments, const uint64_t* zs, const
     hash_to_r_powers(data, n, out);
 }
 
-// Two levels: one SHA-256 per item over its index pair, its l values and its proof (host pool), one over the header, the commitments and the digests
-inline void multiproof_r_powers_host(const uint64_t* commitments, size_t n_commitments, const uint64_t* commitment_indices, const uint64_t* coset_indices,
-                                     const uint64_t* ys, const uint64_t* proofs, size_t count, size_t n, size_t l, uint64_t* out, ParallelFor parallel_for) {
-    const size_t head = 24 + 32 + 32 * n_commitments;
-    std::vector<uint8_t> data(head + 32 * count, 0);
+// The batch level of the coset transcript: tag, sizes and commitments filled in, room for the `count` item digests from coset_batch_head() on
+inline size_t coset_batch_head(size_t n_commitments) { return 24 + 32 + 32 * n_commitments; }
+inline std::vector<uint8_t> coset_batch_transcript(const uint64_t* commitments, size_t n_commitments, size_t count, size_t n, size_t l) {
+    std::vector<uint8_t> data(coset_batch_head(n_commitments) + 32 * count, 0);
     memcpy(data.data(), COSET_BATCH_DOMAIN, 24);
     put_u64be(data.data() + 24, (uint64_t)n);
     put_u64be(data.data() + 32, (uint64_t)l);
     put_u64be(data.data() + 40, (uint64_t)n_commitments);
     put_u64be(data.data() + 48, (uint64_t)count);
     for (size_t c = 0; c < n_commitments; ++c) g1_serialize_compressed_ark(g1_from_wire(commitments + 8 * c), data.data() + 56 + 32 * c);
+    return data;
+}
+// Where the item digests of a batch are hashed (kzg_ctx_set_transcript_device: mode 1 host, 2 device).  Automatic (0) takes the device only
+// inside the envelope that was MEASURED to win (profiles/fs_device.md): at least 4 096 items, chunks of at most 64 values, at least 2 MiB of
+// values.  A lane hashes its item as one dependent chain of 2 + l / 2 blocks, so few long items (count small, l large) are the shape a lane
+// per stream does not fit, and batches of 256 items lose to the two extra round trips at every chunk length: both stay on the host pool.
+constexpr size_t COSET_DEVICE_MIN_COUNT = 4096, COSET_DEVICE_MAX_CHUNK = 64, COSET_DEVICE_MIN_BYTES = (size_t)2 << 20;
+inline bool coset_transcript_on_device(int mode, size_t count, size_t l) {
+    if (mode != 0) return mode == 2;
+    return count >= COSET_DEVICE_MIN_COUNT && l <= COSET_DEVICE_MAX_CHUNK && count * l * 32 >= COSET_DEVICE_MIN_BYTES;
+}
+// Two levels: one SHA-256 per item over its index pair, its l values and its proof (host pool), one over the header, the commitments and the digests
+// (fsdevice.hip computes the same item digests on the device, one lane per item, from coset_item_stream.h)
+inline void multiproof_r_powers_host(const uint64_t* commitments, size_t n_commitments, const uint64_t* commitment_indices, const uint64_t* coset_indices,
+                                     const uint64_t* ys, const uint64_t* proofs, size_t count, size_t n, size_t l, uint64_t* out, ParallelFor parallel_for) {
+    const size_t head = coset_batch_head(n_commitments);
+    std::vector<uint8_t> data = coset_batch_transcript(commitments, n_commitments, count, n, l);
     const size_t per = std::max<size_t>(1, 1024 / l), jobs = (count + per - 1) / per;
     auto body = [&](size_t j) {
         std::vector<uint8_t> item(24 + 16 + 32 * l + 32);

@@ -439,6 +439,22 @@ def coset_interpolate_rlc(ys, coset_indices, weights, n: int, ctx=None) -> np.nd
     return out
 
 
+def sha256_rows(rows, ctx=None) -> np.ndarray:
+    """SHA-256 of every row of a 2-D uint8 array (`kzg_sha256_rows`, GPU: one lane per row): (count, row_len) -> (count, 32)."""
+    rows = np.ascontiguousarray(rows, dtype=np.uint8)
+    if rows.ndim != 2:
+        raise InvalidInputLength()
+    count, row_len = rows.shape
+    ctx = ctx or _lib.default_context()
+    out = np.zeros((count, 32), dtype=np.uint8)
+    u8 = lambda a: a.ctypes.data_as(_lib.u8p)                                    # noqa: E731
+    rc = _lib.load().kzg_sha256_rows(ctx.handle, u8(rows) if rows.size else None, row_len, count, u8(out) if count else None)
+    ctx.check_device(rc)
+    if rc != _lib.OK:
+        raise GenericError(_lib.status_message(rc))
+    return out
+
+
 def compute_challenges_and_evaluate_polynomial(blobs, commitments, ctx=None):
     """helpers.rs:613-665 in ONE call of the C-ABI (`kzg_compute_challenges_and_evaluate_polynomial`): the n transcripts are hashed
     on a pool of host threads, the n barycentric evaluations are one batched GPU launch."""

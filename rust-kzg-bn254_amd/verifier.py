@@ -279,17 +279,22 @@ def _multiproof_args(commitments, commitment_indices, coset_indices, ys, proofs)
     return cm, ci, ki, ys, pf
 
 
-def compute_multiproof_r_powers(commitments, commitment_indices, coset_indices, ys, proofs, n: int) -> np.ndarray:
+def compute_multiproof_r_powers(commitments, commitment_indices, coset_indices, ys, proofs, n: int, ctx=None, device=False) -> np.ndarray:
     """The weights [r^0 .. r^(count-1)] of a batch of coset proofs (`kzg_compute_multiproof_r_powers`, host only): item digests
     d_i = SHA-256(COSET_ITEM_DOMAIN || u64be(c_i) || u64be(k_i) || l x be32(ys_i[j]) || compressed proof_i), then
-    r = SHA-256(COSET_BATCH_DOMAIN || u64be(n) || u64be(l) || u64be(M) || u64be(count) || M x compressed C || d_0 || ..) mod r."""
+    r = SHA-256(COSET_BATCH_DOMAIN || u64be(n) || u64be(l) || u64be(M) || u64be(count) || M x compressed C || d_0 || ..) mod r.
+    `device=True` hashes the item digests on the GPU of `ctx` (`kzg_compute_multiproof_r_powers_device`): the same bits."""
     cm, ci, ki, ys, pf = _multiproof_args(commitments, commitment_indices, coset_indices, ys, proofs)
     count, l = ys.shape[0], ys.shape[1]
     out = np.zeros((count, 4), dtype=np.uint64)
     if count == 0:
         return out
-    rc = _lib.load().kzg_compute_multiproof_r_powers(_lib.ptr(cm) if len(cm) else None, len(cm), _lib.ptr(ci), _lib.ptr(ki), _lib.ptr(ys),
-                                                     _lib.ptr(pf), count, int(n), l, _lib.ptr(out))
+    args = (_lib.ptr(cm) if len(cm) else None, len(cm), _lib.ptr(ci), _lib.ptr(ki), _lib.ptr(ys), _lib.ptr(pf), count, int(n), l, _lib.ptr(out))
+    if device:
+        ctx = ctx or _lib.default_context()
+        _raise_for(_lib.load().kzg_compute_multiproof_r_powers_device(ctx.handle, *args), ctx)
+        return out
+    rc = _lib.load().kzg_compute_multiproof_r_powers(*args)
     if rc != _lib.OK:
         raise GenericError(_lib.status_message(rc))
     return out
