@@ -238,22 +238,23 @@ __device__ __forceinline__ void quad_shfl(QuadXyzz& r, const QuadXyzz& h, int sr
 
 // ---- lane groups: what a kernel written once for both forms needs to know (msm_kernels.h section 6c) -----------------------------
 // One point per LANES adjacent lanes, GROUPS points per wave; `role` is what a lane holds of its point and goes to every primitive.
-// The kernel constants are those of the bucket-reduction kernels: 64 values per workgroup in both forms.
+// The kernel constants are those of the first bucket-reduction level: WG_GROUPS groups of 64 values per workgroup.
 #ifndef KZG_PAIR_WAVES
 #define KZG_PAIR_WAVES 3       // waves per SIMD of the pair kernels (3: <= 168 VGPRs, a wave fits beside two accumulate waves of the other MSM in flight)
 #endif
 #ifndef KZG_QUAD_SMALL_WAVES
 #define KZG_QUAD_SMALL_WAVES 4     // waves per SIMD the small quad launches are compiled for (128 VGPRs with a few spills; 2 = no spills measured the same or 5 % slower)
 #endif
-// the superset-sum transforms of 64 values (msm_kernels.h 6c, which defines them inline; declared plainly here for the units that never use them)
-__device__ void group_zeta64(HalfXyzz& v, uint32_t lane, uint32_t w, bool odd, int32_t* __restrict__ lds);
+// the quads' superset-sum transform of 64 values (msm_kernels.h 6c, which defines it inline; declared plainly here for the units that never use it)
 __device__ void group_zeta64q(QuadXyzz& v, uint32_t lane, uint32_t w, uint32_t q, int32_t* __restrict__ lds);
+// TREE_GROUPS: groups of 64 values a workgroup of the first reduction level carries through the sum tree (group_sum_tree below); 0 = one group
+// through the form's full transform (zeta64)
 struct PairLanes {
     using Point = HalfXyzz;
     using Role = bool;                                   // odd lane
     static constexpr uint32_t LANES = 2, GROUPS = 64 / LANES, LOG_GROUPS = 5;
-    static constexpr int THREADS = 128, WAVES = KZG_PAIR_WAVES;
-    static constexpr int ZETA_LDS_WORDS = 2 * NL * 64;
+    static constexpr int TREE_GROUPS = 2, WG_GROUPS = TREE_GROUPS, THREADS = 128 * WG_GROUPS, WAVES = KZG_PAIR_WAVES;
+    static constexpr int SUMS_LDS_WORDS = 4 * NL * 64 * TREE_GROUPS;
     static constexpr uint32_t FUSED_HEAVY = 12;          // (24 while the groups held neighbouring buckets: the ~100 heavy buckets of a blob's top window then sat in two workgroups)
     static __device__ __forceinline__ Role role(uint32_t lane) { return (lane & 1u) != 0; }
     static __device__ __forceinline__ int affine_half(Role r) { return r ? 2 : 0; }           // the uint4 of an affine point (x: 0, y: 2) the lane's mixed addition takes
@@ -265,14 +266,13 @@ struct PairLanes {
     static __device__ __forceinline__ void madd(Point& r, const Point& acc, const Fq& c, uint32_t neg, Role role) { pair_madd(r, acc, c, neg, role); }
     static __device__ __forceinline__ void shfl_down(Point& r, const Point& h, int d) { half_shfl_down(r, h, d); }
     static __device__ __forceinline__ void shfl(Point& r, const Point& h, int src) { half_shfl(r, h, src); }
-    static constexpr auto& zeta64 = group_zeta64;        // zeta64(v, lane, w, role, lds).  The function itself, not a wrapper: one more level of inlining moved the kernels' code
 };
 struct QuadLanes {
     using Point = QuadXyzz;
     using Role = uint32_t;                               // lane & 3
     static constexpr uint32_t LANES = 4, GROUPS = 64 / LANES, LOG_GROUPS = 4;
-    static constexpr int THREADS = 256, WAVES = KZG_QUAD_SMALL_WAVES;
-    static constexpr int ZETA_LDS_WORDS = (NL + 1) * 256;
+    static constexpr int TREE_GROUPS = 0, WG_GROUPS = 1, THREADS = 256 * WG_GROUPS, WAVES = KZG_QUAD_SMALL_WAVES;
+    static constexpr int SUMS_LDS_WORDS = (NL + 1) * 256;
     static constexpr uint32_t FUSED_HEAVY = 8;           // 16 quads share a heavy bucket
     static __device__ __forceinline__ Role role(uint32_t lane) { return lane & 3u; }
     static __device__ __forceinline__ int affine_half(Role r) { return (r & 1u) ? 2 : 0; }
@@ -284,8 +284,46 @@ struct QuadLanes {
     static __device__ __forceinline__ void madd(Point& r, const Point& acc, const Fq& c, uint32_t neg, Role role) { quad_madd(r, acc, c, neg, role); }
     static __device__ __forceinline__ void shfl_down(Point& r, const Point& h, int d) { quad_shfl_down(r, h, d); }
     static __device__ __forceinline__ void shfl(Point& r, const Point& h, int src) { quad_shfl(r, h, src); }
-    static constexpr auto& zeta64 = group_zeta64q;
+    static constexpr auto& zeta64 = group_zeta64q;       // zeta64(v, lane, w, role, lds).  The function itself, not a wrapper: one more level of inlining moved the kernels' code
 };
+
+// ---- the seven sums of a group of 64 values (the total, and one per index bit) as a WORK-EFFICIENT tree, for NG groups on one workgroup of
+// 64 NG lane groups (either form).
+// The full transforms (msm_kernels.h 6c, 6d) leave a superset sum in every one of the 64 slots; slot 0 and the slots 2^k are all that is read.
+// Step k of the transform (v[x] += v[x + 2^k]) is needed only for the slots x with x mod 2^(k+1) in {0} u {2^j : j < k}: k + 1 slots per
+// block of 2^(k+1), 32, 32, 24, 16, 10, 6 additions per group over the six steps -- 120, where a transform on two waves of pairs issues
+// 384 and executes 192.  The values go to an LDS slot array (the 36 limb planes of HBM, identity = zeros), the live additions of a step are
+// compacted onto the first lane groups of the workgroup (task q -> group, block, j -> slot x), and a wave with no task skips the addition:
+// on pairs the six steps cost 2 + 2 + 2 + 1 + 1 + 1 = 9 wave-level additions per 128 values with NG = 2 (4 + 4 + 3 + 2 + 2 + 1 = 16 per
+// 256 with NG = 4, 6 per 64 with NG = 1) instead of 12 per 64.  Every live slot sees the operands of the full transform in the same
+// order: the sums are the same XYZZ words.
+// Lane group t holds value t (group t / 64, slot t % 64).  Afterwards lds slot 64 gr holds the total of group gr and slot 64 gr + 2^k
+// its sum over the values whose index has bit k set.  Called by every lane of the workgroup (seven barriers inside).
+template <class LG, int NG>
+__device__ __forceinline__ void group_sum_tree(const typename LG::Point& v, uint32_t t, typename LG::Role role, int32_t* __restrict__ lds /* 4 NL x 64 NG words */) {
+    constexpr uint32_t SLOTS = 64 * NG;
+    LG::store(lds, SLOTS, t, v, role);
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t k = 0; k < 6; ++k) {                 // one addition site for the six steps
+        const uint32_t per_block = k + 1, per_group = per_block * (32u >> k), n_tasks = NG * per_group;
+        if ((t & ~(LG::GROUPS - 1)) < n_tasks) {       // wave-uniform: the first task of this wave exists
+            const bool on = t < n_tasks;
+            const uint32_t gr = t / per_group, rem = t - gr * per_group, blk = rem / per_block, j = rem - blk * per_block;
+            const uint32_t x = on ? gr * 64 + (blk << (k + 1)) + (j ? 1u << (j - 1) : 0u) : 0u;
+            typename LG::Point a, b, r;
+            LG::load(a, lds, SLOTS, x, role);          // (every lane loads and adds: the lane groups past the last task add two identities)
+            LG::load(b, lds, SLOTS, x + (1u << k), role);
+            if (!on) {
+                LG::set_inf(a);
+                LG::set_inf(b);
+            }
+            LG::add(r, a, b, role);
+            if (on) LG::store(lds, SLOTS, x, r, role);  // no task of this step reads x (bit k clear) or writes x + 2^k (bit k set)
+        }
+        __syncthreads();
+    }
+}
 
 }  // namespace kzg
 #endif

@@ -268,11 +268,12 @@ static int32_t reduce_tables(const Launch& L) {
     int32_t* x1 = ws.chunkS.as<int32_t>();
     dispatch<true, false>(p.quad1, [&](auto quads) {
         using LG = std::conditional_t<decltype(quads)::value, QuadLanes, PairLanes>;
+        const uint32_t wgs = (G1 + LG::WG_GROUPS - 1) / LG::WG_GROUPS;          // WG_GROUPS groups of 64 buckets per workgroup
         if (p.fused)
-            hipLaunchKernelGGL(k_msm_bucket_bits1_fused<LG>, dim3(G1), dim3(LG::THREADS), 0, L.st, L.bases.points, ws.sorted.as<uint32_t>(), ws.offs.as<uint32_t>(), p.B,
+            hipLaunchKernelGGL(k_msm_bucket_bits1_fused<LG>, dim3(wgs), dim3(LG::THREADS), 0, L.st, L.bases.points, ws.sorted.as<uint32_t>(), ws.offs.as<uint32_t>(), p.B,
                                p.idx_log, p.stride_adj, G1, x1, (size_t)7 * G1, L.d_out);
         else
-            hipLaunchKernelGGL(k_msm_bucket_bits1<LG>, dim3(G1), dim3(LG::THREADS), 0, L.st, ws.offs.as<uint32_t>(), p.B, p.nl, ws.head.as<int32_t>(), (size_t)p.G,
+            hipLaunchKernelGGL(k_msm_bucket_bits1<LG>, dim3(wgs), dim3(LG::THREADS), 0, L.st, ws.offs.as<uint32_t>(), p.B, p.nl, ws.head.as<int32_t>(), (size_t)p.G,
                                ws.cont.as<int32_t>(), (size_t)p.nl, G1, x1, (size_t)7 * G1, L.d_out);
     });
     KZG_MARK(6);

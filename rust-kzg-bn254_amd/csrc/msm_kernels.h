@@ -1197,43 +1197,19 @@ __device__ __forceinline__ void xyzz_store_wire(uint32_t* __restrict__ out_wire,
 // -------------------------------------------------------------------------------------------------
 // 6c. the first of the same two reduction levels on LANE GROUPS: one point per LG::LANES adjacent lanes, written ONCE over the traits
 //     PairLanes / QuadLanes (end of curve_quad.h) and instantiated for both.  Same inputs, same X1 / out_wire layout and the same
-//     group elements as the one-lane form of 6b; 64 values = one workgroup either way.
-//       <PairLanes>  curve_pair.h: 7 multiplications per lane and addition instead of 14; two waves of 32 pairs.
-//       <QuadLanes>  curve_quad.h: four instead of seven, four waves of 16 quads: ~0.7 of the pair form's dependent instructions at
-//                    twice its lanes: used when no other MSM is in flight (then latency is everything and the SIMDs are idle anyway;
-//                    kzg_ctx_set_reduction_lanes(ctx, 2): always the pair kernels).
-//     Only the two superset-sum transforms are written per form (LG::zeta64 names them): their steps across waves differ.
+//     group elements as the one-lane form of 6b.
+//       <PairLanes>  curve_pair.h: 7 multiplications per lane and addition instead of 14; waves of 32 pairs, LG::TREE_GROUPS = 2 groups of
+//                    64 values per four-wave workgroup.  The seven sums of a group come from the work-efficient tree (group_sum_tree, end of
+//                    curve_quad.h): 18 wave-level additions per 256 buckets where the full transform issued 48.  With another MSM in flight
+//                    the level costs its instructions, and the pipelined step follows them (profiles/reduce_tree.md).  Four groups per
+//                    workgroup would be 16 additions, but a workgroup of eight waves finds no room on a CU beside the other MSM's
+//                    accumulate waves, and the step gets slower than with the full transform (same file).
+//       <QuadLanes>  curve_quad.h: four instead of seven, four waves of 16 quads, one group per workgroup: ~0.7 of the pair form's dependent
+//                    instructions at twice its lanes: used when no other MSM is in flight (then latency is everything and the SIMDs are
+//                    idle anyway; kzg_ctx_set_reduction_lanes(ctx, 2): always the pair kernels).  TREE_GROUPS = 0: the quads keep the full
+//                    superset-sum transform over shuffles -- the tree's LDS round trip and barrier per step made the lone level slower
+//                    (2^14 buckets: 0.068-0.070 -> 0.105 ms, profiles/reduce_tree.md).
 // -------------------------------------------------------------------------------------------------
-// Superset-sum transform over the 64 values of a two-wave group, value gp = 32 w + pair: afterwards gp = 0 holds the total and
-// gp = 2^k the sum over the values whose index has bit k set.  Steps 0..4 inside the wave, step 5 through LDS (wave 1 publishes,
-// wave 0 adds).  Called by every lane of both waves (one barrier inside).
-__device__ __forceinline__ void group_zeta64(HalfXyzz& v, uint32_t lane, uint32_t w, bool odd, int32_t* __restrict__ lds /* 2 NL x 64 words */) {
-    const uint32_t pair = lane >> 1;
-#pragma unroll 1
-    for (int k = 0; k < 6; ++k) {                      // one addition site for the six steps
-        HalfXyzz u;
-        bool on;
-        if (k < 5) {
-            half_shfl_down(u, v, 2 << k);
-            on = ((pair >> k) & 1u) == 0;
-        } else {
-            if (w == 1) {
-#pragma unroll
-                for (int j = 0; j < NL; ++j) { lds[j * 64 + lane] = v.inf ? 0 : v.u.l[j]; lds[(NL + j) * 64 + lane] = v.inf ? 0 : v.v.l[j]; }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < NL; ++j) { u.u.l[j] = lds[j * 64 + lane]; u.v.l[j] = lds[(NL + j) * 64 + lane]; }
-            u.inf = fe_is_literal_zero(u.v);
-            on = w == 0;
-        }
-        if (on) {
-            HalfXyzz r;
-            pair_add(r, v, u, odd);
-            v = r;
-        }
-    }
-}
 // Superset-sum transform over the 64 values of a four-wave group, value gp = 16 w + quad: afterwards gp = 0 holds the total and
 // gp = 2^k the sum over the values whose index has bit k set.  Steps 0..3 inside the wave, steps 4 and 5 through LDS (the waves whose
 // index has the bit set publish, the others add).  Called by every lane of the four waves (four barriers inside).
@@ -1268,6 +1244,33 @@ __device__ __forceinline__ void group_zeta64q(QuadXyzz& v, uint32_t lane, uint32
             quad_add(r, v, u, q);
             v = r;
         }
+    }
+}
+// (group_sum_tree<LG, NG>, the work-efficient tree of the same seven sums for NG groups per workgroup: end of curve_quad.h)
+// what the first reduction level writes: role 6 = the total (slot 0), role k < 6 = slot 2^k of each of the workgroup's NG groups
+template <class LG, int NG>
+__device__ __forceinline__ void group_sum_tree_store(uint32_t t, typename LG::Role role, const int32_t* __restrict__ lds, uint32_t G1, int32_t* __restrict__ x1, size_t x_stride,
+                                                     uint32_t* __restrict__ out_wire) {
+    const uint32_t gr = t / 7, zr = t - gr * 7, g = blockIdx.x * NG + gr;
+    if (gr >= (uint32_t)NG || g >= G1) return;
+    typename LG::Point v;
+    LG::load(v, lds, 64 * NG, gr * 64 + (zr == 6 ? 0u : 1u << zr), role);
+    if (G1 == 1) LG::store_wire(out_wire, (size_t)zr, v, role);
+    else LG::store(x1, x_stride, (size_t)zr * G1 + g, v, role);
+}
+// the seven sums of each group of the workgroup, from the values in registers to X1 / out_wire: the tree, or (TREE_GROUPS == 0) the form's full transform
+template <class LG>
+__device__ __forceinline__ void group_sums_out(typename LG::Point& v, uint32_t lane, uint32_t t, typename LG::Role role, int32_t* __restrict__ lds, uint32_t G1,
+                                               int32_t* __restrict__ x1, size_t x_stride, uint32_t* __restrict__ out_wire) {
+    if constexpr (LG::TREE_GROUPS != 0) {
+        group_sum_tree<LG, LG::TREE_GROUPS>(v, t, role, lds);
+        group_sum_tree_store<LG, LG::TREE_GROUPS>(t, role, lds, G1, x1, x_stride, out_wire);
+    } else {
+        LG::zeta64(v, lane, threadIdx.x >> 6, role, lds);
+        const int zr = zeta_role(t);
+        if (zr < 0) return;
+        if (G1 == 1) LG::store_wire(out_wire, (size_t)zr, v, role);
+        else LG::store(x1, x_stride, (size_t)zr * G1 + blockIdx.x, v, role);
     }
 }
 
@@ -1343,21 +1346,18 @@ k_msm_bucket_bits1(const uint32_t* __restrict__ offs, uint32_t B, uint32_t nl, c
                    const int32_t* __restrict__ cont, size_t cont_stride, uint32_t G1, int32_t* __restrict__ x1, size_t x_stride,
                    uint32_t* __restrict__ out_wire /* G1 == 1 only */) {
     latency_bound_kernel();
-    __shared__ int32_t lds[LG::ZETA_LDS_WORDS];
-    const uint32_t g = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63, gp = w * LG::GROUPS + lane / LG::LANES;
+    constexpr int NG = LG::WG_GROUPS;
+    __shared__ int32_t lds[LG::SUMS_LDS_WORDS];
+    const uint32_t lane = threadIdx.x & 63, t = threadIdx.x / LG::LANES;      // lane group t: group t / 64 of the workgroup, value t % 64
     const typename LG::Role role = LG::role(lane);
     const uint32_t L = acc_seg_len(offs[B], nl);
-    const uint32_t bkt = g * 64 + gp;
+    const uint32_t bkt = blockIdx.x * (64 * NG) + t;   // (a group past G1 lies past B: identities)
     BucketSpan s;
     s.g = bkt; s.t1 = 0; s.np = 0; s.long_run = false;
     if (bkt < B && L) s = bucket_span(offs, bkt, L);
     typename LG::Point v;
     bucket_sum_lanes<LG>(v, s, lane, role, head, head_stride, cont, cont_stride);
-    LG::zeta64(v, lane, w, role, lds);
-    const int zr = zeta_role(gp);
-    if (zr < 0) return;
-    if (G1 == 1) LG::store_wire(out_wire, (size_t)zr, v, role);
-    else LG::store(x1, x_stride, (size_t)zr * G1 + g, v, role);
+    group_sums_out<LG>(v, lane, t, role, lds, G1, x1, x_stride, out_wire);
 }
 // level 1 FUSED with the accumulation, for sparse MSMs (a few entries per bucket: commitments of <= 2^12 coefficients on the c = 15
 // tables): lane group = bucket, it adds its own sorted entries with LG::madd (pairs: 5 multiplications per lane and entry) -- no
@@ -1408,12 +1408,14 @@ k_msm_bucket_bits1_fused(const uint4* __restrict__ points, const uint32_t* __res
                          uint32_t idx_log, uint32_t stride_adj, uint32_t G1, int32_t* __restrict__ x1, size_t x_stride,
                          uint32_t* __restrict__ out_wire /* G1 == 1 only */) {
     latency_bound_kernel();
-    __shared__ int32_t lds[LG::ZETA_LDS_WORDS];
-    const uint32_t g = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63, gp = w * LG::GROUPS + lane / LG::LANES;
+    constexpr int NG = LG::WG_GROUPS;
+    __shared__ int32_t lds[LG::SUMS_LDS_WORDS];
+    const uint32_t lane = threadIdx.x & 63, t = threadIdx.x / LG::LANES;      // lane group t: group t / 64 of the workgroup, value t % 64
+    const uint32_t g = blockIdx.x * NG + t / 64, gp = t % 64;
     const typename LG::Role role = LG::role(lane);
     const uint32_t bkt = gp * G1 + g;                   // strided: neighbouring buckets (the few heavy ones of a short top window) go to different workgroups
     uint32_t e = 0, end = 0;
-    if (bkt < B) { e = offs[bkt]; end = offs[bkt + 1]; }
+    if (g < G1 && bkt < B) { e = offs[bkt]; end = offs[bkt + 1]; }
     const uint32_t hb = e, he = end;
     const bool heavy = end - e > LG::FUSED_HEAVY;
     if (heavy) end = e;                                 // summed by the whole wave below
@@ -1453,11 +1455,7 @@ k_msm_bucket_bits1_fused(const uint4* __restrict__ points, const uint32_t* __res
         fused_heavy_bucket<LG>(tot, __shfl(hb, src_lane, 64), __shfl(he, src_lane, 64), lane, points, sorted, idx_log, stride_adj);
         if ((int)(lane & ~(LG::LANES - 1)) == src_lane) v = tot;
     }
-    LG::zeta64(v, lane, w, role, lds);
-    const int zr = zeta_role(gp);
-    if (zr < 0) return;
-    if (G1 == 1) LG::store_wire(out_wire, (size_t)zr, v, role);
-    else LG::store(x1, x_stride, (size_t)zr * G1 + g, v, role);
+    group_sums_out<LG>(v, lane, t, role, lds, G1, x1, x_stride, out_wire);
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -35,11 +35,26 @@ def load(path):
     return {k: sum(v) / len(v) for k, v in agg.items()}
 
 
+def with_bare_names(kernels):
+    """A kernel template that ran in ONE instantiation ("void k_msm_accumulate<false>") is also listed under its bare name
+    ("k_msm_accumulate": what bench.py looks up); a template that ran in several (k_msm_bucket_bits1<PairLanes> / <QuadLanes>) is not."""
+    bare = collections.defaultdict(list)
+    for k in kernels:
+        if "<" in k:
+            bare[k.split("<")[0].replace("void ", "").strip()].append(k)
+    out = dict(kernels)
+    for name, full in bare.items():
+        if len(full) == 1 and name not in out:
+            out[name] = kernels[full[0]]
+    return dict(sorted(out.items()))
+
+
 def main():
     fetch, write = load(sys.argv[1]), load(sys.argv[2])
     out = {"units": "KB per dispatch (average)", "kernels": {}}
     for k in sorted(set(fetch) | set(write)):
         out["kernels"][k] = {"FETCH_SIZE_KB": fetch.get(k), "WRITE_SIZE_KB": write.get(k)}
+    out["kernels"] = with_bare_names(out["kernels"])
     out["log_n"] = int(sys.argv[4]) if len(sys.argv) > 4 else 20          # workload the passes were collected on (bench.py checks it)
     out["kernel_sources"] = list(KERNEL_SOURCES)
     out["kernel_sources_sha256"] = kernel_sources_sha256()                 # of the tree the passes ran on (the snapshot gpurun sent)
