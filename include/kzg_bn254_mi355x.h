@@ -660,6 +660,49 @@ int32_t kzg_verify_multiproof_batch(kzg_ctx* ctx, const kzg_srs* srs, const uint
 int32_t kzg_verify_multiproof(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t commitment_xy_mont[8], const uint64_t proof_xy_mont[8],
                               uint64_t coset_index, const uint64_t* ys_mont, size_t n, size_t chunk_len,
                               const uint64_t* g2_tau_l_mont, int32_t* out_ok);
+/* Locating the bad items of a rejected batch.  The batch equation is linear in the set of items, so for ANY partition of the items into
+ * n_groups groups (group_indices[i] < n_groups is item i's group; a group may be empty) the device produces, in one pass over the batch,
+ * the two G1 sums of every group's own equation:
+ *     L_g     = sum_{i in g} r_i pi_i
+ *     A_{g,t} = sum_{i in g} r_i w^(-k_i t) IFFT_l(ys_i)_t
+ *     R_g     = sum_{i in g} r_i C_{c_i} + sum_{i in g} r_i w^(k_i l) pi_i - sum_t A_{g,t} [tau^t]_1
+ * Group g is good iff e(L_g, [tau^l]_2) = e(R_g, G2).  Summed over all groups (L, R) is exactly the pair kzg_verify_multiproof_batch
+ * checks, so the verdict on the sum of all groups is that entry's verdict for the same inputs and weights.
+ *
+ * kzg_coset_group_sums: the arguments of kzg_verify_multiproof_batch without g2_tau_l_mont and out_ok, the partition, and the outputs
+ * out_lhs_xy_mont / out_rhs_xy_mont (n_groups x 8 u64, affine G1 wire points, canonical words) with out_lhs_is_infinity /
+ * out_rhs_is_infinity (n_groups bytes).  Equal inputs give equal bits, whatever the order of the items inside a group and whatever the
+ * launch geometry.  An empty group gives the identity twice.  r_powers_mont = NULL derives the weights of
+ * kzg_compute_multiproof_r_powers exactly as the batch entry does (device transcript and host fallback included).  The items are sorted
+ * by group on the host as a permutation; the values go up once, in the caller's order.  The n_groups l-point MSMs run as one MSM problem
+ * like kzg_commit_coeff_form_batch_device, and like that call an SRS without per-bit tables gets them on first use: srs is not const.
+ * Errors, in this order: those of kzg_verify_multiproof_batch up to and including the check of coset and commitment indices (a null
+ * group_indices or output counts as a null pointer); a group index >= n_groups, or n_groups = 0 with count > 0 -> KZG_ERR_INVALID_ARG;
+ * count * chunk_len > 2^28 -> KZG_ERR_TOO_LARGE; n_groups > 2^28 -> KZG_ERR_TOO_LARGE (before anything is allocated); a commitment or
+ * proof off the curve -> KZG_ERR_G1_NOT_ON_CURVE.  KZG_ERR_INVALID_ARG also while a kzg_*_begin is in flight (the MSMs use the slots). */
+int32_t kzg_coset_group_sums(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments,
+                             const uint64_t* commitment_indices, const uint64_t* coset_indices, const uint64_t* ys_mont,
+                             const uint64_t* proofs_xy_mont, size_t count, size_t n, size_t chunk_len, const uint64_t* r_powers_mont,
+                             const uint64_t* group_indices, size_t n_groups, uint64_t* out_lhs_xy_mont, uint8_t* out_lhs_is_infinity,
+                             uint64_t* out_rhs_xy_mont, uint8_t* out_rhs_is_infinity);
+/* The group sums above, then a search on the host: prefix sums of the groups' pairs in group order make the pair of any range of groups
+ * a difference of two prefixes; the root is tested first; a range that holds marks all its groups good; a failing range of one group
+ * marks it bad; any other failing range is halved and its left half tested (if that holds, the right half fails without a test).  Each
+ * test is one pairing check (the pooled check of the batch entry) and no GPU work: at most 1 + 2 b ceil(log2 n_groups) checks for b bad
+ * groups, and exactly one for a good batch.  out_group_ok: n_groups bytes, 1 = good; *out_bad_groups = the number of bad groups;
+ * *out_pairing_checks (may be NULL) = the checks made.  KZG_OK with *out_bad_groups = 0 is the accept of kzg_verify_multiproof_batch.
+ * Soundness: a range that holds could in principle hide two bad groups that cancel; with weights derived from the transcript over ALL
+ * inputs (r_powers_mont = NULL, or kzg_compute_multiproof_r_powers) that has negligible probability, with weights of the caller's own
+ * choosing there is no such guarantee.
+ * This entry always pays for the group sums: a caller who expects good batches calls kzg_verify_multiproof_batch first and this one
+ * only after a reject.  count = 0 -> every group good, no device work, no pairing check.
+ * Errors: those of kzg_coset_group_sums in its order (NULL g2_tau_l_mont with chunk_len != 1 where the batch entry reports it), then
+ * g2_tau_l_mont off the twist -> KZG_ERR_G2_TAU_NOT_ON_CURVE. */
+int32_t kzg_verify_multiproof_batch_locate(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments,
+                                           const uint64_t* commitment_indices, const uint64_t* coset_indices, const uint64_t* ys_mont,
+                                           const uint64_t* proofs_xy_mont, size_t count, size_t n, size_t chunk_len,
+                                           const uint64_t* r_powers_mont, const uint64_t* g2_tau_l_mont, const uint64_t* group_indices,
+                                           size_t n_groups, uint8_t* out_group_ok, size_t* out_bad_groups, size_t* out_pairing_checks);
 
 /* ---- erasure decoding: a polynomial from a subset of its cosets ------------------------------------------------------------------
  * The cosets are those above: coset k < m = n / chunk_len is {w^(k + j m) : j < chunk_len}, its values ys[j] = f(w^(k + j m)) (row k

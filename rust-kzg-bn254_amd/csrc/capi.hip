@@ -134,6 +134,8 @@ int32_t msm_srs_common(kzg_ctx* ctx, const kzg_srs* srs, size_t offset, const vo
 // (~0.14-0.2 ms at 512..2048 coefficients: sort, ~13 dependent point additions, host epilogue) per blob.  Here the polynomials share the
 // bases, so they are one MSM problem: width-8 NAF digits over the SRS's per-bit tables, 64 buckets per polynomial in one bucket
 // array (msm.hip msm_run_batch_tables).  An SRS without per-bit tables (fewer than 2^15 points) gets them on the first batched call.
+}  // namespace
+namespace kzg {
 int32_t commit_batch_device(kzg_ctx* ctx, kzg_srs* basis, const void* d_scalars, size_t n, size_t count, uint64_t* out_xy, uint8_t* out_inf) {
     uint4* bits = srs_bits(basis);
     if (!bits) {
@@ -153,6 +155,8 @@ int32_t commit_batch_device(kzg_ctx* ctx, kzg_srs* basis, const void* d_scalars,
     b.points = bits; b.table_stride = (uint32_t)basis->n; b.c = 7; b.W = 255; b.naf = true;
     return msm_run_batch_tables(ctx, b, d_scalars, n, count, out_xy, out_inf);
 }
+}  // namespace kzg
+namespace {
 int32_t commit_batch_common(kzg_ctx* ctx, kzg_srs* srs, const void* scalars, bool on_device, bool eval_form, size_t n, size_t count,
                                    uint64_t* out_xy, uint8_t* out_inf) {
     if (!ctx || !srs || srs->ctx != ctx || !out_xy || (n && count && !scalars)) return KZG_ERR_INVALID_ARG;
@@ -356,6 +360,7 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
     for (auto& b : ctx->mp) b.release();
     ctx->mp_ntt.release();
     for (auto& b : ctx->mv) b.release();
+    for (auto& b : ctx->ml) b.release();
     for (auto& b : ctx->fs) b.release();
     ctx->mv_ntt.release();
     for (auto& b : ctx->rc) b.release();

@@ -353,6 +353,156 @@ int32_t coset_upload_and_derive_weights(kzg_ctx* ctx, const uint64_t* commitment
     return KZG_OK;
 }
 
+// The host checks of kzg_verify_multiproof_batch, in the documented order.  grouped: the entries that take a partition of the items
+// (kzg_coset_group_sums, kzg_verify_multiproof_batch_locate) add the checks of host_locate.h where their table puts them.
+int32_t multiproof_batch_checks(const kzg_ctx* ctx, const kzg_srs* srs, bool output_null, bool input_null, bool g2_missing, size_t n_commitments,
+                                const uint64_t* commitment_indices, const uint64_t* coset_indices, size_t count, size_t n, size_t chunk_len,
+                                const uint64_t* group_indices, size_t n_groups, bool grouped) {
+    if (!ctx || !srs || output_null) return KZG_ERR_INVALID_ARG;
+    if (count && input_null) return KZG_ERR_INVALID_ARG;
+    if (g2_missing) return KZG_ERR_INVALID_ARG;                                          // consts::G2_TAU is [tau]_2 only
+    if (srs->ctx != ctx || srs->lagrange_of != 0) return KZG_ERR_INVALID_ARG;
+    int32_t rc = coset_domain_check(n, chunk_len);
+    if (rc != KZG_OK) return rc;
+    const size_t l = chunk_len, m = n / l;
+    if (l > srs->n) return KZG_ERR_SRS_CAPACITY_EXCEEDED;
+    for (size_t i = 0; i < count; ++i) if (coset_indices[i] >= m || commitment_indices[i] >= n_commitments) return KZG_ERR_INVALID_ARG;
+    if (grouped) { rc = locate_check_groups(group_indices, count, n_groups); if (rc != KZG_OK) return rc; }
+    if (count > ((size_t)1 << 28) / l) return KZG_ERR_TOO_LARGE;
+    if (grouped && n_groups > LOCATE_MAX_GROUPS) return KZG_ERR_TOO_LARGE;
+    return KZG_OK;
+}
+
+// out[i] = r_i w^(k_i l) for the N items (w^l = w_m from a two-level power table); chunks on the host pool
+void coset_shifted_weights(const uint64_t* coset_indices, const uint64_t* r_powers_mont, size_t N, size_t m, uint64_t* out) {
+    using namespace kzg_host;
+    const int log_m = __builtin_ctzll(m), lo_bits = (log_m + 1) / 2, hi_bits = log_m - lo_bits;
+    const uint64_t* wm = fr_roots().w[log_m];
+    std::vector<uint64_t> lo(4 << lo_bits), hi(4 << hi_bits);
+    fr_one(lo.data());
+    for (size_t j = 1; j < ((size_t)1 << lo_bits); ++j) fr_mul(lo.data() + 4 * (j - 1), wm, lo.data() + 4 * j);
+    uint64_t step[4];
+    fr_mul(lo.data() + 4 * (((size_t)1 << lo_bits) - 1), wm, step);                  // w_m^(2^lo_bits)
+    memcpy(hi.data(), lo.data(), 32);
+    for (size_t j = 1; j < ((size_t)1 << hi_bits); ++j) fr_mul(hi.data() + 4 * (j - 1), step, hi.data() + 4 * j);
+    const size_t chunks = N >= 1024 ? 32 : 1, per = (N + chunks - 1) / chunks;
+    auto body = [&](size_t c) {
+        for (size_t i = c * per; i < std::min(N, (c + 1) * per); ++i) {
+            const uint64_t k = coset_indices[i];
+            uint64_t h[4];
+            fr_mul(lo.data() + 4 * (k & (((uint64_t)1 << lo_bits) - 1)), hi.data() + 4 * (k >> lo_bits), h);
+            fr_mul(r_powers_mont + 4 * i, h, out + 4 * i);
+        }
+    };
+    if (chunks > 1) host_parallel_for(chunks, body); else body(0);
+}
+
+// ---- the group sums of a batch of coset proofs (multilocate.hip, host_locate.h) -----------------------------------------------------------
+struct GroupSums {
+    LocatePlan plan;
+    std::vector<kzg_host::Xyzz> lhs, rhs;        // per NON-EMPTY group (plan.segs): L_g, R_g
+};
+
+// The arguments have passed multiproof_batch_checks(.., grouped); count > 0.  Values, indices and weights go up once, in the caller's
+// order; the kernels read through the plan's permutation.  Off-curve points are reported as the batch entry reports them.
+int32_t coset_group_sums_core(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments, const uint64_t* commitment_indices,
+                              const uint64_t* coset_indices, const uint64_t* ys_mont, const uint64_t* proofs_xy_mont, size_t N, size_t n, size_t l,
+                              const uint64_t* r_powers_mont, const uint64_t* group_indices, size_t n_groups, GroupSums* out) {
+    using namespace kzg_host;
+    const bool trace = opts().vb_trace != 0;
+    const auto t0 = Clock::now();
+    int32_t rc = locate_plan(group_indices, N, n_groups, &out->plan);
+    if (rc != KZG_OK) return rc;
+    const LocatePlan& plan = out->plan;
+    const size_t S = plan.segs.size(), M = n_commitments;
+    std::vector<uint64_t> derived;
+    const bool derive = !r_powers_mont;
+    if (derive) { derived.resize(4 * N); r_powers_mont = derived.data(); }
+    const bool on_device = derive && coset_transcript_on_device(ctx->transcript_device.load(std::memory_order_relaxed), N, l);
+    std::unique_lock<std::mutex> lk(ctx->mu, std::defer_lock);
+    uint4* d_w = nullptr;
+    uint64_t* d_k = nullptr;
+    if (on_device) {
+        lk.lock();
+        KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        rc = coset_upload_and_derive_weights(ctx, commitments_xy_mont, M, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, N, n, l, derived.data(), nullptr, nullptr);
+        if (rc != KZG_OK) return rc;
+        d_w = ctx->mv[1].as<uint4>();
+        d_k = reinterpret_cast<uint64_t*>(ctx->mv[1].as<uint8_t>() + N * 32);
+    } else {
+        if (derive) multiproof_r_powers_host(commitments_xy_mont, M, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, N, n, l, derived.data(), host_parallel_for);
+        lk.lock();
+        KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        rc = coset_upload(ctx, ys_mont, coset_indices, r_powers_mont, N, l, &d_w, &d_k);
+        if (rc != KZG_OK) return rc;
+    }
+    // the points, validated on the device on their way into its format: N proofs, then the M commitments
+    KZG_HIP_TRY(ctx, ctx->ml[5].reserve((N + M) * 64));
+    uint32_t off_p = 0, off_c = 0;
+    rc = upload_points(ctx, proofs_xy_mont, N, ctx->ml[5].as<uint4>(), ctx->msm.bases_wire, &off_p);
+    if (rc == KZG_OK && M) rc = upload_points(ctx, commitments_xy_mont, M, ctx->ml[5].as<uint4>() + 4 * N, ctx->msm.bases_wire, &off_c);
+    if (rc != KZG_OK) return rc;
+    if (off_p || off_c) return KZG_ERR_G1_NOT_ON_CURVE;
+    const auto t_up = Clock::now();                                                      // (upload_points synchronises)
+    // 1. the plan, then the coefficients A_{g,t} of every non-empty group (left on the device)
+    rc = locate_upload_plan(ctx, plan);
+    if (rc != KZG_OK) return rc;
+    rc = coset_group_coeffs_device(ctx, ctx->mv[0].as<uint4>(), d_k, d_w, plan, n, l);
+    if (rc != KZG_OK) return rc;
+    // 2. host scalars r_i w^(k_i l) beside those kernels; they and the commitment rows go up for the point sums
+    std::vector<uint64_t> shifted(4 * N);
+    coset_shifted_weights(coset_indices, r_powers_mont, N, n / l, shifted.data());
+    KZG_HIP_TRY(ctx, ctx->ml[4].reserve(N * 40));
+    uint4* d_w2 = ctx->ml[4].as<uint4>();
+    uint64_t* d_ci = reinterpret_cast<uint64_t*>(ctx->ml[4].as<uint8_t>() + N * 32);
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(d_w2, shifted.data(), N * 32, hipMemcpyHostToDevice, ctx->stream));
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(d_ci, commitment_indices, N * 8, hipMemcpyHostToDevice, ctx->stream));
+    KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                                 // the MSM launches run on the slots' streams
+    const auto t_interp = Clock::now();
+    // 3. [sum_t A_{g,t} tau^t]_1 for every non-empty group: S polynomials of l coefficients as one MSM problem
+    std::vector<uint64_t> interp_xy(8 * S);
+    rc = commit_batch_device(ctx, srs, ctx->ml[0].p, l, S, interp_xy.data(), nullptr);
+    if (rc != KZG_OK) return rc;
+    const auto t_msm = Clock::now();
+    // 4. the segmented point sums
+    std::vector<uint64_t> sums(32 * S);
+    rc = locate_point_sums_device(ctx, ctx->ml[5].as<uint4>(), d_ci, d_w, d_w2, plan, sums.data());
+    if (rc != KZG_OK) return rc;
+    lk.unlock();
+    const auto t_pts = Clock::now();
+    // 5. R_g = (point sum) - (interpolation commitment)
+    out->lhs.resize(S);
+    out->rhs.resize(S);
+    const size_t per = 256, jobs = (S + per - 1) / per;
+    auto body = [&](size_t c) {
+        for (size_t j = c * per; j < std::min(S, (c + 1) * per); ++j) {
+            Xyzz b;
+            memcpy(&out->lhs[j], sums.data() + 32 * j, 128);
+            memcpy(&b, sums.data() + 32 * j + 16, 128);
+            Xyzz i = xyzz_from_affine_wire(interp_xy.data() + 8 * j);
+            i.y = neg(i.y);
+            out->rhs[j] = xyzz_add(b, i);
+        }
+    };
+    if (jobs > 1) host_parallel_for(jobs, body); else if (jobs) body(0);
+    if (trace)
+        fprintf(stderr, "coset_group_sums N=%zu l=%zu M=%zu groups=%zu (non-empty %zu): plan + r_powers + upload %.3f ms, interpolation + segment sums %.3f ms, "
+                "coefficient MSMs %.3f ms, point sums %.3f ms, host sums %.3f ms\n", N, l, M, n_groups, S, ms_between(t0, t_up), ms_between(t_up, t_interp),
+                ms_between(t_interp, t_msm), ms_between(t_msm, t_pts), ms_between(t_pts, Clock::now()));
+    return KZG_OK;
+}
+
+// count points -> affine wire words and identity flags, one inversion per 256 points, chunks on the host pool
+void xyzz_to_affine_many(const kzg_host::Xyzz* p, size_t count, uint64_t* out_xy, uint8_t* out_inf) {
+    const size_t per = 256, jobs = (count + per - 1) / per;
+    auto body = [&](size_t c) {
+        const size_t a = c * per, b = std::min(count, (c + 1) * per);
+        kzg_host::xyzz_batch_to_affine(p + a, b - a, out_xy + 8 * a);
+        for (size_t j = a; j < b; ++j) out_inf[j] = kzg_host::is_inf(p[j]) ? 1 : 0;
+    };
+    if (jobs > 1) host_parallel_for(jobs, body); else if (jobs) body(0);
+}
+
 }  // namespace
 
 extern "C" {
@@ -530,16 +680,10 @@ int32_t kzg_verify_multiproof_batch(kzg_ctx* ctx, const kzg_srs* srs, const uint
                                     const uint64_t* proofs_xy_mont, size_t count, size_t n, size_t chunk_len,
                                     const uint64_t* r_powers_mont, const uint64_t* g2_tau_l_mont, int32_t* out_ok) {
     using namespace kzg_host;
-    if (!ctx || !srs || !out_ok) return KZG_ERR_INVALID_ARG;
-    if (count && (!commitments_xy_mont || !commitment_indices || !coset_indices || !ys_mont || !proofs_xy_mont)) return KZG_ERR_INVALID_ARG;
-    if (!g2_tau_l_mont && chunk_len != 1) return KZG_ERR_INVALID_ARG;                     // consts::G2_TAU is [tau]_2 only
-    if (srs->ctx != ctx || srs->lagrange_of != 0) return KZG_ERR_INVALID_ARG;
-    int32_t rc = coset_domain_check(n, chunk_len);
+    int32_t rc = multiproof_batch_checks(ctx, srs, !out_ok, !commitments_xy_mont || !commitment_indices || !coset_indices || !ys_mont || !proofs_xy_mont,
+                                         !g2_tau_l_mont && chunk_len != 1, n_commitments, commitment_indices, coset_indices, count, n, chunk_len, nullptr, 0, false);
     if (rc != KZG_OK) return rc;
     const size_t l = chunk_len, m = n / l, N = count;
-    if (l > srs->n) return KZG_ERR_SRS_CAPACITY_EXCEEDED;
-    for (size_t i = 0; i < N; ++i) if (coset_indices[i] >= m || commitment_indices[i] >= n_commitments) return KZG_ERR_INVALID_ARG;
-    if (N > ((size_t)1 << 28) / l) return KZG_ERR_TOO_LARGE;
     if (N == 0) { *out_ok = 1; return KZG_OK; }
     const bool trace = opts().vb_trace != 0;
     const auto t0 = Clock::now();
@@ -596,25 +740,7 @@ int32_t kzg_verify_multiproof_batch(kzg_ctx* ctx, const kzg_srs* srs, const uint
     // 3. host scalars: r_i w^(k_i l) (w^l = w_m from a two-level power table) and the row sums of the weights
     std::vector<uint64_t> bases(2 * N * 8), scalars(2 * N * 4), row_w(4 * n_commitments, 0);
     {
-        const int log_m = __builtin_ctzll(m), lo_bits = (log_m + 1) / 2, hi_bits = log_m - lo_bits;
-        const uint64_t* wm = fr_roots().w[log_m];
-        std::vector<uint64_t> lo(4 << lo_bits), hi(4 << hi_bits);
-        fr_one(lo.data());
-        for (size_t j = 1; j < ((size_t)1 << lo_bits); ++j) fr_mul(lo.data() + 4 * (j - 1), wm, lo.data() + 4 * j);
-        uint64_t step[4];
-        fr_mul(lo.data() + 4 * (((size_t)1 << lo_bits) - 1), wm, step);                  // w_m^(2^lo_bits)
-        memcpy(hi.data(), lo.data(), 32);
-        for (size_t j = 1; j < ((size_t)1 << hi_bits); ++j) fr_mul(hi.data() + 4 * (j - 1), step, hi.data() + 4 * j);
-        const size_t chunks = N >= 1024 ? 32 : 1, per = (N + chunks - 1) / chunks;
-        auto body = [&](size_t c) {
-            for (size_t i = c * per; i < std::min(N, (c + 1) * per); ++i) {
-                const uint64_t k = coset_indices[i];
-                uint64_t h[4];
-                fr_mul(lo.data() + 4 * (k & (((uint64_t)1 << lo_bits) - 1)), hi.data() + 4 * (k >> lo_bits), h);
-                fr_mul(r_powers_mont + 4 * i, h, scalars.data() + (N + i) * 4);
-            }
-        };
-        if (chunks > 1) host_parallel_for(chunks, body); else body(0);
+        coset_shifted_weights(coset_indices, r_powers_mont, N, m, scalars.data() + N * 4);
         for (size_t i = 0; i < N; ++i) { uint64_t* rw = row_w.data() + 4 * commitment_indices[i]; fr_add(rw, r_powers_mont + 4 * i, rw); }
         memcpy(scalars.data(), r_powers_mont, N * 32);
         memcpy(bases.data(), proofs_xy_mont, N * 64);
@@ -650,6 +776,94 @@ int32_t kzg_verify_multiproof(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t c
     uint64_t one_w[4];
     kzg_host::fr_one(one_w);
     return kzg_verify_multiproof_batch(ctx, srs, commitment_xy_mont, 1, &zero, &coset_index, ys_mont, proof_xy_mont, 1, n, chunk_len, one_w, g2_tau_l_mont, out_ok);
+}
+
+// For every group g of a partition of the items: L_g = sum_{i in g} r_i pi_i and R_g = sum_{i in g} (r_i C_{c_i} + r_i w^(k_i l) pi_i) -
+// sum_t A_{g,t} [tau^t]_1; group g is good iff e(L_g, [tau^l]_2) = e(R_g, G2), and summed over the groups (L, R) is the (lhs, rhs) of
+// kzg_verify_multiproof_batch above.
+int32_t kzg_coset_group_sums(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments, const uint64_t* commitment_indices,
+                             const uint64_t* coset_indices, const uint64_t* ys_mont, const uint64_t* proofs_xy_mont, size_t count, size_t n, size_t chunk_len,
+                             const uint64_t* r_powers_mont, const uint64_t* group_indices, size_t n_groups, uint64_t* out_lhs_xy_mont,
+                             uint8_t* out_lhs_is_infinity, uint64_t* out_rhs_xy_mont, uint8_t* out_rhs_is_infinity) {
+    const bool out_null = n_groups && (!out_lhs_xy_mont || !out_lhs_is_infinity || !out_rhs_xy_mont || !out_rhs_is_infinity);
+    int32_t rc = multiproof_batch_checks(ctx, srs, out_null, !commitments_xy_mont || !commitment_indices || !coset_indices || !ys_mont || !proofs_xy_mont || !group_indices,
+                                         false, n_commitments, commitment_indices, coset_indices, count, n, chunk_len, group_indices, n_groups, true);
+    if (rc != KZG_OK) return rc;
+    GroupSums gs;
+    if (count) {
+        rc = coset_group_sums_core(ctx, srs, commitments_xy_mont, n_commitments, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, count, n, chunk_len,
+                                   r_powers_mont, group_indices, n_groups, &gs);
+        if (rc != KZG_OK) return rc;
+    }
+    if (n_groups) {                                                                      // an empty group: the identity twice
+        memset(out_lhs_xy_mont, 0, n_groups * 64);
+        memset(out_rhs_xy_mont, 0, n_groups * 64);
+        memset(out_lhs_is_infinity, 1, n_groups);
+        memset(out_rhs_is_infinity, 1, n_groups);
+    }
+    const size_t S = gs.plan.segs.size();
+    std::vector<uint64_t> xy(8 * S);
+    std::vector<uint8_t> inf(S);
+    for (int side = 0; side < 2; ++side) {
+        xyzz_to_affine_many(side ? gs.rhs.data() : gs.lhs.data(), S, xy.data(), inf.data());
+        uint64_t* out_xy = side ? out_rhs_xy_mont : out_lhs_xy_mont;
+        uint8_t* out_inf = side ? out_rhs_is_infinity : out_lhs_is_infinity;
+        for (size_t j = 0; j < S; ++j) {
+            memcpy(out_xy + 8 * (size_t)gs.plan.segs[j], xy.data() + 8 * j, 64);
+            out_inf[gs.plan.segs[j]] = inf[j];
+        }
+    }
+    return KZG_OK;
+}
+
+int32_t kzg_verify_multiproof_batch_locate(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments,
+                                           const uint64_t* commitment_indices, const uint64_t* coset_indices, const uint64_t* ys_mont,
+                                           const uint64_t* proofs_xy_mont, size_t count, size_t n, size_t chunk_len, const uint64_t* r_powers_mont,
+                                           const uint64_t* g2_tau_l_mont, const uint64_t* group_indices, size_t n_groups, uint8_t* out_group_ok,
+                                           size_t* out_bad_groups, size_t* out_pairing_checks) {
+    using namespace kzg_host;
+    int32_t rc = multiproof_batch_checks(ctx, srs, !out_bad_groups || (n_groups && !out_group_ok),
+                                         !commitments_xy_mont || !commitment_indices || !coset_indices || !ys_mont || !proofs_xy_mont || !group_indices,
+                                         !g2_tau_l_mont && chunk_len != 1, n_commitments, commitment_indices, coset_indices, count, n, chunk_len, group_indices, n_groups, true);
+    if (rc != KZG_OK) return rc;
+    if (count == 0) {                                                                    // nothing to refuse: no device work, no pairing
+        if (n_groups) memset(out_group_ok, 1, n_groups);
+        *out_bad_groups = 0;
+        if (out_pairing_checks) *out_pairing_checks = 0;
+        return KZG_OK;
+    }
+    G2 g2_tau_l;
+    const bool g2_ok = load_g2_tau(g2_tau_l_mont, &g2_tau_l);                            // reported after an off-curve G1 point, as the batch entry does
+    GroupSums gs;
+    rc = coset_group_sums_core(ctx, srs, commitments_xy_mont, n_commitments, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, count, n, chunk_len,
+                               r_powers_mont, group_indices, n_groups, &gs);
+    if (rc != KZG_OK) return rc;
+    if (!g2_ok) return KZG_ERR_G2_TAU_NOT_ON_CURVE;
+    // the search runs over the non-empty groups: an empty group's pair is the identity twice, it holds and changes no range
+    const auto t0 = Clock::now();
+    struct Ops {
+        Xyzz zero() const { return xyzz_inf(); }
+        Xyzz add(const Xyzz& a, const Xyzz& b) const { return xyzz_add(a, b); }
+        Xyzz sub(const Xyzz& a, Xyzz b) const { b.y = neg(b.y); return xyzz_add(a, b); }
+    };
+    const G2 g2 = g2_generator();
+    auto holds = [&](const Xyzz& lhs, const Xyzz& rhs) {
+        uint64_t a[8], b[8];
+        xyzz_to_affine(lhs, a, nullptr);
+        xyzz_to_affine(rhs, b, nullptr);
+        return pairings_verify_pooled(g1_from_wire(a), g2_tau_l, g1_from_wire(b), g2);
+    };
+    const size_t S = gs.plan.segs.size();
+    std::vector<uint8_t> seg_ok(S, 1);
+    size_t bad = 0;
+    const size_t checks = locate_search(gs.lhs.data(), gs.rhs.data(), S, Ops(), holds, seg_ok.data(), &bad);
+    memset(out_group_ok, 1, n_groups);
+    for (size_t j = 0; j < S; ++j) out_group_ok[gs.plan.segs[j]] = seg_ok[j];
+    *out_bad_groups = bad;
+    if (out_pairing_checks) *out_pairing_checks = checks;
+    if (opts().vb_trace)
+        fprintf(stderr, "kzg_verify_multiproof_batch_locate groups=%zu: search %.3f ms, %zu pairing checks, %zu bad groups\n", n_groups, ms_between(t0, Clock::now()), checks, bad);
+    return KZG_OK;
 }
 
 // verify::verify_blob_kzg_proof (verifier/src/verify.rs:76-98) in one call: validate both points, z = compute_challenge(blob, commitment),

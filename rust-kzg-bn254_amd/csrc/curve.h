@@ -190,6 +190,19 @@ KZG_HD void xyzz_add(Xyzz& r, const Xyzz& a, const Xyzz& b) {
     r.x = v; r.y = y3; r.inf = false;
 }
 
+#if defined(__HIPCC__)
+// the value of lane + d of the wave (a lane without such a partner gets its own value back)
+__device__ __forceinline__ void xyzz_shfl_down(Xyzz& r, const Xyzz& v, int d) {
+    const Fq* s[4] = {&v.x, &v.y, &v.zz, &v.zzz};
+    Fq* t[4] = {&r.x, &r.y, &r.zz, &r.zzz};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int j = 0; j < NL; ++j) t[q]->l[j] = __shfl_down(s[q]->l[j], d, 64);
+    r.inf = __shfl_down((int)v.inf, d, 64) != 0;
+}
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // Memory formats
 // ---------------------------------------------------------------------------------------------

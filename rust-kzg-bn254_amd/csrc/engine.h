@@ -12,6 +12,7 @@
 #include "msm_plan.h"      // MsmBasesShape, msm_batch_capacity
 #include "host_recover.h"  // RecoverPlan
 #include "host_encode.h"   // EncodePlan
+#include "host_locate.h"   // LocatePlan
 
 namespace kzg {
 
@@ -133,7 +134,8 @@ struct kzg_ctx {
     kzg::NttWorkspace mp_ntt;
     kzg::DeviceBuffer mv[4];                   // kzg_coset_interpolate_rlc / kzg_verify_multiproof_batch (multiverify.hip): values | indices + weights | coefficients | partial rows
     kzg::NttWorkspace mv_ntt;
-    kzg::DeviceBuffer fs[2];                   // the coset transcript on the device (fsdevice.hip): commitment rows | proofs, digests | power tables | flag; kzg_sha256_rows: messages, digests
+    kzg::DeviceBuffer ml[6];                   // kzg_coset_group_sums / kzg_verify_multiproof_batch_locate (multilocate.hip): group coefficients | the plan's arrays | partial point sums | group sums | rows + shifted weights | proofs + commitments
+    kzg::DeviceBuffer fs[2];                  // the coset transcript on the device (fsdevice.hip): commitment rows | proofs, digests | power tables | flag; kzg_sha256_rows: messages, digests
     kzg::DeviceBuffer rc[3];                   // kzg_recover_from_cosets (recover.hip): work values | indices, vanishing values, partial products, flag | powers of g
     int rc_gpow_log = -1;                      // rc[2] holds the factored tables of g^t and g^-t for t < 2^rc_gpow_log (-1: none yet)
     kzg::NttWorkspace rc_ntt;                  // its `data` also stages the uploaded coset values (dead before the first transform)
@@ -313,6 +315,13 @@ void multiproof_drop(kzg_srs* srs);
 int32_t multiproof_encode(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, bool eval_form, const EncodePlan& plan, uint64_t* out_ys, uint64_t* out_xy, uint8_t* out_inf);
 // verification of coset proofs (multiverify.hip): d_out[t] = sum_i weights[i] w^(-ks[i] t) IFFT_l(ys_i)[t], enqueued on ctx->stream (d_ys is scratch when l > 1024)
 int32_t coset_interpolate_rlc_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, size_t count, size_t n, size_t l, uint4* d_out);
+// locating the bad groups of a batch (multilocate.hip; LocatePlan: host_locate.h).  Called under ctx->mu with the device set, count > 0.
+// the plan's arrays -> ctx->ml[1] (enqueued); the coefficients A_{g,t} of every non-empty group -> ctx->ml[0], d_ys overwritten (enqueued);
+// per non-empty group the XYZZ wire words of sum r_i pi_i and sum (r_i C_{c_i} + r_i w^(k_i l) pi_i) -> out_xyzz, 2 x 16 u64 each (synchronised)
+int32_t locate_upload_plan(kzg_ctx* ctx, const LocatePlan& plan);
+int32_t coset_group_coeffs_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, const LocatePlan& plan, size_t n, size_t l);
+int32_t locate_point_sums_device(kzg_ctx* ctx, const uint4* d_points, const uint64_t* d_ci, const uint4* d_w, const uint4* d_w2, const LocatePlan& plan,
+                                 uint64_t* out_xyzz);
 // hashing on the device (fsdevice.hip).  Called under ctx->mu with the device set.
 // count messages of row_len bytes each (host, stride row_len) -> count SHA-256 digests (host); synchronised on return
 int32_t sha256_rows_run(kzg_ctx* ctx, const uint8_t* msgs, size_t row_len, size_t count, uint8_t* out_digests);
@@ -360,6 +369,10 @@ int32_t msm_g1_batch_locked(kzg_ctx* ctx, const uint64_t* bases_xy_mont, const u
                             uint64_t* out_xy_mont, uint8_t* out_is_infinity, uint32_t* off_curve);
 int32_t msm_g1_batch_impl(kzg_ctx* ctx, const uint64_t* bases_xy_mont, const uint64_t* scalars_mont, size_t n, size_t batch,
                           uint64_t* out_xy_mont, uint8_t* out_is_infinity, uint32_t* off_curve);
+// `count` polynomials of n coefficients each (device, wire form, one after the other) committed over the first n points of one SRS as ONE
+// MSM problem (capi.hip: the body of kzg_commit_coeff_form_batch_device; builds the SRS's per-bit tables on first use).  The caller holds
+// ctx->mu, has set the device, and the scalars are complete (the launches run on the slots' streams)
+int32_t commit_batch_device(kzg_ctx* ctx, kzg_srs* basis, const void* d_scalars, size_t n, size_t count, uint64_t* out_xy, uint8_t* out_inf);
 // wire points of the host -> device format at d_out through `staging`, synchronised on return (capi_srs.hip)
 int32_t upload_points(kzg_ctx* ctx, const uint64_t* xy, size_t n, uint4* d_out, DeviceBuffer& staging, uint32_t* off_curve = nullptr);
 

@@ -133,4 +133,18 @@ __device__ __forceinline__ void xyzz_scalar_mul(Xyzz& r, const Xyzz& p, const ui
     r = acc;
 }
 
+// [s] P with s a wire Fr scalar and P a device-format affine point (identity: zeros)
+__device__ __forceinline__ void glv_term(Xyzz& r, const uint4* __restrict__ scalar, const uint4* __restrict__ point) {
+    Affine p;
+    if (!affine_load(p, point)) { xyzz_set_inf(r); return; }
+    const uint4 lo = scalar[0], hi = scalar[1];
+    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    uint32_t kc[8], kk[8];
+    fe_wire_to_canonical_words<FrParams>(kc, w);
+    glv_decompose(kk, kc);
+    Xyzz base;
+    xyzz_from_affine(base, p, 0);
+    xyzz_scalar_mul(r, base, kk);
+}
+
 }  // namespace kzg

@@ -736,15 +736,6 @@ k_sort2_bin(const uint32_t* __restrict__ tmp1, const uint32_t* __restrict__ csta
 constexpr uint32_t RUN_SERIAL = KZG_RUN_SERIAL;        // continuation lanes a bucket's owner adds one by one
 constexpr uint32_t NP_SERIAL = 10;        // partials (head included) above which a wave sums a bucket cooperatively
 
-__device__ __forceinline__ void xyzz_shfl_down(Xyzz& r, const Xyzz& v, int d) {
-    const Fq* s[4] = {&v.x, &v.y, &v.zz, &v.zzz};
-    Fq* t[4] = {&r.x, &r.y, &r.zz, &r.zzz};
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int j = 0; j < NL; ++j) t[q]->l[j] = __shfl_down(s[q]->l[j], d, 64);
-    r.inf = __shfl_down((int)v.inf, d, 64) != 0;
-}
 __device__ __forceinline__ uint32_t acc_seg_len(uint32_t E, uint32_t nl) { return (E + nl - 1) / nl; }
 
 // experiment switch: -DKZG_ACC_NOGATHER makes every lane read the same few table points (no HBM gather) to time the arithmetic alone

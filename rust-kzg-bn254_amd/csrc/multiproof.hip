@@ -63,27 +63,13 @@ k_fk20_scatter_coeffs(const uint4* __restrict__ f, uint32_t m, uint32_t l, uint4
     F[2 * (size_t)i + 1] = hi;
 }
 
-// [s] P with s a wire Fr scalar and P a device-format affine point (identity: zeros)
-__device__ __forceinline__ void fk20_term(Xyzz& r, const uint4* __restrict__ scalar, const uint4* __restrict__ point) {
-    Affine p;
-    if (!affine_load(p, point)) { xyzz_set_inf(r); return; }
-    const uint4 lo = scalar[0], hi = scalar[1];
-    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    uint32_t kc[8], kk[8];
-    fe_wire_to_canonical_words<FrParams>(kc, w);
-    glv_decompose(kk, kc);
-    Xyzz base;
-    xyzz_from_affine(base, p, 0);
-    xyzz_scalar_mul(r, base, kk);
-}
-
 // l = 1: H_t = Fhat_t Shat_t, one lane per frequency
 __global__ void __launch_bounds__(256)
 k_fk20_pointwise(const uint4* __restrict__ fhat, const uint4* __restrict__ shat, uint32_t M, int32_t* __restrict__ out) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= M) return;
     Xyzz r;
-    fk20_term(r, fhat + 2 * (size_t)t, shat + 4 * (size_t)t);
+    glv_term(r, fhat + 2 * (size_t)t, shat + 4 * (size_t)t);
     xyzz_store(out, M, t, r);
 }
 
@@ -102,7 +88,7 @@ k_fk20_lincomb(const uint4* __restrict__ fhat, const uint4* __restrict__ shat, u
         for (uint32_t i = 0; i < tpl; ++i) {
             const size_t e = (size_t)((w * tpl + i) * G + g) * M + o;   // term b, frequency o of the l x M arrays
             Xyzz term, s;
-            fk20_term(term, fhat + 2 * e, shat + 4 * e);
+            glv_term(term, fhat + 2 * e, shat + 4 * e);
             xyzz_add<true>(s, acc, term);
             acc = s;
         }

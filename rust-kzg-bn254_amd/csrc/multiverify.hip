@@ -9,7 +9,7 @@
 // sum_i r^i y_i of its batch verifier (verifier/src/batch.rs:228-254).
 //
 // Shapes chosen:
-//   * l <= 1024 (k_coset_interp): one pass over the input, everything else in LDS.  A workgroup of 256 lanes takes tiles of E = 512
+//   * l <= 1024 (k_coset_interp, in coset_kernels.h: multilocate.hip runs its segmented form): one pass over the input, everything else in LDS.  A workgroup of 256 lanes takes tiles of E = 512
 //     values (l <= 512: E / l cosets side by side, 512 at l = 1, 32 at l = 16; one butterfly per lane and stage) or E = 1024 (l = 1024:
 //     one coset, two butterflies per lane), tile after tile with stride gridDim: unpack (no product: the values stay in the wire
 //     residue class a 2^256, the twiddles are internal Montgomery, as in ntt.hip), bit-reversed fill, log l radix-2 stages on 9 limb
@@ -25,188 +25,11 @@
 // is bit-reversed: 2-way and worse bank conflicts there), wave shuffles for the first six stages, a per-coset w^(-k) power chain in
 // place of the table product, more than one tile in flight per workgroup.
 // Measured figures: profiles/multiproof_verify.md.
-#include "engine.h"
-#include "field29.h"
+#include "coset_kernels.h"   // MvTables, MvArgs, k_coset_interp and the helpers below its name (shared with multilocate.hip)
 
 #include <algorithm>
 
 namespace kzg {
-
-struct MvTables { const int32_t* lo; const int32_t* hi; uint32_t lo_len, hi_len; int lo_bits; };
-
-__device__ __forceinline__ void mv_planes_load(Fr& v, const int32_t* planes, uint32_t stride, uint32_t i) {
-#pragma unroll
-    for (int j = 0; j < NL; ++j) v.l[j] = planes[j * stride + i];
-}
-__device__ __forceinline__ void mv_planes_store(int32_t* planes, uint32_t stride, uint32_t i, const Fr& v) {
-#pragma unroll
-    for (int j = 0; j < NL; ++j) planes[j * stride + i] = v.l[j];
-}
-// w_n^-e (e < n) from the inverse tables of the domain: normalised, in (-m, 2m)
-__device__ __forceinline__ void mv_root_pow(Fr& w, const MvTables& t, uint32_t e) {
-    mv_planes_load(w, t.lo, t.lo_len, e & (t.lo_len - 1));
-    const uint32_t eh = e >> t.lo_bits;
-    if (eh != 0) {
-        Fr h;
-        mv_planes_load(h, t.hi, t.hi_len, eh);
-        fe_mul(w, w, h);
-    }
-}
-// the 256-bit words of a wire element as limbs, no product: < 2^256 < 5.3 m, normalised
-__device__ __forceinline__ void mv_load_words(Fr& v, const uint4* __restrict__ p) {
-    const uint4 lo = p[0], hi = p[1];
-    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    fe_unpack(v, w);
-}
-// acc += v with v normalised in (-m, 2m); every 32nd sum is reduced (|acc| < 2 m + 32 * 2 m = 66 m < 169 m), the others normalised
-__device__ __forceinline__ void mv_lazy_add(Fr& acc, const Fr& v, bool reduce) {
-    fe_add(acc, acc, v);
-    if (reduce) fe_reduce(acc); else fe_norm(acc);
-}
-// x[p] += x[p + span] for span = E / 2 .. width: the E / width column groups of the planes folded into the first; operands normalised
-// in (-m, 2m), sums < 4 m reduced to (-0.0001 m, 1.0001 m) again (fe_reduce_small)
-__device__ __forceinline__ void mv_fold(int32_t* x, uint32_t E, uint32_t width, uint32_t tid) {
-    for (uint32_t span = E >> 1; span >= width; span >>= 1) {
-        for (uint32_t p = tid; p < span; p += 256) {
-            Fr a, b;
-            mv_planes_load(a, x, E, p);
-            mv_planes_load(b, x, E, p + span);
-            fe_add(a, a, b);
-            fe_reduce_small(a);
-            mv_planes_store(x, E, p, a);
-        }
-        __syncthreads();
-    }
-}
-
-struct MvArgs {
-    const uint4* ys;            // count x l wire values
-    const uint64_t* ks;         // count coset indices (< n / l, checked by the host)
-    const uint4* weights;       // count wire weights
-    uint32_t count;
-    int log_l, log_n;
-    uint32_t tiles;             // ceil(count / (E / l))
-    MvTables tb;                // inverse tables of the n-point domain
-    int32_t* partial;           // gridDim rows of 9 planes of l words
-};
-
-// dynamic LDS: x 9 x E | scale 9 x (E / l) | stage twiddles 9 x max(l / 2, 1) | coset index E / l
-template <int EPT>
-__global__ void __launch_bounds__(256)
-k_coset_interp(MvArgs a) {
-    extern __shared__ int32_t mv_lds[];
-    constexpr uint32_t E = 256u * EPT;
-    const uint32_t tid = threadIdx.x, l = 1u << a.log_l, cpt = E >> a.log_l, half = l >> 1, ntw = half ? half : 1u;
-    const uint32_t n_mask = (1u << a.log_n) - 1u;
-    int32_t* x = mv_lds;
-    int32_t* sc = x + NL * E;
-    int32_t* tw = sc + NL * cpt;
-    uint32_t* kk = reinterpret_cast<uint32_t*>(tw + NL * ntw);
-    for (uint32_t q = tid; q < half; q += 256) {                    // w_l^-q = w_n^(-q m)
-        Fr w;
-        mv_root_pow(w, a.tb, q << (a.log_n - a.log_l));
-        mv_planes_store(tw, ntw, q, w);
-    }
-    Fr acc[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) fe_set_zero(acc[e]);
-    uint32_t pending = 0;
-#pragma unroll 1
-    for (uint32_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
-        const uint32_t first = tile * cpt;
-        // per coset: r_i / l in internal form (zero past the end), k_i
-        for (uint32_t c = tid; c < cpt; c += 256) {
-            const uint32_t i = first + c;
-            Fr s;
-            uint32_t k = 0;
-            fe_set_zero(s);
-            if (i < a.count) {
-                Fr t;
-                mv_load_words(t, a.weights + 2 * (size_t)i);
-                Fr kin;
-#pragma unroll
-                for (int j = 0; j < NL; ++j) kin.l[j] = (int32_t)FrParams::K_IN[j];
-                fe_mul(s, t, kin);                                   // wire -> internal: (-m, 2m)
-                if (a.log_l) {
-                    Fr ninv;
-#pragma unroll
-                    for (int j = 0; j < NL; ++j) ninv.l[j] = (int32_t)FrParams::NINV[a.log_l * NL + j];
-                    fe_mul(s, s, ninv);
-                }
-                k = (uint32_t)a.ks[i];
-            }
-            mv_planes_store(sc, cpt, c, s);
-            kk[c] = k;
-        }
-        // values: coset c of the tile at [c l, (c + 1) l), entry j at the bit-reversed position
-#pragma unroll
-        for (int e = 0; e < EPT; ++e) {
-            const uint32_t p = tid + 256u * e, c = p >> a.log_l, j = p & (l - 1), i = first + c;
-            Fr v;
-            fe_set_zero(v);
-            if (i < a.count) mv_load_words(v, a.ys + 2 * (((size_t)i << a.log_l) + j));
-            const uint32_t rj = a.log_l ? __brev(j) >> (32 - a.log_l) : 0u;
-            mv_planes_store(x, E, (c << a.log_l) + rj, v);
-        }
-        __syncthreads();
-        // log l decimation-in-time stages.  Bounds: inputs < 2^256 < 5.3 m; stage 0 (every twiddle 1) adds and subtracts them: < 10.6 m;
-        // from stage 1 on b w is in (-m, 2m), so a value grows by 2 m per stage: < 10.6 m + 9 * 2 m = 28.6 m, and |b w| < 58 m^2 < 169 m^2.
-        // Every value is stored normalised.
-#pragma unroll 1
-        for (int s = 0; s < a.log_l; ++s) {
-            const uint32_t h = 1u << s;
-#pragma unroll 1
-            for (uint32_t bi = tid; bi < E / 2; bi += 256) {
-                const uint32_t q = bi & (h - 1), base = ((bi >> s) << (s + 1)) + q;
-                Fr u, v, r0, r1;
-                mv_planes_load(u, x, E, base);
-                mv_planes_load(v, x, E, base + h);
-                if (s != 0) {
-                    Fr w;
-                    mv_planes_load(w, tw, ntw, q << (a.log_l - 1 - s));
-                    fe_mul(v, v, w);
-                }
-                fe_add(r0, u, v);
-                fe_sub(r1, u, v);
-                fe_norm(r0);
-                fe_norm(r1);
-                mv_planes_store(x, E, base, r0);
-                mv_planes_store(x, E, base + h, r1);
-            }
-            __syncthreads();
-        }
-        // entry t of coset c times r_i l^-1 w^(-k_i t), summed per lane across tiles
-        const bool reduce = ++pending == 32;
-        if (reduce) pending = 0;
-#pragma unroll
-        for (int e = 0; e < EPT; ++e) {
-            const uint32_t p = tid + 256u * e, c = p >> a.log_l, t = p & (l - 1);
-            Fr v, s;
-            mv_planes_load(v, x, E, p);
-            mv_planes_load(s, sc, cpt, c);
-            const uint32_t ex = (uint32_t)(((uint64_t)kk[c] * (uint64_t)t) & (uint64_t)n_mask);
-            if (ex != 0) {
-                Fr w;
-                mv_root_pow(w, a.tb, ex);
-                fe_mul(s, s, w);
-            }
-            fe_mul(v, v, s);                                         // |v s| < 28.6 m * 2 m
-            mv_lazy_add(acc[e], v, reduce);
-        }
-        __syncthreads();                                             // the next tile overwrites x, sc, kk
-    }
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-        fe_reduce(acc[e]);                                           // |acc| < 66 m -> (-m, 2m), normalised
-        mv_planes_store(x, E, tid + 256u * e, acc[e]);
-    }
-    __syncthreads();
-    mv_fold(x, E, l, tid);
-    int32_t* row = a.partial + (size_t)blockIdx.x * NL * l;
-    for (uint32_t t = tid; t < l; t += 256)
-#pragma unroll
-        for (int j = 0; j < NL; ++j) row[(size_t)j * l + t] = x[j * E + t];
-}
 
 // out[t] = sum of the `rows` partial rows at column t, canonical wire words.  A workgroup takes cb = min(l, 256) columns with 256 / cb
 // row groups, folded by the tree of k_coset_interp.
@@ -279,9 +102,6 @@ k_coset_twist_sum_global(const uint4* __restrict__ rows, const uint64_t* __restr
     out[2 * (size_t)t + 1] = make_uint4(o[4], o[5], o[6], o[7]);
 }
 
-constexpr size_t MV_LDS_MAX_L = 1024;
-constexpr uint32_t MV_MAX_GROUPS = 1024;
-
 // Enqueued on ctx->stream, called under ctx->mu with the arguments checked (capi_verify.hip): d_ys count x l wire values (OVERWRITTEN when
 // l > 1024), d_ks count indices < n / l, d_weights count wire scalars -> d_out l canonical wire coefficients
 int32_t coset_interpolate_rlc_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, size_t count, size_t n, size_t l, uint4* d_out) {
@@ -311,7 +131,8 @@ int32_t coset_interpolate_rlc_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* 
     MvArgs a;
     a.ys = d_ys; a.ks = d_ks; a.weights = d_weights; a.count = (uint32_t)count; a.log_l = log_l; a.log_n = log_n; a.tiles = tiles; a.tb = tb;
     a.partial = ctx->mv[3].as<int32_t>();
-    const size_t lds = ((size_t)NL * E + (size_t)NL * cpt + (size_t)NL * std::max<size_t>(l / 2, 1) + cpt) * 4;     // <= 55 KiB
+    a.rows = nullptr;
+    const size_t lds = mv_interp_lds_bytes(E, l);
     if (E == 1024) hipLaunchKernelGGL(k_coset_interp<4>, dim3(groups), dim3(256), lds, st, a);
     else hipLaunchKernelGGL(k_coset_interp<2>, dim3(groups), dim3(256), lds, st, a);
     const int log_cb = std::min(log_l, 8);

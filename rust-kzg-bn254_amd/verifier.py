@@ -351,3 +351,75 @@ def verify_multiproof(commitment, proof, coset_index: int, ys, n: int, srs, g2_t
                                            _g2_arg(g2_tau_l), C.byref(ok))
     _raise_for(rc, ctx)
     return bool(ok.value)
+
+
+# ---- locating the bad items of a rejected batch ----------------------------------------------------------------------------------
+pairings_verify = helpers.pairings_verify          # e(a1, a2) == e(b1, b2): the check of one pair of group sums against ([tau^l]_2, G2)
+
+
+def _group_args(groups, n_groups, commitment_indices, n_commitments, count):
+    """(group index per item, n_groups) for `groups` = "commitment" (group = commitment row), "item" (one group per item) or an explicit
+    integer array with `n_groups`."""
+    if isinstance(groups, str):
+        if groups == "commitment":
+            return np.ascontiguousarray(commitment_indices, dtype=np.uint64), int(n_commitments)
+        if groups == "item":
+            return np.arange(count, dtype=np.uint64), int(count)
+        raise GenericError('groups is "commitment", "item" or an array of group indices')
+    gi = np.ascontiguousarray([int(v) for v in groups], dtype=np.uint64)
+    if len(gi) != count:
+        raise GenericError("length's of the input are not the same")
+    if n_groups is None:
+        raise GenericError("an explicit grouping needs n_groups")
+    return gi, int(n_groups)
+
+
+def _locate_args(commitments, commitment_indices, coset_indices, ys, proofs, srs, g2_tau_l, r_powers, ctx, groups, n_groups, need_g2):
+    cm, ci, ki, ys, pf = _multiproof_args(commitments, commitment_indices, coset_indices, ys, proofs)
+    count, l = ys.shape[0], ys.shape[1]
+    if need_g2 and g2_tau_l is None and l != 1:
+        raise GenericError("g2_tau_l = None (consts::G2_TAU) is [tau]_2: chunks of more than one point need [tau^l]_2")
+    gi, n_groups = _group_args(groups, n_groups, ci, len(cm), count)
+    rp = None if r_powers is None else np.ascontiguousarray(_lib.as_u64(r_powers, 0)).reshape(-1, 4)
+    if rp is not None and len(rp) != count:
+        raise GenericError("length's of the input are not the same")
+    ctx = ctx or getattr(srs, "ctx", None) or _lib.default_context()                   # the SRS's own context
+    opt = lambda a: _lib.ptr(a) if count else None                                     # noqa: E731
+    head = (ctx.handle, srs.handle, _lib.ptr(cm) if len(cm) else None, len(cm), opt(ci), opt(ki), opt(ys), opt(pf), count)
+    return ctx, head, l, None if rp is None or count == 0 else _lib.ptr(rp), opt(gi), n_groups, (cm, ci, ki, ys, pf, rp, gi)
+
+
+def coset_group_sums(commitments, commitment_indices, coset_indices, ys, proofs, n: int, srs, r_powers=None, ctx=None, groups="commitment",
+                     n_groups=None):
+    """The two G1 sums (L_g, R_g) of every group's own pairing equation (`kzg_coset_group_sums`): group g of the items is good iff
+    e(L_g, [tau^l]_2) = e(R_g, G2), and the sums over all groups are the pair `verify_multiproof_batch` checks.  `groups` as for
+    `locate_bad_multiproofs`.  Returns (lhs, lhs_is_infinity, rhs, rhs_is_infinity): (n_groups, 8) uint64 affine wire points and
+    (n_groups,) bool arrays; an empty group gives the identity twice."""
+    ctx, head, l, rp, gi, n_groups, _keep = _locate_args(commitments, commitment_indices, coset_indices, ys, proofs, srs, None, r_powers, ctx, groups,
+                                                         n_groups, False)
+    lhs, rhs = np.zeros((n_groups, 8), np.uint64), np.zeros((n_groups, 8), np.uint64)
+    linf, rinf = np.zeros(max(n_groups, 1), np.uint8), np.zeros(max(n_groups, 1), np.uint8)
+    rc = _lib.load().kzg_coset_group_sums(*head, int(n), l, rp, gi, n_groups, _lib.ptr(lhs) if n_groups else None, linf.ctypes.data_as(_lib.u8p),
+                                          _lib.ptr(rhs) if n_groups else None, rinf.ctypes.data_as(_lib.u8p))
+    _raise_for(rc, ctx)
+    return lhs, linf[:n_groups].astype(bool), rhs, rinf[:n_groups].astype(bool)
+
+
+def locate_bad_multiproofs(commitments, commitment_indices, coset_indices, ys, proofs, n: int, srs, g2_tau_l=None, r_powers=None, ctx=None,
+                           groups="commitment", n_groups=None):
+    """Which groups of a batch of coset proofs are bad (`kzg_verify_multiproof_batch_locate`): the group sums once on the GPU, then a
+    search of the tree of those sums on the host, one pairing check per step and at most 1 + 2 b ceil(log2 n_groups) of them for b bad
+    groups.  `groups` = "commitment" (group = commitment row, n_groups = number of commitments), "item" (one group per item) or an
+    integer array of group indices with `n_groups`.  Returns (good, pairing_checks): a bool array of length n_groups (True = good) and
+    the number of pairing checks; all True is the accept of `verify_multiproof_batch`.  This call always pays for the group sums: a
+    caller who expects good batches calls `verify_multiproof_batch` first and this only after a reject."""
+    ctx, head, l, rp, gi, n_groups, _keep = _locate_args(commitments, commitment_indices, coset_indices, ys, proofs, srs, g2_tau_l, r_powers, ctx, groups,
+                                                         n_groups, True)
+    good = np.zeros(max(n_groups, 1), np.uint8)
+    bad, checks = _lib.sz(0), _lib.sz(0)
+    rc = _lib.load().kzg_verify_multiproof_batch_locate(*head, int(n), l, rp, _g2_arg(g2_tau_l), gi, n_groups, good.ctypes.data_as(_lib.u8p), C.byref(bad),
+                                                        C.byref(checks))
+    _raise_for(rc, ctx)
+    good = good[:n_groups].astype(bool)
+    assert int(bad.value) == int((~good).sum())
+    return good, int(checks.value)
