@@ -852,6 +852,66 @@ int32_t kzg_g2_decompress_be_device(kzg_ctx* ctx, const uint8_t* bytes, size_t n
  * file of powers of tau starts with [tau^0]_2).  Errors as above (1. also: out NULL); on any error *out = NULL. */
 int32_t kzg_g2srs_load_compressed_be(kzg_ctx* ctx, const uint8_t* bytes, size_t n_points, kzg_g2srs** out, uint64_t* bad_index);
 
+/* ---- coset items in their serialized form (csrc/g1_decode.h, csrc/cosetbytes.hip, csrc/host_coset_bytes.h) ---------------------------
+ * What a sampler or validator receives off the wire: a commitment or proof is a 32-byte gnark-compressed G1 point (x big-endian, the
+ * top two bits of byte 0: 0b01 = the identity, written 0x40 || 31 zero bytes; 0b10 / 0b11 = the smaller / larger y by
+ * lexicographically_largest), a value is a 32-byte big-endian scalar.  Decoding is STRICT, per element in this order: 1. flag bits
+ * 0b00 (gnark's uncompressed marker), or 0b01 with any other bit set -> KZG_ERR_DESERIALIZE; 2. x >= p -> KZG_ERR_DESERIALIZE (the SRS
+ * loader kzg_srs_load_compressed_be reduces such an x mod p as the reference does; here one byte string names one point, so that the
+ * transcript over the bytes equals the transcript over the decoded points); 3. x^3 + 3 not a square -> KZG_ERR_NOT_ON_CURVE; a value
+ * >= r -> KZG_ERR_DESERIALIZE.  G1 has cofactor 1: a point on the curve is in the group.  The status of an array is that of its
+ * SMALLEST bad index, whatever the launch geometry.  Host bytes are staged in chunks through pinned memory the context already holds.
+ * The device entries are synchronous on slot 0 (KZG_ERR_INVALID_ARG while a kzg_*_begin is in flight on it); every argument check runs
+ * on the host before any launch and the context stays usable after any error.
+ *
+ * kzg_g1_decompress_be_device: n_points points -> wire points (n_points x 8 u64; the identity as the all-zero wire point) and,
+ * when out_is_infinity is not NULL, one identity byte per point.  Errors, in order: 1. a null ctx, or null bytes / out_xy_mont with
+ * n_points > 0 -> KZG_ERR_INVALID_ARG; 2. n_points > 2^28 -> KZG_ERR_TOO_LARGE; 3. a _begin in flight on slot 0 -> KZG_ERR_INVALID_ARG;
+ * 4. the points, as above, *bad_index (may be NULL) = the smallest bad index: then the outputs are not written.  n_points = 0 -> KZG_OK. */
+int32_t kzg_g1_decompress_be_device(kzg_ctx* ctx, const uint8_t* bytes, size_t n_points, uint64_t* out_xy_mont,
+                                    uint8_t* out_is_infinity /* may be NULL */, uint64_t* bad_index);
+/* A batch of items -> the wire words kzg_verify_multiproof_batch_locate, kzg_coset_group_sums and kzg_recover_from_cosets take: ys_be
+ * count x chunk_len x 32 bytes -> out_ys_mont count x chunk_len x 4 u64; proofs_be count x 32 bytes -> out_proofs_xy_mont count x 8
+ * u64.  Either input / output pair may be NULL together (recovery decodes values only).  Errors, in order: 1. a null ctx, one pointer
+ * of a pair NULL and the other not, both pairs NULL with count > 0, chunk_len = 0 with values -> KZG_ERR_INVALID_ARG; 2. count *
+ * chunk_len > 2^28 -> KZG_ERR_TOO_LARGE; 3. a _begin in flight on slot 0 -> KZG_ERR_INVALID_ARG; 4. a bad proof: *bad_array = 1,
+ * *bad_index = its item; 5. a bad value: *bad_array = 2, *bad_index = its ITEM (both may be NULL).  On an error of 4 / 5 the outputs
+ * are not written.  count = 0 -> KZG_OK. */
+int32_t kzg_coset_items_decode_be(kzg_ctx* ctx, const uint8_t* ys_be, const uint8_t* proofs_be, size_t count, size_t chunk_len,
+                                  uint64_t* out_ys_mont, uint64_t* out_proofs_xy_mont, uint64_t* bad_index, int32_t* bad_array);
+/* The disperser's half, host only (the library's host pool): Montgomery words -> canonical big-endian values, wire points ->
+ * compressed points with their sign bit, the all-zero wire point -> 0x40 || zeros.  Pairs may be NULL together as above.  The inputs
+ * are trusted (a point is not checked to be on the curve).  Errors: the pointer / chunk_len rules of kzg_coset_items_decode_be ->
+ * KZG_ERR_INVALID_ARG; count * chunk_len > 2^28 -> KZG_ERR_TOO_LARGE; a value or coordinate not below its modulus ->
+ * KZG_ERR_INVALID_ARG (the outputs are then unspecified). */
+int32_t kzg_coset_items_encode_be(const uint64_t* ys_mont, const uint64_t* proofs_xy_mont, size_t count, size_t chunk_len,
+                                  uint8_t* out_ys_be, uint8_t* out_proofs_be);
+/* The weights of kzg_compute_multiproof_r_powers, bit for bit, from the serialized form of the same items, for every input whose
+ * bytes decode.  Host only.  The item message is assembled from the bytes: be32(ys_i[j]) is the value's bytes as they are, the
+ * ark-compressed point is the gnark bytes reversed with the flag bits remapped (0b10 -> 0, 0b11 -> 0x80, 0b01 -> 0x40); no field
+ * multiplication occurs before the final mod r.  Bytes that do not decode are hashed as given (flag 0b00 -> 0xC0), not validated, like
+ * the existing entry.  Arguments and errors as kzg_compute_multiproof_r_powers. */
+int32_t kzg_compute_multiproof_r_powers_bytes(const uint8_t* commitments_be, size_t n_commitments, const uint64_t* commitment_indices,
+                                              const uint64_t* coset_indices, const uint8_t* ys_be, const uint8_t* proofs_be, size_t count,
+                                              size_t n, size_t chunk_len, uint64_t* out_r_powers_mont);
+/* kzg_verify_multiproof_batch with the decode inside the call: the verdict of that entry on the decoded inputs, and the same weights
+ * bit for bit (r_powers_mont = NULL derives them; out_r_powers_mont, may be NULL, receives the count weights used).  Values go up once
+ * as bytes and are decoded where the interpolation kernel reads them; proofs and commitments go up as 32 bytes each and are decoded
+ * into the bases of the batched MSMs (the decode kernel writes the second copy of the proofs for the r_i w^(k_i l) combination); nothing
+ * decoded returns to the host.  Derived weights read the bytes: on the host pool beside the decode kernels, or -- inside the automatic
+ * envelope, or when kzg_ctx_set_transcript_device forces it -- on the device, hashing the uploaded bytes.  Device memory: the value
+ * bytes (count x chunk_len x 32) on top of what the decoded entry uses.
+ * Errors, in this order: 1. those of kzg_verify_multiproof_batch up to and including the index checks and count * chunk_len > 2^28;
+ * a _begin in flight on slot 0 -> KZG_ERR_INVALID_ARG; 2. a bad commitment (*bad_array = 0); 3. a bad proof (*bad_array = 1); 4. a bad
+ * value (*bad_array = 2), each with the status of the decode rules above and *bad_index = the commitment / item (both may be NULL);
+ * 5. g2_tau_l_mont off the twist -> KZG_ERR_G2_TAU_NOT_ON_CURVE.  count = 0 -> *out_ok = 1.  KZG_VB_TRACE=1 prints the phase times,
+ * `decode` among them, on stderr. */
+int32_t kzg_verify_multiproof_batch_bytes(kzg_ctx* ctx, const kzg_srs* srs, const uint8_t* commitments_be, size_t n_commitments,
+                                          const uint64_t* commitment_indices, const uint64_t* coset_indices, const uint8_t* ys_be,
+                                          const uint8_t* proofs_be, size_t count, size_t n, size_t chunk_len,
+                                          const uint64_t* r_powers_mont /* NULL: derived */, const uint64_t* g2_tau_l_mont, int32_t* out_ok,
+                                          uint64_t* out_r_powers_mont /* may be NULL */, uint64_t* bad_index, int32_t* bad_array);
+
 #ifdef __cplusplus
 }
 #endif

@@ -196,6 +196,12 @@ PROTOTYPES = {
     "kzg_g2_decompress_be": (i32, [u8p, sz, u64p, C.POINTER(C.c_uint64)]),
     "kzg_g2_decompress_be_device": (i32, [vp, u8p, sz, C.c_uint32, u64p, C.POINTER(C.c_uint64)]),
     "kzg_g2srs_load_compressed_be": (i32, [vp, u8p, sz, C.POINTER(vp), C.POINTER(C.c_uint64)]),
+    "kzg_g1_decompress_be_device": (i32, [vp, u8p, sz, u64p, u8p, C.POINTER(C.c_uint64)]),
+    "kzg_coset_items_decode_be": (i32, [vp, u8p, u8p, sz, sz, u64p, u64p, C.POINTER(C.c_uint64), C.POINTER(i32)]),
+    "kzg_coset_items_encode_be": (i32, [u64p, u64p, sz, sz, u8p, u8p]),
+    "kzg_compute_multiproof_r_powers_bytes": (i32, [u8p, sz, u64p, u64p, u8p, u8p, sz, sz, sz, u64p]),
+    "kzg_verify_multiproof_batch_bytes": (i32, [vp, vp, u8p, sz, u64p, u64p, u8p, u8p, sz, sz, sz, u64p, u64p, C.POINTER(i32), u64p, C.POINTER(C.c_uint64),
+                                                C.POINTER(i32)]),
 }
 
 _lib = None

@@ -362,6 +362,7 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
     for (auto& b : ctx->mv) b.release();
     for (auto& b : ctx->ml) b.release();
     for (auto& b : ctx->fs) b.release();
+    for (auto& b : ctx->cb) b.release();
     ctx->mv_ntt.release();
     for (auto& b : ctx->rc) b.release();
     ctx->rc_ntt.release();

@@ -5,6 +5,7 @@
 #include "host_pairing.h"
 #include "host_sha256.h"
 #include "host_fiat_shamir.h"
+#include "host_coset_bytes.h"
 
 #include <algorithm>
 #include <atomic>
@@ -776,6 +777,112 @@ int32_t kzg_verify_multiproof(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t c
     uint64_t one_w[4];
     kzg_host::fr_one(one_w);
     return kzg_verify_multiproof_batch(ctx, srs, commitment_xy_mont, 1, &zero, &coset_index, ys_mont, proof_xy_mont, 1, n, chunk_len, one_w, g2_tau_l_mont, out_ok);
+}
+
+// kzg_verify_multiproof_batch on items in their serialized form: the same equation, weights and verdict, with the decode inside the call.
+// Values go up once as bytes (ctx->cb[0]) and are decoded where the interpolation kernel reads them (ctx->mv[0]); proofs and commitments go up
+// as 32 bytes each (ctx->cb[1]) and are decoded straight into the bases of msm_run_batch (ctx->msm.bases: proofs | proofs | commitments -- the
+// decode kernel writes the second copy of the proofs, the batched MSM of the two combinations reads concatenated bases).  Nothing decoded
+// returns to the host.  The transcript reads the bytes: on the host pool beside the decode kernels, or on the device where the bytes landed.
+int32_t kzg_verify_multiproof_batch_bytes(kzg_ctx* ctx, const kzg_srs* srs, const uint8_t* commitments_be, size_t n_commitments, const uint64_t* commitment_indices,
+                                          const uint64_t* coset_indices, const uint8_t* ys_be, const uint8_t* proofs_be, size_t count, size_t n, size_t chunk_len,
+                                          const uint64_t* r_powers_mont, const uint64_t* g2_tau_l_mont, int32_t* out_ok, uint64_t* out_r_powers_mont,
+                                          uint64_t* bad_index, int32_t* bad_array) {
+    using namespace kzg_host;
+    int32_t rc = multiproof_batch_checks(ctx, srs, !out_ok, !commitments_be || !commitment_indices || !coset_indices || !ys_be || !proofs_be,
+                                         !g2_tau_l_mont && chunk_len != 1, n_commitments, commitment_indices, coset_indices, count, n, chunk_len, nullptr, 0, false);
+    if (rc != KZG_OK) return rc;
+    const size_t l = chunk_len, m = n / l, N = count, M = n_commitments;
+    if (N == 0) { *out_ok = 1; return KZG_OK; }
+    const bool trace = opts().vb_trace != 0;
+    const auto t0 = Clock::now();
+    G2 g2_tau_l;
+    const bool g2_ok = load_g2_tau(g2_tau_l_mont, &g2_tau_l);                            // reported after the bytes, as the decoded entry reports it after the points
+    std::vector<uint64_t> derived;
+    const bool derive = !r_powers_mont;
+    if (derive) { derived.resize(4 * N); r_powers_mont = derived.data(); }
+    const bool on_device = derive && coset_transcript_on_device(ctx->transcript_device.load(std::memory_order_relaxed), N, l);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ctx->slot_pending[0]) { ctx->last_error = "a kzg_*_begin on slot 0 is still in flight: call its end first"; return KZG_ERR_INVALID_ARG; }
+    // 0. uploads and decode kernels: everything is enqueued, then the host transcript runs beside them
+    KZG_HIP_TRY(ctx, ctx->msm.bases.reserve((2 * N + M) * 64));
+    KZG_HIP_TRY(ctx, ctx->msm.scalars.reserve((2 * N + M) * 32 + 32));
+    KZG_HIP_TRY(ctx, ctx->mv[0].reserve(N * l * 32));
+    KZG_HIP_TRY(ctx, ctx->mv[1].reserve(std::max<size_t>(N * 40, 64)));
+    KZG_HIP_TRY(ctx, ctx->mv[2].reserve(l * 32));
+    uint4* d_bases = ctx->msm.bases.as<uint4>();
+    uint4* d_w = ctx->mv[1].as<uint4>();
+    uint64_t* d_k = reinterpret_cast<uint64_t*>(ctx->mv[1].as<uint8_t>() + N * 32);
+    CosetBytesDecode job;
+    job.points_be[0] = commitments_be; job.n_points[0] = M; job.d_points[0] = d_bases + 4 * 2 * N;
+    job.points_be[1] = proofs_be; job.n_points[1] = N; job.d_points[1] = d_bases; job.d_points_copy[1] = d_bases + 4 * N;
+    job.ys_be = ys_be; job.n_values = N * l; job.d_ys = ctx->mv[0].as<uint4>();
+    rc = coset_bytes_enqueue(ctx, &job);
+    if (rc != KZG_OK) return rc;
+    hipError_t e_k = hipMemcpyAsync(d_k, coset_indices, N * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (derive && !on_device && e_k == hipSuccess) {
+        RoctxRange range("kzg:multiproof_verify:r_powers (host, from bytes)");
+        multiproof_r_powers_bytes_host(commitments_be, M, commitment_indices, coset_indices, ys_be, proofs_be, N, n, l, derived.data(), host_parallel_for);
+    }
+    const auto t_rp_host = Clock::now();
+    rc = coset_bytes_collect(ctx, &job);                                                 // (drains the stream on every path: the copy of the indices too)
+    if (e_k != hipSuccess) return set_error(ctx, e_k, "uploading the coset indices");
+    if (rc != KZG_OK) return rc;
+    static const char* const names[3] = {"commitment", "proof", "value of item"};
+    for (int a = 0; a < 3; ++a) {
+        rc = coset_bytes_status(ctx, "kzg_verify_multiproof_batch_bytes", names[a], job.bad[a], a == 2 ? l : 1, bad_index);
+        if (rc != KZG_OK) { if (bad_array) *bad_array = a; return rc; }
+    }
+    if (!g2_ok) return KZG_ERR_G2_TAU_NOT_ON_CURVE;
+    const auto t_dec = Clock::now();
+    // 1. the weights where the interpolation reads them
+    const char* rp_path = derive ? " (host, from bytes, beside the decode)" : " (supplied)";
+    if (on_device) {
+        rc = coset_r_powers_device_bytes(ctx, commitments_be, M, commitment_indices, job.d_ys_be, d_k, job.d_points_be[1], N, n, l, d_w, derived.data());
+        if (rc != KZG_OK) return rc;
+        rp_path = " (device, from bytes)";
+    } else {
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(d_w, r_powers_mont, N * 32, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const auto t_rp = Clock::now();
+    rc = coset_interpolate_rlc_device(ctx, ctx->mv[0].as<uint4>(), d_k, d_w, N, n, l, ctx->mv[2].as<uint4>());
+    if (rc != KZG_OK) return rc;
+    if (trace) KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const auto t_ker = Clock::now();
+    // 2. [sum_i r_i I_i(tau)]_1: an MSM of the coefficients over srs[0 .. l)
+    uint64_t interp_xy[8];
+    uint8_t interp_inf = 0;
+    rc = msm_srs_locked(ctx, srs, 0, ctx->mv[2].p, true, l, interp_xy, &interp_inf, nullptr);
+    if (rc != KZG_OK) return rc;
+    const auto t_msm1 = Clock::now();
+    // 3. host scalars: r_i | r_i w^(k_i l) | the row sums of the weights, in the order of the bases
+    std::vector<uint64_t> scalars((2 * N + M) * 4, 0);
+    memcpy(scalars.data(), r_powers_mont, N * 32);
+    coset_shifted_weights(coset_indices, r_powers_mont, N, m, scalars.data() + N * 4);
+    uint64_t* row_w = scalars.data() + 2 * N * 4;
+    for (size_t i = 0; i < N; ++i) { uint64_t* rw = row_w + 4 * commitment_indices[i]; fr_add(rw, r_powers_mont + 4 * i, rw); }
+    // 4. the two N-point combinations of the proofs and the M-point one of the commitments over the bases the decode kernels wrote
+    const uint4* d_scalars = ctx->msm.scalars.as<uint4>();
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(ctx->msm.scalars.p, scalars.data(), (2 * N + M) * 32, hipMemcpyHostToDevice, ctx->stream));
+    uint64_t sums[2 * 8], c_sum[8];
+    uint8_t infs[2], c_inf = 0;
+    rc = msm_run_batch(ctx, d_bases, d_scalars, N, 2, sums, infs);
+    if (rc == KZG_OK) rc = msm_run_batch(ctx, d_bases + 4 * 2 * N, d_scalars + 2 * 2 * N, M, 1, c_sum, &c_inf);
+    if (rc != KZG_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }            // (`scalars` is in use until the stream is drained)
+    const auto t_msm2 = Clock::now();
+    // 5. point sums and ONE pairing check
+    const G1 lhs = g1_from_wire(sums);
+    const G1 rhs = g1_add(g1_add(g1_from_wire(c_sum), g1_neg(g1_from_wire(interp_xy))), g1_from_wire(sums + 8));
+    *out_ok = pairings_verify_pooled(lhs, g2_tau_l, rhs, g2_generator()) ? 1 : 0;
+    if (out_r_powers_mont) memcpy(out_r_powers_mont, r_powers_mont, N * 32);
+    if (trace)
+        fprintf(stderr, "kzg_verify_multiproof_batch_bytes N=%zu l=%zu M=%zu: decode (staging, uploads, decode kernels; host r_powers beside them %.3f ms) %.3f ms, "
+                "r_powers%s %.3f ms, interpolation kernel %.3f ms, coefficient MSM %.3f ms, host scalars + proof / commitment MSMs %.3f ms, "
+                "point sums + pairing %.3f ms, call %.3f ms\n", N, l, M, derive && !on_device ? ms_between(t0, t_rp_host) : 0.0, ms_between(t0, t_dec), rp_path,
+                ms_between(t_dec, t_rp), ms_between(t_rp, t_ker), ms_between(t_ker, t_msm1), ms_between(t_msm1, t_msm2), ms_between(t_msm2, Clock::now()),
+                ms_between(t0, Clock::now()));
+    return KZG_OK;
 }
 
 // For every group g of a partition of the items: L_g = sum_{i in g} r_i pi_i and R_g = sum_{i in g} (r_i C_{c_i} + r_i w^(k_i l) pi_i) -

@@ -101,4 +101,63 @@ KZG_HD void coset_item_block(uint32_t w[16], const CosetItemSrc& s, uint32_t b, 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The second producer: the same message from the item's SERIALIZED form (cosetbytes.hip k_coset_item_digests_bytes) -- values as 32
+// big-endian bytes each, the proof as 32 gnark-compressed bytes, both as the words a little-endian load of them leaves.  For inputs
+// that decode (g1_decode.h: canonical x, canonical values) be32(y_t) is the value's bytes as they are, and the ark-compressed proof is
+// the gnark bytes reversed with the flag bits remapped (0b10 -> 0, 0b11 -> 0x80, 0b01 -> 0x40, 0b00 -> 0xC0; host_coset_bytes.h
+// gnark_to_ark): no field arithmetic, nothing to refuse here -- the decode kernels refuse, and then no weight is used.
+// ---------------------------------------------------------------------------------------------
+struct CosetItemBytesSrc {
+    const uint32_t* ys;        // l x 8 words of bytes (16-byte aligned)
+    const uint32_t* proof;     // 8 words of bytes (16-byte aligned)
+    uint64_t c, k;
+    uint32_t l;
+};
+
+KZG_HD void coset_item_bytes_slot(uint32_t out[8], const CosetItemBytesSrc& s, uint32_t t) {
+    if (t < s.l) {
+        uint32_t w[8];
+        coset_item_load8(w, s.ys + 8 * (size_t)t);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) out[j] = sha_bswap(w[j]);           // message bytes in order: big-endian word j = the loaded word j, swapped
+    } else if (t == s.l) {
+        uint32_t w[8];
+        coset_item_load8(w, s.proof);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) out[j] = w[7 - j];                  // the reversed bytes as big-endian words: the loaded words in reverse order, unswapped
+        const uint32_t f = (w[0] >> 6) & 3u;                            // the top two bits of gnark's byte 0 = ark's byte 31 = the low byte of out[7]
+        const uint32_t flag = f == 0u ? 0xC0u : f == 1u ? 0x40u : f == 2u ? 0u : 0x80u;
+        out[7] = (out[7] & ~0xC0u) | flag;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) out[j] = 0;
+        if (t == s.l + 1) out[0] = 0x80000000u;
+    }
+}
+
+// the 16 words of block b, as coset_item_block above
+KZG_HD void coset_item_bytes_block(uint32_t w[16], const CosetItemBytesSrc& s, uint32_t b, uint32_t carry[2]) {
+    uint32_t v[8];
+    if (b == 0) {
+        w[0] = 0x4b5a4742u; w[1] = 0x4e323534u; w[2] = 0x5f434f53u; w[3] = 0x45544954u; w[4] = 0x454d5f5fu; w[5] = 0x5f56315fu;   // the tag
+        w[6] = (uint32_t)(s.c >> 32); w[7] = (uint32_t)s.c;
+        w[8] = (uint32_t)(s.k >> 32); w[9] = (uint32_t)s.k;
+    } else {
+        w[0] = carry[0]; w[1] = carry[1];
+        coset_item_bytes_slot(v, s, 2 * b - 1);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) w[2 + j] = v[j];
+    }
+    coset_item_bytes_slot(v, s, 2 * b);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) w[10 + j] = v[j];
+    carry[0] = v[6]; carry[1] = v[7];
+    if (b + 1 == coset_item_blocks(s.l)) {
+        const uint64_t len = coset_item_len(s.l);
+        w[14] = (uint32_t)(len >> 29);
+        w[15] = (uint32_t)(len << 3);
+    }
+}
+
 }  // namespace kzg

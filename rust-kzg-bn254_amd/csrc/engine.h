@@ -136,6 +136,7 @@ struct kzg_ctx {
     kzg::NttWorkspace mv_ntt;
     kzg::DeviceBuffer ml[6];                   // kzg_coset_group_sums / kzg_verify_multiproof_batch_locate (multilocate.hip): group coefficients | the plan's arrays | partial point sums | group sums | rows + shifted weights | proofs + commitments
     kzg::DeviceBuffer fs[2];                  // the coset transcript on the device (fsdevice.hip): commitment rows | proofs, digests | power tables | flag; kzg_sha256_rows: messages, digests
+    kzg::DeviceBuffer cb[2];                   // serialized coset items (cosetbytes.hip): value bytes | point bytes (commitments, proofs), decoded wire points, the bad words
     kzg::DeviceBuffer rc[3];                   // kzg_recover_from_cosets (recover.hip): work values | indices, vanishing values, partial products, flag | powers of g
     int rc_gpow_log = -1;                      // rc[2] holds the factored tables of g^t and g^-t for t < 2^rc_gpow_log (-1: none yet)
     kzg::NttWorkspace rc_ntt;                  // its `data` also stages the uploaded coset values (dead before the first transform)
@@ -332,6 +333,35 @@ int32_t sha256_rows_run(kzg_ctx* ctx, const uint8_t* msgs, size_t row_len, size_
 int32_t coset_r_powers_device(kzg_ctx* ctx, const uint64_t* commitments, size_t n_commitments, const uint64_t* commitment_indices, const uint4* d_ys,
                               const uint64_t* d_ks, const uint64_t* proofs, size_t count, size_t n, size_t l, uint4* d_weights, uint64_t* out_r_powers,
                               bool* fell_back);
+// the same weights from items that are on the device in their SERIALIZED form (d_ys_be: count x l x 32 value bytes, d_proofs_be: count x 32 bytes of
+// gnark-compressed proofs; commitments_be and commitment_indices: host): nothing to convert, nothing to fall back from.  Synchronised on return
+int32_t coset_r_powers_device_bytes(kzg_ctx* ctx, const uint8_t* commitments_be, size_t n_commitments, const uint64_t* commitment_indices, const uint4* d_ys_be,
+                                    const uint64_t* d_ks, const uint4* d_proofs_be, size_t count, size_t n, size_t l, uint4* d_weights, uint64_t* out_r_powers);
+// Serialized coset items decoded on the device (cosetbytes.hip, g1_decode.h).  Called under ctx->mu with the device set and slot 0 idle.  Up to two
+// arrays of gnark-compressed G1 points (32 B each; [0] commitments, [1] proofs) and one of big-endian scalars (32 B each); an absent array has n = 0.
+// The host bytes go up through the pinned memory of slot 0's workspace into ctx->cb (values: cb[0]; points: cb[1]) and stay there (d_*_be).  Points
+// leave in the device format of curve.h (d_points, and a second copy at d_points_copy when that is not null) or, with wire_points, as wire points
+// with one identity byte each (d_inf); values leave as wire scalars.  bad[a] = index << 2 | kind (G1_BAD_* of g1_decode.h; 0 for a value >= r) of
+// the SMALLEST refused index of array a (0 commitments, 1 proofs, 2 values), or 0xFFFFFFFF.
+struct CosetBytesDecode {
+    const uint8_t* points_be[2] = {nullptr, nullptr};
+    size_t n_points[2] = {0, 0};
+    uint4* d_points[2] = {nullptr, nullptr};
+    uint4* d_points_copy[2] = {nullptr, nullptr};
+    uint8_t* d_inf[2] = {nullptr, nullptr};
+    bool wire_points = false;
+    const uint8_t* ys_be = nullptr;
+    size_t n_values = 0;
+    uint4* d_ys = nullptr;
+    const uint4* d_points_be[2] = {nullptr, nullptr};   // (set by the enqueue)
+    const uint4* d_ys_be = nullptr;
+    uint32_t bad[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};   // (set by the collect)
+};
+int32_t coset_bytes_enqueue(kzg_ctx* ctx, CosetBytesDecode* job);    // uploads and kernels on ctx->stream; the host bytes are consumed on return
+int32_t coset_bytes_collect(kzg_ctx* ctx, CosetBytesDecode* job);    // drains the stream, reads the three bad words
+// the status of a bad word (KZG_OK for 0xFFFFFFFF): KZG_ERR_DESERIALIZE / KZG_ERR_NOT_ON_CURVE, the element's index / per_item to *bad_index (may be
+// null), a line with the array's name for kzg_ctx_last_error
+int32_t coset_bytes_status(kzg_ctx* ctx, const char* who, const char* array, uint32_t bad_word, size_t per_item, uint64_t* bad_index);
 // erasure decoding (recover.hip): the polynomial of degree < count l through the values of the plan's cosets (ys: host, count x l wire values), as n
 // coefficients or evaluations on the host; *consistent = its coefficients from plan.degree_bound on are zero.  Called under ctx->mu, synchronised on return
 int32_t recover_run(kzg_ctx* ctx, const RecoverPlan& plan, const uint64_t* ys, bool eval_form, uint64_t* out_poly, int32_t* consistent);

@@ -6,6 +6,8 @@
 //   k_coset_item_digests   one lane per item: the message is produced block by block from the wire values, the coset pair and the wire proof
 //                          (coset_item_stream.h: Montgomery -> canonical, big-endian words, the compressed point), never stored; one flag
 //                          word is set when an input is not canonical (the caller then derives the weights on the host)
+//   k_coset_item_digests_bytes  the same digests from items in their serialized form (kzg_verify_multiproof_batch_bytes): the message is the value
+//                          bytes as they are and the gnark-compressed proof reversed with its flag bits remapped; no field arithmetic, no flag
 //   k_fr_powers_from_tables  out[i] = r^i as lo[i mod S] * hi[i div S] from two host-computed tables of about sqrt(count) wire scalars: wire
 //                          form is the canonical representative, so the words equal those of the host's running product (powers_of)
 // Shapes chosen: a workgroup is ONE wave (no LDS, no barrier); every lane of a wave is at the same block of its message, so the slot
@@ -15,6 +17,7 @@
 #include "engine.h"
 #include "coset_item_stream.h"
 #include "host_fiat_shamir.h"
+#include "host_coset_bytes.h"
 
 #include <algorithm>
 #include <vector>
@@ -69,6 +72,30 @@ k_coset_item_digests(const uint4* __restrict__ ys, const uint64_t* __restrict__ 
     if (bad) atomicOr(flag, 1u);
 }
 
+// the same digests from serialized items: ys = l x 32 value bytes per item, proofs = 32 gnark-compressed bytes per item (coset_item_stream.h,
+// the second producer)
+__global__ void __launch_bounds__(FS_LANES)
+k_coset_item_digests_bytes(const uint4* __restrict__ ys, const uint64_t* __restrict__ cs, const uint64_t* __restrict__ ks, const uint4* __restrict__ proofs,
+                           uint32_t count, uint32_t l, uint4* __restrict__ out) {
+    const uint32_t i = blockIdx.x * FS_LANES + threadIdx.x;
+    if (i >= count) return;
+    CosetItemBytesSrc src;
+    src.ys = reinterpret_cast<const uint32_t*>(ys + 2 * (size_t)i * l);
+    src.proof = reinterpret_cast<const uint32_t*>(proofs + 2 * (size_t)i);
+    src.c = cs[i];
+    src.k = ks[i];
+    src.l = l;
+    const uint32_t nb = coset_item_blocks(l);
+    uint32_t st[8], w[16], carry[2] = {0, 0};
+    sha256_init_state(st);
+#pragma unroll 1
+    for (uint32_t b = 0; b < nb; ++b) {
+        coset_item_bytes_block(w, src, b, carry);
+        sha256_compress(st, w);
+    }
+    fs_store_digest(out, i, st);
+}
+
 __global__ void __launch_bounds__(256)
 k_fr_powers_from_tables(const uint4* __restrict__ lo, const uint4* __restrict__ hi, uint32_t log_s, uint32_t count, uint4* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -90,6 +117,8 @@ k_fr_powers_from_tables(const uint4* __restrict__ lo, const uint4* __restrict__ 
 // -------------------------------------------------------------------------------------------------
 // host drivers (ctx->stream, ctx->fs; called under ctx->mu, synchronised on return)
 // -------------------------------------------------------------------------------------------------
+static int32_t fs_powers_from_transcript(kzg_ctx* ctx, const std::vector<uint8_t>& data, size_t count, int log_s, uint4* d_lo, uint4* d_weights, uint64_t* out_r_powers);
+
 int32_t sha256_rows_run(kzg_ctx* ctx, const uint8_t* msgs, size_t row_len, size_t count, uint8_t* out_digests) {
     if (count == 0) return KZG_OK;
     hipStream_t st = ctx->stream;
@@ -135,6 +164,16 @@ int32_t coset_r_powers_device(kzg_ctx* ctx, const uint64_t* commitments, size_t 
     KZG_HIP_TRY(ctx, hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
     KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
     if (flag) { *fell_back = true; return KZG_OK; }
+    return fs_powers_from_transcript(ctx, data, count, log_s, d_lo, d_weights, out_r_powers);
+}
+
+// the tail of both device transcripts: r from the complete batch transcript (host), its powers as one product of two table entries per lane
+// into d_weights and to out_r_powers (host).  d_lo: room for S + H wire scalars, S = 2^log_s, H = ceil(count / S).  Synchronised on return
+static int32_t fs_powers_from_transcript(kzg_ctx* ctx, const std::vector<uint8_t>& data, size_t count, int log_s, uint4* d_lo, uint4* d_weights, uint64_t* out_r_powers) {
+    using namespace kzg_host;
+    hipStream_t st = ctx->stream;
+    const size_t S = (size_t)1 << log_s, H = (count + S - 1) >> log_s;
+    uint4* d_hi = d_lo + 2 * S;
     uint64_t r[4];
     hash_to_r(data, r);                                                                   // the one sequential stream: 56 + 32 (M + count) bytes
     std::vector<uint64_t> tab(4 * (S + H));
@@ -152,6 +191,31 @@ int32_t coset_r_powers_device(kzg_ctx* ctx, const uint64_t* commitments, size_t 
     KZG_HIP_TRY(ctx, hipMemcpyAsync(out_r_powers, d_weights, count * 32, hipMemcpyDeviceToHost, st));
     KZG_HIP_TRY(ctx, hipStreamSynchronize(st));                                           // (tab and out_r_powers are in use until here)
     return KZG_OK;
+}
+
+// The same weights from items ALREADY on the device in their serialized form (cosetbytes.hip: value bytes, gnark-compressed proofs): the second
+// producer of coset_item_stream.h, no conversion and nothing to fall back from.  commitments_be and commitment_indices: host.  Synchronised on return
+int32_t coset_r_powers_device_bytes(kzg_ctx* ctx, const uint8_t* commitments_be, size_t n_commitments, const uint64_t* commitment_indices, const uint4* d_ys_be,
+                                    const uint64_t* d_ks, const uint4* d_proofs_be, size_t count, size_t n, size_t l, uint4* d_weights, uint64_t* out_r_powers) {
+    using namespace kzg_host;
+    RoctxRange range("kzg:multiproof_verify:r_powers (device, from bytes)");
+    if (count == 0) return KZG_OK;
+    hipStream_t st = ctx->stream;
+    const int bits = count <= 1 ? 0 : 64 - __builtin_clzll((unsigned long long)(count - 1)), log_s = (bits + 1) / 2;
+    const size_t S = (size_t)1 << log_s, H = (count + S - 1) >> log_s;
+    KZG_HIP_TRY(ctx, ctx->fs[0].reserve(count * 8 + 16));                                  // commitment rows
+    KZG_HIP_TRY(ctx, ctx->fs[1].reserve(count * 32 + (S + H) * 32 + 16));                  // digests | lo | hi
+    uint64_t* d_cs = ctx->fs[0].as<uint64_t>();
+    uint4* d_digests = ctx->fs[1].as<uint4>();
+    uint4* d_lo = d_digests + 2 * count;
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(d_cs, commitment_indices, count * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_coset_item_digests_bytes, dim3((unsigned)((count + FS_LANES - 1) / FS_LANES)), dim3(FS_LANES), 0, st, d_ys_be, d_cs, d_ks, d_proofs_be,
+                       (uint32_t)count, (uint32_t)l, d_digests);
+    KZG_HIP_TRY(ctx, hipGetLastError());
+    std::vector<uint8_t> data = coset_batch_transcript_bytes(commitments_be, n_commitments, count, n, l);      // (beside the kernel)
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(data.data() + coset_batch_head(n_commitments), d_digests, count * 32, hipMemcpyDeviceToHost, st));
+    KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    return fs_powers_from_transcript(ctx, data, count, log_s, d_lo, d_weights, out_r_powers);
 }
 
 }  // namespace kzg

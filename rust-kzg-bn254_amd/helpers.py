@@ -123,6 +123,55 @@ def read_g1_point_from_bytes_be(g1_bytes_be: bytes, ctx=None) -> np.ndarray:
     return out
 
 
+def _u8(data, what):
+    buf = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    if len(buf) % 32 != 0:
+        raise DeserializationError("%s: not a multiple of 32 bytes" % what)
+    return buf
+
+
+def raise_for_decode(rc, array, index, ctx=None):
+    """The exception of a strict byte decode (`kzg_g1_decompress_be_device`, `kzg_coset_items_decode_be`,
+    `kzg_verify_multiproof_batch_bytes`): the array's name and the index are part of the message."""
+    if rc == _lib.ERR_DESERIALIZE:
+        raise DeserializationError("%s %d: not a canonical encoding (flag bits, or an integer not below the modulus)" % (array, index))
+    if rc == _lib.ERR_NOT_ON_CURVE:
+        raise NotOnCurveError("%s %d: compressed g1 point not on curve" % (array, index))
+    if ctx is not None:
+        ctx.check_device(rc)
+    if rc != _lib.OK:
+        raise GenericError(_lib.status_message(rc))
+
+
+def decompress_g1_device(data, ctx=None, return_is_infinity=False):
+    """gnark-compressed G1 points (32 bytes each) -> (n, 8) wire points, decoded on the GPU (`kzg_g1_decompress_be_device`), STRICTLY:
+    flag 0b00, a marked identity with other bits set or x >= p is a DeserializationError, an x without a point a NotOnCurveError, each
+    with the smallest bad index.  (`read_g1_point_from_bytes_be` stays on the SRS loader and reduces x mod p as the reference does.)"""
+    buf = _u8(data, "compressed G1 points")
+    n = len(buf) // 32
+    ctx = ctx or _lib.default_context()
+    out = np.zeros((n, 8), dtype=np.uint64)
+    inf = np.zeros(max(n, 1), dtype=np.uint8)
+    bad = C.c_uint64(0)
+    rc = _lib.load().kzg_g1_decompress_be_device(ctx.handle, buf.ctypes.data_as(_lib.u8p) if n else None, n, _lib.ptr(out) if n else None,
+                                                 inf.ctypes.data_as(_lib.u8p), C.byref(bad))
+    raise_for_decode(rc, "point", bad.value, ctx)
+    return (out, inf[:n].astype(bool)) if return_is_infinity else out
+
+
+def compress_g1_be(points) -> bytes:
+    """Wire points -> gnark-compressed bytes, 32 per point (`kzg_coset_items_encode_be`, host): x big-endian, 0b10 / 0b11 in the top two
+    bits of byte 0 for the smaller / larger y, the all-zero wire point as 0x40 and 31 zero bytes."""
+    pts = np.ascontiguousarray(_lib.as_u64(points, 0)).reshape(-1, 8)
+    n = len(pts)
+    out = np.zeros(32 * max(n, 1), dtype=np.uint8)
+    if n:
+        rc = _lib.load().kzg_coset_items_encode_be(None, _lib.ptr(pts), n, 1, None, out.ctypes.data_as(_lib.u8p))
+        if rc != _lib.OK:
+            raise GenericError("a coordinate is not below the modulus" if rc == _lib.ERR_INVALID_ARG else _lib.status_message(rc))
+    return out[:32 * n].tobytes()
+
+
 def to_byte_array(data_fr, max_output_size: int) -> bytes:
     """helpers.rs:80-119."""
     vals = frs_to_ints(data_fr)

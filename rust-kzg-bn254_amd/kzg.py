@@ -451,6 +451,13 @@ class KZG:
             raise GenericError(_lib.status_message(rc))
         return ys, out
 
+    def encode_cosets_be(self, polynomial, srs, n: int, chunk_len: int = 1):
+        """`encode_cosets` in the serialized form a disperser sends (`verifier.encode_coset_items`): (ys_be, proofs_be) bytes, 32 per value
+        (big-endian) and per proof (gnark-compressed), what `verifier.verify_multiproof_batch_bytes` takes."""
+        from . import verifier
+        ys, proofs = self.encode_cosets(polynomial, srs, n, chunk_len)
+        return verifier.encode_coset_items(ys, proofs)
+
     def cosets(self, polynomial_eval_form, chunk_len: int = 1) -> np.ndarray:
         """The values that go with the proofs of `compute_multiproofs`: an (m, chunk_len, 4) array, m = n / chunk_len, whose row k is
         evals[k::m], the evaluations on the coset {w^(k + j m) : j < chunk_len} -- what `verifier.verify_multiproof*` takes as `ys`."""

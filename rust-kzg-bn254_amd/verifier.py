@@ -353,6 +353,116 @@ def verify_multiproof(commitment, proof, coset_index: int, ys, n: int, srs, g2_t
     return bool(ok.value)
 
 
+# ---- coset items in their serialized form ------------------------------------------------------------------------------------------
+# A commitment or proof is a 32-byte gnark-compressed G1 point, a value a 32-byte big-endian scalar.
+_ARRAYS = ("commitment", "proof", "value of item")
+
+
+def _u8_arg(data, want_len, what):
+    buf = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    if len(buf) != want_len:
+        raise InvalidInputLength()
+    return buf, (buf.ctypes.data_as(_lib.u8p) if len(buf) else None)
+
+
+def encode_coset_items(ys, proofs):
+    """The disperser's half (`kzg_coset_items_encode_be`, host): values (count, l, 4) and wire proofs (count, 8) -> (ys_be, proofs_be)
+    bytes, 32 per value and per proof.  Either may be None."""
+    ys_a = None if ys is None else np.ascontiguousarray(_lib.as_u64(ys, 0))
+    if ys_a is not None and (ys_a.ndim != 3 or ys_a.shape[2] != 4):
+        raise InvalidInputLength()
+    pf = None if proofs is None else _pack(proofs, 8)
+    count = len(ys_a) if ys_a is not None else len(pf) if pf is not None else 0
+    if ys_a is not None and pf is not None and len(pf) != count:
+        raise GenericError("length's of the input are not the same")
+    l = ys_a.shape[1] if ys_a is not None else 1
+    out_y = np.zeros(max(count * l * 32, 1), np.uint8) if ys_a is not None else None
+    out_p = np.zeros(max(count * 32, 1), np.uint8) if pf is not None else None
+    if count:
+        rc = _lib.load().kzg_coset_items_encode_be(None if ys_a is None else _lib.ptr(ys_a), None if pf is None else _lib.ptr(pf), count, l,
+                                                   None if out_y is None else out_y.ctypes.data_as(_lib.u8p),
+                                                   None if out_p is None else out_p.ctypes.data_as(_lib.u8p))
+        if rc != _lib.OK:
+            raise GenericError("a value or coordinate is not below its modulus" if rc == _lib.ERR_INVALID_ARG else _lib.status_message(rc))
+    return (None if out_y is None else out_y[:count * l * 32].tobytes()), (None if out_p is None else out_p[:count * 32].tobytes())
+
+
+def decode_coset_items(ys_be, proofs_be, chunk_len: int, ctx=None):
+    """Serialized items -> (ys (count, l, 4), proofs (count, 8)) wire words, decoded strictly on the GPU (`kzg_coset_items_decode_be`):
+    what `locate_bad_multiproofs`, `coset_group_sums` and `KZG.recover_from_cosets` take.  Either input may be None (its output is then
+    None).  DeserializationError / NotOnCurveError name the array and the item; proofs are checked before values."""
+    l = int(chunk_len)
+    if ys_be is None and proofs_be is None:
+        raise InvalidInputLength()
+    if ys_be is not None and (l <= 0 or len(ys_be) % (32 * l) != 0) or proofs_be is not None and len(proofs_be) % 32 != 0:
+        raise InvalidInputLength()
+    count = len(ys_be) // (32 * l) if ys_be is not None else len(proofs_be) // 32
+    yb, yp = (None, None) if ys_be is None else _u8_arg(ys_be, count * l * 32, "values")
+    pb, pp = (None, None) if proofs_be is None else _u8_arg(proofs_be, count * 32, "proofs")
+    ctx = ctx or _lib.default_context()
+    ys = None if ys_be is None else np.zeros((count, l, 4), np.uint64)
+    pf = None if proofs_be is None else np.zeros((count, 8), np.uint64)
+    if count:
+        bad, arr = C.c_uint64(0), _lib.i32(0)
+        rc = _lib.load().kzg_coset_items_decode_be(ctx.handle, yp, pp, count, l, None if ys is None else _lib.ptr(ys), None if pf is None else _lib.ptr(pf),
+                                                   C.byref(bad), C.byref(arr))
+        helpers.raise_for_decode(rc, _ARRAYS[arr.value] if 0 <= arr.value < 3 else "element", bad.value, ctx)
+    return ys, pf
+
+
+def _bytes_args(commitments_be, commitment_indices, coset_indices, ys_be, proofs_be, chunk_len):
+    l = int(chunk_len)
+    if l <= 0 or len(proofs_be) % 32 != 0 or len(commitments_be) % 32 != 0:
+        raise InvalidInputLength()
+    count = len(proofs_be) // 32
+    ci = np.ascontiguousarray([int(v) for v in commitment_indices], dtype=np.uint64)
+    ki = np.ascontiguousarray([int(v) for v in coset_indices], dtype=np.uint64)
+    if not (len(ci) == len(ki) == count):
+        raise GenericError("length's of the input are not the same")
+    cm = _u8_arg(commitments_be, len(commitments_be), "commitments")
+    ys = _u8_arg(ys_be, count * l * 32, "values")
+    pf = _u8_arg(proofs_be, count * 32, "proofs")
+    return cm, ci, ki, ys, pf, count, l
+
+
+def compute_multiproof_r_powers_bytes(commitments_be, commitment_indices, coset_indices, ys_be, proofs_be, n: int, chunk_len: int) -> np.ndarray:
+    """The weights of `compute_multiproof_r_powers`, bit for bit, from the serialized form of the same items
+    (`kzg_compute_multiproof_r_powers_bytes`, host only): the item message is assembled from the bytes, no field arithmetic before the
+    final mod r.  Bytes that do not decode are hashed as given."""
+    cm, ci, ki, ys, pf, count, l = _bytes_args(commitments_be, commitment_indices, coset_indices, ys_be, proofs_be, chunk_len)
+    out = np.zeros((count, 4), dtype=np.uint64)
+    if count:
+        rc = _lib.load().kzg_compute_multiproof_r_powers_bytes(cm[1], len(cm[0]) // 32, _lib.ptr(ci), _lib.ptr(ki), ys[1], pf[1], count, int(n), l, _lib.ptr(out))
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+    return out
+
+
+def verify_multiproof_batch_bytes(commitments_be, commitment_indices, coset_indices, ys_be, proofs_be, n: int, chunk_len: int, srs, g2_tau_l=None,
+                                  r_powers=None, ctx=None, return_r_powers=False):
+    """`verify_multiproof_batch` on serialized items, the decode inside the call (`kzg_verify_multiproof_batch_bytes`): commitments_be
+    M x 32, proofs_be count x 32, ys_be count x l x 32 bytes.  The verdict and the weights are those of the decoded entry on the decoded
+    inputs.  DeserializationError / NotOnCurveError name the array (commitment, proof, value of item) and the index, in that order of
+    arrays.  `return_r_powers=True` returns (ok, weights used)."""
+    cm, ci, ki, ys, pf, count, l = _bytes_args(commitments_be, commitment_indices, coset_indices, ys_be, proofs_be, chunk_len)
+    if g2_tau_l is None and l != 1:
+        raise GenericError("g2_tau_l = None (consts::G2_TAU) is [tau]_2: chunks of more than one point need [tau^l]_2")
+    ctx = ctx or getattr(srs, "ctx", None) or _lib.default_context()
+    rp = None if r_powers is None else np.ascontiguousarray(_lib.as_u64(r_powers, 0)).reshape(-1, 4)
+    if rp is not None and len(rp) != count:
+        raise GenericError("length's of the input are not the same")
+    out_rp = np.zeros((count, 4), dtype=np.uint64)
+    ok, bad, arr = _lib.i32(0), C.c_uint64(0), _lib.i32(-1)
+    rc = _lib.load().kzg_verify_multiproof_batch_bytes(ctx.handle, srs.handle, cm[1], len(cm[0]) // 32, _lib.ptr(ci) if count else None,
+                                                       _lib.ptr(ki) if count else None, ys[1], pf[1], count, int(n), l,
+                                                       None if rp is None or count == 0 else _lib.ptr(rp), _g2_arg(g2_tau_l), C.byref(ok),
+                                                       _lib.ptr(out_rp) if count else None, C.byref(bad), C.byref(arr))
+    if rc in (_lib.ERR_DESERIALIZE, _lib.ERR_NOT_ON_CURVE):
+        helpers.raise_for_decode(rc, _ARRAYS[arr.value] if 0 <= arr.value < 3 else "element", bad.value, ctx)
+    _raise_for(rc, ctx)
+    return (bool(ok.value), out_rp) if return_r_powers else bool(ok.value)
+
+
 # ---- locating the bad items of a rejected batch ----------------------------------------------------------------------------------
 pairings_verify = helpers.pairings_verify          # e(a1, a2) == e(b1, b2): the check of one pair of group sums against ([tau^l]_2, G2)
 
