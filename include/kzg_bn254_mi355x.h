@@ -27,7 +27,7 @@
  *   KZG_ROCTX=1                           roctx ranges around the host phases (rocprofv3 --marker-trace)
  *   KZG_NTT_TILE_LOG=10 / 11              one tile size of the Fr NTT at every transform size
  *   KZG_EXCHANGE_TIMEOUT_S, KZG_RCCL_LIB  the _rccl entries: seconds to wait for a collective (60); the RCCL to dlopen
- * Per-context settings are calls (kzg_ctx_set_msm_window, kzg_ctx_set_reduction_lanes, kzg_ctx_set_transcript_device).  Entry points marked MEASUREMENT ONLY below
+ * Per-context settings are calls (kzg_ctx_set_msm_window, kzg_ctx_set_reduction_lanes, kzg_ctx_set_transcript_device, kzg_ctx_set_encode_group_bytes).  Entry points marked MEASUREMENT ONLY below
  * (kzg_ctx_set_profiling, kzg_ctx_get_msm_profile*, kzg_ctx_measure_valu_rates) exist for bench.py's roofline figures; a host binding can leave them out.
  */
 #ifndef KZG_BN254_MI355X_H
@@ -309,6 +309,55 @@ int32_t kzg_srs_drop_multiproof(kzg_ctx* ctx, kzg_srs* srs);
 int32_t kzg_encode_cosets(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, size_t poly_len /* d */, int32_t eval_form,
                           size_t n, size_t chunk_len, uint64_t* out_ys_mont /* m x chunk_len x 4, may be NULL */,
                           uint64_t* out_proofs_xy_mont /* m x 8, may be NULL */, uint8_t* out_is_infinity /* m */);
+/* kzg_encode_cosets for `count` blobs of one shape (d, n, l, eval_form) in one call.  polys: count x d Fr elements, blob b at
+ * polys + b d 4; row b of every output (out_ys: count x m x l x 4, out_proofs_xy: count x m x 8, out_is_infinity: count x m) is
+ * bit-identical to kzg_encode_cosets on blob b.  The FK20 table is the same (d, l) entry, built once.  The call works through the
+ * blobs in GROUPS whose device workspace fits a byte budget (4 GiB unless kzg_ctx_set_encode_group_bytes says otherwise; a group is
+ * never smaller than one blob, count has no cap): inside a group every stage is one launch for all its blobs, with the stage plan
+ * of the two G1 transforms chosen for the group, and there is one upload and one download per output array.  A shape whose
+ * single-blob stages already fill the device (every scalar-multiplication stage has >= 65 536 lanes) runs as groups of one, through
+ * the launches of kzg_encode_cosets.
+ * Errors, checked on the host before any kernel runs, in this order:
+ *   1. a null ctx, srs or polys; both outputs NULL; proofs without flags; count = 0 -> KZG_ERR_INVALID_ARG;
+ *   2. srs of another context, or a Lagrange-basis handle -> KZG_ERR_INVALID_ARG;
+ *   3. poly_len or n zero or not a power of two -> KZG_ERR_NOT_POWER_OF_TWO;
+ *   4. n > 2^24 -> KZG_ERR_DOMAIN;
+ *   5. poly_len > n, poly_len = 1, chunk_len not a power of two or > poly_len / 2 -> KZG_ERR_INVALID_ARG;
+ *   6. poly_len > kzg_srs_len(srs) -> KZG_ERR_SRS_CAPACITY_EXCEEDED;
+ *   7. a count whose output sizes (count x n x 64 bytes) overflow size_t -> KZG_ERR_INVALID_ARG.
+ * A failed allocation -> KZG_ERR_DEVICE (kzg_ctx_last_error has the text).  After any error the context stays usable. */
+int32_t kzg_encode_cosets_batch(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* polys_mont /* count x d x 4 */, size_t count,
+                                size_t poly_len /* d */, int32_t eval_form, size_t n, size_t chunk_len,
+                                uint64_t* out_ys_mont /* count x m x l x 4, may be NULL */,
+                                uint64_t* out_proofs_xy_mont /* count x m x 8, may be NULL */, uint8_t* out_is_infinity /* count x m */);
+/* The workspace budget of a group of kzg_encode_cosets_batch on this context, in bytes; 0 = the default (4 GiB). */
+int32_t kzg_ctx_set_encode_group_bytes(kzg_ctx* ctx, size_t bytes);
+/* What kzg_encode_cosets_batch would do with these arguments: a pure query (no context, no device).  values / proofs: which outputs
+ * are asked for; group_bytes: the budget, 0 = the default.  Errors: out NULL or neither output -> KZG_ERR_INVALID_ARG, then rows 3, 4,
+ * 5 and 7 of the table above. */
+enum { KZG_ENCODE_FORM_NONE = 0, KZG_ENCODE_FORM_COPY = 1, KZG_ENCODE_FORM_DIRECT = 2, KZG_ENCODE_FORM_RADIX2 = 3 };
+enum { KZG_ENCODE_LOAD_IN_PLACE = 0,   /* the first stage reads the input where it is */
+       KZG_ENCODE_LOAD_COPY = 1,       /* a copy of the strided slice */
+       KZG_ENCODE_LOAD_BITREV = 2,     /* a bit-reversed copy (radix-2) */
+       KZG_ENCODE_LOAD_PAD = 3,        /* the padding copy (direct stages, r >= 2) */
+       KZG_ENCODE_LOAD_SPREAD = 4 };   /* the spread load (radix-2, r >= 2) */
+typedef struct kzg_encode_transform_info {
+    int32_t form;      /* KZG_ENCODE_FORM_*; NONE: no proofs asked for */
+    int32_t pairs;     /* 1: the stages run on lane pairs, 0: on lanes */
+    int32_t stages;    /* stages that multiply points (each one scalar multiplication deep) */
+    int32_t load;      /* KZG_ENCODE_LOAD_* */
+} kzg_encode_transform_info;
+typedef struct kzg_encode_batch_info {
+    uint64_t blobs_per_group;            /* the last group of a call may hold fewer */
+    uint64_t groups;
+    uint64_t group_bytes;                /* device workspace of one full group */
+    int32_t batched;                     /* 0: the groups-of-one rule applies to this shape */
+    int32_t reserved;
+    kzg_encode_transform_info inverse;   /* the inverse G1 FFT of 2d / l points, as planned for a full group */
+    kzg_encode_transform_info forward;   /* the zero-padded forward G1 FFT of n / l points */
+} kzg_encode_batch_info;
+int32_t kzg_encode_cosets_batch_info(size_t poly_len /* d */, size_t n, size_t chunk_len, size_t count, int32_t values, int32_t proofs,
+                                     size_t group_bytes, kzg_encode_batch_info* out);
 /* KZG::compute_proof / compute_proof_impl (kzg.rs:128-178, :215-234, on-domain branch :237-260).
  * roots = KZG::expanded_roots_of_unity (n_roots entries); n != n_roots -> KZG_ERR_ROOTS_LENGTH.
  * out_y (optional, 4 u64) receives y = p(z) (helpers.rs:475-535). */

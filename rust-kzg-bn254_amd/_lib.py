@@ -43,6 +43,20 @@ ERR_IO = -22
 G2_CHECK_SUBGROUP = 1                                            # KZG_G2_CHECK_SUBGROUP, KZG_G2_REJECT_GENERATOR of the header
 G2_REJECT_GENERATOR = 2
 
+
+
+class EncodeTransformInfo(C.Structure):                          # kzg_encode_transform_info of the header
+    _fields_ = [("form", C.c_int32), ("pairs", C.c_int32), ("stages", C.c_int32), ("load", C.c_int32)]
+
+
+class EncodeBatchInfo(C.Structure):                              # kzg_encode_batch_info of the header
+    _fields_ = [("blobs_per_group", C.c_uint64), ("groups", C.c_uint64), ("group_bytes", C.c_uint64), ("batched", C.c_int32),
+                ("reserved", C.c_int32), ("inverse", EncodeTransformInfo), ("forward", EncodeTransformInfo)]
+
+
+ENCODE_FORMS = ("none", "copy", "direct", "radix2")              # KZG_ENCODE_FORM_*
+ENCODE_LOADS = ("in place", "copy", "bitrev", "pad", "spread")   # KZG_ENCODE_LOAD_*
+
 u64p = C.POINTER(C.c_uint64)
 u8p = C.POINTER(C.c_uint8)
 vp = C.c_void_p
@@ -103,6 +117,9 @@ PROTOTYPES = {
     "kzg_srs_drop_lagrange": (i32, [vp, vp]),
     "kzg_compute_multiproofs": (i32, [vp, vp, u64p, sz, i32, sz, u64p, u8p]),
     "kzg_encode_cosets": (i32, [vp, vp, u64p, sz, i32, sz, sz, u64p, u64p, u8p]),
+    "kzg_encode_cosets_batch": (i32, [vp, vp, u64p, sz, sz, i32, sz, sz, u64p, u64p, u8p]),
+    "kzg_ctx_set_encode_group_bytes": (i32, [vp, sz]),
+    "kzg_encode_cosets_batch_info": (i32, [sz, sz, sz, sz, i32, i32, sz, vp]),
     "kzg_srs_cache_multiproof": (i32, [vp, vp, sz, sz]),
     "kzg_srs_drop_multiproof": (i32, [vp, vp]),
     "kzg_blob_to_fr": (i32, [vp, u8p, sz, u64p, sz, C.POINTER(sz)]),
@@ -283,6 +300,12 @@ class Context:
         measurement hook)."""
         if load().kzg_ctx_set_transcript_device(self.handle, mode) != OK:
             raise ValueError("mode must be 0, 1 or 2")
+
+    def set_encode_group_bytes(self, nbytes=0):
+        """The device-workspace budget of a group of `KZG.encode_cosets_batch` on this context, in bytes; 0 = the default (4 GiB).  A group
+        is never smaller than one blob (same results whatever the budget)."""
+        if nbytes < 0 or load().kzg_ctx_set_encode_group_bytes(self.handle, int(nbytes)) != OK:
+            raise ValueError("the budget is a byte count >= 0")
 
     def close(self):
         if self.handle:

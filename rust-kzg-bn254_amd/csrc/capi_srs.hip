@@ -353,6 +353,56 @@ int32_t kzg_encode_cosets(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont,
     return multiproof_encode(ctx, srs, poly_mont, eval_form != 0, plan, out_ys_mont, out_proofs_xy_mont, out_is_infinity);
 }
 
+int32_t kzg_encode_cosets_batch(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* polys_mont, size_t count, size_t poly_len, int32_t eval_form, size_t n,
+                                size_t chunk_len, uint64_t* out_ys_mont, uint64_t* out_proofs_xy_mont, uint8_t* out_is_infinity) {
+    const bool bad_pointers = !ctx || !srs || !polys_mont || (!out_ys_mont && !out_proofs_xy_mont) || (out_proofs_xy_mont && !out_is_infinity);
+    const bool bad_srs = !bad_pointers && (srs->ctx != ctx || srs->lagrange_of != 0);
+    int32_t rc = encode_batch_check(bad_pointers, bad_srs, count, poly_len, n, chunk_len, srs ? srs->n : 0);
+    if (rc != KZG_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const EncodeBatchPlan plan = encode_batch_plan(poly_len, n, chunk_len, count, out_ys_mont != nullptr, out_proofs_xy_mont != nullptr, ctx->encode_group_bytes);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return multiproof_encode_batch(ctx, srs, polys_mont, eval_form != 0, plan, out_ys_mont, out_proofs_xy_mont, out_is_infinity);
+}
+
+int32_t kzg_ctx_set_encode_group_bytes(kzg_ctx* ctx, size_t bytes) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->encode_group_bytes = bytes;
+    return KZG_OK;
+}
+
+static void encode_info_transform(const G1fftPlan& p, kzg_encode_transform_info* t) {
+    t->form = p.form == G1FFT_COPY ? KZG_ENCODE_FORM_COPY : p.form == G1FFT_RADIX2 ? KZG_ENCODE_FORM_RADIX2 : KZG_ENCODE_FORM_DIRECT;
+    t->load = KZG_ENCODE_LOAD_IN_PLACE;
+    t->pairs = 0;
+    t->stages = 0;
+    for (int i = 0; i < p.n_stages; ++i) {
+        const G1fftStage& st = p.stage[i];
+        if (st.K > 0) { ++t->stages; t->pairs = st.kind == G1S_DIRECT_PAIRS || st.kind == G1S_RADIX2_PAIRS; }
+        else t->load = st.kind == G1S_GATHER ? KZG_ENCODE_LOAD_COPY : st.kind == G1S_GATHER_BITREV ? KZG_ENCODE_LOAD_BITREV
+                     : st.kind == G1S_GATHER_PAD ? KZG_ENCODE_LOAD_PAD : KZG_ENCODE_LOAD_SPREAD;
+    }
+}
+
+int32_t kzg_encode_cosets_batch_info(size_t poly_len, size_t n, size_t chunk_len, size_t count, int32_t values, int32_t proofs, size_t group_bytes,
+                                     kzg_encode_batch_info* out) {
+    int32_t rc = encode_batch_check(!out || (!values && !proofs), false, count, poly_len, n, chunk_len, SIZE_MAX);
+    if (rc != KZG_OK) return rc;
+    const EncodeBatchPlan bp = encode_batch_plan(poly_len, n, chunk_len, count, values != 0, proofs != 0, group_bytes);
+    *out = kzg_encode_batch_info{};
+    out->blobs_per_group = bp.group;
+    out->groups = bp.n_groups;
+    out->group_bytes = bp.group_bytes;
+    out->batched = bp.batched ? 1 : 0;
+    if (proofs) {
+        // a group of one runs kzg_encode_cosets' own launches: its plans are those of one transform, which is what batch = 1 gives
+        encode_info_transform(bp.ifft, &out->inverse);
+        encode_info_transform(bp.fft.plan, &out->forward);
+    }
+    return KZG_OK;
+}
+
 int32_t kzg_srs_cache_multiproof(kzg_ctx* ctx, kzg_srs* srs, size_t n, size_t chunk_len) {
     int32_t rc = multiproof_check(ctx, srs, n, chunk_len);
     if (rc != KZG_OK) return rc;

@@ -102,6 +102,7 @@ struct kzg_ctx {
     std::string last_error;
     int msm_c_override = 0;
     int msm_seg_override = 0;
+    size_t encode_group_bytes = 0;         // kzg_ctx_set_encode_group_bytes: the workspace budget of a group of kzg_encode_cosets_batch, 0 = ENCODE_GROUP_BYTES_DEFAULT
     int reduction_lanes = 0;               // kzg_ctx_set_reduction_lanes: 0 automatic, 2 lane pairs, 4 lane quads
     std::atomic<int> transcript_device{0}; // kzg_ctx_set_transcript_device: 0 automatic, 1 always host, 2 always device (the weights of kzg_verify_multiproof_batch)
     bool profiling = false;
@@ -269,6 +270,8 @@ int32_t ntt_get_tables(kzg_ctx* ctx, int log_n, bool inverse, NttTables* out);
 
 // In-place NTT on device data (wire format), natural order in/out.
 int32_t ntt_run(kzg_ctx* ctx, void* d_data, size_t n, bool inverse, hipStream_t st = nullptr, NttWorkspace* ws = nullptr);
+// `rows` transforms of n points, row r at d_data + r n elements, one launch per pass (ntt_run is rows = 1)
+int32_t ntt_run_batch(kzg_ctx* ctx, void* d_data, size_t n, size_t rows, bool inverse, hipStream_t st = nullptr, NttWorkspace* ws = nullptr);
 
 // synthetic SRS P_i = tau^i * G1 written to d_points (device format); device SRS -> wire on the host
 int32_t srs_generate(kzg_ctx* ctx, const uint64_t tau_mont[4], uint64_t first_power, size_t n, uint4* d_points);
@@ -303,10 +306,12 @@ int32_t g1_ifft_run(kzg_ctx* ctx, const kzg_srs* srs, size_t n, uint64_t* out_xy
 int32_t g1_ifft_device(kzg_ctx* ctx, const kzg_srs* srs, size_t n, uint4* d_out, bool wire);
 // the generic G1 transform of XYZZ planes (g1fft.hip): forward or inverse, optional 1/n, input read with its own stride; and the
 // batched affine conversion of n planes.  Both enqueued on st.
-int32_t g1_fft_planes(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t n, int32_t* out, int32_t* tmp, bool inverse, bool scaled);
+// a batch of transforms in one launch sequence: `batch` plane sets, in_batch / out_batch / tmp_batch words apart (the default: one transform)
+struct G1fftBatch { size_t batch = 1, in_batch = 0, out_batch = 0, tmp_batch = 0; };
+int32_t g1_fft_planes(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t n, int32_t* out, int32_t* tmp, bool inverse, bool scaled, const G1fftBatch& b = G1fftBatch());
 // the forward transform of an input that is the identity from point `nonzero` on (host_encode.h: the spread load of the radix-2 form)
-int32_t g1_fft_planes_padded(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t nonzero, size_t n, int32_t* out, int32_t* tmp);
-int32_t g1fft_planes_to_affine(kzg_ctx* ctx, hipStream_t st, const int32_t* planes, size_t n, uint4* d_out, bool wire, int32_t* scratch);
+int32_t g1_fft_planes_padded(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t nonzero, size_t n, int32_t* out, int32_t* tmp, const G1fftBatch& b = G1fftBatch());
+int32_t g1fft_planes_to_affine(kzg_ctx* ctx, hipStream_t st, const int32_t* planes, size_t n, uint4* d_out, bool wire, int32_t* scratch, size_t batch = 1, size_t planes_batch = 0);
 // FK20 multi-proofs (multiproof.hip): the cached FFT_2m(S^(b)) of (srs, n, l), built if absent; the proofs of every coset of l points
 int32_t multiproof_cache(kzg_ctx* ctx, kzg_srs* srs, size_t n, size_t l, const uint4** out);
 int32_t multiproof_run(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, size_t n, bool eval_form, size_t l, uint64_t* out_xy, uint8_t* out_inf);
@@ -314,6 +319,8 @@ void multiproof_drop(kzg_srs* srs);
 // kzg_encode_cosets (multiproof.hip): the m = n / l cosets of values and their proofs for d = plan.d coefficients or evaluations;
 // either output may be null.  Called under ctx->mu with the arguments checked, synchronised on return
 int32_t multiproof_encode(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, bool eval_form, const EncodePlan& plan, uint64_t* out_ys, uint64_t* out_xy, uint8_t* out_inf);
+// kzg_encode_cosets_batch: plan.count blobs of that shape, group by group (host_encode.h EncodeBatchPlan); row b of every output is that of multiproof_encode on blob b
+int32_t multiproof_encode_batch(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* polys_mont, bool eval_form, const EncodeBatchPlan& plan, uint64_t* out_ys, uint64_t* out_xy, uint8_t* out_inf);
 // verification of coset proofs (multiverify.hip): d_out[t] = sum_i weights[i] w^(-ks[i] t) IFFT_l(ys_i)[t], enqueued on ctx->stream (d_ys is scratch when l > 1024)
 int32_t coset_interpolate_rlc_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, size_t count, size_t n, size_t l, uint4* d_out);
 // locating the bad groups of a batch (multilocate.hip; LocatePlan: host_locate.h).  Called under ctx->mu with the device set, count > 0.

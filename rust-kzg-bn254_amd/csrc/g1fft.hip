@@ -103,7 +103,10 @@ k_g1fft_load(const uint4* __restrict__ points, uint32_t n, int32_t* __restrict__
 // ---- small n: one Stockham stage of radix R = 2^K as direct sums, one lane per (output, term) ---------------------------
 __global__ void __launch_bounds__(256)
 k_g1fft_direct(const int32_t* __restrict__ x, int32_t* __restrict__ y, uint32_t n, int log_n, int K, int log_s,
-               const uint4* __restrict__ scal /* n canonical scalars: w^-e, or w^-e / n in the last stage */, int last) {
+               const uint4* __restrict__ scal /* n canonical scalars: w^-e, or w^-e / n in the last stage */, int last,
+               size_t x_batch, size_t y_batch /* words between the plane sets of consecutive transforms of a batch (grid.y) */) {
+    x += blockIdx.y * x_batch;
+    y += blockIdx.y * y_batch;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
     const uint32_t R = 1u << K;
     const uint32_t o = t >> K, jp = t & (R - 1);                 // output element, term j'
@@ -147,7 +150,8 @@ k_g1fft_direct(const int32_t* __restrict__ x, int32_t* __restrict__ y, uint32_t 
 
 // ---- large n: radix-2 decimation in time on bit-reversed input, one butterfly per thread, in place ------------------------
 __global__ void __launch_bounds__(256)
-k_g1fft_stage(int32_t* __restrict__ planes, uint32_t n, int log_n, int s, const uint4* __restrict__ scal, int last) {
+k_g1fft_stage(int32_t* __restrict__ planes, uint32_t n, int log_n, int s, const uint4* __restrict__ scal, int last, size_t batch_stride) {
+    planes += blockIdx.y * batch_stride;
     uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n / 2) return;
     const uint32_t half = 1u << (s - 1);
@@ -186,7 +190,9 @@ k_g1fft_stage(int32_t* __restrict__ planes, uint32_t n, int log_n, int s, const 
 // pair_dbl_any and pair_scalar_mul: glv_lanes.h.
 __global__ void __launch_bounds__(256)
 k_g1fft_direct_pairs(const int32_t* __restrict__ x, int32_t* __restrict__ y, uint32_t n, int log_n, int K, int log_s,
-                     const uint4* __restrict__ scal, int last) {
+                     const uint4* __restrict__ scal, int last, size_t x_batch, size_t y_batch) {
+    x += blockIdx.y * x_batch;
+    y += blockIdx.y * y_batch;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63, pair = t >> 1;
     const bool odd = (t & 1u) != 0;
     const uint32_t R = 1u << K;
@@ -265,7 +271,8 @@ k_g1fft_mul_quads(const int32_t* __restrict__ x, int32_t* __restrict__ partial, 
 }
 
 __global__ void __launch_bounds__(256)
-k_g1fft_stage_pairs(int32_t* __restrict__ planes, uint32_t n, int log_n, int s, const uint4* __restrict__ scal, int last) {
+k_g1fft_stage_pairs(int32_t* __restrict__ planes, uint32_t n, int log_n, int s, const uint4* __restrict__ scal, int last, size_t batch_stride) {
+    planes += blockIdx.y * batch_stride;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, b = t >> 1;
     const bool odd = (t & 1u) != 0;
     const bool active = b < n / 2;                               // n / 2 >= 32 pairs here: whole waves are active or not, except the last one
@@ -533,7 +540,11 @@ __device__ __forceinline__ void affine_emit(uint4* __restrict__ out, size_t i, c
 // products of the denominators ZZ ZZZ go through `scratch` (9 limb planes, stride n).  per lane <= AFF_PER points.
 constexpr uint32_t AFF_PER = 4;        // 16 while the lane's inversion was a 381-product chain; with division steps (fe_invert.h) shorter chains on more lanes win: 84 -> ~45 us at 1 024 points
 __global__ void __launch_bounds__(256)
-k_g1fft_to_affine(const int32_t* __restrict__ planes, uint32_t n, uint4* __restrict__ out, int wire, int32_t* __restrict__ scratch) {
+k_g1fft_to_affine(const int32_t* __restrict__ planes, uint32_t n, uint4* __restrict__ out, int wire, int32_t* __restrict__ scratch,
+                  size_t planes_batch /* words between the plane sets of a batch (grid.y); its outputs and scratch rows are consecutive */) {
+    planes += blockIdx.y * planes_batch;
+    out += (size_t)blockIdx.y * 4 * n;
+    scratch += (size_t)blockIdx.y * NL * n;
     const uint32_t T = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
     Fq run;
@@ -631,7 +642,10 @@ k_g1fft_planes_to_wire(const int32_t* __restrict__ planes, uint32_t n, uint32_t*
 
 // dst[i] = src[j], j = i or bit-reversed i, 36 limb planes each (src: element j of limb plane k at src[k * src_stride + j])
 __global__ void __launch_bounds__(256)
-k_g1fft_gather_planes(const int32_t* __restrict__ src, size_t src_stride, uint32_t n, int32_t* __restrict__ dst, int bitrev_log) {
+k_g1fft_gather_planes(const int32_t* __restrict__ src, size_t src_stride, uint32_t n, int32_t* __restrict__ dst, int bitrev_log,
+                      size_t src_batch, size_t dst_batch) {
+    src += blockIdx.y * src_batch;
+    dst += blockIdx.y * dst_batch;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t j = bitrev_log > 0 ? (__brev(i) >> (32 - bitrev_log)) : i;
@@ -642,7 +656,10 @@ k_g1fft_gather_planes(const int32_t* __restrict__ src, size_t src_stride, uint32
 // ---- a zero-padded input (g1_fft_planes_padded): only the first `nonzero` points of src exist, the identity stands after them ----------
 // dst[i] = src[i] for i < nonzero, the identity (literal zeros) for nonzero <= i < n: the input copy of the direct stages
 __global__ void __launch_bounds__(256)
-k_g1fft_pad_planes(const int32_t* __restrict__ src, size_t src_stride, uint32_t nonzero, uint32_t n, int32_t* __restrict__ dst) {
+k_g1fft_pad_planes(const int32_t* __restrict__ src, size_t src_stride, uint32_t nonzero, uint32_t n, int32_t* __restrict__ dst,
+                   size_t src_batch, size_t dst_batch) {
+    src += blockIdx.y * src_batch;
+    dst += blockIdx.y * dst_batch;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
 #pragma unroll
@@ -653,7 +670,10 @@ k_g1fft_pad_planes(const int32_t* __restrict__ src, size_t src_stride, uint32_t 
 // bit-reversed order the non-zero inputs of the radix-2 form stand on the multiples of r = 2^log_r, and the stages 1 .. log_r are
 // butterflies (A, 0) -> (A, A): after them every run of r consecutive points holds one input, which is what this load writes.
 __global__ void __launch_bounds__(256)
-k_g1fft_spread_planes(const int32_t* __restrict__ src, size_t src_stride, uint32_t n, int log_nonzero, int log_r, int32_t* __restrict__ dst) {
+k_g1fft_spread_planes(const int32_t* __restrict__ src, size_t src_stride, uint32_t n, int log_nonzero, int log_r, int32_t* __restrict__ dst,
+                      size_t src_batch, size_t dst_batch) {
+    src += blockIdx.y * src_batch;
+    dst += blockIdx.y * dst_batch;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t q = i >> log_r;                                 // < 2^log_nonzero
@@ -664,10 +684,11 @@ k_g1fft_spread_planes(const int32_t* __restrict__ src, size_t src_stride, uint32
 
 // n XYZZ planes (stride n) -> n affine points (wire, or the device format of curve.h; identity = zeros), the batched conversion of
 // g1_ifft_device; scratch: n x NL words.  Enqueued on st.
-int32_t g1fft_planes_to_affine(kzg_ctx* ctx, hipStream_t st, const int32_t* planes, size_t n, uint4* d_out, bool wire, int32_t* scratch) {
+// batch plane sets planes_batch words apart (one per grid.y): point i of set b goes to d_out[b n + i], scratch: batch x n x NL words.
+int32_t g1fft_planes_to_affine(kzg_ctx* ctx, hipStream_t st, const int32_t* planes, size_t n, uint4* d_out, bool wire, int32_t* scratch, size_t batch, size_t planes_batch) {
     const size_t lanes = std::max<size_t>(1, (n + AFF_PER - 1) / AFF_PER);
     const unsigned blocks = (unsigned)std::min<size_t>((lanes + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_g1fft_to_affine, dim3(blocks), dim3(256), 0, st, planes, (uint32_t)n, d_out, wire ? 1 : 0, scratch);
+    hipLaunchKernelGGL(k_g1fft_to_affine, dim3(blocks, (unsigned)batch), dim3(256), 0, st, planes, (uint32_t)n, d_out, wire ? 1 : 0, scratch, planes_batch);
     KZG_HIP_TRY(ctx, hipGetLastError());
     return KZG_OK;
 }
@@ -689,6 +710,7 @@ struct G1fftOperands {
     const uint4* tab = nullptr;                     // first-tables stage: the window tables
     uint32_t nonzero = 0;                           // pad / spread load: the points the input has
     int log_nonzero = 0;
+    size_t in_batch = 0, buf_batch[2] = {0, 0};     // a batch (G1fftPlan::batch > 1): words between consecutive transforms' plane sets in `in` and in the two buffers
 };
 
 static int32_t g1fft_fetch_scalars(kzg_ctx* ctx, const G1fftPlan& p, G1fftOperands& io) {
@@ -706,9 +728,10 @@ static int32_t g1fft_launch(kzg_ctx* ctx, hipStream_t st, const G1fftPlan& p, co
     const dim3 block(256);
     for (int i = 0; i < p.n_stages; ++i) {
         const G1fftStage& s = p.stage[i];
-        const dim3 grid((unsigned)s.grid);
+        const dim3 grid((unsigned)s.grid, p.batch);                  // only the plane-to-plane kernels take a batch (the planner gives no other form one)
         const int32_t* src = s.src == G1BUF_INPUT ? io.in : io.buf[s.src];
         int32_t* dst = io.buf[s.dst];
+        const size_t src_batch = s.src == G1BUF_INPUT ? io.in_batch : io.buf_batch[s.src], dst_batch = io.buf_batch[s.dst];
         const uint4* scal = s.scal >= 0 ? io.scal[s.scal] : nullptr;
         const int last = s.last ? 1 : 0;
         switch (s.kind) {
@@ -716,7 +739,7 @@ static int32_t g1fft_launch(kzg_ctx* ctx, hipStream_t st, const G1fftPlan& p, co
             hipLaunchKernelGGL(k_g1fft_load, grid, block, 0, st, io.points, n, dst, s.kind == G1S_LOAD_BITREV ? log_n : 0);
             break;
         case G1S_GATHER: case G1S_GATHER_BITREV:
-            hipLaunchKernelGGL(k_g1fft_gather_planes, grid, block, 0, st, io.in, io.in_stride, n, dst, s.kind == G1S_GATHER_BITREV ? log_n : 0);
+            hipLaunchKernelGGL(k_g1fft_gather_planes, grid, block, 0, st, io.in, io.in_stride, n, dst, s.kind == G1S_GATHER_BITREV ? log_n : 0, io.in_batch, dst_batch);
             break;
         case G1S_BITS:
             hipLaunchKernelGGL(k_g1fft_bits, grid, block, 0, st, io.d_bits, io.srs_n, io.d_t3, io.t3_points, n, log_n, s.K, io.nl.list, io.nl.cnt, s.Q, s.wpo, io.partial);
@@ -725,25 +748,25 @@ static int32_t g1fft_launch(kzg_ctx* ctx, hipStream_t st, const G1fftPlan& p, co
             hipLaunchKernelGGL(k_g1fft_first_tables, grid, block, 0, st, io.tab, io.srs_n, p.tab_c, p.tab_W, n, log_n, s.K, scal, s.wpo, io.partial);
             break;
         case G1S_DIRECT:
-            hipLaunchKernelGGL(k_g1fft_direct, grid, block, 0, st, src, dst, n, log_n, s.K, s.log_s, scal, last);
+            hipLaunchKernelGGL(k_g1fft_direct, grid, block, 0, st, src, dst, n, log_n, s.K, s.log_s, scal, last, src_batch, dst_batch);
             break;
         case G1S_DIRECT_PAIRS:
-            hipLaunchKernelGGL(k_g1fft_direct_pairs, grid, block, 0, st, src, dst, n, log_n, s.K, s.log_s, scal, last);
+            hipLaunchKernelGGL(k_g1fft_direct_pairs, grid, block, 0, st, src, dst, n, log_n, s.K, s.log_s, scal, last, src_batch, dst_batch);
             break;
         case G1S_MUL_QUADS:
             hipLaunchKernelGGL(k_g1fft_mul_quads, grid, block, 0, st, src, io.partial, n, log_n, s.K, s.log_s, scal, last);
             break;
         case G1S_RADIX2:
-            hipLaunchKernelGGL(k_g1fft_stage, grid, block, 0, st, dst, n, log_n, s.log_s, scal, last);
+            hipLaunchKernelGGL(k_g1fft_stage, grid, block, 0, st, dst, n, log_n, s.log_s, scal, last, dst_batch);
             break;
         case G1S_RADIX2_PAIRS:
-            hipLaunchKernelGGL(k_g1fft_stage_pairs, grid, block, 0, st, dst, n, log_n, s.log_s, scal, last);
+            hipLaunchKernelGGL(k_g1fft_stage_pairs, grid, block, 0, st, dst, n, log_n, s.log_s, scal, last, dst_batch);
             break;
         case G1S_GATHER_PAD:
-            hipLaunchKernelGGL(k_g1fft_pad_planes, grid, block, 0, st, io.in, io.in_stride, io.nonzero, n, dst);
+            hipLaunchKernelGGL(k_g1fft_pad_planes, grid, block, 0, st, io.in, io.in_stride, io.nonzero, n, dst, io.in_batch, dst_batch);
             break;
         case G1S_SPREAD_BITREV:
-            hipLaunchKernelGGL(k_g1fft_spread_planes, grid, block, 0, st, io.in, io.in_stride, n, io.log_nonzero, s.log_s, dst);
+            hipLaunchKernelGGL(k_g1fft_spread_planes, grid, block, 0, st, io.in, io.in_stride, n, io.log_nonzero, s.log_s, dst, io.in_batch, dst_batch);
             break;
         case G1S_KINDS:
             break;
@@ -768,7 +791,7 @@ static int32_t g1fft_t3_tables(kzg_ctx* ctx, const kzg_srs* srs, const uint4* d_
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_g1fft_t3_planes, dim3((total + 255) / 256), dim3(256), 0, st, d_bits, (uint32_t)srs->n, pts, total, ctx->poly[0].c.as<int32_t>());
             const size_t lanes = (total + AFF_PER - 1) / AFF_PER;
-            hipLaunchKernelGGL(k_g1fft_to_affine, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, ctx->poly[0].c.as<int32_t>(), total, t3, 0, ctx->poly[0].a.as<int32_t>());
+            hipLaunchKernelGGL(k_g1fft_to_affine, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, ctx->poly[0].c.as<int32_t>(), total, t3, 0, ctx->poly[0].a.as<int32_t>(), (size_t)0);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -825,15 +848,20 @@ int32_t g1_ifft_device(kzg_ctx* ctx, const kzg_srs* srs, size_t n, uint4* d_out,
 // out, tmp: n points each, stride n, neither aliasing in.  The stage plan, the kernels and the scalar tables are g1_ifft's
 // (g1fft_plan.h: the direct stages on lanes or pairs, radix-2 butterflies); forward transforms use the tables of w^+e.
 // Enqueued on st; no synchronisation.
-int32_t g1_fft_planes(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t n, int32_t* out, int32_t* tmp, bool inverse, bool scaled) {
-    const G1fftPlan p = g1fft_plan_planes(n, inverse, scaled, in_stride != n);
+// A batch (b.batch > 1): that many transforms per launch, transform t reading in + t b.in_batch and leaving out + t b.out_batch (words;
+// tmp likewise); the stage plan is chosen for the batch (g1fft_plan.h).
+int32_t g1_fft_planes(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t n, int32_t* out, int32_t* tmp, bool inverse, bool scaled, const G1fftBatch& b) {
+    const G1fftPlan p = g1fft_plan_planes(n, inverse, scaled, in_stride != n, b.batch);
     G1fftOperands io;
     int32_t rc = g1fft_fetch_scalars(ctx, p, io);
     if (rc != KZG_OK) return rc;
     io.in = in;
     io.in_stride = in_stride;
+    io.in_batch = b.in_batch;
     io.buf[p.result] = out;                                                  // the plan's ping-pong ends in out
     io.buf[1 - p.result] = tmp;
+    io.buf_batch[p.result] = b.out_batch;
+    io.buf_batch[1 - p.result] = b.tmp_batch;
     return g1fft_launch(ctx, st, p, io);
 }
 
@@ -841,8 +869,8 @@ int32_t g1_fft_planes(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in
 // in holds `nonzero` points (a power of two, <= n) with stride in_stride.  The plan is host_encode.h's: the direct stages behind a
 // copy that pads, or the spread load and the radix-2 stages log2(n / nonzero) + 1 .. log2 n, on lanes or lane pairs as
 // g1fft_choose_plan says for n.  The same group elements as g1_fft_planes on the padded input.  Enqueued on st.
-int32_t g1_fft_planes_padded(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t nonzero, size_t n, int32_t* out, int32_t* tmp) {
-    const G1fftPaddedPlan pp = g1fft_plan_planes_padded(n, nonzero);
+int32_t g1_fft_planes_padded(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t nonzero, size_t n, int32_t* out, int32_t* tmp, const G1fftBatch& b) {
+    const G1fftPaddedPlan pp = g1fft_plan_planes_padded(n, nonzero, b.batch);
     const G1fftPlan& p = pp.plan;
     G1fftOperands io;
     int32_t rc = g1fft_fetch_scalars(ctx, p, io);
@@ -851,8 +879,11 @@ int32_t g1_fft_planes_padded(kzg_ctx* ctx, hipStream_t st, const int32_t* in, si
     io.in_stride = in_stride;
     io.nonzero = pp.nonzero;
     io.log_nonzero = pp.log_nonzero;
+    io.in_batch = b.in_batch;
     io.buf[p.result] = out;
     io.buf[1 - p.result] = tmp;
+    io.buf_batch[p.result] = b.out_batch;
+    io.buf_batch[1 - p.result] = b.tmp_batch;
     return g1fft_launch(ctx, st, p, io);
 }
 

@@ -77,6 +77,7 @@ struct G1fftPlan {
     bool tab_small; int tab_c, tab_W;   // first-tables stage: the narrow set or the SRS's own, window bits, tables
     size_t bytes_a, bytes_b, bytes_c;   // workspaces poly[0].a (prefix products of the affine conversion), .b (two plane sets), .c (partial sums)
     int result;                    // the plane buffer (0 or 1) that holds the result
+    uint32_t batch;                // transforms per launch (grid.y of the plane-to-plane stage kernels); the grids above are those of ONE transform
 };
 
 inline int g1fft_log2(size_t n) { return ilog2_ceil(n); }
@@ -88,7 +89,14 @@ inline int g1fft_log2(size_t n) { return ilog2_ceil(n); }
 //   direct stages of radix 2^K (one lane or pair per (output, term): n 2^K lanes or pairs), K <= 5
 //   radix-2 butterflies (n / 2 lanes or pairs, work bound: one multiplication per two outputs)
 // *kmax = 0: radix-2 butterflies; else the largest radix bits of the direct stages.  (Shared by g1_ifft and g1_fft_planes.)
-inline void g1fft_choose_plan(size_t n, int log_n, int* kmax_out, bool* pairs_out) {
+// batch: that many transforms of n points share every launch (the blobs of a group of kzg_encode_cosets_batch, a grid dimension of the
+// stage kernels): a stage's lanes are the lanes of one transform times the batch, so a radix that fills the chip for one transform
+// overfills it for eight and the choice moves to smaller radices.  batch = 1 is the choice of a single transform, term for term.
+// Measured on batched stages (profiles/encode_batch.md, one kernel trace per batch of 1, 16 and 64 blobs at d = 2^12, r = 8, l = 16): a stage
+// of a batch that stays within one wave per SIMD takes what a single transform's stage takes -- 1.26 - 1.37 ms on lanes, 0.69 - 0.77 ms on
+// pairs -- and a stage beyond it scales with its lanes (k_fk20_lincomb: 1.28 ms at 8 192 lanes, 2.80 ms at 131 072, 10.5 ms at 524 288), so the
+// constants below serve batches as they stand; whole calls land within 6 % of the model's sum of stages.
+inline void g1fft_choose_plan_batch(size_t n, int log_n, size_t batch, int* kmax_out, bool* pairs_out) {
     int kmax = 0;
     bool pairs = false;
     const double t_lane = 1.25, t_pair = 0.83, cap = 65536.0;
@@ -96,23 +104,25 @@ inline void g1fft_choose_plan(size_t n, int log_n, int* kmax_out, bool* pairs_ou
     for (int mode = 0; mode < 2; ++mode) {                        // 0: one lane per point, 1: lane pairs
         const double t1 = mode ? t_pair : t_lane, width = mode ? 2.0 : 1.0;
         for (int K = 2; K <= 5 && K <= std::max(log_n, 2); ++K) {  // direct stages
-            const double lanes = (double)n * (double)(1u << K) * width;
+            const double lanes = (double)n * (double)(1u << K) * width * (double)batch;
             const double cost = (double)((log_n + K - 1) / K) * t1 * std::max(1.0, lanes / cap);
             if (cost < best) { best = cost; kmax = K; pairs = mode != 0; }
         }
-        const double lanes2 = (double)n / 2.0 * width;             // radix-2 butterflies (+ the scaling multiplication of the last stage)
+        const double lanes2 = (double)n / 2.0 * width * (double)batch;             // radix-2 butterflies (+ the scaling multiplication of the last stage)
         const double cost2 = (double)(log_n + 1) * t1 * std::max(1.0, lanes2 / cap);
         if (cost2 < best) { best = cost2; kmax = 0; pairs = mode != 0; }
     }
     *kmax_out = kmax;
     *pairs_out = pairs;
 }
+inline void g1fft_choose_plan(size_t n, int log_n, int* kmax_out, bool* pairs_out) { g1fft_choose_plan_batch(n, log_n, 1, kmax_out, pairs_out); }
 
 inline G1fftPlan g1fft_plan_begin(size_t n) {
     G1fftPlan p{};
     p.n = (uint32_t)n;
     p.log_n = g1fft_log2(n);
     p.sum_grid = (n * 64 + 255) / 256;
+    p.batch = 1;
     return p;
 }
 inline G1fftStage& g1fft_push(G1fftPlan& p, G1fftStageKind kind, size_t lanes, int src, int dst) {
@@ -135,7 +145,7 @@ inline void g1fft_plan_stages(G1fftPlan& p, const G1fftSrsShape* srs, bool copy_
     const G1fftStageKind copy = srs ? G1S_LOAD : G1S_GATHER, copy_bitrev = srs ? G1S_LOAD_BITREV : G1S_GATHER_BITREV;
     int kmax = 0;
     bool pairs = false;
-    g1fft_choose_plan(n, log_n, &kmax, &pairs);
+    g1fft_choose_plan_batch(n, log_n, p.batch, &kmax, &pairs);
     if (log_n == 0) {
         p.form = G1FFT_COPY;
         g1fft_push(p, copy, n, G1BUF_INPUT, 0);
@@ -256,9 +266,11 @@ inline G1fftPlan g1fft_plan_ifft(size_t n, const G1fftSrsShape& srs) {
 }
 
 // g1_fft_planes: out = sum_j w^(+-ij) in[j] (times 1/n if scaled) on the caller's plane buffers; strided: in_stride != n.  No workspace.
-// The caller names buffer `result` out and the other one tmp, so the transform ends in out.
-inline G1fftPlan g1fft_plan_planes(size_t n, bool inverse, bool scaled, bool strided) {
+// The caller names buffer `result` out and the other one tmp, so the transform ends in out.  batch: transforms per launch (plane sets a
+// fixed distance apart, one per grid.y); the stage plan is chosen for batch x the lanes of one transform.
+inline G1fftPlan g1fft_plan_planes(size_t n, bool inverse, bool scaled, bool strided, size_t batch = 1) {
     G1fftPlan p = g1fft_plan_begin(n);
+    p.batch = (uint32_t)batch;
     const int dir = inverse ? 0 : G1SCAL_FORWARD;
     if (p.log_n > 0) {                                            // one point: the transform (and 1/1) is the identity
         p.scal_keys[p.n_scal_keys++] = dir;

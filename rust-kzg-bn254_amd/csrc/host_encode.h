@@ -1,7 +1,8 @@
 // host_encode.h — the host side of kzg_encode_cosets (multiproof.hip, capi_srs.hip): every argument check of the entry, in the order the
 // header documents, and everything the driver decides before its first launch -- the sizes m, m', r, the shape of the FK20 linear
 // combination, the workspace bytes, and the plan of the one transform that sees n: the m-point G1 FFT of an input that is zero beyond
-// its first m' = m / r points.  Pure host code: no HIP type, no kzg_ctx, no allocation; also compiled with g++ by
+// its first m' = m / r points -- and of kzg_encode_cosets_batch: its checks, the groups a call works through, the bytes of a group, and
+// both G1 transform plans chosen for the blobs of a group (EncodeBatchPlan, below).  Pure host code: no HIP type, no kzg_ctx, no allocation; also compiled with g++ by
 // tests/hostcheck/encodecheck.cpp.
 #pragma once
 #include <algorithm>
@@ -10,6 +11,7 @@
 
 #include "../../include/kzg_bn254_mi355x.h"
 #include "g1fft_plan.h"
+#include "ntt_plan.h"
 
 namespace kzg {
 
@@ -40,9 +42,10 @@ struct G1fftPaddedPlan {
     uint32_t nonzero;
     int log_nonzero, log_r;
 };
-inline G1fftPaddedPlan g1fft_plan_planes_padded(size_t n, size_t nonzero) {
+// batch: transforms per launch, as in g1fft_plan_planes.
+inline G1fftPaddedPlan g1fft_plan_planes_padded(size_t n, size_t nonzero, size_t batch = 1) {
     G1fftPaddedPlan pp{};
-    pp.plan = g1fft_plan_planes(n, false, false, true);
+    pp.plan = g1fft_plan_planes(n, false, false, true, batch);
     pp.nonzero = (uint32_t)nonzero;
     pp.log_nonzero = g1fft_log2(nonzero);
     pp.log_r = pp.plan.log_n - pp.log_nonzero;
@@ -103,6 +106,111 @@ inline EncodePlan encode_plan(size_t poly_len, size_t n, size_t chunk_len, bool 
         p.fft = g1fft_plan_planes_padded(p.m, p.mp);
     }
     return p;
+}
+
+// ---- kzg_encode_cosets_batch: `count` blobs of one shape (d, n, l, form) --------------------------------------------------------------
+// A call works through its blobs in GROUPS.  Inside a group every stage of the encoder is one launch for all its blobs: the blob is
+// grid.y of the kernel, and the blobs' buffers stand one after the other in each kzg_ctx::mp[i], a fixed distance apart (blob_bytes[i]
+// apart for the plane sets; the Fr arrays are compact rows, see below).  A group of one blob runs the launches of kzg_encode_cosets
+// itself (multiproof_encode), so the batched entry is never slower than the loop where batching cannot help.
+//
+// The default budget of a group's workspace: 4 GiB.  From the shapes of profiles/encode.md: one blob needs ~3 MiB at (2^12, r = 8,
+// l = 16), ~50 MiB at (2^16, 8, 16), the largest l = 16 row, and ~300 MiB at (2^16, 8, 1), the largest row: 4 GiB holds 64 blobs of
+// every l = 16 row in one group and 13 of the largest, 1.4 % of the device's 288 GB.  kzg_ctx_set_encode_group_bytes overrides it.
+constexpr size_t ENCODE_GROUP_BYTES_DEFAULT = (size_t)4 << 30;
+constexpr size_t ENCODE_GROUP_MAX = 32768;                      // blobs per group: grid.y of a launch (< 65 536)
+constexpr size_t ENCODE_STAGE_LANE_CAP = 65536;                 // one wave per SIMD: g1fft_choose_plan's cap
+
+// kzg_encode_cosets_batch's checks: encode_check with count == 0 in check 1 and, last, a count whose output sizes overflow size_t
+inline int32_t encode_batch_check(bool bad_pointers, bool bad_srs, size_t count, size_t poly_len, size_t n, size_t chunk_len, size_t srs_len) {
+    int32_t rc = encode_check(bad_pointers || count == 0, bad_srs, poly_len, n, chunk_len, srs_len);
+    if (rc != KZG_OK) return rc;
+    // the largest array is max(n x 32 (values), m x 64 (proofs)) <= n x 64 bytes per blob
+    if (count > SIZE_MAX / (n * ENCODE_AFFINE_BYTES)) return KZG_ERR_INVALID_ARG;
+    return KZG_OK;
+}
+
+// the smallest number of lanes of a stage of the plan that multiplies points (direct and radix-2 stages), one transform
+inline size_t g1fft_plan_min_stage_lanes(const G1fftPlan& p) {
+    size_t lanes = SIZE_MAX;
+    for (int i = 0; i < p.n_stages; ++i)
+        if (p.stage[i].K > 0) lanes = std::min(lanes, p.stage[i].grid * 256);
+    return lanes;
+}
+
+struct EncodeBatchPlan {
+    EncodePlan one;                        // the plan of one blob: the shape, and the launches of a group of one
+    size_t count = 0;
+    // THE RULE for when batching cannot help: a stage is pure latency only while it fits one wave per SIMD (ENCODE_STAGE_LANE_CAP lanes);
+    // beyond that it is throughput bound and B blobs in one launch take B times as long as one.  When proofs are asked for and EVERY
+    // scalar-multiplication stage of ONE blob (the linear combination, each stage of the inverse and of the forward G1 FFT) already has
+    // that many lanes, `batched` is false and the call runs as groups of one.  Values alone (Fr NTTs only) always batch.
+    bool batched = false;
+    size_t min_stage_lanes = 0;            // the smallest of those stages of one blob (0: no proofs)
+    size_t group = 1;                      // blobs per group (the last group of a call may be smaller): >= 1 whatever the budget
+    size_t n_groups = 0;
+    size_t budget = 0;                     // the byte budget the group was sized for
+    size_t f_stride = 0;                   // Fr elements between the coefficient rows of consecutive blobs in mp[0]: n with values, else d
+    // bytes of kzg_ctx::mp[0 .. 5] per blob and per group, and of the Fr NTT workspace (mp_ntt.data, .tmp) per group
+    size_t blob_bytes[6] = {0, 0, 0, 0, 0, 0}, bytes[6] = {0, 0, 0, 0, 0, 0};
+    size_t ntt_bytes[2] = {0, 0};
+    size_t group_bytes = 0;                // everything a group reserves
+    size_t set_points[3] = {0, 0, 0};      // points per blob of the three plane sets mp[2 .. 4]
+    G1fftPlan ifft{};                      // steps 3: the inverse transform of 2m' points, chosen for `group` blobs per launch
+    G1fftPaddedPlan fft{};                 // step 5: the zero-padded forward transform of m points, likewise
+};
+
+// Fr NTT workspace of `rows` transforms of 2^log_n points in one launch per pass (ntt_run_batch): ntt_plan's bytes times the rows
+inline void encode_ntt_bytes(int log_n, size_t rows, size_t out[2]) {
+    if (log_n < 1) return;
+    const NttPlan p = ntt_plan(log_n, false, 256, 0);           // the byte counts depend on log n only
+    out[0] = std::max(out[0], p.bytes_data * rows);
+    out[1] = std::max(out[1], p.bytes_tmp * rows);
+}
+
+// The sizes and the two transform plans of a group of g blobs (1 <= g)
+inline void encode_batch_size_group(EncodeBatchPlan& bp, size_t g) {
+    const EncodePlan& p = bp.one;
+    bp.group = g;
+    bp.group_bytes = 0;
+    for (int i = 0; i < 6; ++i) { bp.bytes[i] = bp.blob_bytes[i] * g; bp.group_bytes += bp.bytes[i]; }
+    bp.ntt_bytes[0] = bp.ntt_bytes[1] = 0;
+    if (p.proofs) encode_ntt_bytes(g1fft_log2(p.M), p.l * g, bp.ntt_bytes);      // the l g rows of 2m' points
+    if (p.values) encode_ntt_bytes(p.log_n, g, bp.ntt_bytes);                    // the g value transforms
+    encode_ntt_bytes(p.log_d, g, bp.ntt_bytes);                                  // eval form: the g inverse transforms of d points
+    bp.group_bytes += bp.ntt_bytes[0] + bp.ntt_bytes[1];
+    if (p.proofs) {
+        bp.ifft = g1fft_plan_planes(p.M, true, true, false, g);
+        bp.fft = g1fft_plan_planes_padded(p.m, p.mp, g);
+    }
+}
+
+// The plan of a call whose arguments passed encode_batch_check.  group_bytes = 0: the default budget.
+inline EncodeBatchPlan encode_batch_plan(size_t poly_len, size_t n, size_t chunk_len, size_t count, bool values, bool proofs, size_t group_bytes) {
+    EncodeBatchPlan bp;
+    bp.one = encode_plan(poly_len, n, chunk_len, values, proofs);
+    const EncodePlan& p = bp.one;
+    bp.count = count;
+    bp.budget = group_bytes ? group_bytes : ENCODE_GROUP_BYTES_DEFAULT;
+    bp.f_stride = values ? p.n : p.d;
+    for (int i = 0; i < 6; ++i) bp.blob_bytes[i] = p.bytes[i];
+    if (proofs) {
+        for (int i = 0; i < 3; ++i) bp.set_points[i] = p.bytes[2 + i] / G1FFT_POINT_BYTES;
+        const size_t lincomb = p.l == 1 ? p.M : ((p.M * p.lincomb.W) << p.lincomb.log_g);
+        bp.min_stage_lanes = std::min(lincomb, std::min(g1fft_plan_min_stage_lanes(g1fft_plan_planes(p.M, true, true, false)),
+                                                        g1fft_plan_min_stage_lanes(g1fft_plan_planes_padded(p.m, p.mp).plan)));
+    }
+    bp.batched = !proofs || bp.min_stage_lanes < ENCODE_STAGE_LANE_CAP;
+    size_t g = 1;
+    if (bp.batched && count > 1) {
+        encode_batch_size_group(bp, 1);
+        // the workspace is linear in the blobs of the group (the transform plans own no bytes): the largest g within the budget
+        const size_t per_blob = std::max<size_t>(bp.group_bytes, 1);
+        g = std::min(std::min(count, ENCODE_GROUP_MAX), std::max<size_t>(1, bp.budget / per_blob));
+    }
+    encode_batch_size_group(bp, g);
+    bp.n_groups = (count + g - 1) / g;
+    return bp;
 }
 
 }  // namespace kzg

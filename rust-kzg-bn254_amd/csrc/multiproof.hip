@@ -20,7 +20,7 @@
 //     a shuffle tree, and for l > 64 up to 32 waves per frequency whose partial sums a second kernel adds; a lane adds l / (64 W) terms
 //     one after the other.  l = 1 is a kernel of its own: one scalar multiplication per frequency, no tree.  Lanes rather than pairs:
 //     the stage is one multiplication deep like an FFT stage, and the pair form's gain there (0.83 against 1.25 ms) was not measured here.
-//   * the Fr side: l NTTs of 2m points, one ntt_run each (a single batched launch was not written: at l = 16 they are 16 short launches).
+//   * the Fr side: l NTTs of 2m points as one batched launch per pass (ntt_run_batch: the row is grid.y).
 //   * the cache build transforms the l sequences one after the other (gather, forward FFT, affine conversion each).
 //
 // The encoder (multiproof_encode, kzg_encode_cosets): d coefficients evaluated on n = r d points, deg f < d.  Every quotient has degree
@@ -28,7 +28,14 @@
 // shared with multiproof_run.  Step 5 alone sees n: pi = DFT_m(h_0 .. h_{m'-1}, 0 x (m - m')), m = n / l, by g1_fft_planes_padded (g1fft.hip;
 // plan in host_encode.h: the spread load instead of the first log2 r radix-2 stages, the zeros never read).  The values are one Fr NTT of
 // the zero-extended coefficients, written coset-major (k_encode_gather_cosets).
-// Measured figures: README.md ("multi-proofs", "the encoder"), profiles/multiproof.md and profiles/encode.md.
+//
+// A batch of blobs (multiproof_encode_batch, kzg_encode_cosets_batch): B blobs of one shape, in groups whose workspace fits a byte budget
+// (host_encode.h EncodeBatchPlan).  Every kernel of steps 1-5 and of the values takes the blob as grid.y and a distance between
+// consecutive blobs' buffers; one blob (grid.y = 1, every distance unused) is the single call.  One lane serves one (blob, frequency,
+// term) of the linear combination rather than looping over the blobs with the table point loaded once: the stage is one scalar
+// multiplication deep and pure latency while it is under one wave per SIMD, so more lanes cost nothing there while a loop over B blobs
+// is B multiplications deep; the table point is 64 bytes against a 127-step chain, and the blobs' reads of it hit the cache.
+// Measured figures: README.md ("multi-proofs", "the encoder"), profiles/multiproof.md, profiles/encode.md and profiles/encode_batch.md.
 #include "engine.h"
 #include "glv.h"
 
@@ -53,9 +60,11 @@ k_fk20_gather_srs(const uint4* __restrict__ srs_points, uint32_t m, uint32_t l, 
 
 // coefficient rows: F[b][j] = f[j l + b] for j < m, 0 for m <= j < 2m (wire Fr, 32 B each)
 __global__ void __launch_bounds__(256)
-k_fk20_scatter_coeffs(const uint4* __restrict__ f, uint32_t m, uint32_t l, uint4* __restrict__ F) {
+k_fk20_scatter_coeffs(const uint4* __restrict__ f, uint32_t m, uint32_t l, uint4* __restrict__ F, size_t f_batch /* Fr elements between blobs (grid.y) */) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, M = 2 * m;
     if (i >= M * l) return;
+    f += 2 * blockIdx.y * f_batch;
+    F += 2 * (size_t)blockIdx.y * M * l;
     const uint32_t b = i / M, j = i - b * M;
     uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
     if (j < m) { const size_t s = (size_t)j * l + b; lo = f[2 * s]; hi = f[2 * s + 1]; }
@@ -65,20 +74,25 @@ k_fk20_scatter_coeffs(const uint4* __restrict__ f, uint32_t m, uint32_t l, uint4
 
 // l = 1: H_t = Fhat_t Shat_t, one lane per frequency
 __global__ void __launch_bounds__(256)
-k_fk20_pointwise(const uint4* __restrict__ fhat, const uint4* __restrict__ shat, uint32_t M, int32_t* __restrict__ out) {
+k_fk20_pointwise(const uint4* __restrict__ fhat, const uint4* __restrict__ shat, uint32_t M, int32_t* __restrict__ out, size_t out_batch /* words between blobs (grid.y) */) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= M) return;
+    fhat += 2 * (size_t)blockIdx.y * M;
+    out += blockIdx.y * out_batch;
     Xyzz r;
     glv_term(r, fhat + 2 * (size_t)t, shat + 4 * (size_t)t);
     xyzz_store(out, M, t, r);
 }
 
 // l > 1: slot (t, w) = sum of the terms b = (w tpl + i) G + g (g < G lanes, i < tpl) of frequency t; G = 2^log_g <= 64 consecutive lanes of
-// one wave per slot, folded by a shuffle tree; slot (t, w) at index t W + w of `out` (stride M W): H itself when W = 1
+// one wave per slot, folded by a shuffle tree; slot (t, w) at index t W + w of `out` (stride M W): H itself when W = 1.  Blob grid.y: its l x M
+// rows of fhat follow those of the blob before it, its `out` is out_batch words further; every blob reads the same shat.
 __global__ void __launch_bounds__(256)
-k_fk20_lincomb(const uint4* __restrict__ fhat, const uint4* __restrict__ shat, uint32_t M, int log_g, uint32_t W, uint32_t tpl, int32_t* __restrict__ out) {
+k_fk20_lincomb(const uint4* __restrict__ fhat, const uint4* __restrict__ shat, uint32_t M, int log_g, uint32_t W, uint32_t tpl, int32_t* __restrict__ out, size_t out_batch) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
     const uint32_t G = 1u << log_g, g = t & (G - 1), slot = t >> log_g;
+    fhat += 2 * (size_t)blockIdx.y * (((size_t)W * tpl) << log_g) * M;
+    out += blockIdx.y * out_batch;
     const uint32_t o = slot / W, w = slot - o * W;
     const bool active = o < M;                                    // no early return: every lane takes part in the tree
     Xyzz acc;
@@ -113,9 +127,11 @@ k_fk20_lincomb(const uint4* __restrict__ fhat, const uint4* __restrict__ shat, u
 
 // H_t = sum of the W partial sums of frequency t (one lane per frequency)
 __global__ void __launch_bounds__(256)
-k_fk20_sum_partials(const int32_t* __restrict__ partial, uint32_t M, uint32_t W, int32_t* __restrict__ out) {
+k_fk20_sum_partials(const int32_t* __restrict__ partial, uint32_t M, uint32_t W, int32_t* __restrict__ out, size_t partial_batch, size_t out_batch) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= M) return;
+    partial += blockIdx.y * partial_batch;
+    out += blockIdx.y * out_batch;
     Xyzz acc;
     xyzz_load(acc, partial, (size_t)M * W, (size_t)t * W);
 #pragma unroll 1
@@ -130,9 +146,11 @@ k_fk20_sum_partials(const int32_t* __restrict__ partial, uint32_t M, uint32_t W,
 
 // out_inf[i] = 1 where the point is the identity
 __global__ void __launch_bounds__(256)
-k_fk20_inf_flags(const int32_t* __restrict__ planes, uint32_t n, uint8_t* __restrict__ out_inf) {
+k_fk20_inf_flags(const int32_t* __restrict__ planes, uint32_t n, uint8_t* __restrict__ out_inf, size_t planes_batch) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    planes += blockIdx.y * planes_batch;
+    out_inf += (size_t)blockIdx.y * n;
     Xyzz v;
     xyzz_load(v, planes, n, i);
     out_inf[i] = v.inf ? 1 : 0;
@@ -183,49 +201,56 @@ void multiproof_drop(kzg_srs* srs) {
 
 // ---- the proofs -------------------------------------------------------------------------------------------------------------------
 // Steps 1-4 for d coefficients on the device (f), shared by multiproof_run (d = n) and multiproof_encode (d <= n): the l rows F^(b)
-// and their NTTs, H = sum_b Fhat^(b) o Shat^(b), the inverse transform of H.  m = d / l, M = 2m; F: l x M wire values; P0 (M W points),
-// P1, P2 (M points each or more): plane sets.  *X_out = the planes that hold IFFT_2m(H) (stride M: h is its slice [m - 1, 2m - 1)),
-// *Y_out = the plane set that is free again (P2 stays scratch).  Enqueued on st.
+// and their NTTs, H = sum_b Fhat^(b) o Shat^(b), the inverse transform of H.  m = d / l, M = 2m; F: l x M wire values; sets.P[0] (M W points),
+// P[1], P[2] (M points each or more): plane sets.  *x = the set that holds IFFT_2m(H) (stride M: h is its slice [m - 1, 2m - 1)),
+// *y = the plane set that is free again (P[2] stays scratch).  Enqueued on st.
+// B blobs (grid.y of every launch): blob b's coefficients at f + b f_batch elements, its rows at F + b l M, its plane sets at
+// P[i] + b P_batch[i] words; the l B rows are one batched NTT, the inverse transform's plan is chosen for B (g1fft_plan.h).
+struct Fk20Sets { int32_t* P[3]; size_t P_batch[3]; };
 static int32_t fk20_h(kzg_ctx* ctx, hipStream_t st, const uint4* shat, const uint4* f, uint4* F, size_t d, size_t l, const Fk20Shape& sh,
-                      int32_t* P0, int32_t* P1, int32_t* P2, int32_t** X_out, int32_t** Y_out) {
+                      const Fk20Sets& sets, int* x, int* y, size_t B = 1, size_t f_batch = 0) {
     const size_t m = d / l, M = 2 * m;
     const int log_g = sh.log_g;
     const uint32_t W = sh.W, tpl = sh.tpl;
-    int32_t rc = KZG_OK;
-    hipLaunchKernelGGL(k_fk20_scatter_coeffs, dim3(grid_of(M * l)), dim3(256), 0, st, f, (uint32_t)m, (uint32_t)l, F);
-    for (size_t b = 0; b < l; ++b) {
-        rc = ntt_run(ctx, F + 2 * b * M, M, false, st, &ctx->mp_ntt);
-        if (rc != KZG_OK) return rc;
-    }
+    const unsigned by = (unsigned)B;
+    int32_t* const* P = sets.P;
+    const size_t* Pb = sets.P_batch;
+    hipLaunchKernelGGL(k_fk20_scatter_coeffs, dim3(grid_of(M * l), by), dim3(256), 0, st, f, (uint32_t)m, (uint32_t)l, F, f_batch);
+    int32_t rc = ntt_run_batch(ctx, F, M, l * B, false, st, &ctx->mp_ntt);
+    if (rc != KZG_OK) return rc;
     // 2. H = sum_b Fhat^(b) o Shat^(b)
-    int32_t* H = W > 1 ? P1 : P0;
+    const int h = W > 1 ? 1 : 0;
     if (l == 1) {
-        hipLaunchKernelGGL(k_fk20_pointwise, dim3(grid_of(M)), dim3(256), 0, st, F, shat, (uint32_t)M, H);
+        hipLaunchKernelGGL(k_fk20_pointwise, dim3(grid_of(M), by), dim3(256), 0, st, F, shat, (uint32_t)M, P[h], Pb[h]);
     } else {
-        hipLaunchKernelGGL(k_fk20_lincomb, dim3(grid_of((M * W) << log_g)), dim3(256), 0, st, F, shat, (uint32_t)M, log_g, W, tpl, P0);
-        if (W > 1) hipLaunchKernelGGL(k_fk20_sum_partials, dim3(grid_of(M)), dim3(256), 0, st, P0, (uint32_t)M, W, H);
+        hipLaunchKernelGGL(k_fk20_lincomb, dim3(grid_of((M * W) << log_g), by), dim3(256), 0, st, F, shat, (uint32_t)M, log_g, W, tpl, P[0], Pb[0]);
+        if (W > 1) hipLaunchKernelGGL(k_fk20_sum_partials, dim3(grid_of(M), by), dim3(256), 0, st, P[0], (uint32_t)M, W, P[h], Pb[0], Pb[h]);
     }
     KZG_HIP_TRY(ctx, hipGetLastError());
     // 3. h = IFFT_2m(H)[m - 1, 2m - 1): left in place for the next transform to read (offset m - 1, stride 2m)
-    int32_t* X = W > 1 ? P0 : P1;                                               // the plane set H is not in
-    rc = g1_fft_planes(ctx, st, H, M, M, X, P2, true, true);
+    const int xi = 1 - h;                                                        // the plane set H is not in
+    G1fftBatch gb;
+    gb.batch = B; gb.in_batch = Pb[h]; gb.out_batch = Pb[xi]; gb.tmp_batch = Pb[2];
+    rc = g1_fft_planes(ctx, st, P[h], M, M, P[xi], P[2], true, true, gb);
     if (rc != KZG_OK) return rc;
-    *X_out = X;
-    *Y_out = H;                                                                  // free again
+    *x = xi;
+    *y = h;                                                                      // free again
     return KZG_OK;
 }
 
-// 5. m points of planes Y -> wire affine points (identity = zeros) and identity flags in `work` (m x 64 B | m x NL words | m flags), copied out
-static int32_t fk20_emit(kzg_ctx* ctx, hipStream_t st, const int32_t* Y, size_t m, uint8_t* work, uint64_t* out_xy, uint8_t* out_inf) {
-    uint4* d_aff = reinterpret_cast<uint4*>(work);                               // m x 64 B
-    int32_t* aff_scratch = reinterpret_cast<int32_t*>(work + m * 64);            // m x NL words
-    uint8_t* d_inf = work + m * (64 + NL * 4);
-    int32_t rc = g1fft_planes_to_affine(ctx, st, Y, m, d_aff, true, aff_scratch);
+// 5. m points of planes Y -> wire affine points (identity = zeros) and identity flags in `work` (m x 64 B | m x NL words | m flags), copied out.
+// B blobs (plane sets Y_batch words apart): B m points, `work` laid out for B m, one download per output array.
+static int32_t fk20_emit(kzg_ctx* ctx, hipStream_t st, const int32_t* Y, size_t m, uint8_t* work, uint64_t* out_xy, uint8_t* out_inf, size_t B = 1, size_t Y_batch = 0) {
+    const size_t pts = B * m;
+    uint4* d_aff = reinterpret_cast<uint4*>(work);                               // pts x 64 B
+    int32_t* aff_scratch = reinterpret_cast<int32_t*>(work + pts * 64);          // pts x NL words
+    uint8_t* d_inf = work + pts * (64 + NL * 4);
+    int32_t rc = g1fft_planes_to_affine(ctx, st, Y, m, d_aff, true, aff_scratch, B, Y_batch);
     if (rc != KZG_OK) return rc;
-    hipLaunchKernelGGL(k_fk20_inf_flags, dim3(grid_of(m)), dim3(256), 0, st, Y, (uint32_t)m, d_inf);
+    hipLaunchKernelGGL(k_fk20_inf_flags, dim3(grid_of(m), (unsigned)B), dim3(256), 0, st, Y, (uint32_t)m, d_inf, Y_batch);
     KZG_HIP_TRY(ctx, hipGetLastError());
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(out_xy, d_aff, m * 64, hipMemcpyDeviceToHost, st));
-    if (out_inf) KZG_HIP_TRY(ctx, hipMemcpyAsync(out_inf, d_inf, m, hipMemcpyDeviceToHost, st));
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(out_xy, d_aff, pts * 64, hipMemcpyDeviceToHost, st));
+    if (out_inf) KZG_HIP_TRY(ctx, hipMemcpyAsync(out_inf, d_inf, pts, hipMemcpyDeviceToHost, st));
     return KZG_OK;
 }
 
@@ -245,15 +270,16 @@ int32_t multiproof_run(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, si
     KZG_HIP_TRY(ctx, ctx->mp[4].reserve(M * 36 * 4));
     KZG_HIP_TRY(ctx, ctx->mp[5].reserve(m * (64 + 1 + NL * 4)));
     uint4* f = ctx->mp[0].as<uint4>();
-    int32_t* P2 = ctx->mp[4].as<int32_t>();
+    const Fk20Sets sets = {{ctx->mp[2].as<int32_t>(), ctx->mp[3].as<int32_t>(), ctx->mp[4].as<int32_t>()}, {0, 0, 0}};
     // 1. coefficients (eval form: inverse NTT on the device), then steps 1-4
     KZG_HIP_TRY(ctx, hipMemcpyAsync(f, poly_mont, n * 32, hipMemcpyHostToDevice, st));
     if (eval_form) { rc = ntt_run(ctx, f, n, true, st, &ctx->mp_ntt); if (rc != KZG_OK) return rc; }
-    int32_t *X = nullptr, *Y = nullptr;
-    rc = fk20_h(ctx, st, shat, f, ctx->mp[1].as<uint4>(), n, l, sh, ctx->mp[2].as<int32_t>(), ctx->mp[3].as<int32_t>(), P2, &X, &Y);
+    int xi = 0, yi = 0;
+    rc = fk20_h(ctx, st, shat, f, ctx->mp[1].as<uint4>(), n, l, sh, sets, &xi, &yi);
     if (rc != KZG_OK) return rc;
+    int32_t *X = sets.P[xi], *Y = sets.P[yi];
     // 4. pi = DFT_m(h): the slice is read in place (offset m - 1, stride 2m); Y: stride m
-    rc = g1_fft_planes(ctx, st, X + (m - 1), M, m, Y, P2, false, false);
+    rc = g1_fft_planes(ctx, st, X + (m - 1), M, m, Y, sets.P[2], false, false);
     if (rc != KZG_OK) return rc;
     // 5. one batched affine conversion (wire form, identity = zeros) and the identity flags
     rc = fk20_emit(ctx, st, Y, m, ctx->mp[5].as<uint8_t>(), out_xy, out_inf);
@@ -268,6 +294,8 @@ __global__ void __launch_bounds__(256)
 k_encode_gather_cosets(const uint4* __restrict__ evals, uint32_t n, int log_l, int log_m, uint4* __restrict__ ys) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    evals += 2 * (size_t)blockIdx.y * n;                           // blob grid.y: rows of n elements on both sides
+    ys += 2 * (size_t)blockIdx.y * n;
     const uint32_t k = i >> log_l, j = i & ((1u << log_l) - 1);
     const size_t s = (size_t)k + ((size_t)j << log_m);
     ys[2 * (size_t)i] = evals[2 * s];
@@ -293,10 +321,12 @@ int32_t multiproof_encode(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont,
     KZG_HIP_TRY(ctx, hipMemcpyAsync(f, poly_mont, d * 32, hipMemcpyHostToDevice, st));
     if (eval_form) { rc = ntt_run(ctx, f, d, true, st, &ctx->mp_ntt); if (rc != KZG_OK) return rc; }
     if (plan.proofs) {
-        int32_t* P2 = ctx->mp[4].as<int32_t>();
-        int32_t *X = nullptr, *Y = nullptr;
-        rc = fk20_h(ctx, st, shat, f, F, d, l, plan.lincomb, ctx->mp[2].as<int32_t>(), ctx->mp[3].as<int32_t>(), P2, &X, &Y);
+        const Fk20Sets sets = {{ctx->mp[2].as<int32_t>(), ctx->mp[3].as<int32_t>(), ctx->mp[4].as<int32_t>()}, {0, 0, 0}};
+        int32_t* P2 = sets.P[2];
+        int xi = 0, yi = 0;
+        rc = fk20_h(ctx, st, shat, f, F, d, l, plan.lincomb, sets, &xi, &yi);
         if (rc != KZG_OK) return rc;
+        int32_t *X = sets.P[xi], *Y = sets.P[yi];
         // pi = DFT_m(h_0 .. h_{m'-1}, 0 x (m - m')): the slice is read in place (offset m' - 1, stride 2m'), the zeros are never read
         rc = g1_fft_planes_padded(ctx, st, X + (mp - 1), M, mp, m, Y, P2);
         if (rc != KZG_OK) return rc;
@@ -313,6 +343,78 @@ int32_t multiproof_encode(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont,
         KZG_HIP_TRY(ctx, hipMemcpyAsync(out_ys, F, n * 32, hipMemcpyDeviceToHost, st));
     }
     KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    return KZG_OK;
+}
+
+// ---- the encoder on a batch of blobs ----------------------------------------------------------------------------------------------------
+// f[b fs + i] = src[b d + i] for i < d, zero for d <= i < fs: the compact rows of a group (uploaded, or inverse-NTT'd in place) into the
+// rows the value transform extends (blob grid.y)
+__global__ void __launch_bounds__(256)
+k_encode_place_coeffs(const uint4* __restrict__ src, uint32_t d, uint32_t fs, uint4* __restrict__ f) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= fs) return;
+    uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+    if (i < d) { const size_t s = (size_t)blockIdx.y * d + i; lo = src[2 * s]; hi = src[2 * s + 1]; }
+    const size_t o = (size_t)blockIdx.y * fs + i;
+    f[2 * o] = lo;
+    f[2 * o + 1] = hi;
+}
+
+// called under ctx->mu with the arguments checked and planned (capi_srs.hip kzg_encode_cosets_batch).  Groups of bp.group blobs, one
+// after the other on the context's stream with a synchronisation behind each (the workspace is reused; overlapping a group's copies
+// with the next one's kernels was not written).  A group of one is multiproof_encode itself.  Inside a group of g blobs the buffers
+// are: mp[0] g rows of f_stride coefficients; mp[1] the compact upload (when f_stride > d), then g x l rows of 2m' (FK20), then g rows
+// of n coset-major values; mp[2 .. 4] g plane sets each, set_points[i] points apart; mp[5] g m affine points | scratch | flags.
+int32_t multiproof_encode_batch(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* polys_mont, bool eval_form, const EncodeBatchPlan& bp, uint64_t* out_ys, uint64_t* out_xy, uint8_t* out_inf) {
+    const EncodePlan& plan = bp.one;
+    const size_t d = plan.d, n = plan.n, l = plan.l, m = plan.m, mp = plan.mp, M = plan.M, fs = bp.f_stride;
+    if (bp.group == 1) {
+        for (size_t b = 0; b < bp.count; ++b) {
+            int32_t rc = multiproof_encode(ctx, srs, polys_mont + b * d * 4, eval_form, plan, out_ys ? out_ys + b * n * 4 : nullptr,
+                                           out_xy ? out_xy + b * m * 8 : nullptr, out_xy ? out_inf + b * m : nullptr);
+            if (rc != KZG_OK) return rc;
+        }
+        return KZG_OK;
+    }
+    RoctxRange range("kzg:encode_cosets_batch");
+    const uint4* shat = nullptr;
+    int32_t rc = KZG_OK;
+    if (plan.proofs) { rc = multiproof_cache(ctx, srs, d, l, &shat); if (rc != KZG_OK) return rc; }
+    hipStream_t st = ctx->stream;
+    for (int i = 0; i < 6; ++i) KZG_HIP_TRY(ctx, ctx->mp[i].reserve(bp.bytes[i]));
+    uint4* f = ctx->mp[0].as<uint4>();
+    uint4* F = ctx->mp[1].as<uint4>();
+    Fk20Sets sets;
+    for (int i = 0; i < 3; ++i) { sets.P[i] = ctx->mp[2 + i].as<int32_t>(); sets.P_batch[i] = bp.set_points[i] * 4 * NL; }
+    for (size_t b0 = 0; b0 < bp.count; b0 += bp.group) {
+        const size_t g = std::min(bp.group, bp.count - b0);           // (the last group may be smaller: its transforms are planned for g)
+        const unsigned gy = (unsigned)g;
+        const uint64_t* src = polys_mont + b0 * d * 4;
+        // the coefficients of the group: one upload; eval form: g inverse NTTs of d points, one launch per pass
+        uint4* up = fs == d ? f : F;
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(up, src, g * d * 32, hipMemcpyHostToDevice, st));
+        if (eval_form) { rc = ntt_run_batch(ctx, up, d, g, true, st, &ctx->mp_ntt); if (rc != KZG_OK) return rc; }
+        if (fs != d) hipLaunchKernelGGL(k_encode_place_coeffs, dim3(grid_of(fs), gy), dim3(256), 0, st, up, (uint32_t)d, (uint32_t)fs, f);
+        if (plan.proofs) {
+            int xi = 0, yi = 0;
+            rc = fk20_h(ctx, st, shat, f, F, d, l, plan.lincomb, sets, &xi, &yi, g, fs);
+            if (rc != KZG_OK) return rc;
+            G1fftBatch gb;
+            gb.batch = g; gb.in_batch = sets.P_batch[xi]; gb.out_batch = sets.P_batch[yi]; gb.tmp_batch = sets.P_batch[2];
+            rc = g1_fft_planes_padded(ctx, st, sets.P[xi] + (mp - 1), M, mp, m, sets.P[yi], sets.P[2], gb);
+            if (rc != KZG_OK) return rc;
+            rc = fk20_emit(ctx, st, sets.P[yi], m, ctx->mp[5].as<uint8_t>(), out_xy + b0 * m * 8, out_inf + b0 * m, g, sets.P_batch[yi]);
+            if (rc != KZG_OK) return rc;
+        }
+        if (plan.values) {
+            rc = ntt_run_batch(ctx, f, n, g, false, st, &ctx->mp_ntt);      // rows of n: the coefficients zero-extended (placed above, or n = d)
+            if (rc != KZG_OK) return rc;
+            hipLaunchKernelGGL(k_encode_gather_cosets, dim3(grid_of(n), gy), dim3(256), 0, st, f, (uint32_t)n, plan.log_l, plan.log_m, F);
+            KZG_HIP_TRY(ctx, hipGetLastError());
+            KZG_HIP_TRY(ctx, hipMemcpyAsync(out_ys + b0 * n * 4, F, g * n * 32, hipMemcpyDeviceToHost, st));
+        }
+        KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
     return KZG_OK;
 }
 

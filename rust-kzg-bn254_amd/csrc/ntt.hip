@@ -130,6 +130,9 @@ k_ntt_pass(const uint4* __restrict__ in_words, uint4* __restrict__ out_words, Nt
     const uint32_t n_units = N >> K;
     const uint32_t tid = threadIdx.x;
     const bool last = a.next_K == 0;
+    // a batch of transforms (ntt_run_batch): row blockIdx.y of N consecutive elements in every buffer; the tables are shared
+    in_words += (size_t)blockIdx.y << (log_n + 1);
+    out_words += (size_t)blockIdx.y << (log_n + 1);
 
     // per-workgroup local twiddles w_R^t = w_N^(t * N/R), t < R/2 (the same for every tile of the pass)
     for (uint32_t t = tid; t < (R >> 1); t += NTT_THREADS) {
@@ -421,9 +424,9 @@ void ntt_release_device_caches(int dev) {
 }
 
 // one pass of the plan: THE launch of k_ntt_pass, the switch over its instantiations
-static void ntt_launch_pass(const NttPlan& plan, int pi, const uint4* src, uint4* dst, const NttTables& tb, int lo_bits, const uint4* next_tw, hipStream_t st) {
+static void ntt_launch_pass(const NttPlan& plan, int pi, const uint4* src, uint4* dst, const NttTables& tb, int lo_bits, const uint4* next_tw, hipStream_t st, unsigned rows) {
     const NttPass& s = plan.pass[pi];
-#define NTT_LAUNCH(...) hipLaunchKernelGGL((k_ntt_pass<__VA_ARGS__>), dim3(s.grid), dim3(plan.threads), 0, st, src, dst, s.args, tb.lo, tb.lo_len, lo_bits, tb.hi, tb.hi_len, next_tw)
+#define NTT_LAUNCH(...) hipLaunchKernelGGL((k_ntt_pass<__VA_ARGS__>), dim3(s.grid, rows), dim3(plan.threads), 0, st, src, dst, s.args, tb.lo, tb.lo_len, lo_bits, tb.hi, tb.hi_len, next_tw)
     switch (plan.kernel) {
     case NTT_K_SLIM7: NTT_LAUNCH(NTT_TILE_LOG_SMALL, 7); break;
     case NTT_K_SLIM8: NTT_LAUNCH(NTT_TILE_LOG_SMALL, 8); break;
@@ -436,13 +439,15 @@ static void ntt_launch_pass(const NttPlan& plan, int pi, const uint4* src, uint4
 static_assert(NttTile<NTT_TILE_LOG_SMALL>::THREADS == (1 << NTT_TILE_LOG_SMALL) / NTT_EPT && NttTile<NTT_TILE_LOG_BIG>::THREADS == (1 << NTT_TILE_LOG_BIG) / NTT_EPT,
               "NttPlan::threads is the workgroup size k_ntt_pass is bounded to");
 
-// the driver: plan (ntt_plan.h), tables, the reserves from the plan, then its passes
-int32_t ntt_run(kzg_ctx* ctx, void* d_data, size_t n, bool inverse, hipStream_t st, NttWorkspace* ws) {
+// the driver: plan (ntt_plan.h), tables, the reserves from the plan, then its passes.  `rows` transforms of n points, row r at d_data + r n
+// elements, as ONE launch per pass (grid.y = the row; 65 535 rows per launch sequence, more in further sequences): the plan is that of one
+// transform, its workspaces hold `rows` rows.  ntt_run is rows = 1.
+int32_t ntt_run_batch(kzg_ctx* ctx, void* d_data, size_t n, size_t rows, bool inverse, hipStream_t st, NttWorkspace* ws) {
     if (!st) st = ctx->stream;
     if (!ws) ws = &ctx->ntt;
     if (n == 0 || (n & (n - 1)) != 0) return KZG_ERR_NOT_POWER_OF_TWO;
     if (n > ((size_t)1 << NTT_MAX_LOG)) return KZG_ERR_DOMAIN;
-    if (n == 1) return KZG_OK;
+    if (n == 1 || rows == 0) return KZG_OK;
     RoctxRange range(inverse ? "kzg:fr_intt" : "kzg:fr_ntt");
     const int log_n = ilog2_ceil(n);
     NttTables tb;
@@ -452,22 +457,28 @@ int32_t ntt_run(kzg_ctx* ctx, void* d_data, size_t n, bool inverse, hipStream_t 
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
     NttPlan plan = ntt_plan(log_n, inverse, cus, opts().ntt_tile_log);
-    if (plan.bytes_data) KZG_HIP_TRY(ctx, ws->data.reserve(plan.bytes_data));
-    if (plan.bytes_tmp) KZG_HIP_TRY(ctx, ws->tmp.reserve(plan.bytes_tmp));
-    uint4* const bufs[3] = {reinterpret_cast<uint4*>(d_data), ws->data.as<uint4>(), ws->tmp.as<uint4>()};      // by NttBuf
-    for (int pi = 0; pi < plan.n_passes; ++pi) {
-        const NttPass& s = plan.pass[pi];
-        const uint4* next_tw = nullptr;
-        if (s.tw) {
-            rc = ntt_get_pass_twiddles(ctx, log_n, inverse, s.args.next_K, s.args.next_log_s, tb, lo_bits, &next_tw, s.tw_scaled);
-            if (rc != KZG_OK) return rc;
-            if (s.tw_scaled && !next_tw) ntt_plan_fold_missing(plan);
+    constexpr size_t ROWS_MAX = 65535;                                       // grid.y of one launch
+    const size_t span = std::min(rows, ROWS_MAX);
+    if (plan.bytes_data) KZG_HIP_TRY(ctx, ws->data.reserve(plan.bytes_data * span));
+    if (plan.bytes_tmp) KZG_HIP_TRY(ctx, ws->tmp.reserve(plan.bytes_tmp * span));
+    for (size_t r0 = 0; r0 < rows; r0 += ROWS_MAX) {
+        uint4* const bufs[3] = {reinterpret_cast<uint4*>(d_data) + 2 * n * r0, ws->data.as<uint4>(), ws->tmp.as<uint4>()};      // by NttBuf
+        for (int pi = 0; pi < plan.n_passes; ++pi) {
+            const NttPass& s = plan.pass[pi];
+            const uint4* next_tw = nullptr;
+            if (s.tw) {
+                rc = ntt_get_pass_twiddles(ctx, log_n, inverse, s.args.next_K, s.args.next_log_s, tb, lo_bits, &next_tw, s.tw_scaled);
+                if (rc != KZG_OK) return rc;
+                if (s.tw_scaled && !next_tw) ntt_plan_fold_missing(plan);
+            }
+            ntt_launch_pass(plan, pi, bufs[s.src], bufs[s.dst], tb, lo_bits, next_tw, st, (unsigned)std::min(rows - r0, ROWS_MAX));
         }
-        ntt_launch_pass(plan, pi, bufs[s.src], bufs[s.dst], tb, lo_bits, next_tw, st);
     }
     KZG_HIP_TRY(ctx, hipGetLastError());
     return KZG_OK;
 }
+
+int32_t ntt_run(kzg_ctx* ctx, void* d_data, size_t n, bool inverse, hipStream_t st, NttWorkspace* ws) { return ntt_run_batch(ctx, d_data, n, 1, inverse, st, ws); }
 
 }  // namespace kzg
 

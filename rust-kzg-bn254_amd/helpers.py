@@ -359,6 +359,25 @@ def check_g2_subgroup(points, ctx=None) -> None:
         raise ValueError(_lib.status_message(rc))
 
 
+def encode_batch_info(d: int, n: int, chunk_len: int, count: int, values: bool = True, proofs: bool = True, group_bytes: int = 0) -> dict:
+    """What `KZG.encode_cosets_batch` does with `count` blobs of shape (d, n, chunk_len) under a workspace budget of `group_bytes` (0: the
+    default) -- `kzg_encode_cosets_batch_info`, a pure query: blobs per group, groups, workspace bytes of a group, whether the shape
+    batches at all, and for the inverse and the forward G1 transform the form ("direct" / "radix2" / "copy"), lanes or pairs, the stages
+    that multiply points and the load in front of them ("in place", "copy", "bitrev", "pad", "spread")."""
+    info = _lib.EncodeBatchInfo()
+    rc = _lib.load().kzg_encode_cosets_batch_info(d, n, chunk_len, count, 1 if values else 0, 1 if proofs else 0, group_bytes, C.byref(info))
+    if rc == _lib.ERR_NOT_POWER_OF_TWO:
+        raise GenericError("length provided is not a power of 2")
+    if rc != _lib.OK:
+        raise GenericError(_lib.status_message(rc))
+
+    def transform(t):
+        return {"form": _lib.ENCODE_FORMS[t.form], "pairs": bool(t.pairs), "stages": int(t.stages), "load": _lib.ENCODE_LOADS[t.load]}
+
+    return {"blobs_per_group": int(info.blobs_per_group), "groups": int(info.groups), "group_bytes": int(info.group_bytes),
+            "batched": bool(info.batched), "inverse": transform(info.inverse), "forward": transform(info.forward)}
+
+
 def compute_powers(base, count: int) -> np.ndarray:
     """helpers.rs:298-315: [base^0 .. base^(count-1)]."""
     b = fr_to_int(base)

@@ -451,6 +451,74 @@ class KZG:
             raise GenericError(_lib.status_message(rc))
         return ys, out
 
+    def encode_cosets_batch(self, polynomials, srs, n: int, chunk_len: int = 1, values: bool = True, proofs: bool = True, eval_form=None):
+        """`encode_cosets` for B blobs of one shape in one call (`kzg_encode_cosets_batch`): `polynomials` is a list of
+        PolynomialCoeffForm or of PolynomialEvalForm of one length d, or one (B, d, 4) array of wire elements with `eval_form=` True /
+        False.  Returns (ys, proofs): ys (B, m, chunk_len, 4), proofs (B, m, 8), row b bit-identical to `encode_cosets` of blob b;
+        `values=False` / `proofs=False` leaves that one out (None).  The library works through the blobs in groups whose device
+        workspace fits `Context.set_encode_group_bytes` (`helpers.encode_batch_info` tells how a shape is grouped and planned)."""
+        if isinstance(polynomials, np.ndarray):
+            if eval_form is None:
+                raise TypeError("encode_cosets_batch of an array needs eval_form=True or False")
+            data = _lib.as_u64(polynomials, 4)
+            if polynomials.ndim != 3 or polynomials.shape[2] != 4:
+                raise GenericError("encode_cosets_batch takes a (B, d, 4) array")
+            count, d = int(polynomials.shape[0]), int(polynomials.shape[1])
+            ef = 1 if eval_form else 0
+        else:
+            polys = list(polynomials)
+            if polys and all(isinstance(q, PolynomialEvalForm) for q in polys):
+                ef, rows = 1, [q.evaluations() for q in polys]
+            elif polys and all(isinstance(q, PolynomialCoeffForm) for q in polys):
+                ef, rows = 0, [q.coeffs() for q in polys]
+            elif not polys:
+                raise GenericError("encode_cosets_batch needs at least one polynomial")
+            else:
+                raise TypeError("encode_cosets_batch takes polynomials of one form: PolynomialEvalForm or PolynomialCoeffForm")
+            if eval_form is not None and bool(eval_form) != bool(ef):
+                raise TypeError("eval_form= contradicts the polynomials' form")
+            count, d = len(polys), len(polys[0])
+            if any(len(q) != d for q in polys):
+                raise GenericError("encode_cosets_batch needs polynomials of one length")
+            data = np.ascontiguousarray(np.stack([_lib.as_u64(r, 4) for r in rows]), dtype=np.uint64) if d else np.zeros((count, 0, 4), dtype=np.uint64)
+        n = int(n)
+        chunk_len = int(chunk_len)
+        if count <= 0:
+            raise GenericError("encode_cosets_batch needs at least one polynomial")
+        if not values and not proofs:
+            raise GenericError("encode_cosets needs values, proofs or both")
+        if d <= 0 or (d & (d - 1)) != 0 or n <= 0 or (n & (n - 1)) != 0:
+            raise FFTError("length provided is not a power of 2")
+        if n > 1 << 24:
+            raise FFTError("Could not perform IFFT due to domain consturction error")
+        if d < 2:
+            raise GenericError("encode_cosets needs a polynomial of at least 2 elements")
+        if d > n:
+            raise GenericError("the domain is shorter than the polynomial")
+        if chunk_len <= 0 or (chunk_len & (chunk_len - 1)) != 0:
+            raise GenericError("chunk length is not a power of 2")
+        if chunk_len > d // 2:
+            raise GenericError("chunk length exceeds half the polynomial length")
+        if d > len(srs):
+            raise SrsCapacityExceeded(d, len(srs))
+        ctx = self._ctx()
+        m = n // chunk_len
+        ys = np.zeros((count, m, chunk_len, 4), dtype=np.uint64) if values else None
+        out = np.zeros((count, m, 8), dtype=np.uint64) if proofs else None
+        inf = np.zeros(count * m, dtype=np.uint8)
+        rc = _lib.load().kzg_encode_cosets_batch(ctx.handle, srs.handle, _lib.ptr(data), count, d, ef, n, chunk_len,
+                                                 _lib.ptr(ys) if values else None, _lib.ptr(out) if proofs else None, inf.ctypes.data_as(_lib.u8p))
+        if rc == _lib.ERR_NOT_POWER_OF_TWO:
+            raise FFTError("length provided is not a power of 2")
+        if rc == _lib.ERR_DOMAIN:
+            raise FFTError("Could not perform IFFT due to domain consturction error")
+        if rc == _lib.ERR_SRS_CAPACITY_EXCEEDED:
+            raise SrsCapacityExceeded(d, len(srs))
+        ctx.check_device(rc)
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+        return ys, out
+
     def encode_cosets_be(self, polynomial, srs, n: int, chunk_len: int = 1):
         """`encode_cosets` in the serialized form a disperser sends (`verifier.encode_coset_items`): (ys_be, proofs_be) bytes, 32 per value
         (big-endian) and per proof (gnark-compressed), what `verifier.verify_multiproof_batch_bytes` takes."""
