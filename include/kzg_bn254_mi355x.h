@@ -826,7 +826,52 @@ int32_t kzg_commit_with_length_proof(kzg_ctx* ctx, const kzg_srs* g1_srs, const 
                                      uint64_t trailing_first_power, uint64_t srs_order, const uint64_t* coeffs_mont, size_t n,
                                      uint64_t claimed_len, uint64_t out_commitment_xy[8], uint64_t out_length_commitment[16],
                                      uint64_t out_length_proof[16]);
-/* The two pairing checks above, g1_tau_shift_xy = [tau^(N-d)]_1.  Host only: two calls of the pairing check, no random weight.  A
+/* ---- many blobs in one call: the batched G2 MSM over SHARED bases ---------------------------------------------------------------------
+ * A disperser publishes one header per blob, and every blob of a call uses the same two base windows (g2_srs[0 .. n) and
+ * g2_trailing[off .. off + n)).  `count` blobs are therefore ONE bucket problem per GROUP of blobs: one digit pass, one sort and one
+ * launch sequence (the sort's launches and six more, whatever the number of blobs and base sets) carry every blob of the group, so the
+ * fixed cost of a short G2 MSM is paid once per group (csrc/g2msm.hip, planned in csrc/g2msm_plan.h).  All outputs are affine wire
+ * points: row b is bit for bit what the single call returns for blob b.  count = 0 -> KZG_OK, nothing written; n = 0 -> identities
+ * (zeros, flags 1).  count has no cap below 2^20: a call works through its groups.  Synchronous, slot 0, as every G2 call. */
+/* count scalar sets of n scalars each, set b at scalars + b n 4, all against srs[offset .. offset + n).  Errors, in order: 1. a null
+ * ctx, srs or out, null scalars with n and count non-zero, a handle of another device -> KZG_ERR_INVALID_ARG; 2. count > 2^20 ->
+ * KZG_ERR_TOO_LARGE, count n 32 overflowing size_t -> KZG_ERR_INVALID_ARG; 3. offset + n > kzg_g2srs_len -> KZG_ERR_POLY_LENGTH.
+ * _device: the scalars are already in device memory. */
+int32_t kzg_msm_g2_srs_batch(kzg_ctx* ctx, const kzg_g2srs* srs, size_t offset, const uint64_t* scalars_mont, size_t n, size_t count,
+                             uint64_t* out_g2_mont /* count x 16 */, uint8_t* out_is_infinity /* count, may be NULL */);
+int32_t kzg_msm_g2_srs_batch_device(kzg_ctx* ctx, const kzg_g2srs* srs, size_t offset, const void* d_scalars_mont, size_t n, size_t count,
+                                    uint64_t* out_g2_mont /* count x 16 */, uint8_t* out_is_infinity /* count, may be NULL */);
+/* count blobs of n coefficients each (blob b at coeffs + b n 4), one claimed length: row b of every output = kzg_commit_with_length_proof
+ * on blob b, bit for bit.  The scalars are uploaded once; the G1 commitments are what kzg_commit_coeff_form_batch_device returns for
+ * them (g1_srs is not const: that path may build the per-bit tables); the two G2 outputs of a group come from one digit pass and one
+ * sort, which both base sets share.  Errors, checked on the host before any launch, in this order: 1. a null pointer (coeffs only
+ * when n and count are non-zero) or a handle of another device -> KZG_ERR_INVALID_ARG; 2. count > 2^20 -> KZG_ERR_TOO_LARGE, count n 32
+ * overflowing size_t -> KZG_ERR_INVALID_ARG; 3. rows 2 to 5 of kzg_commit_with_length_proof. */
+int32_t kzg_commit_with_length_proof_batch(kzg_ctx* ctx, kzg_srs* g1_srs, const kzg_g2srs* g2_srs, const kzg_g2srs* g2_trailing,
+                                           uint64_t trailing_first_power, uint64_t srs_order, const uint64_t* coeffs_mont /* count x n x 4 */,
+                                           size_t n, size_t count, uint64_t claimed_len, uint64_t* out_commitments_xy /* count x 8 */,
+                                           uint64_t* out_length_commitments /* count x 16 */, uint64_t* out_length_proofs /* count x 16 */);
+/* The most blobs per group of the batched G2 calls on this context; 0 = the planner's choice (same results whatever the value). */
+int32_t kzg_ctx_set_g2_batch_group(kzg_ctx* ctx, uint32_t max_blobs);
+/* What a batched G2 call of `count` blobs of n scalars over nb (1 or 2) base sets would do under max_blobs: a pure query (no context,
+ * no device; lanes as planned for a 256-CU device).  The plan fields describe a FULL group.  Errors: out NULL or nb not 1 or 2 ->
+ * KZG_ERR_INVALID_ARG; then row 2 of the tables above.  n = 0 or count = 0: no group (all fields 0). */
+typedef struct kzg_g2_batch_info {
+    uint64_t blobs_per_group;   /* the last group of a call may hold fewer */
+    uint64_t groups;
+    uint64_t entries;           /* sorted entries of a full group at most: blobs_per_group x W x n */
+    uint64_t workspace_bytes;   /* device buffers of a full group, the sort's included */
+    uint32_t batched;           /* 0: the shape goes blob by blob through the single call's path (groups of one, that path's own plan) */
+    uint32_t c, W;              /* window bits and windows: the single call's */
+    uint32_t G;                 /* buckets of one base set: blobs_per_group x W x 2^(c-1) */
+    uint32_t nl, seg;           /* accumulate lanes per base set, sorted entries per lane at most */
+    uint32_t sort_small;        /* 1: the global-atomic sort (fewer than 2^18 entries), 0: the tiled one */
+    uint32_t scan1;             /* 1: the one-workgroup scan of the bucket counts, 0: the three-kernel one */
+    uint32_t launches;          /* kernel launches and memsets per group */
+    uint32_t reserved;
+} kzg_g2_batch_info;
+int32_t kzg_msm_g2_batch_info(size_t n, uint32_t nb, size_t count, uint32_t max_blobs, kzg_g2_batch_info* out);
+/* The two pairing checks of a header (the top of this section), g1_tau_shift_xy = [tau^(N-d)]_1.  Host only: two calls of the pairing check, no random weight.  A
  * failed check is *out_ok = 0 with KZG_OK.  A G1 input off the curve -> KZG_ERR_G1_NOT_ON_CURVE; a G2 input off the twist ->
  * KZG_ERR_G2_TAU_NOT_ON_CURVE.  The subgroup of the G2 inputs is not checked (see kzg_verify_proof). */
 int32_t kzg_verify_length_proof(const uint64_t commitment_xy[8], const uint64_t length_commitment[16], const uint64_t length_proof[16],

@@ -54,6 +54,12 @@ class EncodeBatchInfo(C.Structure):                              # kzg_encode_ba
                 ("reserved", C.c_int32), ("inverse", EncodeTransformInfo), ("forward", EncodeTransformInfo)]
 
 
+class G2BatchInfo(C.Structure):                                  # kzg_g2_batch_info of the header
+    _fields_ = [("blobs_per_group", C.c_uint64), ("groups", C.c_uint64), ("entries", C.c_uint64), ("workspace_bytes", C.c_uint64),
+                ("batched", C.c_uint32), ("c", C.c_uint32), ("W", C.c_uint32), ("G", C.c_uint32), ("nl", C.c_uint32), ("seg", C.c_uint32),
+                ("sort_small", C.c_uint32), ("scan1", C.c_uint32), ("launches", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 ENCODE_FORMS = ("none", "copy", "direct", "radix2")              # KZG_ENCODE_FORM_*
 ENCODE_LOADS = ("in place", "copy", "bitrev", "pad", "spread")   # KZG_ENCODE_LOAD_*
 
@@ -205,6 +211,11 @@ PROTOTYPES = {
     "kzg_commit_g2_coeff_form": (i32, [vp, vp, u64p, sz, u64p, u8p]),
     "kzg_commit_g2_eval_form": (i32, [vp, vp, u64p, sz, u64p, u8p]),
     "kzg_commit_with_length_proof": (i32, [vp, vp, vp, vp, C.c_uint64, C.c_uint64, u64p, sz, C.c_uint64, u64p, u64p, u64p]),
+    "kzg_msm_g2_srs_batch": (i32, [vp, vp, sz, u64p, sz, sz, u64p, u8p]),
+    "kzg_msm_g2_srs_batch_device": (i32, [vp, vp, sz, vp, sz, sz, u64p, u8p]),
+    "kzg_commit_with_length_proof_batch": (i32, [vp, vp, vp, vp, C.c_uint64, C.c_uint64, u64p, sz, sz, C.c_uint64, u64p, u64p, u64p]),
+    "kzg_ctx_set_g2_batch_group": (i32, [vp, C.c_uint32]),
+    "kzg_msm_g2_batch_info": (i32, [sz, C.c_uint32, sz, C.c_uint32, vp]),
     "kzg_verify_length_proof": (i32, [u64p, u64p, u64p, u64p, C.POINTER(i32)]),
     "kzg_pairings_product_verify": (i32, [u64p, u64p, sz, C.POINTER(i32)]),
     "kzg_g2_check_subgroup": (i32, [vp, u64p, sz, C.POINTER(C.c_uint64)]),
@@ -306,6 +317,12 @@ class Context:
         is never smaller than one blob (same results whatever the budget)."""
         if nbytes < 0 or load().kzg_ctx_set_encode_group_bytes(self.handle, int(nbytes)) != OK:
             raise ValueError("the budget is a byte count >= 0")
+
+    def set_g2_batch_group(self, max_blobs=0):
+        """The most blobs per group of the batched G2 calls (`KZG.commit_with_length_proof_batch`, `G2SRS.msm_batch`) on this context; 0 =
+        the planner's choice (same results whatever the value; `helpers.g2_batch_info` tells how a shape is grouped)."""
+        if not 0 <= max_blobs < 2 ** 32 or load().kzg_ctx_set_g2_batch_group(self.handle, int(max_blobs)) != OK:
+            raise ValueError("the cap is a blob count >= 0")
 
     def close(self):
         if self.handle:

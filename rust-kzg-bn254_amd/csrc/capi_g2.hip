@@ -1,11 +1,12 @@
 // capi_g2.hip — the G2 part of the C-ABI (include/kzg_bn254_mi355x.h, "G2 on the device"): the device-resident G2 SRS handle, the G2
-// MSM over caller bases or a handle, G2 commitments, the blob header (commitment, length commitment, length proof) in one call, its
-// verification by two pairing checks, the batched verification of headers (subgroup test and weighted sums on the device, one
-// product of pairings), and the decoders of gnark-compressed G2 points: on the host, and on the device into wire points or a resident
+// MSM over caller bases or a handle, G2 commitments, the blob header (commitment, length commitment, length proof) in one call, the
+// headers of many blobs and the batched MSM over shared bases (with the pure query of their plan), the header's verification by two
+// pairing checks, the batched verification of headers (subgroup test and weighted sums on the device, one product of pairings), and the decoders of gnark-compressed G2 points: on the host, and on the device into wire points or a resident
 // handle.  The kernels and their drivers are g2msm.hip, g2batch.hip and g2decode.hip; every argument check here runs before any launch.
 #include "engine.h"
 #include <new>
 #include "field29.h"
+#include "g2msm_plan.h"
 #include "host_g2_decode.h"
 #include "host_fiat_shamir.h"
 
@@ -73,6 +74,35 @@ int32_t msm_g2_srs_common(kzg_ctx* ctx, const kzg_g2srs* srs, size_t offset, con
     if (offset > srs->n || n > srs->n - offset) return KZG_ERR_POLY_LENGTH;
     std::lock_guard<std::mutex> lk(ctx->mu);
     return msm_g2_srs_locked(ctx, srs, offset, scalars, on_device, n, out, out_inf);
+}
+
+
+// the size of a batch: row 2 of the batched calls' error tables
+int32_t g2_batch_size_check(size_t n, size_t count) {
+    if (count > ((size_t)1 << 20)) return KZG_ERR_TOO_LARGE;
+    if (n && count && n > SIZE_MAX / 32 / count) return KZG_ERR_INVALID_ARG;           // count n 32 bytes of scalars
+    return KZG_OK;
+}
+int32_t msm_g2_srs_batch_common(kzg_ctx* ctx, const kzg_g2srs* srs, size_t offset, const void* scalars, bool on_device, size_t n, size_t count,
+                                uint64_t* out, uint8_t* out_inf) {
+    if (!ctx || !srs || srs->ctx->device != ctx->device || !out || (n && count && !scalars)) return KZG_ERR_INVALID_ARG;
+    { const int32_t rc = g2_batch_size_check(n, count); if (rc != KZG_OK) return rc; }
+    if (offset > srs->n || n > srs->n - offset) return KZG_ERR_POLY_LENGTH;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (slot0_busy(ctx)) return KZG_ERR_INVALID_ARG;
+    if (count == 0) return KZG_OK;
+    if (n == 0) {
+        memset(out, 0, count * 128);
+        if (out_inf) memset(out_inf, 1, count);
+        return KZG_OK;
+    }
+    const void* d_scalars = scalars;
+    if (!on_device) { const int32_t rc = stage_scalars_g2(ctx, static_cast<const uint64_t*>(scalars), count * n, &d_scalars); if (rc != KZG_OK) return rc; }
+    const uint4* pts[1] = {srs->d_points + 8 * offset};
+    uint64_t* outs[1] = {out};
+    uint8_t* infs[1] = {out_inf};
+    return g2_msm_batch_run(ctx, pts, 1, d_scalars, n, count, outs, infs);
 }
 
 }  // namespace
@@ -217,6 +247,83 @@ int32_t kzg_commit_with_length_proof(kzg_ctx* ctx, const kzg_srs* g1_srs, const 
     if (rc != KZG_OK) return rc;
     memcpy(out_length_commitment, out2, 128);
     memcpy(out_length_proof, out2 + 16, 128);
+    return KZG_OK;
+}
+
+// ---- many blobs in one call: the batched G2 MSM over shared bases (g2msm.hip g2_msm_batch_run) -----------------------------------------
+int32_t kzg_msm_g2_srs_batch(kzg_ctx* ctx, const kzg_g2srs* srs, size_t offset, const uint64_t* scalars_mont, size_t n, size_t count,
+                             uint64_t* out_g2_mont, uint8_t* out_is_infinity) {
+    return msm_g2_srs_batch_common(ctx, srs, offset, scalars_mont, false, n, count, out_g2_mont, out_is_infinity);
+}
+int32_t kzg_msm_g2_srs_batch_device(kzg_ctx* ctx, const kzg_g2srs* srs, size_t offset, const void* d_scalars_mont, size_t n, size_t count,
+                                    uint64_t* out_g2_mont, uint8_t* out_is_infinity) {
+    return msm_g2_srs_batch_common(ctx, srs, offset, d_scalars_mont, true, n, count, out_g2_mont, out_is_infinity);
+}
+
+int32_t kzg_commit_with_length_proof_batch(kzg_ctx* ctx, kzg_srs* g1_srs, const kzg_g2srs* g2_srs, const kzg_g2srs* g2_trailing,
+                                           uint64_t trailing_first_power, uint64_t srs_order, const uint64_t* coeffs_mont, size_t n, size_t count,
+                                           uint64_t claimed_len, uint64_t* out_commitments_xy, uint64_t* out_length_commitments,
+                                           uint64_t* out_length_proofs) {
+    // 1. pointers and devices
+    if (!ctx || !g1_srs || !g2_srs || !g2_trailing || !out_commitments_xy || !out_length_commitments || !out_length_proofs || (n && count && !coeffs_mont))
+        return KZG_ERR_INVALID_ARG;
+    if (g1_srs->ctx->device != ctx->device || g2_srs->ctx->device != ctx->device || g2_trailing->ctx->device != ctx->device) return KZG_ERR_INVALID_ARG;
+    // 2. the size of the batch
+    { const int32_t rc = g2_batch_size_check(n, count); if (rc != KZG_OK) return rc; }
+    // 3. rows 2 to 5 of kzg_commit_with_length_proof
+    if (!is_pow2(srs_order) || !is_pow2(claimed_len)) return KZG_ERR_NOT_POWER_OF_TWO;
+    if (n > claimed_len || claimed_len > srs_order) return KZG_ERR_INVALID_ARG;
+    if (srs_order - claimed_len < trailing_first_power) return KZG_ERR_SRS_CAPACITY_EXCEEDED;
+    const uint64_t off = srs_order - claimed_len - trailing_first_power;
+    if (off > g2_trailing->n || claimed_len > g2_trailing->n - off) return KZG_ERR_SRS_CAPACITY_EXCEEDED;
+    if (n > g1_srs->n || n > g2_srs->n) return KZG_ERR_POLY_LENGTH;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (slot0_busy(ctx)) return KZG_ERR_INVALID_ARG;
+    if (count == 0) return KZG_OK;
+    if (n == 0) {
+        memset(out_commitments_xy, 0, count * 64); memset(out_length_commitments, 0, count * 128); memset(out_length_proofs, 0, count * 128);
+        return KZG_OK;
+    }
+    const void* d_scalars;
+    int32_t rc = stage_scalars_g2(ctx, coeffs_mont, count * n, &d_scalars);     // the one upload: every MSM of every blob reads it
+    if (rc != KZG_OK) return rc;
+    KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                          // (the G1 launches run on the slots' streams)
+    rc = commit_batch_device(ctx, g1_srs, d_scalars, n, count, out_commitments_xy, nullptr);
+    if (rc != KZG_OK) return rc;
+    const uint4* pts[2] = {g2_srs->d_points, g2_trailing->d_points + 8 * off};
+    uint64_t* outs[2] = {out_length_commitments, out_length_proofs};
+    return g2_msm_batch_run(ctx, pts, 2, d_scalars, n, count, outs, nullptr);    // per group: one digit pass and sort, both base sets in every launch
+}
+
+int32_t kzg_ctx_set_g2_batch_group(kzg_ctx* ctx, uint32_t max_blobs) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->g2_batch_group = max_blobs;
+    return KZG_OK;
+}
+
+int32_t kzg_msm_g2_batch_info(size_t n, uint32_t nb, size_t count, uint32_t max_blobs, kzg_g2_batch_info* out) {
+    if (!out || (nb != 1 && nb != 2)) return KZG_ERR_INVALID_ARG;
+    { const int32_t rc = g2_batch_size_check(n, count); if (rc != KZG_OK) return rc; }
+    *out = kzg_g2_batch_info{};
+    if (n == 0 || count == 0) return KZG_OK;
+    const uint32_t wave_slots = 256 * 4 * G2_ACC_WAVES;                  // a 256-CU device (what kzg_ctx_create finds on an MI355X)
+    const uint32_t group = g2_batch_group(n, nb, count, max_blobs);
+    out->batched = group ? 1 : 0;
+    out->blobs_per_group = group ? group : 1;
+    out->groups = (count + out->blobs_per_group - 1) / out->blobs_per_group;
+    if (group) {
+        const G2BatchPlan p = g2_make_batch_plan(n, nb, group, wave_slots);
+        out->entries = p.entries(); out->workspace_bytes = p.workspace_bytes;
+        out->c = (uint32_t)p.c; out->W = (uint32_t)p.W; out->G = p.G; out->nl = p.nl; out->seg = p.seg;
+        out->sort_small = p.sort.sort_small ? 1 : 0; out->scan1 = p.G <= SCAN1_MAX ? 1 : 0; out->launches = p.launches;
+    } else {                                                             // one launch (of the first G2MSM_MAX_LAUNCH scalars) of g2_msm_run
+        const G2Plan p = g2_make_plan(std::min<size_t>(n, G2MSM_MAX_LAUNCH), nb, wave_slots);
+        out->entries = p.entries(); out->workspace_bytes = p.workspace_bytes;
+        out->c = (uint32_t)p.c; out->W = (uint32_t)p.W; out->G = p.G; out->nl = p.nl; out->seg = p.seg;
+        out->sort_small = p.sort.sort_small ? 1 : 0; out->scan1 = p.G <= SCAN1_MAX ? 1 : 0; out->launches = p.launches;
+    }
     return KZG_OK;
 }
 

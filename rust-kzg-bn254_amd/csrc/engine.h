@@ -103,6 +103,7 @@ struct kzg_ctx {
     int msm_c_override = 0;
     int msm_seg_override = 0;
     size_t encode_group_bytes = 0;         // kzg_ctx_set_encode_group_bytes: the workspace budget of a group of kzg_encode_cosets_batch, 0 = ENCODE_GROUP_BYTES_DEFAULT
+    uint32_t g2_batch_group = 0;           // kzg_ctx_set_g2_batch_group: most blobs per group of the batched G2 MSM, 0 = the planner's choice (g2msm_plan.h)
     int reduction_lanes = 0;               // kzg_ctx_set_reduction_lanes: 0 automatic, 2 lane pairs, 4 lane quads
     std::atomic<int> transcript_device{0}; // kzg_ctx_set_transcript_device: 0 automatic, 1 always host, 2 always device (the weights of kzg_verify_multiproof_batch)
     bool profiling = false;
@@ -282,6 +283,11 @@ int32_t fr_powers_canonical(kzg_ctx* ctx, const uint64_t tau_mont[4], uint64_t f
 // the MSM of ONE scalar set (device, wire form) over nb <= 2 base sets (device format, 8 uint4 per point): digits and sort once, accumulate and
 // reduce per set; out: nb x 16 u64 affine wire points, out_inf: nb flags (may be null)
 int32_t g2_msm_run(kzg_ctx* ctx, const uint4* const* d_points, uint32_t nb, const void* d_scalars, size_t n, uint64_t* out_g2, uint8_t* out_inf);
+// `count` scalar sets of n scalars each (device, wire form, one after the other), ALL over the same nb <= 2 base sets of n points: groups of
+// blobs planned by g2_batch_group (g2msm_plan.h; ctx->g2_batch_group caps them), one sort and one launch sequence per group for every
+// blob and base set in it.  out_g2[s]: count x 16 u64 affine wire points of base set s, out_inf[s]: count flags (the array or an entry may be null)
+int32_t g2_msm_batch_run(kzg_ctx* ctx, const uint4* const* d_points, uint32_t nb, const void* d_scalars, size_t n, size_t count, uint64_t* const* out_g2,
+                         uint8_t* const* out_inf);
 // n wire points of the host -> device format at d_out, every point checked on the twist (or the identity); *bad = index of the first one off it, or -1
 int32_t g2_upload_points(kzg_ctx* ctx, const uint64_t* g2_mont, size_t n, uint4* d_out, int64_t* bad);
 int32_t g2_generate_points(kzg_ctx* ctx, const uint64_t tau_mont[4], uint64_t first_power, size_t n, uint4* d_out);

@@ -173,6 +173,9 @@ static int32_t sort_from_digits(const Launch& L) {
     MsmWorkspace& ws = L.ws;
     hipStream_t st = L.st;
     const uint32_t n_total = p.n * p.batch;
+    // the scatters add (set / windows_per_msm) * n to an entry's index (batched MSMs over concatenated bases): no set reaches this divisor,
+    // so over shared bases the term is 0
+    const uint32_t windows_per_msm = p.shared_bases ? 0xFFFFFFFFu : (uint32_t)p.W;
     KZG_HIP_TRY(L.ctx, hipMemsetAsync(ws.count.p, 0, (size_t)p.G * 4, st));
     hipLaunchKernelGGL(k_msm_digits, dim3((n_total + 255) / 256), dim3(256), 0, st, L.d_scalars, n_total, p.n, p.c, p.W, ws.digits.as<uint32_t>(), (uint32_t*)nullptr);
     KZG_MARK(1);
@@ -183,7 +186,7 @@ static int32_t sort_from_digits(const Launch& L) {
         scan_counts(L);
         KZG_MARK(2);
         hipLaunchKernelGGL(k_sort_small_scatter, dim3(ge), dim3(256), 0, st, ws.digits.as<uint32_t>(), entries, p.n, p.set_len, p.B,
-                           ws.offs.as<uint32_t>(), ws.blockbase.as<uint32_t>(), p.idx_stride, (uint32_t)p.W, ws.sorted.as<uint32_t>());
+                           ws.offs.as<uint32_t>(), ws.blockbase.as<uint32_t>(), p.idx_stride, windows_per_msm, ws.sorted.as<uint32_t>());
     } else {
         const size_t lds_bytes = (size_t)p.B * 4;
         hipLaunchKernelGGL(k_sort_hist, dim3(p.tiles), dim3(256), lds_bytes, st, ws.digits.as<uint32_t>(), p.set_len, p.tile_len,
@@ -192,7 +195,7 @@ static int32_t sort_from_digits(const Launch& L) {
         KZG_MARK(2);
         hipLaunchKernelGGL(k_sort_scatter, dim3(p.tiles), dim3(256), lds_bytes, st, ws.digits.as<uint32_t>(), p.n, p.set_len, p.tile_len,
                            p.tiles_per_set, p.B, ws.offs.as<uint32_t>(), ws.blockbase.as<uint32_t>(), p.idx_stride,
-                           (uint32_t)p.W, ws.sorted.as<uint32_t>());
+                           windows_per_msm, ws.sorted.as<uint32_t>());
     }
     KZG_MARK(3);
     return KZG_OK;
@@ -342,11 +345,12 @@ int32_t msm_pinned_out(kzg_ctx* ctx, MsmWorkspace& ws) {
     KZG_HIP_TRY(ctx, hipHostGetDevicePointer(&ws.pinned_out_dev, ws.pinned_out, 0));
     return KZG_OK;
 }
-// Digits and counting sort of ONE generic-mode scalar set on `st` for the G2 driver (g2msm.hip), whose kernels add points of another
+// Digits and counting sort of generic-mode scalar sets on `st` for the G2 driver (g2msm.hip), whose kernels add points of another
 // type: ws.sorted and ws.offs as enqueue_sort leaves them (entries index | sign << 31 grouped by bucket, p.G + 1 offsets).  p: a plan
-// of make_plan without tables and with batch 1; only the buffers of the sort are reserved.
+// of make_plan without tables, with batch 1 or -- p.batch sets of p.n scalars one after the other, all over the same bases -- marked
+// shared_bases (every entry then holds its in-set index); only the buffers of the sort are reserved.
 int32_t msm_sort_generic(kzg_ctx* ctx, MsmWorkspace& ws, hipStream_t st, const uint4* d_scalars, const Plan& p) {
-    if (p.tables || p.batch != 1 || p.bitsum) return KZG_ERR_INVALID_ARG;
+    if (p.tables || p.bitsum || p.batch == 0 || (p.batch != 1 && !p.shared_bases)) return KZG_ERR_INVALID_ARG;
     for (int i : {WS_DIGITS, WS_SORTED, WS_COUNT, WS_BLOCKBASE, WS_OFFS, WS_BLOCK_SUMS}) KZG_HIP_TRY(ctx, ws_buffer(ws, i)->reserve(p.bytes[i]));
     const MsmBases none;
     const Launch L{ctx, ws, st, none, d_scalars, p, nullptr, false};

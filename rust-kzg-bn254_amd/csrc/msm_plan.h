@@ -41,6 +41,8 @@ inline int ilog2_floor(size_t n) { int k = 0; while ((n >> (k + 1)) != 0) ++k; r
 struct Plan {
     uint32_t n;          // pairs per MSM in this launch
     uint32_t batch;      // independent MSMs of n pairs each (generic mode only; 1 otherwise)
+    bool shared_bases = false;   // generic mode, batch > 1: every MSM of the batch reads the SAME n bases, so a sorted entry holds the in-MSM
+                                 // index i < n, not msm * n + i (the G2 driver's batches, g2msm_plan.h; set by the caller of make_plan)
     bool tables;         // table mode
     bool naf;            // table mode over the per-bit tables: width-(c + 1) NAF digits (msm_kernels.h), W = most entries per scalar
     uint32_t polys;      // BATCHED table mode (NAF, c = 7): the n scalars are `polys` polynomials of n / polys coefficients over the same bases,

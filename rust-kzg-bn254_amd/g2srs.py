@@ -112,6 +112,22 @@ class G2SRS:
             self.ctx.check_device(_lib.load().kzg_g2srs_download(self.ctx.handle, self.handle, 0, self._n, _lib.ptr(out)))
         return out
 
+    def msm_batch(self, scalars, offset: int = 0) -> np.ndarray:
+        """(B, n, 4) Fr wire scalars -> (B, 16) wire points: row b = sum_i scalars[b][i] * point[offset + i] (`kzg_msm_g2_srs_batch`), the
+        blobs of a group in one sort and one launch sequence; bit for bit the single MSM of every row."""
+        sc = np.ascontiguousarray(scalars, dtype=np.uint64)
+        if sc.ndim != 3 or sc.shape[2] != 4:
+            raise GenericError("scalars: a (B, n, 4) array of Fr wire words")
+        count, n = sc.shape[0], sc.shape[1]
+        out = np.zeros((count, 16), dtype=np.uint64)
+        rc = _lib.load().kzg_msm_g2_srs_batch(self.ctx.handle, self.handle, offset, _lib.ptr(sc) if sc.size else None, n, count, _lib.ptr(out), None)
+        if rc == _lib.ERR_POLY_LENGTH:
+            raise GenericError("polynomial length is not correct")
+        self.ctx.check_device(rc)
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+        return out
+
     def __len__(self):
         return self._n
 

@@ -378,6 +378,20 @@ def encode_batch_info(d: int, n: int, chunk_len: int, count: int, values: bool =
             "batched": bool(info.batched), "inverse": transform(info.inverse), "forward": transform(info.forward)}
 
 
+def g2_batch_info(n: int, nb: int, count: int, max_blobs: int = 0) -> dict:
+    """What a batched G2 call (`KZG.commit_with_length_proof_batch`: nb = 2, `G2SRS.msm_batch`: nb = 1) does with `count` blobs of n
+    scalars under a cap of `max_blobs` blobs per group (0: none) -- `kzg_msm_g2_batch_info`, a pure query: blobs per group, groups,
+    whether the shape batches at all, and for a full group the window bits c, windows W, buckets G, sorted entries, accumulate lanes
+    nl, entries per lane seg, the sort form, the scan form, launches and workspace bytes."""
+    info = _lib.G2BatchInfo()
+    rc = _lib.load().kzg_msm_g2_batch_info(n, nb, count, max_blobs, C.byref(info))
+    if rc != _lib.OK:
+        raise GenericError(_lib.status_message(rc))
+    out = {name: int(getattr(info, name)) for name, _ in _lib.G2BatchInfo._fields_ if name != "reserved"}
+    out["batched"] = bool(out["batched"])
+    return out
+
+
 def compute_powers(base, count: int) -> np.ndarray:
     """helpers.rs:298-315: [base^0 .. base^(count-1)]."""
     b = fr_to_int(base)

@@ -128,6 +128,33 @@ class KZG:
             raise GenericError(_lib.status_message(rc))
         return c, c2, pi2
 
+    def commit_with_length_proof_batch(self, polys, srs, g2_srs, g2_trailing, srs_order: int, claimed_len: int):
+        """The headers of B blobs of one length and one claimed length in ONE call (`kzg_commit_with_length_proof_batch`): arrays (B, 8),
+        (B, 16), (B, 16) whose row b is `commit_with_length_proof` of polys[b], bit for bit.  One scalar upload; the G1 commitments are
+        the batched commitments'; the G2 elements of a group of blobs come from one sort and one launch sequence (both base sets in every
+        launch; `helpers.g2_batch_info` tells how a shape is grouped, `Context.set_g2_batch_group` caps the groups)."""
+        ctx = self._ctx()
+        rows = [_lib.as_u64(p.coeffs() if hasattr(p, "coeffs") else p, 4).reshape(-1, 4) for p in polys]
+        count = len(rows)
+        n = len(rows[0]) if rows else 0
+        if any(len(r) != n for r in rows):
+            raise GenericError("batched headers need polynomials of one length")
+        data = np.ascontiguousarray(np.concatenate(rows, axis=0)) if n and count else np.zeros((0, 4), dtype=np.uint64)
+        c = np.zeros((count, 8), dtype=np.uint64); c2 = np.zeros((count, 16), dtype=np.uint64); pi2 = np.zeros((count, 16), dtype=np.uint64)
+        rc = _lib.load().kzg_commit_with_length_proof_batch(ctx.handle, srs.handle, g2_srs.handle, g2_trailing.handle, g2_trailing.first_power, srs_order,
+                                                            _lib.ptr(data) if data.size else None, n, count, claimed_len, _lib.ptr(c), _lib.ptr(c2),
+                                                            _lib.ptr(pi2))
+        if rc == _lib.ERR_NOT_POWER_OF_TWO:
+            raise FFTError("length provided is not a power of 2")
+        if rc == _lib.ERR_SRS_CAPACITY_EXCEEDED:
+            raise SrsCapacityExceeded(int(claimed_len), len(g2_trailing))
+        if rc == _lib.ERR_POLY_LENGTH:
+            raise SerializationError("polynomial length is not correct")
+        ctx.check_device(rc)
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+        return c, c2, pi2
+
     # ---- batched commitments: many polynomials of one length against one SRS in one kernel sequence (no counterpart in the
     # reference, which commits one polynomial per call; same values as that many calls) -----------------------------------------
     def _commit_batch(self, rows, srs, eval_form):
