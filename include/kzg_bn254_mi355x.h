@@ -27,7 +27,7 @@
  *   KZG_ROCTX=1                           roctx ranges around the host phases (rocprofv3 --marker-trace)
  *   KZG_NTT_TILE_LOG=10 / 11              one tile size of the Fr NTT at every transform size
  *   KZG_EXCHANGE_TIMEOUT_S, KZG_RCCL_LIB  the _rccl entries: seconds to wait for a collective (60); the RCCL to dlopen
- * Per-context settings are calls (kzg_ctx_set_msm_window, kzg_ctx_set_reduction_lanes, kzg_ctx_set_transcript_device, kzg_ctx_set_encode_group_bytes).  Entry points marked MEASUREMENT ONLY below
+ * Per-context settings are calls (kzg_ctx_set_msm_window, kzg_ctx_set_reduction_lanes, kzg_ctx_set_transcript_device, kzg_ctx_set_encode_group_bytes, kzg_ctx_set_recover_group_bytes).  Entry points marked MEASUREMENT ONLY below
  * (kzg_ctx_set_profiling, kzg_ctx_get_msm_profile*, kzg_ctx_measure_valu_rates) exist for bench.py's roofline figures; a host binding can leave them out.
  */
 #ifndef KZG_BN254_MI355X_H
@@ -777,6 +777,49 @@ int32_t kzg_verify_multiproof_batch_locate(kzg_ctx* ctx, kzg_srs* srs, const uin
 int32_t kzg_recover_from_cosets(kzg_ctx* ctx, const uint64_t* ys_mont, const uint64_t* coset_indices, size_t count, size_t n,
                                 size_t chunk_len, size_t degree_bound, int32_t eval_form, uint64_t* out_poly_mont,
                                 int32_t* out_consistent);
+/* kzg_recover_from_cosets for `blobs` blobs of one shape (n, chunk_len, count, degree_bound, eval_form) in one call.  ys_mont: blobs x
+ * count x chunk_len x 4 u64, blob b at ys_mont + b count chunk_len 4.  coset_indices: index_rows x count; index_rows = 1: every blob
+ * has these cosets, in this order of items; index_rows = blobs: row b belongs to blob b.  Row b of out_polys_mont (blobs x out_len x 4)
+ * and out_consistent[b] (may be NULL) are bit-identical to kzg_recover_from_cosets on blob b with its row of indices, whatever the
+ * grouping, the launch geometry, the order of the items inside a blob and whichever other blobs share the call.
+ * out_len: 0 means n.  With eval_form = 1 it must be 0 or n.  With eval_form = 0 any value with degree_bound (resolved: 0 -> count *
+ * chunk_len) <= out_len <= n is allowed: only the first out_len coefficients of each blob are written and downloaded (a consistent blob
+ * has nothing but zeros from degree_bound on); the rows are compacted on the device, the download is one contiguous copy.  The flag
+ * still covers every coefficient from degree_bound to n.
+ * The blobs' missing sets are deduplicated into patterns (a set, whatever the order of the items): the vanishing values are computed
+ * once per pattern of a group, not once per blob.  The call works through the blobs in GROUPS whose device workspace fits a byte
+ * budget (4 GiB unless kzg_ctx_set_recover_group_bytes says otherwise; at most 32 768 blobs; sized for the worst case of one pattern
+ * per blob, so the grouping depends on the shape alone; never smaller than one blob): inside a group every stage is one launch for
+ * all its blobs, with one upload of the values, one of indices and patterns, one download of the rows and one of the flags.
+ * Synchronous, host buffers, no SRS.
+ * Errors, checked on the host before any kernel runs, in this order:
+ *   1. a null ctx, ys, indices or output, or blobs = 0 -> KZG_ERR_INVALID_ARG;
+ *   2. index_rows neither 1 nor blobs -> KZG_ERR_INVALID_ARG;
+ *   3. rows 2 .. 5 of kzg_recover_from_cosets' table, unchanged;
+ *   4. an index >= m or a duplicate index in any row -> KZG_ERR_INVALID_ARG;
+ *   5. degree_bound > count * chunk_len -> KZG_ERR_INVALID_ARG;
+ *   6. a bad out_len -> KZG_ERR_INVALID_ARG;
+ *   7. m * (m - count) > 2^32 -> KZG_ERR_TOO_LARGE;
+ *   8. blobs x n x 32 bytes overflowing size_t -> KZG_ERR_INVALID_ARG.
+ * After any error the context stays usable. */
+int32_t kzg_recover_from_cosets_batch(kzg_ctx* ctx, const uint64_t* ys_mont /* blobs x count x chunk_len x 4 */,
+                                      const uint64_t* coset_indices /* index_rows x count */, size_t index_rows, size_t blobs,
+                                      size_t count, size_t n, size_t chunk_len, size_t degree_bound, int32_t eval_form,
+                                      size_t out_len /* 0 = n */, uint64_t* out_polys_mont /* blobs x out_len x 4 */,
+                                      int32_t* out_consistent /* blobs, may be NULL */);
+/* The workspace budget of a group of kzg_recover_from_cosets_batch on this context, in bytes; 0 = the default (4 GiB). */
+int32_t kzg_ctx_set_recover_group_bytes(kzg_ctx* ctx, size_t bytes);
+/* How kzg_recover_from_cosets_batch groups these blobs: a pure query (no context, no device).  group_bytes: the budget, 0 = the
+ * default.  Errors: out NULL or blobs = 0 -> KZG_ERR_INVALID_ARG, rows 3 of the table above, out_len > n -> KZG_ERR_INVALID_ARG, rows 7
+ * and 8. */
+typedef struct kzg_recover_batch_info_t {    /* (_t: the function below has the plain name, and C has one name space for both) */
+    uint64_t blobs_per_group;            /* the last group of a call may hold fewer */
+    uint64_t groups;
+    uint64_t group_bytes;                /* device workspace of one full group, every blob with its own pattern */
+    uint64_t blob_bytes;                 /* of which per blob */
+} kzg_recover_batch_info_t;
+int32_t kzg_recover_batch_info(size_t blobs, size_t count, size_t n, size_t chunk_len, size_t out_len, size_t group_bytes,
+                               kzg_recover_batch_info_t* out);
 
 /* ---- G2 on the device: SRS handle, MSM, length commitment and length proof ---------------------------------------------------------
  * The published blob header of the protocol is (commitment in G1, length commitment in G2, length proof in G2, length): with N the

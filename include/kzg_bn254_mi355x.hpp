@@ -482,6 +482,27 @@ public:
                                                        const Context& ctx = Context::default_context()) const {
         return PolynomialCoeffForm::new_(recover_impl(coset_indices, ys, n, degree_bound, 0, ctx));
     }
+    // The same for `blobs` blobs of one shape in one call (kzg_recover_from_cosets_batch): ys holds blobs x count x l values, coset_indices `count`
+    // indices for all blobs or blobs x count, row b for blob b.  polys: blobs x out_len elements (evaluations, or with eval_form = false coefficients;
+    // out_len = 0 means n), row b bit-identical to the single call on blob b.  It does NOT throw on an inconsistent blob: consistent[b] says which.
+    struct RecoveredBatch { std::vector<Fr> polys; std::vector<int32_t> consistent; size_t out_len = 0; };
+    RecoveredBatch recover_from_cosets_batch(const std::vector<uint64_t>& coset_indices, const std::vector<Fr>& ys, size_t blobs, size_t count, size_t n,
+                                             size_t degree_bound = 0, bool eval_form = true, size_t out_len = 0,
+                                             const Context& ctx = Context::default_context()) const {
+        if (blobs == 0 || count == 0 || ys.empty() || ys.size() % (blobs * count) != 0) throw KzgError::GenericError("ys must hold blobs x count rows of one length");
+        if (coset_indices.size() != count && coset_indices.size() != blobs * count) throw KzgError::GenericError("coset indices must hold count or blobs x count entries");
+        const size_t l = ys.size() / (blobs * count);
+        if (n < 2 || (n & (n - 1)) != 0) throw KzgError::FFTError("length provided is not a power of 2");
+        RecoveredBatch out;
+        out.out_len = out_len ? out_len : n;
+        if (out.out_len > n) throw KzgError::GenericError("out_len is for coefficients, between the degree bound and n");
+        out.polys.resize(blobs * out.out_len);
+        out.consistent.resize(blobs);
+        detail::check(kzg_recover_from_cosets_batch(ctx.handle(), ys.data()->limbs.data(), coset_indices.data(), coset_indices.size() == count ? 1 : blobs, blobs, count,
+                                                    n, l, degree_bound, eval_form ? 1 : 0, out_len, out.polys.data()->limbs.data(), out.consistent.data()),
+                      ctx.handle());
+        return out;
+    }
 private:
     static EncodedCosets encode_impl(const std::vector<Fr>& poly, int32_t eval_form, const SRS& srs, size_t n, size_t l, bool values, bool proofs) {
         const size_t d = poly.size();

@@ -54,7 +54,11 @@ class EncodeBatchInfo(C.Structure):                              # kzg_encode_ba
                 ("reserved", C.c_int32), ("inverse", EncodeTransformInfo), ("forward", EncodeTransformInfo)]
 
 
-class G2BatchInfo(C.Structure):                                  # kzg_g2_batch_info of the header
+class RecoverBatchInfo(C.Structure):                             # kzg_recover_batch_info_t of the header
+    _fields_ = [("blobs_per_group", C.c_uint64), ("groups", C.c_uint64), ("group_bytes", C.c_uint64), ("blob_bytes", C.c_uint64)]
+
+
+class G2BatchInfo(C.Structure):                                 # kzg_g2_batch_info of the header
     _fields_ = [("blobs_per_group", C.c_uint64), ("groups", C.c_uint64), ("entries", C.c_uint64), ("workspace_bytes", C.c_uint64),
                 ("batched", C.c_uint32), ("c", C.c_uint32), ("W", C.c_uint32), ("G", C.c_uint32), ("nl", C.c_uint32), ("seg", C.c_uint32),
                 ("sort_small", C.c_uint32), ("scan1", C.c_uint32), ("launches", C.c_uint32), ("reserved", C.c_uint32)]
@@ -200,6 +204,9 @@ PROTOTYPES = {
     "kzg_verify_multiproof_batch_locate": (i32, [vp, vp, u64p, sz, u64p, u64p, u64p, u64p, sz, sz, sz, u64p, u64p, u64p, sz, u8p, C.POINTER(sz),
                                                  C.POINTER(sz)]),
     "kzg_recover_from_cosets": (i32, [vp, u64p, u64p, sz, sz, sz, sz, i32, u64p, C.POINTER(i32)]),
+    "kzg_recover_from_cosets_batch": (i32, [vp, u64p, u64p, sz, sz, sz, sz, sz, sz, i32, sz, u64p, C.POINTER(i32)]),
+    "kzg_ctx_set_recover_group_bytes": (i32, [vp, sz]),
+    "kzg_recover_batch_info": (i32, [sz, sz, sz, sz, sz, sz, vp]),
     "kzg_g2srs_upload": (i32, [vp, u64p, sz, C.POINTER(vp), C.POINTER(C.c_uint64)]),
     "kzg_g2srs_generate": (i32, [vp, u64p, C.c_uint64, sz, C.POINTER(vp)]),
     "kzg_g2srs_download": (i32, [vp, vp, sz, sz, u64p]),
@@ -316,6 +323,12 @@ class Context:
         """The device-workspace budget of a group of `KZG.encode_cosets_batch` on this context, in bytes; 0 = the default (4 GiB).  A group
         is never smaller than one blob (same results whatever the budget)."""
         if nbytes < 0 or load().kzg_ctx_set_encode_group_bytes(self.handle, int(nbytes)) != OK:
+            raise ValueError("the budget is a byte count >= 0")
+
+    def set_recover_group_bytes(self, nbytes=0):
+        """The device-workspace budget of a group of `KZG.recover_from_cosets_batch` on this context, in bytes; 0 = the default (4 GiB).
+        A group is never smaller than one blob (same results whatever the budget; `helpers.recover_batch_info` tells the grouping)."""
+        if nbytes < 0 or load().kzg_ctx_set_recover_group_bytes(self.handle, int(nbytes)) != OK:
             raise ValueError("the budget is a byte count >= 0")
 
     def set_g2_batch_group(self, max_blobs=0):

@@ -674,6 +674,39 @@ int32_t kzg_recover_from_cosets(kzg_ctx* ctx, const uint64_t* ys_mont, const uin
     return KZG_OK;
 }
 
+// the same for many blobs of one shape: the checks (host_recover.h), the plan under the context's budget, then recover.hip group by group
+int32_t kzg_recover_from_cosets_batch(kzg_ctx* ctx, const uint64_t* ys_mont, const uint64_t* coset_indices, size_t index_rows, size_t blobs, size_t count,
+                                      size_t n, size_t chunk_len, size_t degree_bound, int32_t eval_form, size_t out_len, uint64_t* out_polys_mont,
+                                      int32_t* out_consistent) {
+    int32_t rc = recover_batch_check(!ctx || !ys_mont || !coset_indices || !out_polys_mont, coset_indices, index_rows, blobs, count, n, chunk_len, degree_bound,
+                                     eval_form != 0, out_len);
+    if (rc != KZG_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    RecoverBatchPlan plan;
+    recover_batch_plan(coset_indices, index_rows, blobs, count, n, chunk_len, degree_bound, eval_form != 0, out_len, ctx->recover_group_bytes, &plan);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return recover_run_batch(ctx, plan, ys_mont, out_polys_mont, out_consistent);
+}
+
+int32_t kzg_ctx_set_recover_group_bytes(kzg_ctx* ctx, size_t bytes) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->recover_group_bytes = bytes;
+    return KZG_OK;
+}
+
+int32_t kzg_recover_batch_info(size_t blobs, size_t count, size_t n, size_t chunk_len, size_t out_len, size_t group_bytes, kzg_recover_batch_info_t* out) {
+    const int32_t rc = recover_batch_info_check(!out, blobs, count, n, chunk_len, out_len);
+    if (rc != KZG_OK) return rc;
+    const RecoverBatchGroups g = recover_batch_groups(blobs, count, n, chunk_len, group_bytes);
+    *out = kzg_recover_batch_info_t{};
+    out->blobs_per_group = g.group;
+    out->groups = g.n_groups;
+    out->group_bytes = g.group_bytes;
+    out->blob_bytes = g.blob_bytes;
+    return KZG_OK;
+}
+
 // accept <=> e(sum_i r_i pi_i, [tau^l]_2) = e(sum_rows R_row C_row - sum_t A_t [tau^t]_1 + sum_i r_i w^(k_i l) pi_i, G2), from
 // pi_i tau^l = C - I_i(tau) + w^(k_i l) pi_i.  For l = 1 this is batch.rs:228-254.
 int32_t kzg_verify_multiproof_batch(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments,

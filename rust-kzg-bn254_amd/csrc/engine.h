@@ -10,7 +10,7 @@
 #include <string>
 #include "../../include/kzg_bn254_mi355x.h"
 #include "msm_plan.h"      // MsmBasesShape, msm_batch_capacity
-#include "host_recover.h"  // RecoverPlan
+#include "host_recover.h"  // RecoverPlan, RecoverBatchPlan
 #include "host_encode.h"   // EncodePlan
 #include "host_locate.h"   // LocatePlan
 
@@ -103,6 +103,7 @@ struct kzg_ctx {
     int msm_c_override = 0;
     int msm_seg_override = 0;
     size_t encode_group_bytes = 0;         // kzg_ctx_set_encode_group_bytes: the workspace budget of a group of kzg_encode_cosets_batch, 0 = ENCODE_GROUP_BYTES_DEFAULT
+    size_t recover_group_bytes = 0;        // kzg_ctx_set_recover_group_bytes: the same for kzg_recover_from_cosets_batch, 0 = RECOVER_GROUP_BYTES_DEFAULT
     uint32_t g2_batch_group = 0;           // kzg_ctx_set_g2_batch_group: most blobs per group of the batched G2 MSM, 0 = the planner's choice (g2msm_plan.h)
     int reduction_lanes = 0;               // kzg_ctx_set_reduction_lanes: 0 automatic, 2 lane pairs, 4 lane quads
     std::atomic<int> transcript_device{0}; // kzg_ctx_set_transcript_device: 0 automatic, 1 always host, 2 always device (the weights of kzg_verify_multiproof_batch)
@@ -139,9 +140,9 @@ struct kzg_ctx {
     kzg::DeviceBuffer ml[6];                   // kzg_coset_group_sums / kzg_verify_multiproof_batch_locate (multilocate.hip): group coefficients | the plan's arrays | partial point sums | group sums | rows + shifted weights | proofs + commitments
     kzg::DeviceBuffer fs[2];                  // the coset transcript on the device (fsdevice.hip): commitment rows | proofs, digests | power tables | flag; kzg_sha256_rows: messages, digests
     kzg::DeviceBuffer cb[2];                   // serialized coset items (cosetbytes.hip): value bytes | point bytes (commitments, proofs), decoded wire points, the bad words
-    kzg::DeviceBuffer rc[3];                   // kzg_recover_from_cosets (recover.hip): work values | indices, vanishing values, partial products, flag | powers of g
+    kzg::DeviceBuffer rc[3];                   // kzg_recover_from_cosets(_batch) (recover.hip), for a group of blobs: work values | item maps, patterns, missing lists, flags, vanishing values, partial products (RecoverBatchPlan's layout) | powers of g
     int rc_gpow_log = -1;                      // rc[2] holds the factored tables of g^t and g^-t for t < 2^rc_gpow_log (-1: none yet)
-    kzg::NttWorkspace rc_ntt;                  // its `data` also stages the uploaded coset values (dead before the first transform)
+    kzg::NttWorkspace rc_ntt;                  // its `data` also stages the uploaded coset values (dead before the first transform) and the compacted rows of out_len < n (after the last)
 };
 
 struct kzg_srs {
@@ -378,6 +379,9 @@ int32_t coset_bytes_status(kzg_ctx* ctx, const char* who, const char* array, uin
 // erasure decoding (recover.hip): the polynomial of degree < count l through the values of the plan's cosets (ys: host, count x l wire values), as n
 // coefficients or evaluations on the host; *consistent = its coefficients from plan.degree_bound on are zero.  Called under ctx->mu, synchronised on return
 int32_t recover_run(kzg_ctx* ctx, const RecoverPlan& plan, const uint64_t* ys, bool eval_form, uint64_t* out_poly, int32_t* consistent);
+// the same for the plan's blobs, group by group, every stage one launch per group (ys: blobs x count x l, out_polys: blobs x plan.out_len wire values,
+// consistent: blobs flags or null); recover_run is the batch of one
+int32_t recover_run_batch(kzg_ctx* ctx, const RecoverBatchPlan& plan, const uint64_t* ys, uint64_t* out_polys, int32_t* consistent);
 
 // polynomial pipeline (poly.hip)
 int32_t proof_run(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* evals, size_t n, const uint64_t z[4],

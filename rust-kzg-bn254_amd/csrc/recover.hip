@@ -1,4 +1,4 @@
-// recover.hip — erasure decoding (kzg_recover_from_cosets, capi_verify.hip): from the values of `count` of the m = n / l cosets
+// recover.hip — erasure decoding (kzg_recover_from_cosets, kzg_recover_from_cosets_batch, capi_verify.hip): from the values of `count` of the m = n / l cosets
 // {w^(k + j m) : j < l} of the n-point domain to the polynomial f of degree < count l through them, as n coefficients or n evaluations.
 // The reference has no coset code; the conventions are those of multiproof.hip and multiverify.hip.
 //
@@ -8,24 +8,35 @@
 // domain {g w^i}, g = 5, where Z(g w^i) = z(s w^(l i)), s = g^l, has no zero (s is not an m-th root of unity: g^n != 1):
 //   1. k_recover_vanish / k_recover_vanish_fold   z on the m points w^(l p) and on the m points s w^(l p); the latter inverted
 //   2. k_recover_scatter                          D (every position written once: no memset, no index of the caller reaches a store)
-//   3. ntt_run inverse                            P = f Z
-//   4. k_recover_scale<0>, ntt_run forward        P_t g^t -> P(g w^i)
+//   3. ntt_run_batch inverse                      P = f Z
+//   4. k_recover_scale<0>, ntt_run_batch forward  P_t g^t -> P(g w^i)
 //   5. k_recover_scale<1>                         / z(s w^(l (i mod m)))  -> f(g w^i)
-//   6. ntt_run inverse, k_recover_scale<2>        g^-t -> the coefficients of f; a word of flags ORs "a coefficient from degree_bound on is not zero"
-//   7. ntt_run forward                            when evaluations are asked for
+//   6. ntt_run_batch inverse, k_recover_scale<2>  g^-t -> the coefficients of f; a word of flags ORs "a coefficient from degree_bound on is not zero"
+//   7. ntt_run_batch forward                      when evaluations are asked for
+// ONE set of kernels serves both entries.  A call works through its blobs in groups (host_recover.h: RecoverBatchPlan); inside a group every
+// stage above is one launch: scatter, the scale passes and the transforms take the blob as grid.y (one flag word per blob), the vanishing
+// values take the PATTERN -- a distinct missing set of the group -- as a grid dimension, with one missing list and one zdom / zsinv / partial
+// region per pattern, and blob b reads the item map of its index row and the values of pattern_of[b].  The split of M aims all patterns
+// together at RECOVER_TARGET_GROUPS workgroups (recover_vanish_split).  The single call is the group of one blob, one index row, one pattern:
+// the same launches with grid.y = grid.z = 1 as before the batch existed, one small upload instead of two.  Per group: one upload of the values,
+// one of item maps + patterns + missing lists, one download of the rows, one of the flags, one synchronisation.  With one index row for all
+// blobs the later groups of a call reuse the first group's upload and vanishing values.  Rows shorter than n (coefficients, out_len < n) are
+// compacted by k_recover_scale<2> into the transforms' scratch, dead by then, so the download stays one contiguous copy (a strided 2-D copy
+// from the work rows was the alternative; not measured).
 // Shapes chosen:
 //   * the vanishing values are DIRECT products, 2 m |M| field products (no coefficient form of z, no product tree): one lane per output
 //     point keeps a running product over tiles of 256 roots, staged in LDS as 9 limb planes (every lane reads the same root: an LDS
 //     broadcast).  The roots w_n^(l k) come from the forward tables of the n-point domain (ntt_get_tables).  2 m / 256 workgroups do not
-//     fill the device below m = 2^17, so M is split across blockIdx.y into up to RC_TARGET_GROUPS workgroups in all and the fold multiplies
+//     fill the device below m = 2^17, so M is split across blockIdx.y into up to RECOVER_TARGET_GROUPS workgroups in all and the fold multiplies
 //     the partial products: a field product, the same element whatever the split, and canonical words leave the call.
 //   * the m divisors are inverted once: Montgomery's trick per workgroup of 256 (product tree in LDS, one fe_inverse_safegcd: lds_tree_invert).
 //   * g^t and g^-t are factored like the twiddle tables, 2^10 + n / 2^10 entries each (one product per element from 2^10 on), kept per context.
 //   * values stay in the wire residue class a 2^256 between the kernels (the factors are internal Montgomery), as in ntt.hip; every kernel
 //     writes canonical words, so equal inputs give equal bits.
-// Lazy-reduction bounds are written at each site; the boundcheck build counts violations (tests/test_gpu_recover.py).
+// Lazy-reduction bounds are written at each site; the boundcheck build counts violations (tests/test_gpu_recover.py, tests/test_gpu_recover_batch.py).
 // Not tried: the scale passes fused into the first load / last store of the transforms next to them, two running products per lane
-// (fe_mul2), a product tree for m > 2^16, the complement form z = (Y^m - 1) / prod_present.  Measured figures: profiles/recover.md.
+// (fe_mul2), a product tree for m > 2^16, the complement form z = (Y^m - 1) / prod_present, pinned staging, one group's copies behind the next group's kernels.  Measured figures: profiles/recover.md,
+// profiles/recover_batch.md.
 #include "poly_common.h"
 #include "fe_invert.h"
 
@@ -33,11 +44,11 @@
 
 namespace kzg {
 
-constexpr uint32_t RC_THREADS = 256;
-constexpr uint32_t RC_TILE = 256;                  // roots per LDS tile: one per lane to stage
+constexpr uint32_t RC_THREADS = RECOVER_THREADS;   // 256 (host_recover.h: the workspace of a group depends on the geometry)
+constexpr uint32_t RC_TILE = RECOVER_TILE;         // roots per LDS tile: one per lane to stage
 constexpr int RC_LO_BITS = 10;                     // g^t = glo[t & 1023] ghi[t >> 10]
 constexpr uint32_t RC_LO_LEN = 1u << RC_LO_BITS;
-constexpr uint32_t RC_TARGET_GROUPS = 1024;        // workgroups of k_recover_vanish in all: four waves per SIMD on 256 CUs
+static_assert(NL == RECOVER_LIMBS && RC_TILE == RC_THREADS, "host_recover.h sizes the limb planes; one lane stages one root");
 
 struct RcPow { const int32_t* lo; const int32_t* hi; uint32_t hi_len; };
 
@@ -47,13 +58,17 @@ __device__ __forceinline__ void rc_load_words(Fr& v, const uint4* __restrict__ p
     const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
     fe_unpack(v, w);
 }
-// v normalised in (-m, 2m) -> canonical words
-__device__ __forceinline__ void rc_store_canon(uint4* __restrict__ p, size_t i, Fr& v) {
-    fe_canon(v);
+// v canonical -> its words
+__device__ __forceinline__ void rc_store_words(uint4* __restrict__ p, size_t i, const Fr& v) {
     uint32_t o[8];
     fe_pack(o, v);
     p[2 * i] = make_uint4(o[0], o[1], o[2], o[3]);
     p[2 * i + 1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+// v normalised in (-m, 2m) -> canonical words
+__device__ __forceinline__ void rc_store_canon(uint4* __restrict__ p, size_t i, Fr& v) {
+    fe_canon(v);
+    rc_store_words(p, i, v);
 }
 // g^(+-t), t < 2^10 hi_len, from the factored table: in (-m, 2m), normalised
 __device__ __forceinline__ void rc_gpow(Fr& w, const RcPow& t, uint32_t e) {
@@ -89,20 +104,22 @@ k_recover_gpow_table(int32_t* __restrict__ planes, uint32_t len, uint32_t step, 
 
 // ---- 1. vanishing values ---------------------------------------------------------------------------------------------------------------
 struct RcVanishArgs {
-    const uint32_t* missing;    // |M| coset indices < m, ascending
+    const uint32_t* missing;    // gridDim.z patterns of |M| coset indices < m, each ascending
     uint32_t n_missing, per_split;
     uint32_t m;
     int log_l;
     NttTables tb;               // forward tables of the n-point domain
     RcPow gp;                   // g^t
-    int32_t* partial;           // gridDim.y rows of 9 planes of 2 m words
+    int32_t* partial;           // per pattern: gridDim.y rows of 9 planes of 2 m words
 };
-// lane p < 2 m of row blockIdx.y: prod over the row's slice of M of (x_p - w^(l k)), x_p = w^(l p) (p < m) or g^l w^(l (p - m)).  An empty
-// slice (M empty) gives 1.
+// lane p < 2 m of row blockIdx.y of pattern blockIdx.z: prod over the row's slice of M of (x_p - w^(l k)), x_p = w^(l p) (p < m) or
+// g^l w^(l (p - m)).  An empty slice (M empty) gives 1.
 __global__ void __launch_bounds__(RC_THREADS)
 k_recover_vanish(RcVanishArgs a) {
     __shared__ int32_t roots[NL * RC_TILE];
     const uint32_t tid = threadIdx.x, p = blockIdx.x * RC_THREADS + tid, two_m = 2 * a.m;
+    const uint32_t* __restrict__ missing = a.missing + (size_t)blockIdx.z * a.n_missing;
+    int32_t* __restrict__ partial = a.partial + (size_t)blockIdx.z * NL * gridDim.y * two_m;
     const uint32_t first = blockIdx.y * a.per_split, last = min(a.n_missing, first + a.per_split);
     Fr x, acc;
     fe_set_one(acc);
@@ -121,7 +138,7 @@ k_recover_vanish(RcVanishArgs a) {
         const uint32_t cnt = min(RC_TILE, last - base);
         if (tid < cnt) {
             Fr w;
-            domain_elem(w, a.tb, a.missing[base + tid] << a.log_l);
+            domain_elem(w, a.tb, missing[base + tid] << a.log_l);
             pl_store(roots, RC_TILE, tid, w);
         }
         __syncthreads();
@@ -134,16 +151,19 @@ k_recover_vanish(RcVanishArgs a) {
         }
         __syncthreads();                                             // the next tile overwrites the roots
     }
-    if (p < two_m) pl_store(a.partial, (size_t)gridDim.y * two_m, (size_t)blockIdx.y * two_m + p, acc);
+    if (p < two_m) pl_store(partial, (size_t)gridDim.y * two_m, (size_t)blockIdx.y * two_m + p, acc);
 }
 
-// lane p < 2 m: the product of its `rows` partial products; p < m: stored (zdom[p] = z(w^(l p))); p >= m: inverted, Montgomery's trick per
+// lane p < 2 m of pattern blockIdx.y: the product of its `rows` partial products; p < m: stored (zdom[p] = z(w^(l p))); p >= m: inverted, Montgomery's trick per
 // workgroup (lds_tree_invert), zsinv[p - m] = 1 / z(s w^(l (p - m))).  No divisor is zero.
 __global__ void __launch_bounds__(RC_THREADS)
 k_recover_vanish_fold(const int32_t* __restrict__ partial, uint32_t rows, uint32_t m, int32_t* __restrict__ zdom, int32_t* __restrict__ zsinv) {
     __shared__ int32_t tree[NL * 2 * RC_THREADS];                    // heap order: root 1, leaves RC_THREADS + t
     constexpr uint32_t Lf = RC_THREADS, S = 2 * RC_THREADS;
     const uint32_t t = threadIdx.x, p = blockIdx.x * RC_THREADS + t, two_m = 2 * m;
+    partial += (size_t)blockIdx.y * NL * rows * two_m;
+    zdom += (size_t)blockIdx.y * NL * m;
+    zsinv += (size_t)blockIdx.y * NL * m;
     Fr v;
     fe_set_one(v);
     if (p < two_m) {
@@ -166,11 +186,17 @@ k_recover_vanish_fold(const int32_t* __restrict__ partial, uint32_t rows, uint32
 }
 
 // ---- 2. D_i = ys z(w^(l k)) on a present coset k = i mod m (entry j = i / m of its item), 0 on a missing one ------------------------------
+// Blob blockIdx.y: its count l values, its row of n work values, the item map of its index row (item_stride = 0: one row for all) and the
+// zdom of its pattern.
 __global__ void __launch_bounds__(RC_THREADS)
-k_recover_scatter(const uint4* __restrict__ ys, const uint32_t* __restrict__ item_of, uint32_t n, uint32_t m, int log_m, int log_l,
-                  const int32_t* __restrict__ zdom, uint4* __restrict__ data) {
-    const uint32_t i = blockIdx.x * RC_THREADS + threadIdx.x;
+k_recover_scatter(const uint4* __restrict__ ys, const uint32_t* __restrict__ item_of, uint32_t item_stride, const uint32_t* __restrict__ pattern_of,
+                  uint32_t count, uint32_t n, uint32_t m, int log_m, int log_l, const int32_t* __restrict__ zdom, uint4* __restrict__ data) {
+    const uint32_t i = blockIdx.x * RC_THREADS + threadIdx.x, b = blockIdx.y;
     if (i >= n) return;
+    ys += 2 * ((size_t)b * count << log_l);
+    item_of += (size_t)b * item_stride;
+    zdom += (size_t)pattern_of[b] * NL * m;                          // < patterns of the group by construction (host_recover.h)
+    data += 2 * (size_t)b * n;
     const uint32_t k = i & (m - 1), j = i >> log_m, item = item_of[k];
     Fr v;
     fe_set_zero(v);
@@ -183,24 +209,31 @@ k_recover_scatter(const uint4* __restrict__ ys, const uint32_t* __restrict__ ite
     rc_store_canon(data, i, v);
 }
 
-// ---- 4, 5, 6: the pointwise passes.  MODE 0: entry t times g^t; 1: entry i times zsinv[i mod m]; 2: entry t times g^-t, and the flag --------
+// ---- 4, 5, 6: the pointwise passes on row blockIdx.y.  MODE 0: entry t times g^t; 1: entry i times zsinv[i mod m] of the blob's pattern;
+// 2: entry t times g^-t, and the blob's flag.  MODE 2 writes the first out_len entries of the row to row blockIdx.y of `out`, out_len apart:
+// out = data and out_len = n is in place, out_len < n compacts the rows into another buffer for one contiguous download (the entries
+// from out_len on are only tested).
 template <int MODE>
 __global__ void __launch_bounds__(RC_THREADS)
-k_recover_scale(uint4* __restrict__ data, uint32_t n, RcPow gp, const int32_t* __restrict__ zsinv, uint32_t m, uint32_t degree_bound,
-                uint32_t* __restrict__ flag) {
-    const uint32_t i = blockIdx.x * RC_THREADS + threadIdx.x;
+k_recover_scale(uint4* data, uint32_t n, RcPow gp, const int32_t* __restrict__ zsinv, const uint32_t* __restrict__ pattern_of, uint32_t m,
+                uint32_t degree_bound, uint32_t* __restrict__ flag, uint4* out, uint32_t out_len) {
+    const uint32_t i = blockIdx.x * RC_THREADS + threadIdx.x, b = blockIdx.y;
     bool nonzero = false;
     if (i < n) {
         Fr v, f;
-        rc_load_words(v, data, i);                                   // < 5.3 m
-        if (MODE == 1) pl_load(f, zsinv, m, i & (m - 1));
+        rc_load_words(v, data + 2 * (size_t)b * n, i);               // < 5.3 m
+        if (MODE == 1) pl_load(f, zsinv + (size_t)pattern_of[b] * NL * m, m, i & (m - 1));
         else rc_gpow(f, gp, i);
         fe_mul(v, v, f);                                             // |v f| < 5.3 m * 2 m
-        rc_store_canon(data, i, v);
-        if (MODE == 2) nonzero = i >= degree_bound && !fe_is_literal_zero(v);
+        if (MODE != 2) rc_store_canon(data + 2 * (size_t)b * n, i, v);
+        else {
+            fe_canon(v);                                             // (-m, 2m) -> canonical: the flag tests the words whether or not they are stored
+            if (i < out_len) rc_store_words(out + 2 * (size_t)b * out_len, i, v);
+            nonzero = i >= degree_bound && !fe_is_literal_zero(v);
+        }
     }
     if (MODE == 2) {
-        if (__syncthreads_or(nonzero) && threadIdx.x == 0) *flag = 1u;   // every writer stores the same word
+        if (__syncthreads_or(nonzero) && threadIdx.x == 0) flag[b] = 1u;   // every writer stores the same word
     }
 }
 
@@ -229,64 +262,86 @@ static int32_t recover_gpow_tables(kzg_ctx* ctx, int log_n, RcPow* fwd, RcPow* i
     return KZG_OK;
 }
 
-int32_t recover_run(kzg_ctx* ctx, const RecoverPlan& plan, const uint64_t* ys, bool eval_form, uint64_t* out_poly, int32_t* consistent) {
-    RoctxRange range("kzg:recover_from_cosets");
+// The blobs [b0, b0 + g) of the plan: one launch per stage, the blob as grid.y, the pattern as a grid dimension of the vanishing values.
+// `fresh`: upload indices and patterns and compute the vanishing values (false: those of the previous group serve, one index row).
+static int32_t recover_run_group(kzg_ctx* ctx, const RecoverBatchPlan& plan, size_t b0, size_t g, bool fresh, const NttTables& tb, const RcPow& gp,
+                                 const RcPow& gpi, const uint64_t* ys, uint64_t* out_polys, int32_t* consistent) {
     hipStream_t st = ctx->stream;
-    const size_t n = plan.n, l = plan.l, m = plan.m, count = plan.count, n_missing = plan.missing.size();
+    const size_t n = plan.n, l = plan.l, m = plan.m, count = plan.count, out_len = plan.out_len;
+    uint32_t* small = ctx->rc[1].as<uint32_t>();
+    int32_t* zdom = ctx->rc[1].as<int32_t>() + plan.w_zdom;
+    int32_t* zsinv = ctx->rc[1].as<int32_t>() + plan.w_zsinv;
+    uint4* staged = ctx->rc_ntt.data.as<uint4>();                    // the uploaded values now, the transforms' scratch afterwards, compacted rows at the end
+    uint4* data = ctx->rc[0].as<uint4>();
+    std::vector<uint32_t> stage;                                     // alive until the synchronisation below
+    std::vector<uint32_t> flags(g, 0);
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(staged, ys + b0 * count * l * 4, g * count * l * 32, hipMemcpyHostToDevice, st));
+    KZG_HIP_TRY(ctx, hipMemsetAsync(small + plan.w_flag, 0, g * 4, st));
+    if (fresh) {
+        size_t words = 0;
+        const size_t P = recover_batch_stage(plan, b0, g, &stage, &words);
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(small, stage.data(), words * 4, hipMemcpyHostToDevice, st));
+        // vanishing values: 2 m / 256 column groups x `splits` slices of M x P patterns
+        const RecoverSplit sp = recover_vanish_split(m, plan.n_missing, P);
+        RcVanishArgs va;
+        va.missing = small + plan.w_miss; va.n_missing = (uint32_t)plan.n_missing; va.per_split = sp.per_split; va.m = (uint32_t)m; va.log_l = plan.log_l;
+        va.tb = tb; va.gp = gp; va.partial = ctx->rc[1].as<int32_t>() + plan.w_part;
+        hipLaunchKernelGGL(k_recover_vanish, dim3(sp.xgroups, sp.splits, (unsigned)P), dim3(RC_THREADS), 0, st, va);
+        hipLaunchKernelGGL(k_recover_vanish_fold, dim3(sp.xgroups, (unsigned)P), dim3(RC_THREADS), 0, st, va.partial, sp.splits, (uint32_t)m, zdom, zsinv);
+    }
+    const dim3 ngrid((unsigned)((n + RC_THREADS - 1) / RC_THREADS), (unsigned)g);
+    const uint32_t* pattern_of = small + plan.w_pat;
+    hipLaunchKernelGGL(k_recover_scatter, ngrid, dim3(RC_THREADS), 0, st, staged, small + plan.w_item, plan.index_rows == 1 ? 0u : (uint32_t)m, pattern_of,
+                       (uint32_t)count, (uint32_t)n, (uint32_t)m, plan.log_m, plan.log_l, zdom, data);
+    KZG_HIP_TRY(ctx, hipGetLastError());
+    int32_t rc = ntt_run_batch(ctx, data, n, g, true, st, &ctx->rc_ntt);     // f Z
+    if (rc != KZG_OK) return rc;
+    hipLaunchKernelGGL(k_recover_scale<0>, ngrid, dim3(RC_THREADS), 0, st, data, (uint32_t)n, gp, nullptr, nullptr, (uint32_t)m, 0u, nullptr, nullptr, 0u);
+    rc = ntt_run_batch(ctx, data, n, g, false, st, &ctx->rc_ntt);            // (f Z)(g w^i)
+    if (rc != KZG_OK) return rc;
+    hipLaunchKernelGGL(k_recover_scale<1>, ngrid, dim3(RC_THREADS), 0, st, data, (uint32_t)n, gp, zsinv, pattern_of, (uint32_t)m, 0u, nullptr, nullptr, 0u);
+    rc = ntt_run_batch(ctx, data, n, g, true, st, &ctx->rc_ntt);             // f(g X)
+    if (rc != KZG_OK) return rc;
+    // the rows leave from `data` in place, or, shorter than n, compacted into the transforms' scratch (dead after the last transform): one contiguous download
+    uint4* rows = out_len < n ? staged : data;
+    hipLaunchKernelGGL(k_recover_scale<2>, ngrid, dim3(RC_THREADS), 0, st, data, (uint32_t)n, gpi, nullptr, nullptr, (uint32_t)m, (uint32_t)plan.degree_bound,
+                       small + plan.w_flag, rows, (uint32_t)out_len);
+    KZG_HIP_TRY(ctx, hipGetLastError());
+    if (plan.eval_form) {                                            // out_len = n
+        rc = ntt_run_batch(ctx, data, n, g, false, st, &ctx->rc_ntt);
+        if (rc != KZG_OK) return rc;
+    }
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(out_polys + b0 * out_len * 4, rows, g * out_len * 32, hipMemcpyDeviceToHost, st));
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(flags.data(), small + plan.w_flag, g * 4, hipMemcpyDeviceToHost, st));
+    KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (consistent)
+        for (size_t i = 0; i < g; ++i) consistent[b0 + i] = flags[i] ? 0 : 1;
+    return KZG_OK;
+}
+
+int32_t recover_run_batch(kzg_ctx* ctx, const RecoverBatchPlan& plan, const uint64_t* ys, uint64_t* out_polys, int32_t* consistent) {
+    RoctxRange range(plan.blobs == 1 ? "kzg:recover_from_cosets" : "kzg:recover_from_cosets_batch");
     NttTables tb;
     int32_t rc = ntt_get_tables(ctx, plan.log_n, false, &tb);
     if (rc != KZG_OK) return rc;
     RcPow gp, gpi;
     rc = recover_gpow_tables(ctx, plan.log_n, &gp, &gpi);
     if (rc != KZG_OK) return rc;
-    // vanishing values: 2 m / 256 column groups x `splits` slices of M
-    const uint32_t xgroups = (uint32_t)((2 * m + RC_THREADS - 1) / RC_THREADS);
-    const uint32_t tiles = (uint32_t)((n_missing + RC_TILE - 1) / RC_TILE);
-    const uint32_t splits = std::max(1u, std::min(RC_TARGET_GROUPS / xgroups, tiles));
-    const uint32_t per_split = std::max(1u, (tiles + splits - 1) / splits) * RC_TILE;
-    // rc[1]: item_of m | missing |M| (u32) | flag | zdom 9 m | zsinv 9 m | partial splits x 9 x 2 m (words)
-    const size_t w_item = 0, w_miss = w_item + m, w_flag = w_miss + n_missing, w_zdom = (w_flag + 1 + 3) & ~(size_t)3, w_zsinv = w_zdom + NL * m,
-                 w_part = w_zsinv + NL * m, w_end = w_part + (size_t)splits * NL * 2 * m;
-    KZG_HIP_TRY(ctx, ctx->rc[0].reserve(n * 32));
-    KZG_HIP_TRY(ctx, ctx->rc[1].reserve(w_end * 4));
-    KZG_HIP_TRY(ctx, ctx->rc_ntt.data.reserve(n * 32));              // the uploaded values now, the transforms' scratch afterwards
-    uint32_t* small = ctx->rc[1].as<uint32_t>();
-    int32_t* zdom = ctx->rc[1].as<int32_t>() + w_zdom;
-    int32_t* zsinv = ctx->rc[1].as<int32_t>() + w_zsinv;
-    uint4* d_ys = ctx->rc_ntt.data.as<uint4>();
-    uint4* data = ctx->rc[0].as<uint4>();
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(d_ys, ys, count * l * 32, hipMemcpyHostToDevice, st));
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(small + w_item, plan.item_of.data(), m * 4, hipMemcpyHostToDevice, st));
-    if (n_missing) KZG_HIP_TRY(ctx, hipMemcpyAsync(small + w_miss, plan.missing.data(), n_missing * 4, hipMemcpyHostToDevice, st));
-    KZG_HIP_TRY(ctx, hipMemsetAsync(small + w_flag, 0, 4, st));
-    RcVanishArgs va;
-    va.missing = small + w_miss; va.n_missing = (uint32_t)n_missing; va.per_split = per_split; va.m = (uint32_t)m; va.log_l = plan.log_l;
-    va.tb = tb; va.gp = gp; va.partial = ctx->rc[1].as<int32_t>() + w_part;
-    hipLaunchKernelGGL(k_recover_vanish, dim3(xgroups, splits), dim3(RC_THREADS), 0, st, va);
-    hipLaunchKernelGGL(k_recover_vanish_fold, dim3(xgroups), dim3(RC_THREADS), 0, st, va.partial, splits, (uint32_t)m, zdom, zsinv);
-    const dim3 ngrid((unsigned)((n + RC_THREADS - 1) / RC_THREADS));
-    hipLaunchKernelGGL(k_recover_scatter, ngrid, dim3(RC_THREADS), 0, st, d_ys, small + w_item, (uint32_t)n, (uint32_t)m, plan.log_m, plan.log_l, zdom, data);
-    KZG_HIP_TRY(ctx, hipGetLastError());
-    rc = ntt_run(ctx, data, n, true, st, &ctx->rc_ntt);              // f Z
-    if (rc != KZG_OK) return rc;
-    hipLaunchKernelGGL(k_recover_scale<0>, ngrid, dim3(RC_THREADS), 0, st, data, (uint32_t)n, gp, nullptr, (uint32_t)m, 0u, nullptr);
-    rc = ntt_run(ctx, data, n, false, st, &ctx->rc_ntt);             // (f Z)(g w^i)
-    if (rc != KZG_OK) return rc;
-    hipLaunchKernelGGL(k_recover_scale<1>, ngrid, dim3(RC_THREADS), 0, st, data, (uint32_t)n, gp, zsinv, (uint32_t)m, 0u, nullptr);
-    rc = ntt_run(ctx, data, n, true, st, &ctx->rc_ntt);              // f(g X)
-    if (rc != KZG_OK) return rc;
-    hipLaunchKernelGGL(k_recover_scale<2>, ngrid, dim3(RC_THREADS), 0, st, data, (uint32_t)n, gpi, nullptr, (uint32_t)m, (uint32_t)plan.degree_bound, small + w_flag);
-    KZG_HIP_TRY(ctx, hipGetLastError());
-    if (eval_form) {
-        rc = ntt_run(ctx, data, n, false, st, &ctx->rc_ntt);
+    const size_t cap = plan.groups.group;                            // every group works in the buffers of a full one
+    KZG_HIP_TRY(ctx, ctx->rc[0].reserve(cap * plan.n * 32));
+    KZG_HIP_TRY(ctx, ctx->rc[1].reserve(plan.w_end * 4));
+    KZG_HIP_TRY(ctx, ctx->rc_ntt.data.reserve(cap * plan.n * 32));   // >= the staged values (count l <= n), the transforms' `data`, the compacted rows
+    for (size_t b0 = 0; b0 < plan.blobs; b0 += cap) {
+        const size_t g = std::min(cap, plan.blobs - b0);
+        // with one index row every group has the same item map, pattern and vanishing values, at the same place
+        rc = recover_run_group(ctx, plan, b0, g, b0 == 0 || plan.index_rows != 1, tb, gp, gpi, ys, out_polys, consistent);
         if (rc != KZG_OK) return rc;
     }
-    uint32_t flag = 0;
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(out_poly, data, n * 32, hipMemcpyDeviceToHost, st));
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(&flag, small + w_flag, 4, hipMemcpyDeviceToHost, st));
-    KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    *consistent = flag ? 0 : 1;
     return KZG_OK;
+}
+
+int32_t recover_run(kzg_ctx* ctx, const RecoverPlan& plan, const uint64_t* ys, bool eval_form, uint64_t* out_poly, int32_t* consistent) {
+    return recover_run_batch(ctx, recover_batch_of_one(plan, eval_form), ys, out_poly, consistent);
 }
 
 }  // namespace kzg

@@ -378,6 +378,20 @@ def encode_batch_info(d: int, n: int, chunk_len: int, count: int, values: bool =
             "batched": bool(info.batched), "inverse": transform(info.inverse), "forward": transform(info.forward)}
 
 
+def recover_batch_info(blobs: int, count: int, n: int, chunk_len: int, out_len: int = 0, group_bytes: int = 0) -> dict:
+    """How `KZG.recover_from_cosets_batch` groups `blobs` blobs of `count` cosets of shape (n, chunk_len) under a workspace budget of
+    `group_bytes` (0: the default) -- `kzg_recover_batch_info`, a pure query: blobs per group, groups, workspace bytes of a full group
+    (sized for one pattern per blob) and of one blob."""
+    info = _lib.RecoverBatchInfo()
+    rc = _lib.load().kzg_recover_batch_info(blobs, count, n, chunk_len, out_len, group_bytes, C.byref(info))
+    if rc == _lib.ERR_NOT_POWER_OF_TWO:
+        raise GenericError("length provided is not a power of 2")
+    if rc != _lib.OK:
+        raise GenericError(_lib.status_message(rc))
+    return {"blobs_per_group": int(info.blobs_per_group), "groups": int(info.groups), "group_bytes": int(info.group_bytes),
+            "blob_bytes": int(info.blob_bytes)}
+
+
 def g2_batch_info(n: int, nb: int, count: int, max_blobs: int = 0) -> dict:
     """What a batched G2 call (`KZG.commit_with_length_proof_batch`: nb = 2, `G2SRS.msm_batch`: nb = 1) does with `count` blobs of n
     scalars under a cap of `max_blobs` blobs per group (0: none) -- `kzg_msm_g2_batch_info`, a pure query: blobs per group, groups,

@@ -610,6 +610,52 @@ class KZG:
             raise GenericError("the cosets are not the values of a polynomial below the degree bound")
         return PolynomialEvalForm(out) if eval_form else PolynomialCoeffForm(out)
 
+    def recover_from_cosets_batch(self, coset_indices, ys, n: int, degree_bound=None, eval_form: bool = True, out_len=None):
+        """`recover_from_cosets` for B blobs of one shape in one call (`kzg_recover_from_cosets_batch`).  `ys` is a (B, count, chunk_len, 4)
+        array; `coset_indices` has the shape (count,), the cosets every blob has, or (B, count), row b those of blob b.  Returns
+        (array (B, out_len, 4), consistent): row b is bit-identical to `recover_from_cosets` of blob b, evaluations or with
+        eval_form=False coefficients, and `consistent` is a bool array (B,).  Unlike the single call this one does NOT raise on values that
+        are not those of a polynomial below `degree_bound`: consistent[b] is False and row b is still the interpolant.  `out_len` (None
+        or 0: n; coefficients only) keeps the first out_len >= degree bound coefficients of each blob.  The library works through the
+        blobs in groups whose device workspace fits `Context.set_recover_group_bytes` (`helpers.recover_batch_info`)."""
+        ys = np.ascontiguousarray(ys, dtype=np.uint64)
+        idx = np.ascontiguousarray(coset_indices, dtype=np.uint64)
+        n = int(n)
+        if ys.ndim != 4 or ys.shape[3] != 4 or ys.shape[0] == 0:
+            raise GenericError("ys must have the shape (B, count, chunk_len, 4) with B >= 1")
+        blobs, count, chunk_len = int(ys.shape[0]), int(ys.shape[1]), int(ys.shape[2])
+        if idx.shape not in ((count,), (blobs, count)):
+            raise GenericError("coset indices must have the shape (count,) or (B, count)")
+        index_rows = 1 if idx.ndim == 1 else blobs
+        if n < 2 or (n & (n - 1)) != 0:
+            raise FFTError("length provided is not a power of 2")
+        if chunk_len <= 0 or (chunk_len & (chunk_len - 1)) != 0:
+            raise GenericError("chunk length is not a power of 2")
+        if chunk_len > n // 2:
+            raise GenericError("chunk length exceeds half the polynomial length")
+        m = n // chunk_len
+        if count == 0 or count > m:
+            raise GenericError("the number of cosets must be between 1 and n / chunk length")
+        bound = count * chunk_len if not degree_bound else int(degree_bound)               # None or 0: the default, as in the C-ABI
+        if bound < 0 or bound > count * chunk_len:
+            raise GenericError("too few cosets for the degree bound")
+        rows = n if not out_len else int(out_len)
+        if rows != n and (eval_form or not bound <= rows <= n):
+            raise GenericError("out_len is for coefficients, between the degree bound and n")
+        ctx = self._ctx()
+        out = np.zeros((blobs, rows, 4), dtype=np.uint64)
+        consistent = np.zeros(blobs, dtype=np.int32)
+        rc = _lib.load().kzg_recover_from_cosets_batch(ctx.handle, _lib.ptr(ys), _lib.ptr(idx), index_rows, blobs, count, n, chunk_len, bound,
+                                                       1 if eval_form else 0, rows, _lib.ptr(out), consistent.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc == _lib.ERR_DOMAIN:
+            raise FFTError("Could not perform IFFT due to domain consturction error")
+        if rc == _lib.ERR_INVALID_ARG:                                                        # an index >= m, or the same coset twice in a row
+            raise GenericError("coset indices must be distinct and below n / chunk length")
+        ctx.check_device(rc)
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+        return out, consistent.astype(bool)
+
     # kzg.rs:237-260
     def compute_quotient_eval_on_domain(self, z_fr, eval_fr, value_fr):
         """sum over the stored roots w^i != z of (f_i - value) w^i / ((z - w^i) z): the quotient's evaluation at the domain point z, on the GPU
