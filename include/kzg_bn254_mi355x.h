@@ -897,14 +897,16 @@ int32_t kzg_commit_with_length_proof_batch(kzg_ctx* ctx, kzg_srs* g1_srs, const 
 /* The most blobs per group of the batched G2 calls on this context; 0 = the planner's choice (same results whatever the value). */
 int32_t kzg_ctx_set_g2_batch_group(kzg_ctx* ctx, uint32_t max_blobs);
 /* What a batched G2 call of `count` blobs of n scalars over nb (1 or 2) base sets would do under max_blobs: a pure query (no context,
- * no device; lanes as planned for a 256-CU device).  The plan fields describe a FULL group.  Errors: out NULL or nb not 1 or 2 ->
- * KZG_ERR_INVALID_ARG; then row 2 of the tables above.  n = 0 or count = 0: no group (all fields 0). */
+ * no device; lanes as planned for a 256-CU device).  The plan fields describe a FULL group.  Single and batched calls share one plan:
+ * a batched = 0 row (no two blobs fit one launch) is that plan for one blob -- above 2^22 scalars for the blob's first 2^22 -- with
+ * both base sets in every launch: 6 launches behind the sort whatever nb, buffers nb times as large.  Errors: out NULL or nb not 1 or
+ * 2 -> KZG_ERR_INVALID_ARG; then row 2 of the tables above.  n = 0 or count = 0: no group (all fields 0). */
 typedef struct kzg_g2_batch_info {
     uint64_t blobs_per_group;   /* the last group of a call may hold fewer */
     uint64_t groups;
     uint64_t entries;           /* sorted entries of a full group at most: blobs_per_group x W x n */
     uint64_t workspace_bytes;   /* device buffers of a full group, the sort's included */
-    uint32_t batched;           /* 0: the shape goes blob by blob through the single call's path (groups of one, that path's own plan) */
+    uint32_t batched;           /* 0: no two blobs fit one launch, or a blob is above one launch: groups of one */
     uint32_t c, W;              /* window bits and windows: the single call's */
     uint32_t G;                 /* buckets of one base set: blobs_per_group x W x 2^(c-1) */
     uint32_t nl, seg;           /* accumulate lanes per base set, sorted entries per lane at most */

@@ -309,21 +309,15 @@ int32_t kzg_msm_g2_batch_info(size_t n, uint32_t nb, size_t count, uint32_t max_
     *out = kzg_g2_batch_info{};
     if (n == 0 || count == 0) return KZG_OK;
     const uint32_t wave_slots = 256 * 4 * G2_ACC_WAVES;                  // a 256-CU device (what kzg_ctx_create finds on an MI355X)
-    const uint32_t group = g2_batch_group(n, nb, count, max_blobs);
-    out->batched = group ? 1 : 0;
-    out->blobs_per_group = group ? group : 1;
+    const bool batched = g2_batch_shares(n, nb);
+    out->batched = batched ? 1 : 0;
+    out->blobs_per_group = batched ? g2_batch_group(n, nb, count, max_blobs) : 1;
     out->groups = (count + out->blobs_per_group - 1) / out->blobs_per_group;
-    if (group) {
-        const G2BatchPlan p = g2_make_batch_plan(n, nb, group, wave_slots);
-        out->entries = p.entries(); out->workspace_bytes = p.workspace_bytes;
-        out->c = (uint32_t)p.c; out->W = (uint32_t)p.W; out->G = p.G; out->nl = p.nl; out->seg = p.seg;
-        out->sort_small = p.sort.sort_small ? 1 : 0; out->scan1 = p.G <= SCAN1_MAX ? 1 : 0; out->launches = p.launches;
-    } else {                                                             // one launch (of the first G2MSM_MAX_LAUNCH scalars) of g2_msm_run
-        const G2Plan p = g2_make_plan(std::min<size_t>(n, G2MSM_MAX_LAUNCH), nb, wave_slots);
-        out->entries = p.entries(); out->workspace_bytes = p.workspace_bytes;
-        out->c = (uint32_t)p.c; out->W = (uint32_t)p.W; out->G = p.G; out->nl = p.nl; out->seg = p.seg;
-        out->sort_small = p.sort.sort_small ? 1 : 0; out->scan1 = p.G <= SCAN1_MAX ? 1 : 0; out->launches = p.launches;
-    }
+    // the first launch: above the launch cap, of the first G2MSM_MAX_LAUNCH scalars of one blob
+    const G2Plan p = g2_make_plan(std::min<size_t>(n, G2MSM_MAX_LAUNCH), nb, out->blobs_per_group, wave_slots);
+    out->entries = p.entries(); out->workspace_bytes = p.workspace_bytes;
+    out->c = (uint32_t)p.c; out->W = (uint32_t)p.W; out->G = p.G; out->nl = p.nl; out->seg = p.seg;
+    out->sort_small = p.sort.sort_small ? 1 : 0; out->scan1 = p.G <= SCAN1_MAX ? 1 : 0; out->launches = p.launches;
     return KZG_OK;
 }
 

@@ -281,12 +281,12 @@ int32_t srs_download(kzg_ctx* ctx, const uint4* d_points, size_t n, uint64_t* ou
 int32_t fr_powers_canonical(kzg_ctx* ctx, const uint64_t tau_mont[4], uint64_t first_power, size_t n, const uint4** d_out);
 
 // G2 (g2msm.hip).  Called under ctx->mu with the device set; every one is synchronised on return.
-// the MSM of ONE scalar set (device, wire form) over nb <= 2 base sets (device format, 8 uint4 per point): digits and sort once, accumulate and
-// reduce per set; out: nb x 16 u64 affine wire points, out_inf: nb flags (may be null)
+// the MSM of ONE scalar set (device, wire form) over nb <= 2 base sets (device format, 8 uint4 per point): g2_msm_batch_run with count = 1;
+// out: nb x 16 u64 affine wire points, out_inf: nb flags (may be null)
 int32_t g2_msm_run(kzg_ctx* ctx, const uint4* const* d_points, uint32_t nb, const void* d_scalars, size_t n, uint64_t* out_g2, uint8_t* out_inf);
 // `count` scalar sets of n scalars each (device, wire form, one after the other), ALL over the same nb <= 2 base sets of n points: groups of
 // blobs planned by g2_batch_group (g2msm_plan.h; ctx->g2_batch_group caps them), one sort and one launch sequence per group for every
-// blob and base set in it.  out_g2[s]: count x 16 u64 affine wire points of base set s, out_inf[s]: count flags (the array or an entry may be null)
+// blob and base set in it; a blob above G2MSM_MAX_LAUNCH scalars alone, in parts.  out_g2[s]: count x 16 u64 affine wire points of base set s, out_inf[s]: count flags (the array or an entry may be null)
 int32_t g2_msm_batch_run(kzg_ctx* ctx, const uint4* const* d_points, uint32_t nb, const void* d_scalars, size_t n, size_t count, uint64_t* const* out_g2,
                          uint8_t* const* out_inf);
 // n wire points of the host -> device format at d_out, every point checked on the twist (or the identity); *bad = index of the first one off it, or -1

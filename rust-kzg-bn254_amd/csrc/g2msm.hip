@@ -9,7 +9,7 @@
 //   k_g2_red_*               per window sum_k (k + 1) B_k by chunked running sums, left as W wire-format XYZZ values
 // The O(W c) Horner doublings and the one inversion run on the host (host_pairing.h).  What a launch does is decided in g2msm_plan.h.
 // Many scalar sets over the SAME bases (the blob headers of one call, g2_msm_batch_run) are one bucket problem per group of blobs: one
-// sort with in-blob indices, k_g2_accumulate_batch and the SETS instantiations of the other kernels with the base set as grid.y.
+// sort with in-blob indices, then every kernel once with the base set as grid.y.  A single MSM is the group of one blob.
 // Everything here is integer VALU work: no MFMA.
 //
 // Register budget (profiles/g2msm.md has the compiler's figures): a G2 accumulator is 8 Fq = 72 limb registers, a gathered point 36, a
@@ -39,7 +39,7 @@ __device__ __noinline__ void g2_flush(const G2Xyzz& acc, bool is_cont, int32_t* 
     else g2_store(head, head_stride, g, acc);
 }
 
-// the lane's work, shared by the two kernels below: head / cont are those of the lane's base set
+// the lane's work: head / cont are those of the lane's base set
 __device__ __forceinline__ void g2_accumulate_lane(const uint4* __restrict__ points, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offs,
                                                    uint32_t G, int32_t* __restrict__ head, size_t head_stride, int32_t* __restrict__ cont, size_t cont_stride) {
     const uint32_t nl = gridDim.x * blockDim.x;
@@ -76,19 +76,13 @@ __device__ __forceinline__ void g2_accumulate_lane(const uint4* __restrict__ poi
     { const G2Xyzz done = acc; g2_flush(done, is_cont, head, head_stride, g, cont, cont_stride, t); }
 }
 
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G2_ACC_WAVES, G2_ACC_WAVES)))
-k_g2_accumulate(const uint4* __restrict__ points, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offs, uint32_t G,
-                int32_t* __restrict__ head, size_t head_stride, int32_t* __restrict__ cont, size_t cont_stride) {
-    g2_accumulate_lane(points, sorted, offs, G, head, head_stride, cont, cont_stride);
-}
-
-// The batched form (g2_msm_batch_run): the buckets are those of every blob of a group (G = blobs W B, entries = in-blob indices), and
-// grid.y = base set.  Every set reads the same `sorted` and `offs`; its partial sums go to head + s G and cont + s nl of buffers whose
-// limb planes are nb G and nb nl values apart (the strides passed in).
+// The buckets are those of every blob of the launch (G = blobs W B, entries = in-blob indices), and grid.y = base set.  Every set reads
+// the same `sorted` and `offs`; its partial sums go to head + s G and cont + s nl of buffers whose limb planes are nb G and nb nl values
+// apart (the strides passed in).
 struct G2BaseSets { const uint4* points[2]; };
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G2_ACC_WAVES, G2_ACC_WAVES)))
-k_g2_accumulate_batch(const G2BaseSets bases, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offs, uint32_t G,
-                      int32_t* __restrict__ head, size_t head_stride, int32_t* __restrict__ cont, size_t cont_stride) {
+k_g2_accumulate(const G2BaseSets bases, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offs, uint32_t G,
+                int32_t* __restrict__ head, size_t head_stride, int32_t* __restrict__ cont, size_t cont_stride) {
     const uint32_t s = blockIdx.y;
     g2_accumulate_lane(bases.points[s], sorted, offs, G, head + (size_t)s * G, head_stride, cont + (size_t)s * (gridDim.x * blockDim.x), cont_stride);
 }
@@ -97,7 +91,7 @@ k_g2_accumulate_batch(const G2BaseSets bases, const uint32_t* __restrict__ sorte
 // 2. lane partials -> bucket sums
 // -------------------------------------------------------------------------------------------------
 // (g2_shfl: curve_g2.h)
-// Bucket g of the G = W * B buckets is stored at a transposed position so that the reduction kernels, where lane t walks chunk t
+// Bucket g of the G buckets is stored at a transposed position so that the reduction kernels, where lane t walks chunk t
 // (buckets t m .. t m + m - 1), read consecutive addresses across lanes.
 __device__ __forceinline__ size_t g2_bucket_pos(uint32_t g, uint32_t m, uint32_t n_chunks) { return (size_t)(g % m) * n_chunks + (g / m); }
 
@@ -110,15 +104,14 @@ __device__ __forceinline__ void g2_partial(G2Xyzz& v, uint32_t g, uint32_t t1, u
 // One lane per bucket.  Buckets of up to G2_NP_SERIAL partials are summed by their lane; heavier ones (skewed or equal scalars: few
 // distinct digits) one after the other by the whole wave: lanes take partials round-robin, then a six-step shuffle tree.  The order of
 // the additions depends on the plan (nl) and the offsets only.
-// SETS (this kernel and the four of section 3; the batched driver): grid.y = base set s, whose values sit s G (head, bucket), s nl (cont)
-// and s n_chunks (chunk arrays) into buffers whose limb planes are nb times as far apart -- the strides passed in.  The windows are those
-// of every blob of the group (G = blobs W B); nothing else differs, and the SETS = false instantiations are the single call's kernels.
-template <bool SETS>
+// This kernel and the four of section 3: grid.y = base set s, whose values sit s G (head, bucket), s nl (cont) and s n_chunks (chunk
+// arrays) into buffers whose limb planes are nb times as far apart -- the strides passed in.  The windows are those of every blob of the
+// launch (G = blobs W B).
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_g2_bucket_fin(const uint32_t* __restrict__ offs, uint32_t G, uint32_t nl, uint32_t m, uint32_t n_chunks,
                 const int32_t* __restrict__ head, size_t head_stride, const int32_t* __restrict__ cont, size_t cont_stride,
                 int32_t* __restrict__ bucket, size_t bucket_stride) {
-    if (SETS) { head += (size_t)blockIdx.y * G; cont += (size_t)blockIdx.y * nl; bucket += (size_t)blockIdx.y * G; }
+    head += (size_t)blockIdx.y * G; cont += (size_t)blockIdx.y * nl; bucket += (size_t)blockIdx.y * G;
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
     const uint32_t E = offs[G];
     const uint32_t L = (E + nl - 1) / nl;
@@ -169,10 +162,9 @@ k_g2_bucket_fin(const uint32_t* __restrict__ offs, uint32_t G, uint32_t nl, uint
 //    (the scheme of the G1 generic mode, msm_kernels.h section 6, on G2 values)
 // -------------------------------------------------------------------------------------------------
 // (a) chunk sums S_t
-template <bool SETS>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_g2_red_chunk_sums(const int32_t* __restrict__ bucket, size_t bucket_stride, uint32_t n_chunks, uint32_t m, int32_t* __restrict__ chunkS, size_t chunk_stride) {
-    if (SETS) { bucket += (size_t)blockIdx.y * n_chunks * m; chunkS += (size_t)blockIdx.y * n_chunks; }      // (n_chunks m = G)
+    bucket += (size_t)blockIdx.y * n_chunks * m; chunkS += (size_t)blockIdx.y * n_chunks;      // (n_chunks m = G)
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_chunks) return;
     G2Xyzz acc;
@@ -187,10 +179,9 @@ k_g2_red_chunk_sums(const int32_t* __restrict__ bucket, size_t bucket_stride, ui
     g2_store(chunkS, chunk_stride, t, acc);
 }
 // (b) one block per window: inclusive suffix scan of the T chunk sums (Hillis-Steele through global memory): a[w T + t] = sum_{u >= t} S_u
-template <bool SETS>
 __global__ void __launch_bounds__(G2_RED_T) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_g2_red_suffix_scan(int32_t* __restrict__ a, int32_t* __restrict__ b, size_t stride, uint32_t T) {
-    if (SETS) { a += (size_t)blockIdx.y * gridDim.x * T; b += (size_t)blockIdx.y * gridDim.x * T; }          // (gridDim.x T = n_chunks)
+    a += (size_t)blockIdx.y * gridDim.x * T; b += (size_t)blockIdx.y * gridDim.x * T;          // (gridDim.x T = n_chunks)
     const uint32_t t = threadIdx.x;
     const size_t base = (size_t)blockIdx.x * T;
     int32_t* src = a;
@@ -218,11 +209,10 @@ k_g2_red_suffix_scan(int32_t* __restrict__ a, int32_t* __restrict__ b, size_t st
     }
 }
 // (c) chunk running sums, seeded with the suffix of the later chunks of the window
-template <bool SETS>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_g2_red_chunk_running(const int32_t* __restrict__ bucket, size_t bucket_stride, const int32_t* __restrict__ suffix, size_t chunk_stride,
                        uint32_t n_chunks, uint32_t T, uint32_t m, int32_t* __restrict__ chunkA) {
-    if (SETS) { bucket += (size_t)blockIdx.y * n_chunks * m; suffix += (size_t)blockIdx.y * n_chunks; chunkA += (size_t)blockIdx.y * n_chunks; }
+    bucket += (size_t)blockIdx.y * n_chunks * m; suffix += (size_t)blockIdx.y * n_chunks; chunkA += (size_t)blockIdx.y * n_chunks;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_chunks) return;
     G2Xyzz run, acc;
@@ -239,10 +229,9 @@ k_g2_red_chunk_running(const int32_t* __restrict__ bucket, size_t bucket_stride,
     g2_store(chunkA, chunk_stride, t, acc);
 }
 // (d) one block per window: tree sum of the T chunk results, left as wire-format XYZZ (64 u32)
-template <bool SETS>
 __global__ void __launch_bounds__(G2_RED_T) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_g2_red_window_sum(int32_t* __restrict__ a, size_t stride, uint32_t T, uint32_t* __restrict__ out_wire) {
-    if (SETS) { a += (size_t)blockIdx.y * gridDim.x * T; out_wire += (size_t)blockIdx.y * gridDim.x * G2_WIRE_WORDS; }   // (set s: values s n_windows ..)
+    a += (size_t)blockIdx.y * gridDim.x * T; out_wire += (size_t)blockIdx.y * gridDim.x * G2_WIRE_WORDS;   // (set s: values s n_windows ..)
     const uint32_t t = threadIdx.x;
     const size_t base = (size_t)blockIdx.x * T;
 #pragma unroll 1
@@ -374,68 +363,16 @@ static DeviceBuffer* g2_ws_buffer(MsmWorkspace& ws, int which) {
     return buffers[which];
 }
 
-// one launch of at most G2MSM_MAX_LAUNCH pairs on slot 0's workspace and stream, synchronised: results[s] = the sum over base set s
-static int32_t g2_msm_launch(kzg_ctx* ctx, const uint4* const* d_points, uint32_t nb, const uint4* d_scalars, size_t n, H::G2* results) {
+// one launch: `blobs` scalar sets (d_scalars: blobs x n, one after the other; n <= G2MSM_MAX_LAUNCH) over nb shared base sets on slot 0's
+// workspace and stream, synchronised: results[s * blobs + b] = the sum of blob b over base set s.  The sort's launches and six more,
+// whatever blobs and nb.
+static int32_t g2_msm_launch(kzg_ctx* ctx, const uint4* const* d_points, uint32_t nb, const uint4* d_scalars, size_t n, uint32_t blobs, H::G2* results) {
     MsmWorkspace& ws = ctx->msm;
     hipStream_t st = ctx->stream;
-    const G2Plan p = g2_make_plan(n, nb, ctx->acc_wave_slots / 3 * G2_ACC_WAVES);
+    const G2Plan p = g2_make_plan(n, nb, blobs, ctx->acc_wave_slots / 3 * G2_ACC_WAVES);
     {
         const char* error = nullptr;
-        const int32_t rc = g2_plan_status(p, n, MSM_MAX_OUT * 32 / G2_WIRE_WORDS, &error);
-        if (error) ctx->last_error = error;
-        if (rc != KZG_OK) return rc;
-    }
-    for (int i = 0; i < G2WS_BUFFERS; ++i) KZG_HIP_TRY(ctx, g2_ws_buffer(ws, i)->reserve(p.bytes[i]));
-    { const int32_t rc = msm_pinned_out(ctx, ws); if (rc != KZG_OK) return rc; }
-    { const int32_t rc = msm_sort_generic(ctx, ws, st, d_scalars, p.sort); if (rc != KZG_OK) return rc; }
-    const uint32_t n_chunks = p.n_chunks(), gc = (n_chunks + 255) / 256;
-    const size_t G = p.G;
-    for (uint32_t s = 0; s < nb; ++s) {
-        uint32_t* d_out = reinterpret_cast<uint32_t*>(ws.pinned_out_dev) + (size_t)s * p.W * G2_WIRE_WORDS;
-        hipLaunchKernelGGL(k_g2_accumulate, dim3(p.nl / 256), dim3(256), 0, st, d_points[s], ws.sorted.as<uint32_t>(), ws.offs.as<uint32_t>(), p.G,
-                           ws.head.as<int32_t>(), G, ws.cont.as<int32_t>(), (size_t)p.nl);
-        hipLaunchKernelGGL(k_g2_bucket_fin<false>, dim3((p.G + 255) / 256), dim3(256), 0, st, ws.offs.as<uint32_t>(), p.G, p.nl, p.m, n_chunks, ws.head.as<int32_t>(), G,
-                           ws.cont.as<int32_t>(), (size_t)p.nl, ws.bucket.as<int32_t>(), G);
-        hipLaunchKernelGGL(k_g2_red_chunk_sums<false>, dim3(gc), dim3(256), 0, st, ws.bucket.as<int32_t>(), G, n_chunks, p.m, ws.chunkS.as<int32_t>(), (size_t)n_chunks);
-        hipLaunchKernelGGL(k_g2_red_suffix_scan<false>, dim3(p.W), dim3(p.T), 0, st, ws.chunkS.as<int32_t>(), ws.chunkTmp.as<int32_t>(), (size_t)n_chunks, p.T);
-        hipLaunchKernelGGL(k_g2_red_chunk_running<false>, dim3(gc), dim3(256), 0, st, ws.bucket.as<int32_t>(), G, ws.chunkS.as<int32_t>(), (size_t)n_chunks, n_chunks,
-                           p.T, p.m, ws.chunkA.as<int32_t>());
-        hipLaunchKernelGGL(k_g2_red_window_sum<false>, dim3(p.W), dim3(p.T), 0, st, ws.chunkA.as<int32_t>(), (size_t)n_chunks, p.T, d_out);
-    }
-    KZG_HIP_TRY(ctx, hipGetLastError());
-    KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    for (uint32_t s = 0; s < nb; ++s)
-        results[s] = g2_horner(reinterpret_cast<const uint32_t*>(ws.pinned_out) + (size_t)s * p.W * G2_WIRE_WORDS, p.W, p.c);
-    return KZG_OK;
-}
-
-int32_t g2_msm_run(kzg_ctx* ctx, const uint4* const* d_points, uint32_t nb, const void* d_scalars, size_t n, uint64_t* out_g2, uint8_t* out_inf) {
-    if (nb != 1 && nb != 2) return KZG_ERR_INVALID_ARG;
-    H::G2 total[2] = {H::g2_inf(), H::g2_inf()};
-    for (size_t lo = 0; lo < n; lo += G2MSM_MAX_LAUNCH) {           // parts of at most G2MSM_MAX_LAUNCH pairs, added on the host
-        const size_t len = std::min<size_t>(G2MSM_MAX_LAUNCH, n - lo);
-        const uint4* pts[2] = {d_points[0] + 8 * lo, nb == 2 ? d_points[1] + 8 * lo : nullptr};
-        H::G2 part[2];
-        const int32_t rc = g2_msm_launch(ctx, pts, nb, static_cast<const uint4*>(d_scalars) + 2 * lo, len, part);
-        if (rc != KZG_OK) return rc;
-        for (uint32_t s = 0; s < nb; ++s) total[s] = H::g2_add(total[s], part[s]);
-    }
-    for (uint32_t s = 0; s < nb; ++s) {
-        H::g2_to_wire(total[s], out_g2 + 16 * s);
-        if (out_inf) out_inf[s] = total[s].inf ? 1 : 0;
-    }
-    return KZG_OK;
-}
-
-// one group of `blobs` scalar sets (d_scalars: blobs x n, one after the other) over nb shared base sets on slot 0's workspace and stream,
-// synchronised: results[s * blobs + b] = the sum of blob b over base set s.  The sort's launches and six more, whatever blobs and nb.
-static int32_t g2_msm_batch_launch(kzg_ctx* ctx, const uint4* const* d_points, uint32_t nb, const uint4* d_scalars, size_t n, uint32_t blobs, H::G2* results) {
-    MsmWorkspace& ws = ctx->msm;
-    hipStream_t st = ctx->stream;
-    const G2BatchPlan p = g2_make_batch_plan(n, nb, blobs, ctx->acc_wave_slots / 3 * G2_ACC_WAVES);
-    {
-        const char* error = nullptr;
-        const int32_t rc = g2_batch_plan_status(p, n, G2_RESULT_CAP, &error);
+        const int32_t rc = g2_plan_status(p, n, G2_RESULT_CAP, &error);
         if (error) ctx->last_error = error;
         if (rc != KZG_OK) return rc;
     }
@@ -447,15 +384,15 @@ static int32_t g2_msm_batch_launch(kzg_ctx* ctx, const uint4* const* d_points, u
     G2BaseSets sets{};
     for (uint32_t s = 0; s < nb; ++s) sets.points[s] = d_points[s];
     uint32_t* d_out = reinterpret_cast<uint32_t*>(ws.pinned_out_dev);
-    hipLaunchKernelGGL(k_g2_accumulate_batch, dim3(p.nl / 256, nb), dim3(256), 0, st, sets, ws.sorted.as<uint32_t>(), ws.offs.as<uint32_t>(), p.G,
+    hipLaunchKernelGGL(k_g2_accumulate, dim3(p.nl / 256, nb), dim3(256), 0, st, sets, ws.sorted.as<uint32_t>(), ws.offs.as<uint32_t>(), p.G,
                        ws.head.as<int32_t>(), hs, ws.cont.as<int32_t>(), cs);
-    hipLaunchKernelGGL(k_g2_bucket_fin<true>, dim3((p.G + 255) / 256, nb), dim3(256), 0, st, ws.offs.as<uint32_t>(), p.G, p.nl, p.m, n_chunks, ws.head.as<int32_t>(), hs,
+    hipLaunchKernelGGL(k_g2_bucket_fin, dim3((p.G + 255) / 256, nb), dim3(256), 0, st, ws.offs.as<uint32_t>(), p.G, p.nl, p.m, n_chunks, ws.head.as<int32_t>(), hs,
                        ws.cont.as<int32_t>(), cs, ws.bucket.as<int32_t>(), hs);
-    hipLaunchKernelGGL(k_g2_red_chunk_sums<true>, dim3(gc, nb), dim3(256), 0, st, ws.bucket.as<int32_t>(), hs, n_chunks, p.m, ws.chunkS.as<int32_t>(), ks);
-    hipLaunchKernelGGL(k_g2_red_suffix_scan<true>, dim3(n_windows, nb), dim3(p.T), 0, st, ws.chunkS.as<int32_t>(), ws.chunkTmp.as<int32_t>(), ks, p.T);
-    hipLaunchKernelGGL(k_g2_red_chunk_running<true>, dim3(gc, nb), dim3(256), 0, st, ws.bucket.as<int32_t>(), hs, ws.chunkS.as<int32_t>(), ks, n_chunks, p.T, p.m,
+    hipLaunchKernelGGL(k_g2_red_chunk_sums, dim3(gc, nb), dim3(256), 0, st, ws.bucket.as<int32_t>(), hs, n_chunks, p.m, ws.chunkS.as<int32_t>(), ks);
+    hipLaunchKernelGGL(k_g2_red_suffix_scan, dim3(n_windows, nb), dim3(p.T), 0, st, ws.chunkS.as<int32_t>(), ws.chunkTmp.as<int32_t>(), ks, p.T);
+    hipLaunchKernelGGL(k_g2_red_chunk_running, dim3(gc, nb), dim3(256), 0, st, ws.bucket.as<int32_t>(), hs, ws.chunkS.as<int32_t>(), ks, n_chunks, p.T, p.m,
                        ws.chunkA.as<int32_t>());
-    hipLaunchKernelGGL(k_g2_red_window_sum<true>, dim3(n_windows, nb), dim3(p.T), 0, st, ws.chunkA.as<int32_t>(), ks, p.T, d_out);
+    hipLaunchKernelGGL(k_g2_red_window_sum, dim3(n_windows, nb), dim3(p.T), 0, st, ws.chunkA.as<int32_t>(), ks, p.T, d_out);
     KZG_HIP_TRY(ctx, hipGetLastError());
     KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
     // nb * blobs Horner combinations of ~300 dependent host additions each: on the host pool
@@ -465,29 +402,23 @@ static int32_t g2_msm_batch_launch(kzg_ctx* ctx, const uint4* const* d_points, u
     return KZG_OK;
 }
 
+// `count` scalar sets of n scalars each over nb shared base sets: launches of g2_batch_group blobs; a blob above G2MSM_MAX_LAUNCH pairs
+// goes alone, in parts of at most that many pairs whose sums the host adds
 int32_t g2_msm_batch_run(kzg_ctx* ctx, const uint4* const* d_points, uint32_t nb, const void* d_scalars, size_t n, size_t count, uint64_t* const* out_g2,
                          uint8_t* const* out_inf) {
     if (nb != 1 && nb != 2) return KZG_ERR_INVALID_ARG;
     const uint4* sc = static_cast<const uint4*>(d_scalars);
-    const uint32_t group = g2_batch_group(n, nb, count, ctx->g2_batch_group);
-    if (group == 0) {                                  // blob by blob through the single call's path
-        for (size_t b = 0; b < count; ++b) {
-            uint64_t out2[32];
-            uint8_t inf2[2];
-            const int32_t rc = g2_msm_run(ctx, d_points, nb, sc + 2 * b * n, n, out2, inf2);
-            if (rc != KZG_OK) return rc;
-            for (uint32_t s = 0; s < nb; ++s) {
-                memcpy(out_g2[s] + 16 * b, out2 + 16 * s, 128);
-                if (out_inf && out_inf[s]) out_inf[s][b] = inf2[s];
-            }
-        }
-        return KZG_OK;
-    }
-    std::vector<H::G2> results((size_t)nb * group);
+    const uint32_t group = n == 0 || n > G2MSM_MAX_LAUNCH ? 1 : g2_batch_group(n, nb, count, ctx->g2_batch_group);      // (>= 1: nb was checked)
+    std::vector<H::G2> results((size_t)nb * group, H::g2_inf()), part(nb);                // (n = 0: no launch, every sum the identity)
     for (size_t lo = 0; lo < count; lo += group) {
         const uint32_t blobs = (uint32_t)std::min<size_t>(group, count - lo);
-        const int32_t rc = g2_msm_batch_launch(ctx, d_points, nb, sc + 2 * lo * n, n, blobs, results.data());
-        if (rc != KZG_OK) return rc;
+        for (size_t at = 0; at < n; at += G2MSM_MAX_LAUNCH) {       // (one round unless n > G2MSM_MAX_LAUNCH: then blobs = 1)
+            const uint4* pts[2] = {d_points[0] + 8 * at, nb == 2 ? d_points[1] + 8 * at : nullptr};
+            H::G2* const dst = at ? part.data() : results.data();
+            const int32_t rc = g2_msm_launch(ctx, pts, nb, sc + 2 * (lo * n + at), std::min<size_t>(G2MSM_MAX_LAUNCH, n - at), blobs, dst);
+            if (rc != KZG_OK) return rc;
+            if (at) for (uint32_t s = 0; s < nb; ++s) results[s] = H::g2_add(results[s], part[s]);
+        }
         for (uint32_t s = 0; s < nb; ++s)
             for (uint32_t b = 0; b < blobs; ++b) {
                 const H::G2& r = results[(size_t)s * blobs + b];
@@ -496,6 +427,13 @@ int32_t g2_msm_batch_run(kzg_ctx* ctx, const uint4* const* d_points, uint32_t nb
             }
     }
     return KZG_OK;
+}
+
+// the single MSM: the batch of one.  out_g2: 16 nb words, out_inf (may be null): nb bytes
+int32_t g2_msm_run(kzg_ctx* ctx, const uint4* const* d_points, uint32_t nb, const void* d_scalars, size_t n, uint64_t* out_g2, uint8_t* out_inf) {
+    uint64_t* const outs[2] = {out_g2, out_g2 + 16};
+    uint8_t* const infs[2] = {out_inf, out_inf ? out_inf + 1 : nullptr};
+    return g2_msm_batch_run(ctx, d_points, nb, d_scalars, n, 1, outs, infs);
 }
 
 int32_t g2_upload_points(kzg_ctx* ctx, const uint64_t* g2_mont, size_t n, uint4* d_out, int64_t* bad) {

@@ -2,7 +2,8 @@
 (`kzg_msm_g2_srs_batch`).  Setup of order N = 2^16 with a known tau, as tests/test_gpu_length_proof.py.  The contract is equality with
 the loop of single calls, bit for bit, on all three outputs: lengths that are no power of two (in-blob indexing), both sides of a
 window-width change and of the 2^18-entry sort switch, groups of 2, 2, 1 under a cap, degenerate blobs among random ones, identity bases, a
-non-zero offset, the three-kernel scan of the bucket counts (33 blobs of 2^14 coefficients, against the closed forms), the error table in
+non-zero offset, groups of one, closed forms over two different base sets (single call and batch: the single call is the batch of one), the
+three-kernel scan of the bucket counts (33 blobs of 2^14 coefficients, against the closed forms), the error table in
 its documented order, accept / reject through the batched verifier, and the same kernels in the bound-checked build.  `helpers.g2_batch_info`
 proves that a shape takes the path the test means.  Every test with more than one blob fails if the accumulate indexed blob * n + i into
 the shared bases."""
@@ -145,6 +146,108 @@ def test_groups_under_a_cap_give_the_same_bits(setup):
         ctx.set_g2_batch_group(0)
     assert_rows_equal(got, want)
     assert_rows_equal(got, loop(setup, rows, d, key=(n, d)))
+
+
+def test_groups_of_one_give_the_same_bits(setup):
+    n, d, B = 300, 512, 3
+    rows = blobs_of(n)[:B]
+    info = helpers.g2_batch_info(n, 2, B, max_blobs=1)
+    assert info["groups"] == 3 and info["blobs_per_group"] == 1 and info["batched"]
+    ctx = _lib.default_context()
+    want = batch(setup, rows, d)                                                               # one group of three
+    ctx.set_g2_batch_group(1)
+    try:
+        got = batch(setup, rows, d)
+    finally:
+        ctx.set_g2_batch_group(0)
+    assert_rows_equal(got, want)
+
+
+# ---- closed forms over two DIFFERENT base sets: since the single call is the batch of one, "batch = loop of single calls" compares one
+# implementation with itself; here both are compared with [sum a_i s_i] G2 and [sum a_i t_i] G2 for known s_i != t_i
+CF_MAX = 2048
+CF_SHAPES = [(64, 64), (300, 512), (2048, 2048)]           # lane cap inactive; active with c = 4; c = 5
+
+
+@pytest.fixture(scope="module")
+def two_sets():
+    """CF_MAX bases [s_i] G2 and CF_MAX bases [t_i] G2 with known s_i != t_i (computed once, never modified)"""
+    rnd = random.Random(4242)
+    s = [rnd.randrange(1, R_) for _ in range(CF_MAX)]
+    t = [rnd.randrange(1, R_) for _ in range(CF_MAX)]
+    assert all(x != y for x, y in zip(s, t))
+    ps = np.stack([helpers.g2_mul_generator(fr_from_int(v)) for v in s])
+    pt = np.stack([helpers.g2_mul_generator(fr_from_int(v)) for v in t])
+    ps.setflags(write=False); pt.setflags(write=False)
+    g1 = k.SRS.generate(TAU, CF_MAX)
+    yield s, t, ps, pt, g1
+    g1.close()
+
+
+def g2_of(total):
+    return helpers.g2_mul_generator(fr_from_int(total % R_)) if total % R_ else np.zeros(16, np.uint64)
+
+
+@pytest.mark.parametrize("n,d", CF_SHAPES)
+def test_single_and_batch_match_the_closed_forms_over_two_base_sets(two_sets, n, d):
+    s, t, ps, pt, g1 = two_sets
+    dead = sorted({0, 63, 64, n - 1} & set(range(n)))                                          # identity bases in set 1 only
+    pts1 = np.array(pt[:d])
+    pts1[dead] = 0
+    t_live = [0 if i in dead else t[i] for i in range(n)]
+    assert helpers.g2_batch_info(n, 2, 1)["c"] == {64: 4, 300: 4, 2048: 5}[n]
+    info = helpers.g2_batch_info(n, 2, 1)
+    assert (info["nl"] == -(-4 * info["G"] // 256) * 256 < -(-info["entries"] // 4)) == (n != 64)          # the lane cap binds, or does not
+    rnd = random.Random(500 + n)
+    ints = {"random": [rnd.randrange(R_) for _ in range(n)], "equal": [rnd.randrange(1, R_)] * n, "zero": [0] * n,
+            "random2": [rnd.randrange(R_) for _ in range(n)]}
+    rows = {name: frs_from_ints(a) for name, a in ints.items()}
+    want = {name: (g2_of(sum(x * y for x, y in zip(a, s))), g2_of(sum(x * y for x, y in zip(a, t_live)))) for name, a in ints.items()}
+    assert not want["zero"][0].any() and not want["zero"][1].any() and want["equal"][1].any()
+    h0 = k.G2SRS.from_points(np.ascontiguousarray(ps[:d]))
+    h1 = k.G2SRS.from_points(pts1, first_power=N - d)
+    hs = (g1, h0, h1)
+    try:
+        for name in ints:                                                                      # the single call
+            _, c2, pi2 = single(hs, rows[name], d)
+            assert np.array_equal(c2, want[name][0]) and np.array_equal(pi2, want[name][1]), name
+        for names in (["random"], ["zero"], ["random", "zero", "equal"], ["zero", "zero", "zero"], ["equal", "random2", "random"]):      # B = 1, 3
+            _, c2, pi2 = batch(hs, [rows[x] for x in names], d)
+            for b, name in enumerate(names):
+                assert np.array_equal(c2[b], want[name][0]) and np.array_equal(pi2[b], want[name][1]), (names, b)
+        # the identity's flag: the all-zero set over set 1, single and batched
+        lib, ctx = _lib.load(), _lib.default_context()
+        out = np.ones(16, np.uint64); inf = C.c_uint8(0)
+        assert lib.kzg_msm_g2_srs(ctx.handle, h1.handle, 0, _lib.ptr(rows["zero"]), n, _lib.ptr(out), C.byref(inf)) == _lib.OK
+        assert inf.value == 1 and not out.any()
+        z3 = np.ascontiguousarray(np.stack([rows["zero"], rows["random"], rows["zero"]]))
+        out3 = np.ones((3, 16), np.uint64); flags = np.full(3, 7, np.uint8)
+        assert lib.kzg_msm_g2_srs_batch(ctx.handle, h1.handle, 0, _lib.ptr(z3), n, 3, _lib.ptr(out3), flags.ctypes.data_as(_lib.u8p)) == _lib.OK
+        assert list(flags) == [1, 0, 1] and not out3[0].any() and not out3[2].any() and np.array_equal(out3[1], want["random"][1])
+    finally:
+        h0.close(); h1.close()
+
+
+def test_the_query_of_one_blob_agrees_with_the_planner(tmp_path):
+    """pure query, no GPU work: `kzg_msm_g2_batch_info` at count = 1 against the lines of tests/hostcheck/g2msm_plancheck.cpp"""
+    exe = str(tmp_path / "g2msm_plancheck")
+    csrc = os.path.join(ROOT, "rust-kzg-bn254_amd", "csrc")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wno-unknown-pragmas", "-I" + csrc, os.path.join(HERE, "hostcheck", "g2msm_plancheck.cpp"), "-o", exe])
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    rows = [{f.split("=")[0]: int(f.split("=")[1]) for f in ln.split()} for ln in res.stdout.splitlines() if " count=1 max=0 " in ln]
+    by_key = {(r["n"], r["nb"]): r for r in rows}
+    for n in (1, 64, 257, 2047, 2048, 4096, 1 << 16, 1 << 20):
+        for nb in (1, 2):
+            r, got = by_key[(n, nb)], helpers.g2_batch_info(n, nb, 1)
+            assert got["batched"] and got["blobs_per_group"] == 1 == r["group"] and got["groups"] == 1
+            for a, b in (("c", "c"), ("W", "W"), ("G", "G"), ("entries", "entries"), ("nl", "nl"), ("seg", "seg"), ("sort_small", "small"), ("scan1", "scan1"),
+                         ("launches", "launches"), ("workspace_bytes", "bytes")):
+                assert got[a] == r[b], (n, nb, a)
+    for nb in (1, 2):                                                                          # no two blobs of 2^22 scalars fit one launch
+        got = helpers.g2_batch_info(1 << 22, nb, 3)
+        assert not got["batched"] and got["blobs_per_group"] == 1 and got["groups"] == 3
+        assert got["launches"] == 2 + got["sort_small"] + 1 + (1 if got["scan1"] else 3) + 1 + 6       # six behind the sort, whatever nb
 
 
 def degenerate_rows():

@@ -2,7 +2,8 @@
 each, in the same process, the G1 MSM of the same n in GENERIC mode (an SRS uploaded with KZG_NO_PRECOMPUTE=1: no window or per-bit
 tables, the same bucket method with the same window bits).  Also: 4 096 host double-and-add multiplications in G2 (`kzg_validate_g2_point`
 runs one `g2_mul` by r each; the sum of 4 096 of them is what a host G2 MSM of 2^12 pairs costs without its additions), and the blob
-header call (`kzg_commit_with_length_proof`) beside its three parts called one by one.  Every timed window is a synchronous call that
+header call (`kzg_commit_with_length_proof`, two base sets) beside its three parts called one by one, at 2^12 or at every exponent of
+G2_HEADER_LG.  Every timed window is a synchronous call that
 returns host data; each shape is warmed up twice; the figure is the median of the repetitions (min and max beside it).
 G2_SIZES="12,16,20" overrides the sizes, G2_REPS the repetitions, G2_OUT names a JSON file."""
 import ctypes as C, json, os, statistics, sys, time
@@ -31,7 +32,8 @@ def median_ms(fn, reps):
 
 
 out = {"rows": [], "reps": reps}
-top = 1 << max(sizes)
+header_lgs = [int(s) for s in os.environ.get("G2_HEADER_LG", "12").split(",")]
+top = 1 << max(sizes + header_lgs)
 t0 = time.perf_counter()
 g2 = k.G2SRS.generate(TAU, top, ctx=ctx)
 out["g2_srs_generate_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
@@ -67,33 +69,31 @@ for _ in range(4096):
 out["host_g2_mul_x4096_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
 print("host g2_mul x 4096: %.1f ms" % out["host_g2_mul_x4096_ms"], flush=True)
 
-# the header call beside its three parts
-N, d = 1 << 16, 1 << 12
-n = d
-trailing = k.G2SRS.generate(TAU, d, first_power=N - d, ctx=ctx)
-sc = np.ascontiguousarray(rng.integers(0, 1 << 60, size=(n, 4), dtype=np.uint64))
-c = np.zeros(8, np.uint64); c2 = np.zeros(16, np.uint64); pi2 = np.zeros(16, np.uint64); inf = C.c_uint8(0)
+# the header call (nb = 2) beside its three parts, at every length of G2_HEADER_LG
+for lg in header_lgs:
+    d = 1 << lg
+    N = max(1 << 16, d)
+    n = d
+    trailing = k.G2SRS.generate(TAU, d, first_power=N - d, ctx=ctx)
+    sc = np.ascontiguousarray(rng.integers(0, 1 << 60, size=(n, 4), dtype=np.uint64))
+    c = np.zeros(8, np.uint64); c2 = np.zeros(16, np.uint64); pi2 = np.zeros(16, np.uint64); inf = C.c_uint8(0)
 
+    def header():
+        assert lib.kzg_commit_with_length_proof(ctx.handle, g1.handle, g2.handle, trailing.handle, N - d, N, _lib.ptr(sc), n, d, _lib.ptr(c), _lib.ptr(c2), _lib.ptr(pi2)) == 0
 
-def header():
-    assert lib.kzg_commit_with_length_proof(ctx.handle, g1.handle, g2.handle, trailing.handle, N - d, N, _lib.ptr(sc), n, d, _lib.ptr(c), _lib.ptr(c2), _lib.ptr(pi2)) == 0
+    s1 = np.zeros(8, np.uint64); s2 = np.zeros(16, np.uint64); s3 = np.zeros(16, np.uint64)
 
+    def parts():
+        assert lib.kzg_commit_coeff_form(ctx.handle, g1.handle, _lib.ptr(sc), n, _lib.ptr(s1), C.byref(inf)) == 0
+        assert lib.kzg_commit_g2_coeff_form(ctx.handle, g2.handle, _lib.ptr(sc), n, _lib.ptr(s2), C.byref(inf)) == 0
+        assert lib.kzg_msm_g2_srs(ctx.handle, trailing.handle, 0, _lib.ptr(sc), n, _lib.ptr(s3), C.byref(inf)) == 0
 
-s1 = np.zeros(8, np.uint64); s2 = np.zeros(16, np.uint64); s3 = np.zeros(16, np.uint64)
-
-
-def parts():
-    assert lib.kzg_commit_coeff_form(ctx.handle, g1.handle, _lib.ptr(sc), n, _lib.ptr(s1), C.byref(inf)) == 0
-    assert lib.kzg_commit_g2_coeff_form(ctx.handle, g2.handle, _lib.ptr(sc), n, _lib.ptr(s2), C.byref(inf)) == 0
-    assert lib.kzg_msm_g2_srs(ctx.handle, trailing.handle, 0, _lib.ptr(sc), n, _lib.ptr(s3), C.byref(inf)) == 0
-
-
-for _ in range(2):
-    header(); parts()
-assert np.array_equal(c, s1) and np.array_equal(c2, s2) and np.array_equal(pi2, s3)
-h, p = median_ms(header, reps), median_ms(parts, reps)
-out["header_2_12"] = {"n": n, "header_call_ms": h[0], "min_ms": h[1], "max_ms": h[2], "three_parts_ms": p[0], "parts_min_ms": p[1], "parts_max_ms": p[2]}
-print(out["header_2_12"], flush=True)
+    for _ in range(2):
+        header(); parts()
+    assert np.array_equal(c, s1) and np.array_equal(c2, s2) and np.array_equal(pi2, s3)
+    h, p = median_ms(header, reps), median_ms(parts, reps)
+    out["header_2_%d" % lg] = {"n": n, "header_call_ms": h[0], "min_ms": h[1], "max_ms": h[2], "three_parts_ms": p[0], "parts_min_ms": p[1], "parts_max_ms": p[2]}
+    print(out["header_2_%d" % lg], flush=True)
 if os.environ.get("G2_OUT"):
     os.makedirs(os.path.dirname(os.path.abspath(os.environ["G2_OUT"])), exist_ok=True)
     json.dump(out, open(os.environ["G2_OUT"], "w"), indent=1)
