@@ -1,5 +1,5 @@
 // capi.hip — the C-ABI of include/kzg_bn254_mi355x.h: contexts, MSM, NTT, commitments, proofs, challenges.  Plain pointers and sizes only.
-// (The SRS surface: capi_srs.hip; the verifiers: capi_verify.hip; environment, host pool, error text: runtime.hip.)
+// (The SRS surface: capi_srs.hip; the verifiers: capi_verify.hip, capi_coset.hip; environment, host pool, error text: runtime.hip.)
 #include "engine.h"
 #include "host_curve.h"
 #include "host_pairing.h"
@@ -246,7 +246,7 @@ int32_t blob_proof_common(kzg_ctx* ctx, const kzg_srs* srs, const uint8_t* blob_
     if (n > srs->n) return KZG_ERR_SRS_CAPACITY_EXCEEDED;                            // kzg.rs:89-94 (commit_eval_form of the quotient)
     std::lock_guard<std::mutex> lk(ctx->mu);
     KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ctx->slot_pending[0]) { ctx->last_error = "a kzg_*_begin on slot 0 is still in flight: call its end first"; return KZG_ERR_INVALID_ARG; }
+    if (slot0_refused(ctx)) return KZG_ERR_INVALID_ARG;
     // the transcript prefix does not depend on the commitment: hash it on a host thread while the GPU works
     kzg_host::Sha256 sh;
     kzg_host::sha256_init(sh);

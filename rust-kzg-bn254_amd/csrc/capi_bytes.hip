@@ -1,6 +1,6 @@
 // capi_bytes.hip — the serialized-form surface of the C-ABI: gnark-compressed G1 points and big-endian scalars to and from the wire words the
 // verifier entries take (cosetbytes.hip on the device, host_coset_bytes.h on the host).  The fused verifier, kzg_verify_multiproof_batch_bytes,
-// lives beside the entry it mirrors in capi_verify.hip.
+// lives beside the entry it mirrors in capi_coset.hip.
 #include "engine.h"
 #include "host_coset_bytes.h"
 
@@ -11,14 +11,6 @@
 
 using namespace kzg;
 
-namespace {
-bool slot0_pending(kzg_ctx* ctx) {
-    if (!ctx->slot_pending[0]) return false;
-    ctx->last_error = "a kzg_*_begin on slot 0 is still in flight: call its end first";
-    return true;
-}
-}  // namespace
-
 extern "C" {
 
 int32_t kzg_g1_decompress_be_device(kzg_ctx* ctx, const uint8_t* bytes, size_t n_points, uint64_t* out_xy_mont, uint8_t* out_is_infinity, uint64_t* bad_index) {
@@ -27,7 +19,7 @@ int32_t kzg_g1_decompress_be_device(kzg_ctx* ctx, const uint8_t* bytes, size_t n
     if (n_points == 0) return KZG_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
     KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (slot0_pending(ctx)) return KZG_ERR_INVALID_ARG;
+    if (slot0_refused(ctx)) return KZG_ERR_INVALID_ARG;
     KZG_HIP_TRY(ctx, ctx->msm.bases.reserve(n_points * 65));                              // wire points | identity bytes
     CosetBytesDecode job;
     job.points_be[0] = bytes;
@@ -56,7 +48,7 @@ int32_t kzg_coset_items_decode_be(kzg_ctx* ctx, const uint8_t* ys_be, const uint
     const size_t V = ys_be ? count * chunk_len : 0, N = proofs_be ? count : 0;
     std::lock_guard<std::mutex> lk(ctx->mu);
     KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (slot0_pending(ctx)) return KZG_ERR_INVALID_ARG;
+    if (slot0_refused(ctx)) return KZG_ERR_INVALID_ARG;
     KZG_HIP_TRY(ctx, ctx->msm.bases.reserve(std::max<size_t>(N * 65, 64)));
     KZG_HIP_TRY(ctx, ctx->mv[0].reserve(std::max<size_t>(V * 32, 32)));
     CosetBytesDecode job;
@@ -88,15 +80,14 @@ int32_t kzg_coset_items_encode_be(const uint64_t* ys_mont, const uint64_t* proof
     if (count > ((size_t)1 << 28) / std::max<size_t>(chunk_len, 1)) return KZG_ERR_TOO_LARGE;
     std::atomic<int> bad{0};
     const size_t per = std::max<size_t>(1, 1024 / std::max<size_t>(chunk_len, 1)), jobs = (count + per - 1) / per;
-    auto body = [&](size_t j) {
+    host_parallel_for(jobs, [&](size_t j) {
         for (size_t i = j * per; i < std::min(count, (j + 1) * per); ++i) {
             if (ys_mont)
                 for (size_t t = 0; t < chunk_len; ++t)
                     if (!kzg_host::fr_encode_be(ys_mont + 4 * (i * chunk_len + t), out_ys_be + 32 * (i * chunk_len + t))) bad.store(1, std::memory_order_relaxed);
             if (proofs_xy_mont && !kzg_host::g1_encode_be(proofs_xy_mont + 8 * i, out_proofs_be + 32 * i)) bad.store(1, std::memory_order_relaxed);
         }
-    };
-    if (jobs > 1) host_parallel_for(jobs, body); else if (jobs == 1) body(0);
+    });
     return bad.load() ? KZG_ERR_INVALID_ARG : KZG_OK;
 }
 

@@ -1,15 +1,14 @@
 // capi_verify.hip — the verifier surface of the C-ABI: the pairing checks (O(1) host pairing, the data-parallel part on the GPU), the
-// two batch verifiers (blob proofs: verifier/src/batch.rs; FK20 coset proofs) and the transcript entries they are built on.
+// batch verifier of blob proofs (verifier/src/batch.rs) with its transcript entries, rows of SHA-256, erasure decoding.
+// (The verifiers of FK20 coset proofs: capi_coset.hip.)
 #include "engine.h"
 #include "host_curve.h"
 #include "host_pairing.h"
 #include "host_sha256.h"
 #include "host_fiat_shamir.h"
-#include "host_coset_bytes.h"
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -17,21 +16,16 @@
 
 using namespace kzg;
 using kzg_host::blob_padded_len;
-using kzg_host::multiproof_r_powers_host;
 using kzg_host::r_powers_host;
 
-namespace {
-
-using Clock = std::chrono::steady_clock;
-double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
-
 // ---- verifier surface: O(1) host pairing, data-parallel part on the GPU ---------------------------------------------
+namespace kzg {
 bool load_g2_tau(const uint64_t* g2_tau_mont, kzg_host::G2* out) {
     *out = g2_tau_mont ? kzg_host::g2_from_wire(g2_tau_mont) : kzg_host::g2_tau_mainnet();
     return kzg_host::g2_on_curve(*out);
 }
 
-// helpers::pairings_verify for the batch verifier: the two Miller loops on the persistent host pool (a parked worker wakes in ~20 us; host_pairing.h's own
+// helpers::pairings_verify for the batch verifiers: the two Miller loops on the persistent host pool (a parked worker wakes in ~20 us; host_pairing.h's own
 // form starts a std::thread per call), then the one final exponentiation.  Same Fq12 values, bit for bit.
 bool pairings_verify_pooled(const kzg_host::G1& a1, const kzg_host::G2& a2, const kzg_host::G1& b1, const kzg_host::G2& b2) {
     using namespace kzg_host;
@@ -43,6 +37,9 @@ bool pairings_verify_pooled(const kzg_host::G1& a1, const kzg_host::G2& a2, cons
     if (bad[0] || bad[1]) return false;
     return fq12_is_one(final_exponentiation_x(mul(f[0], f[1])));
 }
+}  // namespace kzg
+
+namespace {
 int32_t verify_batch_core(kzg_ctx* ctx, const uint64_t* commitments_xy_mont, const uint64_t* zs_mont, const uint64_t* ys_mont,
                                  const uint64_t* proofs_xy_mont, const uint64_t* r_powers_mont, size_t n,
                                  const uint64_t* g2_tau_mont, int32_t* out_ok) {
@@ -137,7 +134,7 @@ int32_t challenges_and_evaluations(kzg_ctx* ctx, const uint8_t* const* blobs, co
     group_end.push_back(n);
     std::lock_guard<std::mutex> lk(ctx->mu);
     KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ctx->slot_pending[0]) { ctx->last_error = "a kzg_*_begin on slot 0 is still in flight: call its end first"; return KZG_ERR_INVALID_ARG; }
+    if (slot0_refused(ctx)) return KZG_ERR_INVALID_ARG;
     std::vector<uint8_t> fallback(n, 0);
     size_t g0 = 0;
     for (size_t g1 : group_end) {
@@ -292,218 +289,6 @@ int32_t challenges_and_evaluations(kzg_ctx* ctx, const uint8_t* const* blobs, co
     return KZG_OK;
 }
 
-// the domain / chunk table of kzg_compute_multiproofs, in the documented order
-int32_t coset_domain_check(size_t n, size_t chunk_len) {
-    if (n == 0 || (n & (n - 1)) != 0) return KZG_ERR_NOT_POWER_OF_TWO;
-    if (n > ((size_t)1 << 24)) return KZG_ERR_DOMAIN;
-    if (n == 1 || chunk_len == 0 || (chunk_len & (chunk_len - 1)) != 0 || chunk_len > n / 2) return KZG_ERR_INVALID_ARG;
-    return KZG_OK;
-}
-
-// the upload alone: values -> ctx->mv[0], weights | indices -> ctx->mv[1] (weights == nullptr: their place is left for the caller to fill on the
-// device); room for the l coefficients in ctx->mv[2].  Enqueued on ctx->stream; the caller holds ctx->mu
-int32_t coset_upload(kzg_ctx* ctx, const uint64_t* ys, const uint64_t* coset_indices, const uint64_t* weights, size_t count, size_t l, uint4** d_w, uint64_t** d_k) {
-    KZG_HIP_TRY(ctx, ctx->mv[0].reserve(std::max<size_t>(count * l * 32, 32)));           // (count == 0: the kernels still get valid pointers)
-    KZG_HIP_TRY(ctx, ctx->mv[1].reserve(std::max<size_t>(count * 40, 64)));
-    KZG_HIP_TRY(ctx, ctx->mv[2].reserve(l * 32));
-    *d_w = ctx->mv[1].as<uint4>();
-    *d_k = reinterpret_cast<uint64_t*>(ctx->mv[1].as<uint8_t>() + count * 32);
-    if (count) {
-        KZG_HIP_TRY(ctx, hipMemcpyAsync(ctx->mv[0].p, ys, count * l * 32, hipMemcpyHostToDevice, ctx->stream));
-        if (weights) KZG_HIP_TRY(ctx, hipMemcpyAsync(*d_w, weights, count * 32, hipMemcpyHostToDevice, ctx->stream));
-        KZG_HIP_TRY(ctx, hipMemcpyAsync(*d_k, coset_indices, count * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
-    return KZG_OK;
-}
-// values, weights and indices of `count` cosets -> ctx->mv[0] | mv[1], then their l coefficients sum_i weights[i] I_i into ctx->mv[2] (left on the
-// device, enqueued on ctx->stream).  The caller holds ctx->mu.  t_uploaded != nullptr (trace): the stream is drained behind the uploads, the time
-// taken there, and drained again behind the kernels, so that the caller's phase times are those of the GPU work.
-int32_t coset_upload_and_interpolate(kzg_ctx* ctx, const uint64_t* ys, const uint64_t* coset_indices, const uint64_t* weights, size_t count, size_t n, size_t l,
-                                     Clock::time_point* t_uploaded) {
-    uint4* d_w = nullptr;
-    uint64_t* d_k = nullptr;
-    int32_t rc = coset_upload(ctx, ys, coset_indices, weights, count, l, &d_w, &d_k);
-    if (rc != KZG_OK) return rc;
-    if (t_uploaded) { KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); *t_uploaded = Clock::now(); }
-    rc = coset_interpolate_rlc_device(ctx, ctx->mv[0].as<uint4>(), d_k, d_w, count, n, l, ctx->mv[2].as<uint4>());
-    if (rc != KZG_OK) return rc;
-    if (t_uploaded) KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return KZG_OK;
-}
-
-// The weights with the item digests hashed on the device: values and indices go up as for the interpolation (they stay in ctx->mv[0] / mv[1], the
-// weights land in mv[1] too), the weights come back to out.  Inputs that are not canonical give the host's bits: that transcript is
-// recomputed there and its weights uploaded.  The caller holds ctx->mu.  *on_host (may be null) = that fallback ran.
-int32_t coset_upload_and_derive_weights(kzg_ctx* ctx, const uint64_t* commitments, size_t n_commitments, const uint64_t* commitment_indices,
-                                        const uint64_t* coset_indices, const uint64_t* ys, const uint64_t* proofs, size_t count, size_t n, size_t l, uint64_t* out,
-                                        Clock::time_point* t_uploaded, bool* on_host) {
-    uint4* d_w = nullptr;
-    uint64_t* d_k = nullptr;
-    int32_t rc = coset_upload(ctx, ys, coset_indices, nullptr, count, l, &d_w, &d_k);
-    if (rc != KZG_OK) return rc;
-    if (t_uploaded) { KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); *t_uploaded = Clock::now(); }
-    bool fell_back = false;
-    rc = coset_r_powers_device(ctx, commitments, n_commitments, commitment_indices, ctx->mv[0].as<uint4>(), d_k, proofs, count, n, l, d_w, out, &fell_back);
-    if (rc != KZG_OK) return rc;
-    if (fell_back) {
-        multiproof_r_powers_host(commitments, n_commitments, commitment_indices, coset_indices, ys, proofs, count, n, l, out, host_parallel_for);
-        KZG_HIP_TRY(ctx, hipMemcpyAsync(d_w, out, count * 32, hipMemcpyHostToDevice, ctx->stream));
-        KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    if (on_host) *on_host = fell_back;
-    return KZG_OK;
-}
-
-// The host checks of kzg_verify_multiproof_batch, in the documented order.  grouped: the entries that take a partition of the items
-// (kzg_coset_group_sums, kzg_verify_multiproof_batch_locate) add the checks of host_locate.h where their table puts them.
-int32_t multiproof_batch_checks(const kzg_ctx* ctx, const kzg_srs* srs, bool output_null, bool input_null, bool g2_missing, size_t n_commitments,
-                                const uint64_t* commitment_indices, const uint64_t* coset_indices, size_t count, size_t n, size_t chunk_len,
-                                const uint64_t* group_indices, size_t n_groups, bool grouped) {
-    if (!ctx || !srs || output_null) return KZG_ERR_INVALID_ARG;
-    if (count && input_null) return KZG_ERR_INVALID_ARG;
-    if (g2_missing) return KZG_ERR_INVALID_ARG;                                          // consts::G2_TAU is [tau]_2 only
-    if (srs->ctx != ctx || srs->lagrange_of != 0) return KZG_ERR_INVALID_ARG;
-    int32_t rc = coset_domain_check(n, chunk_len);
-    if (rc != KZG_OK) return rc;
-    const size_t l = chunk_len, m = n / l;
-    if (l > srs->n) return KZG_ERR_SRS_CAPACITY_EXCEEDED;
-    for (size_t i = 0; i < count; ++i) if (coset_indices[i] >= m || commitment_indices[i] >= n_commitments) return KZG_ERR_INVALID_ARG;
-    if (grouped) { rc = locate_check_groups(group_indices, count, n_groups); if (rc != KZG_OK) return rc; }
-    if (count > ((size_t)1 << 28) / l) return KZG_ERR_TOO_LARGE;
-    if (grouped && n_groups > LOCATE_MAX_GROUPS) return KZG_ERR_TOO_LARGE;
-    return KZG_OK;
-}
-
-// out[i] = r_i w^(k_i l) for the N items (w^l = w_m from a two-level power table); chunks on the host pool
-void coset_shifted_weights(const uint64_t* coset_indices, const uint64_t* r_powers_mont, size_t N, size_t m, uint64_t* out) {
-    using namespace kzg_host;
-    const int log_m = __builtin_ctzll(m), lo_bits = (log_m + 1) / 2, hi_bits = log_m - lo_bits;
-    const uint64_t* wm = fr_roots().w[log_m];
-    std::vector<uint64_t> lo(4 << lo_bits), hi(4 << hi_bits);
-    fr_one(lo.data());
-    for (size_t j = 1; j < ((size_t)1 << lo_bits); ++j) fr_mul(lo.data() + 4 * (j - 1), wm, lo.data() + 4 * j);
-    uint64_t step[4];
-    fr_mul(lo.data() + 4 * (((size_t)1 << lo_bits) - 1), wm, step);                  // w_m^(2^lo_bits)
-    memcpy(hi.data(), lo.data(), 32);
-    for (size_t j = 1; j < ((size_t)1 << hi_bits); ++j) fr_mul(hi.data() + 4 * (j - 1), step, hi.data() + 4 * j);
-    const size_t chunks = N >= 1024 ? 32 : 1, per = (N + chunks - 1) / chunks;
-    auto body = [&](size_t c) {
-        for (size_t i = c * per; i < std::min(N, (c + 1) * per); ++i) {
-            const uint64_t k = coset_indices[i];
-            uint64_t h[4];
-            fr_mul(lo.data() + 4 * (k & (((uint64_t)1 << lo_bits) - 1)), hi.data() + 4 * (k >> lo_bits), h);
-            fr_mul(r_powers_mont + 4 * i, h, out + 4 * i);
-        }
-    };
-    if (chunks > 1) host_parallel_for(chunks, body); else body(0);
-}
-
-// ---- the group sums of a batch of coset proofs (multilocate.hip, host_locate.h) -----------------------------------------------------------
-struct GroupSums {
-    LocatePlan plan;
-    std::vector<kzg_host::Xyzz> lhs, rhs;        // per NON-EMPTY group (plan.segs): L_g, R_g
-};
-
-// The arguments have passed multiproof_batch_checks(.., grouped); count > 0.  Values, indices and weights go up once, in the caller's
-// order; the kernels read through the plan's permutation.  Off-curve points are reported as the batch entry reports them.
-int32_t coset_group_sums_core(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments, const uint64_t* commitment_indices,
-                              const uint64_t* coset_indices, const uint64_t* ys_mont, const uint64_t* proofs_xy_mont, size_t N, size_t n, size_t l,
-                              const uint64_t* r_powers_mont, const uint64_t* group_indices, size_t n_groups, GroupSums* out) {
-    using namespace kzg_host;
-    const bool trace = opts().vb_trace != 0;
-    const auto t0 = Clock::now();
-    int32_t rc = locate_plan(group_indices, N, n_groups, &out->plan);
-    if (rc != KZG_OK) return rc;
-    const LocatePlan& plan = out->plan;
-    const size_t S = plan.segs.size(), M = n_commitments;
-    std::vector<uint64_t> derived;
-    const bool derive = !r_powers_mont;
-    if (derive) { derived.resize(4 * N); r_powers_mont = derived.data(); }
-    const bool on_device = derive && coset_transcript_on_device(ctx->transcript_device.load(std::memory_order_relaxed), N, l);
-    std::unique_lock<std::mutex> lk(ctx->mu, std::defer_lock);
-    uint4* d_w = nullptr;
-    uint64_t* d_k = nullptr;
-    if (on_device) {
-        lk.lock();
-        KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        rc = coset_upload_and_derive_weights(ctx, commitments_xy_mont, M, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, N, n, l, derived.data(), nullptr, nullptr);
-        if (rc != KZG_OK) return rc;
-        d_w = ctx->mv[1].as<uint4>();
-        d_k = reinterpret_cast<uint64_t*>(ctx->mv[1].as<uint8_t>() + N * 32);
-    } else {
-        if (derive) multiproof_r_powers_host(commitments_xy_mont, M, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, N, n, l, derived.data(), host_parallel_for);
-        lk.lock();
-        KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        rc = coset_upload(ctx, ys_mont, coset_indices, r_powers_mont, N, l, &d_w, &d_k);
-        if (rc != KZG_OK) return rc;
-    }
-    // the points, validated on the device on their way into its format: N proofs, then the M commitments
-    KZG_HIP_TRY(ctx, ctx->ml[5].reserve((N + M) * 64));
-    uint32_t off_p = 0, off_c = 0;
-    rc = upload_points(ctx, proofs_xy_mont, N, ctx->ml[5].as<uint4>(), ctx->msm.bases_wire, &off_p);
-    if (rc == KZG_OK && M) rc = upload_points(ctx, commitments_xy_mont, M, ctx->ml[5].as<uint4>() + 4 * N, ctx->msm.bases_wire, &off_c);
-    if (rc != KZG_OK) return rc;
-    if (off_p || off_c) return KZG_ERR_G1_NOT_ON_CURVE;
-    const auto t_up = Clock::now();                                                      // (upload_points synchronises)
-    // 1. the plan, then the coefficients A_{g,t} of every non-empty group (left on the device)
-    rc = locate_upload_plan(ctx, plan);
-    if (rc != KZG_OK) return rc;
-    rc = coset_group_coeffs_device(ctx, ctx->mv[0].as<uint4>(), d_k, d_w, plan, n, l);
-    if (rc != KZG_OK) return rc;
-    // 2. host scalars r_i w^(k_i l) beside those kernels; they and the commitment rows go up for the point sums
-    std::vector<uint64_t> shifted(4 * N);
-    coset_shifted_weights(coset_indices, r_powers_mont, N, n / l, shifted.data());
-    KZG_HIP_TRY(ctx, ctx->ml[4].reserve(N * 40));
-    uint4* d_w2 = ctx->ml[4].as<uint4>();
-    uint64_t* d_ci = reinterpret_cast<uint64_t*>(ctx->ml[4].as<uint8_t>() + N * 32);
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(d_w2, shifted.data(), N * 32, hipMemcpyHostToDevice, ctx->stream));
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(d_ci, commitment_indices, N * 8, hipMemcpyHostToDevice, ctx->stream));
-    KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                                 // the MSM launches run on the slots' streams
-    const auto t_interp = Clock::now();
-    // 3. [sum_t A_{g,t} tau^t]_1 for every non-empty group: S polynomials of l coefficients as one MSM problem
-    std::vector<uint64_t> interp_xy(8 * S);
-    rc = commit_batch_device(ctx, srs, ctx->ml[0].p, l, S, interp_xy.data(), nullptr);
-    if (rc != KZG_OK) return rc;
-    const auto t_msm = Clock::now();
-    // 4. the segmented point sums
-    std::vector<uint64_t> sums(32 * S);
-    rc = locate_point_sums_device(ctx, ctx->ml[5].as<uint4>(), d_ci, d_w, d_w2, plan, sums.data());
-    if (rc != KZG_OK) return rc;
-    lk.unlock();
-    const auto t_pts = Clock::now();
-    // 5. R_g = (point sum) - (interpolation commitment)
-    out->lhs.resize(S);
-    out->rhs.resize(S);
-    const size_t per = 256, jobs = (S + per - 1) / per;
-    auto body = [&](size_t c) {
-        for (size_t j = c * per; j < std::min(S, (c + 1) * per); ++j) {
-            Xyzz b;
-            memcpy(&out->lhs[j], sums.data() + 32 * j, 128);
-            memcpy(&b, sums.data() + 32 * j + 16, 128);
-            Xyzz i = xyzz_from_affine_wire(interp_xy.data() + 8 * j);
-            i.y = neg(i.y);
-            out->rhs[j] = xyzz_add(b, i);
-        }
-    };
-    if (jobs > 1) host_parallel_for(jobs, body); else if (jobs) body(0);
-    if (trace)
-        fprintf(stderr, "coset_group_sums N=%zu l=%zu M=%zu groups=%zu (non-empty %zu): plan + r_powers + upload %.3f ms, interpolation + segment sums %.3f ms, "
-                "coefficient MSMs %.3f ms, point sums %.3f ms, host sums %.3f ms\n", N, l, M, n_groups, S, ms_between(t0, t_up), ms_between(t_up, t_interp),
-                ms_between(t_interp, t_msm), ms_between(t_msm, t_pts), ms_between(t_pts, Clock::now()));
-    return KZG_OK;
-}
-
-// count points -> affine wire words and identity flags, one inversion per 256 points, chunks on the host pool
-void xyzz_to_affine_many(const kzg_host::Xyzz* p, size_t count, uint64_t* out_xy, uint8_t* out_inf) {
-    const size_t per = 256, jobs = (count + per - 1) / per;
-    auto body = [&](size_t c) {
-        const size_t a = c * per, b = std::min(count, (c + 1) * per);
-        kzg_host::xyzz_batch_to_affine(p + a, b - a, out_xy + 8 * a);
-        for (size_t j = a; j < b; ++j) out_inf[j] = kzg_host::is_inf(p[j]) ? 1 : 0;
-    };
-    if (jobs > 1) host_parallel_for(jobs, body); else if (jobs) body(0);
-}
-
 }  // namespace
 
 extern "C" {
@@ -607,30 +392,6 @@ int32_t kzg_compute_r_powers(const uint64_t* commitments_xy_mont, const uint64_t
     return KZG_OK;
 }
 
-// ---- verification of FK20 coset proofs (multiverify.hip; the proofs: kzg_compute_multiproofs) ---------------------------------
-int32_t kzg_compute_multiproof_r_powers(const uint64_t* commitments_xy_mont, size_t n_commitments, const uint64_t* commitment_indices,
-                                        const uint64_t* coset_indices, const uint64_t* ys_mont, const uint64_t* proofs_xy_mont,
-                                        size_t count, size_t n, size_t chunk_len, uint64_t* out_r_powers_mont) {
-    if (count == 0) return KZG_OK;
-    if (!commitment_indices || !coset_indices || !ys_mont || !proofs_xy_mont || !out_r_powers_mont || (n_commitments && !commitments_xy_mont)) return KZG_ERR_INVALID_ARG;
-    if (chunk_len == 0 || count > ((size_t)1 << 28) / chunk_len) return chunk_len == 0 ? KZG_ERR_INVALID_ARG : KZG_ERR_TOO_LARGE;
-    multiproof_r_powers_host(commitments_xy_mont, n_commitments, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, count, n, chunk_len, out_r_powers_mont, host_parallel_for);
-    return KZG_OK;
-}
-
-int32_t kzg_compute_multiproof_r_powers_device(kzg_ctx* ctx, const uint64_t* commitments_xy_mont, size_t n_commitments, const uint64_t* commitment_indices,
-                                               const uint64_t* coset_indices, const uint64_t* ys_mont, const uint64_t* proofs_xy_mont,
-                                               size_t count, size_t n, size_t chunk_len, uint64_t* out_r_powers_mont) {
-    if (!ctx) return KZG_ERR_INVALID_ARG;
-    if (count == 0) return KZG_OK;
-    if (!commitment_indices || !coset_indices || !ys_mont || !proofs_xy_mont || !out_r_powers_mont || (n_commitments && !commitments_xy_mont)) return KZG_ERR_INVALID_ARG;
-    if (chunk_len == 0 || count > ((size_t)1 << 28) / chunk_len) return chunk_len == 0 ? KZG_ERR_INVALID_ARG : KZG_ERR_TOO_LARGE;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return coset_upload_and_derive_weights(ctx, commitments_xy_mont, n_commitments, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, count, n, chunk_len,
-                                           out_r_powers_mont, nullptr, nullptr);
-}
-
 int32_t kzg_sha256_rows(kzg_ctx* ctx, const uint8_t* msgs, size_t row_len, size_t count, uint8_t* out_digests) {
     if (!ctx) return KZG_ERR_INVALID_ARG;
     if (count == 0) return KZG_OK;
@@ -639,24 +400,6 @@ int32_t kzg_sha256_rows(kzg_ctx* ctx, const uint8_t* msgs, size_t row_len, size_
     std::lock_guard<std::mutex> lk(ctx->mu);
     KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     return sha256_rows_run(ctx, msgs, row_len, count, out_digests);
-}
-
-int32_t kzg_coset_interpolate_rlc(kzg_ctx* ctx, const uint64_t* ys_mont, const uint64_t* coset_indices, const uint64_t* weights_mont,
-                                  size_t count, size_t n, size_t chunk_len, uint64_t* out_coeffs_mont) {
-    if (!ctx || !out_coeffs_mont) return KZG_ERR_INVALID_ARG;
-    if (count && (!ys_mont || !coset_indices || !weights_mont)) return KZG_ERR_INVALID_ARG;
-    int32_t rc = coset_domain_check(n, chunk_len);
-    if (rc != KZG_OK) return rc;
-    for (size_t i = 0; i < count; ++i) if (coset_indices[i] >= n / chunk_len) return KZG_ERR_INVALID_ARG;
-    if (count > ((size_t)1 << 28) / chunk_len) return KZG_ERR_TOO_LARGE;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t l = chunk_len;
-    rc = coset_upload_and_interpolate(ctx, ys_mont, coset_indices, weights_mont, count, n, l, nullptr);
-    if (rc != KZG_OK) return rc;
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(out_coeffs_mont, ctx->mv[2].p, l * 32, hipMemcpyDeviceToHost, ctx->stream));
-    KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return KZG_OK;
 }
 
 // erasure decoding: every check on the host before the context is touched (host_recover.h), then recover.hip
@@ -704,305 +447,6 @@ int32_t kzg_recover_batch_info(size_t blobs, size_t count, size_t n, size_t chun
     out->groups = g.n_groups;
     out->group_bytes = g.group_bytes;
     out->blob_bytes = g.blob_bytes;
-    return KZG_OK;
-}
-
-// accept <=> e(sum_i r_i pi_i, [tau^l]_2) = e(sum_rows R_row C_row - sum_t A_t [tau^t]_1 + sum_i r_i w^(k_i l) pi_i, G2), from
-// pi_i tau^l = C - I_i(tau) + w^(k_i l) pi_i.  For l = 1 this is batch.rs:228-254.
-int32_t kzg_verify_multiproof_batch(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments,
-                                    const uint64_t* commitment_indices, const uint64_t* coset_indices, const uint64_t* ys_mont,
-                                    const uint64_t* proofs_xy_mont, size_t count, size_t n, size_t chunk_len,
-                                    const uint64_t* r_powers_mont, const uint64_t* g2_tau_l_mont, int32_t* out_ok) {
-    using namespace kzg_host;
-    int32_t rc = multiproof_batch_checks(ctx, srs, !out_ok, !commitments_xy_mont || !commitment_indices || !coset_indices || !ys_mont || !proofs_xy_mont,
-                                         !g2_tau_l_mont && chunk_len != 1, n_commitments, commitment_indices, coset_indices, count, n, chunk_len, nullptr, 0, false);
-    if (rc != KZG_OK) return rc;
-    const size_t l = chunk_len, m = n / l, N = count;
-    if (N == 0) { *out_ok = 1; return KZG_OK; }
-    const bool trace = opts().vb_trace != 0;
-    const auto t0 = Clock::now();
-    G2 g2_tau_l;
-    const bool g2_ok = load_g2_tau(g2_tau_l_mont, &g2_tau_l);                            // reported after an off-curve G1 point, as verify_batch_core does
-    std::vector<uint64_t> derived;
-    const bool derive = !r_powers_mont;
-    if (derive) { derived.resize(4 * N); r_powers_mont = derived.data(); }
-    const bool on_device = derive && coset_transcript_on_device(ctx->transcript_device.load(std::memory_order_relaxed), N, l);   // (no lock: the host transcript never waits for the context)
-    std::unique_lock<std::mutex> lk(ctx->mu, std::defer_lock);
-    const char* rp_path = "";
-    double rp_ms = 0, up_ms = 0;
-    if (on_device) {
-        lk.lock();
-        // 0 + 1. values and indices go up ONCE; the item digests are hashed where they landed, the batch hash runs here, the weights are written where
-        // the interpolation reads them and come back for the host scalars of step 3
-        KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        auto t_up = t0;
-        bool on_host = false;
-        rc = coset_upload_and_derive_weights(ctx, commitments_xy_mont, n_commitments, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, N, n, l, derived.data(),
-                                             trace ? &t_up : nullptr, &on_host);
-        if (rc != KZG_OK) return rc;
-        const auto t_rp = Clock::now();
-        rp_path = on_host ? " (device, then host: an input is not canonical)" : " (device)";
-        up_ms = ms_between(t0, t_up);
-        rp_ms = ms_between(t_up, t_rp);
-        rc = coset_interpolate_rlc_device(ctx, ctx->mv[0].as<uint4>(), reinterpret_cast<uint64_t*>(ctx->mv[1].as<uint8_t>() + N * 32), ctx->mv[1].as<uint4>(), N, n, l,
-                                          ctx->mv[2].as<uint4>());
-        if (rc != KZG_OK) return rc;
-        if (trace) KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    } else {
-        if (derive) {                                                                    // (the host transcript needs no context)
-            RoctxRange range("kzg:multiproof_verify:r_powers (host)");
-            multiproof_r_powers_host(commitments_xy_mont, n_commitments, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, N, n, l, derived.data(), host_parallel_for);
-            rp_path = " (host)";
-        }
-        const auto t_rp = Clock::now();
-        lk.lock();
-        KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        // 1. values, indices, weights -> the l coefficients A_t (left on the device)
-        auto t_up = t_rp;
-        rc = coset_upload_and_interpolate(ctx, ys_mont, coset_indices, r_powers_mont, N, n, l, trace ? &t_up : nullptr);
-        if (rc != KZG_OK) return rc;
-        rp_ms = ms_between(t0, t_rp);
-        up_ms = ms_between(t_rp, t_up);
-    }
-    const auto t_ker = Clock::now();
-    // 2. [sum_i r_i I_i(tau)]_1: an MSM of the coefficients over srs[0 .. l)
-    uint64_t interp_xy[8];
-    uint8_t interp_inf = 0;
-    rc = msm_srs_locked(ctx, srs, 0, ctx->mv[2].p, true, l, interp_xy, &interp_inf, nullptr);
-    if (rc != KZG_OK) return rc;
-    const auto t_msm1 = Clock::now();
-    // 3. host scalars: r_i w^(k_i l) (w^l = w_m from a two-level power table) and the row sums of the weights
-    std::vector<uint64_t> bases(2 * N * 8), scalars(2 * N * 4), row_w(4 * n_commitments, 0);
-    {
-        coset_shifted_weights(coset_indices, r_powers_mont, N, m, scalars.data() + N * 4);
-        for (size_t i = 0; i < N; ++i) { uint64_t* rw = row_w.data() + 4 * commitment_indices[i]; fr_add(rw, r_powers_mont + 4 * i, rw); }
-        memcpy(scalars.data(), r_powers_mont, N * 32);
-        memcpy(bases.data(), proofs_xy_mont, N * 64);
-        memcpy(bases.data() + N * 8, proofs_xy_mont, N * 64);
-    }
-    // 4. the two N-point combinations of the proofs and the M-point one of the commitments; every uploaded point is checked on the device
-    uint64_t sums[2 * 8], c_sum[8];
-    uint8_t infs[2], c_inf = 0;
-    uint32_t off_p = 0, off_c = 0;
-    rc = msm_g1_batch_locked(ctx, bases.data(), scalars.data(), N, 2, sums, infs, &off_p);
-    if (rc != KZG_OK) return rc;
-    rc = msm_g1_batch_locked(ctx, commitments_xy_mont, row_w.data(), n_commitments, 1, c_sum, &c_inf, &off_c);
-    if (rc != KZG_OK) return rc;
-    if (off_p || off_c) return KZG_ERR_G1_NOT_ON_CURVE;
-    if (!g2_ok) return KZG_ERR_G2_TAU_NOT_ON_CURVE;
-    const auto t_msm2 = Clock::now();
-    // 5. point sums and ONE pairing check
-    const G1 lhs = g1_from_wire(sums);
-    const G1 rhs = g1_add(g1_add(g1_from_wire(c_sum), g1_neg(g1_from_wire(interp_xy))), g1_from_wire(sums + 8));
-    *out_ok = pairings_verify_pooled(lhs, g2_tau_l, rhs, g2_generator()) ? 1 : 0;
-    if (trace)
-        fprintf(stderr, "kzg_verify_multiproof_batch N=%zu l=%zu M=%zu: r_powers%s %.3f ms, upload %.3f ms, interpolation kernel %.3f ms, coefficient MSM %.3f ms, "
-                "host scalars + proof / commitment MSMs %.3f ms, point sums + pairing %.3f ms, call %.3f ms\n", N, l, n_commitments, rp_path, rp_ms, up_ms,
-                ms_between(t0, t_ker) - rp_ms - up_ms, ms_between(t_ker, t_msm1), ms_between(t_msm1, t_msm2), ms_between(t_msm2, Clock::now()), ms_between(t0, Clock::now()));
-    return KZG_OK;
-}
-
-int32_t kzg_verify_multiproof(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t commitment_xy_mont[8], const uint64_t proof_xy_mont[8],
-                              uint64_t coset_index, const uint64_t* ys_mont, size_t n, size_t chunk_len,
-                              const uint64_t* g2_tau_l_mont, int32_t* out_ok) {
-    if (!commitment_xy_mont || !proof_xy_mont || !ys_mont) return KZG_ERR_INVALID_ARG;
-    const uint64_t zero = 0;
-    uint64_t one_w[4];
-    kzg_host::fr_one(one_w);
-    return kzg_verify_multiproof_batch(ctx, srs, commitment_xy_mont, 1, &zero, &coset_index, ys_mont, proof_xy_mont, 1, n, chunk_len, one_w, g2_tau_l_mont, out_ok);
-}
-
-// kzg_verify_multiproof_batch on items in their serialized form: the same equation, weights and verdict, with the decode inside the call.
-// Values go up once as bytes (ctx->cb[0]) and are decoded where the interpolation kernel reads them (ctx->mv[0]); proofs and commitments go up
-// as 32 bytes each (ctx->cb[1]) and are decoded straight into the bases of msm_run_batch (ctx->msm.bases: proofs | proofs | commitments -- the
-// decode kernel writes the second copy of the proofs, the batched MSM of the two combinations reads concatenated bases).  Nothing decoded
-// returns to the host.  The transcript reads the bytes: on the host pool beside the decode kernels, or on the device where the bytes landed.
-int32_t kzg_verify_multiproof_batch_bytes(kzg_ctx* ctx, const kzg_srs* srs, const uint8_t* commitments_be, size_t n_commitments, const uint64_t* commitment_indices,
-                                          const uint64_t* coset_indices, const uint8_t* ys_be, const uint8_t* proofs_be, size_t count, size_t n, size_t chunk_len,
-                                          const uint64_t* r_powers_mont, const uint64_t* g2_tau_l_mont, int32_t* out_ok, uint64_t* out_r_powers_mont,
-                                          uint64_t* bad_index, int32_t* bad_array) {
-    using namespace kzg_host;
-    int32_t rc = multiproof_batch_checks(ctx, srs, !out_ok, !commitments_be || !commitment_indices || !coset_indices || !ys_be || !proofs_be,
-                                         !g2_tau_l_mont && chunk_len != 1, n_commitments, commitment_indices, coset_indices, count, n, chunk_len, nullptr, 0, false);
-    if (rc != KZG_OK) return rc;
-    const size_t l = chunk_len, m = n / l, N = count, M = n_commitments;
-    if (N == 0) { *out_ok = 1; return KZG_OK; }
-    const bool trace = opts().vb_trace != 0;
-    const auto t0 = Clock::now();
-    G2 g2_tau_l;
-    const bool g2_ok = load_g2_tau(g2_tau_l_mont, &g2_tau_l);                            // reported after the bytes, as the decoded entry reports it after the points
-    std::vector<uint64_t> derived;
-    const bool derive = !r_powers_mont;
-    if (derive) { derived.resize(4 * N); r_powers_mont = derived.data(); }
-    const bool on_device = derive && coset_transcript_on_device(ctx->transcript_device.load(std::memory_order_relaxed), N, l);
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ctx->slot_pending[0]) { ctx->last_error = "a kzg_*_begin on slot 0 is still in flight: call its end first"; return KZG_ERR_INVALID_ARG; }
-    // 0. uploads and decode kernels: everything is enqueued, then the host transcript runs beside them
-    KZG_HIP_TRY(ctx, ctx->msm.bases.reserve((2 * N + M) * 64));
-    KZG_HIP_TRY(ctx, ctx->msm.scalars.reserve((2 * N + M) * 32 + 32));
-    KZG_HIP_TRY(ctx, ctx->mv[0].reserve(N * l * 32));
-    KZG_HIP_TRY(ctx, ctx->mv[1].reserve(std::max<size_t>(N * 40, 64)));
-    KZG_HIP_TRY(ctx, ctx->mv[2].reserve(l * 32));
-    uint4* d_bases = ctx->msm.bases.as<uint4>();
-    uint4* d_w = ctx->mv[1].as<uint4>();
-    uint64_t* d_k = reinterpret_cast<uint64_t*>(ctx->mv[1].as<uint8_t>() + N * 32);
-    CosetBytesDecode job;
-    job.points_be[0] = commitments_be; job.n_points[0] = M; job.d_points[0] = d_bases + 4 * 2 * N;
-    job.points_be[1] = proofs_be; job.n_points[1] = N; job.d_points[1] = d_bases; job.d_points_copy[1] = d_bases + 4 * N;
-    job.ys_be = ys_be; job.n_values = N * l; job.d_ys = ctx->mv[0].as<uint4>();
-    rc = coset_bytes_enqueue(ctx, &job);
-    if (rc != KZG_OK) return rc;
-    hipError_t e_k = hipMemcpyAsync(d_k, coset_indices, N * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (derive && !on_device && e_k == hipSuccess) {
-        RoctxRange range("kzg:multiproof_verify:r_powers (host, from bytes)");
-        multiproof_r_powers_bytes_host(commitments_be, M, commitment_indices, coset_indices, ys_be, proofs_be, N, n, l, derived.data(), host_parallel_for);
-    }
-    const auto t_rp_host = Clock::now();
-    rc = coset_bytes_collect(ctx, &job);                                                 // (drains the stream on every path: the copy of the indices too)
-    if (e_k != hipSuccess) return set_error(ctx, e_k, "uploading the coset indices");
-    if (rc != KZG_OK) return rc;
-    static const char* const names[3] = {"commitment", "proof", "value of item"};
-    for (int a = 0; a < 3; ++a) {
-        rc = coset_bytes_status(ctx, "kzg_verify_multiproof_batch_bytes", names[a], job.bad[a], a == 2 ? l : 1, bad_index);
-        if (rc != KZG_OK) { if (bad_array) *bad_array = a; return rc; }
-    }
-    if (!g2_ok) return KZG_ERR_G2_TAU_NOT_ON_CURVE;
-    const auto t_dec = Clock::now();
-    // 1. the weights where the interpolation reads them
-    const char* rp_path = derive ? " (host, from bytes, beside the decode)" : " (supplied)";
-    if (on_device) {
-        rc = coset_r_powers_device_bytes(ctx, commitments_be, M, commitment_indices, job.d_ys_be, d_k, job.d_points_be[1], N, n, l, d_w, derived.data());
-        if (rc != KZG_OK) return rc;
-        rp_path = " (device, from bytes)";
-    } else {
-        KZG_HIP_TRY(ctx, hipMemcpyAsync(d_w, r_powers_mont, N * 32, hipMemcpyHostToDevice, ctx->stream));
-    }
-    const auto t_rp = Clock::now();
-    rc = coset_interpolate_rlc_device(ctx, ctx->mv[0].as<uint4>(), d_k, d_w, N, n, l, ctx->mv[2].as<uint4>());
-    if (rc != KZG_OK) return rc;
-    if (trace) KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const auto t_ker = Clock::now();
-    // 2. [sum_i r_i I_i(tau)]_1: an MSM of the coefficients over srs[0 .. l)
-    uint64_t interp_xy[8];
-    uint8_t interp_inf = 0;
-    rc = msm_srs_locked(ctx, srs, 0, ctx->mv[2].p, true, l, interp_xy, &interp_inf, nullptr);
-    if (rc != KZG_OK) return rc;
-    const auto t_msm1 = Clock::now();
-    // 3. host scalars: r_i | r_i w^(k_i l) | the row sums of the weights, in the order of the bases
-    std::vector<uint64_t> scalars((2 * N + M) * 4, 0);
-    memcpy(scalars.data(), r_powers_mont, N * 32);
-    coset_shifted_weights(coset_indices, r_powers_mont, N, m, scalars.data() + N * 4);
-    uint64_t* row_w = scalars.data() + 2 * N * 4;
-    for (size_t i = 0; i < N; ++i) { uint64_t* rw = row_w + 4 * commitment_indices[i]; fr_add(rw, r_powers_mont + 4 * i, rw); }
-    // 4. the two N-point combinations of the proofs and the M-point one of the commitments over the bases the decode kernels wrote
-    const uint4* d_scalars = ctx->msm.scalars.as<uint4>();
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(ctx->msm.scalars.p, scalars.data(), (2 * N + M) * 32, hipMemcpyHostToDevice, ctx->stream));
-    uint64_t sums[2 * 8], c_sum[8];
-    uint8_t infs[2], c_inf = 0;
-    rc = msm_run_batch(ctx, d_bases, d_scalars, N, 2, sums, infs);
-    if (rc == KZG_OK) rc = msm_run_batch(ctx, d_bases + 4 * 2 * N, d_scalars + 2 * 2 * N, M, 1, c_sum, &c_inf);
-    if (rc != KZG_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }            // (`scalars` is in use until the stream is drained)
-    const auto t_msm2 = Clock::now();
-    // 5. point sums and ONE pairing check
-    const G1 lhs = g1_from_wire(sums);
-    const G1 rhs = g1_add(g1_add(g1_from_wire(c_sum), g1_neg(g1_from_wire(interp_xy))), g1_from_wire(sums + 8));
-    *out_ok = pairings_verify_pooled(lhs, g2_tau_l, rhs, g2_generator()) ? 1 : 0;
-    if (out_r_powers_mont) memcpy(out_r_powers_mont, r_powers_mont, N * 32);
-    if (trace)
-        fprintf(stderr, "kzg_verify_multiproof_batch_bytes N=%zu l=%zu M=%zu: decode (staging, uploads, decode kernels; host r_powers beside them %.3f ms) %.3f ms, "
-                "r_powers%s %.3f ms, interpolation kernel %.3f ms, coefficient MSM %.3f ms, host scalars + proof / commitment MSMs %.3f ms, "
-                "point sums + pairing %.3f ms, call %.3f ms\n", N, l, M, derive && !on_device ? ms_between(t0, t_rp_host) : 0.0, ms_between(t0, t_dec), rp_path,
-                ms_between(t_dec, t_rp), ms_between(t_rp, t_ker), ms_between(t_ker, t_msm1), ms_between(t_msm1, t_msm2), ms_between(t_msm2, Clock::now()),
-                ms_between(t0, Clock::now()));
-    return KZG_OK;
-}
-
-// For every group g of a partition of the items: L_g = sum_{i in g} r_i pi_i and R_g = sum_{i in g} (r_i C_{c_i} + r_i w^(k_i l) pi_i) -
-// sum_t A_{g,t} [tau^t]_1; group g is good iff e(L_g, [tau^l]_2) = e(R_g, G2), and summed over the groups (L, R) is the (lhs, rhs) of
-// kzg_verify_multiproof_batch above.
-int32_t kzg_coset_group_sums(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments, const uint64_t* commitment_indices,
-                             const uint64_t* coset_indices, const uint64_t* ys_mont, const uint64_t* proofs_xy_mont, size_t count, size_t n, size_t chunk_len,
-                             const uint64_t* r_powers_mont, const uint64_t* group_indices, size_t n_groups, uint64_t* out_lhs_xy_mont,
-                             uint8_t* out_lhs_is_infinity, uint64_t* out_rhs_xy_mont, uint8_t* out_rhs_is_infinity) {
-    const bool out_null = n_groups && (!out_lhs_xy_mont || !out_lhs_is_infinity || !out_rhs_xy_mont || !out_rhs_is_infinity);
-    int32_t rc = multiproof_batch_checks(ctx, srs, out_null, !commitments_xy_mont || !commitment_indices || !coset_indices || !ys_mont || !proofs_xy_mont || !group_indices,
-                                         false, n_commitments, commitment_indices, coset_indices, count, n, chunk_len, group_indices, n_groups, true);
-    if (rc != KZG_OK) return rc;
-    GroupSums gs;
-    if (count) {
-        rc = coset_group_sums_core(ctx, srs, commitments_xy_mont, n_commitments, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, count, n, chunk_len,
-                                   r_powers_mont, group_indices, n_groups, &gs);
-        if (rc != KZG_OK) return rc;
-    }
-    if (n_groups) {                                                                      // an empty group: the identity twice
-        memset(out_lhs_xy_mont, 0, n_groups * 64);
-        memset(out_rhs_xy_mont, 0, n_groups * 64);
-        memset(out_lhs_is_infinity, 1, n_groups);
-        memset(out_rhs_is_infinity, 1, n_groups);
-    }
-    const size_t S = gs.plan.segs.size();
-    std::vector<uint64_t> xy(8 * S);
-    std::vector<uint8_t> inf(S);
-    for (int side = 0; side < 2; ++side) {
-        xyzz_to_affine_many(side ? gs.rhs.data() : gs.lhs.data(), S, xy.data(), inf.data());
-        uint64_t* out_xy = side ? out_rhs_xy_mont : out_lhs_xy_mont;
-        uint8_t* out_inf = side ? out_rhs_is_infinity : out_lhs_is_infinity;
-        for (size_t j = 0; j < S; ++j) {
-            memcpy(out_xy + 8 * (size_t)gs.plan.segs[j], xy.data() + 8 * j, 64);
-            out_inf[gs.plan.segs[j]] = inf[j];
-        }
-    }
-    return KZG_OK;
-}
-
-int32_t kzg_verify_multiproof_batch_locate(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments,
-                                           const uint64_t* commitment_indices, const uint64_t* coset_indices, const uint64_t* ys_mont,
-                                           const uint64_t* proofs_xy_mont, size_t count, size_t n, size_t chunk_len, const uint64_t* r_powers_mont,
-                                           const uint64_t* g2_tau_l_mont, const uint64_t* group_indices, size_t n_groups, uint8_t* out_group_ok,
-                                           size_t* out_bad_groups, size_t* out_pairing_checks) {
-    using namespace kzg_host;
-    int32_t rc = multiproof_batch_checks(ctx, srs, !out_bad_groups || (n_groups && !out_group_ok),
-                                         !commitments_xy_mont || !commitment_indices || !coset_indices || !ys_mont || !proofs_xy_mont || !group_indices,
-                                         !g2_tau_l_mont && chunk_len != 1, n_commitments, commitment_indices, coset_indices, count, n, chunk_len, group_indices, n_groups, true);
-    if (rc != KZG_OK) return rc;
-    if (count == 0) {                                                                    // nothing to refuse: no device work, no pairing
-        if (n_groups) memset(out_group_ok, 1, n_groups);
-        *out_bad_groups = 0;
-        if (out_pairing_checks) *out_pairing_checks = 0;
-        return KZG_OK;
-    }
-    G2 g2_tau_l;
-    const bool g2_ok = load_g2_tau(g2_tau_l_mont, &g2_tau_l);                            // reported after an off-curve G1 point, as the batch entry does
-    GroupSums gs;
-    rc = coset_group_sums_core(ctx, srs, commitments_xy_mont, n_commitments, commitment_indices, coset_indices, ys_mont, proofs_xy_mont, count, n, chunk_len,
-                               r_powers_mont, group_indices, n_groups, &gs);
-    if (rc != KZG_OK) return rc;
-    if (!g2_ok) return KZG_ERR_G2_TAU_NOT_ON_CURVE;
-    // the search runs over the non-empty groups: an empty group's pair is the identity twice, it holds and changes no range
-    const auto t0 = Clock::now();
-    struct Ops {
-        Xyzz zero() const { return xyzz_inf(); }
-        Xyzz add(const Xyzz& a, const Xyzz& b) const { return xyzz_add(a, b); }
-        Xyzz sub(const Xyzz& a, Xyzz b) const { b.y = neg(b.y); return xyzz_add(a, b); }
-    };
-    const G2 g2 = g2_generator();
-    auto holds = [&](const Xyzz& lhs, const Xyzz& rhs) {
-        uint64_t a[8], b[8];
-        xyzz_to_affine(lhs, a, nullptr);
-        xyzz_to_affine(rhs, b, nullptr);
-        return pairings_verify_pooled(g1_from_wire(a), g2_tau_l, g1_from_wire(b), g2);
-    };
-    const size_t S = gs.plan.segs.size();
-    std::vector<uint8_t> seg_ok(S, 1);
-    size_t bad = 0;
-    const size_t checks = locate_search(gs.lhs.data(), gs.rhs.data(), S, Ops(), holds, seg_ok.data(), &bad);
-    memset(out_group_ok, 1, n_groups);
-    for (size_t j = 0; j < S; ++j) out_group_ok[gs.plan.segs[j]] = seg_ok[j];
-    *out_bad_groups = bad;
-    if (out_pairing_checks) *out_pairing_checks = checks;
-    if (opts().vb_trace)
-        fprintf(stderr, "kzg_verify_multiproof_batch_locate groups=%zu: search %.3f ms, %zu pairing checks, %zu bad groups\n", n_groups, ms_between(t0, Clock::now()), checks, bad);
     return KZG_OK;
 }
 

@@ -1,6 +1,6 @@
 // cosetbytes.hip — coset items decoded from their serialized form on the device: what a sampler or validator receives off the wire, 32-byte
 // gnark-compressed G1 points (commitments, proofs) and 32-byte big-endian scalars (values), into the words the verifier's kernels read.
-// Behind kzg_g1_decompress_be_device, kzg_coset_items_decode_be (capi_bytes.hip) and kzg_verify_multiproof_batch_bytes (capi_verify.hip).
+// Behind kzg_g1_decompress_be_device, kzg_coset_items_decode_be (capi_bytes.hip) and kzg_verify_multiproof_batch_bytes (capi_coset.hip).
 //
 //   k_g1_decode_be<WIRE>   one lane per point, 32 B in as two uint4: g1_decode.h (flags, canonical x, y = (x^3 + 3)^((p + 1) / 4) by the
 //                          3-bit window of g2_decode.h, the sign rule).  Out: the device format of curve.h, 64 B, optionally twice (the

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <chrono>
 #include <cstdint>
 #include <functional>
 #include <map>
@@ -14,6 +15,7 @@
 #include "host_encode.h"   // EncodePlan
 #include "host_locate.h"   // LocatePlan
 
+namespace kzg_host { struct G1; struct G2; }   // host_pairing.h
 namespace kzg {
 
 struct DeviceBuffer {
@@ -424,6 +426,17 @@ int32_t commit_batch_device(kzg_ctx* ctx, kzg_srs* basis, const void* d_scalars,
 int32_t upload_points(kzg_ctx* ctx, const uint64_t* xy, size_t n, uint4* d_out, DeviceBuffer& staging, uint32_t* off_curve = nullptr);
 
 int32_t set_error(kzg_ctx* ctx, hipError_t e, const char* where);
+// true (and the line for kzg_ctx_last_error) while a kzg_*_begin holds slot 0's buffers, which the synchronous entries work in; names_msm_end: the text of msm.hip
+inline bool slot0_refused(kzg_ctx* ctx, bool names_msm_end = false) {
+    if (ctx->slot_pending[0]) ctx->last_error = std::string("a kzg_*_begin on slot 0 is still in flight: call ") + (names_msm_end ? "kzg_msm_g1_srs_end(ctx, 0, ..)" : "its end") + " first";
+    return ctx->slot_pending[0] != nullptr;
+}
+// shared by the verifier units (defined in capi_verify.hip, used there and in capi_coset.hip): the G2 point of a pairing check (nullptr: consts::G2_TAU;
+// false = not on the twist), helpers::pairings_verify with the two Miller loops on the host pool, the clock of the KZG_VB_TRACE lines
+using Clock = std::chrono::steady_clock;
+inline double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+bool load_g2_tau(const uint64_t* g2_tau_mont, kzg_host::G2* out);
+bool pairings_verify_pooled(const kzg_host::G1& a1, const kzg_host::G2& a2, const kzg_host::G1& b1, const kzg_host::G2& b2);
 // the context's high-priority auxiliary stream (lagrange.hip)
 int32_t ctx_aux_stream(kzg_ctx* ctx, hipStream_t fallback, hipStream_t* out);
 // the points only, no window / per-bit tables (set-up paths that need the points once: kzg_multi_cache_lagrange)

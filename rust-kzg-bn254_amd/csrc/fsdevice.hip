@@ -117,7 +117,18 @@ k_fr_powers_from_tables(const uint4* __restrict__ lo, const uint4* __restrict__ 
 // -------------------------------------------------------------------------------------------------
 // host drivers (ctx->stream, ctx->fs; called under ctx->mu, synchronised on return)
 // -------------------------------------------------------------------------------------------------
-static int32_t fs_powers_from_transcript(kzg_ctx* ctx, const std::vector<uint8_t>& data, size_t count, int log_s, uint4* d_lo, uint4* d_weights, uint64_t* out_r_powers);
+// ctx->fs[1] of both device transcripts of `count` items: digests | lo | hi | flag, lo = S = 2^log_s entries of r^a and hi = H of r^(b S); S H >= count,
+// both about sqrt(count)
+struct FsBuffers { int log_s; size_t S, H; uint4 *d_digests, *d_lo, *d_hi; uint32_t* d_flag; };
+static hipError_t fs_buffers(kzg_ctx* ctx, size_t count, FsBuffers* b) {
+    const int bits = count <= 1 ? 0 : 64 - __builtin_clzll((unsigned long long)(count - 1)), log_s = (bits + 1) / 2;
+    const size_t S = (size_t)1 << log_s, H = (count + S - 1) >> log_s;
+    const hipError_t e = ctx->fs[1].reserve(count * 32 + (S + H) * 32 + 16);
+    uint4* d = ctx->fs[1].as<uint4>();
+    *b = FsBuffers{log_s, S, H, d, d + 2 * count, d + 2 * (count + S), reinterpret_cast<uint32_t*>(d + 2 * (count + S + H))};
+    return e;
+}
+static int32_t fs_powers_from_transcript(kzg_ctx* ctx, const std::vector<uint8_t>& data, size_t count, const FsBuffers& b, uint4* d_weights, uint64_t* out_r_powers);
 
 int32_t sha256_rows_run(kzg_ctx* ctx, const uint8_t* msgs, size_t row_len, size_t count, uint8_t* out_digests) {
     if (count == 0) return KZG_OK;
@@ -141,39 +152,32 @@ int32_t coset_r_powers_device(kzg_ctx* ctx, const uint64_t* commitments, size_t 
     *fell_back = false;
     if (count == 0) return KZG_OK;
     hipStream_t st = ctx->stream;
-    // S = 2^log_s entries of r^a and H of r^(b S): S H >= count, both about sqrt(count)
-    const int bits = count <= 1 ? 0 : 64 - __builtin_clzll((unsigned long long)(count - 1)), log_s = (bits + 1) / 2;
-    const size_t S = (size_t)1 << log_s, H = (count + S - 1) >> log_s;
+    FsBuffers b;
+    KZG_HIP_TRY(ctx, fs_buffers(ctx, count, &b));
     KZG_HIP_TRY(ctx, ctx->fs[0].reserve(count * 72));                                      // proofs | commitment rows
-    KZG_HIP_TRY(ctx, ctx->fs[1].reserve(count * 32 + (S + H) * 32 + 16));                  // digests | lo | hi | flag
     uint4* d_proofs = ctx->fs[0].as<uint4>();
     uint64_t* d_cs = reinterpret_cast<uint64_t*>(ctx->fs[0].as<uint8_t>() + count * 64);
-    uint4* d_digests = ctx->fs[1].as<uint4>();
-    uint4* d_lo = d_digests + 2 * count;
-    uint4* d_hi = d_lo + 2 * S;
-    uint32_t* d_flag = reinterpret_cast<uint32_t*>(d_hi + 2 * H);
     KZG_HIP_TRY(ctx, hipMemcpyAsync(d_proofs, proofs, count * 64, hipMemcpyHostToDevice, st));
     KZG_HIP_TRY(ctx, hipMemcpyAsync(d_cs, commitment_indices, count * 8, hipMemcpyHostToDevice, st));
-    KZG_HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 16, st));
+    KZG_HIP_TRY(ctx, hipMemsetAsync(b.d_flag, 0, 16, st));
     hipLaunchKernelGGL(k_coset_item_digests, dim3((unsigned)((count + FS_LANES - 1) / FS_LANES)), dim3(FS_LANES), 0, st, d_ys, d_cs, d_ks, d_proofs,
-                       (uint32_t)count, (uint32_t)l, d_digests, d_flag);
+                       (uint32_t)count, (uint32_t)l, b.d_digests, b.d_flag);
     KZG_HIP_TRY(ctx, hipGetLastError());
     std::vector<uint8_t> data = coset_batch_transcript(commitments, n_commitments, count, n, l);       // (beside the kernel)
     uint32_t flag = 0;
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(data.data() + coset_batch_head(n_commitments), d_digests, count * 32, hipMemcpyDeviceToHost, st));
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(data.data() + coset_batch_head(n_commitments), b.d_digests, count * 32, hipMemcpyDeviceToHost, st));
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(&flag, b.d_flag, 4, hipMemcpyDeviceToHost, st));
     KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
     if (flag) { *fell_back = true; return KZG_OK; }
-    return fs_powers_from_transcript(ctx, data, count, log_s, d_lo, d_weights, out_r_powers);
+    return fs_powers_from_transcript(ctx, data, count, b, d_weights, out_r_powers);
 }
 
 // the tail of both device transcripts: r from the complete batch transcript (host), its powers as one product of two table entries per lane
-// into d_weights and to out_r_powers (host).  d_lo: room for S + H wire scalars, S = 2^log_s, H = ceil(count / S).  Synchronised on return
-static int32_t fs_powers_from_transcript(kzg_ctx* ctx, const std::vector<uint8_t>& data, size_t count, int log_s, uint4* d_lo, uint4* d_weights, uint64_t* out_r_powers) {
+// into d_weights and to out_r_powers (host).  Synchronised on return
+static int32_t fs_powers_from_transcript(kzg_ctx* ctx, const std::vector<uint8_t>& data, size_t count, const FsBuffers& b, uint4* d_weights, uint64_t* out_r_powers) {
     using namespace kzg_host;
     hipStream_t st = ctx->stream;
-    const size_t S = (size_t)1 << log_s, H = (count + S - 1) >> log_s;
-    uint4* d_hi = d_lo + 2 * S;
+    const size_t S = b.S, H = b.H;
     uint64_t r[4];
     hash_to_r(data, r);                                                                   // the one sequential stream: 56 + 32 (M + count) bytes
     std::vector<uint64_t> tab(4 * (S + H));
@@ -185,8 +189,8 @@ static int32_t fs_powers_from_transcript(kzg_ctx* ctx, const std::vector<uint8_t
     fr_mul(lo + 4 * (S - 1), r, step);                                                    // r^S
     fr_one(hi);
     for (size_t j = 1; j < H; ++j) fr_mul(hi + 4 * (j - 1), step, hi + 4 * j);
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(d_lo, tab.data(), (S + H) * 32, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_fr_powers_from_tables, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, d_lo, d_hi, (uint32_t)log_s, (uint32_t)count, d_weights);
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(b.d_lo, tab.data(), (S + H) * 32, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_fr_powers_from_tables, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, b.d_lo, b.d_hi, (uint32_t)b.log_s, (uint32_t)count, d_weights);
     KZG_HIP_TRY(ctx, hipGetLastError());
     KZG_HIP_TRY(ctx, hipMemcpyAsync(out_r_powers, d_weights, count * 32, hipMemcpyDeviceToHost, st));
     KZG_HIP_TRY(ctx, hipStreamSynchronize(st));                                           // (tab and out_r_powers are in use until here)
@@ -201,21 +205,18 @@ int32_t coset_r_powers_device_bytes(kzg_ctx* ctx, const uint8_t* commitments_be,
     RoctxRange range("kzg:multiproof_verify:r_powers (device, from bytes)");
     if (count == 0) return KZG_OK;
     hipStream_t st = ctx->stream;
-    const int bits = count <= 1 ? 0 : 64 - __builtin_clzll((unsigned long long)(count - 1)), log_s = (bits + 1) / 2;
-    const size_t S = (size_t)1 << log_s, H = (count + S - 1) >> log_s;
+    FsBuffers b;
+    KZG_HIP_TRY(ctx, fs_buffers(ctx, count, &b));
     KZG_HIP_TRY(ctx, ctx->fs[0].reserve(count * 8 + 16));                                  // commitment rows
-    KZG_HIP_TRY(ctx, ctx->fs[1].reserve(count * 32 + (S + H) * 32 + 16));                  // digests | lo | hi
     uint64_t* d_cs = ctx->fs[0].as<uint64_t>();
-    uint4* d_digests = ctx->fs[1].as<uint4>();
-    uint4* d_lo = d_digests + 2 * count;
     KZG_HIP_TRY(ctx, hipMemcpyAsync(d_cs, commitment_indices, count * 8, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_coset_item_digests_bytes, dim3((unsigned)((count + FS_LANES - 1) / FS_LANES)), dim3(FS_LANES), 0, st, d_ys_be, d_cs, d_ks, d_proofs_be,
-                       (uint32_t)count, (uint32_t)l, d_digests);
+                       (uint32_t)count, (uint32_t)l, b.d_digests);
     KZG_HIP_TRY(ctx, hipGetLastError());
     std::vector<uint8_t> data = coset_batch_transcript_bytes(commitments_be, n_commitments, count, n, l);      // (beside the kernel)
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(data.data() + coset_batch_head(n_commitments), d_digests, count * 32, hipMemcpyDeviceToHost, st));
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(data.data() + coset_batch_head(n_commitments), b.d_digests, count * 32, hipMemcpyDeviceToHost, st));
     KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    return fs_powers_from_transcript(ctx, data, count, log_s, d_lo, d_weights, out_r_powers);
+    return fs_powers_from_transcript(ctx, data, count, b, d_weights, out_r_powers);
 }
 
 }  // namespace kzg

@@ -1,4 +1,4 @@
-// host_locate.h — the host side of kzg_coset_group_sums / kzg_verify_multiproof_batch_locate (multilocate.hip, capi_verify.hip): the checks
+// host_locate.h — the host side of kzg_coset_group_sums / kzg_verify_multiproof_batch_locate (multilocate.hip, capi_coset.hip): the checks
 // of the group arguments in the order the header documents, the stable counting sort of the items by group (a permutation and segment
 // offsets: the values themselves are never reordered), and the search of the tree of group sums for the bad groups.
 // Pure host code: no HIP type, no kzg_ctx, no device call, no curve arithmetic of its own (the search is a template over the point type

@@ -1,4 +1,4 @@
-// multilocate.hip — the device side of locating the bad items of a rejected batch of coset proofs (capi_verify.hip kzg_coset_group_sums,
+// multilocate.hip — the device side of locating the bad items of a rejected batch of coset proofs (capi_coset.hip kzg_coset_group_sums,
 // kzg_verify_multiproof_batch_locate; the plan: host_locate.h).  The batch equation of multiverify.hip is linear in the set of items, so
 // for ANY partition of the N items into groups the device can produce, in one pass, the two G1 sums of every group's own equation:
 //
@@ -189,7 +189,7 @@ k_locate_fold(const int32_t* __restrict__ partial, uint32_t n_part, const uint32
     }
 }
 
-// ---- host drivers: enqueued on ctx->stream, called under ctx->mu with the arguments checked (capi_verify.hip) ----------------------------
+// ---- host drivers: enqueued on ctx->stream, called under ctx->mu with the arguments checked (capi_coset.hip) -----------------------------
 
 // The plan's arrays -> ctx->ml[1]: perm | seg_of | seg_off | part_off (uint32 each)
 int32_t locate_upload_plan(kzg_ctx* ctx, const LocatePlan& plan) {

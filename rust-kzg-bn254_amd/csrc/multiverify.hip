@@ -1,4 +1,4 @@
-// multiverify.hip — the Fr side of verifying FK20 coset proofs (multiproof.hip makes them; capi_verify.hip kzg_verify_multiproof_batch checks them):
+// multiverify.hip — the Fr side of verifying FK20 coset proofs (multiproof.hip makes them; capi_coset.hip kzg_verify_multiproof_batch checks them):
 // N cosets of l values each -> the l coefficients of ONE aggregated interpolation polynomial,
 //
 //     A_t = sum_i r_i w^(-k_i t) IFFT_l(ys_i)_t,   t < l        (IFFT_l over the root w^m = w_l, natural order in and out, 1 / l included)
@@ -102,7 +102,7 @@ k_coset_twist_sum_global(const uint4* __restrict__ rows, const uint64_t* __restr
     out[2 * (size_t)t + 1] = make_uint4(o[4], o[5], o[6], o[7]);
 }
 
-// Enqueued on ctx->stream, called under ctx->mu with the arguments checked (capi_verify.hip): d_ys count x l wire values (OVERWRITTEN when
+// Enqueued on ctx->stream, called under ctx->mu with the arguments checked (capi_coset.hip): d_ys count x l wire values (OVERWRITTEN when
 // l > 1024), d_ks count indices < n / l, d_weights count wire scalars -> d_out l canonical wire coefficients
 int32_t coset_interpolate_rlc_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, size_t count, size_t n, size_t l, uint4* d_out) {
     RoctxRange range("kzg:coset_interpolate_rlc");
