@@ -931,7 +931,7 @@ int32_t kzg_verify_length_proof(const uint64_t commitment_xy[8], const uint64_t 
  * and one final exponentiation whatever the count.  A batch with a bad header passes with probability about 2^-128 over the weights
  * (independent r_i, one rho between the two equations).  On the device: the on-twist test, the order-r subgroup
  * test of both G2 elements (one 63-bit chain per point, csrc/g2_chain.h), the chains [r_i]C2_i and [r_i]pi2_i with their sums
- * (csrc/g2batch.hip) and the G1 MSM for U.  Locating the bad header of a rejected batch is the caller's (bisection). */
+ * (csrc/g2batch.hip) and the G1 MSM for U.  A rejected batch names no header: kzg_verify_length_proof_batch_locate below finds the bad ones. */
 /* host only: prod_k e(g1s[k], g2s[k]) == 1 (EIP-197's predicate), any count; identity inputs contribute 1.
  * G1 off the curve -> KZG_ERR_G1_NOT_ON_CURVE, G2 off the twist -> KZG_ERR_G2_TAU_NOT_ON_CURVE (every G1 input is tested first). */
 int32_t kzg_pairings_product_verify(const uint64_t* g1s_xy, const uint64_t* g2s, size_t count, int32_t* out_ok);
@@ -966,6 +966,57 @@ int32_t kzg_verify_length_proof_batch(kzg_ctx* ctx, const uint64_t* commitments_
                                       const uint64_t* length_proofs, const uint64_t* claimed_lens, size_t count,
                                       const uint64_t* shift_lens, const uint64_t* g1_tau_shifts_xy, size_t n_shifts,
                                       const uint64_t* weights_mont /* NULL: derived */, int32_t* out_ok, uint64_t* bad_index);
+/* Locating the bad headers of a rejected batch.  The equation above is linear in the set of headers, so for ANY partition of the headers
+ * into n_groups groups (group_indices[i] < n_groups is header i's group; a group may be empty) the device produces, in one pass over the
+ * batch, the components of every group's own equation, with the weights of the batch entry (weights_mont, or derived when NULL):
+ *     U_g     = sum_{i in g} r_i C_i                              (G1)
+ *     W_{g,s} = sum_{i in g, d_i = shift_lens[s]} r_i C2_i        (G2, s < n_shifts)
+ *     Pi_g    = sum_{i in g} r_i pi2_i                            (G2)
+ * Group g is good iff  e(U_g, G2) e(-G1, sum_s W_{g,s} + [rho]Pi_g) prod_s e([rho]T_s, W_{g,s}) = 1.  Summed over all groups the
+ * components are those of the batch entry, so the verdict on the sum of all groups is that entry's verdict for the same inputs and
+ * weights; the equation of any union of groups is the same predicate on the component-wise sums.
+ *
+ * kzg_header_group_sums: the inputs of the batch entry, the partition, and the outputs out_u_xy (n_groups x 8 u64, affine G1 wire points)
+ * with out_u_is_infinity (n_groups bytes), out_w_g2 (n_groups x n_shifts x 16 u64, row g n_shifts + s = W_{g,s}) and out_pi_g2 (n_groups
+ * x 16 u64): affine wire points, the G2 identity all zeros; an empty group, and a length no header of a group claims, give identities.
+ * Equal inputs give equal bits, whatever the order of the headers inside a group and whatever the launch geometry.  On the device: the
+ * G2 points lie one per lane in the sorted order of a composite key (g n_shifts + s for C2_i, n_groups n_shifts + g for pi2_i; the
+ * stable counting sort of csrc/host_locate.h, a permutation), every lane runs its chain [r_i]P, a segmented scan over the wave and one
+ * wave per segment leave the sums (csrc/g2batch.hip); U_g takes the GLV multiplication and the segmented scan of the coset entries
+ * (csrc/multilocate.hip), keyed by group.
+ * Errors: rows 1-7 of the batch entry's table in its order (a null group_indices with count > 0, or a null output with n_groups > 0,
+ * counts as a null pointer under row 1), with two rows behind row 4, before any curve check or allocation:
+ *   4a. a group index >= n_groups, or n_groups = 0 with count > 0 -> KZG_ERR_INVALID_ARG;
+ *   4b. n_groups * (n_shifts + 1) > 2^28 -> KZG_ERR_TOO_LARGE.
+ * count = 0 -> identities everywhere, no device work.  Synchronous, slot 0 (KZG_ERR_INVALID_ARG while a _begin on slot 0 is in
+ * flight); the context is usable after any error. */
+int32_t kzg_header_group_sums(kzg_ctx* ctx, const uint64_t* commitments_xy, const uint64_t* length_commitments,
+                              const uint64_t* length_proofs, const uint64_t* claimed_lens, size_t count, const uint64_t* shift_lens,
+                              const uint64_t* g1_tau_shifts_xy, size_t n_shifts, const uint64_t* weights_mont /* NULL: derived */,
+                              const uint64_t* group_indices, size_t n_groups, uint64_t* out_u_xy, uint8_t* out_u_is_infinity,
+                              uint64_t* out_w_g2, uint64_t* out_pi_g2, uint64_t* bad_index);
+/* The group sums above, then a search on the host (the one of kzg_verify_multiproof_batch_locate): prefix sums of the groups' components
+ * in group order make the components of any range of groups a difference of two prefixes; the root is tested first; a range that holds
+ * marks all its groups good; a failing range of one group marks it bad; any other failing range is halved and its left half tested (if
+ * that holds, the right half fails without a test).  Each test is one product of pairings on the host pool, 3 + (lengths present in
+ * the batch) Miller loops with rho on the G1 side (e(-[rho]G1, Pi) for e(-G1, [rho]Pi); [rho]G1 and [rho]T_s are computed once per
+ * call), and no GPU work: at most 1 + 2 b ceil(log2 n_groups) checks for b bad groups, exactly one for a good batch.  out_group_ok:
+ * n_groups bytes, 1 = good; *out_bad_groups = the number of bad groups; *out_pairing_checks (may be NULL) = the checks made.  KZG_OK
+ * with *out_bad_groups = 0 is the accept of the batch entry.  The host work in front of the search is linear in n_groups x (2 + lengths
+ * present): with one group per header and very large counts it outweighs the device pass, so group coarsely first (profiles/header_locate.md).
+ * Soundness: a range that holds could in principle hide bad groups that cancel; with weights derived from the transcript over ALL
+ * inputs (weights_mont = NULL, or kzg_compute_header_batch_weights) that has negligible probability, with weights of the caller's own
+ * choosing there is no such guarantee.
+ * This entry always pays for the group sums: a caller who expects good batches calls the batch entry first and this one only after a
+ * reject.  count = 0 -> every group good, no device work, no pairing check.  Errors: those of kzg_header_group_sums in its order
+ * (a null out_bad_groups, or a null out_group_ok with n_groups > 0, under row 1).  Synchronous, slot 0.  KZG_VB_TRACE=1 prints the
+ * phases on stderr: shared prefix, G2 group sums, G1 group sums, host sums, search with its number of checks. */
+int32_t kzg_verify_length_proof_batch_locate(kzg_ctx* ctx, const uint64_t* commitments_xy, const uint64_t* length_commitments,
+                                             const uint64_t* length_proofs, const uint64_t* claimed_lens, size_t count,
+                                             const uint64_t* shift_lens, const uint64_t* g1_tau_shifts_xy, size_t n_shifts,
+                                             const uint64_t* weights_mont /* NULL: derived */, const uint64_t* group_indices,
+                                             size_t n_groups, uint8_t* out_group_ok, size_t* out_bad_groups,
+                                             size_t* out_pairing_checks /* may be NULL */, uint64_t* bad_index);
 /* n_points gnark-compressed G2 points (64 bytes each: X.A1 || X.A0 big-endian, top two bits of the first byte 0b10 = the smaller y,
  * 0b11 = the larger; the format of the reference's g2.point.powerOf2) -> wire points, on the library's host thread pool.  Flag bits
  * not 0b10 / 0b11 or a coordinate not below the modulus -> KZG_ERR_DESERIALIZE; no point of that x on the twist, a point outside the

@@ -228,6 +228,9 @@ PROTOTYPES = {
     "kzg_g2_check_subgroup": (i32, [vp, u64p, sz, C.POINTER(C.c_uint64)]),
     "kzg_compute_header_batch_weights": (i32, [u64p, u64p, u64p, u64p, sz, u64p, u64p, sz, u64p]),
     "kzg_verify_length_proof_batch": (i32, [vp, u64p, u64p, u64p, u64p, sz, u64p, u64p, sz, u64p, C.POINTER(i32), C.POINTER(C.c_uint64)]),
+    "kzg_header_group_sums": (i32, [vp, u64p, u64p, u64p, u64p, sz, u64p, u64p, sz, u64p, u64p, sz, u64p, u8p, u64p, u64p, C.POINTER(C.c_uint64)]),
+    "kzg_verify_length_proof_batch_locate": (i32, [vp, u64p, u64p, u64p, u64p, sz, u64p, u64p, sz, u64p, u64p, sz, u8p, C.POINTER(sz), C.POINTER(sz),
+                                                   C.POINTER(C.c_uint64)]),
     "kzg_g2_decompress_be": (i32, [u8p, sz, u64p, C.POINTER(C.c_uint64)]),
     "kzg_g2_decompress_be_device": (i32, [vp, u8p, sz, C.c_uint32, u64p, C.POINTER(C.c_uint64)]),
     "kzg_g2srs_load_compressed_be": (i32, [vp, u8p, sz, C.POINTER(vp), C.POINTER(C.c_uint64)]),

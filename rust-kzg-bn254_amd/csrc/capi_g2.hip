@@ -1,19 +1,23 @@
 // capi_g2.hip — the G2 part of the C-ABI (include/kzg_bn254_mi355x.h, "G2 on the device"): the device-resident G2 SRS handle, the G2
 // MSM over caller bases or a handle, G2 commitments, the blob header (commitment, length commitment, length proof) in one call, the
 // headers of many blobs and the batched MSM over shared bases (with the pure query of their plan), the header's verification by two
-// pairing checks, the batched verification of headers (subgroup test and weighted sums on the device, one product of pairings), and the decoders of gnark-compressed G2 points: on the host, and on the device into wire points or a resident
+// pairing checks, the batched verification of headers (subgroup test and weighted sums on the device, one product of pairings), the group sums of such a
+// batch and the search for its bad headers (one shared prefix of checks, uploads and weights for the three; host_header_locate.h), and the decoders of gnark-compressed G2 points: on the host, and on the device into wire points or a resident
 // handle.  The kernels and their drivers are g2msm.hip, g2batch.hip and g2decode.hip; every argument check here runs before any launch.
 #include "engine.h"
 #include <new>
 #include "field29.h"
 #include "g2msm_plan.h"
+#include "host_curve.h"
 #include "host_g2_decode.h"
 #include "host_fiat_shamir.h"
+#include "host_header_locate.h"
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
+#include <mutex>
 #include <string>
 #include <vector>
 #include <cstring>
@@ -103,6 +107,143 @@ int32_t msm_g2_srs_batch_common(kzg_ctx* ctx, const kzg_g2srs* srs, size_t offse
     uint64_t* outs[1] = {out};
     uint8_t* infs[1] = {out_inf};
     return g2_msm_batch_run(ctx, pts, 1, d_scalars, n, count, outs, infs);
+}
+
+// ---- batches of blob headers: what kzg_verify_length_proof_batch, kzg_header_group_sums and kzg_verify_length_proof_batch_locate share --------
+// Where a batch of headers stands once the shared prefix has run: every input checked (rows 1-7 of the header's table), the G2 points on the
+// device, the weights at hand.
+struct HeaderStage {
+    std::unique_lock<std::mutex> lk;             // ctx->mu: taken behind row 5, held until the entry is done with the device
+    std::vector<uint8_t> length_class;           // [header] -> the position of its claimed length in shift_lens
+    std::vector<kzg_host::G1> shifts;            // T_s, on the curve
+    const uint4* d_points = nullptr;             // ctx->msm.bases, device format: C2_0, pi2_0, C2_1, pi2_1, ..
+    size_t n_points = 0;
+    const uint64_t* weights = nullptr;           // wire form: r_0 .. r_(count-1), rho; supplied or derived (then in `derived`)
+    std::vector<uint64_t> derived, canon;        // canon: the same count + 1 values as canonical words
+    int bits = 0;                                // the bit length of the largest r_i: the trip count of the G2 chains
+    Clock::time_point t0, t1, t2;                // start of row 5, the end of the on-twist test, the end of the subgroup test
+};
+
+// Rows 1-4 (host_header_locate.h: with the group rows of a grouped entry), *empty = (count == 0) and nothing else done; else rows 5-7 and the
+// weights.  `who` names the entry in the lines for kzg_ctx_last_error.
+int32_t header_batch_prefix(const char* who, kzg_ctx* ctx, bool output_null, const uint64_t* commitments_xy, const uint64_t* length_commitments,
+                            const uint64_t* length_proofs, const uint64_t* claimed_lens, size_t count, const uint64_t* shift_lens,
+                            const uint64_t* g1_tau_shifts_xy, size_t n_shifts, const uint64_t* weights_mont, const HeaderGrouping& grp, uint64_t* bad_index,
+                            bool* empty, HeaderStage* st) {
+    using namespace kzg_host;
+    // 1-4 (and 4a, 4b)
+    int32_t rc = header_batch_checks(!ctx || output_null, commitments_xy, length_commitments, length_proofs, claimed_lens, count, shift_lens, g1_tau_shifts_xy, n_shifts,
+                                     grp, &st->length_class, bad_index);
+    if (rc != KZG_OK) return rc;
+    *empty = count == 0;
+    if (count == 0) return KZG_OK;
+    st->t0 = Clock::now();
+    // 5. G1 inputs on the curve: the commitments (the header's index), then the shifts (the shift's position in the list)
+    {
+        std::atomic<uint64_t> first_bad{UINT64_MAX};
+        const size_t per = 256, jobs = (count + per - 1) / per;
+        auto body = [&](size_t j) {
+            for (size_t i = j * per; i < std::min(count, (j + 1) * per); ++i) {
+                if (g1_on_curve(g1_from_wire(commitments_xy + 8 * i))) continue;
+                uint64_t cur = first_bad.load();
+                while (i < cur && !first_bad.compare_exchange_weak(cur, (uint64_t)i)) {}
+                return;
+            }
+        };
+        if (jobs > 1) host_parallel_for(jobs, body); else body(0);
+        if (first_bad.load() != UINT64_MAX) { if (bad_index) *bad_index = first_bad.load(); return KZG_ERR_G1_NOT_ON_CURVE; }
+    }
+    st->shifts.resize(n_shifts);
+    for (size_t g = 0; g < n_shifts; ++g) {
+        st->shifts[g] = g1_from_wire(g1_tau_shifts_xy + 8 * g);
+        if (!g1_on_curve(st->shifts[g])) { if (bad_index) *bad_index = (uint64_t)g; return KZG_ERR_G1_NOT_ON_CURVE; }
+    }
+    st->lk = std::unique_lock<std::mutex>(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (slot0_busy(ctx)) return KZG_ERR_INVALID_ARG;
+    // 6. G2 inputs on the twist: uploaded as C2_0, pi2_0, C2_1, pi2_1, ..: point j belongs to header j / 2, C2 in front of pi2
+    const size_t n_points = 2 * count;
+    std::vector<uint64_t> inter(n_points * 16);
+    for (size_t i = 0; i < count; ++i) { memcpy(inter.data() + 32 * i, length_commitments + 16 * i, 128); memcpy(inter.data() + 32 * i + 16, length_proofs + 16 * i, 128); }
+    KZG_HIP_TRY(ctx, ctx->msm.bases.reserve(n_points * 128));
+    st->d_points = ctx->msm.bases.as<uint4>();
+    st->n_points = n_points;
+    int64_t bad = -1;
+    rc = g2_upload_points(ctx, inter.data(), n_points, ctx->msm.bases.as<uint4>(), &bad);
+    if (rc != KZG_OK) return rc;
+    if (bad >= 0) {
+        if (bad_index) *bad_index = (uint64_t)bad / 2;
+        ctx->last_error = std::string(who) + ": the length " + (bad & 1 ? "proof" : "commitment") + " of header " + std::to_string(bad / 2) + " is not on the twist";
+        return KZG_ERR_G2_TAU_NOT_ON_CURVE;
+    }
+    st->t1 = Clock::now();
+    // 7. G2 inputs in the order-r subgroup
+    rc = g2_subgroup_check(ctx, st->d_points, n_points, &bad);
+    if (rc != KZG_OK) return rc;
+    if (bad >= 0) {
+        if (bad_index) *bad_index = (uint64_t)bad / 2;
+        ctx->last_error = std::string(who) + ": the length " + (bad & 1 ? "proof" : "commitment") + " of header " + std::to_string(bad / 2) + " is not in the order-r subgroup";
+        return KZG_ERR_NOT_ON_CURVE;
+    }
+    st->t2 = Clock::now();
+    // the weights r_0 .. r_(count-1), rho: wire form for the G1 side, canonical words for the G2 chains
+    if (!weights_mont) {
+        st->derived.resize((count + 1) * 4);
+        header_batch_weights_host(commitments_xy, length_commitments, length_proofs, claimed_lens, count, shift_lens, g1_tau_shifts_xy, n_shifts, st->derived.data(), host_parallel_for);
+        weights_mont = st->derived.data();
+    }
+    st->weights = weights_mont;
+    st->canon.resize((count + 1) * 4);
+    st->bits = 0;
+    for (size_t i = 0; i <= count; ++i) {
+        uint64_t* k = st->canon.data() + 4 * i;
+        fr_wire_to_canonical(weights_mont + 4 * i, k);
+        if (i == count) break;                                      // rho multiplies on the host
+        for (int w = 3; w >= 0; --w) if (k[w]) { st->bits = std::max(st->bits, 64 * w + 64 - __builtin_clzll(k[w])); break; }
+    }
+    return KZG_OK;
+}
+
+// The device's part of the grouped entries: per non-empty group U_g (XYZZ), per non-empty (group, length class) W_{g,s} and per non-empty
+// group Pi_g (affine wire points), in the segment order of the two plans.
+struct HeaderGroupSums {
+    LocatePlan g1_plan, g2_plan;                 // the headers by group; the 2 count G2 points by the composite key of host_header_locate.h
+    std::vector<kzg_host::Xyzz> u;               // per segment of g1_plan
+    std::vector<uint64_t> q;                     // per segment of g2_plan: 16 u64
+    double ms_g2 = 0, ms_g1 = 0;
+};
+
+// The stage has passed header_batch_prefix with the grouping; count > 0.  The G2 points are on the device already; the commitments go up
+// here, validated again on their way into the device format (they have passed row 5).
+int32_t header_group_sums_core(kzg_ctx* ctx, const HeaderStage& st, const uint64_t* commitments_xy, size_t count, size_t n_shifts, const uint64_t* group_indices,
+                               size_t n_groups, HeaderGroupSums* out) {
+    const auto t0 = Clock::now();
+    std::vector<uint64_t> keys;
+    header_locate_keys(group_indices, st.length_class.data(), count, n_groups, n_shifts, &keys);
+    int32_t rc = locate_plan(keys.data(), keys.size(), header_n_keys(n_groups, n_shifts), &out->g2_plan);
+    if (rc != KZG_OK) return rc;
+    out->q.resize(16 * out->g2_plan.segs.size());
+    rc = g2_locate_segment_sums(ctx, st.d_points, st.n_points, out->g2_plan, reinterpret_cast<const uint32_t*>(st.canon.data()), count, st.bits, out->q.data());
+    if (rc != KZG_OK) return rc;
+    const auto t1 = Clock::now();
+    rc = locate_plan(group_indices, count, n_groups, &out->g1_plan);
+    if (rc != KZG_OK) return rc;
+    KZG_HIP_TRY(ctx, ctx->ml[5].reserve(count * 64));
+    KZG_HIP_TRY(ctx, ctx->ml[4].reserve(count * 32));
+    uint32_t off_curve = 0;
+    rc = upload_points(ctx, commitments_xy, count, ctx->ml[5].as<uint4>(), ctx->msm.bases_wire, &off_curve);
+    if (rc != KZG_OK) return rc;
+    if (off_curve) return KZG_ERR_G1_NOT_ON_CURVE;
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(ctx->ml[4].p, st.weights, count * 32, hipMemcpyHostToDevice, ctx->stream));
+    rc = locate_upload_plan(ctx, out->g1_plan);
+    if (rc != KZG_OK) return rc;
+    out->u.resize(out->g1_plan.segs.size());
+    static_assert(sizeof(kzg_host::Xyzz) == 128, "the device leaves 16 wire words per sum");
+    rc = locate_group_sums_g1_device(ctx, ctx->ml[5].as<uint4>(), ctx->ml[4].as<uint4>(), out->g1_plan, reinterpret_cast<uint64_t*>(out->u.data()));
+    if (rc != KZG_OK) return rc;
+    out->ms_g2 = ms_between(t0, t1);
+    out->ms_g1 = ms_between(t1, Clock::now());
+    return KZG_OK;
 }
 
 }  // namespace
@@ -385,93 +526,21 @@ int32_t kzg_verify_length_proof_batch(kzg_ctx* ctx, const uint64_t* commitments_
                                       const uint64_t* shift_lens, const uint64_t* g1_tau_shifts_xy, size_t n_shifts,
                                       const uint64_t* weights_mont, int32_t* out_ok, uint64_t* bad_index) {
     using namespace kzg_host;
-    using Clock = std::chrono::steady_clock;
-    auto ms = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    // 1. pointers and the shape of the shift list
-    if (!ctx || !out_ok) return KZG_ERR_INVALID_ARG;
-    if (count && (!commitments_xy || !length_commitments || !length_proofs || !claimed_lens || !shift_lens || !g1_tau_shifts_xy || n_shifts == 0)) return KZG_ERR_INVALID_ARG;
-    if (n_shifts > 64 || (n_shifts && (!shift_lens || !g1_tau_shifts_xy))) return KZG_ERR_INVALID_ARG;
-    for (size_t g = 0; g < n_shifts; ++g)
-        for (size_t h = 0; h < g; ++h) if (shift_lens[g] == shift_lens[h]) return KZG_ERR_INVALID_ARG;
-    // 2. powers of two
-    for (size_t g = 0; g < n_shifts; ++g) if (!is_pow2(shift_lens[g])) return KZG_ERR_NOT_POWER_OF_TWO;
-    for (size_t i = 0; i < count; ++i) if (!is_pow2(claimed_lens[i])) return KZG_ERR_NOT_POWER_OF_TWO;
-    // 3. every claimed length has its shift
-    int8_t group_of_log[64];
-    memset(group_of_log, -1, sizeof group_of_log);
-    for (size_t g = 0; g < n_shifts; ++g) group_of_log[__builtin_ctzll(shift_lens[g])] = (int8_t)g;
-    std::vector<uint8_t> group(count);
-    for (size_t i = 0; i < count; ++i) {
-        const int8_t g = group_of_log[__builtin_ctzll(claimed_lens[i])];
-        if (g < 0) { if (bad_index) *bad_index = (uint64_t)i; return KZG_ERR_INVALID_ARG; }
-        group[i] = (uint8_t)g;
-    }
-    // 4. size
-    if (count > ((size_t)1 << 20)) return KZG_ERR_TOO_LARGE;
-    if (count == 0) { *out_ok = 1; return KZG_OK; }
-    const auto t0 = Clock::now();
-    // 5. G1 inputs on the curve: the commitments (the header's index), then the shifts (the shift's position in the list)
-    {
-        std::atomic<uint64_t> first_bad{UINT64_MAX};
-        const size_t per = 256, jobs = (count + per - 1) / per;
-        auto body = [&](size_t j) {
-            for (size_t i = j * per; i < std::min(count, (j + 1) * per); ++i) {
-                if (g1_on_curve(g1_from_wire(commitments_xy + 8 * i))) continue;
-                uint64_t cur = first_bad.load();
-                while (i < cur && !first_bad.compare_exchange_weak(cur, (uint64_t)i)) {}
-                return;
-            }
-        };
-        if (jobs > 1) host_parallel_for(jobs, body); else body(0);
-        if (first_bad.load() != UINT64_MAX) { if (bad_index) *bad_index = first_bad.load(); return KZG_ERR_G1_NOT_ON_CURVE; }
-    }
-    std::vector<G1> shifts(n_shifts);
-    for (size_t g = 0; g < n_shifts; ++g) {
-        shifts[g] = g1_from_wire(g1_tau_shifts_xy + 8 * g);
-        if (!g1_on_curve(shifts[g])) { if (bad_index) *bad_index = (uint64_t)g; return KZG_ERR_G1_NOT_ON_CURVE; }
-    }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (slot0_busy(ctx)) return KZG_ERR_INVALID_ARG;
-    // 6. G2 inputs on the twist: uploaded as C2_0, pi2_0, C2_1, pi2_1, ..: point j belongs to header j / 2, C2 in front of pi2
-    const size_t n_points = 2 * count;
-    std::vector<uint64_t> inter(n_points * 16);
-    for (size_t i = 0; i < count; ++i) { memcpy(inter.data() + 32 * i, length_commitments + 16 * i, 128); memcpy(inter.data() + 32 * i + 16, length_proofs + 16 * i, 128); }
-    KZG_HIP_TRY(ctx, ctx->msm.bases.reserve(n_points * 128));
-    const uint4* d_points = ctx->msm.bases.as<uint4>();
-    int64_t bad = -1;
-    int32_t rc = g2_upload_points(ctx, inter.data(), n_points, ctx->msm.bases.as<uint4>(), &bad);
+    auto ms = ms_between;
+    HeaderStage st;
+    bool empty = false;
+    int32_t rc = header_batch_prefix("kzg_verify_length_proof_batch", ctx, !out_ok, commitments_xy, length_commitments, length_proofs, claimed_lens, count, shift_lens,
+                                     g1_tau_shifts_xy, n_shifts, weights_mont, HeaderGrouping(), bad_index, &empty, &st);
     if (rc != KZG_OK) return rc;
-    if (bad >= 0) {
-        if (bad_index) *bad_index = (uint64_t)bad / 2;
-        ctx->last_error = std::string("kzg_verify_length_proof_batch: the length ") + (bad & 1 ? "proof" : "commitment") + " of header " + std::to_string(bad / 2) + " is not on the twist";
-        return KZG_ERR_G2_TAU_NOT_ON_CURVE;
-    }
-    const auto t1 = Clock::now();
-    // 7. G2 inputs in the order-r subgroup
-    rc = g2_subgroup_check(ctx, d_points, n_points, &bad);
-    if (rc != KZG_OK) return rc;
-    if (bad >= 0) {
-        if (bad_index) *bad_index = (uint64_t)bad / 2;
-        ctx->last_error = std::string("kzg_verify_length_proof_batch: the length ") + (bad & 1 ? "proof" : "commitment") + " of header " + std::to_string(bad / 2) + " is not in the order-r subgroup";
-        return KZG_ERR_NOT_ON_CURVE;
-    }
-    const auto t2 = Clock::now();
-    // the weights r_0 .. r_(count-1), rho: wire form for the G1 MSM, canonical words for the G2 chains
-    std::vector<uint64_t> derived;
-    if (!weights_mont) {
-        derived.resize((count + 1) * 4);
-        header_batch_weights_host(commitments_xy, length_commitments, length_proofs, claimed_lens, count, shift_lens, g1_tau_shifts_xy, n_shifts, derived.data(), host_parallel_for);
-        weights_mont = derived.data();
-    }
-    std::vector<uint64_t> canon((count + 1) * 4);
-    int bits = 0;
-    for (size_t i = 0; i <= count; ++i) {
-        uint64_t* k = canon.data() + 4 * i;
-        fr_wire_to_canonical(weights_mont + 4 * i, k);
-        if (i == count) break;                                      // rho multiplies on the host
-        for (int w = 3; w >= 0; --w) if (k[w]) { bits = std::max(bits, 64 * w + 64 - __builtin_clzll(k[w])); break; }
-    }
+    if (empty) { *out_ok = 1; return KZG_OK; }
+    weights_mont = st.weights;
+    const std::vector<uint8_t>& group = st.length_class;
+    const std::vector<G1>& shifts = st.shifts;
+    const std::vector<uint64_t>& canon = st.canon;
+    const uint4* d_points = st.d_points;
+    const size_t n_points = st.n_points;
+    const int bits = st.bits;
+    const auto t0 = st.t0, t1 = st.t1, t2 = st.t2;
     // lanes: the C2 of every group in the list's order, each group padded to whole tiles of 64, then every pi2
     std::vector<size_t> group_count(n_shifts, 0), tile_begin(n_shifts + 2, 0);
     for (size_t i = 0; i < count; ++i) ++group_count[group[i]];
@@ -527,6 +596,128 @@ int32_t kzg_verify_length_proof_batch(kzg_ctx* ctx, const uint64_t* commitments_
         fprintf(stderr, "  verify_length_proof_batch count=%zu groups=%zu bits=%d: checks + upload + on-twist %.3f ms, subgroup %.3f ms, weights + weighted sums %.3f ms, G1 MSM %.3f ms, host sums + pairing %.3f ms\n",
                 count, n_shifts, bits, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4), ms(t4, Clock::now()));
     }
+    return KZG_OK;
+}
+
+// ---- locating the bad headers of a rejected batch (g2batch.hip k_g2_locate_*, multilocate.hip k_locate_*<1>, host_header_locate.h) ----------
+int32_t kzg_header_group_sums(kzg_ctx* ctx, const uint64_t* commitments_xy, const uint64_t* length_commitments, const uint64_t* length_proofs,
+                              const uint64_t* claimed_lens, size_t count, const uint64_t* shift_lens, const uint64_t* g1_tau_shifts_xy, size_t n_shifts,
+                              const uint64_t* weights_mont, const uint64_t* group_indices, size_t n_groups, uint64_t* out_u_xy, uint8_t* out_u_is_infinity,
+                              uint64_t* out_w_g2, uint64_t* out_pi_g2, uint64_t* bad_index) {
+    HeaderStage st;
+    HeaderGrouping grp;
+    grp.on = true; grp.group_indices = group_indices; grp.n_groups = n_groups;
+    bool empty = false;
+    const bool out_null = n_groups && (!out_u_xy || !out_u_is_infinity || !out_pi_g2 || (n_shifts && !out_w_g2));
+    int32_t rc = header_batch_prefix("kzg_header_group_sums", ctx, out_null, commitments_xy, length_commitments, length_proofs, claimed_lens, count, shift_lens,
+                                     g1_tau_shifts_xy, n_shifts, weights_mont, grp, bad_index, &empty, &st);
+    if (rc != KZG_OK) return rc;
+    HeaderGroupSums gs;
+    if (!empty) {
+        rc = header_group_sums_core(ctx, st, commitments_xy, count, n_shifts, group_indices, n_groups, &gs);
+        if (rc != KZG_OK) return rc;
+        st.lk.unlock();
+    }
+    if (n_groups) {                                                  // an empty group, an unclaimed class: identities
+        memset(out_u_xy, 0, n_groups * 64);
+        memset(out_u_is_infinity, 1, n_groups);
+        if (n_shifts) memset(out_w_g2, 0, n_groups * n_shifts * 128);
+        memset(out_pi_g2, 0, n_groups * 128);
+    }
+    const size_t S = gs.g1_plan.segs.size(), per = 256;
+    std::vector<uint64_t> xy(8 * S);
+    host_parallel_for((S + per - 1) / per, [&](size_t c) {
+        const size_t a = c * per, b = std::min(S, (c + 1) * per);
+        kzg_host::xyzz_batch_to_affine(gs.u.data() + a, b - a, xy.data() + 8 * a);
+    });
+    for (size_t j = 0; j < S; ++j) {
+        memcpy(out_u_xy + 8 * (size_t)gs.g1_plan.segs[j], xy.data() + 8 * j, 64);
+        out_u_is_infinity[gs.g1_plan.segs[j]] = kzg_host::is_inf(gs.u[j]) ? 1 : 0;
+    }
+    const size_t n_w = n_groups * n_shifts;                          // a key below it is g n_shifts + s: the row of W_{g,s} in out_w_g2
+    for (size_t j = 0; j < gs.g2_plan.segs.size(); ++j) {
+        const size_t key = gs.g2_plan.segs[j];
+        memcpy(key < n_w ? out_w_g2 + 16 * key : out_pi_g2 + 16 * (key - n_w), gs.q.data() + 16 * j, 128);
+    }
+    return KZG_OK;
+}
+
+int32_t kzg_verify_length_proof_batch_locate(kzg_ctx* ctx, const uint64_t* commitments_xy, const uint64_t* length_commitments, const uint64_t* length_proofs,
+                                             const uint64_t* claimed_lens, size_t count, const uint64_t* shift_lens, const uint64_t* g1_tau_shifts_xy,
+                                             size_t n_shifts, const uint64_t* weights_mont, const uint64_t* group_indices, size_t n_groups,
+                                             uint8_t* out_group_ok, size_t* out_bad_groups, size_t* out_pairing_checks, uint64_t* bad_index) {
+    using namespace kzg_host;
+    HeaderStage st;
+    HeaderGrouping grp;
+    grp.on = true; grp.group_indices = group_indices; grp.n_groups = n_groups;
+    bool empty = false;
+    int32_t rc = header_batch_prefix("kzg_verify_length_proof_batch_locate", ctx, !out_bad_groups || (n_groups && !out_group_ok), commitments_xy, length_commitments,
+                                     length_proofs, claimed_lens, count, shift_lens, g1_tau_shifts_xy, n_shifts, weights_mont, grp, bad_index, &empty, &st);
+    if (rc != KZG_OK) return rc;
+    if (empty) {                                                     // nothing to refuse: no device work, no pairing
+        if (n_groups) memset(out_group_ok, 1, n_groups);
+        *out_bad_groups = 0;
+        if (out_pairing_checks) *out_pairing_checks = 0;
+        return KZG_OK;
+    }
+    const auto t_sums = Clock::now();
+    HeaderGroupSums gs;
+    rc = header_group_sums_core(ctx, st, commitments_xy, count, n_shifts, group_indices, n_groups, &gs);
+    if (rc != KZG_OK) return rc;
+    st.lk.unlock();                                                  // the rest is host work
+    const auto t_host = Clock::now();
+    // the leaves: U_g on the left, (Pi_g, W_{g,s} for the classes present) on the right
+    const HeaderClasses cls = header_present_classes(st.length_class.data(), count, n_shifts);
+    using Sums = HeaderSums<Xyzz, G2Jac>;
+    std::vector<Sums> lhs, rhs;
+    header_assemble(gs.g1_plan, gs.g2_plan, n_groups, n_shifts, cls, [&](size_t j) { return gs.u[j]; },
+                    [&](size_t j) { return g2j_from_affine(g2_from_wire(gs.q.data() + 16 * j)); }, xyzz_inf(), g2j_inf(), &lhs, &rhs);
+    // what every test multiplies: rho on the G1 side, once per call
+    const uint64_t* rho = st.canon.data() + 4 * count;
+    G1 g1; g1.x = FQ_ONE; g1.y = FQ_TWO; g1.inf = false;
+    HeaderFixed<G1, G2> fx;
+    fx.g2 = g2_generator();
+    fx.neg_g1 = g1_neg(g1);
+    fx.neg_rho_g1 = g1_neg(g1_mul(g1, rho));
+    for (uint32_t s : cls.present) fx.rho_shift.push_back(g1_mul(st.shifts[s], rho));
+    struct OpsA {
+        Xyzz zero() const { return xyzz_inf(); }
+        Xyzz add(const Xyzz& a, const Xyzz& b) const { return xyzz_add(a, b); }
+        Xyzz sub(const Xyzz& a, Xyzz b) const { b.y = neg(b.y); return xyzz_add(a, b); }
+    };
+    struct OpsB {
+        G2Jac zero() const { return g2j_inf(); }
+        G2Jac add(const G2Jac& a, const G2Jac& b) const { return g2j_add(a, b); }
+        G2Jac sub(const G2Jac& a, const G2Jac& b) const { return g2j_add(a, g2j_neg(b)); }
+    };
+    bool first = true;
+    auto t_search = t_host;
+    auto holds = [&](const Sums& l, const Sums& r) {
+        if (first) { first = false; t_search = Clock::now(); }      // the prefix sums end where the first test begins
+        uint64_t a[8];
+        uint8_t u_inf = 0;
+        xyzz_to_affine(l.u, a, &u_inf);
+        G1 U = g1_from_wire(a);
+        if (u_inf) U.inf = true;
+        std::vector<G2> q(1 + cls.present.size(), g2_inf());
+        G2Jac sum_w = g2j_inf();
+        for (size_t k = 0; k < r.q.size() && k < q.size(); ++k) {
+            q[k] = g2j_to_affine(r.q[k]);
+            if (k) sum_w = g2j_add(sum_w, r.q[k]);
+        }
+        std::vector<G1> ps;
+        std::vector<G2> qs;
+        header_pairs(fx, U, q, g2j_to_affine(sum_w), &ps, &qs);
+        return pairings_product_is_one(ps.data(), qs.data(), (int)ps.size(), host_parallel_for);
+    };
+    size_t bad = 0;
+    const size_t checks = locate_search(lhs.data(), rhs.data(), n_groups, HeaderSumOps<Xyzz, G2Jac, OpsA, OpsB>(), holds, out_group_ok, &bad);
+    *out_bad_groups = bad;
+    if (out_pairing_checks) *out_pairing_checks = checks;
+    if (opts().vb_trace)
+        fprintf(stderr, "  verify_length_proof_batch_locate count=%zu groups=%zu classes=%zu bits=%d: shared prefix %.3f ms, G2 group sums %.3f ms, G1 group sums %.3f ms, "
+                "host sums %.3f ms, search %.3f ms, %zu pairing checks, %zu bad groups\n", count, n_groups, cls.present.size(), st.bits, ms_between(st.t0, t_sums), gs.ms_g2,
+                gs.ms_g1, ms_between(t_host, t_search), ms_between(t_search, Clock::now()), checks, bad);
     return KZG_OK;
 }
 

@@ -139,7 +139,7 @@ struct kzg_ctx {
     kzg::NttWorkspace mp_ntt;
     kzg::DeviceBuffer mv[4];                   // kzg_coset_interpolate_rlc / kzg_verify_multiproof_batch (multiverify.hip): values | indices + weights | coefficients | partial rows
     kzg::NttWorkspace mv_ntt;
-    kzg::DeviceBuffer ml[6];                   // kzg_coset_group_sums / kzg_verify_multiproof_batch_locate (multilocate.hip): group coefficients | the plan's arrays | partial point sums | group sums | rows + shifted weights | proofs + commitments
+    kzg::DeviceBuffer ml[6];                   // kzg_coset_group_sums / kzg_verify_multiproof_batch_locate (multilocate.hip): group coefficients | the plan's arrays | partial point sums | group sums | rows + shifted weights | proofs + commitments; kzg_header_group_sums (capi_g2.hip) works in [1] .. [5] the same way
     kzg::DeviceBuffer fs[2];                  // the coset transcript on the device (fsdevice.hip): commitment rows | proofs, digests | power tables | flag; kzg_sha256_rows: messages, digests
     kzg::DeviceBuffer cb[2];                   // serialized coset items (cosetbytes.hip): value bytes | point bytes (commitments, proofs), decoded wire points, the bad words
     kzg::DeviceBuffer rc[3];                   // kzg_recover_from_cosets(_batch) (recover.hip), for a group of blobs: work values | item maps, patterns, missing lists, flags, vanishing values, partial products (RecoverBatchPlan's layout) | powers of g
@@ -302,6 +302,10 @@ int32_t g2_subgroup_check(kzg_ctx* ctx, const uint4* d_points, size_t n, int64_t
 // every tile of 64 lanes is summed: out_tiles_g2 = n_lanes / 64 affine wire points.  n_lanes is a multiple of 64.
 int32_t g2_weighted_tile_sums(kzg_ctx* ctx, const uint4* d_points, size_t n_points, const uint32_t* lanes, size_t n_lanes, const uint32_t* weights_canonical,
                               size_t n_weights, uint32_t weight_shift, int bits, uint64_t* out_tiles_g2);
+// One sum per SEGMENT of a plan over one key per point (locate_plan of host_locate.h on n_points keys): point p is multiplied by weight p >> 1 (canonical
+// words, the low `bits` bits) and the points of a segment are summed: out_seg_g2 = plan.segs.size() affine wire points.  n_points <= 2^21.  Uses ctx->ml[1..3]
+int32_t g2_locate_segment_sums(kzg_ctx* ctx, const uint4* d_points, size_t n_points, const LocatePlan& plan, const uint32_t* weights_canonical, size_t n_weights,
+                               int bits, uint64_t* out_seg_g2);
 // g2decode.hip: n gnark-compressed points of the host decoded on the device (g2_decode.h; flags: KZG_G2_CHECK_SUBGROUP | KZG_G2_REJECT_GENERATOR) into
 // d_points (device format) or, with d_points == nullptr, as wire points to out_wire (host; written only when no point is refused).
 // *bad_word = index << 2 | kind (G2_BAD_* of g2_decode.h) of the smallest refused index, or 0xFFFFFFFF
@@ -339,6 +343,9 @@ int32_t locate_upload_plan(kzg_ctx* ctx, const LocatePlan& plan);
 int32_t coset_group_coeffs_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, const LocatePlan& plan, size_t n, size_t l);
 int32_t locate_point_sums_device(kzg_ctx* ctx, const uint4* d_points, const uint64_t* d_ci, const uint4* d_w, const uint4* d_w2, const LocatePlan& plan,
                                  uint64_t* out_xyzz);
+// the one-sum form (the header batch): per non-empty group the XYZZ wire words (16 u64) of sum [w_i] P_i over plan.count device-format points and
+// wire weights in the caller's order; the plan uploaded by locate_upload_plan (synchronised)
+int32_t locate_group_sums_g1_device(kzg_ctx* ctx, const uint4* d_points, const uint4* d_w, const LocatePlan& plan, uint64_t* out_xyzz);
 // hashing on the device (fsdevice.hip).  Called under ctx->mu with the device set.
 // count messages of row_len bytes each (host, stride row_len) -> count SHA-256 digests (host); synchronised on return
 int32_t sha256_rows_run(kzg_ctx* ctx, const uint8_t* msgs, size_t row_len, size_t count, uint8_t* out_digests);

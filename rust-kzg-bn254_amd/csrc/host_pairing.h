@@ -158,6 +158,37 @@ inline G2Jac g2j_madd(const G2Jac& t, const G2& p) {               // mixed addi
     r.Z = mul(t.Z, H);
     return r;
 }
+// the general addition (add-2007-bl without the Z doubling), the negation and the way back: the prefix sums of kzg_verify_length_proof_batch_locate
+inline G2Jac g2j_inf() { G2Jac r; memset(&r, 0, sizeof r); r.inf = true; return r; }
+inline G2Jac g2j_from_affine(const G2& p) {
+    if (p.inf) return g2j_inf();
+    G2Jac r; r.X = p.x; r.Y = p.y; r.Z = {FQ_ONE, fq_zero()}; r.inf = false;
+    return r;
+}
+inline G2Jac g2j_neg(const G2Jac& t) { G2Jac r = t; if (!t.inf) r.Y = neg(t.Y); return r; }
+inline G2Jac g2j_add(const G2Jac& a, const G2Jac& b) {
+    if (a.inf) return b;
+    if (b.inf) return a;
+    const Fq2 Z1Z1 = sqr(a.Z), Z2Z2 = sqr(b.Z);
+    const Fq2 U1 = mul(a.X, Z2Z2), U2 = mul(b.X, Z1Z1);
+    const Fq2 S1 = mul(a.Y, mul(b.Z, Z2Z2)), S2 = mul(b.Y, mul(a.Z, Z1Z1));
+    const Fq2 H = sub(U2, U1), rr = sub(S2, S1);
+    if (is_zero(H)) return is_zero(rr) ? g2j_dbl(a) : g2j_inf();
+    const Fq2 HH = sqr(H), HHH = mul(H, HH), V = mul(U1, HH);
+    G2Jac r; r.inf = false;
+    r.X = sub(sub(sqr(rr), HHH), dbl2(V));
+    r.Y = sub(mul(rr, sub(V, r.X)), mul(S1, HHH));
+    r.Z = mul(mul(a.Z, b.Z), H);
+    return r;
+}
+inline G2 g2j_to_affine(const G2Jac& t) {
+    if (t.inf) return g2_inf();
+    const Fq2 zi = inv(t.Z), zi2 = sqr(zi);
+    G2 r; r.inf = false;
+    r.x = mul(t.X, zi2);
+    r.y = mul(t.Y, mul(zi2, zi));
+    return r;
+}
 inline G2 g2_mul(const G2& p, const uint64_t k[4]) {
     G2Jac acc; acc.inf = true; acc.X = {fq_zero(), fq_zero()}; acc.Y = acc.X; acc.Z = acc.X;
     for (int i = 255; i >= 0; --i) {

@@ -24,6 +24,8 @@
 //     xyzz_scalar_mul (identity base, zero scalar).  Points are validated on upload (points_wire_to_device with the curve check).
 //   * no atomics, no floating point; the sums are group elements and leave as canonical affine words, so equal inputs give equal bits
 //     whatever the order of the items inside a group and whatever the grid.
+//   * the header batch (capi_g2.hip kzg_header_group_sums) takes the same two kernels with ONE sum per segment, U_g = sum_{i in g} r_i C_i:
+//     the template parameter SUMS of k_locate_terms / k_locate_fold, driven by locate_group_sums_g1_device.
 // Not tried: a joint (Shamir) chain for the two multiplications of pi_i, lane pairs (glv_lanes.h), a fused interpolation + segment sum.
 #include "coset_kernels.h"
 #include "glv.h"
@@ -127,46 +129,51 @@ struct LocateArgs {
 // Lane s < count (sorted position): item i = perm[s]; a = [r_i] pi_i, b = [r_i] C_{c_i} + [r_i w^(k_i l)] pi_i; then the scan; the first
 // lane of each (wave, segment) stores both sums at slot part_off[seg] + wave - seg_off[seg] / 64 (< part_off[seg + 1] by host_locate.h's
 // count of the waves a segment touches).  No lane returns before the scan.
+// SUMS = 1 (the header batch, capi_g2.hip): the one sum [w_i] points[i] per segment, no second scalar, no commitment row.
+template <int SUMS>
 __global__ void __launch_bounds__(256)
 k_locate_terms(LocateArgs a) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
     const bool active = s < a.count;
     Xyzz l, r;
     xyzz_set_inf(l);
-    xyzz_set_inf(r);
+    if (SUMS == 2) xyzz_set_inf(r);
     uint32_t key = 0xFFFFFFFFu;
     if (active) {
         const uint32_t i = a.perm[s];
         key = a.seg_of[s];
         const uint4* proof = a.points + 4 * (size_t)i;
         locate_term(l, a.w + 2 * (size_t)i, proof);
-        Xyzz t, u;
-        locate_term(t, a.w2 + 2 * (size_t)i, proof);
-        locate_term(u, a.w + 2 * (size_t)i, a.points + 4 * ((size_t)a.n_proofs + (size_t)a.ci[i]));
-        xyzz_add<true>(r, u, t);
+        if (SUMS == 2) {
+            Xyzz t, u;
+            locate_term(t, a.w2 + 2 * (size_t)i, proof);
+            locate_term(u, a.w + 2 * (size_t)i, a.points + 4 * ((size_t)a.n_proofs + (size_t)a.ci[i]));
+            xyzz_add<true>(r, u, t);
+        }
     }
     locate_seg_scan(l, key, active, lane);
-    locate_seg_scan(r, key, active, lane);
+    if (SUMS == 2) locate_seg_scan(r, key, active, lane);
     const uint32_t kprev = __shfl_up(key, 1, 64);
     if (active && (lane == 0 || kprev != key)) {
         const uint32_t slot = a.part_off[key] + (s >> 6) - (a.seg_off[key] >> 6);
-        xyzz_store(a.partial, 2 * (size_t)a.n_part, slot, l);
-        xyzz_store(a.partial, 2 * (size_t)a.n_part, (size_t)a.n_part + slot, r);
+        xyzz_store(a.partial, SUMS * (size_t)a.n_part, slot, l);
+        if (SUMS == 2) xyzz_store(a.partial, 2 * (size_t)a.n_part, (size_t)a.n_part + slot, r);
     }
 }
 
-// One wave per (segment, sum): workgroup 2 j + q adds the partials [part_off[j], part_off[j + 1]) of sum q (0: L, 1: R) and leaves the 32
-// XYZZ wire words at out[2 j + q].
+// One wave per (segment, sum): workgroup SUMS j + q adds the partials [part_off[j], part_off[j + 1]) of sum q (0: L, 1: R) and leaves the 32
+// XYZZ wire words at out[SUMS j + q].
+template <int SUMS>
 __global__ void __launch_bounds__(64)
 k_locate_fold(const int32_t* __restrict__ partial, uint32_t n_part, const uint32_t* __restrict__ part_off, uint32_t* __restrict__ out_wire) {
-    const uint32_t j = blockIdx.x >> 1, q = blockIdx.x & 1, lane = threadIdx.x;
+    const uint32_t j = blockIdx.x / SUMS, q = blockIdx.x % SUMS, lane = threadIdx.x;
     const uint32_t p0 = part_off[j], p1 = part_off[j + 1];
     Xyzz acc;
     xyzz_set_inf(acc);
 #pragma unroll 1
     for (uint32_t p = p0 + lane; p < p1; p += 64) {
         Xyzz v, t;
-        xyzz_load(v, partial, 2 * (size_t)n_part, (size_t)q * n_part + p);
+        xyzz_load(v, partial, SUMS * (size_t)n_part, (size_t)q * n_part + p);
         xyzz_add<true>(t, acc, v);
         acc = t;
     }
@@ -254,11 +261,34 @@ int32_t locate_point_sums_device(kzg_ctx* ctx, const uint4* d_points, const uint
     a.perm = d_plan; a.seg_of = d_plan + N; a.seg_off = d_plan + 2 * N; a.part_off = d_plan + 2 * N + S + 1;
     a.ci = d_ci; a.w = d_w; a.w2 = d_w2;
     a.partial = ctx->ml[2].as<int32_t>(); a.n_part = (uint32_t)n_part;
-    hipLaunchKernelGGL(k_locate_terms, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_locate_terms<2>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, a);
     KZG_HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_locate_fold, dim3((unsigned)(2 * S)), dim3(64), 0, ctx->stream, a.partial, a.n_part, a.part_off, ctx->ml[3].as<uint32_t>());
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_locate_fold<2>), dim3((unsigned)(2 * S)), dim3(64), 0, ctx->stream, a.partial, a.n_part, a.part_off, ctx->ml[3].as<uint32_t>());
     KZG_HIP_TRY(ctx, hipGetLastError());
     KZG_HIP_TRY(ctx, hipMemcpyAsync(out_xyzz, ctx->ml[3].p, S * 2 * 128, hipMemcpyDeviceToHost, ctx->stream));
+    KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return KZG_OK;
+}
+
+// The one-sum form (the header batch): d_points `count` device-format points and d_w their wire weights, both in the caller's order; the plan
+// (of the headers by group) uploaded by locate_upload_plan -> out_xyzz: per segment the XYZZ wire words (16 u64) of sum [w_i] P_i.
+// Synchronised on return.  count > 0.
+int32_t locate_group_sums_g1_device(kzg_ctx* ctx, const uint4* d_points, const uint4* d_w, const LocatePlan& plan, uint64_t* out_xyzz) {
+    RoctxRange range("kzg:locate_group_sums_g1");
+    const size_t N = plan.count, S = plan.segs.size(), n_part = plan.part_off.back();
+    KZG_HIP_TRY(ctx, ctx->ml[2].reserve(n_part * 4 * NL * 4));
+    KZG_HIP_TRY(ctx, ctx->ml[3].reserve(S * 128));
+    const uint32_t* d_plan = ctx->ml[1].as<uint32_t>();
+    LocateArgs a;
+    a.points = d_points; a.n_proofs = 0; a.count = (uint32_t)N;
+    a.perm = d_plan; a.seg_of = d_plan + N; a.seg_off = d_plan + 2 * N; a.part_off = d_plan + 2 * N + S + 1;
+    a.ci = nullptr; a.w = d_w; a.w2 = nullptr;
+    a.partial = ctx->ml[2].as<int32_t>(); a.n_part = (uint32_t)n_part;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_locate_terms<1>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, a);
+    KZG_HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_locate_fold<1>), dim3((unsigned)S), dim3(64), 0, ctx->stream, a.partial, a.n_part, a.part_off, ctx->ml[3].as<uint32_t>());
+    KZG_HIP_TRY(ctx, hipGetLastError());
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(out_xyzz, ctx->ml[3].p, S * 128, hipMemcpyDeviceToHost, ctx->stream));
     KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return KZG_OK;
 }

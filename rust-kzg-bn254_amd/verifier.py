@@ -115,19 +115,30 @@ def verify_length_proof_batch(commitments, length_commitments, length_proofs, cl
     """`count` blob headers (C_i, C2_i, pi2_i, d_i) in ONE product of pairings (`kzg_verify_length_proof_batch`): the on-twist and
     order-r subgroup tests of both G2 elements and the weighted sums run on the GPU.  shifts = {d: [tau^(N-d)]_1} for every claimed
     length (header_shifts builds it from a G1 SRS); weights = None derives them from the transcript, else (count + 1, 4) Fr wire
-    words r_0 .. r_(count-1), rho.  False = the equation failed (some header is bad: bisect); NotOnCurveError names the first header
-    with an input off its curve or outside the subgroup."""
+    words r_0 .. r_(count-1), rho.  False = the equation failed (some header is bad: `locate_bad_headers` names it);
+    NotOnCurveError names the first header with an input off its curve or outside the subgroup."""
     c, c2, p2, lens, shift_lens, shift_pts = _header_args(commitments, length_commitments, length_proofs, claimed_lens, shifts)
-    w = None
-    if weights is not None:
-        w = np.ascontiguousarray(_lib.as_u64(weights, 4)).reshape(-1, 4)
-        if len(w) != len(c) + 1:
-            raise InvalidInputLength()
+    w = _header_weights(weights, len(c))
     ctx = ctx or _lib.default_context()                             # (no context is created before the arguments pass)
     ok = _lib.i32(0)
     bad = C.c_uint64(0)
     rc = _lib.load().kzg_verify_length_proof_batch(ctx.handle, _opt(c), _opt(c2), _opt(p2), _opt(lens), len(c), _opt(shift_lens), _opt(shift_pts),
                                                    len(shift_lens), None if w is None else _lib.ptr(w), C.byref(ok), C.byref(bad))
+    _raise_for_header(rc, bad, len(c), len(shift_lens), ctx)
+    return bool(ok.value)
+
+
+def _header_weights(weights, count):
+    if weights is None:
+        return None
+    w = np.ascontiguousarray(_lib.as_u64(weights, 4)).reshape(-1, 4)
+    if len(w) != count + 1:
+        raise InvalidInputLength()
+    return w
+
+
+def _raise_for_header(rc, bad, count, n_shifts, ctx, grouped=False):
+    """the statuses of the header-batch entries (kzg_verify_length_proof_batch and the two grouped entries behind it)"""
     if rc == _lib.ERR_G1_NOT_ON_CURVE:
         raise NotOnCurveError("G1 point %d not on curve" % bad.value)
     if rc == _lib.ERR_G2_TAU_NOT_ON_CURVE:
@@ -136,10 +147,62 @@ def verify_length_proof_batch(commitments, length_commitments, length_proofs, cl
         raise NotOnCurveError("G2 point of header %d not in correct subgroup" % bad.value)
     if rc == _lib.ERR_NOT_POWER_OF_TWO:
         raise GenericError("a claimed length is not a power of two")
-    if rc == _lib.ERR_INVALID_ARG and len(c) and len(shift_lens):
-        raise GenericError("a claimed length has no shift, a shift length is listed twice, more than 64 shifts, or slot 0 is in flight")
+    if rc == _lib.ERR_INVALID_ARG and count and n_shifts:
+        raise GenericError("a claimed length has no shift, a shift length is listed twice, more than 64 shifts, " +
+                           ("a group index is not below n_groups, " if grouped else "") + "or slot 0 is in flight")
     _raise_for(rc, ctx)
-    return bool(ok.value)
+
+
+def _header_group_args(groups, n_groups, count):
+    """(group index per header, n_groups) for `groups` = "item" (one group per header) or an integer array with `n_groups`"""
+    if isinstance(groups, str) and groups != "item":
+        raise GenericError('groups is "item" or an array of group indices')
+    return _group_args(groups, n_groups, None, 0, count)
+
+
+def header_group_sums(commitments, length_commitments, length_proofs, claimed_lens, shifts, weights=None, ctx=None, groups="item", n_groups=None):
+    """The components of every group's own header equation (`kzg_header_group_sums`), one pass on the GPU: U_g = sum r_i C_i,
+    W_(g,s) = sum over the group's headers of the s-th listed length of r_i C2_i, Pi_g = sum r_i pi2_i, with the weights of
+    `verify_length_proof_batch`.  Group g is good iff e(U_g, G2) e(-G1, sum_s W_(g,s) + [rho]Pi_g) prod_s e([rho]T_s, W_(g,s)) = 1, and the
+    sums over all groups are what `verify_length_proof_batch` checks.  `groups` as for `locate_bad_headers`.  Returns (u, u_is_infinity,
+    w, pi): (n_groups, 8) G1 wire points with a bool array, (n_groups, len(shifts), 16) and (n_groups, 16) G2 wire points (the identity
+    all zeros; the length classes in the order of `shifts`); an empty group gives identities."""
+    c, c2, p2, lens, shift_lens, shift_pts = _header_args(commitments, length_commitments, length_proofs, claimed_lens, shifts)
+    w = _header_weights(weights, len(c))
+    gi, n_groups = _header_group_args(groups, n_groups, len(c))
+    ctx = ctx or _lib.default_context()
+    n_shifts = len(shift_lens)
+    u, uinf = np.zeros((n_groups, 8), np.uint64), np.zeros(max(n_groups, 1), np.uint8)
+    wg, pi = np.zeros((n_groups, n_shifts, 16), np.uint64), np.zeros((n_groups, 16), np.uint64)
+    bad = C.c_uint64(0)
+    rc = _lib.load().kzg_header_group_sums(ctx.handle, _opt(c), _opt(c2), _opt(p2), _opt(lens), len(c), _opt(shift_lens), _opt(shift_pts), n_shifts,
+                                           None if w is None else _lib.ptr(w), _opt(gi), n_groups, _opt(u), uinf.ctypes.data_as(_lib.u8p), _opt(wg), _opt(pi),
+                                           C.byref(bad))
+    _raise_for_header(rc, bad, len(c), n_shifts, ctx, grouped=True)
+    return u, uinf[:n_groups].astype(bool), wg, pi
+
+
+def locate_bad_headers(commitments, length_commitments, length_proofs, claimed_lens, shifts, weights=None, ctx=None, groups="item", n_groups=None):
+    """Which groups of a batch of blob headers are bad (`kzg_verify_length_proof_batch_locate`): the group sums once on the GPU, then a
+    search of the tree of those sums on the host, one product of pairings per step and at most 1 + 2 b ceil(log2 n_groups) of them for b
+    bad groups.  `groups` = "item" (one group per header) or an integer array of group indices with `n_groups`; the other arguments are
+    those of `verify_length_proof_batch`.  Returns (good, pairing_checks): a bool array of length n_groups (True = good) and the number
+    of pairing checks; all True is the accept of `verify_length_proof_batch`.  This call always pays for the group sums: a caller who
+    expects good batches calls `verify_length_proof_batch` first and this only after a reject.  The verdicts are sound for derived
+    weights (weights=None, or `compute_header_batch_weights`); bad groups can cancel inside a range under weights of the caller's own."""
+    c, c2, p2, lens, shift_lens, shift_pts = _header_args(commitments, length_commitments, length_proofs, claimed_lens, shifts)
+    w = _header_weights(weights, len(c))
+    gi, n_groups = _header_group_args(groups, n_groups, len(c))
+    ctx = ctx or _lib.default_context()
+    good = np.zeros(max(n_groups, 1), np.uint8)
+    n_bad, checks, bad = _lib.sz(0), _lib.sz(0), C.c_uint64(0)
+    rc = _lib.load().kzg_verify_length_proof_batch_locate(ctx.handle, _opt(c), _opt(c2), _opt(p2), _opt(lens), len(c), _opt(shift_lens), _opt(shift_pts),
+                                                          len(shift_lens), None if w is None else _lib.ptr(w), _opt(gi), n_groups,
+                                                          good.ctypes.data_as(_lib.u8p), C.byref(n_bad), C.byref(checks), C.byref(bad))
+    _raise_for_header(rc, bad, len(c), len(shift_lens), ctx, grouped=True)
+    good = good[:n_groups].astype(bool)
+    assert int(n_bad.value) == int((~good).sum())
+    return good, int(checks.value)
 
 
 def verify_blob_kzg_proof(blob, commitment, proof, g2_tau=None, ctx=None) -> bool:
