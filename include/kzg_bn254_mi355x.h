@@ -358,6 +358,56 @@ typedef struct kzg_encode_batch_info {
 } kzg_encode_batch_info;
 int32_t kzg_encode_cosets_batch_info(size_t poly_len /* d */, size_t n, size_t chunk_len, size_t count, int32_t values, int32_t proofs,
                                      size_t group_bytes, kzg_encode_batch_info* out);
+/* The values and the proofs of SELECTED cosets of polynomials the caller holds, without computing every proof: what a node answers a
+ * sampling request with, what a disperser re-sends, what a retriever re-seeds after kzg_recover_from_cosets.  The conventions are
+ * kzg_encode_cosets': polys holds `count` polynomials of d = poly_len elements each (coefficients, or with eval_form = 1 evaluations on
+ * the d-point domain; each REFERENCED polynomial is inverse-NTT'd once on the device), n = r d, l = chunk_len, m = n / l.
+ * n_items (polynomial, coset) pairs: item i is coset coset_indices[i] < m of polynomial poly_indices[i] < count (poly_indices NULL: every
+ * item is of polynomial 0).  Row i of out_ys (n_items x l x 4) and out_proofs_xy (n_items x 8) / out_is_infinity (n_items) is bit for bit
+ * row coset_indices[i] of kzg_encode_cosets on that polynomial.  Either output may be NULL (it is then not computed), not both.
+ * Per item the device divides f by X^l - w^(k l) (d field products in lanes of at most 64 dependent ones; the remainder gives the values
+ * through one l-point NTT) and commits the quotient over the first d points of the SRS: k d MSM terms for k items, against the 2d
+ * scalar multiplications and two G1 FFTs of the encoder -- the cheaper route for a few cosets (profiles/prove_cosets.md has the
+ * crossover).  The items are worked through in GROUPS whose device workspace (per item: its d x 32-byte quotient row, the segment heads,
+ * the remainder) fits the budget of kzg_ctx_set_encode_group_bytes (default 4 GiB; a group is never smaller than one item; the bits do
+ * not depend on it); the proofs of a group are one batched commitment (kzg_commit_coeff_form_batch's path: the SRS gets its per-bit
+ * tables on first use), of a group of one item a single MSM.  Duplicate items are allowed and give equal rows.
+ * Errors, checked on the host before any kernel runs, in this order:
+ *   1. a null ctx, srs, polys or coset_indices; both outputs NULL; proofs without flags; count = 0 -> KZG_ERR_INVALID_ARG;
+ *   2. srs of another context, or a Lagrange-basis handle -> KZG_ERR_INVALID_ARG;
+ *   3. rows 3, 4, 5 and 6 of kzg_encode_cosets' table, with its codes;
+ *   4. a polynomial index >= count or a coset index >= m -> KZG_ERR_INVALID_ARG, *bad_index (may be NULL) = the smallest such item;
+ *   5. sizes that overflow size_t (count x d x 32 bytes, n_items x the largest output row) -> KZG_ERR_INVALID_ARG.
+ * n_items = 0 (after these checks) -> KZG_OK, nothing written, no device work.  The call is synchronous on slot 0: while a kzg_*_begin
+ * is in flight there it returns KZG_ERR_INVALID_ARG (with proofs: while one is in flight on any slot, as the batched commitments use
+ * them all).  A failed allocation -> KZG_ERR_DEVICE.  After any error the context stays usable. */
+int32_t kzg_prove_cosets(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* polys_mont /* count x d x 4 */, size_t count, size_t poly_len /* d */,
+                         int32_t eval_form, size_t n, size_t chunk_len, const uint64_t* poly_indices /* n_items, may be NULL */,
+                         const uint64_t* coset_indices /* n_items */, size_t n_items, uint64_t* out_ys_mont /* n_items x l x 4, may be NULL */,
+                         uint64_t* out_proofs_xy_mont /* n_items x 8, may be NULL */, uint8_t* out_is_infinity /* n_items */, uint64_t* bad_index);
+/* The quotient polynomials themselves: row i of out_q (n_items x d x 4 canonical wire words, the top l of each row zero) holds the
+ * coefficients of f / (X^l - w^(k l)) for item i, and / or the values out_ys as above: no SRS.  Either output may be NULL, not both.
+ * The errors are those of kzg_prove_cosets without the SRS (no check 2, no row 6), the largest output row being d x 32 bytes. */
+int32_t kzg_coset_quotients(kzg_ctx* ctx, const uint64_t* polys_mont /* count x d x 4 */, size_t count, size_t poly_len /* d */, int32_t eval_form,
+                            size_t n, size_t chunk_len, const uint64_t* poly_indices /* n_items, may be NULL */, const uint64_t* coset_indices,
+                            size_t n_items, uint64_t* out_q_mont /* n_items x d x 4, may be NULL */, uint64_t* out_ys_mont, uint64_t* bad_index);
+/* What kzg_prove_cosets would do with these arguments: a pure query (no context, no device).  values / proofs: which outputs are asked
+ * for (proofs: the quotient rows are kept, as kzg_coset_quotients with out_q does); group_bytes: the budget, 0 = the default.  Errors: out
+ * NULL, neither output or count = 0 -> KZG_ERR_INVALID_ARG, then rows 3, 4 and 5 of kzg_encode_cosets' table and check 5 above. */
+typedef struct kzg_prove_cosets_info_t {    /* (_t: C has one name space for the struct and the function) */
+    uint64_t items_per_group;            /* the last group of a call may hold fewer */
+    uint64_t groups;
+    uint64_t group_bytes;                /* device workspace of one full group */
+    uint64_t item_bytes;                 /* of one item */
+    uint32_t seg_len;                    /* S: the most dependent field products a lane runs in one pass */
+    uint32_t segments;                   /* segments of one chain of d / l coefficients */
+    uint32_t carry_levels;               /* passes of the same recurrence over the segment heads (0: a chain is one segment) */
+    uint32_t launches;                   /* kernel launches of a group in front of the MSM: local and fix-up passes, the values' NTT passes */
+    uint32_t msm_single;                 /* 1: a group is one item and its proof is a single MSM, 0: a batched commitment */
+    uint32_t reserved;
+} kzg_prove_cosets_info_t;
+int32_t kzg_prove_cosets_info(size_t poly_len /* d */, size_t n, size_t chunk_len, size_t count, size_t n_items, int32_t values, int32_t proofs,
+                              size_t group_bytes, kzg_prove_cosets_info_t* out);
 /* KZG::compute_proof / compute_proof_impl (kzg.rs:128-178, :215-234, on-domain branch :237-260).
  * roots = KZG::expanded_roots_of_unity (n_roots entries); n != n_roots -> KZG_ERR_ROOTS_LENGTH.
  * out_y (optional, 4 u64) receives y = p(z) (helpers.rs:475-535). */

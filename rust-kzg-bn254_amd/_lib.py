@@ -58,6 +58,12 @@ class RecoverBatchInfo(C.Structure):                             # kzg_recover_b
     _fields_ = [("blobs_per_group", C.c_uint64), ("groups", C.c_uint64), ("group_bytes", C.c_uint64), ("blob_bytes", C.c_uint64)]
 
 
+class ProveCosetsInfo(C.Structure):                              # kzg_prove_cosets_info_t of the header
+    _fields_ = [("items_per_group", C.c_uint64), ("groups", C.c_uint64), ("group_bytes", C.c_uint64), ("item_bytes", C.c_uint64),
+                ("seg_len", C.c_uint32), ("segments", C.c_uint32), ("carry_levels", C.c_uint32), ("launches", C.c_uint32),
+                ("msm_single", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class G2BatchInfo(C.Structure):                                 # kzg_g2_batch_info of the header
     _fields_ = [("blobs_per_group", C.c_uint64), ("groups", C.c_uint64), ("entries", C.c_uint64), ("workspace_bytes", C.c_uint64),
                 ("batched", C.c_uint32), ("c", C.c_uint32), ("W", C.c_uint32), ("G", C.c_uint32), ("nl", C.c_uint32), ("seg", C.c_uint32),
@@ -130,6 +136,9 @@ PROTOTYPES = {
     "kzg_encode_cosets_batch": (i32, [vp, vp, u64p, sz, sz, i32, sz, sz, u64p, u64p, u8p]),
     "kzg_ctx_set_encode_group_bytes": (i32, [vp, sz]),
     "kzg_encode_cosets_batch_info": (i32, [sz, sz, sz, sz, i32, i32, sz, vp]),
+    "kzg_prove_cosets": (i32, [vp, vp, u64p, sz, sz, i32, sz, sz, u64p, u64p, sz, u64p, u64p, u8p, u64p]),
+    "kzg_coset_quotients": (i32, [vp, u64p, sz, sz, i32, sz, sz, u64p, u64p, sz, u64p, u64p, u64p]),
+    "kzg_prove_cosets_info": (i32, [sz, sz, sz, sz, sz, i32, i32, sz, vp]),
     "kzg_srs_cache_multiproof": (i32, [vp, vp, sz, sz]),
     "kzg_srs_drop_multiproof": (i32, [vp, vp]),
     "kzg_blob_to_fr": (i32, [vp, u8p, sz, u64p, sz, C.POINTER(sz)]),

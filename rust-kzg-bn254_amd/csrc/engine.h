@@ -14,6 +14,7 @@
 #include "host_recover.h"  // RecoverPlan, RecoverBatchPlan
 #include "host_encode.h"   // EncodePlan
 #include "host_locate.h"   // LocatePlan
+#include "host_prove_cosets.h"   // ProveCosetsPlan
 
 namespace kzg_host { struct G1; struct G2; }   // host_pairing.h
 namespace kzg {
@@ -145,6 +146,8 @@ struct kzg_ctx {
     kzg::DeviceBuffer rc[3];                   // kzg_recover_from_cosets(_batch) (recover.hip), for a group of blobs: work values | item maps, patterns, missing lists, flags, vanishing values, partial products (RecoverBatchPlan's layout) | powers of g
     int rc_gpow_log = -1;                      // rc[2] holds the factored tables of g^t and g^-t for t < 2^rc_gpow_log (-1: none yet)
     kzg::NttWorkspace rc_ntt;                  // its `data` also stages the uploaded coset values (dead before the first transform) and the compacted rows of out_len < n (after the last)
+    kzg::DeviceBuffer pc[4];                   // kzg_prove_cosets / kzg_coset_quotients (provecosets.hip): the referenced polynomials' coefficients | a group's quotient rows | its heads block, then its twisted remainders | its items' polynomial slots and coset indices
+    kzg::NttWorkspace pc_ntt;                  // the inverse transforms of eval-form polynomials, the l-point transforms of the values
 };
 
 struct kzg_srs {
@@ -385,6 +388,11 @@ int32_t coset_bytes_collect(kzg_ctx* ctx, CosetBytesDecode* job);    // drains t
 // the status of a bad word (KZG_OK for 0xFFFFFFFF): KZG_ERR_DESERIALIZE / KZG_ERR_NOT_ON_CURVE, the element's index / per_item to *bad_index (may be
 // null), a line with the array's name for kzg_ctx_last_error
 int32_t coset_bytes_status(kzg_ctx* ctx, const char* who, const char* array, uint32_t bad_word, size_t per_item, uint64_t* bad_index);
+// selected cosets (provecosets.hip): per item (poly_indices[i] or 0, coset_indices[i]) the quotient row (out_q: d wire words), the l values (out_ys) and the
+// proof (out_xy, out_inf; needs srs), each optional; rows bit-identical to multiproof_encode's.  Called under ctx->mu with the device set, the arguments checked,
+// plan.n_items > 0 and slot 0 idle; synchronised on return
+int32_t prove_cosets_run(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* polys_mont, size_t count, bool eval_form, const ProveCosetsPlan& plan,
+                         const uint64_t* poly_indices, const uint64_t* coset_indices, uint64_t* out_q, uint64_t* out_ys, uint64_t* out_xy, uint8_t* out_inf);
 // erasure decoding (recover.hip): the polynomial of degree < count l through the values of the plan's cosets (ys: host, count x l wire values), as n
 // coefficients or evaluations on the host; *consistent = its coefficients from plan.degree_bound on are zero.  Called under ctx->mu, synchronised on return
 int32_t recover_run(kzg_ctx* ctx, const RecoverPlan& plan, const uint64_t* ys, bool eval_form, uint64_t* out_poly, int32_t* consistent);

@@ -378,6 +378,23 @@ def encode_batch_info(d: int, n: int, chunk_len: int, count: int, values: bool =
             "batched": bool(info.batched), "inverse": transform(info.inverse), "forward": transform(info.forward)}
 
 
+def prove_cosets_info(d: int, n: int, chunk_len: int, n_items: int, count: int = 1, values: bool = True, proofs: bool = True, group_bytes: int = 0) -> dict:
+    """What `KZG.prove_cosets_batch` does with `n_items` items of `count` polynomials of shape (d, n, chunk_len) under a workspace budget
+    of `group_bytes` (0: the default) -- `kzg_prove_cosets_info`, a pure query: items per group, groups, workspace bytes of a full group
+    and of one item, the segment length S (the most dependent field products of a lane in one pass), the segments of one chain of
+    d / chunk_len coefficients, the carry levels above them, the kernel launches of a group in front of the MSM, and whether a group of
+    one item takes the single MSM."""
+    info = _lib.ProveCosetsInfo()
+    rc = _lib.load().kzg_prove_cosets_info(d, n, chunk_len, count, n_items, 1 if values else 0, 1 if proofs else 0, group_bytes, C.byref(info))
+    if rc == _lib.ERR_NOT_POWER_OF_TWO:
+        raise GenericError("length provided is not a power of 2")
+    if rc != _lib.OK:
+        raise GenericError(_lib.status_message(rc))
+    out = {name: int(getattr(info, name)) for name, _ in _lib.ProveCosetsInfo._fields_ if name != "reserved"}
+    out["msm_single"] = bool(out["msm_single"])
+    return out
+
+
 def recover_batch_info(blobs: int, count: int, n: int, chunk_len: int, out_len: int = 0, group_bytes: int = 0) -> dict:
     """How `KZG.recover_from_cosets_batch` groups `blobs` blobs of `count` cosets of shape (n, chunk_len) under a workspace budget of
     `group_bytes` (0: the default) -- `kzg_recover_batch_info`, a pure query: blobs per group, groups, workspace bytes of a full group

@@ -553,6 +553,131 @@ class KZG:
         ys, proofs = self.encode_cosets(polynomial, srs, n, chunk_len)
         return verifier.encode_coset_items(ys, proofs)
 
+    @staticmethod
+    def _coset_items_polys(name, polynomials, eval_form):
+        """(data (B, d, 4), count, d, eval_form flag) of the polynomials of `prove_cosets_batch` / `coset_quotients`: one polynomial, a list
+        of one form and length, or a (B, d, 4) array with eval_form= True / False."""
+        if isinstance(polynomials, (PolynomialEvalForm, PolynomialCoeffForm)):
+            polynomials = [polynomials]
+        if isinstance(polynomials, np.ndarray):
+            if eval_form is None:
+                raise TypeError("%s of an array needs eval_form=True or False" % name)
+            if polynomials.ndim != 3 or polynomials.shape[2] != 4:
+                raise GenericError("%s takes a (B, d, 4) array" % name)
+            return np.ascontiguousarray(polynomials, dtype=np.uint64), int(polynomials.shape[0]), int(polynomials.shape[1]), 1 if eval_form else 0
+        polys = list(polynomials)
+        if polys and all(isinstance(q, PolynomialEvalForm) for q in polys):
+            ef, rows = 1, [q.evaluations() for q in polys]
+        elif polys and all(isinstance(q, PolynomialCoeffForm) for q in polys):
+            ef, rows = 0, [q.coeffs() for q in polys]
+        elif not polys:
+            raise GenericError("%s needs at least one polynomial" % name)
+        else:
+            raise TypeError("%s takes polynomials of one form: PolynomialEvalForm or PolynomialCoeffForm" % name)
+        if eval_form is not None and bool(eval_form) != bool(ef):
+            raise TypeError("eval_form= contradicts the polynomials' form")
+        d = len(polys[0])
+        if any(len(q) != d for q in polys):
+            raise GenericError("%s needs polynomials of one length" % name)
+        data = np.ascontiguousarray(np.stack([_lib.as_u64(r, 4) for r in rows]), dtype=np.uint64) if d else np.zeros((len(polys), 0, 4), dtype=np.uint64)
+        return data, len(polys), d, ef
+
+    @staticmethod
+    def _coset_items_check(count, d, n, chunk_len, poly_indices, coset_indices, srs_len):
+        """The argument errors of `encode_cosets`, then the items: (poly index array or None, coset index array)."""
+        if d <= 0 or (d & (d - 1)) != 0 or n <= 0 or (n & (n - 1)) != 0:
+            raise FFTError("length provided is not a power of 2")
+        if n > 1 << 24:
+            raise FFTError("Could not perform IFFT due to domain consturction error")
+        if d < 2:
+            raise GenericError("encode_cosets needs a polynomial of at least 2 elements")
+        if d > n:
+            raise GenericError("the domain is shorter than the polynomial")
+        if chunk_len <= 0 or (chunk_len & (chunk_len - 1)) != 0:
+            raise GenericError("chunk length is not a power of 2")
+        if chunk_len > d // 2:
+            raise GenericError("chunk length exceeds half the polynomial length")
+        if srs_len is not None and d > srs_len:
+            raise SrsCapacityExceeded(d, srs_len)
+        ks = np.ascontiguousarray(np.asarray(coset_indices, dtype=np.int64).reshape(-1))
+        ps = None if poly_indices is None else np.ascontiguousarray(np.asarray(poly_indices, dtype=np.int64).reshape(-1))
+        if ps is not None and len(ps) != len(ks):
+            raise GenericError("one polynomial index per coset index")
+        m = n // chunk_len
+        if len(ks) and (int(ks.min()) < 0 or int(ks.max()) >= m):
+            raise GenericError("coset indices must be below n / chunk length")
+        if ps is not None and len(ps) and (int(ps.min()) < 0 or int(ps.max()) >= count):
+            raise GenericError("polynomial indices must be below the number of polynomials")
+        return (None if ps is None else ps.astype(np.uint64)), ks.astype(np.uint64)
+
+    @staticmethod
+    def _coset_items_status(ctx, rc, d, srs_len):
+        """The status of `kzg_prove_cosets` / `kzg_coset_quotients` as `encode_cosets` raises it (KZG_ERR_INVALID_ARG: ValueError)."""
+        if rc == _lib.ERR_NOT_POWER_OF_TWO:
+            raise FFTError("length provided is not a power of 2")
+        if rc == _lib.ERR_DOMAIN:
+            raise FFTError("Could not perform IFFT due to domain consturction error")
+        if rc == _lib.ERR_SRS_CAPACITY_EXCEEDED:
+            raise SrsCapacityExceeded(d, srs_len)
+        ctx.check_device(rc)
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+
+    def prove_cosets_batch(self, polynomials, srs, n: int, poly_indices, coset_indices, chunk_len: int = 1, values: bool = True,
+                           proofs: bool = True, eval_form=None):
+        """The values and proofs of selected cosets (`kzg_prove_cosets`), without the FK20 pipeline that computes every proof: item i is
+        coset `coset_indices[i]` of `polynomials[poly_indices[i]]` (`poly_indices=None`: of polynomial 0).  `polynomials` is as in
+        `encode_cosets_batch`.  Returns (ys, proofs): ys (n_items, chunk_len, 4), proofs (n_items, 8), row i bit-identical to row
+        `coset_indices[i]` of `encode_cosets` on that polynomial; `values=False` / `proofs=False` leaves that one out (None).  Duplicate
+        items are allowed.  The library works through the items in groups whose device workspace fits `Context.set_encode_group_bytes`
+        (`helpers.prove_cosets_info` tells the grouping and the passes)."""
+        data, count, d, ef = self._coset_items_polys("prove_cosets_batch", polynomials, eval_form)
+        n = int(n)
+        chunk_len = int(chunk_len)
+        if not values and not proofs:
+            raise GenericError("prove_cosets needs values, proofs or both")
+        ps, ks = self._coset_items_check(count, d, n, chunk_len, poly_indices, coset_indices, len(srs))
+        k = len(ks)
+        ctx = self._ctx()
+        ys = np.zeros((k, chunk_len, 4), dtype=np.uint64) if values else None
+        out = np.zeros((k, 8), dtype=np.uint64) if proofs else None
+        inf = np.zeros(max(k, 1), dtype=np.uint8)
+        bad = C.c_uint64(0)
+        rc = _lib.load().kzg_prove_cosets(ctx.handle, srs.handle, _lib.ptr(data), count, d, ef, n, chunk_len, None if ps is None else _lib.ptr(ps),
+                                          _lib.ptr(ks), k, _lib.ptr(ys) if values else None, _lib.ptr(out) if proofs else None,
+                                          inf.ctypes.data_as(_lib.u8p), C.byref(bad))
+        self._coset_items_status(ctx, rc, d, len(srs))
+        return ys, out
+
+    def prove_cosets(self, polynomial, srs, n: int, coset_indices, chunk_len: int = 1, values: bool = True, proofs: bool = True):
+        """`prove_cosets_batch` on one polynomial (a PolynomialCoeffForm, or a PolynomialEvalForm on the d-point domain): the rows
+        `coset_indices` of `encode_cosets(polynomial, srs, n, chunk_len)`, in that order, at the cost of one division and one commitment
+        per coset."""
+        if not isinstance(polynomial, (PolynomialEvalForm, PolynomialCoeffForm)):
+            raise TypeError("prove_cosets takes a PolynomialEvalForm or a PolynomialCoeffForm")
+        return self.prove_cosets_batch([polynomial], srs, n, None, coset_indices, chunk_len, values, proofs)
+
+    def coset_quotients(self, polynomials, n: int, poly_indices, coset_indices, chunk_len: int = 1, quotients: bool = True, values: bool = False,
+                        eval_form=None):
+        """The quotient polynomials behind `prove_cosets_batch` (`kzg_coset_quotients`; no SRS): returns (q, ys) with q an (n_items, d, 4)
+        array, row i the coefficients of f / (X^chunk_len - w^(k chunk_len)) for item i (the top chunk_len of them zero), and ys the
+        values as in `prove_cosets_batch`; `quotients=False` / `values=False` leaves that one out (None)."""
+        data, count, d, ef = self._coset_items_polys("coset_quotients", polynomials, eval_form)
+        n = int(n)
+        chunk_len = int(chunk_len)
+        if not quotients and not values:
+            raise GenericError("coset_quotients needs quotients, values or both")
+        ps, ks = self._coset_items_check(count, d, n, chunk_len, poly_indices, coset_indices, None)
+        k = len(ks)
+        ctx = self._ctx()
+        q = np.zeros((k, d, 4), dtype=np.uint64) if quotients else None
+        ys = np.zeros((k, chunk_len, 4), dtype=np.uint64) if values else None
+        bad = C.c_uint64(0)
+        rc = _lib.load().kzg_coset_quotients(ctx.handle, _lib.ptr(data), count, d, ef, n, chunk_len, None if ps is None else _lib.ptr(ps), _lib.ptr(ks), k,
+                                             _lib.ptr(q) if quotients else None, _lib.ptr(ys) if values else None, C.byref(bad))
+        self._coset_items_status(ctx, rc, d, 0)
+        return q, ys
+
     def cosets(self, polynomial_eval_form, chunk_len: int = 1) -> np.ndarray:
         """The values that go with the proofs of `compute_multiproofs`: an (m, chunk_len, 4) array, m = n / chunk_len, whose row k is
         evals[k::m], the evaluations on the coset {w^(k + j m) : j < chunk_len} -- what `verifier.verify_multiproof*` takes as `ys`."""
