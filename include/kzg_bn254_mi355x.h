@@ -1152,6 +1152,61 @@ int32_t kzg_verify_multiproof_batch_bytes(kzg_ctx* ctx, const kzg_srs* srs, cons
                                           const uint64_t* r_powers_mont /* NULL: derived */, const uint64_t* g2_tau_l_mont, int32_t* out_ok,
                                           uint64_t* out_r_powers_mont /* may be NULL */, uint64_t* bad_index, int32_t* bad_array);
 
+/* ---- blob headers in their serialized form (csrc/headerbytes.hip, csrc/header_item_stream.h, csrc/host_header_bytes.h) ---------------
+ * What a validator receives off the wire, per header (C, C2, pi2, d): the commitment as 32 bytes in the G1 format above (identity 0x40
+ * || 31 zeros, strict); the length commitment and the length proof as 64 bytes each in the G2 format of kzg_g2_decompress_be (X.A1 ||
+ * X.A0 big-endian, 0b10 / 0b11 = the smaller / larger y) EXTENDED BY THE IDENTITY, 0b01 with every other bit zero, written 0x40 || 63
+ * zero bytes (the header of the zero polynomial is valid); the claimed lengths stay a uint64_t array.  Decoding a G2 element, in this
+ * order: 1. flag bits 0b00, or 0b01 with any other bit set -> KZG_ERR_DESERIALIZE; 2. a coordinate >= p -> KZG_ERR_DESERIALIZE; 3. no
+ * point of that x on the twist -> KZG_ERR_NOT_ON_CURVE; 4. a point outside the order-r subgroup -> KZG_ERR_NOT_ON_CURVE.  The generator
+ * is a valid element (f = 1).  kzg_g2_decompress_be_device keeps its own rule: it has no identity.  One byte string names one point, so
+ * the header transcript over the decoded points is a function of the bytes.
+ *
+ * kzg_header_items_encode_be: the disperser's half, host only (the library's host pool): wire points -> the three byte arrays (32, 64,
+ * 64 bytes per header); the all-zero wire point encodes as the identity.  The inputs are trusted (no curve or subgroup check).  Each
+ * input / output pair may be NULL together.  Errors: one pointer of a pair NULL and the other not, or all pairs NULL with count > 0 ->
+ * KZG_ERR_INVALID_ARG; count > 2^20 -> KZG_ERR_TOO_LARGE; a coordinate not below p -> KZG_ERR_INVALID_ARG (the outputs are then
+ * unspecified). */
+int32_t kzg_header_items_encode_be(const uint64_t* commitments_xy, const uint64_t* length_commitments, const uint64_t* length_proofs,
+                                   size_t count, uint8_t* out_commitments_be, uint8_t* out_length_commitments_be,
+                                   uint8_t* out_length_proofs_be);
+/* The byte arrays -> the wire points the decoded header entries take, on the device: commitments count x 8 u64, G2 elements count x 16
+ * u64 each, an identity all zeros.  Every G2 element is subgroup-checked.  Errors, in order: 1. a null ctx, or any null array with
+ * count > 0 -> KZG_ERR_INVALID_ARG; 2. count > 2^20 -> KZG_ERR_TOO_LARGE; 3. a _begin in flight on slot 0 -> KZG_ERR_INVALID_ARG; 4. a
+ * bad commitment: *bad_array = 0; 5. a bad G2 element: *bad_array = 1 (length commitment) or 2 (length proof), the smallest header
+ * that has one, its length commitment in front of its length proof; *bad_index = the header (both may be NULL).  On an error of 4 / 5
+ * the outputs are not written.  count = 0 -> KZG_OK.  Synchronous, slot 0. */
+int32_t kzg_header_items_decode_be(kzg_ctx* ctx, const uint8_t* commitments_be, const uint8_t* length_commitments_be,
+                                   const uint8_t* length_proofs_be, size_t count, uint64_t* out_commitments_xy,
+                                   uint64_t* out_length_commitments, uint64_t* out_length_proofs, uint64_t* bad_index, int32_t* bad_array);
+/* kzg_verify_length_proof_batch with the decode inside the call: for every input that decodes, *out_ok is that entry's on the output
+ * of kzg_header_items_decode_be, and the weights are the same bit for bit (weights_mont = NULL derives them; out_weights_mont, may be
+ * NULL, receives the count + 1 weights used).  One pass on the device decodes the G2 elements where the chains read them and runs the
+ * order-r subgroup test there, the ONE 63-bit chain an element gets; the commitments are decoded into the bases of the G1 MSM; nothing
+ * decoded returns to the host.  Derived weights: the item digests are hashed on the device, one lane per header, from the commitment's
+ * bytes and the decoded G2 points (32 bytes per header come down); the batch hash, the count + 1 weight hashes and the bit length of
+ * the largest weight stay on the host.  With supplied weights no digest kernel runs.
+ * Errors, in this order: 1. rows 1-4 of kzg_verify_length_proof_batch's table, on the host before any launch; 2. a _begin in flight on
+ * slot 0 -> KZG_ERR_INVALID_ARG; 3. a shift off the curve -> KZG_ERR_G1_NOT_ON_CURVE, *bad_array = 3, *bad_index = its position in the
+ * list; 4. a bad commitment: *bad_array = 0; 5. a bad G2 element: *bad_array = 1 / 2 as for kzg_header_items_decode_be; 4 and 5 with the
+ * status of the decode rules above and *bad_index = the header (both may be NULL).  count = 0 -> *out_ok = 1, no device work.  The
+ * context is usable after any error.  KZG_VB_TRACE=1 prints the phase times, `decode` and `digests` among them, on stderr. */
+int32_t kzg_verify_length_proof_batch_bytes(kzg_ctx* ctx, const uint8_t* commitments_be, const uint8_t* length_commitments_be,
+                                            const uint8_t* length_proofs_be, const uint64_t* claimed_lens, size_t count,
+                                            const uint64_t* shift_lens, const uint64_t* g1_tau_shifts_xy, size_t n_shifts,
+                                            const uint64_t* weights_mont /* NULL: derived */, int32_t* out_ok,
+                                            uint64_t* out_weights_mont /* may be NULL */, uint64_t* bad_index, int32_t* bad_array);
+/* kzg_verify_length_proof_batch_locate on serialized headers: the same prefix as the entry above, then the group sums and the search of
+ * the decoded entry; out_group_ok, *out_bad_groups and *out_pairing_checks are that entry's on the output of
+ * kzg_header_items_decode_be.  The commitments are decoded where the G1 group sums read them: nothing decoded returns to the host.
+ * Errors: as above, with rows 4a / 4b of the grouped entries behind row 4. */
+int32_t kzg_verify_length_proof_batch_locate_bytes(kzg_ctx* ctx, const uint8_t* commitments_be, const uint8_t* length_commitments_be,
+                                                   const uint8_t* length_proofs_be, const uint64_t* claimed_lens, size_t count,
+                                                   const uint64_t* shift_lens, const uint64_t* g1_tau_shifts_xy, size_t n_shifts,
+                                                   const uint64_t* weights_mont /* NULL: derived */, const uint64_t* group_indices,
+                                                   size_t n_groups, uint8_t* out_group_ok, size_t* out_bad_groups,
+                                                   size_t* out_pairing_checks /* may be NULL */, uint64_t* bad_index, int32_t* bad_array);
+
 #ifdef __cplusplus
 }
 #endif

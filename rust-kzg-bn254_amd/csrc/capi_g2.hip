@@ -2,7 +2,8 @@
 // MSM over caller bases or a handle, G2 commitments, the blob header (commitment, length commitment, length proof) in one call, the
 // headers of many blobs and the batched MSM over shared bases (with the pure query of their plan), the header's verification by two
 // pairing checks, the batched verification of headers (subgroup test and weighted sums on the device, one product of pairings), the group sums of such a
-// batch and the search for its bad headers (one shared prefix of checks, uploads and weights for the three; host_header_locate.h), and the decoders of gnark-compressed G2 points: on the host, and on the device into wire points or a resident
+// batch and the search for its bad headers (one shared prefix of checks, uploads and weights for the three; host_header_locate.h), the same two verdicts from
+// SERIALIZED headers (a second prefix that decodes on the device, headerbytes.hip; the tails are shared) with the headers' encoder and decoder, and the decoders of gnark-compressed G2 points: on the host, and on the device into wire points or a resident
 // handle.  The kernels and their drivers are g2msm.hip, g2batch.hip and g2decode.hip; every argument check here runs before any launch.
 #include "engine.h"
 #include <new>
@@ -11,6 +12,7 @@
 #include "host_curve.h"
 #include "host_g2_decode.h"
 #include "host_fiat_shamir.h"
+#include "host_header_bytes.h"
 #include "host_header_locate.h"
 
 #include <algorithm>
@@ -122,6 +124,22 @@ struct HeaderStage {
     std::vector<uint64_t> derived, canon;        // canon: the same count + 1 values as canonical words
     int bits = 0;                                // the bit length of the largest r_i: the trip count of the G2 chains
     Clock::time_point t0, t1, t2;                // start of row 5, the end of the on-twist test, the end of the subgroup test
+    // the prefix for serialized headers: the commitments are on the device too (ctx->ml[5], device format), decoded where the G1 sums read
+    // them, and no tail uploads them; t1 = the end of the decode, t2 = the end of the item digests
+    const uint4* d_commitments = nullptr;
+    bool from_bytes = false;
+    // the weights as the tails read them: wire form for the G1 side, canonical words for the G2 chains, the chains' trip count
+    void set_weights(const uint64_t* weights_mont, size_t count) {
+        weights = weights_mont;
+        canon.resize((count + 1) * 4);
+        bits = 0;
+        for (size_t i = 0; i <= count; ++i) {
+            uint64_t* k = canon.data() + 4 * i;
+            kzg_host::fr_wire_to_canonical(weights_mont + 4 * i, k);
+            if (i == count) break;                                  // rho multiplies on the host
+            for (int w = 3; w >= 0; --w) if (k[w]) { bits = std::max(bits, 64 * w + 64 - __builtin_clzll(k[w])); break; }
+        }
+    }
 };
 
 // Rows 1-4 (host_header_locate.h: with the group rows of a grouped entry), *empty = (count == 0) and nothing else done; else rows 5-7 and the
@@ -192,15 +210,61 @@ int32_t header_batch_prefix(const char* who, kzg_ctx* ctx, bool output_null, con
         header_batch_weights_host(commitments_xy, length_commitments, length_proofs, claimed_lens, count, shift_lens, g1_tau_shifts_xy, n_shifts, st->derived.data(), host_parallel_for);
         weights_mont = st->derived.data();
     }
-    st->weights = weights_mont;
-    st->canon.resize((count + 1) * 4);
-    st->bits = 0;
-    for (size_t i = 0; i <= count; ++i) {
-        uint64_t* k = st->canon.data() + 4 * i;
-        fr_wire_to_canonical(weights_mont + 4 * i, k);
-        if (i == count) break;                                      // rho multiplies on the host
-        for (int w = 3; w >= 0; --w) if (k[w]) { st->bits = std::max(st->bits, 64 * w + 64 - __builtin_clzll(k[w])); break; }
+    st->set_weights(weights_mont, count);
+    return KZG_OK;
+}
+
+// The same stage from SERIALIZED headers (kzg_verify_length_proof_batch_bytes, kzg_verify_length_proof_batch_locate_bytes): rows 1-4 on the
+// host, slot 0, the shifts on the curve (*bad_array = 3), then one decode pass on the device (headerbytes.hip): the G2 elements land
+// subgroup-checked where the chains read them (ONE 63-bit chain per element: the decoder's is the only one), the commitments where the G1
+// sums read them, nothing decoded returns to the host.  A refused element sets *bad_array (0 commitment, 1 length commitment, 2 length
+// proof) and *bad_index.  Derived weights hash the items on the device (32 B per header come down for the batch hash, which stays here).
+int32_t header_batch_prefix_bytes(const char* who, kzg_ctx* ctx, bool output_null, const uint8_t* commitments_be, const uint8_t* length_commitments_be,
+                                  const uint8_t* length_proofs_be, const uint64_t* claimed_lens, size_t count, const uint64_t* shift_lens,
+                                  const uint64_t* g1_tau_shifts_xy, size_t n_shifts, const uint64_t* weights_mont, const HeaderGrouping& grp, uint64_t* bad_index,
+                                  int32_t* bad_array, bool* empty, HeaderStage* st) {
+    using namespace kzg_host;
+    int32_t rc = header_batch_checks(!ctx || output_null, commitments_be, length_commitments_be, length_proofs_be, claimed_lens, count, shift_lens, g1_tau_shifts_xy,
+                                     n_shifts, grp, &st->length_class, bad_index);
+    if (rc != KZG_OK) return rc;
+    *empty = count == 0;
+    if (count == 0) return KZG_OK;
+    st->t0 = Clock::now();
+    st->from_bytes = true;
+    st->lk = std::unique_lock<std::mutex>(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (slot0_busy(ctx)) return KZG_ERR_INVALID_ARG;
+    st->shifts.resize(n_shifts);
+    for (size_t g = 0; g < n_shifts; ++g) {
+        st->shifts[g] = g1_from_wire(g1_tau_shifts_xy + 8 * g);
+        if (!g1_on_curve(st->shifts[g])) { if (bad_index) *bad_index = (uint64_t)g; if (bad_array) *bad_array = 3; return KZG_ERR_G1_NOT_ON_CURVE; }
     }
+    const size_t n_points = 2 * count;
+    KZG_HIP_TRY(ctx, ctx->msm.bases.reserve(n_points * 128));
+    KZG_HIP_TRY(ctx, ctx->ml[5].reserve(count * 64));
+    HeaderBytesDecode job;
+    job.commitments_be = commitments_be; job.length_commitments_be = length_commitments_be; job.length_proofs_be = length_proofs_be;
+    job.count = count;
+    job.d_commitments = ctx->ml[5].as<uint4>();
+    job.d_g2 = ctx->msm.bases.as<uint4>();
+    rc = header_bytes_decode(ctx, &job);
+    if (rc != KZG_OK) return rc;
+    rc = header_bytes_status(ctx, who, job, bad_index, bad_array);
+    if (rc != KZG_OK) return rc;
+    st->d_points = job.d_g2;
+    st->n_points = n_points;
+    st->d_commitments = job.d_commitments;
+    st->t1 = Clock::now();
+    if (!weights_mont) {
+        std::vector<uint8_t> data = header_batch_transcript(count, shift_lens, g1_tau_shifts_xy, n_shifts);
+        rc = header_item_digests_run(ctx, job.d_commitments_be, job.d_g2, claimed_lens, count, data.data() + header_batch_head(n_shifts));
+        if (rc != KZG_OK) return rc;
+        st->derived.resize((count + 1) * 4);
+        header_weights_from_transcript(data, count, st->derived.data(), host_parallel_for);
+        weights_mont = st->derived.data();
+    }
+    st->t2 = Clock::now();
+    st->set_weights(weights_mont, count);
     return KZG_OK;
 }
 
@@ -214,7 +278,8 @@ struct HeaderGroupSums {
 };
 
 // The stage has passed header_batch_prefix with the grouping; count > 0.  The G2 points are on the device already; the commitments go up
-// here, validated again on their way into the device format (they have passed row 5).
+// here, validated again on their way into the device format (they have passed row 5), unless the stage holds them (serialized headers: they
+// were decoded into ctx->ml[5], and commitments_xy is null).
 int32_t header_group_sums_core(kzg_ctx* ctx, const HeaderStage& st, const uint64_t* commitments_xy, size_t count, size_t n_shifts, const uint64_t* group_indices,
                                size_t n_groups, HeaderGroupSums* out) {
     const auto t0 = Clock::now();
@@ -228,12 +293,14 @@ int32_t header_group_sums_core(kzg_ctx* ctx, const HeaderStage& st, const uint64
     const auto t1 = Clock::now();
     rc = locate_plan(group_indices, count, n_groups, &out->g1_plan);
     if (rc != KZG_OK) return rc;
-    KZG_HIP_TRY(ctx, ctx->ml[5].reserve(count * 64));
     KZG_HIP_TRY(ctx, ctx->ml[4].reserve(count * 32));
-    uint32_t off_curve = 0;
-    rc = upload_points(ctx, commitments_xy, count, ctx->ml[5].as<uint4>(), ctx->msm.bases_wire, &off_curve);
-    if (rc != KZG_OK) return rc;
-    if (off_curve) return KZG_ERR_G1_NOT_ON_CURVE;
+    if (!st.d_commitments) {
+        KZG_HIP_TRY(ctx, ctx->ml[5].reserve(count * 64));
+        uint32_t off_curve = 0;
+        rc = upload_points(ctx, commitments_xy, count, ctx->ml[5].as<uint4>(), ctx->msm.bases_wire, &off_curve);
+        if (rc != KZG_OK) return rc;
+        if (off_curve) return KZG_ERR_G1_NOT_ON_CURVE;
+    }
     KZG_HIP_TRY(ctx, hipMemcpyAsync(ctx->ml[4].p, st.weights, count * 32, hipMemcpyHostToDevice, ctx->stream));
     rc = locate_upload_plan(ctx, out->g1_plan);
     if (rc != KZG_OK) return rc;
@@ -243,6 +310,159 @@ int32_t header_group_sums_core(kzg_ctx* ctx, const HeaderStage& st, const uint64
     if (rc != KZG_OK) return rc;
     out->ms_g2 = ms_between(t0, t1);
     out->ms_g1 = ms_between(t1, Clock::now());
+    return KZG_OK;
+}
+
+// The tail of the batch entries: the stage has passed a prefix, count > 0.  commitments_xy: the wire commitments, or null when the stage holds
+// them on the device.  Synchronised on return.
+int32_t header_verify_tail(kzg_ctx* ctx, const HeaderStage& st, const uint64_t* commitments_xy, size_t count, size_t n_shifts, int32_t* out_ok) {
+    using namespace kzg_host;
+    auto ms = ms_between;
+    const uint64_t* weights_mont = st.weights;
+    int32_t rc;
+    const std::vector<uint8_t>& group = st.length_class;
+    const std::vector<G1>& shifts = st.shifts;
+    const std::vector<uint64_t>& canon = st.canon;
+    const uint4* d_points = st.d_points;
+    const size_t n_points = st.n_points;
+    const int bits = st.bits;
+    const auto t0 = st.t0, t1 = st.t1, t2 = st.t2;
+    // lanes: the C2 of every group in the list's order, each group padded to whole tiles of 64, then every pi2
+    std::vector<size_t> group_count(n_shifts, 0), tile_begin(n_shifts + 2, 0);
+    for (size_t i = 0; i < count; ++i) ++group_count[group[i]];
+    for (size_t g = 0; g < n_shifts; ++g) tile_begin[g + 1] = tile_begin[g] + (group_count[g] + 63) / 64;
+    tile_begin[n_shifts + 1] = tile_begin[n_shifts] + (count + 63) / 64;
+    const size_t tiles = tile_begin[n_shifts + 1];
+    std::vector<uint32_t> lanes(tiles * 64, 0xFFFFFFFFu);
+    {
+        std::vector<size_t> next(n_shifts);
+        for (size_t g = 0; g < n_shifts; ++g) next[g] = tile_begin[g] * 64;
+        for (size_t i = 0; i < count; ++i) { lanes[next[group[i]]++] = (uint32_t)(2 * i); lanes[tile_begin[n_shifts] * 64 + i] = (uint32_t)(2 * i + 1); }
+    }
+    std::vector<uint64_t> tile_sums(tiles * 16);
+    rc = g2_weighted_tile_sums(ctx, d_points, n_points, lanes.data(), lanes.size(), reinterpret_cast<const uint32_t*>(canon.data()), count, 1, bits, tile_sums.data());
+    if (rc != KZG_OK) return rc;
+    const auto t3 = Clock::now();
+    // U = sum r_i C_i: the variable-base G1 MSM of the batched verifiers
+    uint64_t u_xy[8];
+    uint8_t u_inf = 0;
+    if (st.d_commitments) {
+        const void* d_scalars;
+        rc = stage_scalars_g2(ctx, weights_mont, count, &d_scalars);
+        if (rc == KZG_OK) rc = msm_run_batch(ctx, st.d_commitments, d_scalars, count, 1, u_xy, &u_inf);
+    } else {
+        rc = msm_g1_batch_locked(ctx, commitments_xy, weights_mont, count, 1, u_xy, &u_inf, nullptr);
+    }
+    if (rc != KZG_OK) return rc;
+    const auto t4 = Clock::now();
+    // W_g, Pi: the tiles of one sum added in Jacobian coordinates, one inversion per sum
+    auto sum_tiles = [&](size_t lo, size_t hi) {
+        G2Jac acc; acc.inf = true; acc.X = {fq_zero(), fq_zero()}; acc.Y = acc.X; acc.Z = acc.X;
+        for (size_t t = lo; t < hi; ++t) acc = g2j_madd(acc, g2_from_wire(tile_sums.data() + 16 * t));
+        if (acc.inf) return g2_inf();
+        const Fq2 zi = inv(acc.Z), zi2 = sqr(zi);
+        G2 r; r.inf = false;
+        r.x = mul(acc.X, zi2);
+        r.y = mul(acc.Y, mul(zi2, zi));
+        return r;
+    };
+    std::vector<G2> W(n_shifts);
+    G2 S = g2_inf();
+    for (size_t g = 0; g < n_shifts; ++g) { W[g] = sum_tiles(tile_begin[g], tile_begin[g + 1]); S = g2_add(S, W[g]); }
+    const G2 Pi = sum_tiles(tile_begin[n_shifts], tile_begin[n_shifts + 1]);
+    // e(U, G2) e(-G1, S + [rho]Pi) prod_g e([rho]T_g, W_g) == 1
+    const uint64_t* rho = canon.data() + 4 * count;
+    std::vector<G1> ps;
+    std::vector<G2> qs;
+    G1 g1; g1.x = FQ_ONE; g1.y = FQ_TWO; g1.inf = false;
+    G1 U = g1_from_wire(u_xy);
+    if (u_inf) U.inf = true;
+    ps.push_back(U); qs.push_back(g2_generator());
+    ps.push_back(g1_neg(g1)); qs.push_back(g2_add(S, g2_mul(Pi, rho)));
+    for (size_t g = 0; g < n_shifts; ++g) {
+        if (group_count[g] == 0) continue;
+        ps.push_back(g1_mul(shifts[g], rho)); qs.push_back(W[g]);
+    }
+    *out_ok = pairings_product_is_one(ps.data(), qs.data(), (int)ps.size(), host_parallel_for) ? 1 : 0;
+    if (opts().vb_trace && st.from_bytes) {
+        fprintf(stderr, "  verify_length_proof_batch_bytes count=%zu groups=%zu bits=%d: checks + decode (staging, uploads, decode kernels with the subgroup chain) %.3f ms, "
+                "digests + weights %.3f ms, weighted sums %.3f ms, G1 MSM %.3f ms, host sums + pairing %.3f ms\n",
+                count, n_shifts, bits, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4), ms(t4, Clock::now()));
+    } else if (opts().vb_trace) {
+        fprintf(stderr, "  verify_length_proof_batch count=%zu groups=%zu bits=%d: checks + upload + on-twist %.3f ms, subgroup %.3f ms, weights + weighted sums %.3f ms, G1 MSM %.3f ms, host sums + pairing %.3f ms\n",
+                count, n_shifts, bits, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4), ms(t4, Clock::now()));
+    }
+    return KZG_OK;
+}
+
+
+// The tail of the locate entries: the stage has passed a prefix with the grouping, count > 0; commitments_xy as for header_verify_tail.
+int32_t header_locate_tail(kzg_ctx* ctx, HeaderStage& st, const uint64_t* commitments_xy, size_t count, size_t n_shifts, const uint64_t* group_indices, size_t n_groups,
+                           uint8_t* out_group_ok, size_t* out_bad_groups, size_t* out_pairing_checks) {
+    using namespace kzg_host;
+    int32_t rc;
+    const auto t_sums = Clock::now();
+    HeaderGroupSums gs;
+    rc = header_group_sums_core(ctx, st, commitments_xy, count, n_shifts, group_indices, n_groups, &gs);
+    if (rc != KZG_OK) return rc;
+    st.lk.unlock();                                                  // the rest is host work
+    const auto t_host = Clock::now();
+    // the leaves: U_g on the left, (Pi_g, W_{g,s} for the classes present) on the right
+    const HeaderClasses cls = header_present_classes(st.length_class.data(), count, n_shifts);
+    using Sums = HeaderSums<Xyzz, G2Jac>;
+    std::vector<Sums> lhs, rhs;
+    header_assemble(gs.g1_plan, gs.g2_plan, n_groups, n_shifts, cls, [&](size_t j) { return gs.u[j]; },
+                    [&](size_t j) { return g2j_from_affine(g2_from_wire(gs.q.data() + 16 * j)); }, xyzz_inf(), g2j_inf(), &lhs, &rhs);
+    // what every test multiplies: rho on the G1 side, once per call
+    const uint64_t* rho = st.canon.data() + 4 * count;
+    G1 g1; g1.x = FQ_ONE; g1.y = FQ_TWO; g1.inf = false;
+    HeaderFixed<G1, G2> fx;
+    fx.g2 = g2_generator();
+    fx.neg_g1 = g1_neg(g1);
+    fx.neg_rho_g1 = g1_neg(g1_mul(g1, rho));
+    for (uint32_t s : cls.present) fx.rho_shift.push_back(g1_mul(st.shifts[s], rho));
+    struct OpsA {
+        Xyzz zero() const { return xyzz_inf(); }
+        Xyzz add(const Xyzz& a, const Xyzz& b) const { return xyzz_add(a, b); }
+        Xyzz sub(const Xyzz& a, Xyzz b) const { b.y = neg(b.y); return xyzz_add(a, b); }
+    };
+    struct OpsB {
+        G2Jac zero() const { return g2j_inf(); }
+        G2Jac add(const G2Jac& a, const G2Jac& b) const { return g2j_add(a, b); }
+        G2Jac sub(const G2Jac& a, const G2Jac& b) const { return g2j_add(a, g2j_neg(b)); }
+    };
+    bool first = true;
+    auto t_search = t_host;
+    auto holds = [&](const Sums& l, const Sums& r) {
+        if (first) { first = false; t_search = Clock::now(); }      // the prefix sums end where the first test begins
+        uint64_t a[8];
+        uint8_t u_inf = 0;
+        xyzz_to_affine(l.u, a, &u_inf);
+        G1 U = g1_from_wire(a);
+        if (u_inf) U.inf = true;
+        std::vector<G2> q(1 + cls.present.size(), g2_inf());
+        G2Jac sum_w = g2j_inf();
+        for (size_t k = 0; k < r.q.size() && k < q.size(); ++k) {
+            q[k] = g2j_to_affine(r.q[k]);
+            if (k) sum_w = g2j_add(sum_w, r.q[k]);
+        }
+        std::vector<G1> ps;
+        std::vector<G2> qs;
+        header_pairs(fx, U, q, g2j_to_affine(sum_w), &ps, &qs);
+        return pairings_product_is_one(ps.data(), qs.data(), (int)ps.size(), host_parallel_for);
+    };
+    size_t bad = 0;
+    const size_t checks = locate_search(lhs.data(), rhs.data(), n_groups, HeaderSumOps<Xyzz, G2Jac, OpsA, OpsB>(), holds, out_group_ok, &bad);
+    *out_bad_groups = bad;
+    if (out_pairing_checks) *out_pairing_checks = checks;
+    if (opts().vb_trace) {
+        char parts[96] = "";
+        if (st.from_bytes) snprintf(parts, sizeof parts, " (checks + decode %.3f ms, digests + weights %.3f ms)", ms_between(st.t0, st.t1), ms_between(st.t1, st.t2));
+        fprintf(stderr, "  verify_length_proof_batch_locate%s count=%zu groups=%zu classes=%zu bits=%d: shared prefix%s %.3f ms, G2 group sums %.3f ms, G1 group sums %.3f ms, "
+                "host sums %.3f ms, search %.3f ms, %zu pairing checks, %zu bad groups\n", st.from_bytes ? "_bytes" : "",
+                count, n_groups, cls.present.size(), st.bits, parts, ms_between(st.t0, t_sums), gs.ms_g2,
+                gs.ms_g1, ms_between(t_host, t_search), ms_between(t_search, Clock::now()), checks, bad);
+    }
     return KZG_OK;
 }
 
@@ -525,78 +745,13 @@ int32_t kzg_verify_length_proof_batch(kzg_ctx* ctx, const uint64_t* commitments_
                                       const uint64_t* length_proofs, const uint64_t* claimed_lens, size_t count,
                                       const uint64_t* shift_lens, const uint64_t* g1_tau_shifts_xy, size_t n_shifts,
                                       const uint64_t* weights_mont, int32_t* out_ok, uint64_t* bad_index) {
-    using namespace kzg_host;
-    auto ms = ms_between;
     HeaderStage st;
     bool empty = false;
     int32_t rc = header_batch_prefix("kzg_verify_length_proof_batch", ctx, !out_ok, commitments_xy, length_commitments, length_proofs, claimed_lens, count, shift_lens,
                                      g1_tau_shifts_xy, n_shifts, weights_mont, HeaderGrouping(), bad_index, &empty, &st);
     if (rc != KZG_OK) return rc;
     if (empty) { *out_ok = 1; return KZG_OK; }
-    weights_mont = st.weights;
-    const std::vector<uint8_t>& group = st.length_class;
-    const std::vector<G1>& shifts = st.shifts;
-    const std::vector<uint64_t>& canon = st.canon;
-    const uint4* d_points = st.d_points;
-    const size_t n_points = st.n_points;
-    const int bits = st.bits;
-    const auto t0 = st.t0, t1 = st.t1, t2 = st.t2;
-    // lanes: the C2 of every group in the list's order, each group padded to whole tiles of 64, then every pi2
-    std::vector<size_t> group_count(n_shifts, 0), tile_begin(n_shifts + 2, 0);
-    for (size_t i = 0; i < count; ++i) ++group_count[group[i]];
-    for (size_t g = 0; g < n_shifts; ++g) tile_begin[g + 1] = tile_begin[g] + (group_count[g] + 63) / 64;
-    tile_begin[n_shifts + 1] = tile_begin[n_shifts] + (count + 63) / 64;
-    const size_t tiles = tile_begin[n_shifts + 1];
-    std::vector<uint32_t> lanes(tiles * 64, 0xFFFFFFFFu);
-    {
-        std::vector<size_t> next(n_shifts);
-        for (size_t g = 0; g < n_shifts; ++g) next[g] = tile_begin[g] * 64;
-        for (size_t i = 0; i < count; ++i) { lanes[next[group[i]]++] = (uint32_t)(2 * i); lanes[tile_begin[n_shifts] * 64 + i] = (uint32_t)(2 * i + 1); }
-    }
-    std::vector<uint64_t> tile_sums(tiles * 16);
-    rc = g2_weighted_tile_sums(ctx, d_points, n_points, lanes.data(), lanes.size(), reinterpret_cast<const uint32_t*>(canon.data()), count, 1, bits, tile_sums.data());
-    if (rc != KZG_OK) return rc;
-    const auto t3 = Clock::now();
-    // U = sum r_i C_i: the variable-base G1 MSM of the batched verifiers
-    uint64_t u_xy[8];
-    uint8_t u_inf = 0;
-    rc = msm_g1_batch_locked(ctx, commitments_xy, weights_mont, count, 1, u_xy, &u_inf, nullptr);
-    if (rc != KZG_OK) return rc;
-    const auto t4 = Clock::now();
-    // W_g, Pi: the tiles of one sum added in Jacobian coordinates, one inversion per sum
-    auto sum_tiles = [&](size_t lo, size_t hi) {
-        G2Jac acc; acc.inf = true; acc.X = {fq_zero(), fq_zero()}; acc.Y = acc.X; acc.Z = acc.X;
-        for (size_t t = lo; t < hi; ++t) acc = g2j_madd(acc, g2_from_wire(tile_sums.data() + 16 * t));
-        if (acc.inf) return g2_inf();
-        const Fq2 zi = inv(acc.Z), zi2 = sqr(zi);
-        G2 r; r.inf = false;
-        r.x = mul(acc.X, zi2);
-        r.y = mul(acc.Y, mul(zi2, zi));
-        return r;
-    };
-    std::vector<G2> W(n_shifts);
-    G2 S = g2_inf();
-    for (size_t g = 0; g < n_shifts; ++g) { W[g] = sum_tiles(tile_begin[g], tile_begin[g + 1]); S = g2_add(S, W[g]); }
-    const G2 Pi = sum_tiles(tile_begin[n_shifts], tile_begin[n_shifts + 1]);
-    // e(U, G2) e(-G1, S + [rho]Pi) prod_g e([rho]T_g, W_g) == 1
-    const uint64_t* rho = canon.data() + 4 * count;
-    std::vector<G1> ps;
-    std::vector<G2> qs;
-    G1 g1; g1.x = FQ_ONE; g1.y = FQ_TWO; g1.inf = false;
-    G1 U = g1_from_wire(u_xy);
-    if (u_inf) U.inf = true;
-    ps.push_back(U); qs.push_back(g2_generator());
-    ps.push_back(g1_neg(g1)); qs.push_back(g2_add(S, g2_mul(Pi, rho)));
-    for (size_t g = 0; g < n_shifts; ++g) {
-        if (group_count[g] == 0) continue;
-        ps.push_back(g1_mul(shifts[g], rho)); qs.push_back(W[g]);
-    }
-    *out_ok = pairings_product_is_one(ps.data(), qs.data(), (int)ps.size(), host_parallel_for) ? 1 : 0;
-    if (opts().vb_trace) {
-        fprintf(stderr, "  verify_length_proof_batch count=%zu groups=%zu bits=%d: checks + upload + on-twist %.3f ms, subgroup %.3f ms, weights + weighted sums %.3f ms, G1 MSM %.3f ms, host sums + pairing %.3f ms\n",
-                count, n_shifts, bits, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4), ms(t4, Clock::now()));
-    }
-    return KZG_OK;
+    return header_verify_tail(ctx, st, commitments_xy, count, n_shifts, out_ok);
 }
 
 // ---- locating the bad headers of a rejected batch (g2batch.hip k_g2_locate_*, multilocate.hip k_locate_*<1>, host_header_locate.h) ----------
@@ -646,7 +801,6 @@ int32_t kzg_verify_length_proof_batch_locate(kzg_ctx* ctx, const uint64_t* commi
                                              const uint64_t* claimed_lens, size_t count, const uint64_t* shift_lens, const uint64_t* g1_tau_shifts_xy,
                                              size_t n_shifts, const uint64_t* weights_mont, const uint64_t* group_indices, size_t n_groups,
                                              uint8_t* out_group_ok, size_t* out_bad_groups, size_t* out_pairing_checks, uint64_t* bad_index) {
-    using namespace kzg_host;
     HeaderStage st;
     HeaderGrouping grp;
     grp.on = true; grp.group_indices = group_indices; grp.n_groups = n_groups;
@@ -660,65 +814,95 @@ int32_t kzg_verify_length_proof_batch_locate(kzg_ctx* ctx, const uint64_t* commi
         if (out_pairing_checks) *out_pairing_checks = 0;
         return KZG_OK;
     }
-    const auto t_sums = Clock::now();
-    HeaderGroupSums gs;
-    rc = header_group_sums_core(ctx, st, commitments_xy, count, n_shifts, group_indices, n_groups, &gs);
-    if (rc != KZG_OK) return rc;
-    st.lk.unlock();                                                  // the rest is host work
-    const auto t_host = Clock::now();
-    // the leaves: U_g on the left, (Pi_g, W_{g,s} for the classes present) on the right
-    const HeaderClasses cls = header_present_classes(st.length_class.data(), count, n_shifts);
-    using Sums = HeaderSums<Xyzz, G2Jac>;
-    std::vector<Sums> lhs, rhs;
-    header_assemble(gs.g1_plan, gs.g2_plan, n_groups, n_shifts, cls, [&](size_t j) { return gs.u[j]; },
-                    [&](size_t j) { return g2j_from_affine(g2_from_wire(gs.q.data() + 16 * j)); }, xyzz_inf(), g2j_inf(), &lhs, &rhs);
-    // what every test multiplies: rho on the G1 side, once per call
-    const uint64_t* rho = st.canon.data() + 4 * count;
-    G1 g1; g1.x = FQ_ONE; g1.y = FQ_TWO; g1.inf = false;
-    HeaderFixed<G1, G2> fx;
-    fx.g2 = g2_generator();
-    fx.neg_g1 = g1_neg(g1);
-    fx.neg_rho_g1 = g1_neg(g1_mul(g1, rho));
-    for (uint32_t s : cls.present) fx.rho_shift.push_back(g1_mul(st.shifts[s], rho));
-    struct OpsA {
-        Xyzz zero() const { return xyzz_inf(); }
-        Xyzz add(const Xyzz& a, const Xyzz& b) const { return xyzz_add(a, b); }
-        Xyzz sub(const Xyzz& a, Xyzz b) const { b.y = neg(b.y); return xyzz_add(a, b); }
-    };
-    struct OpsB {
-        G2Jac zero() const { return g2j_inf(); }
-        G2Jac add(const G2Jac& a, const G2Jac& b) const { return g2j_add(a, b); }
-        G2Jac sub(const G2Jac& a, const G2Jac& b) const { return g2j_add(a, g2j_neg(b)); }
-    };
-    bool first = true;
-    auto t_search = t_host;
-    auto holds = [&](const Sums& l, const Sums& r) {
-        if (first) { first = false; t_search = Clock::now(); }      // the prefix sums end where the first test begins
-        uint64_t a[8];
-        uint8_t u_inf = 0;
-        xyzz_to_affine(l.u, a, &u_inf);
-        G1 U = g1_from_wire(a);
-        if (u_inf) U.inf = true;
-        std::vector<G2> q(1 + cls.present.size(), g2_inf());
-        G2Jac sum_w = g2j_inf();
-        for (size_t k = 0; k < r.q.size() && k < q.size(); ++k) {
-            q[k] = g2j_to_affine(r.q[k]);
-            if (k) sum_w = g2j_add(sum_w, r.q[k]);
+    return header_locate_tail(ctx, st, commitments_xy, count, n_shifts, group_indices, n_groups, out_group_ok, out_bad_groups, out_pairing_checks);
+}
+
+// ---- blob headers in their serialized form (headerbytes.hip, host_header_bytes.h) ----------------------------------------------------------
+int32_t kzg_header_items_encode_be(const uint64_t* commitments_xy, const uint64_t* length_commitments, const uint64_t* length_proofs, size_t count,
+                                   uint8_t* out_commitments_be, uint8_t* out_length_commitments_be, uint8_t* out_length_proofs_be) {
+    if ((commitments_xy == nullptr) != (out_commitments_be == nullptr) || (length_commitments == nullptr) != (out_length_commitments_be == nullptr) ||
+        (length_proofs == nullptr) != (out_length_proofs_be == nullptr))
+        return KZG_ERR_INVALID_ARG;
+    if (count && !commitments_xy && !length_commitments && !length_proofs) return KZG_ERR_INVALID_ARG;
+    if (count > kzg::HEADER_MAX_COUNT) return KZG_ERR_TOO_LARGE;
+    std::atomic<int> bad{0};
+    const size_t per = 256, jobs = (count + per - 1) / per;
+    host_parallel_for(jobs, [&](size_t j) {
+        for (size_t i = j * per; i < std::min(count, (j + 1) * per); ++i) {
+            bool ok = true;
+            if (commitments_xy) ok = kzg_host::g1_encode_be(commitments_xy + 8 * i, out_commitments_be + 32 * i) && ok;
+            if (length_commitments) ok = kzg_host::g2_encode_be(length_commitments + 16 * i, out_length_commitments_be + 64 * i) && ok;
+            if (length_proofs) ok = kzg_host::g2_encode_be(length_proofs + 16 * i, out_length_proofs_be + 64 * i) && ok;
+            if (!ok) bad.store(1, std::memory_order_relaxed);
         }
-        std::vector<G1> ps;
-        std::vector<G2> qs;
-        header_pairs(fx, U, q, g2j_to_affine(sum_w), &ps, &qs);
-        return pairings_product_is_one(ps.data(), qs.data(), (int)ps.size(), host_parallel_for);
-    };
-    size_t bad = 0;
-    const size_t checks = locate_search(lhs.data(), rhs.data(), n_groups, HeaderSumOps<Xyzz, G2Jac, OpsA, OpsB>(), holds, out_group_ok, &bad);
-    *out_bad_groups = bad;
-    if (out_pairing_checks) *out_pairing_checks = checks;
-    if (opts().vb_trace)
-        fprintf(stderr, "  verify_length_proof_batch_locate count=%zu groups=%zu classes=%zu bits=%d: shared prefix %.3f ms, G2 group sums %.3f ms, G1 group sums %.3f ms, "
-                "host sums %.3f ms, search %.3f ms, %zu pairing checks, %zu bad groups\n", count, n_groups, cls.present.size(), st.bits, ms_between(st.t0, t_sums), gs.ms_g2,
-                gs.ms_g1, ms_between(t_host, t_search), ms_between(t_search, Clock::now()), checks, bad);
+    });
+    return bad.load() ? KZG_ERR_INVALID_ARG : KZG_OK;
+}
+
+int32_t kzg_header_items_decode_be(kzg_ctx* ctx, const uint8_t* commitments_be, const uint8_t* length_commitments_be, const uint8_t* length_proofs_be, size_t count,
+                                   uint64_t* out_commitments_xy, uint64_t* out_length_commitments, uint64_t* out_length_proofs, uint64_t* bad_index,
+                                   int32_t* bad_array) {
+    if (!ctx) return KZG_ERR_INVALID_ARG;
+    if (count && (!commitments_be || !length_commitments_be || !length_proofs_be || !out_commitments_xy || !out_length_commitments || !out_length_proofs))
+        return KZG_ERR_INVALID_ARG;
+    if (count > kzg::HEADER_MAX_COUNT) return KZG_ERR_TOO_LARGE;
+    if (count == 0) return KZG_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (slot0_busy(ctx)) return KZG_ERR_INVALID_ARG;
+    KZG_HIP_TRY(ctx, ctx->msm.bases.reserve(2 * count * 128));
+    KZG_HIP_TRY(ctx, ctx->ml[5].reserve(count * 65));                                   // wire commitments | identity bytes
+    HeaderBytesDecode job;
+    job.commitments_be = commitments_be; job.length_commitments_be = length_commitments_be; job.length_proofs_be = length_proofs_be;
+    job.count = count;
+    job.wire = true;
+    job.d_commitments = ctx->ml[5].as<uint4>();
+    job.d_commitments_inf = ctx->ml[5].as<uint8_t>() + count * 64;
+    job.d_g2 = ctx->msm.bases.as<uint4>();
+    int32_t rc = header_bytes_decode(ctx, &job);
+    if (rc != KZG_OK) return rc;
+    rc = header_bytes_status(ctx, "kzg_header_items_decode_be", job, bad_index, bad_array);
+    if (rc != KZG_OK) return rc;
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(out_commitments_xy, job.d_commitments, count * 64, hipMemcpyDeviceToHost, ctx->stream));
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(out_length_commitments, job.d_g2, count * 128, hipMemcpyDeviceToHost, ctx->stream));
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(out_length_proofs, job.d_g2 + 8 * count, count * 128, hipMemcpyDeviceToHost, ctx->stream));
+    KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return KZG_OK;
+}
+
+int32_t kzg_verify_length_proof_batch_bytes(kzg_ctx* ctx, const uint8_t* commitments_be, const uint8_t* length_commitments_be, const uint8_t* length_proofs_be,
+                                            const uint64_t* claimed_lens, size_t count, const uint64_t* shift_lens, const uint64_t* g1_tau_shifts_xy, size_t n_shifts,
+                                            const uint64_t* weights_mont, int32_t* out_ok, uint64_t* out_weights_mont, uint64_t* bad_index, int32_t* bad_array) {
+    HeaderStage st;
+    bool empty = false;
+    int32_t rc = header_batch_prefix_bytes("kzg_verify_length_proof_batch_bytes", ctx, !out_ok, commitments_be, length_commitments_be, length_proofs_be, claimed_lens, count,
+                                           shift_lens, g1_tau_shifts_xy, n_shifts, weights_mont, HeaderGrouping(), bad_index, bad_array, &empty, &st);
+    if (rc != KZG_OK) return rc;
+    if (empty) { *out_ok = 1; return KZG_OK; }
+    rc = header_verify_tail(ctx, st, nullptr, count, n_shifts, out_ok);
+    if (rc == KZG_OK && out_weights_mont) memcpy(out_weights_mont, st.weights, (count + 1) * 32);
+    return rc;
+}
+
+int32_t kzg_verify_length_proof_batch_locate_bytes(kzg_ctx* ctx, const uint8_t* commitments_be, const uint8_t* length_commitments_be, const uint8_t* length_proofs_be,
+                                                   const uint64_t* claimed_lens, size_t count, const uint64_t* shift_lens, const uint64_t* g1_tau_shifts_xy,
+                                                   size_t n_shifts, const uint64_t* weights_mont, const uint64_t* group_indices, size_t n_groups,
+                                                   uint8_t* out_group_ok, size_t* out_bad_groups, size_t* out_pairing_checks, uint64_t* bad_index, int32_t* bad_array) {
+    HeaderStage st;
+    HeaderGrouping grp;
+    grp.on = true; grp.group_indices = group_indices; grp.n_groups = n_groups;
+    bool empty = false;
+    int32_t rc = header_batch_prefix_bytes("kzg_verify_length_proof_batch_locate_bytes", ctx, !out_bad_groups || (n_groups && !out_group_ok), commitments_be,
+                                           length_commitments_be, length_proofs_be, claimed_lens, count, shift_lens, g1_tau_shifts_xy, n_shifts, weights_mont, grp,
+                                           bad_index, bad_array, &empty, &st);
+    if (rc != KZG_OK) return rc;
+    if (empty) {                                                     // nothing to refuse: no device work, no pairing
+        if (n_groups) memset(out_group_ok, 1, n_groups);
+        *out_bad_groups = 0;
+        if (out_pairing_checks) *out_pairing_checks = 0;
+        return KZG_OK;
+    }
+    return header_locate_tail(ctx, st, nullptr, count, n_shifts, group_indices, n_groups, out_group_ok, out_bad_groups, out_pairing_checks);
 }
 
 int32_t kzg_g2_decompress_be(const uint8_t* bytes, size_t n_points, uint64_t* out_g2_mont, uint64_t* bad_index) {

@@ -388,6 +388,30 @@ int32_t coset_bytes_collect(kzg_ctx* ctx, CosetBytesDecode* job);    // drains t
 // the status of a bad word (KZG_OK for 0xFFFFFFFF): KZG_ERR_DESERIALIZE / KZG_ERR_NOT_ON_CURVE, the element's index / per_item to *bad_index (may be
 // null), a line with the array's name for kzg_ctx_last_error
 int32_t coset_bytes_status(kzg_ctx* ctx, const char* who, const char* array, uint32_t bad_word, size_t per_item, uint64_t* bad_index);
+// Serialized blob headers decoded on the device (headerbytes.hip).  Called under ctx->mu with the device set and slot 0 idle; count <= 2^20.  Per
+// header 32 B of gnark-compressed commitment and 64 B each of length commitment and length proof (g2_decode.h's format and the identity 0x40 || 63
+// zeros), staged through the pinned memory of slot 0's workspace into ws.bases_wire (G2) and ctx->cb[1] (G1), where they stay.  The G2 elements
+// leave subgroup-checked at d_g2: the device format of curve_g2.h in the order C2_0, pi2_0, C2_1, .. or, with `wire`, wire points, the count C2 in
+// front of the count pi2 (the identity as zeros either way).  The commitments leave at d_commitments in the device format of curve.h or, with `wire`,
+// as wire points with one identity byte each at d_commitments_inf.  bad_g1 = index << 2 | kind (G1_BAD_* of g1_decode.h) of the smallest refused
+// commitment, bad_g2 = (2 header + (0 C2, 1 pi2)) << 2 | kind (G2_BAD_* of g2_decode.h) of the smallest refused element, or 0xFFFFFFFF.
+struct HeaderBytesDecode {
+    const uint8_t *commitments_be = nullptr, *length_commitments_be = nullptr, *length_proofs_be = nullptr;
+    size_t count = 0;
+    bool wire = false;
+    uint4* d_commitments = nullptr;
+    uint8_t* d_commitments_inf = nullptr;
+    uint4* d_g2 = nullptr;
+    const uint4* d_commitments_be = nullptr;       // (set by the decode)
+    uint32_t bad_g1 = 0xFFFFFFFFu, bad_g2 = 0xFFFFFFFFu;
+};
+int32_t header_bytes_decode(kzg_ctx* ctx, HeaderBytesDecode* job);   // synchronised on return
+// the status of its two bad words (KZG_OK when both are 0xFFFFFFFF), a bad commitment first: KZG_ERR_DESERIALIZE / KZG_ERR_NOT_ON_CURVE, the header to
+// *bad_index and 0 / 1 / 2 (commitment, length commitment, length proof) to *bad_array (both may be null), a line for kzg_ctx_last_error
+int32_t header_bytes_status(kzg_ctx* ctx, const char* who, const HeaderBytesDecode& job, uint64_t* bad_index, int32_t* bad_array);
+// the item digests of the header transcript (host_fiat_shamir.h header_item_message), one lane per header, from the commitments' bytes and the decoded
+// G2 points where header_bytes_decode left them (device format); claimed_lens and out_digests (32 B per header): host.  Uses ctx->fs.  Synchronised on return
+int32_t header_item_digests_run(kzg_ctx* ctx, const uint4* d_commitments_be, const uint4* d_g2, const uint64_t* claimed_lens, size_t count, uint8_t* out_digests);
 // selected cosets (provecosets.hip): per item (poly_indices[i] or 0, coset_indices[i]) the quotient row (out_q: d wire words), the l values (out_ys) and the
 // proof (out_xy, out_inf; needs srs), each optional; rows bit-identical to multiproof_encode's.  Called under ctx->mu with the device set, the arguments checked,
 // plan.n_items > 0 and slot 0 idle; synchronised on return

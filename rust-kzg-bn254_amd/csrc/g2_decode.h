@@ -15,6 +15,7 @@
 // tests/hostcheck/g2sqrtcheck.cpp, which compares every one BY VALUE with host_pairing.h / host_g2_decode.h.  Bounds are annotated per
 // line as in fq2.h (class F: (-m, 2m); class O: (-0.0001m, 1.0001m); products as their value in m^2 against 169).
 #pragma once
+#include <cstddef>
 #include "g2_chain.h"
 
 namespace kzg {
@@ -25,6 +26,11 @@ constexpr uint32_t G2_BAD_NO_POINT = 1;         // x^3 + b is not a square: no p
 constexpr uint32_t G2_BAD_SUBGROUP = 2;         // not in the order-r subgroup
 constexpr uint32_t G2_BAD_GENERATOR = 3;        // the generator itself
 constexpr uint32_t G2_DECODE_OK = 4;
+
+// how the host drivers feed the decode kernels (g2decode.hip, headerbytes.hip): compressed points per staged chunk (1 MiB of pinned
+// memory) and per kernel launch (one wave per SIMD fills the device with 65 536 lanes)
+constexpr size_t G2_DECODE_CHUNK = 16384;
+constexpr size_t G2_DECODE_LAUNCH = 4 * G2_DECODE_CHUNK;
 
 // ---------------------------------------------------------------------------------------------
 // bytes

@@ -55,8 +55,7 @@ k_g2_decompress(const uint4* __restrict__ bytes, uint4* __restrict__ out, uint32
 // The bytes reach the device in chunks through the two halves of the workspace's pinned result buffer (one half is filled while the
 // other is in flight: no pinned allocation grows with n), and a kernel starts behind every G2_DECODE_LAUNCH points: a launch of one
 // wave per SIMD fills the device with 65 536 lanes, and launches of one stream run one after the other.
-constexpr size_t G2_DECODE_CHUNK = 16384;                           // points per staged chunk: 1 MiB
-constexpr size_t G2_DECODE_LAUNCH = 4 * G2_DECODE_CHUNK;            // points per kernel launch
+// (G2_DECODE_CHUNK points per staged chunk, G2_DECODE_LAUNCH points per kernel launch: g2_decode.h)
 static_assert(2 * G2_DECODE_CHUNK * 64 <= (size_t)MSM_MAX_OUT * 128, "two chunks fit the pinned result buffer");
 
 namespace {

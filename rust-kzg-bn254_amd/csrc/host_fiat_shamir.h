@@ -170,11 +170,20 @@ inline void g2_serialize_be(const G2& p, uint8_t out[128]) {
 // the coset transcript: d_i = SHA-256(item tag || u64be(len_i) || C_i || C2_i || pi2_i) on the host pool, seed = SHA-256(batch tag ||
 // u64be(count) || u64be(n_shifts) || n_shifts x (u64be(len) || shift) || d_0 .. d_(count-1)), and weight j = the first 16 bytes, read
 // big-endian, of SHA-256(seed || u64be(j)); j = count is rho, the weight between the two equations.
-inline void header_batch_weights_host(const uint64_t* commitments, const uint64_t* length_commitments, const uint64_t* length_proofs,
-                                      const uint64_t* claimed_lens, size_t count, const uint64_t* shift_lens, const uint64_t* shifts, size_t n_shifts,
-                                      uint64_t* out, ParallelFor parallel_for) {
-    const size_t head = 24 + 16 + 40 * n_shifts;
-    std::vector<uint8_t> data(head + 32 * count, 0);
+// The pieces are functions of their own for the entries that hash the items elsewhere (headerbytes.hip, from serialized headers): the item
+// message, the batch level with tag, sizes and shifts filled in and room for the `count` item digests from header_batch_head() on, the tail.
+constexpr size_t HEADER_ITEM_BYTES = 24 + 8 + 32 + 128 + 128;
+inline void header_item_message(uint64_t claimed_len, const uint64_t commitment[8], const uint64_t length_commitment[16], const uint64_t length_proof[16],
+                                uint8_t item[HEADER_ITEM_BYTES]) {
+    memcpy(item, HEADER_ITEM_DOMAIN, 24);
+    put_u64be(item + 24, claimed_len);
+    g1_serialize_compressed_ark(g1_from_wire(commitment), item + 32);
+    g2_serialize_be(g2_from_wire(length_commitment), item + 64);
+    g2_serialize_be(g2_from_wire(length_proof), item + 192);
+}
+inline size_t header_batch_head(size_t n_shifts) { return 24 + 16 + 40 * n_shifts; }
+inline std::vector<uint8_t> header_batch_transcript(size_t count, const uint64_t* shift_lens, const uint64_t* shifts, size_t n_shifts) {
+    std::vector<uint8_t> data(header_batch_head(n_shifts) + 32 * count, 0);
     memcpy(data.data(), HEADER_BATCH_DOMAIN, 24);
     put_u64be(data.data() + 24, (uint64_t)count);
     put_u64be(data.data() + 32, (uint64_t)n_shifts);
@@ -182,22 +191,10 @@ inline void header_batch_weights_host(const uint64_t* commitments, const uint64_
         put_u64be(data.data() + 40 + 40 * g, shift_lens[g]);
         g1_serialize_compressed_ark(g1_from_wire(shifts + 8 * g), data.data() + 48 + 40 * g);
     }
-    const size_t per = 64, jobs = (count + per - 1) / per;
-    auto body = [&](size_t j) {
-        uint8_t item[24 + 8 + 32 + 128 + 128];
-        memcpy(item, HEADER_ITEM_DOMAIN, 24);
-        for (size_t i = j * per; i < std::min(count, (j + 1) * per); ++i) {
-            put_u64be(item + 24, claimed_lens[i]);
-            g1_serialize_compressed_ark(g1_from_wire(commitments + 8 * i), item + 32);
-            g2_serialize_be(g2_from_wire(length_commitments + 16 * i), item + 64);
-            g2_serialize_be(g2_from_wire(length_proofs + 16 * i), item + 192);
-            Sha256 sh;
-            sha256_init(sh);
-            sha256_update(sh, item, sizeof item);
-            sha256_final(sh, data.data() + head + 32 * i);
-        }
-    };
-    if (jobs > 1) parallel_for(jobs, body); else if (jobs == 1) body(0);
+    return data;
+}
+// the tail: the seed over the complete batch transcript, then the count + 1 one-block weight hashes
+inline void header_weights_from_transcript(const std::vector<uint8_t>& data, size_t count, uint64_t* out, ParallelFor parallel_for) {
     uint8_t seed[40];
     {
         Sha256 sh;
@@ -221,6 +218,25 @@ inline void header_batch_weights_host(const uint64_t* commitments, const uint64_
         }
     };
     if (wjobs > 1) parallel_for(wjobs, wbody); else wbody(0);
+}
+inline void header_batch_weights_host(const uint64_t* commitments, const uint64_t* length_commitments, const uint64_t* length_proofs,
+                                      const uint64_t* claimed_lens, size_t count, const uint64_t* shift_lens, const uint64_t* shifts, size_t n_shifts,
+                                      uint64_t* out, ParallelFor parallel_for) {
+    const size_t head = header_batch_head(n_shifts);
+    std::vector<uint8_t> data = header_batch_transcript(count, shift_lens, shifts, n_shifts);
+    const size_t per = 64, jobs = (count + per - 1) / per;
+    auto body = [&](size_t j) {
+        uint8_t item[HEADER_ITEM_BYTES];
+        for (size_t i = j * per; i < std::min(count, (j + 1) * per); ++i) {
+            header_item_message(claimed_lens[i], commitments + 8 * i, length_commitments + 16 * i, length_proofs + 16 * i, item);
+            Sha256 sh;
+            sha256_init(sh);
+            sha256_update(sh, item, sizeof item);
+            sha256_final(sh, data.data() + head + 32 * i);
+        }
+    };
+    if (jobs > 1) parallel_for(jobs, body); else if (jobs == 1) body(0);
+    header_weights_from_transcript(data, count, out, parallel_for);
 }
 
 }  // namespace kzg_host

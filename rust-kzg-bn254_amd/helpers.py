@@ -172,6 +172,20 @@ def compress_g1_be(points) -> bytes:
     return out[:32 * n].tobytes()
 
 
+def compress_g2_be(points) -> bytes:
+    """G2 wire points -> gnark-compressed bytes, 64 per point (`kzg_header_items_encode_be`, host): X.A1 || X.A0 big-endian, 0b10 / 0b11 in
+    the top two bits of byte 0 for the smaller / larger y, the all-zero wire point as 0x40 and 63 zero bytes (the identity of the header
+    format; the G2 SRS loaders have none)."""
+    pts = np.ascontiguousarray(_lib.as_u64(points, 0)).reshape(-1, 16)
+    n = len(pts)
+    out = np.zeros(64 * max(n, 1), dtype=np.uint8)
+    if n:
+        rc = _lib.load().kzg_header_items_encode_be(None, _lib.ptr(pts), None, n, None, out.ctypes.data_as(_lib.u8p), None)
+        if rc != _lib.OK:
+            raise GenericError("a coordinate is not below the modulus" if rc == _lib.ERR_INVALID_ARG else _lib.status_message(rc))
+    return out[:64 * n].tobytes()
+
+
 def to_byte_array(data_fr, max_output_size: int) -> bytes:
     """helpers.rs:80-119."""
     vals = frs_to_ints(data_fr)

@@ -155,6 +155,12 @@ class KZG:
             raise GenericError(_lib.status_message(rc))
         return c, c2, pi2
 
+    def commit_with_length_proof_batch_be(self, polys, srs, g2_srs, g2_trailing, srs_order: int, claimed_len: int):
+        """`commit_with_length_proof_batch` in the serialized form a disperser sends (`verifier.encode_header_items`): (commitments_be,
+        length_commitments_be, length_proofs_be) bytes, 32 / 64 / 64 per header, what `verifier.verify_length_proof_batch_bytes` takes."""
+        from . import verifier
+        return verifier.encode_header_items(*self.commit_with_length_proof_batch(polys, srs, g2_srs, g2_trailing, srs_order, claimed_len))
+
     # ---- batched commitments: many polynomials of one length against one SRS in one kernel sequence (no counterpart in the
     # reference, which commits one polynomial per call; same values as that many calls) -----------------------------------------
     def _commit_batch(self, rows, srs, eval_form):

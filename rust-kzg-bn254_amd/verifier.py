@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib, helpers
 from .consts import BYTES_PER_FIELD_ELEMENT, FR_MODULUS, RANDOM_CHALLENGE_KZG_BATCH_DOMAIN
-from .errors import GenericError, InvalidInputLength, NotOnCurveError
+from .errors import DeserializationError, GenericError, InvalidInputLength, NotOnCurveError
 from .fr import fr_from_int, fr_to_int
 
 
@@ -200,6 +200,124 @@ def locate_bad_headers(commitments, length_commitments, length_proofs, claimed_l
                                                           len(shift_lens), None if w is None else _lib.ptr(w), _opt(gi), n_groups,
                                                           good.ctypes.data_as(_lib.u8p), C.byref(n_bad), C.byref(checks), C.byref(bad))
     _raise_for_header(rc, bad, len(c), len(shift_lens), ctx, grouped=True)
+    good = good[:n_groups].astype(bool)
+    assert int(n_bad.value) == int((~good).sum())
+    return good, int(checks.value)
+
+
+# ---- blob headers in their serialized form -----------------------------------------------------------------------------------------
+# Per header: the commitment as 32 gnark-compressed bytes, the length commitment and the length proof as 64 gnark-compressed bytes each
+# (the identity 0x40 and zeros), the claimed length as an integer.
+_HEADER_ARRAYS = ("commitment", "length commitment", "length proof", "shift")
+
+
+def _header_u8(data, per):
+    buf = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    if len(buf) % per != 0:
+        raise InvalidInputLength()
+    return buf
+
+
+def _header_bytes_args(commitments_be, length_commitments_be, length_proofs_be, claimed_lens, shifts):
+    c, c2, p2 = _header_u8(commitments_be, 32), _header_u8(length_commitments_be, 64), _header_u8(length_proofs_be, 64)
+    lens = np.ascontiguousarray([int(d) for d in claimed_lens], dtype=np.uint64)
+    count = len(lens)
+    if not (len(c) == 32 * count and len(c2) == 64 * count and len(p2) == 64 * count):
+        raise InvalidInputLength()
+    shift_lens = np.ascontiguousarray([int(d) for d in shifts], dtype=np.uint64)
+    shift_pts = np.ascontiguousarray([_lib.as_u64(shifts[d], 0).reshape(8) for d in shifts], dtype=np.uint64).reshape(-1, 8)
+    u8 = lambda a: a.ctypes.data_as(_lib.u8p) if a.size else None                       # noqa: E731
+    return (c, c2, p2), (u8(c), u8(c2), u8(p2)), lens, shift_lens, shift_pts
+
+
+def _raise_for_header_bytes(rc, bad, arr, count, n_shifts, ctx, grouped=False):
+    """the statuses of the header entries on serialized input: a refused element by the name of its array and its header"""
+    name = _HEADER_ARRAYS[arr.value] if 0 <= arr.value < 4 else "element"
+    if rc == _lib.ERR_DESERIALIZE:
+        raise DeserializationError("%s %d: not a canonical encoding (flag bits, or a coordinate not below the modulus)" % (name, bad.value))
+    if rc == _lib.ERR_NOT_ON_CURVE:
+        raise NotOnCurveError("%s %d: no such point on the curve" % (name, bad.value) if arr.value == 0 else
+                              "%s %d: no such point on the twist, or not in the order-r subgroup" % (name, bad.value))
+    if rc == _lib.ERR_G1_NOT_ON_CURVE:
+        raise NotOnCurveError("shift %d not on curve" % bad.value)
+    _raise_for_header(rc, bad, count, n_shifts, ctx, grouped)
+
+
+def encode_header_items(commitments, length_commitments, length_proofs):
+    """The disperser's half (`kzg_header_items_encode_be`, host): wire commitments (count, 8) and wire G2 elements (count, 16) each ->
+    (commitments_be, length_commitments_be, length_proofs_be) bytes, 32 / 64 / 64 per header; an all-zero wire point encodes as the
+    identity.  Any of the three may be None (its output is then None)."""
+    arrs = [None if a is None else np.ascontiguousarray(_lib.as_u64(a, w)).reshape(-1, w) for a, w in ((commitments, 8), (length_commitments, 16), (length_proofs, 16))]
+    counts = {len(a) for a in arrs if a is not None}
+    if len(counts) > 1:
+        raise InvalidInputLength()
+    count = counts.pop() if counts else 0
+    outs = [None if a is None else np.zeros(max(count * per, 1), np.uint8) for a, per in zip(arrs, (32, 64, 64))]
+    if count:
+        rc = _lib.load().kzg_header_items_encode_be(*[None if a is None else _lib.ptr(a) for a in arrs], count,
+                                                    *[None if o is None else o.ctypes.data_as(_lib.u8p) for o in outs])
+        if rc != _lib.OK:
+            raise GenericError("a coordinate is not below the modulus" if rc == _lib.ERR_INVALID_ARG else _lib.status_message(rc))
+    return tuple(None if o is None else o[:count * per].tobytes() for o, per in zip(outs, (32, 64, 64)))
+
+
+def decode_header_items(commitments_be, length_commitments_be, length_proofs_be, ctx=None):
+    """Serialized headers -> (commitments (count, 8), length_commitments (count, 16), length_proofs (count, 16)) wire words, decoded
+    strictly on the GPU with the subgroup test of every G2 element (`kzg_header_items_decode_be`): what `verify_length_proof_batch`,
+    `header_group_sums` and `locate_bad_headers` take.  DeserializationError / NotOnCurveError name the array and the header: a bad
+    commitment first, then the smallest header with a bad G2 element, its length commitment in front of its length proof."""
+    c, c2, p2 = _header_u8(commitments_be, 32), _header_u8(length_commitments_be, 64), _header_u8(length_proofs_be, 64)
+    count = len(c) // 32
+    if len(c2) != 64 * count or len(p2) != 64 * count:
+        raise InvalidInputLength()
+    out = np.zeros((count, 8), np.uint64), np.zeros((count, 16), np.uint64), np.zeros((count, 16), np.uint64)
+    if count:
+        ctx = ctx or _lib.default_context()
+        bad, arr = C.c_uint64(0), _lib.i32(-1)
+        rc = _lib.load().kzg_header_items_decode_be(ctx.handle, *[a.ctypes.data_as(_lib.u8p) for a in (c, c2, p2)], count, *[_lib.ptr(o) for o in out],
+                                                    C.byref(bad), C.byref(arr))
+        _raise_for_header_bytes(rc, bad, arr, count, 1, ctx)
+    return out
+
+
+def verify_length_proof_batch_bytes(commitments_be, length_commitments_be, length_proofs_be, claimed_lens, shifts, weights=None, ctx=None,
+                                    return_weights=False):
+    """`verify_length_proof_batch` on serialized headers, the decode inside the call (`kzg_verify_length_proof_batch_bytes`): one pass on
+    the GPU decodes the G2 elements where the chains read them and runs their one subgroup test, the commitments are decoded into the
+    bases of the G1 MSM, derived weights hash the items on the GPU.  The verdict and the weights are those of the decoded entry on
+    `decode_header_items` of the same bytes.  DeserializationError / NotOnCurveError name the array and the header as
+    `decode_header_items` does.  `return_weights=True` returns (ok, the count + 1 weights used)."""
+    arrs, ptrs, lens, shift_lens, shift_pts = _header_bytes_args(commitments_be, length_commitments_be, length_proofs_be, claimed_lens, shifts)
+    count = len(lens)
+    w = _header_weights(weights, count)
+    ctx = ctx or _lib.default_context()
+    out_w = np.zeros((count + 1, 4), np.uint64)
+    ok, bad, arr = _lib.i32(0), C.c_uint64(0), _lib.i32(-1)
+    rc = _lib.load().kzg_verify_length_proof_batch_bytes(ctx.handle, *ptrs, _opt(lens), count, _opt(shift_lens), _opt(shift_pts), len(shift_lens),
+                                                         None if w is None else _lib.ptr(w), C.byref(ok), _lib.ptr(out_w) if count else None, C.byref(bad),
+                                                         C.byref(arr))
+    _raise_for_header_bytes(rc, bad, arr, count, len(shift_lens), ctx)
+    if count == 0 and return_weights:
+        out_w = compute_header_batch_weights(np.zeros((0, 8), np.uint64), np.zeros((0, 16), np.uint64), np.zeros((0, 16), np.uint64), [], shifts) if w is None else w
+    return (bool(ok.value), out_w) if return_weights else bool(ok.value)
+
+
+def locate_bad_headers_bytes(commitments_be, length_commitments_be, length_proofs_be, claimed_lens, shifts, weights=None, ctx=None, groups="item",
+                             n_groups=None):
+    """`locate_bad_headers` on serialized headers (`kzg_verify_length_proof_batch_locate_bytes`): the prefix of
+    `verify_length_proof_batch_bytes`, then the group sums and the search of the decoded entry.  Returns (good, pairing_checks), those of
+    `locate_bad_headers` on `decode_header_items` of the same bytes."""
+    arrs, ptrs, lens, shift_lens, shift_pts = _header_bytes_args(commitments_be, length_commitments_be, length_proofs_be, claimed_lens, shifts)
+    count = len(lens)
+    w = _header_weights(weights, count)
+    gi, n_groups = _header_group_args(groups, n_groups, count)
+    ctx = ctx or _lib.default_context()
+    good = np.zeros(max(n_groups, 1), np.uint8)
+    n_bad, checks, bad, arr = _lib.sz(0), _lib.sz(0), C.c_uint64(0), _lib.i32(-1)
+    rc = _lib.load().kzg_verify_length_proof_batch_locate_bytes(ctx.handle, *ptrs, _opt(lens), count, _opt(shift_lens), _opt(shift_pts), len(shift_lens),
+                                                                None if w is None else _lib.ptr(w), _opt(gi), n_groups, good.ctypes.data_as(_lib.u8p),
+                                                                C.byref(n_bad), C.byref(checks), C.byref(bad), C.byref(arr))
+    _raise_for_header_bytes(rc, bad, arr, count, len(shift_lens), ctx, grouped=True)
     good = good[:n_groups].astype(bool)
     assert int(n_bad.value) == int((~good).sum())
     return good, int(checks.value)
