@@ -1151,6 +1151,39 @@ int32_t kzg_verify_multiproof_batch_bytes(kzg_ctx* ctx, const kzg_srs* srs, cons
                                           const uint8_t* proofs_be, size_t count, size_t n, size_t chunk_len,
                                           const uint64_t* r_powers_mont /* NULL: derived */, const uint64_t* g2_tau_l_mont, int32_t* out_ok,
                                           uint64_t* out_r_powers_mont /* may be NULL */, uint64_t* bad_index, int32_t* bad_array);
+/* ---- the retriever's half in serialized form (csrc/recover.hip, csrc/host_recover.h) --------------------------------------------------
+ * kzg_recover_from_cosets_batch with the codec inside the call: big-endian values in, big-endian rows out.  For every input whose
+ * values decode, row b of out_polys_be is kzg_coset_items_encode_be of row b of kzg_recover_from_cosets_batch on the output of
+ * kzg_coset_items_decode_be, byte for byte, and out_consistent[b] is that call's flag.  The values go up once, as bytes, and are
+ * decoded where the first kernel loads them; the rows are encoded where the last kernel stores them; no word form crosses the bus.
+ * Errors, in this order: 1 .. 8. the table of kzg_recover_from_cosets_batch, unchanged; 9. blobs * count * chunk_len > 2^28 ->
+ * KZG_ERR_TOO_LARGE; 10. a _begin in flight on slot 0 -> KZG_ERR_INVALID_ARG; 11. a value >= r -> KZG_ERR_DESERIALIZE, *bad_index (may
+ * be NULL) = the ITEM b * count + i of the smallest bad value.  The blobs are worked through in the groups of kzg_recover_batch_info,
+ * in order, and the call ends at the first group that holds a bad value: rows of that group and of earlier ones may already have been
+ * written, flags of earlier ones only.  The context stays usable after any error. */
+int32_t kzg_recover_from_cosets_batch_bytes(kzg_ctx* ctx, const uint8_t* ys_be /* blobs x count x chunk_len x 32 */,
+                                            const uint64_t* coset_indices /* index_rows x count */, size_t index_rows, size_t blobs,
+                                            size_t count, size_t n, size_t chunk_len, size_t degree_bound, int32_t eval_form,
+                                            size_t out_len /* 0 = n */, uint8_t* out_polys_be /* blobs x out_len x 32 */,
+                                            int32_t* out_consistent /* blobs, may be NULL */, uint64_t* bad_index /* may be NULL */);
+/* The retriever's call: verify the chunks of `blobs` blobs against their commitments and, if the batch is accepted, recover the blobs.
+ * *out_ok, the weights (r_powers_mont = NULL derives them: the same bits) and every decode refusal (*bad_array 0 / 1 / 2, *bad_index)
+ * are those of kzg_verify_multiproof_batch_bytes on the blobs x count items with n_commitments = blobs, commitment_indices[i] = i /
+ * count and the coset indices flattened (a single row repeated per blob).  With *out_ok = 1 the outputs are those of
+ * kzg_recover_from_cosets_batch_bytes on the same values.  With *out_ok = 0 the status is KZG_OK, no recovery kernel runs and
+ * out_polys_be / out_consistent are not written: go to kzg_verify_multiproof_batch_locate.  The values are uploaded once; the recovery
+ * reads the bytes where the verifier's front end left them on the device.  Device memory: what both halves use today, held side by side.
+ * Errors, in this order, the first two groups on the host before anything is launched: 1. rows 1 .. 9 of
+ * kzg_recover_from_cosets_batch_bytes (its pointers: ctx, ys_be, coset_indices, out_polys_be); 2. the host checks of
+ * kzg_verify_multiproof_batch_bytes (its pointers: srs, commitments_be, proofs_be, out_ok, g2_tau_l_mont when chunk_len != 1; the SRS;
+ * chunk_len > the SRS), a _begin in flight on slot 0; 3. that entry's device-side refusals in its order (commitment, proof, value, then
+ * g2_tau_l_mont off the twist).  KZG_VB_TRACE=1 prints the phase times, `recover` among them, on stderr. */
+int32_t kzg_retrieve_blobs_bytes(kzg_ctx* ctx, const kzg_srs* srs, const uint8_t* commitments_be /* blobs x 32 */,
+                                 const uint64_t* coset_indices, size_t index_rows, const uint8_t* ys_be,
+                                 const uint8_t* proofs_be /* blobs x count x 32 */, size_t blobs, size_t count, size_t n, size_t chunk_len,
+                                 size_t degree_bound, int32_t eval_form, size_t out_len, const uint64_t* r_powers_mont /* NULL: derived */,
+                                 const uint64_t* g2_tau_l_mont, int32_t* out_ok, uint8_t* out_polys_be, int32_t* out_consistent,
+                                 uint64_t* bad_index, int32_t* bad_array);
 
 /* ---- blob headers in their serialized form (csrc/headerbytes.hip, csrc/header_item_stream.h, csrc/host_header_bytes.h) ---------------
  * What a validator receives off the wire, per header (C, C2, pi2, d): the commitment as 32 bytes in the G1 format above (identity 0x40

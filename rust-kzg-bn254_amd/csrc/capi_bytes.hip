@@ -1,6 +1,7 @@
 // capi_bytes.hip — the serialized-form surface of the C-ABI: gnark-compressed G1 points and big-endian scalars to and from the wire words the
 // verifier entries take (cosetbytes.hip on the device, host_coset_bytes.h on the host).  The fused verifier, kzg_verify_multiproof_batch_bytes,
-// lives beside the entry it mirrors in capi_coset.hip.
+// lives beside the entry it mirrors in capi_coset.hip, and so does the retriever's call built on it, kzg_retrieve_blobs_bytes; the recovery with the
+// codec inside, kzg_recover_from_cosets_batch_bytes, is here.
 #include "engine.h"
 #include "host_coset_bytes.h"
 
@@ -89,6 +90,27 @@ int32_t kzg_coset_items_encode_be(const uint64_t* ys_mont, const uint64_t* proof
         }
     });
     return bad.load() ? KZG_ERR_INVALID_ARG : KZG_OK;
+}
+
+// kzg_recover_from_cosets_batch with the codec inside the call: the values go up once as bytes and are decoded where the scatter kernel loads
+// them, the rows are encoded where the last kernel stores them (recover.hip).  Checks on the host first (host_recover.h)
+int32_t kzg_recover_from_cosets_batch_bytes(kzg_ctx* ctx, const uint8_t* ys_be, const uint64_t* coset_indices, size_t index_rows, size_t blobs, size_t count, size_t n,
+                                            size_t chunk_len, size_t degree_bound, int32_t eval_form, size_t out_len, uint8_t* out_polys_be, int32_t* out_consistent,
+                                            uint64_t* bad_index) {
+    int32_t rc = recover_bytes_check(!ctx || !ys_be || !coset_indices || !out_polys_be, coset_indices, index_rows, blobs, count, n, chunk_len, degree_bound,
+                                     eval_form != 0, out_len);
+    if (rc != KZG_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (slot0_refused(ctx)) return KZG_ERR_INVALID_ARG;
+    RecoverBatchPlan plan;
+    recover_batch_plan(coset_indices, index_rows, blobs, count, n, chunk_len, degree_bound, eval_form != 0, out_len, ctx->recover_group_bytes, &plan);
+    uint32_t bad_word = 0xFFFFFFFFu;
+    RecoverIo io;
+    io.ys = ys_be; io.ys_be = true; io.out = out_polys_be; io.out_be = true; io.consistent = out_consistent; io.bad_word = &bad_word;
+    rc = recover_run_batch(ctx, plan, io);
+    if (rc == KZG_ERR_DESERIALIZE) return coset_bytes_status(ctx, "kzg_recover_from_cosets_batch_bytes", "value of item", bad_word, chunk_len, bad_index);
+    return rc;
 }
 
 int32_t kzg_compute_multiproof_r_powers_bytes(const uint8_t* commitments_be, size_t n_commitments, const uint64_t* commitment_indices, const uint64_t* coset_indices,

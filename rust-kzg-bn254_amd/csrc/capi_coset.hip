@@ -1,6 +1,7 @@
 // capi_coset.hip — the coset-proof verifiers of the C-ABI (the proofs: kzg_compute_multiproofs): the weights of the batch transcript, the
 // interpolation entry, the batch equation on wire words and on serialized bytes (two front ends, coset_stage_words and coset_stage_bytes, leave the items
-// of a call on the device; one tail, coset_batch_tail, runs it), the group sums and the search for the bad groups.  Host scalars: host_coset_verify.h.
+// of a call on the device; one tail, coset_batch_tail, runs it), the retriever's call on top of the bytes front end (verify, then recover.hip on the
+// value bytes the front end left on the device), the group sums and the search for the bad groups.  Host scalars: host_coset_verify.h.
 #include "engine.h"
 #include "host_curve.h"
 #include "host_fiat_shamir.h"
@@ -433,7 +434,61 @@ int32_t kzg_verify_multiproof_batch_bytes(kzg_ctx* ctx, const kzg_srs* srs, cons
     return KZG_OK;
 }
 
-// For every group g of a partition of the items: L_g = sum_{i in g} r_i pi_i and R_g = sum_{i in g} (r_i C_{c_i} + r_i w^(k_i l) pi_i) -
+// The retriever's call: kzg_verify_multiproof_batch_bytes on the chunks of `blobs` blobs (item b count + j: commitment b, coset j of the blob's index
+// row) and, if the batch is accepted, kzg_recover_from_cosets_batch_bytes on the same values -- uploaded ONCE.  Where the recovery reads them: the
+// front end leaves the value bytes in ctx->cb[0] and the decoded words in ctx->mv[0].  The interpolation reads mv[0] in place for l <= 1024 but
+// transforms it in place above that (multiverify.hip: ntt_run per coset), while nothing behind the front end writes cb[0] (the device transcript and
+// the MSMs read it or work elsewhere): the bytes are what every shape leaves intact, so the scatter kernel decodes them on load, one path for all l
+// at one field product per value in a kernel bound by its loads.  The verifier has already refused every value >= r, so the recovery meets none.
+// Checks: the recovery's table on the host, then the verifier's table on the host, nothing launched before both; then the verifier's device-side
+// refusals in its order.  *out_ok = 0: KZG_OK, no recovery kernel runs, out_polys_be / out_consistent are not written.  Device memory: what both
+// halves use, side by side (the verifier's cb / mv / msm workspaces stay reserved while the recovery's rc / rc_ntt ones are filled).
+int32_t kzg_retrieve_blobs_bytes(kzg_ctx* ctx, const kzg_srs* srs, const uint8_t* commitments_be, const uint64_t* coset_indices, size_t index_rows, const uint8_t* ys_be,
+                                 const uint8_t* proofs_be, size_t blobs, size_t count, size_t n, size_t chunk_len, size_t degree_bound, int32_t eval_form, size_t out_len,
+                                 const uint64_t* r_powers_mont, const uint64_t* g2_tau_l_mont, int32_t* out_ok, uint8_t* out_polys_be, int32_t* out_consistent,
+                                 uint64_t* bad_index, int32_t* bad_array) {
+    int32_t rc = recover_bytes_check(!ctx || !ys_be || !coset_indices || !out_polys_be, coset_indices, index_rows, blobs, count, n, chunk_len, degree_bound,
+                                     eval_form != 0, out_len);
+    if (rc != KZG_OK) return rc;
+    const size_t N = blobs * count;
+    std::vector<uint64_t> cosets, rows;
+    retrieve_items(coset_indices, index_rows, blobs, count, &cosets, &rows);
+    rc = multiproof_batch_checks(ctx, srs, !out_ok, !commitments_be || !proofs_be, !g2_tau_l_mont && chunk_len != 1, blobs, rows.data(), cosets.data(), N, n, chunk_len,
+                                 nullptr, 0, false);
+    if (rc != KZG_OK) return rc;
+    const auto t0 = Clock::now();
+    kzg_host::G2 g2_tau_l;
+    const bool g2_ok = load_g2_tau(g2_tau_l_mont, &g2_tau_l);
+    CosetStage st;
+    rc = coset_stage_bytes(ctx, "kzg_retrieve_blobs_bytes", commitments_be, blobs, rows.data(), cosets.data(), ys_be, proofs_be, N, n, chunk_len, r_powers_mont, g2_ok,
+                           bad_index, bad_array, &st);
+    if (rc != KZG_OK) return rc;
+    CosetTailTimes t;
+    rc = coset_batch_tail(ctx, srs, st, g2_tau_l, out_ok, &t);
+    if (rc != KZG_OK) return rc;
+    const auto t_verified = Clock::now();
+    if (*out_ok) {
+        RecoverBatchPlan plan;
+        recover_batch_plan(coset_indices, index_rows, blobs, count, n, chunk_len, degree_bound, eval_form != 0, out_len, ctx->recover_group_bytes, &plan);
+        uint32_t bad_word = 0xFFFFFFFFu;
+        RecoverIo io;
+        io.d_ys = ctx->cb[0].as<uint4>(); io.ys_be = true; io.out = out_polys_be; io.out_be = true; io.consistent = out_consistent; io.bad_word = &bad_word;
+        rc = recover_run_batch(ctx, plan, io);
+        if (rc == KZG_ERR_DESERIALIZE) {                                                 // (unreachable behind the verifier's decode; reported as that would)
+            if (bad_array) *bad_array = 2;
+            return coset_bytes_status(ctx, "kzg_retrieve_blobs_bytes", "value of item", bad_word, chunk_len, bad_index);
+        }
+        if (rc != KZG_OK) return rc;
+    }
+    if (opts().vb_trace)
+        fprintf(stderr, "kzg_retrieve_blobs_bytes blobs=%zu count=%zu l=%zu: decode %.3f ms, r_powers%s %.3f ms, interpolation kernel %.3f ms, coefficient MSM %.3f ms, "
+                "host scalars + proof / commitment MSMs %.3f ms, point sums + pairing %.3f ms, recover%s %.3f ms, call %.3f ms\n", blobs, count, chunk_len, st.ms[1],
+                st.rp_path, st.ms[2], ms_between(t.start, t.interpolated), ms_between(t.interpolated, t.coeff_msm), ms_between(t.coeff_msm, t.point_msms),
+                ms_between(t.point_msms, t_verified), *out_ok ? "" : " (skipped: the batch is refused)", ms_between(t_verified, Clock::now()), ms_between(t0, Clock::now()));
+    return KZG_OK;
+}
+
+// For every group g of a partition of the items: L_g =sum_{i in g} r_i pi_i and R_g = sum_{i in g} (r_i C_{c_i} + r_i w^(k_i l) pi_i) -
 // sum_t A_{g,t} [tau^t]_1; group g is good iff e(L_g, [tau^l]_2) = e(R_g, G2), and summed over the groups (L, R) is the (lhs, rhs) of
 // kzg_verify_multiproof_batch above.
 int32_t kzg_coset_group_sums(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments, const uint64_t* commitment_indices,

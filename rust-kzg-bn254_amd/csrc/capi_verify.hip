@@ -428,7 +428,9 @@ int32_t kzg_recover_from_cosets_batch(kzg_ctx* ctx, const uint64_t* ys_mont, con
     RecoverBatchPlan plan;
     recover_batch_plan(coset_indices, index_rows, blobs, count, n, chunk_len, degree_bound, eval_form != 0, out_len, ctx->recover_group_bytes, &plan);
     KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return recover_run_batch(ctx, plan, ys_mont, out_polys_mont, out_consistent);
+    RecoverIo io;
+    io.ys = ys_mont; io.out = out_polys_mont; io.consistent = out_consistent;
+    return recover_run_batch(ctx, plan, io);
 }
 
 int32_t kzg_ctx_set_recover_group_bytes(kzg_ctx* ctx, size_t bytes) {

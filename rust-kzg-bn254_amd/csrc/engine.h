@@ -143,7 +143,7 @@ struct kzg_ctx {
     kzg::DeviceBuffer ml[6];                   // kzg_coset_group_sums / kzg_verify_multiproof_batch_locate (multilocate.hip): group coefficients | the plan's arrays | partial point sums | group sums | rows + shifted weights | proofs + commitments; kzg_header_group_sums (capi_g2.hip) works in [1] .. [5] the same way
     kzg::DeviceBuffer fs[2];                  // the coset transcript on the device (fsdevice.hip): commitment rows | proofs, digests | power tables | flag; kzg_sha256_rows: messages, digests
     kzg::DeviceBuffer cb[2];                   // serialized coset items (cosetbytes.hip): value bytes | point bytes (commitments, proofs), decoded wire points, the bad words
-    kzg::DeviceBuffer rc[3];                   // kzg_recover_from_cosets(_batch) (recover.hip), for a group of blobs: work values | item maps, patterns, missing lists, flags, vanishing values, partial products (RecoverBatchPlan's layout) | powers of g
+    kzg::DeviceBuffer rc[3];                   // kzg_recover_from_cosets(_batch) (recover.hip), for a group of blobs: work values | item maps, patterns, missing lists, flags, vanishing values, partial products (RecoverBatchPlan's layout), then the bad word of a call on serialized values | powers of g
     int rc_gpow_log = -1;                      // rc[2] holds the factored tables of g^t and g^-t for t < 2^rc_gpow_log (-1: none yet)
     kzg::NttWorkspace rc_ntt;                  // its `data` also stages the uploaded coset values (dead before the first transform) and the compacted rows of out_len < n (after the last)
     kzg::DeviceBuffer pc[4];                   // kzg_prove_cosets / kzg_coset_quotients (provecosets.hip): the referenced polynomials' coefficients | a group's quotient rows | its heads block, then its twisted remainders | its items' polynomial slots and coset indices
@@ -420,9 +420,19 @@ int32_t prove_cosets_run(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* polys_mont,
 // erasure decoding (recover.hip): the polynomial of degree < count l through the values of the plan's cosets (ys: host, count x l wire values), as n
 // coefficients or evaluations on the host; *consistent = its coefficients from plan.degree_bound on are zero.  Called under ctx->mu, synchronised on return
 int32_t recover_run(kzg_ctx* ctx, const RecoverPlan& plan, const uint64_t* ys, bool eval_form, uint64_t* out_poly, int32_t* consistent);
-// the same for the plan's blobs, group by group, every stage one launch per group (ys: blobs x count x l, out_polys: blobs x plan.out_len wire values,
-// consistent: blobs flags or null); recover_run is the batch of one
-int32_t recover_run_batch(kzg_ctx* ctx, const RecoverBatchPlan& plan, const uint64_t* ys, uint64_t* out_polys, int32_t* consistent);
+// Where a batch takes its values (blobs x count x l, 32 B each) and how its rows (blobs x plan.out_len, 32 B each) leave
+struct RecoverIo {
+    const void* ys = nullptr;          // host values, staged group by group; ignored when d_ys is set
+    const uint4* d_ys = nullptr;       // or: the values where they lie on the device (valid on ctx->stream), no upload
+    bool ys_be = false;                // the values are 32-byte big-endian integers (decoded on load), not wire words
+    void* out = nullptr;               // host rows
+    bool out_be = false;               // ... as 32-byte big-endian integers, not wire words
+    int32_t* consistent = nullptr;     // blobs flags or null
+    uint32_t* bad_word = nullptr;      // ys_be, KZG_ERR_DESERIALIZE: (the smallest index of a value >= r) << 2, for coset_bytes_status; may be null
+};
+// the same for the plan's blobs, group by group, every stage one launch per group; recover_run is the batch of one on host words.  With ys_be a value
+// >= r ends the call at its group with KZG_ERR_DESERIALIZE (rows up to that group may have been written; needs blobs x count x l <= 2^28)
+int32_t recover_run_batch(kzg_ctx* ctx, const RecoverBatchPlan& plan, const RecoverIo& io);
 
 // polynomial pipeline (poly.hip)
 int32_t proof_run(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* evals, size_t n, const uint64_t z[4],

@@ -91,5 +91,13 @@ KZG_HD bool fr_decode_be_to_wire(uint32_t out[8], const uint32_t raw[8]) {
     fe_pack(out, t);
     return below;
 }
+// the way back: wire form (canonical) -> the 32 big-endian bytes of the integer (as 8 words), the exact inverse of fr_decode_be_to_wire
+// on every canonical wire element
+KZG_HD void fr_encode_wire_to_be(uint32_t out_raw[8], const uint32_t wire[8]) {
+    uint32_t w32[8];
+    fe_wire_to_canonical_words<FrParams>(w32, wire);                         // [0, 2^256) below 5.3m, times 32: the integer in [0, m)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) out_raw[k] = __builtin_bswap32(w32[7 - k]);
+}
 
 }  // namespace kzg

@@ -3,8 +3,9 @@
 // the vanishing polynomial) and, per coset, the item that carries its values.  Nothing here grows with n: the work is O(m), m = n / l.
 // kzg_recover_from_cosets_batch adds the plan of a batch (below): the checks of its table, the blobs' missing sets deduplicated into
 // PATTERNS, the grouping by a byte budget, the word layout of a group's small arrays and the host array one upload carries.
-// Pure host code: no HIP type, no kzg_ctx, no device call; also compiled with g++ by tests/hostcheck/recovercheck.cpp and
-// tests/hostcheck/recoverbatchcheck.cpp.
+// The serialized-form entries (kzg_recover_from_cosets_batch_bytes, kzg_retrieve_blobs_bytes) add their table and the blobs' chunks as verifier items.
+// Pure host code: no HIP type, no kzg_ctx, no device call; also compiled with g++ by tests/hostcheck/recovercheck.cpp,
+// tests/hostcheck/recoverbatchcheck.cpp and tests/hostcheck/recoverbytescheck.cpp.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -131,6 +132,29 @@ inline int32_t recover_batch_check(bool any_null, const uint64_t* coset_indices,
     if (out_len != 0 && (eval_form ? out_len != n : (out_len < bound || out_len > n))) return KZG_ERR_INVALID_ARG;
     return recover_batch_size_check(blobs, count, n, l);
 }
+// ---- the serialized-form entries (kzg_recover_from_cosets_batch_bytes, kzg_retrieve_blobs_bytes) ---------------------------------------------
+// A refused value is reported as (its index in the call) << 2 in one 32-bit word, the convention of the byte decoders, whose cap is the same
+constexpr size_t RECOVER_BYTES_MAX_VALUES = (size_t)1 << 28;
+// kzg_recover_from_cosets_batch_bytes: the table of kzg_recover_from_cosets_batch unchanged and in its order, then the cap on the values of a call
+inline int32_t recover_bytes_check(bool any_null, const uint64_t* coset_indices, size_t index_rows, size_t blobs, size_t count, size_t n,
+                                   size_t chunk_len, size_t degree_bound, bool eval_form, size_t out_len) {
+    const int32_t rc = recover_batch_check(any_null, coset_indices, index_rows, blobs, count, n, chunk_len, degree_bound, eval_form, out_len);
+    if (rc != KZG_OK) return rc;
+    if (blobs > RECOVER_BYTES_MAX_VALUES / (count * chunk_len)) return KZG_ERR_TOO_LARGE;
+    return KZG_OK;
+}
+// kzg_retrieve_blobs_bytes runs the same table first, then the verifier's (capi_coset.hip) on the blobs' chunks as its items: item i = b count + j has commitment row b and coset coset_indices[(index_rows == 1 ? 0 : b) count + j]
+inline void retrieve_items(const uint64_t* coset_indices, size_t index_rows, size_t blobs, size_t count, std::vector<uint64_t>* cosets,
+                           std::vector<uint64_t>* rows) {
+    cosets->resize(blobs * count);
+    rows->resize(blobs * count);
+    for (size_t b = 0; b < blobs; ++b)
+        for (size_t j = 0; j < count; ++j) {
+            (*cosets)[b * count + j] = coset_indices[(index_rows == 1 ? 0 : b) * count + j];
+            (*rows)[b * count + j] = b;
+        }
+}
+
 // kzg_recover_batch_info's checks: the rows a shape alone can fail (no indices, no bound, no form: out_len is only held to <= n)
 inline int32_t recover_batch_info_check(bool any_null, size_t blobs, size_t count, size_t n, size_t chunk_len, size_t out_len) {
     if (any_null || blobs == 0) return KZG_ERR_INVALID_ARG;

@@ -33,12 +33,24 @@
 //   * g^t and g^-t are factored like the twiddle tables, 2^10 + n / 2^10 entries each (one product per element from 2^10 on), kept per context.
 //   * values stay in the wire residue class a 2^256 between the kernels (the factors are internal Montgomery), as in ntt.hip; every kernel
 //     writes canonical words, so equal inputs give equal bits.
-// Lazy-reduction bounds are written at each site; the boundcheck build counts violations (tests/test_gpu_recover.py, tests/test_gpu_recover_batch.py).
+// SERIALIZED FORM (kzg_recover_from_cosets_batch_bytes, kzg_retrieve_blobs_bytes): the same driver takes its values as 32-byte big-endian
+// integers and writes its rows as such (RecoverIo, engine.h).  The values are decoded ON LOAD by k_recover_scatter<true>: every present
+// value is read exactly once there, so the decode is a byte swap, a compare with r and one product into the wire class in front of the
+// product with zdom -- no pass of its own over count l 32 B per blob (k_fr_decode_be in place over the staged bytes was the alternative).
+// The fused load keeps the kernel free of scratch (the compiler's figures: profiles/recover_bytes.md).  A value >= r computes with zero
+// and reports atomicMin(bad, value index << 2) on one word per call, read with the group's flags at the group's one synchronisation;
+// the call stops at the first group with a bad value (groups are in order: it holds the smallest bad index of the call), and rows of
+// that group and of EARLIER groups may already have been written to the caller's buffer (flags: of earlier groups only).  Coefficient rows leave through fr_encode_wire_to_be in
+// k_recover_scale<2, true>; evaluation rows get one in-place pass k_fr_encode_be behind the last transform.  The values may also be
+// device-resident (words or bytes): no upload at all, the scatter reads them where they lie.
+// Lazy-reduction bounds are written at each site; the boundcheck build counts violations (tests/test_gpu_recover.py, tests/test_gpu_recover_batch.py,
+// tests/test_gpu_recover_bytes.py).
 // Not tried: the scale passes fused into the first load / last store of the transforms next to them, two running products per lane
 // (fe_mul2), a product tree for m > 2^16, the complement form z = (Y^m - 1) / prod_present, pinned staging, one group's copies behind the next group's kernels.  Measured figures: profiles/recover.md,
 // profiles/recover_batch.md.
 #include "poly_common.h"
 #include "fe_invert.h"
+#include "g1_decode.h"   // the steps of fr_decode_be_to_wire on load, fr_encode_wire_to_be on store
 
 #include <algorithm>
 
@@ -187,10 +199,14 @@ k_recover_vanish_fold(const int32_t* __restrict__ partial, uint32_t rows, uint32
 
 // ---- 2. D_i = ys z(w^(l k)) on a present coset k = i mod m (entry j = i / m of its item), 0 on a missing one ------------------------------
 // Blob blockIdx.y: its count l values, its row of n work values, the item map of its index row (item_stride = 0: one row for all) and the
-// zdom of its pattern.
+// zdom of its pattern.  BE: the values are 32-byte big-endian integers, decoded on load by the steps of fr_decode_be_to_wire; one >= r counts
+// as zero and reports its index in the call, first_value + its place in the group (< 2^28: host_recover.h), through atomicMin on the call's
+// one word.
+template <bool BE>
 __global__ void __launch_bounds__(RC_THREADS)
 k_recover_scatter(const uint4* __restrict__ ys, const uint32_t* __restrict__ item_of, uint32_t item_stride, const uint32_t* __restrict__ pattern_of,
-                  uint32_t count, uint32_t n, uint32_t m, int log_m, int log_l, const int32_t* __restrict__ zdom, uint4* __restrict__ data) {
+                  uint32_t count, uint32_t n, uint32_t m, int log_m, int log_l, const int32_t* __restrict__ zdom, uint4* __restrict__ data,
+                  uint32_t first_value, uint32_t* __restrict__ bad) {
     const uint32_t i = blockIdx.x * RC_THREADS + threadIdx.x, b = blockIdx.y;
     if (i >= n) return;
     ys += 2 * ((size_t)b * count << log_l);
@@ -202,7 +218,29 @@ k_recover_scatter(const uint4* __restrict__ ys, const uint32_t* __restrict__ ite
     fe_set_zero(v);
     if (item != RECOVER_NO_ITEM) {                                   // item < count by construction (host_recover.h)
         Fr z;
-        rc_load_words(v, ys, ((size_t)item << log_l) + j);           // < 5.3 m
+        const size_t at = ((size_t)item << log_l) + j;
+        if (BE) {
+            const uint4 q0 = ys[2 * at], q1 = ys[2 * at + 1];
+            const uint32_t raw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+            uint32_t w32[8];
+#pragma unroll
+            for (int t = 0; t < 8; ++t) w32[t] = __builtin_bswap32(raw[7 - t]);
+            bool below = false;
+#pragma unroll
+            for (int t = 0; t < 8; ++t) below = w32[t] < FrParams::P32[t] ? true : (w32[t] > FrParams::P32[t] ? false : below);
+            if (!below) {
+                atomicMin(bad, (first_value + (((uint32_t)b * count + item) << log_l) + j) << 2);
+#pragma unroll
+                for (int t = 0; t < 8; ++t) w32[t] = 0;
+            }
+            Fr kin;
+            fe_unpack(v, w32);                                       // [0, 2^256): below 5.3 m
+#pragma unroll
+            for (int t = 0; t < NL; ++t) kin.l[t] = (int32_t)FrParams::K_RAW[t];
+            fe_mul(v, v, kin);                                       // 5.3 m * m: v 2^256 in (-m, 2m)
+        } else {
+            rc_load_words(v, ys, at);                                // < 5.3 m
+        }
         pl_load(z, zdom, m, k);                                      // (-m, 2m)
         fe_mul(v, v, z);                                             // |v z| < 5.3 m * 2 m
     }
@@ -212,8 +250,8 @@ k_recover_scatter(const uint4* __restrict__ ys, const uint32_t* __restrict__ ite
 // ---- 4, 5, 6: the pointwise passes on row blockIdx.y.  MODE 0: entry t times g^t; 1: entry i times zsinv[i mod m] of the blob's pattern;
 // 2: entry t times g^-t, and the blob's flag.  MODE 2 writes the first out_len entries of the row to row blockIdx.y of `out`, out_len apart:
 // out = data and out_len = n is in place, out_len < n compacts the rows into another buffer for one contiguous download (the entries
-// from out_len on are only tested).
-template <int MODE>
+// from out_len on are only tested).  BE (MODE 2): the stored entries leave as 32 big-endian bytes; the flag tests the canonical words as before.
+template <int MODE, bool BE = false>
 __global__ void __launch_bounds__(RC_THREADS)
 k_recover_scale(uint4* data, uint32_t n, RcPow gp, const int32_t* __restrict__ zsinv, const uint32_t* __restrict__ pattern_of, uint32_t m,
                 uint32_t degree_bound, uint32_t* __restrict__ flag, uint4* out, uint32_t out_len) {
@@ -228,13 +266,36 @@ k_recover_scale(uint4* data, uint32_t n, RcPow gp, const int32_t* __restrict__ z
         if (MODE != 2) rc_store_canon(data + 2 * (size_t)b * n, i, v);
         else {
             fe_canon(v);                                             // (-m, 2m) -> canonical: the flag tests the words whether or not they are stored
-            if (i < out_len) rc_store_words(out + 2 * (size_t)b * out_len, i, v);
+            if (i < out_len) {
+                if (BE) {
+                    uint32_t w[8], o[8];
+                    fe_pack(w, v);
+                    fr_encode_wire_to_be(o, w);                      // words < m, times 32
+                    out[2 * ((size_t)b * out_len + i)] = make_uint4(o[0], o[1], o[2], o[3]);
+                    out[2 * ((size_t)b * out_len + i) + 1] = make_uint4(o[4], o[5], o[6], o[7]);
+                } else {
+                    rc_store_words(out + 2 * (size_t)b * out_len, i, v);
+                }
+            }
             nonzero = i >= degree_bound && !fe_is_literal_zero(v);
         }
     }
     if (MODE == 2) {
         if (__syncthreads_or(nonzero) && threadIdx.x == 0) flag[b] = 1u;   // every writer stores the same word
     }
+}
+
+// ---- 7'. evaluation rows leaving as bytes: `total` canonical wire values in place, one lane per value, 2 x uint4 in and out ----------------
+__global__ void __launch_bounds__(RC_THREADS)
+k_fr_encode_be(uint4* __restrict__ rows, size_t total) {
+    const size_t i = (size_t)blockIdx.x * RC_THREADS + threadIdx.x;
+    if (i >= total) return;
+    const uint4 q0 = rows[2 * i], q1 = rows[2 * i + 1];
+    const uint32_t w[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+    uint32_t o[8];
+    fr_encode_wire_to_be(o, w);                                      // canonical words < m, times 32
+    rows[2 * i] = make_uint4(o[0], o[1], o[2], o[3]);
+    rows[2 * i + 1] = make_uint4(o[4], o[5], o[6], o[7]);
 }
 
 // the factored tables of g^t and g^-t for t < 2^log_n in ctx->rc[2], built on ctx->stream when the context has none that long
@@ -264,8 +325,10 @@ static int32_t recover_gpow_tables(kzg_ctx* ctx, int log_n, RcPow* fwd, RcPow* i
 
 // The blobs [b0, b0 + g) of the plan: one launch per stage, the blob as grid.y, the pattern as a grid dimension of the vanishing values.
 // `fresh`: upload indices and patterns and compute the vanishing values (false: those of the previous group serve, one index row).
+// The values come from the host (words or bytes, staged alike: 32 B each) or lie on the device already; the rows leave as words or as bytes
+// (io: RecoverIo, engine.h).  d_bad: the bad word of a call on serialized values, behind the plan's layout in rc[1].
 static int32_t recover_run_group(kzg_ctx* ctx, const RecoverBatchPlan& plan, size_t b0, size_t g, bool fresh, const NttTables& tb, const RcPow& gp,
-                                 const RcPow& gpi, const uint64_t* ys, uint64_t* out_polys, int32_t* consistent) {
+                                 const RcPow& gpi, const RecoverIo& io, uint32_t* d_bad) {
     hipStream_t st = ctx->stream;
     const size_t n = plan.n, l = plan.l, m = plan.m, count = plan.count, out_len = plan.out_len;
     uint32_t* small = ctx->rc[1].as<uint32_t>();
@@ -275,7 +338,9 @@ static int32_t recover_run_group(kzg_ctx* ctx, const RecoverBatchPlan& plan, siz
     uint4* data = ctx->rc[0].as<uint4>();
     std::vector<uint32_t> stage;                                     // alive until the synchronisation below
     std::vector<uint32_t> flags(g, 0);
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(staged, ys + b0 * count * l * 4, g * count * l * 32, hipMemcpyHostToDevice, st));
+    const uint4* values = staged;
+    if (io.d_ys) values = io.d_ys + 2 * b0 * count * l;              // resident: read in place
+    else KZG_HIP_TRY(ctx, hipMemcpyAsync(staged, static_cast<const uint8_t*>(io.ys) + b0 * count * l * 32, g * count * l * 32, hipMemcpyHostToDevice, st));
     KZG_HIP_TRY(ctx, hipMemsetAsync(small + plan.w_flag, 0, g * 4, st));
     if (fresh) {
         size_t words = 0;
@@ -291,8 +356,13 @@ static int32_t recover_run_group(kzg_ctx* ctx, const RecoverBatchPlan& plan, siz
     }
     const dim3 ngrid((unsigned)((n + RC_THREADS - 1) / RC_THREADS), (unsigned)g);
     const uint32_t* pattern_of = small + plan.w_pat;
-    hipLaunchKernelGGL(k_recover_scatter, ngrid, dim3(RC_THREADS), 0, st, staged, small + plan.w_item, plan.index_rows == 1 ? 0u : (uint32_t)m, pattern_of,
-                       (uint32_t)count, (uint32_t)n, (uint32_t)m, plan.log_m, plan.log_l, zdom, data);
+    const uint32_t item_stride = plan.index_rows == 1 ? 0u : (uint32_t)m;
+    if (io.ys_be)
+        hipLaunchKernelGGL(k_recover_scatter<true>, ngrid, dim3(RC_THREADS), 0, st, values, small + plan.w_item, item_stride, pattern_of, (uint32_t)count, (uint32_t)n,
+                           (uint32_t)m, plan.log_m, plan.log_l, zdom, data, (uint32_t)(b0 * count * l), d_bad);
+    else
+        hipLaunchKernelGGL(k_recover_scatter<false>, ngrid, dim3(RC_THREADS), 0, st, values, small + plan.w_item, item_stride, pattern_of, (uint32_t)count, (uint32_t)n,
+                           (uint32_t)m, plan.log_m, plan.log_l, zdom, data, 0u, static_cast<uint32_t*>(nullptr));
     KZG_HIP_TRY(ctx, hipGetLastError());
     int32_t rc = ntt_run_batch(ctx, data, n, g, true, st, &ctx->rc_ntt);     // f Z
     if (rc != KZG_OK) return rc;
@@ -304,22 +374,37 @@ static int32_t recover_run_group(kzg_ctx* ctx, const RecoverBatchPlan& plan, siz
     if (rc != KZG_OK) return rc;
     // the rows leave from `data` in place, or, shorter than n, compacted into the transforms' scratch (dead after the last transform): one contiguous download
     uint4* rows = out_len < n ? staged : data;
-    hipLaunchKernelGGL(k_recover_scale<2>, ngrid, dim3(RC_THREADS), 0, st, data, (uint32_t)n, gpi, nullptr, nullptr, (uint32_t)m, (uint32_t)plan.degree_bound,
-                       small + plan.w_flag, rows, (uint32_t)out_len);
+    // coefficient rows are encoded as they are stored; evaluation rows pass through the last transform as words and are encoded behind it
+    if (io.out_be && !plan.eval_form)
+        hipLaunchKernelGGL((k_recover_scale<2, true>), ngrid, dim3(RC_THREADS), 0, st, data, (uint32_t)n, gpi, nullptr, nullptr, (uint32_t)m, (uint32_t)plan.degree_bound,
+                           small + plan.w_flag, rows, (uint32_t)out_len);
+    else
+        hipLaunchKernelGGL(k_recover_scale<2>, ngrid, dim3(RC_THREADS), 0, st, data, (uint32_t)n, gpi, nullptr, nullptr, (uint32_t)m, (uint32_t)plan.degree_bound,
+                           small + plan.w_flag, rows, (uint32_t)out_len);
     KZG_HIP_TRY(ctx, hipGetLastError());
     if (plan.eval_form) {                                            // out_len = n
         rc = ntt_run_batch(ctx, data, n, g, false, st, &ctx->rc_ntt);
         if (rc != KZG_OK) return rc;
+        if (io.out_be) {                                             // g n values fit the group's budget: far below 2^32 workgroups
+            hipLaunchKernelGGL(k_fr_encode_be, dim3((unsigned)((g * n + RC_THREADS - 1) / RC_THREADS)), dim3(RC_THREADS), 0, st, data, g * n);
+            KZG_HIP_TRY(ctx, hipGetLastError());
+        }
     }
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(out_polys + b0 * out_len * 4, rows, g * out_len * 32, hipMemcpyDeviceToHost, st));
+    uint32_t bad = 0xFFFFFFFFu;                                      // read with the flags at the group's one synchronisation
+    if (io.ys_be) KZG_HIP_TRY(ctx, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(static_cast<uint8_t*>(io.out) + b0 * out_len * 32, rows, g * out_len * 32, hipMemcpyDeviceToHost, st));
     KZG_HIP_TRY(ctx, hipMemcpyAsync(flags.data(), small + plan.w_flag, g * 4, hipMemcpyDeviceToHost, st));
     KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (consistent)
-        for (size_t i = 0; i < g; ++i) consistent[b0 + i] = flags[i] ? 0 : 1;
+    if (bad != 0xFFFFFFFFu) {                                        // the call ends here; this group's flags are not reported
+        if (io.bad_word) *io.bad_word = bad;
+        return KZG_ERR_DESERIALIZE;
+    }
+    if (io.consistent)
+        for (size_t i = 0; i < g; ++i) io.consistent[b0 + i] = flags[i] ? 0 : 1;
     return KZG_OK;
 }
 
-int32_t recover_run_batch(kzg_ctx* ctx, const RecoverBatchPlan& plan, const uint64_t* ys, uint64_t* out_polys, int32_t* consistent) {
+int32_t recover_run_batch(kzg_ctx* ctx, const RecoverBatchPlan& plan, const RecoverIo& io) {
     RoctxRange range(plan.blobs == 1 ? "kzg:recover_from_cosets" : "kzg:recover_from_cosets_batch");
     NttTables tb;
     int32_t rc = ntt_get_tables(ctx, plan.log_n, false, &tb);
@@ -329,19 +414,23 @@ int32_t recover_run_batch(kzg_ctx* ctx, const RecoverBatchPlan& plan, const uint
     if (rc != KZG_OK) return rc;
     const size_t cap = plan.groups.group;                            // every group works in the buffers of a full one
     KZG_HIP_TRY(ctx, ctx->rc[0].reserve(cap * plan.n * 32));
-    KZG_HIP_TRY(ctx, ctx->rc[1].reserve(plan.w_end * 4));
+    KZG_HIP_TRY(ctx, ctx->rc[1].reserve(plan.w_end * 4 + 16));       // + the bad word of a call on serialized values, behind the layout
     KZG_HIP_TRY(ctx, ctx->rc_ntt.data.reserve(cap * plan.n * 32));   // >= the staged values (count l <= n), the transforms' `data`, the compacted rows
+    uint32_t* d_bad = ctx->rc[1].as<uint32_t>() + plan.w_end;
+    if (io.ys_be) KZG_HIP_TRY(ctx, hipMemsetAsync(d_bad, 0xFF, 4, ctx->stream));
     for (size_t b0 = 0; b0 < plan.blobs; b0 += cap) {
         const size_t g = std::min(cap, plan.blobs - b0);
         // with one index row every group has the same item map, pattern and vanishing values, at the same place
-        rc = recover_run_group(ctx, plan, b0, g, b0 == 0 || plan.index_rows != 1, tb, gp, gpi, ys, out_polys, consistent);
+        rc = recover_run_group(ctx, plan, b0, g, b0 == 0 || plan.index_rows != 1, tb, gp, gpi, io, d_bad);
         if (rc != KZG_OK) return rc;
     }
     return KZG_OK;
 }
 
 int32_t recover_run(kzg_ctx* ctx, const RecoverPlan& plan, const uint64_t* ys, bool eval_form, uint64_t* out_poly, int32_t* consistent) {
-    return recover_run_batch(ctx, recover_batch_of_one(plan, eval_form), ys, out_poly, consistent);
+    RecoverIo io;
+    io.ys = ys; io.out = out_poly; io.consistent = consistent;
+    return recover_run_batch(ctx, recover_batch_of_one(plan, eval_form), io);
 }
 
 }  // namespace kzg

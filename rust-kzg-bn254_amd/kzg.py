@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, helpers
-from .errors import CommitError, FFTError, GenericError, NotOnCurveError, SerializationError, SrsCapacityExceeded
+from .errors import CommitError, FFTError, GenericError, InvalidInputLength, NotOnCurveError, SerializationError, SrsCapacityExceeded
 from .fr import g1_is_identity
 from .polynomial import PolynomialCoeffForm, PolynomialEvalForm
 
@@ -786,6 +786,57 @@ class KZG:
         if rc != _lib.OK:
             raise GenericError(_lib.status_message(rc))
         return out, consistent.astype(bool)
+
+    def recover_from_cosets_batch_bytes(self, coset_indices, ys_be, n: int, chunk_len: int, degree_bound=None, eval_form: bool = True, out_len=None):
+        """`recover_from_cosets_batch` on chunks as they come off the wire, the codec inside the call
+        (`kzg_recover_from_cosets_batch_bytes`): `ys_be` holds B x count x chunk_len big-endian values of 32 bytes, `coset_indices` has the
+        shape (count,) or (B, count).  Returns (bytes, consistent): B x out_len x 32 bytes, row b byte for byte `encode_coset_items` of row
+        b of `recover_from_cosets_batch` on the decoded values, and a bool array (B,).  A value not below r raises DeserializationError
+        naming its item b * count + i.  Everything else as `recover_from_cosets_batch`."""
+        idx = np.ascontiguousarray(coset_indices, dtype=np.uint64)
+        n, chunk_len = int(n), int(chunk_len)
+        if idx.ndim not in (1, 2) or idx.shape[-1] == 0:
+            raise GenericError("coset indices must have the shape (count,) or (B, count)")
+        count = int(idx.shape[-1])
+        if n < 2 or (n & (n - 1)) != 0:
+            raise FFTError("length provided is not a power of 2")
+        if chunk_len <= 0 or (chunk_len & (chunk_len - 1)) != 0:
+            raise GenericError("chunk length is not a power of 2")
+        if chunk_len > n // 2:
+            raise GenericError("chunk length exceeds half the polynomial length")
+        buf = np.frombuffer(bytes(ys_be), dtype=np.uint8) if not isinstance(ys_be, np.ndarray) else np.ascontiguousarray(ys_be, dtype=np.uint8).reshape(-1)
+        per_blob = count * chunk_len * 32
+        if len(buf) == 0 or len(buf) % per_blob != 0:
+            raise InvalidInputLength()
+        blobs = len(buf) // per_blob
+        if idx.ndim == 2 and idx.shape[0] != blobs:
+            raise GenericError("coset indices must have the shape (count,) or (B, count)")
+        index_rows = 1 if idx.ndim == 1 else blobs
+        if count > n // chunk_len:
+            raise GenericError("the number of cosets must be between 1 and n / chunk length")
+        bound = count * chunk_len if not degree_bound else int(degree_bound)               # None or 0: the default, as in the C-ABI
+        if bound < 0 or bound > count * chunk_len:
+            raise GenericError("too few cosets for the degree bound")
+        rows = n if not out_len else int(out_len)
+        if rows != n and (eval_form or not bound <= rows <= n):
+            raise GenericError("out_len is for coefficients, between the degree bound and n")
+        ctx = self._ctx()
+        out = np.zeros(blobs * rows * 32, dtype=np.uint8)
+        consistent = np.zeros(blobs, dtype=np.int32)
+        bad = C.c_uint64(0)
+        rc = _lib.load().kzg_recover_from_cosets_batch_bytes(ctx.handle, buf.ctypes.data_as(_lib.u8p), _lib.ptr(idx), index_rows, blobs, count, n, chunk_len, bound,
+                                                             1 if eval_form else 0, rows, out.ctypes.data_as(_lib.u8p),
+                                                             consistent.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(bad))
+        if rc == _lib.ERR_DESERIALIZE:
+            helpers.raise_for_decode(rc, "value of item", bad.value, ctx)
+        if rc == _lib.ERR_DOMAIN:
+            raise FFTError("Could not perform IFFT due to domain consturction error")
+        if rc == _lib.ERR_INVALID_ARG:                                                        # an index >= m, the same coset twice in a row, or slot 0 busy
+            raise GenericError("coset indices must be distinct and below n / chunk length (or slot 0 is in flight)")
+        ctx.check_device(rc)
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+        return out.tobytes(), consistent.astype(bool)
 
     # kzg.rs:237-260
     def compute_quotient_eval_on_domain(self, z_fr, eval_fr, value_fr):

@@ -644,6 +644,51 @@ def verify_multiproof_batch_bytes(commitments_be, commitment_indices, coset_indi
     return (bool(ok.value), out_rp) if return_r_powers else bool(ok.value)
 
 
+def retrieve_blobs_bytes(commitments_be, coset_indices, ys_be, proofs_be, n: int, chunk_len: int, srs, g2_tau_l=None, degree_bound=None,
+                         eval_form: bool = True, out_len=None, r_powers=None, ctx=None):
+    """The retriever's call (`kzg_retrieve_blobs_bytes`): verify the chunks of B blobs against their commitments and, if the batch is
+    accepted, recover the blobs -- values uploaded once, bytes in and bytes out.  commitments_be B x 32 bytes; `coset_indices` (count,)
+    or (B, count); ys_be B x count x l x 32 and proofs_be B x count x 32 bytes.  Returns (ok, polys_be, consistent): with ok True the
+    outputs of `KZG.recover_from_cosets_batch_bytes`, with ok False (None, None) -- go to `locate_bad_multiproofs`.  The verdict, the
+    weights and the refusals (DeserializationError / NotOnCurveError naming array and index) are those of `verify_multiproof_batch_bytes`
+    on the B x count items."""
+    n, l = int(n), int(chunk_len)
+    idx = np.ascontiguousarray(coset_indices, dtype=np.uint64)
+    if l <= 0 or len(commitments_be) == 0 or len(commitments_be) % 32 != 0 or idx.ndim not in (1, 2) or idx.shape[-1] == 0:
+        raise InvalidInputLength()
+    blobs, count = len(commitments_be) // 32, int(idx.shape[-1])
+    if idx.ndim == 2 and idx.shape[0] != blobs:
+        raise GenericError("coset indices must have the shape (count,) or (B, count)")
+    if g2_tau_l is None and l != 1:
+        raise GenericError("g2_tau_l = None (consts::G2_TAU) is [tau]_2: chunks of more than one point need [tau^l]_2")
+    cm = _u8_arg(commitments_be, blobs * 32, "commitments")
+    ys = _u8_arg(ys_be, blobs * count * l * 32, "values")
+    pf = _u8_arg(proofs_be, blobs * count * 32, "proofs")
+    rp = None if r_powers is None else np.ascontiguousarray(_lib.as_u64(r_powers, 0)).reshape(-1, 4)
+    if rp is not None and len(rp) != blobs * count:
+        raise GenericError("length's of the input are not the same")
+    bound = 0 if not degree_bound else int(degree_bound)
+    rows = n if not out_len else int(out_len)
+    if rows <= 0 or bound < 0:
+        raise GenericError("out_len is for coefficients, between the degree bound and n")
+    ctx = ctx or getattr(srs, "ctx", None) or _lib.default_context()
+    out = np.zeros(blobs * rows * 32, dtype=np.uint8)
+    consistent = np.zeros(blobs, dtype=np.int32)
+    ok, bad, arr = _lib.i32(0), C.c_uint64(0), _lib.i32(-1)
+    rc = _lib.load().kzg_retrieve_blobs_bytes(ctx.handle, srs.handle, cm[1], _lib.ptr(idx), 1 if idx.ndim == 1 else blobs, ys[1], pf[1], blobs, count, n, l, bound,
+                                              1 if eval_form else 0, rows, None if rp is None else _lib.ptr(rp), _g2_arg(g2_tau_l), C.byref(ok),
+                                              out.ctypes.data_as(_lib.u8p), consistent.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(bad), C.byref(arr))
+    if rc in (_lib.ERR_DESERIALIZE, _lib.ERR_NOT_ON_CURVE):
+        helpers.raise_for_decode(rc, _ARRAYS[arr.value] if 0 <= arr.value < 3 else "element", bad.value, ctx)
+    if rc == _lib.ERR_INVALID_ARG:
+        raise GenericError("the shape, the coset indices (distinct, below n / chunk length), the degree bound or out_len is not valid, the SRS is not "
+                           "this context's monomial one, or slot 0 is in flight")
+    _raise_for(rc, ctx)
+    if not ok.value:
+        return False, None, None
+    return True, out.tobytes(), consistent.astype(bool)
+
+
 # ---- locating the bad items of a rejected batch ----------------------------------------------------------------------------------
 pairings_verify = helpers.pairings_verify          # e(a1, a2) == e(b1, b2): the check of one pair of group sums against ([tau^l]_2, G2)
 
