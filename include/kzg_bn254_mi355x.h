@@ -1240,6 +1240,48 @@ int32_t kzg_verify_length_proof_batch_locate_bytes(kzg_ctx* ctx, const uint8_t* 
                                                    size_t n_groups, uint8_t* out_group_ok, size_t* out_bad_groups,
                                                    size_t* out_pairing_checks /* may be NULL */, uint64_t* bad_index, int32_t* bad_array);
 
+/* ---- the disperser's half in serialized form (csrc/multiproof.hip, csrc/g1_decode.h) ---------------------------------------------------
+ * kzg_encode_cosets_batch with the codec inside the call: blobs of 32-byte big-endian field elements in, serialized chunks out.  For
+ * every input whose bytes decode (kzg_coset_items_decode_be's rule for a value: canonical, a value >= r is refused, not reduced),
+ * out_ys_be and out_proofs_be are kzg_coset_items_encode_be of kzg_encode_cosets_batch on the decoded blobs, byte for byte, and
+ * out_commitments_be is the compressed kzg_commit_coeff_form_batch of the blobs' coefficients (with eval_form = 1 that is also the
+ * compressed kzg_commit_eval_form_batch: a point has one affine form; it is computed from the coefficients the call holds after its
+ * inverse transform, no Lagrange basis is built).  Each output may be NULL (it is then not computed), not all three.
+ * The groups, their plans and the byte budget are kzg_encode_cosets_batch's (kzg_encode_cosets_batch_info,
+ * kzg_ctx_set_encode_group_bytes), a shape that runs as groups of one included.  Per group the blobs go up once, as bytes, into the
+ * buffer the words would have gone to, and are decoded where the group's first kernel loads them; the value rows are encoded where
+ * the gather kernel stores them (32 bytes a value), the proofs are compressed by the affine conversion behind FK20 (32 bytes a proof,
+ * the identity 0x40 || zeros: no flag array); the commitments are the batched G1 MSM over the resident coefficients, one wire point a
+ * blob, compressed on the host.  Device memory: that of kzg_encode_cosets_batch plus 64 bytes.
+ * Errors, in this order, 1 - 3 on the host before anything is launched: 1. rows 1 - 7 of kzg_encode_cosets_batch with this entry's
+ * pointers (ctx, srs, blobs_be; all three outputs NULL -> KZG_ERR_INVALID_ARG); 2. count * poly_len > 2^28 -> KZG_ERR_TOO_LARGE; 3. a
+ * _begin in flight on slot 0 -> KZG_ERR_INVALID_ARG; 4. a value >= r -> KZG_ERR_DESERIALIZE, *bad_index (may be NULL) = b * poly_len + i
+ * of the smallest bad value of the first group that holds one.  The groups run in order and the call ends at that group, before any
+ * of its outputs is written; outputs of earlier groups have been.  The context stays usable after any error. */
+int32_t kzg_encode_cosets_batch_bytes(kzg_ctx* ctx, kzg_srs* srs, const uint8_t* blobs_be /* count x d x 32 */, size_t count,
+                                      size_t poly_len /* d */, int32_t eval_form, size_t n, size_t chunk_len,
+                                      uint8_t* out_commitments_be /* count x 32, may be NULL */,
+                                      uint8_t* out_ys_be /* count x m x l x 32, may be NULL */,
+                                      uint8_t* out_proofs_be /* count x m x 32, may be NULL */, uint64_t* bad_index /* may be NULL */);
+/* The disperser's call: kzg_encode_cosets_batch_bytes with eval_form = 0 (headers are defined on coefficients) and, from the same
+ * resident coefficients, the blob headers.  The outputs are those of that entry plus kzg_header_items_encode_be of
+ * kzg_commit_with_length_proof_batch (g2_srs, g2_trailing, trailing_first_power, srs_order, claimed_len as there, n = poly_len) on the
+ * decoded blobs, byte for byte: out_length_commitments_be and out_length_proofs_be, count x 64 each.  Per group the decoded
+ * coefficients that feed the encoder also feed the batched G1 MSM and the batched G2 MSM over both base sets (which may split the
+ * group further by its own rule, kzg_msm_g2_batch_info); a blob's two G2 elements come down as wire points and are compressed on the
+ * host.  The three header outputs are required, out_ys_be and out_proofs_be may each be NULL.  Device memory: that of
+ * kzg_encode_cosets_batch_bytes and of the G2 MSM of one group (slot 0's workspace), side by side.
+ * Errors, in this order, 1 - 3 on the host before anything is launched: 1. rows 1 - 2 of kzg_encode_cosets_batch_bytes (a null
+ * g2_srs, g2_trailing or header output counts as a null pointer of row 1); 2. a G2 handle of another device -> KZG_ERR_INVALID_ARG,
+ * then rows 3 onward of kzg_commit_with_length_proof_batch; 3. a _begin in flight on slot 0 -> KZG_ERR_INVALID_ARG; 4. a value >= r as
+ * above. */
+int32_t kzg_disperse_blobs_bytes(kzg_ctx* ctx, kzg_srs* srs, const kzg_g2srs* g2_srs, const kzg_g2srs* g2_trailing,
+                                 uint64_t trailing_first_power, uint64_t srs_order, const uint8_t* blobs_be /* count x d x 32 */,
+                                 size_t count, size_t poly_len /* d */, size_t n, size_t chunk_len, uint64_t claimed_len,
+                                 uint8_t* out_commitments_be /* count x 32 */, uint8_t* out_length_commitments_be /* count x 64 */,
+                                 uint8_t* out_length_proofs_be /* count x 64 */, uint8_t* out_ys_be /* count x m x l x 32, may be NULL */,
+                                 uint8_t* out_proofs_be /* count x m x 32, may be NULL */, uint64_t* bad_index /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

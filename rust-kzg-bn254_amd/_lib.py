@@ -258,6 +258,9 @@ PROTOTYPES = {
                                                   C.POINTER(i32)]),
     "kzg_verify_length_proof_batch_locate_bytes": (i32, [vp, u8p, u8p, u8p, u64p, sz, u64p, u64p, sz, u64p, u64p, sz, u8p, C.POINTER(sz), C.POINTER(sz),
                                                          C.POINTER(C.c_uint64), C.POINTER(i32)]),
+    "kzg_encode_cosets_batch_bytes": (i32, [vp, vp, u8p, sz, sz, i32, sz, sz, u8p, u8p, u8p, C.POINTER(C.c_uint64)]),
+    "kzg_disperse_blobs_bytes": (i32, [vp, vp, vp, vp, C.c_uint64, C.c_uint64, u8p, sz, sz, sz, sz, C.c_uint64, u8p, u8p, u8p, u8p, u8p,
+                                       C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

@@ -365,6 +365,63 @@ int32_t kzg_encode_cosets_batch(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly
     return multiproof_encode_batch(ctx, srs, polys_mont, eval_form != 0, plan, out_ys_mont, out_proofs_xy_mont, out_is_infinity);
 }
 
+// ---- the encoder in serialized form: bytes in, bytes out (multiproof.hip encode_groups with an EncodeBytesIo) -----------------------------------
+// the host checks of kzg_encode_cosets_batch_bytes in their order: rows 1 - 7 of kzg_encode_cosets_batch with this entry's pointers, then count x poly_len
+static int32_t encode_bytes_check(kzg_ctx* ctx, kzg_srs* srs, const uint8_t* blobs_be, size_t count, size_t poly_len, size_t n, size_t chunk_len, bool no_output) {
+    const bool bad_pointers = !ctx || !srs || !blobs_be || no_output;
+    const bool bad_srs = !bad_pointers && (srs->ctx != ctx || srs->lagrange_of != 0);
+    int32_t rc = encode_batch_check(bad_pointers, bad_srs, count, poly_len, n, chunk_len, srs ? srs->n : 0);
+    if (rc != KZG_OK) return rc;
+    if (count > ((size_t)1 << 28) / poly_len) return KZG_ERR_TOO_LARGE;                // the bad word holds (b poly_len + i) << 2
+    return KZG_OK;
+}
+// under ctx->mu: slot 0 idle (the commitments run on the slots), the plan with the context's budget, the run, the status of a refused value
+static int32_t encode_bytes_run(kzg_ctx* ctx, kzg_srs* srs, const char* who, size_t count, size_t poly_len, int32_t eval_form, size_t n, size_t chunk_len, EncodeBytesIo& io,
+                                uint64_t* bad_index) {
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (slot0_refused(ctx)) return KZG_ERR_INVALID_ARG;
+    const EncodeBatchPlan plan = encode_batch_plan(poly_len, n, chunk_len, count, io.ys_be != nullptr, io.proofs_be != nullptr, ctx->encode_group_bytes);
+    uint32_t bad_word = 0xFFFFFFFFu;
+    io.bad_word = &bad_word;
+    const int32_t rc = multiproof_encode_batch_bytes(ctx, srs, eval_form != 0, plan, io);
+    if (rc == KZG_ERR_DESERIALIZE) return coset_bytes_status(ctx, who, "value", bad_word, 1, bad_index);
+    return rc;
+}
+
+int32_t kzg_encode_cosets_batch_bytes(kzg_ctx* ctx, kzg_srs* srs, const uint8_t* blobs_be, size_t count, size_t poly_len, int32_t eval_form, size_t n, size_t chunk_len,
+                                      uint8_t* out_commitments_be, uint8_t* out_ys_be, uint8_t* out_proofs_be, uint64_t* bad_index) {
+    int32_t rc = encode_bytes_check(ctx, srs, blobs_be, count, poly_len, n, chunk_len, !out_commitments_be && !out_ys_be && !out_proofs_be);
+    if (rc != KZG_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    EncodeBytesIo io;
+    io.blobs_be = blobs_be; io.ys_be = out_ys_be; io.proofs_be = out_proofs_be; io.commitments_be = out_commitments_be;
+    return encode_bytes_run(ctx, srs, "kzg_encode_cosets_batch_bytes", count, poly_len, eval_form, n, chunk_len, io, bad_index);
+}
+
+int32_t kzg_disperse_blobs_bytes(kzg_ctx* ctx, kzg_srs* srs, const kzg_g2srs* g2_srs, const kzg_g2srs* g2_trailing, uint64_t trailing_first_power, uint64_t srs_order,
+                                 const uint8_t* blobs_be, size_t count, size_t poly_len, size_t n, size_t chunk_len, uint64_t claimed_len, uint8_t* out_commitments_be,
+                                 uint8_t* out_length_commitments_be, uint8_t* out_length_proofs_be, uint8_t* out_ys_be, uint8_t* out_proofs_be, uint64_t* bad_index) {
+    // the header is one unit: its three outputs are required; the chunks stay optional
+    const bool no_header = !g2_srs || !g2_trailing || !out_commitments_be || !out_length_commitments_be || !out_length_proofs_be;
+    int32_t rc = encode_bytes_check(ctx, srs, blobs_be, count, poly_len, n, chunk_len, no_header);
+    if (rc != KZG_OK) return rc;
+    if (g2_srs->ctx->device != ctx->device || g2_trailing->ctx->device != ctx->device) return KZG_ERR_INVALID_ARG;
+    // rows 3 onward of kzg_commit_with_length_proof_batch, the polynomial length being poly_len
+    const auto pow2 = [](uint64_t v) { return v != 0 && (v & (v - 1)) == 0; };
+    if (!pow2(srs_order) || !pow2(claimed_len)) return KZG_ERR_NOT_POWER_OF_TWO;
+    if (poly_len > claimed_len || claimed_len > srs_order) return KZG_ERR_INVALID_ARG;
+    if (srs_order - claimed_len < trailing_first_power) return KZG_ERR_SRS_CAPACITY_EXCEEDED;
+    const uint64_t off = srs_order - claimed_len - trailing_first_power;
+    if (off > g2_trailing->n || claimed_len > g2_trailing->n - off) return KZG_ERR_SRS_CAPACITY_EXCEEDED;
+    if (poly_len > g2_srs->n) return KZG_ERR_POLY_LENGTH;                                  // (poly_len <= the G1 SRS: row 6 above)
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    EncodeBytesIo io;
+    io.blobs_be = blobs_be; io.ys_be = out_ys_be; io.proofs_be = out_proofs_be; io.commitments_be = out_commitments_be;
+    io.g2_points[0] = g2_srs->d_points; io.g2_points[1] = g2_trailing->d_points + 8 * off;
+    io.length_commitments_be = out_length_commitments_be; io.length_proofs_be = out_length_proofs_be;
+    return encode_bytes_run(ctx, srs, "kzg_disperse_blobs_bytes", count, poly_len, 0, n, chunk_len, io, bad_index);
+}
+
 int32_t kzg_ctx_set_encode_group_bytes(kzg_ctx* ctx, size_t bytes) {
     if (!ctx) return KZG_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);

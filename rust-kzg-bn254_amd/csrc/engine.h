@@ -327,7 +327,9 @@ struct G1fftBatch { size_t batch = 1, in_batch = 0, out_batch = 0, tmp_batch = 0
 int32_t g1_fft_planes(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t n, int32_t* out, int32_t* tmp, bool inverse, bool scaled, const G1fftBatch& b = G1fftBatch());
 // the forward transform of an input that is the identity from point `nonzero` on (host_encode.h: the spread load of the radix-2 form)
 int32_t g1_fft_planes_padded(kzg_ctx* ctx, hipStream_t st, const int32_t* in, size_t in_stride, size_t nonzero, size_t n, int32_t* out, int32_t* tmp, const G1fftBatch& b = G1fftBatch());
-int32_t g1fft_planes_to_affine(kzg_ctx* ctx, hipStream_t st, const int32_t* planes, size_t n, uint4* d_out, bool wire, int32_t* scratch, size_t batch = 1, size_t planes_batch = 0);
+// compressed: 32 gnark-compressed bytes per point (g1_decode.h g1_compress_point; the identity is in the bytes) instead of 64
+int32_t g1fft_planes_to_affine(kzg_ctx* ctx, hipStream_t st, const int32_t* planes, size_t n, uint4* d_out, bool wire, int32_t* scratch, size_t batch = 1, size_t planes_batch = 0,
+                               bool compressed = false);
 // FK20 multi-proofs (multiproof.hip): the cached FFT_2m(S^(b)) of (srs, n, l), built if absent; the proofs of every coset of l points
 int32_t multiproof_cache(kzg_ctx* ctx, kzg_srs* srs, size_t n, size_t l, const uint4** out);
 int32_t multiproof_run(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, size_t n, bool eval_form, size_t l, uint64_t* out_xy, uint8_t* out_inf);
@@ -337,6 +339,22 @@ void multiproof_drop(kzg_srs* srs);
 int32_t multiproof_encode(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, bool eval_form, const EncodePlan& plan, uint64_t* out_ys, uint64_t* out_xy, uint8_t* out_inf);
 // kzg_encode_cosets_batch: plan.count blobs of that shape, group by group (host_encode.h EncodeBatchPlan); row b of every output is that of multiproof_encode on blob b
 int32_t multiproof_encode_batch(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* polys_mont, bool eval_form, const EncodeBatchPlan& plan, uint64_t* out_ys, uint64_t* out_xy, uint8_t* out_inf);
+// The SERIALIZED form of the same driver (kzg_encode_cosets_batch_bytes, kzg_disperse_blobs_bytes): the blobs are 32-byte big-endian integers, decoded on the
+// device where the group's first kernel loads them; values leave as 32 big-endian bytes each, proofs as 32 gnark-compressed bytes (no flag array).  Per group the
+// decoded coefficients also feed commit_batch_device (commitments_be: 32 B per blob) and, with g2_points set, g2_msm_batch_run over the two base sets (64 B per
+// blob each); those points are compressed on the host.  A value >= r ends the call at its group with KZG_ERR_DESERIALIZE and *bad_word = (the smallest bad
+// b poly_len + i of that group) << 2, before any output of that group is written (needs count x poly_len <= 2^28).  Needs slot 0 idle when commitments_be is set.
+struct EncodeBytesIo {
+    const uint8_t* blobs_be = nullptr;          // count x d x 32
+    uint8_t* ys_be = nullptr;                   // count x n x 32 or null (plan.values)
+    uint8_t* proofs_be = nullptr;               // count x m x 32 or null (plan.proofs)
+    uint8_t* commitments_be = nullptr;          // count x 32 or null
+    const uint4* g2_points[2] = {nullptr, nullptr};   // the disperser's call: the G2 SRS and the trailing powers from their offset (device format), d points each
+    uint8_t* length_commitments_be = nullptr;   // count x 64 each
+    uint8_t* length_proofs_be = nullptr;
+    uint32_t* bad_word = nullptr;               // may be null
+};
+int32_t multiproof_encode_batch_bytes(kzg_ctx* ctx, kzg_srs* srs, bool eval_form, const EncodeBatchPlan& plan, const EncodeBytesIo& io);
 // verification of coset proofs (multiverify.hip): d_out[t] = sum_i weights[i] w^(-ks[i] t) IFFT_l(ys_i)[t], enqueued on ctx->stream (d_ys is scratch when l > 1024)
 int32_t coset_interpolate_rlc_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, size_t count, size_t n, size_t l, uint4* d_out);
 // locating the bad groups of a batch (multilocate.hip; LocatePlan: host_locate.h).  Called under ctx->mu with the device set, count > 0.

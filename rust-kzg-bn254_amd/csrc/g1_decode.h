@@ -12,8 +12,11 @@
 // The exponentiation is the fixed 3-bit window of g2_decode.h (fq_sqrt_candidate: 249 squarings, at most 89 products), the byte
 // decode and the sign rule are that header's too.  G1 has cofactor 1: a point on the curve is in the group.
 //
-// Every function is KZG_HD: hipcc compiles it for the kernels of cosetbytes.hip, g++ with -DKZG_BOUND_CHECK for
-// tests/hostcheck/g1decodecheck.cpp.  Bounds per line as in g2_decode.h (class F: (-m, 2m); class O: (-0.0001m, 1.0001m)).
+// The way out is here too: g1_compress_point, the inverse of g1_decompress_point, which the affine conversion behind FK20 ends in when the
+// encoder writes bytes (g1fft.hip k_g1fft_to_affine<true>), and the scalar codec both ways (recover.hip, multiproof.hip).
+//
+// Every function is KZG_HD: hipcc compiles it for the kernels of cosetbytes.hip, recover.hip, multiproof.hip and g1fft.hip, g++ with -DKZG_BOUND_CHECK for
+// tests/hostcheck/g1decodecheck.cpp and tests/hostcheck/g1compresscheck.cpp.  Bounds per line as in g2_decode.h (class F: (-m, 2m); class O: (-0.0001m, 1.0001m)).
 #pragma once
 #include "g2_decode.h"
 
@@ -60,6 +63,41 @@ KZG_HD uint32_t g1_decompress_point(Fq& x, Fq& y, const uint32_t raw[8]) {
     fe_canon(x);
     fe_canon(y);
     return G1_DECODE_OK;
+}
+
+// The way out, the inverse of g1_decompress_point: an affine point in the internal form (x, y in class F; ignored for the identity) -> the
+// 32 gnark bytes as the 8 words a little-endian store of them takes.  x leaves canonical and big-endian, the flag is 0b10 / 0b11 by the
+// decoder's own rule (fq_plain_is_large on the canonical y), the identity is 0x40 followed by zeros: kzg_host::g1_encode_be (host_coset_bytes.h)
+// byte for byte.
+KZG_HD void g1_compress_point(uint32_t raw[8], const Fq& x, const Fq& y, bool identity) {
+    if (identity) {
+        raw[0] = 0x40u;                            // byte 0
+#pragma unroll
+        for (int k = 1; k < 8; ++k) raw[k] = 0u;
+        return;
+    }
+    Fq one_plain, c;
+    fe_set_zero(one_plain);
+    one_plain.l[0] = 1;
+    fe_mul(c, x, one_plain);                       // 2 * 1: internal -> plain integer, class F
+    fe_canon(c);                                   // [0, m)
+    uint32_t w32[8];
+    fe_pack(w32, c);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) raw[k] = __builtin_bswap32(w32[7 - k]);      // big-endian bytes 4k .. 4k + 3 = little-endian word 7 - k
+    bool zero;
+    const bool large = fq_plain_is_large(y, zero);                           // y in class F
+    raw[0] |= large ? 0xC0u : 0x80u;               // x < p < 2^254 leaves the top two bits of byte 0 free
+}
+// the same from a wire point (arkworks Montgomery words, canonical; the all-zero point is the identity, as the wire outputs write it)
+KZG_HD void g1_compress_wire_point(uint32_t raw[8], const uint32_t wire[16]) {
+    uint32_t any = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) any |= wire[k];
+    Fq x, y;
+    fe_from_wire(x, wire);                         // 5.3 * 1: class F
+    fe_from_wire(y, wire + 8);
+    g1_compress_point(raw, x, y, any == 0);
 }
 
 // the point in the device format of curve.h (x || y, canonical internal limbs packed to 2 x 8 words); the identity is 16 zero words, which

@@ -19,6 +19,7 @@
 #include "curve_pair.h"
 #include "curve_quad.h"
 #include "fe_invert.h"
+#include "g1_decode.h"   // g1_compress_point: the affine conversion's compressed output
 #include "naf.h"
 #include "glv.h"
 #include "glv_lanes.h"
@@ -510,7 +511,26 @@ k_g1fft_sum_partials(const int32_t* __restrict__ partial, uint32_t waves_per_out
 }
 
 // ---- XYZZ -> affine ------------------------------------------------------------------------------------------------------
+// BYTES: the point leaves as its 32 gnark-compressed bytes (g1_decode.h g1_compress_point; the identity 0x40 || zeros, no flag beside it),
+// two uint4 per point instead of four; `wire` is then unused
+template <bool BYTES>
 __device__ __forceinline__ void affine_emit(uint4* __restrict__ out, size_t i, const Xyzz& r, const Fq& inv_zz_zzz /* 1 / (ZZ ZZZ) */, bool wire) {
+    if (BYTES) {
+        uint32_t o[8];
+        Fq t, x, y;
+        fe_set_zero(x);
+        fe_set_zero(y);
+        if (!r.inf) {
+            fe_mul(t, inv_zz_zzz, r.zzz);          // 1 / ZZ
+            fe_mul(x, r.x, t);
+            fe_mul(t, inv_zz_zzz, r.zz);           // 1 / ZZZ
+            fe_mul(y, r.y, t);                     // x, y: class F
+        }
+        g1_compress_point(o, x, y, r.inf);
+        out[2 * i] = make_uint4(o[0], o[1], o[2], o[3]);
+        out[2 * i + 1] = make_uint4(o[4], o[5], o[6], o[7]);
+        return;
+    }
     uint32_t o[16];
     if (r.inf) {
 #pragma unroll
@@ -539,11 +559,12 @@ __device__ __forceinline__ void affine_emit(uint4* __restrict__ out, size_t i, c
 // lane t converts the points i = t, t + T, t + 2T, ... (T = number of lanes) with ONE inversion (Montgomery's trick): prefix
 // products of the denominators ZZ ZZZ go through `scratch` (9 limb planes, stride n).  per lane <= AFF_PER points.
 constexpr uint32_t AFF_PER = 4;        // 16 while the lane's inversion was a 381-product chain; with division steps (fe_invert.h) shorter chains on more lanes win: 84 -> ~45 us at 1 024 points
+template <bool BYTES = false>
 __global__ void __launch_bounds__(256)
 k_g1fft_to_affine(const int32_t* __restrict__ planes, uint32_t n, uint4* __restrict__ out, int wire, int32_t* __restrict__ scratch,
                   size_t planes_batch /* words between the plane sets of a batch (grid.y); its outputs and scratch rows are consecutive */) {
     planes += blockIdx.y * planes_batch;
-    out += (size_t)blockIdx.y * 4 * n;
+    out += (size_t)blockIdx.y * (BYTES ? 2 : 4) * n;
     scratch += (size_t)blockIdx.y * NL * n;
     const uint32_t T = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
@@ -571,7 +592,7 @@ k_g1fft_to_affine(const int32_t* __restrict__ planes, uint32_t n, uint4* __restr
         if (v.inf) fe_set_one(d); else fe_mul(d, v.zz, v.zzz);
         fe_mul(iv, rinv, pre);
         fe_mul(rinv, rinv, d);
-        affine_emit(out, i, v, iv, wire != 0);
+        affine_emit<BYTES>(out, i, v, iv, wire != 0);
     }
 }
 
@@ -685,10 +706,13 @@ k_g1fft_spread_planes(const int32_t* __restrict__ src, size_t src_stride, uint32
 // n XYZZ planes (stride n) -> n affine points (wire, or the device format of curve.h; identity = zeros), the batched conversion of
 // g1_ifft_device; scratch: n x NL words.  Enqueued on st.
 // batch plane sets planes_batch words apart (one per grid.y): point i of set b goes to d_out[b n + i], scratch: batch x n x NL words.
-int32_t g1fft_planes_to_affine(kzg_ctx* ctx, hipStream_t st, const int32_t* planes, size_t n, uint4* d_out, bool wire, int32_t* scratch, size_t batch, size_t planes_batch) {
+// compressed: the points leave as 32 gnark-compressed bytes each (point i of set b at d_out + 2 (b n + i)); `wire` is then unused.
+int32_t g1fft_planes_to_affine(kzg_ctx* ctx, hipStream_t st, const int32_t* planes, size_t n, uint4* d_out, bool wire, int32_t* scratch, size_t batch, size_t planes_batch,
+                               bool compressed) {
     const size_t lanes = std::max<size_t>(1, (n + AFF_PER - 1) / AFF_PER);
     const unsigned blocks = (unsigned)std::min<size_t>((lanes + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_g1fft_to_affine, dim3(blocks, (unsigned)batch), dim3(256), 0, st, planes, (uint32_t)n, d_out, wire ? 1 : 0, scratch, planes_batch);
+    if (compressed) hipLaunchKernelGGL(k_g1fft_to_affine<true>, dim3(blocks, (unsigned)batch), dim3(256), 0, st, planes, (uint32_t)n, d_out, 0, scratch, planes_batch);
+    else hipLaunchKernelGGL(k_g1fft_to_affine<false>, dim3(blocks, (unsigned)batch), dim3(256), 0, st, planes, (uint32_t)n, d_out, wire ? 1 : 0, scratch, planes_batch);
     KZG_HIP_TRY(ctx, hipGetLastError());
     return KZG_OK;
 }
@@ -791,7 +815,7 @@ static int32_t g1fft_t3_tables(kzg_ctx* ctx, const kzg_srs* srs, const uint4* d_
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_g1fft_t3_planes, dim3((total + 255) / 256), dim3(256), 0, st, d_bits, (uint32_t)srs->n, pts, total, ctx->poly[0].c.as<int32_t>());
             const size_t lanes = (total + AFF_PER - 1) / AFF_PER;
-            hipLaunchKernelGGL(k_g1fft_to_affine, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, ctx->poly[0].c.as<int32_t>(), total, t3, 0, ctx->poly[0].a.as<int32_t>(), (size_t)0);
+            hipLaunchKernelGGL(k_g1fft_to_affine<false>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, ctx->poly[0].c.as<int32_t>(), total, t3, 0, ctx->poly[0].a.as<int32_t>(), (size_t)0);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(st);

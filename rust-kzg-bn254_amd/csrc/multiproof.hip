@@ -38,11 +38,14 @@
 // Measured figures: README.md ("multi-proofs", "the encoder"), profiles/multiproof.md, profiles/encode.md and profiles/encode_batch.md.
 #include "engine.h"
 #include "glv.h"
+#include "g1_decode.h"          // the steps of fr_decode_be_to_wire on load, fr_encode_wire_to_be on store
+#include "host_header_bytes.h"   // g1_encode_be, g2_encode_be: the few header points of a group are compressed on the host
 
 #include <algorithm>
 #include <map>
 #include <mutex>
 #include <utility>
+#include <vector>
 
 namespace kzg {
 
@@ -240,11 +243,19 @@ static int32_t fk20_h(kzg_ctx* ctx, hipStream_t st, const uint4* shat, const uin
 
 // 5. m points of planes Y -> wire affine points (identity = zeros) and identity flags in `work` (m x 64 B | m x NL words | m flags), copied out.
 // B blobs (plane sets Y_batch words apart): B m points, `work` laid out for B m, one download per output array.
-static int32_t fk20_emit(kzg_ctx* ctx, hipStream_t st, const int32_t* Y, size_t m, uint8_t* work, uint64_t* out_xy, uint8_t* out_inf, size_t B = 1, size_t Y_batch = 0) {
+// compressed: out_xy receives 32 gnark-compressed bytes per point (the first half of the same region of `work`), the identity is in the bytes: no flags.
+static int32_t fk20_emit(kzg_ctx* ctx, hipStream_t st, const int32_t* Y, size_t m, uint8_t* work, void* out_xy, uint8_t* out_inf, size_t B = 1, size_t Y_batch = 0,
+                         bool compressed = false) {
     const size_t pts = B * m;
     uint4* d_aff = reinterpret_cast<uint4*>(work);                               // pts x 64 B
     int32_t* aff_scratch = reinterpret_cast<int32_t*>(work + pts * 64);          // pts x NL words
     uint8_t* d_inf = work + pts * (64 + NL * 4);
+    if (compressed) {
+        int32_t rc = g1fft_planes_to_affine(ctx, st, Y, m, d_aff, true, aff_scratch, B, Y_batch, true);
+        if (rc != KZG_OK) return rc;
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(out_xy, d_aff, pts * 32, hipMemcpyDeviceToHost, st));
+        return KZG_OK;
+    }
     int32_t rc = g1fft_planes_to_affine(ctx, st, Y, m, d_aff, true, aff_scratch, B, Y_batch);
     if (rc != KZG_OK) return rc;
     hipLaunchKernelGGL(k_fk20_inf_flags, dim3(grid_of(m), (unsigned)B), dim3(256), 0, st, Y, (uint32_t)m, d_inf, Y_batch);
@@ -289,7 +300,9 @@ int32_t multiproof_run(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, si
 }
 
 // ---- the encoder: cosets of values and their proofs for d coefficients on a domain of n = r d points --------------------------------
-// ys[k l + j] = evals[k + j m]: the coset-major order of KZG.cosets (wire Fr, 32 B each)
+// ys[k l + j] = evals[k + j m]: the coset-major order of KZG.cosets (wire Fr, 32 B each).  BE: the values (canonical wire words: the
+// transform's last pass writes them so) leave as 32 big-endian bytes each, by the steps of fr_encode_wire_to_be, as k_recover_scale<2, true> does.
+template <bool BE = false>
 __global__ void __launch_bounds__(256)
 k_encode_gather_cosets(const uint4* __restrict__ evals, uint32_t n, int log_l, int log_m, uint4* __restrict__ ys) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -298,28 +311,126 @@ k_encode_gather_cosets(const uint4* __restrict__ evals, uint32_t n, int log_l, i
     ys += 2 * (size_t)blockIdx.y * n;
     const uint32_t k = i >> log_l, j = i & ((1u << log_l) - 1);
     const size_t s = (size_t)k + ((size_t)j << log_m);
+    if (BE) {
+        const uint4 q0 = evals[2 * s], q1 = evals[2 * s + 1];
+        const uint32_t w[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+        uint32_t o[8];
+        fr_encode_wire_to_be(o, w);                                // canonical words < m, times 32
+        ys[2 * (size_t)i] = make_uint4(o[0], o[1], o[2], o[3]);
+        ys[2 * (size_t)i + 1] = make_uint4(o[4], o[5], o[6], o[7]);
+        return;
+    }
     ys[2 * (size_t)i] = evals[2 * s];
     ys[2 * (size_t)i + 1] = evals[2 * s + 1];
 }
 
 static_assert(ENCODE_LIMBS == NL && G1FFT_POINT_BYTES == 4 * NL * 4, "host_encode.h sizes the workspaces from these");
 
+// ---- the encoder on a batch of blobs ----------------------------------------------------------------------------------------------------
+// f[b fs + i] = src[b d + i] for i < d, zero for d <= i < fs: the compact rows of a group (uploaded, or inverse-NTT'd in place) into the
+// rows the value transform extends (blob grid.y)
+// BE: the compact rows are the blobs' bytes, 32-byte big-endian integers, decoded on load by the steps of fr_decode_be_to_wire (a byte
+// swap, a strict compare with r, one product); one >= r reports atomicMin(bad, (first_value + b d + i) << 2) on the call's one word (the
+// call then ends before anything computed from it leaves).  decoded != nullptr: the wire words also go back to the compact row (the
+// lane's own element), where the commitments read them.
+template <bool BE = false>
+__global__ void __launch_bounds__(256)
+k_encode_place_coeffs(const uint4* __restrict__ src, uint32_t d, uint32_t fs, uint4* __restrict__ f, uint32_t first_value, uint32_t* __restrict__ bad,
+                      uint4* __restrict__ decoded) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= fs) return;
+    uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+    if (i < d) {
+        const size_t s = (size_t)blockIdx.y * d + i;
+        lo = src[2 * s]; hi = src[2 * s + 1];
+        if (BE) {
+            const uint32_t raw[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+            uint32_t w[8];
+            if (!fr_decode_be_to_wire(w, raw)) atomicMin(bad, (first_value + (uint32_t)s) << 2);      // < 2^28 values in a call
+            lo = make_uint4(w[0], w[1], w[2], w[3]); hi = make_uint4(w[4], w[5], w[6], w[7]);
+            if (decoded) { decoded[2 * s] = lo; decoded[2 * s + 1] = hi; }
+        }
+    }
+    const size_t o = (size_t)blockIdx.y * fs + i;
+    f[2 * o] = lo;
+    f[2 * o + 1] = hi;
+}
+// the same decode in place over `total` staged values (compact rows that the next kernel reads as words: f_stride = d, or an inverse
+// transform comes first), one lane per value
+__global__ void __launch_bounds__(256)
+k_encode_decode_be(uint4* __restrict__ rows, uint32_t total, uint32_t first_value, uint32_t* __restrict__ bad) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const uint4 q0 = rows[2 * (size_t)i], q1 = rows[2 * (size_t)i + 1];
+    const uint32_t raw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+    uint32_t w[8];
+    if (!fr_decode_be_to_wire(w, raw)) atomicMin(bad, (first_value + i) << 2);
+    rows[2 * (size_t)i] = make_uint4(w[0], w[1], w[2], w[3]);
+    rows[2 * (size_t)i + 1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+
+// ---- the serialized form (kzg_encode_cosets_batch_bytes, kzg_disperse_blobs_bytes) ---------------------------------------------------------
+// The drivers below take an EncodeBytesIo (engine.h) or none.  With one: the blobs go up as their bytes, into the buffer the words would go to (32 B
+// a value either way), and are decoded where the group's first kernel loads them -- k_encode_place_coeffs<true> for coefficient-form blobs whose rows
+// are placed (f_stride > d), k_encode_decode_be in place otherwise (f_stride = d, the single blob, or an inverse transform comes first); the value rows
+// leave through k_encode_gather_cosets<true>, the proofs through the compressed form of the affine conversion.  The call's bad word stands behind the
+// coefficient rows in mp[0].  Once a group's decoded coefficients are complete, encode_bytes_front reads the bad word (a refused value ends the call
+// there: nothing computed from it leaves) and commits the rows: commit_batch_device for the commitments, g2_msm_batch_run over both G2 base sets for the
+// headers.  Those run on the slots' streams and return wire points (8 / 16 words a blob), which the host compresses: a blob has one G1 and two G2 elements.
+// coeffs: g compact rows of d wire values, enqueued on st; b0: the first blob of the group.
+static int32_t encode_bytes_front(kzg_ctx* ctx, kzg_srs* srs, hipStream_t st, const EncodeBytesIo& io, const uint32_t* d_bad, const uint4* coeffs, size_t d, size_t b0, size_t g) {
+    uint32_t bad = 0xFFFFFFFFu;
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+    KZG_HIP_TRY(ctx, hipStreamSynchronize(st));                     // (the G1 and G2 launches run on the slots' streams: the rows are complete)
+    if (bad != 0xFFFFFFFFu) {
+        if (io.bad_word) *io.bad_word = bad;
+        return KZG_ERR_DESERIALIZE;
+    }
+    if (!io.commitments_be) return KZG_OK;
+    std::vector<uint64_t> xy(g * 8);
+    int32_t rc = commit_batch_device(ctx, srs, coeffs, d, g, xy.data(), nullptr);
+    if (rc != KZG_OK) return rc;
+    bool ok = true;
+    for (size_t i = 0; i < g; ++i) ok = kzg_host::g1_encode_be(xy.data() + 8 * i, io.commitments_be + 32 * (b0 + i)) && ok;
+    if (io.g2_points[0]) {
+        std::vector<uint64_t> c2(g * 16), p2(g * 16);
+        uint64_t* outs[2] = {c2.data(), p2.data()};
+        rc = g2_msm_batch_run(ctx, io.g2_points, 2, coeffs, d, g, outs, nullptr);
+        if (rc != KZG_OK) return rc;
+        for (size_t i = 0; i < g; ++i) {
+            ok = kzg_host::g2_encode_be(c2.data() + 16 * i, io.length_commitments_be + 64 * (b0 + i)) && ok;
+            ok = kzg_host::g2_encode_be(p2.data() + 16 * i, io.length_proofs_be + 64 * (b0 + i)) && ok;
+        }
+    }
+    if (!ok) { ctx->last_error = "a commitment of the encoder left the device with a coordinate not below p"; return KZG_ERR_DEVICE; }
+    return KZG_OK;
+}
+
 // called under ctx->mu with the arguments checked and planned (capi_srs.hip kzg_encode_cosets).  The FK20 steps 1-4 see d only (the
 // cache entry is (d, l)); step 5 is the m-point transform of h zero-padded (g1_fft_planes_padded); the values are one n-point NTT of the
-// zero-extended coefficients.
-int32_t multiproof_encode(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, bool eval_form, const EncodePlan& plan, uint64_t* out_ys, uint64_t* out_xy, uint8_t* out_inf) {
+// zero-extended coefficients.  io: the serialized form, `src` then the bytes of blob `blob` of the call and the outputs that blob's rows.
+static int32_t encode_one(kzg_ctx* ctx, kzg_srs* srs, const void* src, bool eval_form, const EncodePlan& plan, void* out_ys, void* out_xy, uint8_t* out_inf,
+                          const EncodeBytesIo* io, size_t blob) {
     RoctxRange range("kzg:encode_cosets");
     const size_t d = plan.d, n = plan.n, l = plan.l, m = plan.m, mp = plan.mp, M = plan.M;
     const uint4* shat = nullptr;
     int32_t rc = KZG_OK;
     if (plan.proofs) { rc = multiproof_cache(ctx, srs, d, l, &shat); if (rc != KZG_OK) return rc; }
     hipStream_t st = ctx->stream;
-    for (int i = 0; i < 6; ++i) KZG_HIP_TRY(ctx, ctx->mp[i].reserve(plan.bytes[i]));
+    KZG_HIP_TRY(ctx, ctx->mp[0].reserve(plan.bytes[0] + (io ? 64 : 0)));          // + the bad word of the serialized form
+    for (int i = 1; i < 6; ++i) KZG_HIP_TRY(ctx, ctx->mp[i].reserve(plan.bytes[i]));
     uint4* f = ctx->mp[0].as<uint4>();
     uint4* F = ctx->mp[1].as<uint4>();
     // the d coefficients (eval form: inverse NTT of size d on the device)
-    KZG_HIP_TRY(ctx, hipMemcpyAsync(f, poly_mont, d * 32, hipMemcpyHostToDevice, st));
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(f, src, d * 32, hipMemcpyHostToDevice, st));
+    uint32_t* d_bad = reinterpret_cast<uint32_t*>(ctx->mp[0].as<uint8_t>() + plan.bytes[0]);
+    if (io) {
+        KZG_HIP_TRY(ctx, hipMemsetAsync(d_bad, 0xFF, 4, st));
+        hipLaunchKernelGGL(k_encode_decode_be, dim3(grid_of(d)), dim3(256), 0, st, f, (uint32_t)d, (uint32_t)(blob * d), d_bad);
+        KZG_HIP_TRY(ctx, hipGetLastError());
+    }
     if (eval_form) { rc = ntt_run(ctx, f, d, true, st, &ctx->mp_ntt); if (rc != KZG_OK) return rc; }
+    if (io) { rc = encode_bytes_front(ctx, srs, st, *io, d_bad, f, d, blob, 1); if (rc != KZG_OK) return rc; }
     if (plan.proofs) {
         const Fk20Sets sets = {{ctx->mp[2].as<int32_t>(), ctx->mp[3].as<int32_t>(), ctx->mp[4].as<int32_t>()}, {0, 0, 0}};
         int32_t* P2 = sets.P[2];
@@ -330,7 +441,7 @@ int32_t multiproof_encode(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont,
         // pi = DFT_m(h_0 .. h_{m'-1}, 0 x (m - m')): the slice is read in place (offset m' - 1, stride 2m'), the zeros are never read
         rc = g1_fft_planes_padded(ctx, st, X + (mp - 1), M, mp, m, Y, P2);
         if (rc != KZG_OK) return rc;
-        rc = fk20_emit(ctx, st, Y, m, ctx->mp[5].as<uint8_t>(), out_xy, out_inf);
+        rc = fk20_emit(ctx, st, Y, m, ctx->mp[5].as<uint8_t>(), out_xy, out_inf, 1, 0, io != nullptr);
         if (rc != KZG_OK) return rc;
     }
     if (plan.values) {
@@ -338,40 +449,33 @@ int32_t multiproof_encode(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont,
         if (n > d) KZG_HIP_TRY(ctx, hipMemsetAsync(f + 2 * d, 0, (n - d) * 32, st));
         rc = ntt_run(ctx, f, n, false, st, &ctx->mp_ntt);
         if (rc != KZG_OK) return rc;
-        hipLaunchKernelGGL(k_encode_gather_cosets, dim3(grid_of(n)), dim3(256), 0, st, f, (uint32_t)n, plan.log_l, plan.log_m, F);
+        if (io) hipLaunchKernelGGL(k_encode_gather_cosets<true>, dim3(grid_of(n)), dim3(256), 0, st, f, (uint32_t)n, plan.log_l, plan.log_m, F);
+        else hipLaunchKernelGGL(k_encode_gather_cosets<false>, dim3(grid_of(n)), dim3(256), 0, st, f, (uint32_t)n, plan.log_l, plan.log_m, F);
         KZG_HIP_TRY(ctx, hipGetLastError());
         KZG_HIP_TRY(ctx, hipMemcpyAsync(out_ys, F, n * 32, hipMemcpyDeviceToHost, st));
     }
     KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
     return KZG_OK;
 }
-
-// ---- the encoder on a batch of blobs ----------------------------------------------------------------------------------------------------
-// f[b fs + i] = src[b d + i] for i < d, zero for d <= i < fs: the compact rows of a group (uploaded, or inverse-NTT'd in place) into the
-// rows the value transform extends (blob grid.y)
-__global__ void __launch_bounds__(256)
-k_encode_place_coeffs(const uint4* __restrict__ src, uint32_t d, uint32_t fs, uint4* __restrict__ f) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= fs) return;
-    uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
-    if (i < d) { const size_t s = (size_t)blockIdx.y * d + i; lo = src[2 * s]; hi = src[2 * s + 1]; }
-    const size_t o = (size_t)blockIdx.y * fs + i;
-    f[2 * o] = lo;
-    f[2 * o + 1] = hi;
+int32_t multiproof_encode(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly_mont, bool eval_form, const EncodePlan& plan, uint64_t* out_ys, uint64_t* out_xy, uint8_t* out_inf) {
+    return encode_one(ctx, srs, poly_mont, eval_form, plan, out_ys, out_xy, out_inf, nullptr, 0);
 }
 
 // called under ctx->mu with the arguments checked and planned (capi_srs.hip kzg_encode_cosets_batch).  Groups of bp.group blobs, one
 // after the other on the context's stream with a synchronisation behind each (the workspace is reused; overlapping a group's copies
-// with the next one's kernels was not written).  A group of one is multiproof_encode itself.  Inside a group of g blobs the buffers
+// with the next one's kernels was not written).  A group of one is encode_one itself.  Inside a group of g blobs the buffers
 // are: mp[0] g rows of f_stride coefficients; mp[1] the compact upload (when f_stride > d), then g x l rows of 2m' (FK20), then g rows
 // of n coset-major values; mp[2 .. 4] g plane sets each, set_points[i] points apart; mp[5] g m affine points | scratch | flags.
-int32_t multiproof_encode_batch(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* polys_mont, bool eval_form, const EncodeBatchPlan& bp, uint64_t* out_ys, uint64_t* out_xy, uint8_t* out_inf) {
+// io: the serialized form.  polys, out_ys and out_xy are then its blobs_be, ys_be and proofs_be: 32 B a value either way, 32 B a proof instead of 64.
+static int32_t encode_groups(kzg_ctx* ctx, kzg_srs* srs, const uint8_t* polys, bool eval_form, const EncodeBatchPlan& bp, uint8_t* out_ys, uint8_t* out_xy, uint8_t* out_inf,
+                             const EncodeBytesIo* io) {
     const EncodePlan& plan = bp.one;
     const size_t d = plan.d, n = plan.n, l = plan.l, m = plan.m, mp = plan.mp, M = plan.M, fs = bp.f_stride;
+    const size_t proof_bytes = io ? 32 : 64;
     if (bp.group == 1) {
         for (size_t b = 0; b < bp.count; ++b) {
-            int32_t rc = multiproof_encode(ctx, srs, polys_mont + b * d * 4, eval_form, plan, out_ys ? out_ys + b * n * 4 : nullptr,
-                                           out_xy ? out_xy + b * m * 8 : nullptr, out_xy ? out_inf + b * m : nullptr);
+            int32_t rc = encode_one(ctx, srs, polys + b * d * 32, eval_form, plan, out_ys ? out_ys + b * n * 32 : nullptr,
+                                    out_xy ? out_xy + b * m * proof_bytes : nullptr, out_xy && out_inf ? out_inf + b * m : nullptr, io, b);
             if (rc != KZG_OK) return rc;
         }
         return KZG_OK;
@@ -381,20 +485,35 @@ int32_t multiproof_encode_batch(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly
     int32_t rc = KZG_OK;
     if (plan.proofs) { rc = multiproof_cache(ctx, srs, d, l, &shat); if (rc != KZG_OK) return rc; }
     hipStream_t st = ctx->stream;
-    for (int i = 0; i < 6; ++i) KZG_HIP_TRY(ctx, ctx->mp[i].reserve(bp.bytes[i]));
+    KZG_HIP_TRY(ctx, ctx->mp[0].reserve(bp.bytes[0] + (io ? 64 : 0)));            // + the bad word of the serialized form
+    for (int i = 1; i < 6; ++i) KZG_HIP_TRY(ctx, ctx->mp[i].reserve(bp.bytes[i]));
     uint4* f = ctx->mp[0].as<uint4>();
     uint4* F = ctx->mp[1].as<uint4>();
+    uint32_t* d_bad = reinterpret_cast<uint32_t*>(ctx->mp[0].as<uint8_t>() + bp.bytes[0]);
+    if (io) KZG_HIP_TRY(ctx, hipMemsetAsync(d_bad, 0xFF, 4, st));
     Fk20Sets sets;
     for (int i = 0; i < 3; ++i) { sets.P[i] = ctx->mp[2 + i].as<int32_t>(); sets.P_batch[i] = bp.set_points[i] * 4 * NL; }
     for (size_t b0 = 0; b0 < bp.count; b0 += bp.group) {
         const size_t g = std::min(bp.group, bp.count - b0);           // (the last group may be smaller: its transforms are planned for g)
         const unsigned gy = (unsigned)g;
-        const uint64_t* src = polys_mont + b0 * d * 4;
+        const uint8_t* src = polys + b0 * d * 32;
         // the coefficients of the group: one upload; eval form: g inverse NTTs of d points, one launch per pass
         uint4* up = fs == d ? f : F;
         KZG_HIP_TRY(ctx, hipMemcpyAsync(up, src, g * d * 32, hipMemcpyHostToDevice, st));
+        const bool decode_on_place = io && fs != d && !eval_form;     // else the staged bytes are decoded in place: their next reader takes words
+        if (io && !decode_on_place) hipLaunchKernelGGL(k_encode_decode_be, dim3(grid_of(g * d)), dim3(256), 0, st, up, (uint32_t)(g * d), (uint32_t)(b0 * d), d_bad);
         if (eval_form) { rc = ntt_run_batch(ctx, up, d, g, true, st, &ctx->mp_ntt); if (rc != KZG_OK) return rc; }
-        if (fs != d) hipLaunchKernelGGL(k_encode_place_coeffs, dim3(grid_of(fs), gy), dim3(256), 0, st, up, (uint32_t)d, (uint32_t)fs, f);
+        if (decode_on_place)
+            hipLaunchKernelGGL(k_encode_place_coeffs<true>, dim3(grid_of(fs), gy), dim3(256), 0, st, up, (uint32_t)d, (uint32_t)fs, f, (uint32_t)(b0 * d), d_bad,
+                               io->commitments_be ? up : static_cast<uint4*>(nullptr));
+        else if (fs != d)
+            hipLaunchKernelGGL(k_encode_place_coeffs<false>, dim3(grid_of(fs), gy), dim3(256), 0, st, up, (uint32_t)d, (uint32_t)fs, f, 0u, static_cast<uint32_t*>(nullptr), static_cast<uint4*>(nullptr));
+        if (io) {
+            KZG_HIP_TRY(ctx, hipGetLastError());
+            // the compact rows (where f_stride > d they live in the buffer FK20 overwrites: these reads come first)
+            rc = encode_bytes_front(ctx, srs, st, *io, d_bad, up, d, b0, g);
+            if (rc != KZG_OK) return rc;
+        }
         if (plan.proofs) {
             int xi = 0, yi = 0;
             rc = fk20_h(ctx, st, shat, f, F, d, l, plan.lincomb, sets, &xi, &yi, g, fs);
@@ -403,19 +522,26 @@ int32_t multiproof_encode_batch(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* poly
             gb.batch = g; gb.in_batch = sets.P_batch[xi]; gb.out_batch = sets.P_batch[yi]; gb.tmp_batch = sets.P_batch[2];
             rc = g1_fft_planes_padded(ctx, st, sets.P[xi] + (mp - 1), M, mp, m, sets.P[yi], sets.P[2], gb);
             if (rc != KZG_OK) return rc;
-            rc = fk20_emit(ctx, st, sets.P[yi], m, ctx->mp[5].as<uint8_t>(), out_xy + b0 * m * 8, out_inf + b0 * m, g, sets.P_batch[yi]);
+            rc = fk20_emit(ctx, st, sets.P[yi], m, ctx->mp[5].as<uint8_t>(), out_xy + b0 * m * proof_bytes, out_inf ? out_inf + b0 * m : nullptr, g, sets.P_batch[yi], io != nullptr);
             if (rc != KZG_OK) return rc;
         }
         if (plan.values) {
             rc = ntt_run_batch(ctx, f, n, g, false, st, &ctx->mp_ntt);      // rows of n: the coefficients zero-extended (placed above, or n = d)
             if (rc != KZG_OK) return rc;
-            hipLaunchKernelGGL(k_encode_gather_cosets, dim3(grid_of(n), gy), dim3(256), 0, st, f, (uint32_t)n, plan.log_l, plan.log_m, F);
+            if (io) hipLaunchKernelGGL(k_encode_gather_cosets<true>, dim3(grid_of(n), gy), dim3(256), 0, st, f, (uint32_t)n, plan.log_l, plan.log_m, F);
+            else hipLaunchKernelGGL(k_encode_gather_cosets<false>, dim3(grid_of(n), gy), dim3(256), 0, st, f, (uint32_t)n, plan.log_l, plan.log_m, F);
             KZG_HIP_TRY(ctx, hipGetLastError());
-            KZG_HIP_TRY(ctx, hipMemcpyAsync(out_ys + b0 * n * 4, F, g * n * 32, hipMemcpyDeviceToHost, st));
+            KZG_HIP_TRY(ctx, hipMemcpyAsync(out_ys + b0 * n * 32, F, g * n * 32, hipMemcpyDeviceToHost, st));
         }
         KZG_HIP_TRY(ctx, hipStreamSynchronize(st));
     }
     return KZG_OK;
+}
+int32_t multiproof_encode_batch(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* polys_mont, bool eval_form, const EncodeBatchPlan& bp, uint64_t* out_ys, uint64_t* out_xy, uint8_t* out_inf) {
+    return encode_groups(ctx, srs, reinterpret_cast<const uint8_t*>(polys_mont), eval_form, bp, reinterpret_cast<uint8_t*>(out_ys), reinterpret_cast<uint8_t*>(out_xy), out_inf, nullptr);
+}
+int32_t multiproof_encode_batch_bytes(kzg_ctx* ctx, kzg_srs* srs, bool eval_form, const EncodeBatchPlan& bp, const EncodeBytesIo& io) {
+    return encode_groups(ctx, srs, io.blobs_be, eval_form, bp, io.ys_be, io.proofs_be, nullptr, &io);
 }
 
 }  // namespace kzg

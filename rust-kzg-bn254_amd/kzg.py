@@ -560,6 +560,118 @@ class KZG:
         return verifier.encode_coset_items(ys, proofs)
 
     @staticmethod
+    def _blob_rows_be(name, blobs):
+        """(uint8 buffer, B, d) of blobs of 32-byte big-endian field elements: one `bytes` / `Blob` (B = 1), a list of them of one
+        length, or a (B, d * 32) uint8 array."""
+        if isinstance(blobs, np.ndarray):
+            if blobs.dtype != np.uint8 or blobs.ndim != 2:
+                raise GenericError("%s takes a (B, d * 32) uint8 array" % name)
+            buf, count = np.ascontiguousarray(blobs).reshape(-1), int(blobs.shape[0])
+            row = int(blobs.shape[1])
+        else:
+            if isinstance(blobs, (bytes, bytearray, memoryview)) or hasattr(blobs, "data"):
+                blobs = [blobs]
+            rows = [bytes(b.data()) if hasattr(b, "data") else bytes(b) for b in blobs]
+            count = len(rows)
+            row = len(rows[0]) if rows else 0
+            if any(len(r) != row for r in rows):
+                raise GenericError("%s needs blobs of one length" % name)
+            buf = np.frombuffer(b"".join(rows), dtype=np.uint8)
+        if count <= 0:
+            raise GenericError("%s needs at least one blob" % name)
+        if row == 0 or row % 32 != 0:
+            raise InvalidInputLength()
+        return buf, count, row // 32
+
+    @staticmethod
+    def _encode_shape_checks(d, n, chunk_len, srs):
+        if d <= 0 or (d & (d - 1)) != 0 or n <= 0 or (n & (n - 1)) != 0:
+            raise FFTError("length provided is not a power of 2")
+        if n > 1 << 24:
+            raise FFTError("Could not perform IFFT due to domain consturction error")
+        if d < 2:
+            raise GenericError("encode_cosets needs a polynomial of at least 2 elements")
+        if d > n:
+            raise GenericError("the domain is shorter than the polynomial")
+        if chunk_len <= 0 or (chunk_len & (chunk_len - 1)) != 0:
+            raise GenericError("chunk length is not a power of 2")
+        if chunk_len > d // 2:
+            raise GenericError("chunk length exceeds half the polynomial length")
+        if d > len(srs):
+            raise SrsCapacityExceeded(d, len(srs))
+
+    @staticmethod
+    def _raise_encode_bytes_status(ctx, rc, bad, d, srs):
+        if rc == _lib.ERR_DESERIALIZE:
+            raise SerializationError("blob %d, element %d: not a canonical field element (an integer not below r)" % (bad // d, bad % d))
+        if rc == _lib.ERR_NOT_POWER_OF_TWO:
+            raise FFTError("length provided is not a power of 2")
+        if rc == _lib.ERR_DOMAIN:
+            raise FFTError("Could not perform IFFT due to domain consturction error")
+        if rc == _lib.ERR_SRS_CAPACITY_EXCEEDED:
+            raise SrsCapacityExceeded(d, len(srs))
+        ctx.check_device(rc)
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+
+    def encode_cosets_batch_bytes(self, blobs, srs, n: int, chunk_len: int = 1, eval_form: bool = False, commitments: bool = True, values: bool = True,
+                                  proofs: bool = True):
+        """`encode_cosets_batch` from blobs to the bytes a disperser sends, the codec inside the call (`kzg_encode_cosets_batch_bytes`).
+        `blobs`: `bytes`, `Blob` objects (a list of one length, or one) or a (B, d * 32) uint8 array of 32-byte big-endian field elements,
+        coefficients or (eval_form=True) evaluations.  Returns (commitments_be, ys_be, proofs_be): B x 32, B x n x 32 and B x m x 32 bytes
+        (None where the keyword is False): byte for byte `verifier.encode_coset_items` of `encode_cosets_batch` on the decoded blobs, and
+        the compressed commitments of their coefficients.  An element not below r raises SerializationError naming the blob and the
+        element; everything else as `encode_cosets_batch`."""
+        buf, count, d = self._blob_rows_be("encode_cosets_batch_bytes", blobs)
+        n, chunk_len = int(n), int(chunk_len)
+        if not commitments and not values and not proofs:
+            raise GenericError("encode_cosets needs commitments, values, proofs or any of them")
+        self._encode_shape_checks(d, n, chunk_len, srs)
+        ctx = self._ctx()
+        m = n // chunk_len
+        cm = np.zeros(count * 32, dtype=np.uint8) if commitments else None
+        ys = np.zeros(count * n * 32, dtype=np.uint8) if values else None
+        pr = np.zeros(count * m * 32, dtype=np.uint8) if proofs else None
+        p8 = lambda a: a.ctypes.data_as(_lib.u8p) if a is not None else None
+        bad = C.c_uint64(0)
+        rc = _lib.load().kzg_encode_cosets_batch_bytes(ctx.handle, srs.handle, p8(buf), count, d, 1 if eval_form else 0, n, chunk_len, p8(cm), p8(ys), p8(pr),
+                                                       C.byref(bad))
+        self._raise_encode_bytes_status(ctx, rc, bad.value, d, srs)
+        return tuple(a.tobytes() if a is not None else None for a in (cm, ys, pr))
+
+    def disperse_blobs_bytes(self, blobs, srs, g2_srs, g2_trailing, srs_order: int, claimed_len: int, n: int, chunk_len: int = 1, values: bool = True,
+                             proofs: bool = True):
+        """The disperser's call (`kzg_disperse_blobs_bytes`): from blobs of 32-byte big-endian coefficients (as `encode_cosets_batch_bytes`
+        takes them) to everything that leaves for the network.  Returns (commitments_be, length_commitments_be, length_proofs_be, ys_be,
+        proofs_be): the three header arrays are byte for byte `commit_with_length_proof_batch_be` on the decoded blobs (32 / 64 / 64
+        bytes per blob), the chunks those of `encode_cosets_batch_bytes` (None where the keyword is False).  One upload, as bytes; the
+        decoded coefficients feed the encoder, the G1 commitments and the G2 MSMs.  Errors as `encode_cosets_batch_bytes` and
+        `commit_with_length_proof_batch`."""
+        buf, count, d = self._blob_rows_be("disperse_blobs_bytes", blobs)
+        n, chunk_len = int(n), int(chunk_len)
+        self._encode_shape_checks(d, n, chunk_len, srs)
+        srs_order, claimed_len = int(srs_order), int(claimed_len)
+        if srs_order <= 0 or (srs_order & (srs_order - 1)) != 0 or claimed_len <= 0 or (claimed_len & (claimed_len - 1)) != 0:
+            raise FFTError("length provided is not a power of 2")
+        if d > claimed_len or claimed_len > srs_order:
+            raise GenericError("the claimed length must lie between the polynomial's length and the order of the setup")
+        ctx = self._ctx()
+        m = n // chunk_len
+        cm = np.zeros(count * 32, dtype=np.uint8); c2 = np.zeros(count * 64, dtype=np.uint8); pi2 = np.zeros(count * 64, dtype=np.uint8)
+        ys = np.zeros(count * n * 32, dtype=np.uint8) if values else None
+        pr = np.zeros(count * m * 32, dtype=np.uint8) if proofs else None
+        p8 = lambda a: a.ctypes.data_as(_lib.u8p) if a is not None else None
+        bad = C.c_uint64(0)
+        rc = _lib.load().kzg_disperse_blobs_bytes(ctx.handle, srs.handle, g2_srs.handle, g2_trailing.handle, g2_trailing.first_power, int(srs_order), p8(buf), count, d,
+                                                  n, chunk_len, int(claimed_len), p8(cm), p8(c2), p8(pi2), p8(ys), p8(pr), C.byref(bad))
+        if rc == _lib.ERR_SRS_CAPACITY_EXCEEDED:
+            raise SrsCapacityExceeded(int(claimed_len), len(g2_trailing))
+        if rc == _lib.ERR_POLY_LENGTH:
+            raise SerializationError("polynomial length is not correct")
+        self._raise_encode_bytes_status(ctx, rc, bad.value, d, srs)
+        return tuple(a.tobytes() if a is not None else None for a in (cm, c2, pi2, ys, pr))
+
+    @staticmethod
     def _coset_items_polys(name, polynomials, eval_form):
         """(data (B, d, 4), count, d, eval_form flag) of the polynomials of `prove_cosets_batch` / `coset_quotients`: one polynomial, a list
         of one form and length, or a (B, d, 4) array with eval_form= True / False."""
