@@ -13,11 +13,10 @@
 // SMALLEST bad index, whatever the launch geometry.  Plain vector loads and stores only; integer VALU work throughout, no MFMA.  The
 // compiler's figures for the kernels: profiles/coset_bytes.md.
 #include "engine.h"
+#include "byte_stager.h"
 #include "g1_decode.h"
-#include "msm_limits.h"
 
 #include <algorithm>
-#include <cstring>
 #include <string>
 
 namespace kzg {
@@ -69,52 +68,11 @@ k_fr_decode_be(const uint4* __restrict__ bytes, uint4* __restrict__ out, uint32_
 // -------------------------------------------------------------------------------------------------
 // host driver (slot 0's workspace and stream)
 // -------------------------------------------------------------------------------------------------
-// The bytes reach the device in chunks through the two halves of the workspace's pinned result buffer, as in g2decode.hip (one half is
-// filled while the other is in flight: no pinned allocation grows with the batch); ONE stager serves the arrays of a call one after the
-// other, so a half is reused only behind the copy that last read it.  A kernel starts behind every COSET_BYTES_LAUNCH bytes.
-constexpr size_t COSET_BYTES_CHUNK = (size_t)1 << 20;               // bytes per staged chunk: 32 768 points or values
-constexpr size_t COSET_BYTES_LAUNCH = 4 * COSET_BYTES_CHUNK;        // bytes per kernel launch: 131 072 lanes
-static_assert(2 * COSET_BYTES_CHUNK <= (size_t)MSM_MAX_OUT * 128, "two chunks fit the pinned result buffer");
+// The bytes go up through a ByteStager (byte_stager.h: the pinned halves and their lifetime rules): ONE stager serves the arrays of a
+// call one after the other, the caller's own when it has staged bytes already.  A kernel starts behind every COSET_BYTES_LAUNCH bytes.
+constexpr size_t COSET_BYTES_LAUNCH = 4 * STAGE_CHUNK_BYTES;        // bytes per kernel launch: 131 072 lanes
 
-namespace {
-struct ByteStager {
-    hipStream_t st = nullptr;
-    char* pinned = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    size_t chunk = 0;
-    ~ByteStager() { for (hipEvent_t v : ev) if (v) (void)hipEventDestroy(v); }
-    hipError_t init(hipStream_t stream, void* pinned_buf) {
-        st = stream;
-        pinned = static_cast<char*>(pinned_buf);
-        for (hipEvent_t& v : ev) { const hipError_t e = hipEventCreateWithFlags(&v, hipEventDisableTiming); if (e != hipSuccess) return e; }
-        return hipSuccess;
-    }
-    // bytes of src -> d_dst; launch(lo, hi) is called behind the copies of every COSET_BYTES_LAUNCH bytes (byte offsets, multiples of 32)
-    template <class Launch>
-    hipError_t push(const uint8_t* src, size_t bytes, char* d_dst, Launch&& launch) {
-        size_t launched = 0;
-        for (size_t lo = 0; lo < bytes; lo += COSET_BYTES_CHUNK, ++chunk) {
-            const size_t len = std::min(COSET_BYTES_CHUNK, bytes - lo), half = chunk & 1;
-            hipError_t e = chunk >= 2 ? hipEventSynchronize(ev[half]) : hipSuccess;      // the copy that last read this half has finished
-            if (e != hipSuccess) return e;
-            memcpy(pinned + half * COSET_BYTES_CHUNK, src + lo, len);
-            e = hipMemcpyAsync(d_dst + lo, pinned + half * COSET_BYTES_CHUNK, len, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipEventRecord(ev[half], st);
-            if (e != hipSuccess) return e;
-            const size_t staged = lo + len;
-            if (staged - launched >= COSET_BYTES_LAUNCH || staged == bytes) {
-                launch(launched, staged);
-                e = hipGetLastError();
-                if (e != hipSuccess) return e;
-                launched = staged;
-            }
-        }
-        return hipSuccess;
-    }
-};
-}  // namespace
-
-int32_t coset_bytes_enqueue(kzg_ctx* ctx, CosetBytesDecode* job) {
+int32_t coset_bytes_enqueue(kzg_ctx* ctx, CosetBytesDecode* job, ByteStager* in_use) {
     MsmWorkspace& ws = ctx->msm;
     hipStream_t st = ctx->stream;
     const size_t M = job->n_points[0], N = job->n_points[1], V = job->n_values;
@@ -127,14 +85,15 @@ int32_t coset_bytes_enqueue(kzg_ctx* ctx, CosetBytesDecode* job) {
     job->d_points_be[0] = reinterpret_cast<const uint4*>(d_pts);
     job->d_points_be[1] = reinterpret_cast<const uint4*>(d_pts + M * 32);
     job->d_ys_be = ctx->cb[0].as<uint4>();
-    ByteStager stager;
-    hipError_t e = stager.init(st, ws.pinned_out);
+    ByteStager own;
+    ByteStager& stager = in_use ? *in_use : own;
+    hipError_t e = in_use ? hipSuccess : own.init(st, ws.pinned_out);
     if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0xFF, 16, st);
     for (int a = 0; a < 2 && e == hipSuccess; ++a) {
         const size_t n = job->n_points[a];
         if (n == 0) continue;
         char* d_bytes = d_pts + (a ? M * 32 : 0);
-        e = stager.push(job->points_be[a], n * 32, d_bytes, [&](size_t lo, size_t hi) {
+        e = stager.push(job->points_be[a], n * 32, d_bytes, COSET_BYTES_LAUNCH, [&](size_t lo, size_t hi) {
             const size_t p0 = lo / 32;
             const uint32_t cnt = (uint32_t)((hi - lo) / 32);
             const dim3 grid((cnt + 255) / 256), block(256);
@@ -148,7 +107,7 @@ int32_t coset_bytes_enqueue(kzg_ctx* ctx, CosetBytesDecode* job) {
     }
     if (e == hipSuccess && V) {
         char* d_bytes = ctx->cb[0].as<char>();
-        e = stager.push(job->ys_be, V * 32, d_bytes, [&](size_t lo, size_t hi) {
+        e = stager.push(job->ys_be, V * 32, d_bytes, COSET_BYTES_LAUNCH, [&](size_t lo, size_t hi) {
             const size_t v0 = lo / 32;
             const uint32_t cnt = (uint32_t)((hi - lo) / 32);
             hipLaunchKernelGGL(k_fr_decode_be, dim3((cnt + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint4*>(d_bytes + lo), job->d_ys + 2 * v0, cnt, (uint32_t)v0,
@@ -156,11 +115,9 @@ int32_t coset_bytes_enqueue(kzg_ctx* ctx, CosetBytesDecode* job) {
         });
     }
     if (e != hipSuccess) {
-        (void)hipStreamSynchronize(st);                             // (the pinned halves are in use until here)
+        (void)hipStreamSynchronize(st);                             // (byte_stager.h: drained before an error leaves)
         return set_error(ctx, e, "decoding serialized coset items");
     }
-    // the stager's events go with it: the copies they mark are ordered in front of everything the caller enqueues on this stream, and the
-    // pinned halves are next written by a reduction kernel of an MSM on this stream or by the next call's stager, behind a synchronisation
     return KZG_OK;
 }
 

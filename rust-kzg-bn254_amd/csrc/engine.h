@@ -310,7 +310,8 @@ int32_t g2_weighted_tile_sums(kzg_ctx* ctx, const uint4* d_points, size_t n_poin
 int32_t g2_locate_segment_sums(kzg_ctx* ctx, const uint4* d_points, size_t n_points, const LocatePlan& plan, const uint32_t* weights_canonical, size_t n_weights,
                                int bits, uint64_t* out_seg_g2);
 // g2decode.hip: n gnark-compressed points of the host decoded on the device (g2_decode.h; flags: KZG_G2_CHECK_SUBGROUP | KZG_G2_REJECT_GENERATOR) into
-// d_points (device format) or, with d_points == nullptr, as wire points to out_wire (host; written only when no point is refused).
+// d_points (device format) or, with d_points == nullptr, as wire points to out_wire (host; written only when no point is refused).  Called under
+// ctx->mu with slot 0 idle: the bytes go up through a ByteStager (byte_stager.h).  Synchronised on return.
 // *bad_word = index << 2 | kind (G2_BAD_* of g2_decode.h) of the smallest refused index, or 0xFFFFFFFF
 int32_t g2_decompress_run(kzg_ctx* ctx, const uint8_t* bytes, size_t n, uint32_t flags, uint4* d_points, uint64_t* out_wire, uint32_t* bad_word);
 // the status of such a bad word (KZG_OK for 0xFFFFFFFF), its index to *bad_index (may be null), a line for kzg_ctx_last_error
@@ -383,7 +384,7 @@ int32_t coset_r_powers_device_bytes(kzg_ctx* ctx, const uint8_t* commitments_be,
                                     const uint64_t* d_ks, const uint4* d_proofs_be, size_t count, size_t n, size_t l, uint4* d_weights, uint64_t* out_r_powers);
 // Serialized coset items decoded on the device (cosetbytes.hip, g1_decode.h).  Called under ctx->mu with the device set and slot 0 idle.  Up to two
 // arrays of gnark-compressed G1 points (32 B each; [0] commitments, [1] proofs) and one of big-endian scalars (32 B each); an absent array has n = 0.
-// The host bytes go up through the pinned memory of slot 0's workspace into ctx->cb (values: cb[0]; points: cb[1]) and stay there (d_*_be).  Points
+// The host bytes go up through a ByteStager (byte_stager.h) into ctx->cb (values: cb[0]; points: cb[1]) and stay there (d_*_be).  Points
 // leave in the device format of curve.h (d_points, and a second copy at d_points_copy when that is not null) or, with wire_points, as wire points
 // with one identity byte each (d_inf); values leave as wire scalars.  bad[a] = index << 2 | kind (G1_BAD_* of g1_decode.h; 0 for a value >= r) of
 // the SMALLEST refused index of array a (0 commitments, 1 proofs, 2 values), or 0xFFFFFFFF.
@@ -401,14 +402,16 @@ struct CosetBytesDecode {
     const uint4* d_ys_be = nullptr;
     uint32_t bad[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};   // (set by the collect)
 };
-int32_t coset_bytes_enqueue(kzg_ctx* ctx, CosetBytesDecode* job);    // uploads and kernels on ctx->stream; the host bytes are consumed on return
+// uploads and kernels on ctx->stream; the host bytes are consumed on return.  in_use: the stager of a caller that has staged bytes in this call already
+struct ByteStager;
+int32_t coset_bytes_enqueue(kzg_ctx* ctx, CosetBytesDecode* job, ByteStager* in_use = nullptr);
 int32_t coset_bytes_collect(kzg_ctx* ctx, CosetBytesDecode* job);    // drains the stream, reads the three bad words
 // the status of a bad word (KZG_OK for 0xFFFFFFFF): KZG_ERR_DESERIALIZE / KZG_ERR_NOT_ON_CURVE, the element's index / per_item to *bad_index (may be
 // null), a line with the array's name for kzg_ctx_last_error
 int32_t coset_bytes_status(kzg_ctx* ctx, const char* who, const char* array, uint32_t bad_word, size_t per_item, uint64_t* bad_index);
 // Serialized blob headers decoded on the device (headerbytes.hip).  Called under ctx->mu with the device set and slot 0 idle; count <= 2^20.  Per
 // header 32 B of gnark-compressed commitment and 64 B each of length commitment and length proof (g2_decode.h's format and the identity 0x40 || 63
-// zeros), staged through the pinned memory of slot 0's workspace into ws.bases_wire (G2) and ctx->cb[1] (G1), where they stay.  The G2 elements
+// zeros), staged through ONE ByteStager (byte_stager.h) into ws.bases_wire (G2) and ctx->cb[1] (G1), where they stay.  The G2 elements
 // leave subgroup-checked at d_g2: the device format of curve_g2.h in the order C2_0, pi2_0, C2_1, .. or, with `wire`, wire points, the count C2 in
 // front of the count pi2 (the identity as zeros either way).  The commitments leave at d_commitments in the device format of curve.h or, with `wire`,
 // as wire points with one identity byte each at d_commitments_inf.  bad_g1 = index << 2 | kind (G1_BAD_* of g1_decode.h) of the smallest refused

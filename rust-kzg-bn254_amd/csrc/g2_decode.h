@@ -27,11 +27,6 @@ constexpr uint32_t G2_BAD_SUBGROUP = 2;         // not in the order-r subgroup
 constexpr uint32_t G2_BAD_GENERATOR = 3;        // the generator itself
 constexpr uint32_t G2_DECODE_OK = 4;
 
-// how the host drivers feed the decode kernels (g2decode.hip, headerbytes.hip): compressed points per staged chunk (1 MiB of pinned
-// memory) and per kernel launch (one wave per SIMD fills the device with 65 536 lanes)
-constexpr size_t G2_DECODE_CHUNK = 16384;
-constexpr size_t G2_DECODE_LAUNCH = 4 * G2_DECODE_CHUNK;
-
 // ---------------------------------------------------------------------------------------------
 // bytes
 // ---------------------------------------------------------------------------------------------
@@ -205,5 +200,30 @@ KZG_HD bool g2_is_generator(const G2Affine& p) {
         diff |= (uint32_t)(p.x.c0.l[j] ^ gx.c0.l[j]) | (uint32_t)(p.x.c1.l[j] ^ gx.c1.l[j]) | (uint32_t)(p.y.c0.l[j] ^ gy.c0.l[j]) | (uint32_t)(p.y.c1.l[j] ^ gy.c1.l[j]);
     return diff == 0;
 }
+
+#if defined(__HIPCC__)
+// ---------------------------------------------------------------------------------------------
+// what the decode kernels share around g2_decompress_point (k_g2_decompress, k_header_g2_decode)
+// ---------------------------------------------------------------------------------------------
+// the 64 bytes of one point as four uint4
+__device__ __forceinline__ void g2_load_raw(uint32_t raw[16], const uint4* __restrict__ src) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { const uint4 q = src[k]; raw[4 * k] = q.x; raw[4 * k + 1] = q.y; raw[4 * k + 2] = q.z; raw[4 * k + 3] = q.w; }
+}
+// a decoded point (canonical) as the 32 words it leaves in: wire words (WIRE) or the device format of curve_g2.h
+template <bool WIRE>
+__device__ __forceinline__ void g2_point_to_words(uint32_t o[32], const G2Affine& p) {
+    if (WIRE) {
+        fq2_to_wire(o, p.x);
+        fq2_to_wire(o + 16, p.y);
+    } else {
+        fe_pack(o, p.x.c0); fe_pack(o + 8, p.x.c1); fe_pack(o + 16, p.y.c0); fe_pack(o + 24, p.y.c1);      // (canonical already)
+    }
+}
+__device__ __forceinline__ void g2_store_words(uint4* __restrict__ dst, const uint32_t o[32]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) dst[k] = make_uint4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
+}
+#endif
 
 }  // namespace kzg

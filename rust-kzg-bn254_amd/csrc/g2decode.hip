@@ -11,11 +11,9 @@
 // of the two, not their sum; profiles/g2_decompress.md has the compiler's figures.  The budget is that of k_g2_subgroup_check: one wave per
 // SIMD, one point per lane.  Integer VALU work throughout: no MFMA.
 #include "engine.h"
+#include "byte_stager.h"
 #include "g2_decode.h"
-#include "msm_limits.h"
 
-#include <algorithm>
-#include <cstring>
 #include <string>
 
 namespace kzg {
@@ -26,8 +24,7 @@ k_g2_decompress(const uint4* __restrict__ bytes, uint4* __restrict__ out, uint32
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint32_t raw[16];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { const uint4 q = bytes[4 * (size_t)i + k]; raw[4 * k] = q.x; raw[4 * k + 1] = q.y; raw[4 * k + 2] = q.z; raw[4 * k + 3] = q.w; }
+    g2_load_raw(raw, bytes + 4 * (size_t)i);
     G2Affine p;
     uint32_t kind = g2_decompress_point(p, raw);
     if (kind == G2_DECODE_OK && (flags & KZG_G2_CHECK_SUBGROUP) && !g2_in_subgroup(p)) kind = G2_BAD_SUBGROUP;
@@ -35,35 +32,18 @@ k_g2_decompress(const uint4* __restrict__ bytes, uint4* __restrict__ out, uint32
     uint32_t o[32];
 #pragma unroll
     for (int j = 0; j < 32; ++j) o[j] = 0;
-    if (kind == G2_DECODE_OK) {
-        if (WIRE) {
-            fq2_to_wire(o, p.x);
-            fq2_to_wire(o + 16, p.y);
-        } else {
-            fe_pack(o, p.x.c0); fe_pack(o + 8, p.x.c1); fe_pack(o + 16, p.y.c0); fe_pack(o + 24, p.y.c1);      // (canonical already)
-        }
-    } else {
-        atomicMin(bad, (first + i) << 2 | kind);                    // first + i < 2^28
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) out[8 * (size_t)i + k] = make_uint4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
+    if (kind == G2_DECODE_OK) g2_point_to_words<WIRE>(o, p);
+    else atomicMin(bad, (first + i) << 2 | kind);                   // first + i < 2^28
+    g2_store_words(out + 8 * (size_t)i, o);
 }
 
 // -------------------------------------------------------------------------------------------------
 // host driver (slot 0's workspace and stream, synchronised on return)
 // -------------------------------------------------------------------------------------------------
-// The bytes reach the device in chunks through the two halves of the workspace's pinned result buffer (one half is filled while the
-// other is in flight: no pinned allocation grows with n), and a kernel starts behind every G2_DECODE_LAUNCH points: a launch of one
-// wave per SIMD fills the device with 65 536 lanes, and launches of one stream run one after the other.
-// (G2_DECODE_CHUNK points per staged chunk, G2_DECODE_LAUNCH points per kernel launch: g2_decode.h)
-static_assert(2 * G2_DECODE_CHUNK * 64 <= (size_t)MSM_MAX_OUT * 128, "two chunks fit the pinned result buffer");
-
-namespace {
-struct EventPair {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~EventPair() { for (hipEvent_t v : e) if (v) (void)hipEventDestroy(v); }
-};
-}  // namespace
+// The bytes go up through a ByteStager (byte_stager.h: the pinned halves and their lifetime rules), and a kernel starts behind every
+// G2_DECODE_LAUNCH points: a launch of one wave per SIMD fills the device with 65 536 lanes, and launches of one stream run one after
+// the other.
+constexpr size_t G2_DECODE_LAUNCH = 4 * STAGE_CHUNK_BYTES / 64;     // points per kernel launch
 
 // n compressed points (host) -> d_points (device format, n x 128 B) when d_points != nullptr, else wire points to out_wire (host) through
 // ws.bases.  *bad_word = index << 2 | kind of the smallest refused index, or 0xFFFFFFFF; out_wire is written only when no point is refused.
@@ -79,32 +59,22 @@ int32_t g2_decompress_run(kzg_ctx* ctx, const uint8_t* bytes, size_t n, uint32_t
     { const int32_t rc = msm_pinned_out(ctx, ws); if (rc != KZG_OK) return rc; }
     char* d_bytes = ws.bases_wire.as<char>();
     uint32_t* d_bad = reinterpret_cast<uint32_t*>(d_bytes + n * 64);
-    char* pinned = static_cast<char*>(ws.pinned_out);
-    EventPair ev;
-    for (hipEvent_t& v : ev.e) KZG_HIP_TRY(ctx, hipEventCreateWithFlags(&v, hipEventDisableTiming));
-    uint32_t h_bad = 0xFFFFFFFFu;
-    hipError_t e = hipMemcpyAsync(d_bad, &h_bad, 4, hipMemcpyHostToDevice, st);
-    size_t launched = 0, chunk = 0;
-    for (size_t lo = 0; lo < n && e == hipSuccess; lo += G2_DECODE_CHUNK, ++chunk) {
-        const size_t len = std::min(G2_DECODE_CHUNK, n - lo), half = chunk & 1;
-        if (chunk >= 2) e = hipEventSynchronize(ev.e[half]);        // the copy that last read this half has finished
-        if (e != hipSuccess) break;
-        memcpy(pinned + half * G2_DECODE_CHUNK * 64, bytes + lo * 64, len * 64);
-        e = hipMemcpyAsync(d_bytes + lo * 64, pinned + half * G2_DECODE_CHUNK * 64, len * 64, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipEventRecord(ev.e[half], st);
-        const size_t staged = lo + len;
-        if (e == hipSuccess && (staged - launched >= G2_DECODE_LAUNCH || staged == n)) {
-            const uint32_t cnt = (uint32_t)(staged - launched);
+    ByteStager stager;
+    hipError_t e = stager.init(st, ws.pinned_out);
+    if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0xFF, 4, st);
+    if (e == hipSuccess) {
+        e = stager.push(bytes, n * 64, d_bytes, G2_DECODE_LAUNCH * 64, [&](size_t lo, size_t hi) {
+            const size_t p0 = lo / 64;
+            const uint32_t cnt = (uint32_t)((hi - lo) / 64);
             const dim3 grid((cnt + 255) / 256), block(256);
-            const uint4* src = reinterpret_cast<const uint4*>(d_bytes + launched * 64);
-            if (wire) hipLaunchKernelGGL(k_g2_decompress<true>, grid, block, 0, st, src, d_points + 8 * launched, cnt, (uint32_t)launched, flags, d_bad);
-            else hipLaunchKernelGGL(k_g2_decompress<false>, grid, block, 0, st, src, d_points + 8 * launched, cnt, (uint32_t)launched, flags, d_bad);
-            e = hipGetLastError();
-            launched = staged;
-        }
+            const uint4* src = reinterpret_cast<const uint4*>(d_bytes + lo);
+            if (wire) hipLaunchKernelGGL(k_g2_decompress<true>, grid, block, 0, st, src, d_points + 8 * p0, cnt, (uint32_t)p0, flags, d_bad);
+            else hipLaunchKernelGGL(k_g2_decompress<false>, grid, block, 0, st, src, d_points + 8 * p0, cnt, (uint32_t)p0, flags, d_bad);
+        });
     }
+    uint32_t h_bad = 0xFFFFFFFFu;
     if (e == hipSuccess) e = hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);                 // (on every path: the pinned halves and &h_bad are in use until here)
+    const hipError_t es = hipStreamSynchronize(st);                 // (on every path: byte_stager.h, and &h_bad is being written until here)
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return set_error(ctx, e, "decoding compressed G2 points");
     *bad_word = h_bad;

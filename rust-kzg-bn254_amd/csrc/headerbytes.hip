@@ -17,12 +17,11 @@
 // The commitments go through k_g1_decode_be (cosetbytes.hip).  Plain vector loads and stores only; integer VALU work throughout, no MFMA.
 // The compiler's figures for the kernels and the measured times: profiles/header_bytes.md.
 #include "engine.h"
+#include "byte_stager.h"
 #include "g2_decode.h"
 #include "header_item_stream.h"
-#include "msm_limits.h"
 
 #include <algorithm>
-#include <cstring>
 #include <string>
 
 namespace kzg {
@@ -36,10 +35,8 @@ k_header_g2_decode(const uint4* __restrict__ c2, const uint4* __restrict__ pi2, 
     if (e >= n_elems) return;
     const uint32_t h = h0 + (e >> 1), which = e & 1u;
     if (h >= count) return;
-    const uint4* src = (which ? pi2 : c2) + 4 * (size_t)h;
     uint32_t raw[16];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { const uint4 q = src[k]; raw[4 * k] = q.x; raw[4 * k + 1] = q.y; raw[4 * k + 2] = q.z; raw[4 * k + 3] = q.w; }
+    g2_load_raw(raw, (which ? pi2 : c2) + 4 * (size_t)h);
     uint32_t rest = raw[0] ^ 0x40u;                                 // the identity: byte 0 = 0x40, every other bit zero
 #pragma unroll
     for (int k = 1; k < 16; ++k) rest |= raw[k];
@@ -53,19 +50,9 @@ k_header_g2_decode(const uint4* __restrict__ c2, const uint4* __restrict__ pi2, 
     uint32_t o[32];
 #pragma unroll
     for (int j = 0; j < 32; ++j) o[j] = 0;
-    if (kind != G2_DECODE_OK) {
-        atomicMin(bad, (2 * h + which) << 2 | kind);                // 2 h + which < 2^21
-    } else if (!identity) {
-        if (WIRE) {
-            fq2_to_wire(o, p.x);
-            fq2_to_wire(o + 16, p.y);
-        } else {
-            fe_pack(o, p.x.c0); fe_pack(o + 8, p.x.c1); fe_pack(o + 16, p.y.c0); fe_pack(o + 24, p.y.c1);      // (canonical already)
-        }
-    }
-    uint4* dst = out + 8 * (WIRE ? (size_t)which * count + h : 2 * (size_t)h + which);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) dst[k] = make_uint4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
+    if (kind != G2_DECODE_OK) atomicMin(bad, (2 * h + which) << 2 | kind);      // 2 h + which < 2^21
+    else if (!identity) g2_point_to_words<WIRE>(o, p);
+    g2_store_words(out + 8 * (WIRE ? (size_t)which * count + h : 2 * (size_t)h + which), o);
 }
 
 constexpr uint32_t HEADER_FS_LANES = 64;
@@ -90,19 +77,11 @@ k_header_item_digests(const uint4* __restrict__ commitments_be, const uint4* __r
 // -------------------------------------------------------------------------------------------------
 // host drivers (slot 0's workspace and stream, synchronised on return)
 // -------------------------------------------------------------------------------------------------
-// The G2 bytes reach the device as g2_decompress_run's do: in pieces of at most G2_DECODE_CHUNK elements through the two halves of the
-// workspace's pinned result buffer (no pinned allocation grows with the batch), the two arrays of a run of headers one after the other, and
-// a kernel starts behind every G2_DECODE_LAUNCH elements.  The commitments follow through the stager of cosetbytes.hip, which works in the
-// same two halves: it starts once the last G2 piece has left them.
-static_assert(2 * G2_DECODE_CHUNK * 64 <= (size_t)MSM_MAX_OUT * 128, "two pieces fit the pinned result buffer");
-constexpr size_t HEADER_DECODE_LAUNCH = G2_DECODE_LAUNCH / 2;        // headers per launch of k_header_g2_decode
-
-namespace {
-struct EventPair {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~EventPair() { for (hipEvent_t v : e) if (v) (void)hipEventDestroy(v); }
-};
-}  // namespace
+// ONE ByteStager (byte_stager.h: the pinned halves and their lifetime rules) serves the whole call: per run of HEADER_PIECE headers a piece
+// of C2 bytes and a piece of pi2 bytes, a kernel behind every HEADER_DECODE_LAUNCH headers, then the commitments through
+// coset_bytes_enqueue (cosetbytes.hip) on the same stager, whose wait-before-reuse covers the halves the last G2 pieces are leaving.
+constexpr size_t HEADER_PIECE = STAGE_CHUNK_BYTES / 64;              // headers per staged piece of either G2 array
+constexpr size_t HEADER_DECODE_LAUNCH = 2 * HEADER_PIECE;            // headers per launch of k_header_g2_decode: 65 536 lanes
 
 int32_t header_bytes_decode(kzg_ctx* ctx, HeaderBytesDecode* job) {
     const size_t n = job->count;
@@ -116,22 +95,13 @@ int32_t header_bytes_decode(kzg_ctx* ctx, HeaderBytesDecode* job) {
     char* d_arr[2] = {ws.bases_wire.as<char>(), ws.bases_wire.as<char>() + n * 64};
     uint32_t* d_bad = reinterpret_cast<uint32_t*>(ws.bases_wire.as<char>() + 2 * n * 64);
     const uint8_t* h_arr[2] = {job->length_commitments_be, job->length_proofs_be};
-    char* pinned = static_cast<char*>(ws.pinned_out);
-    EventPair ev;
-    for (hipEvent_t& v : ev.e) KZG_HIP_TRY(ctx, hipEventCreateWithFlags(&v, hipEventDisableTiming));
-    uint32_t h_bad = 0xFFFFFFFFu;
-    hipError_t e = hipMemcpyAsync(d_bad, &h_bad, 4, hipMemcpyHostToDevice, st);
-    size_t launched = 0, piece = 0;
-    for (size_t lo = 0; lo < n && e == hipSuccess; lo += G2_DECODE_CHUNK) {
-        const size_t len = std::min(G2_DECODE_CHUNK, n - lo);
-        for (int a = 0; a < 2 && e == hipSuccess; ++a, ++piece) {
-            const size_t half = piece & 1;
-            if (piece >= 2) e = hipEventSynchronize(ev.e[half]);      // the copy that last read this half has finished
-            if (e != hipSuccess) break;
-            memcpy(pinned + half * G2_DECODE_CHUNK * 64, h_arr[a] + lo * 64, len * 64);
-            e = hipMemcpyAsync(d_arr[a] + lo * 64, pinned + half * G2_DECODE_CHUNK * 64, len * 64, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipEventRecord(ev.e[half], st);
-        }
+    ByteStager stager;
+    hipError_t e = stager.init(st, ws.pinned_out);
+    if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0xFF, 4, st);
+    size_t launched = 0;
+    for (size_t lo = 0; lo < n && e == hipSuccess; lo += HEADER_PIECE) {
+        const size_t len = std::min(HEADER_PIECE, n - lo);
+        for (int a = 0; a < 2 && e == hipSuccess; ++a) e = stager.copy(h_arr[a] + lo * 64, len * 64, d_arr[a] + lo * 64);
         const size_t staged = lo + len;
         if (e == hipSuccess && (staged - launched >= HEADER_DECODE_LAUNCH || staged == n)) {
             const uint32_t cnt = (uint32_t)(2 * (staged - launched));
@@ -143,9 +113,8 @@ int32_t header_bytes_decode(kzg_ctx* ctx, HeaderBytesDecode* job) {
             launched = staged;
         }
     }
-    for (int h = 0; h < 2 && e == hipSuccess; ++h) e = hipEventSynchronize(ev.e[h]);      // both halves are free for the next stager
     if (e != hipSuccess) {
-        (void)hipStreamSynchronize(st);                                                    // (the pinned halves and &h_bad are in use until here)
+        (void)hipStreamSynchronize(st);                                                    // (byte_stager.h: drained before an error leaves)
         return set_error(ctx, e, "decoding serialized header elements");
     }
     CosetBytesDecode g1;
@@ -154,7 +123,8 @@ int32_t header_bytes_decode(kzg_ctx* ctx, HeaderBytesDecode* job) {
     g1.d_points[0] = job->d_commitments;
     g1.d_inf[0] = job->d_commitments_inf;
     g1.wire_points = job->wire;
-    int32_t rc = coset_bytes_enqueue(ctx, &g1);
+    int32_t rc = coset_bytes_enqueue(ctx, &g1, &stager);
+    uint32_t h_bad = 0xFFFFFFFFu;
     if (rc == KZG_OK) e = hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, st);
     const int32_t rc2 = rc == KZG_OK ? coset_bytes_collect(ctx, &g1) : ((void)hipStreamSynchronize(st), rc);     // (drains the stream on every path)
     if (rc2 != KZG_OK) return rc2;

@@ -193,6 +193,81 @@ def test_encode_decode_round_trip(k, l, count):
             k.verifier.decode_coset_items(bytes(bad), bytes(badp), l)
 
 
+# ---- 3b. more than one staged piece, more than one launch --------------------------------------------------------------------------------
+# The bytes go up in pieces of 32 768 points or values through two pinned halves (csrc/byte_stager.h) and a kernel starts behind every
+# 131 072.  A pool of POOL distinct items is tiled up to the count: POOL is odd, so it divides neither a piece nor a launch, and a copy or
+# launch offset that is wrong by a whole piece reads other bytes.  The yardstick is the pool's own decode by the same entry (compared with
+# the golden points and the host conversion here), tiled the same way.
+POOL = 1021
+
+
+def tiled(pool_bytes, n):
+    return bytearray((pool_bytes * (n // POOL + 1))[:32 * n])
+
+
+@pytest.fixture(scope="module")
+def point_pool(k, golden):
+    data, wire = golden
+    out = k.helpers.decompress_g1_device(data[:32 * POOL])
+    assert np.array_equal(out, wire[:POOL])
+    return data[:32 * POOL], out
+
+
+@pytest.fixture(scope="module")
+def value_pool(k):
+    rnd = random.Random(1021)
+    vals = [0, R_ - 1] + [rnd.randrange(R_) for _ in range(POOL - 2)]
+    data = b"".join(v.to_bytes(32, "big") for v in vals)
+    out, _ = k.verifier.decode_coset_items(data, None, 1)
+    assert np.array_equal(out[:, 0], pyref.frs_to_mont(vals))
+    return data, out
+
+
+def test_points_across_three_pieces_are_bit_equal(k, point_pool):
+    data, out = point_pool
+    n = 65537
+    b = tiled(data, n)
+    b[:32] = b[32 * (n - 1):] = IDENTITY_BE
+    got, inf = k.helpers.decompress_g1_device(bytes(b), return_is_infinity=True)
+    want = out[np.arange(n) % POOL]
+    want[0] = want[n - 1] = 0
+    assert np.array_equal(got, want)
+    assert inf[0] and inf[n - 1] and inf.sum() == 2
+
+
+def test_bad_points_in_the_second_launch(k, point_pool):
+    data, _ = point_pool
+    L = k._lib
+    n = 131074
+    b = tiled(data, n)
+    b[32 * 131072:32 * 131073] = damage(bytes(b[32 * 131072:32 * 131073]), "off")
+    b[32 * 131073:32 * 131074] = damage(bytes(b[32 * 131073:32 * 131074]), "x=p")
+    rc, bad, _, _ = raw_decompress(k, bytes(b), n)
+    assert (rc, bad) == (L.ERR_NOT_ON_CURVE, 131072)
+
+
+def test_values_across_a_second_launch(k, value_pool):
+    data, out = value_pool
+    L = k._lib
+    n = 131074
+    b = tiled(data, n)
+    got, _ = k.verifier.decode_coset_items(bytes(b), None, 1)
+    assert np.array_equal(got, out[np.arange(n) % POOL])
+    b[32 * 131072:32 * 131073] = R_.to_bytes(32, "big")
+    b[32 * 131073:32 * 131074] = b"\xff" * 32
+    yb = np.frombuffer(bytes(b), np.uint8)
+    oy = np.zeros((n, 1, 4), np.uint64)
+    idx, arr = C.c_uint64(0), L.i32(-1)
+    rc = L.load().kzg_coset_items_decode_be(L.default_context().handle, yb.ctypes.data_as(u8p), None, n, 1, L.ptr(oy), None, C.byref(idx), C.byref(arr))
+    assert (rc, idx.value, arr.value) == (L.ERR_DESERIALIZE, 131072, 2)
+
+
+def test_one_stager_serves_proofs_and_values_with_three_pieces_each(k, point_pool, value_pool):
+    n = 65537
+    ys, pf = k.verifier.decode_coset_items(bytes(tiled(value_pool[0], n)), bytes(tiled(point_pool[0], n)), 1)
+    assert np.array_equal(ys, value_pool[1][np.arange(n) % POOL]) and np.array_equal(pf, point_pool[1][np.arange(n) % POOL])
+
+
 # ---- 4. the fused verifier ----------------------------------------------------------------------------------------------------------------
 def check_fused_equals_decoded(k, world, l, count):
     V = k.verifier

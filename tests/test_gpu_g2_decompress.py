@@ -205,6 +205,43 @@ def test_the_smallest_bad_index_is_reported_with_its_own_kind(powers, compressed
     assert _device(data, _lib.G2_CHECK_SUBGROUP)[:2] == (_lib.ERR_NOT_ON_CURVE, 64)
 
 
+# ---- 3b. more than one staged piece, more than one launch --------------------------------------------------------------------------------
+# The bytes go up in pieces of 16 384 points through two pinned halves (csrc/byte_stager.h) and a kernel starts behind every 65 536.  A
+# pool of 299 distinct points ([tau^1 .. tau^299]_2: one of the 300 dropped) is tiled up to the count: 299 is odd, so it divides neither a
+# piece nor a launch, and a copy or launch offset that is wrong by a whole piece reads other bytes.  The yardstick is the pool's own decode
+# by the same entry (compared with the host decoder above), tiled the same way.
+POOL = N - 1
+
+
+def _tiled(pool_bytes, item, n):
+    return (pool_bytes * (n // (len(pool_bytes) // item) + 1))[:item * n]
+
+
+@pytest.fixture(scope="module")
+def pool(powers, compressed):
+    data = compressed[0][64:64 * N]
+    rc, _, out = _device(data, _lib.G2_CHECK_SUBGROUP)
+    assert rc == _lib.OK and np.array_equal(out, powers[1:N])
+    return data, out
+
+
+@pytest.mark.parametrize("n,flags", [(32769, 0), (65538, _lib.G2_CHECK_SUBGROUP)], ids=["three_pieces_half_0_reused", "a_second_launch"])
+def test_tiled_pool_across_pieces_and_launches_is_bit_equal(pool, n, flags):
+    data, out = pool
+    rc, _, got = _device(_tiled(data, 64, n), flags)
+    assert rc == _lib.OK and np.array_equal(got, out[np.arange(n) % POOL])
+
+
+def test_bad_points_in_the_second_launch_and_the_second_piece(pool):
+    data, _ = pool
+    rnd = random.Random(8)
+    big = _tiled(data, 64, 65538)
+    both = _damaged(_damaged(big, 65536, "no_point_of_that_x", rnd), 65537, "flag_cleared", rnd)
+    assert _device(both, _lib.G2_CHECK_SUBGROUP)[:2] == (_lib.ERR_NOT_ON_CURVE, 65536)
+    one = _damaged(big[:64 * 32769], 16384, "no_point_of_that_x", rnd)          # the first point of the second piece
+    assert _device(one, 0)[:2] == (_lib.ERR_NOT_ON_CURVE, 16384)
+
+
 # ---- 4. x^3 + b in Fq ----------------------------------------------------------------------------------------------------------------
 def test_points_whose_y_squared_lies_in_fq():
     """x = (x0, x1) with x0^2 = (x1^3 - b1) / (3 x1) makes the u-part of x^3 + b vanish: the a1 = 0 branch of the square root, with

@@ -341,6 +341,29 @@ def test_a_batch_one_header_above_a_decode_launch(k, env):
     assert V.verify_length_proof_batch_bytes(c_be, c2_be, wrong, lens, env.shifts, ctx=env.ctx) is False
 
 
+def test_a_batch_above_a_decode_launch_tiled_with_an_odd_period(k, env):
+    """The same count with the headers in a sequence of period 1 021 over the pool (header i is pool header (i mod 1 021) mod 260): 1 021
+    is odd, so it divides neither a staged piece (16 384 headers) nor a launch, and a copy or launch offset that is wrong by a whole piece
+    reads other bytes (16 384 = 48 mod 1 021, and neither 48 nor 48 - 1 021 is a multiple of 260).  One stager (csrc/byte_stager.h) takes
+    2 x 3 G2 pieces and then the 2 pieces of the commitments, the first of them in a half that a G2 piece used last."""
+    count = 32769
+    idx = (np.arange(count) % 1021) % POOL
+    c_be = np.frombuffer(b"".join(env.c_be), np.uint8).reshape(POOL, 32)[idx]
+    c2_be = np.frombuffer(b"".join(env.c2_be), np.uint8).reshape(POOL, 64)[idx]
+    pi2_be = np.frombuffer(b"".join(env.pi2_be[4]), np.uint8).reshape(POOL, 64)[idx]
+    lens = [4] * count
+    V = k.verifier
+    assert V.verify_length_proof_batch_bytes(c_be, c2_be, pi2_be, lens, env.shifts, ctx=env.ctx) is True
+    bad = c2_be.copy()
+    bad[16384] = np.frombuffer(bad_element(env, "c2", "no point")[0], np.uint8)       # the first header of the second pair of pieces
+    with pytest.raises(k.errors.NotOnCurveError, match="length commitment 16384"):
+        V.verify_length_proof_batch_bytes(c_be, bad, pi2_be, lens, env.shifts, ctx=env.ctx)
+    wrong = pi2_be.copy()
+    wrong[32768] = pi2_be[5]                                        # a subgroup point, the wrong one: the equation fails
+    assert not np.array_equal(wrong[32768], pi2_be[32768])
+    assert V.verify_length_proof_batch_bytes(c_be, c2_be, wrong, lens, env.shifts, ctx=env.ctx) is False
+
+
 # ---- arguments ------------------------------------------------------------------------------------------------------------------------
 def test_argument_errors_in_their_order(k, env):
     L = k._lib
