@@ -1184,6 +1184,68 @@ int32_t kzg_retrieve_blobs_bytes(kzg_ctx* ctx, const kzg_srs* srs, const uint8_t
                                  size_t degree_bound, int32_t eval_form, size_t out_len, const uint64_t* r_powers_mont /* NULL: derived */,
                                  const uint64_t* g2_tau_l_mont, int32_t* out_ok, uint8_t* out_polys_be, int32_t* out_consistent,
                                  uint64_t* bad_index, int32_t* bad_array);
+/* kzg_verify_multiproof_batch_locate on serialized items: the front end of kzg_verify_multiproof_batch_bytes, then the group sums and the
+ * search of the decoded entry over what that front end left on the device.  For every input whose bytes decode, out_group_ok,
+ * *out_bad_groups and *out_pairing_checks are those of kzg_verify_multiproof_batch_locate on the output of kzg_coset_items_decode_be
+ * (with the commitments decoded), and the weights are the same bit for bit (r_powers_mont = NULL derives them; out_r_powers_mont, may be
+ * NULL, receives the count weights used).  Values, proofs and commitments go up once, as bytes; nothing decoded returns to the host.
+ * Errors, in this order: 1. the host checks of kzg_verify_multiproof_batch_locate, in its order (null pointers: those of the bytes entry
+ * with out_bad_groups, out_group_ok when n_groups > 0 and group_indices when count > 0; ...; a group index >= n_groups; count *
+ * chunk_len > 2^28; n_groups > 2^28); 2. a _begin in flight on slot 0 -> KZG_ERR_INVALID_ARG; 3. the decode refusals exactly as
+ * kzg_verify_multiproof_batch_bytes reports them: a bad commitment (*bad_array = 0), a bad proof (1), a bad value (2), *bad_index, the
+ * status of the smallest bad index; 4. g2_tau_l_mont off the twist -> KZG_ERR_G2_TAU_NOT_ON_CURVE.  count = 0: every group good, no
+ * device work, no pairing check.  KZG_VB_TRACE=1 prints the phase times on stderr. */
+int32_t kzg_verify_multiproof_batch_locate_bytes(kzg_ctx* ctx, kzg_srs* srs, const uint8_t* commitments_be, size_t n_commitments,
+                                                 const uint64_t* commitment_indices, const uint64_t* coset_indices, const uint8_t* ys_be,
+                                                 const uint8_t* proofs_be, size_t count, size_t n, size_t chunk_len,
+                                                 const uint64_t* r_powers_mont /* NULL: derived */, const uint64_t* g2_tau_l_mont,
+                                                 const uint64_t* group_indices, size_t n_groups, uint8_t* out_group_ok,
+                                                 size_t* out_bad_groups, size_t* out_pairing_checks /* may be NULL */,
+                                                 uint64_t* out_r_powers_mont /* may be NULL */, uint64_t* bad_index, int32_t* bad_array);
+/* The retriever's call that survives bad chunks.  A retriever holds `count` chunks per blob, more than it needs, from operators it does
+ * not trust: this call names the bad chunks and recovers every blob from its first use_count good ones, in item order.  Items and
+ * arguments as kzg_retrieve_blobs_bytes; out_ok is replaced by
+ *   out_item_status[b * count + j]   0 good; 1 decodes but fails its equation; 2 proof bytes not canonical (flag bits, x >= p); 3 the
+ *                                    proof's x has no point on the curve; 4 a value >= r.  The smallest of 2 / 3 / 4 that applies
+ *                                    wins: a proof is reported before a value, as in the other entries;
+ *   out_blob_status[b]               0 recovered; 1 fewer than use_count good items: row b of out_polys_be is zero bytes and
+ *                                    out_consistent[b] = 0;
+ *   *out_bad_items, *out_unrecovered the number of items of status != 0 and of blobs of status 1;
+ *   *out_pairing_checks              (may be NULL) the pairing checks spent.
+ * A commitment that does not decode stays a call error (*bad_array = 0): it is the retriever's own input.
+ * Weights: r_powers_mont = NULL derives those of kzg_compute_multiproof_r_powers_bytes on the bytes AS GIVEN (both transcript paths hash
+ * bytes and decode nothing, so a refusal changes no weight); then every refused item (status 2 / 3 / 4) enters every sum with weight 0
+ * -- a small kernel zeroes them on the device -- and every other item keeps its weight.  out_r_powers_mont (may be NULL) receives the
+ * blobs x count weights used: those bits, zero at every refused item.  The status arrays, the counts and the weights are written behind
+ * the last step that can fail: an error leaves them as the caller handed them in.  The context's lock is held for the whole call, the
+ * host-side pairing checks included (the located pass and the recovery read what the front end left on the device).
+ * Equation: the batch equation runs once.  If it holds, every non-refused item is good and *out_pairing_checks = 1.  If it fails, the bad
+ * items are located on what the front end left on the device -- no byte crosses the bus again, no weight is derived again, the per-item
+ * rows r_i w^(-k_i t) IFFT_l(ys_i)_t are computed once -- in two levels with the search of kzg_verify_multiproof_batch_locate: groups =
+ * blobs, then groups = the single non-refused items of the bad blobs only (segment sums, group MSMs and point sums over that subset).
+ * *out_pairing_checks <= 1 + (1 + 2 B ceil(log2 blobs)) + (1 + 2 b ceil(log2 I)) for B bad blobs, their I items and b bad items.
+ * Recovery: rows and flags of a recovered blob are byte for byte those of kzg_recover_from_cosets_batch_bytes on its chosen chunks (one
+ * index row per blob, the same degree_bound, eval_form and out_len); the value bytes are read where the verifier left them.  With
+ * use_count = count and nothing bad, rows and flags are those of kzg_retrieve_blobs_bytes.  All of the above returns KZG_OK.
+ * Errors, in this order, 1 and 2 on the host before anything is launched: 1. the recovery's table: a null ctx, ys_be, coset_indices,
+ * out_polys_be, out_item_status, out_blob_status, out_bad_items or out_unrecovered, or blobs = 0 -> KZG_ERR_INVALID_ARG; index_rows not
+ * 1 or blobs -> KZG_ERR_INVALID_ARG; n not a power of two -> KZG_ERR_NOT_POWER_OF_TWO; n > 2^24 -> KZG_ERR_DOMAIN; n = 1, chunk_len not
+ * a power of two or > n / 2, count = 0 or > n / chunk_len, use_count = 0 or > count -> KZG_ERR_INVALID_ARG; a coset index >= n /
+ * chunk_len or twice in one row -> KZG_ERR_INVALID_ARG; degree_bound > use_count * chunk_len -> KZG_ERR_INVALID_ARG; out_len (evaluations:
+ * not n; coefficients: below the bound or above n) -> KZG_ERR_INVALID_ARG; (n / chunk_len) * (n / chunk_len - use_count) > 2^32 ->
+ * KZG_ERR_TOO_LARGE; blobs * n * 32 overflows -> KZG_ERR_INVALID_ARG; blobs * count * chunk_len > 2^28 -> KZG_ERR_TOO_LARGE; 2. the host
+ * checks of kzg_verify_multiproof_batch_bytes (srs, commitments_be, proofs_be, g2_tau_l_mont when chunk_len != 1; the SRS; chunk_len >
+ * the SRS); 3. a _begin in flight on slot 0 -> KZG_ERR_INVALID_ARG; 4. a bad commitment, *bad_array = 0, *bad_index = the blob;
+ * 5. g2_tau_l_mont off the twist.  KZG_VB_TRACE=1 prints the phase times on stderr. */
+int32_t kzg_retrieve_blobs_bytes_tolerant(kzg_ctx* ctx, kzg_srs* srs, const uint8_t* commitments_be /* blobs x 32 */,
+                                          const uint64_t* coset_indices, size_t index_rows, const uint8_t* ys_be,
+                                          const uint8_t* proofs_be /* blobs x count x 32 */, size_t blobs, size_t count, size_t use_count,
+                                          size_t n, size_t chunk_len, size_t degree_bound, int32_t eval_form, size_t out_len,
+                                          const uint64_t* r_powers_mont /* NULL: derived */, const uint64_t* g2_tau_l_mont,
+                                          uint8_t* out_item_status /* blobs x count */, uint8_t* out_blob_status /* blobs */,
+                                          size_t* out_bad_items, size_t* out_unrecovered, size_t* out_pairing_checks /* may be NULL */,
+                                          uint8_t* out_polys_be, int32_t* out_consistent /* may be NULL */,
+                                          uint64_t* out_r_powers_mont /* may be NULL */, uint64_t* bad_index, int32_t* bad_array);
 
 /* ---- blob headers in their serialized form (csrc/headerbytes.hip, csrc/header_item_stream.h, csrc/host_header_bytes.h) ---------------
  * What a validator receives off the wire, per header (C, C2, pi2, d): the commitment as 32 bytes in the G1 format above (identity 0x40

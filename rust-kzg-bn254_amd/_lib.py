@@ -252,6 +252,10 @@ PROTOTYPES = {
     "kzg_recover_from_cosets_batch_bytes": (i32, [vp, u8p, u64p, sz, sz, sz, sz, sz, sz, i32, sz, u8p, C.POINTER(i32), C.POINTER(C.c_uint64)]),
     "kzg_retrieve_blobs_bytes": (i32, [vp, vp, u8p, u64p, sz, u8p, u8p, sz, sz, sz, sz, sz, i32, sz, u64p, u64p, C.POINTER(i32), u8p, C.POINTER(i32),
                                        C.POINTER(C.c_uint64), C.POINTER(i32)]),
+    "kzg_verify_multiproof_batch_locate_bytes": (i32, [vp, vp, u8p, sz, u64p, u64p, u8p, u8p, sz, sz, sz, u64p, u64p, u64p, sz, u8p, C.POINTER(sz),
+                                                       C.POINTER(sz), u64p, C.POINTER(C.c_uint64), C.POINTER(i32)]),
+    "kzg_retrieve_blobs_bytes_tolerant": (i32, [vp, vp, u8p, u64p, sz, u8p, u8p, sz, sz, sz, sz, sz, sz, i32, sz, u64p, u64p, u8p, u8p, C.POINTER(sz),
+                                                C.POINTER(sz), C.POINTER(sz), u8p, C.POINTER(i32), u64p, C.POINTER(C.c_uint64), C.POINTER(i32)]),
     "kzg_header_items_encode_be": (i32, [u64p, u64p, u64p, sz, u8p, u8p, u8p]),
     "kzg_header_items_decode_be": (i32, [vp, u8p, u8p, u8p, sz, u64p, u64p, u64p, C.POINTER(C.c_uint64), C.POINTER(i32)]),
     "kzg_verify_length_proof_batch_bytes": (i32, [vp, u8p, u8p, u8p, u64p, sz, u64p, u64p, sz, u64p, C.POINTER(i32), u64p, C.POINTER(C.c_uint64),

@@ -150,9 +150,13 @@ int32_t coset_stage_words(kzg_ctx* ctx, const uint64_t* commitments, size_t M, c
 // and commitments go up as 32 bytes each (ctx->cb[1]) and are decoded straight into the layout of CosetStage (the decode kernel writes the
 // second copy of the proofs).  Nothing decoded returns to the host.  The transcript reads the bytes: on the host pool beside the decode kernels,
 // or on the device where the bytes landed.  who: the entry, for the line of a refused element.  ms: host r_powers beside the decode, decode, r_powers.
+// item_status (kzg_retrieve_blobs_bytes_tolerant): a proof or value that does not decode does not end the call; item i gets its RETRIEVE_ITEM_* there
+// (2 / 3 / 4, the smallest that applies, else 0), its decoded proof and values are zeros and its weight is ZERO wherever the stage keeps weights
+// (s->r_powers, then a copy in s->derived, and s->d_w): the item enters every sum with weight 0 and every other item keeps its weight.  The
+// transcript hashes the bytes as given on either path (host_fiat_shamir.h, fsdevice.hip: nothing there decodes), so a refusal changes no weight.
 int32_t coset_stage_bytes(kzg_ctx* ctx, const char* who, const uint8_t* commitments_be, size_t M, const uint64_t* commitment_indices, const uint64_t* coset_indices,
                           const uint8_t* ys_be, const uint8_t* proofs_be, size_t N, size_t n, size_t l, const uint64_t* r_powers, bool g2_ok, uint64_t* bad_index,
-                          int32_t* bad_array, CosetStage* s) {
+                          int32_t* bad_array, CosetStage* s, std::vector<uint8_t>* item_status = nullptr) {
     const auto t0 = Clock::now();
     const bool derive = !r_powers, on_device = s->begin(ctx->transcript_device.load(std::memory_order_relaxed), N, M, n, l, coset_indices, commitment_indices, r_powers);
     s->lk = std::unique_lock<std::mutex>(ctx->mu);
@@ -168,6 +172,7 @@ int32_t coset_stage_bytes(kzg_ctx* ctx, const char* who, const uint8_t* commitme
     job.points_be[0] = commitments_be; job.n_points[0] = M; job.d_points[0] = s->d_bases + 4 * 2 * N;
     job.points_be[1] = proofs_be; job.n_points[1] = N; job.d_points[1] = s->d_bases; job.d_points_copy[1] = s->d_bases + 4 * N;
     job.ys_be = ys_be; job.n_values = N * l; job.d_ys = s->d_ys;
+    job.item_status = item_status != nullptr; job.values_per_item = l;
     rc = coset_bytes_enqueue(ctx, &job);
     if (rc != KZG_OK) return rc;
     hipError_t e_k = hipMemcpyAsync(s->d_k, coset_indices, N * 8, hipMemcpyHostToDevice, ctx->stream);
@@ -185,6 +190,21 @@ int32_t coset_stage_bytes(kzg_ctx* ctx, const char* who, const uint8_t* commitme
         if (rc != KZG_OK) { if (bad_array) *bad_array = a; return rc; }
     }
     if (!g2_ok) return KZG_ERR_G2_TAU_NOT_ON_CURVE;                                      // (before the device transcript, which nothing refuses)
+    bool refused = false;
+    if (item_status) {
+        item_status->resize(N);
+        for (size_t i = 0; i < N; ++i) {
+            const uint32_t w = job.status[i];
+            (*item_status)[i] = w & COSET_ITEM_PROOF_BYTES ? RETRIEVE_ITEM_PROOF_BYTES : w & COSET_ITEM_PROOF_OFF_CURVE ? RETRIEVE_ITEM_PROOF_OFF_CURVE
+                                : w & COSET_ITEM_VALUE ? RETRIEVE_ITEM_VALUE : RETRIEVE_ITEM_GOOD;
+            refused = refused || w != 0;
+        }
+    }
+    auto mask_host = [&]() {                                                             // the host's copy of the weights, refused items zeroed
+        if (!refused) return;
+        if (s->r_powers != s->derived.data()) { s->derived.assign(s->r_powers, s->r_powers + 4 * N); s->r_powers = s->derived.data(); }
+        for (size_t i = 0; i < N; ++i) if (job.status[i]) memset(s->derived.data() + 4 * i, 0, 32);
+    };
     const auto t_dec = Clock::now();
     // 1. the weights where the interpolation reads them
     s->rp_path = derive ? " (host, from bytes, beside the decode)" : " (supplied)";
@@ -192,7 +212,10 @@ int32_t coset_stage_bytes(kzg_ctx* ctx, const char* who, const uint8_t* commitme
         rc = coset_r_powers_device_bytes(ctx, commitments_be, M, commitment_indices, job.d_ys_be, s->d_k, job.d_points_be[1], N, n, l, s->d_w, s->derived.data());
         if (rc != KZG_OK) return rc;
         s->rp_path = " (device, from bytes)";
+        mask_host();
+        if (refused) { rc = coset_mask_refused_weights(ctx, s->d_w, job.d_status, N); if (rc != KZG_OK) return rc; }
     } else {
+        mask_host();
         KZG_HIP_TRY(ctx, hipMemcpyAsync(s->d_w, s->r_powers, N * 32, hipMemcpyHostToDevice, ctx->stream));
     }
     s->ms[0] = derive && !on_device ? ms_between(t0, t_rp_host) : 0.0;
@@ -309,6 +332,88 @@ int32_t coset_group_sums_core(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* commit
                 "coefficient MSMs %.3f ms, point sums %.3f ms, host sums %.3f ms\n", N, l, M, n_groups, S, ms_between(t0, t_up), ms_between(t_up, t_interp),
                 ms_between(t_interp, t_msm), ms_between(t_msm, t_pts), ms_between(t_pts, Clock::now()));
     return KZG_OK;
+}
+
+// ---- the same sums over a stage that a bytes front end has left on the device (kzg_verify_multiproof_batch_locate_bytes, the tolerant retriever) ----
+// What the stage holds and what survives a REJECTED coset_batch_tail over it (read from the code that runs there):
+//   * the points, s.d_bases = proofs | proofs | commitments: every MSM driver takes its bases as const and sorts digits into its own workspace
+//     (msm.hip: ws.sorted / ws.offs / buckets); nothing reserves or writes ctx->msm.bases behind the front end.  The point sums read the second
+//     copy of the proofs and the commitments behind it, the layout locate_point_sums_device wants;
+//   * the weights and coset indices, s.d_w / s.d_k in ctx->mv[1]: only read;
+//   * the values, s.d_ys in ctx->mv[0]: read in place for l <= 1024; for l > 1024 the tail has replaced row i by IFFT_l(ys_i) (one ntt_run per
+//     coset, the call coset_item_rows_device would make itself), so the rows are taken from there: `transformed`;
+//   * the value bytes, ctx->cb[0], and the point bytes and status words, ctx->cb[1]: written by the front end only.
+// The item rows are computed ONCE per call (ResidentSums::rows_ready) and summed under as many plans as the caller searches.
+struct ResidentSums {
+    const CosetStage* s = nullptr;
+    bool transformed = false;                    // a tail has run over the stage (matters for l > 1024)
+    bool rows_ready = false;
+    uint4* d_w2 = nullptr; uint64_t* d_ci = nullptr;     // ctx->ml[4]: r_i w^(k_i l) | commitment rows, per item
+};
+
+int32_t resident_group_sums(kzg_ctx* ctx, kzg_srs* srs, ResidentSums* r, const LocatePlan& plan, GroupSums* out) {
+    using namespace kzg_host;
+    const CosetStage& st = *r->s;
+    const size_t N = st.N, l = st.l, S = plan.segs.size();
+    int32_t rc = KZG_OK;
+    if (!r->rows_ready) {
+        std::vector<uint64_t> shifted(4 * N);
+        coset_shifted_weights(st.coset_indices, st.r_powers, N, st.n / l, shifted.data(), host_parallel_for);
+        KZG_HIP_TRY(ctx, ctx->ml[4].reserve(N * 40));
+        r->d_w2 = ctx->ml[4].as<uint4>();
+        r->d_ci = reinterpret_cast<uint64_t*>(ctx->ml[4].as<uint8_t>() + N * 32);
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(r->d_w2, shifted.data(), N * 32, hipMemcpyHostToDevice, ctx->stream));
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(r->d_ci, st.commitment_indices, N * 8, hipMemcpyHostToDevice, ctx->stream));
+        rc = coset_item_rows_device(ctx, st.d_ys, st.d_k, st.d_w, N, st.n, l, r->transformed);
+        if (rc != KZG_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                             // (`shifted` is in use until here)
+        r->rows_ready = true;
+    }
+    out->lhs.clear();
+    out->rhs.clear();
+    if (S == 0) return KZG_OK;
+    rc = locate_upload_plan(ctx, plan);
+    if (rc == KZG_OK) rc = coset_seg_sums_device(ctx, st.d_ys, plan, l);
+    if (rc != KZG_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }            // (the plan's arrays are in flight)
+    KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                                 // the MSM launches run on the slots' streams
+    std::vector<uint64_t> interp_xy(8 * S);
+    rc = commit_batch_device(ctx, srs, ctx->ml[0].p, l, S, interp_xy.data(), nullptr);
+    if (rc != KZG_OK) return rc;
+    std::vector<uint64_t> sums(32 * S);
+    rc = locate_point_sums_device(ctx, st.d_bases + 4 * N, r->d_ci, st.d_w, r->d_w2, plan, sums.data(), N);
+    if (rc != KZG_OK) return rc;
+    out->lhs.resize(S);
+    out->rhs.resize(S);
+    const size_t per = 256;
+    host_parallel_for((S + per - 1) / per, [&](size_t c) {
+        for (size_t j = c * per; j < std::min(S, (c + 1) * per); ++j) {
+            Xyzz b;
+            memcpy(&out->lhs[j], sums.data() + 32 * j, 128);
+            memcpy(&b, sums.data() + 32 * j + 16, 128);
+            Xyzz i = xyzz_from_affine_wire(interp_xy.data() + 8 * j);
+            i.y = neg(i.y);
+            out->rhs[j] = xyzz_add(b, i);
+        }
+    });
+    return KZG_OK;
+}
+
+// The search of host_locate.h over the segments' pairs: seg_ok[j] = 1 for a good segment, *bad = the bad ones.  Returns the pairing checks.
+size_t group_search(const GroupSums& gs, const kzg_host::G2& g2_tau_l, uint8_t* seg_ok, size_t* bad) {
+    using namespace kzg_host;
+    struct Ops {
+        Xyzz zero() const { return xyzz_inf(); }
+        Xyzz add(const Xyzz& a, const Xyzz& b) const { return xyzz_add(a, b); }
+        Xyzz sub(const Xyzz& a, Xyzz b) const { b.y = neg(b.y); return xyzz_add(a, b); }
+    };
+    const G2 g2 = g2_generator();
+    auto holds = [&](const Xyzz& lhs, const Xyzz& rhs) {
+        uint64_t a[8], b[8];
+        xyzz_to_affine(lhs, a, nullptr);
+        xyzz_to_affine(rhs, b, nullptr);
+        return pairings_verify_pooled(g1_from_wire(a), g2_tau_l, g1_from_wire(b), g2);
+    };
+    return locate_search(gs.lhs.data(), gs.rhs.data(), gs.lhs.size(), Ops(), holds, seg_ok, bad);
 }
 
 // count points -> affine wire words and identity flags, one inversion per 256 points, chunks on the host pool
@@ -551,28 +656,169 @@ int32_t kzg_verify_multiproof_batch_locate(kzg_ctx* ctx, kzg_srs* srs, const uin
     if (!g2_ok) return KZG_ERR_G2_TAU_NOT_ON_CURVE;
     // the search runs over the non-empty groups: an empty group's pair is the identity twice, it holds and changes no range
     const auto t0 = Clock::now();
-    struct Ops {
-        Xyzz zero() const { return xyzz_inf(); }
-        Xyzz add(const Xyzz& a, const Xyzz& b) const { return xyzz_add(a, b); }
-        Xyzz sub(const Xyzz& a, Xyzz b) const { b.y = neg(b.y); return xyzz_add(a, b); }
-    };
-    const G2 g2 = g2_generator();
-    auto holds = [&](const Xyzz& lhs, const Xyzz& rhs) {
-        uint64_t a[8], b[8];
-        xyzz_to_affine(lhs, a, nullptr);
-        xyzz_to_affine(rhs, b, nullptr);
-        return pairings_verify_pooled(g1_from_wire(a), g2_tau_l, g1_from_wire(b), g2);
-    };
     const size_t S = gs.plan.segs.size();
     std::vector<uint8_t> seg_ok(S, 1);
     size_t bad = 0;
-    const size_t checks = locate_search(gs.lhs.data(), gs.rhs.data(), S, Ops(), holds, seg_ok.data(), &bad);
+    const size_t checks = group_search(gs, g2_tau_l, seg_ok.data(), &bad);
     memset(out_group_ok, 1, n_groups);
     for (size_t j = 0; j < S; ++j) out_group_ok[gs.plan.segs[j]] = seg_ok[j];
     *out_bad_groups = bad;
     if (out_pairing_checks) *out_pairing_checks = checks;
     if (opts().vb_trace)
         fprintf(stderr, "kzg_verify_multiproof_batch_locate groups=%zu: search %.3f ms, %zu pairing checks, %zu bad groups\n", n_groups, ms_between(t0, Clock::now()), checks, bad);
+    return KZG_OK;
+}
+
+// kzg_verify_multiproof_batch_locate on items in their serialized form: the bytes front end of kzg_verify_multiproof_batch_bytes, then the group
+// sums over what it left on the device and the search of the decoded entry
+int32_t kzg_verify_multiproof_batch_locate_bytes(kzg_ctx* ctx, kzg_srs* srs, const uint8_t* commitments_be, size_t n_commitments, const uint64_t* commitment_indices,
+                                                 const uint64_t* coset_indices, const uint8_t* ys_be, const uint8_t* proofs_be, size_t count, size_t n, size_t chunk_len,
+                                                 const uint64_t* r_powers_mont, const uint64_t* g2_tau_l_mont, const uint64_t* group_indices, size_t n_groups,
+                                                 uint8_t* out_group_ok, size_t* out_bad_groups, size_t* out_pairing_checks, uint64_t* out_r_powers_mont,
+                                                 uint64_t* bad_index, int32_t* bad_array) {
+    int32_t rc = multiproof_batch_checks(ctx, srs, !out_bad_groups || (n_groups && !out_group_ok),
+                                         !commitments_be || !commitment_indices || !coset_indices || !ys_be || !proofs_be || !group_indices,
+                                         !g2_tau_l_mont && chunk_len != 1, n_commitments, commitment_indices, coset_indices, count, n, chunk_len, group_indices, n_groups, true);
+    if (rc != KZG_OK) return rc;
+    if (count == 0) {                                                                    // nothing to refuse: no device work, no pairing
+        if (n_groups) memset(out_group_ok, 1, n_groups);
+        *out_bad_groups = 0;
+        if (out_pairing_checks) *out_pairing_checks = 0;
+        return KZG_OK;
+    }
+    const auto t0 = Clock::now();
+    kzg_host::G2 g2_tau_l;
+    const bool g2_ok = load_g2_tau(g2_tau_l_mont, &g2_tau_l);                            // reported after the bytes, as the batch entry on bytes does
+    GroupSums gs;
+    rc = locate_plan(group_indices, count, n_groups, &gs.plan);
+    if (rc != KZG_OK) return rc;
+    CosetStage st;
+    rc = coset_stage_bytes(ctx, "kzg_verify_multiproof_batch_locate_bytes", commitments_be, n_commitments, commitment_indices, coset_indices, ys_be, proofs_be, count, n,
+                           chunk_len, r_powers_mont, g2_ok, bad_index, bad_array, &st);
+    if (rc != KZG_OK) return rc;
+    const auto t_staged = Clock::now();
+    ResidentSums rs;
+    rs.s = &st;
+    rc = resident_group_sums(ctx, srs, &rs, gs.plan, &gs);
+    if (rc != KZG_OK) return rc;
+    st.lk.unlock();
+    const auto t_sums = Clock::now();
+    const size_t S = gs.plan.segs.size();
+    std::vector<uint8_t> seg_ok(S, 1);
+    size_t bad = 0;
+    const size_t checks = group_search(gs, g2_tau_l, seg_ok.data(), &bad);
+    if (n_groups) memset(out_group_ok, 1, n_groups);
+    for (size_t j = 0; j < S; ++j) out_group_ok[gs.plan.segs[j]] = seg_ok[j];
+    *out_bad_groups = bad;
+    if (out_pairing_checks) *out_pairing_checks = checks;
+    if (out_r_powers_mont) memcpy(out_r_powers_mont, st.r_powers, count * 32);
+    if (opts().vb_trace)
+        fprintf(stderr, "kzg_verify_multiproof_batch_locate_bytes N=%zu l=%zu M=%zu groups=%zu (non-empty %zu): decode + r_powers%s %.3f ms, group sums %.3f ms, "
+                "search %.3f ms, %zu pairing checks, %zu bad groups\n", count, chunk_len, n_commitments, n_groups, S, st.rp_path, ms_between(t0, t_staged),
+                ms_between(t_staged, t_sums), ms_between(t_sums, Clock::now()), checks, bad);
+    return KZG_OK;
+}
+
+// The retriever's call that survives bad chunks: the front end of kzg_retrieve_blobs_bytes with per-item decode status, the batch equation once
+// (refused items at weight 0), on a reject the located pass over the resident stage in two levels (blobs, then the single items of the bad
+// blobs), and the recovery of every blob from its first use_count good items, reading the value bytes where the front end left them.
+int32_t kzg_retrieve_blobs_bytes_tolerant(kzg_ctx* ctx, kzg_srs* srs, const uint8_t* commitments_be, const uint64_t* coset_indices, size_t index_rows,
+                                          const uint8_t* ys_be, const uint8_t* proofs_be, size_t blobs, size_t count, size_t use_count, size_t n, size_t chunk_len,
+                                          size_t degree_bound, int32_t eval_form, size_t out_len, const uint64_t* r_powers_mont, const uint64_t* g2_tau_l_mont,
+                                          uint8_t* out_item_status, uint8_t* out_blob_status, size_t* out_bad_items, size_t* out_unrecovered,
+                                          size_t* out_pairing_checks, uint8_t* out_polys_be, int32_t* out_consistent, uint64_t* out_r_powers_mont, uint64_t* bad_index,
+                                          int32_t* bad_array) {
+    int32_t rc = retrieve_tolerant_check(!ctx || !ys_be || !coset_indices || !out_polys_be || !out_item_status || !out_blob_status || !out_bad_items || !out_unrecovered,
+                                         coset_indices, index_rows, blobs, count, use_count, n, chunk_len, degree_bound, eval_form != 0, out_len);
+    if (rc != KZG_OK) return rc;
+    const size_t N = blobs * count, l = chunk_len;
+    std::vector<uint64_t> cosets, rows;
+    retrieve_items(coset_indices, index_rows, blobs, count, &cosets, &rows);
+    rc = multiproof_batch_checks(ctx, srs, false, !commitments_be || !proofs_be, !g2_tau_l_mont && chunk_len != 1, blobs, rows.data(), cosets.data(), N, n, chunk_len,
+                                 nullptr, 0, false);
+    if (rc != KZG_OK) return rc;
+    const auto t0 = Clock::now();
+    kzg_host::G2 g2_tau_l;
+    const bool g2_ok = load_g2_tau(g2_tau_l_mont, &g2_tau_l);
+    CosetStage st;
+    std::vector<uint8_t> status;
+    rc = coset_stage_bytes(ctx, "kzg_retrieve_blobs_bytes_tolerant", commitments_be, blobs, rows.data(), cosets.data(), ys_be, proofs_be, N, n, l, r_powers_mont, g2_ok,
+                           bad_index, bad_array, &st, &status);
+    if (rc != KZG_OK) return rc;
+    CosetTailTimes t;
+    int32_t ok = 0;
+    rc = coset_batch_tail(ctx, srs, st, g2_tau_l, &ok, &t);
+    if (rc != KZG_OK) return rc;
+    const auto t_verified = Clock::now();
+    size_t checks = 1;
+    // ctx->mu (st.lk) stays held through the host-side searches below, so threads that share the context wait for their pairing checks too.  It
+    // cannot be released in between: the located pass and the recovery read what the front end left in ctx->cb / mv / msm.bases, and any other
+    // entry on this context would overwrite it.  A caller who wants overlap gives each thread its own context.
+    if (!ok) {
+        // level 1: groups = blobs (every item; a refused one adds the identity).  Level 2: groups = the single non-refused items of the bad blobs.
+        // Two levels because the tree over all items costs 2 ceil(log2 N) checks per bad item AND sums, MSMs and point sums for N groups; the
+        // blobs first cost ceil(log2 blobs) levels over `blobs` groups, and only the bad blobs' items become groups of their own.
+        ResidentSums rs;
+        rs.s = &st; rs.transformed = true;
+        GroupSums gs;
+        rc = locate_plan(rows.data(), N, blobs, &gs.plan);
+        if (rc == KZG_OK) rc = resident_group_sums(ctx, srs, &rs, gs.plan, &gs);
+        if (rc != KZG_OK) return rc;
+        std::vector<uint8_t> blob_ok(blobs, 1);                                          // (count > 0: every blob is a segment, segment b = blob b)
+        size_t bad_blobs = 0;
+        checks += group_search(gs, g2_tau_l, blob_ok.data(), &bad_blobs);
+        std::vector<uint32_t> items;
+        for (size_t b = 0; b < blobs; ++b)
+            if (!blob_ok[b])
+                for (size_t j = 0; j < count; ++j) if (status[b * count + j] == RETRIEVE_ITEM_GOOD) items.push_back((uint32_t)(b * count + j));
+        if (!items.empty()) {
+            std::vector<uint64_t> own(items.size());
+            for (size_t j = 0; j < items.size(); ++j) own[j] = j;
+            rc = locate_subset_plan(items.data(), own.data(), items.size(), items.size(), &gs.plan);
+            if (rc == KZG_OK) rc = resident_group_sums(ctx, srs, &rs, gs.plan, &gs);
+            if (rc != KZG_OK) return rc;
+            std::vector<uint8_t> item_ok(items.size(), 1);                               // (segment j = chosen item j)
+            size_t bad_items = 0;
+            checks += group_search(gs, g2_tau_l, item_ok.data(), &bad_items);
+            for (size_t j = 0; j < items.size(); ++j) if (!item_ok[j]) status[items[j]] = RETRIEVE_ITEM_BAD_EQUATION;
+        }
+    }
+    const auto t_located = Clock::now();
+    size_t bad_items = 0;
+    for (size_t i = 0; i < N; ++i) bad_items += status[i] != RETRIEVE_ITEM_GOOD;
+    std::vector<uint32_t> chosen;
+    std::vector<uint8_t> blob_status;
+    const size_t unrecovered = retrieve_choose(status.data(), blobs, count, use_count, &chosen, &blob_status);
+    RecoverBatchPlan plan;
+    recover_selected_plan(coset_indices, index_rows, blobs, count, use_count, chosen.data(), blob_status.data(), n, l, degree_bound, eval_form != 0, out_len,
+                          ctx->recover_group_bytes, &plan);
+    if (unrecovered == blobs) {                                                          // nothing to recover: zero rows, no kernel
+        memset(out_polys_be, 0, blobs * plan.out_len * 32);
+    } else {
+        uint32_t bad_word = 0xFFFFFFFFu;                                                 // (stays: a chosen item has passed the decode, no other value is read)
+        RecoverIo io;
+        io.d_ys = ctx->cb[0].as<uint4>(); io.ys_be = true; io.out = out_polys_be; io.out_be = true; io.consistent = out_consistent; io.bad_word = &bad_word;
+        rc = recover_run_batch(ctx, plan, io);
+        if (rc != KZG_OK) return rc;
+    }
+    // every output is written here, behind the last call that can fail: an error leaves all of them as the caller handed them in
+    // (the rows excepted, which the recovery writes group by group)
+    memcpy(out_item_status, status.data(), N);
+    memcpy(out_blob_status, blob_status.data(), blobs);
+    *out_bad_items = bad_items;
+    *out_unrecovered = unrecovered;
+    if (out_pairing_checks) *out_pairing_checks = checks;
+    if (out_r_powers_mont) memcpy(out_r_powers_mont, st.r_powers, N * 32);
+    for (size_t b = 0; b < blobs; ++b)
+        if (blob_status[b]) {                                                            // (its work row is zero already: an item map without items)
+            memset(out_polys_be + b * plan.out_len * 32, 0, plan.out_len * 32);
+            if (out_consistent) out_consistent[b] = 0;
+        }
+    if (opts().vb_trace)
+        fprintf(stderr, "kzg_retrieve_blobs_bytes_tolerant blobs=%zu count=%zu use=%zu l=%zu: decode %.3f ms, r_powers%s %.3f ms, batch equation %.3f ms (%s), "
+                "locate %.3f ms, %zu pairing checks, %zu bad items, %zu blobs not recovered, recover %.3f ms, call %.3f ms\n", blobs, count, use_count, l, st.ms[1],
+                st.rp_path, st.ms[2], ms_between(t.start, t_verified), ok ? "holds" : "fails", ms_between(t_verified, t_located), checks, bad_items, unrecovered,
+                ms_between(t_located, Clock::now()), ms_between(t0, Clock::now()));
     return KZG_OK;
 }
 

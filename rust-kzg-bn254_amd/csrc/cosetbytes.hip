@@ -9,9 +9,13 @@
 //                          A refused point leaves as zeros.
 //   k_fr_decode_be         one lane per value, so consecutive lanes read consecutive 32-byte words: byte swap, compare with r, one product
 //                          into Montgomery form.  A value >= r is refused (zeros).
+//   k_mask_refused_weights one lane per item: the weight of an item whose status word is not zero becomes zero (the tolerant retriever).
 // Refusals go through ONE word per array, atomicMin over index << 2 | kind, as in g2decode.hip: the reported status is that of the
-// SMALLEST bad index, whatever the launch geometry.  Plain vector loads and stores only; integer VALU work throughout, no MFMA.  The
-// compiler's figures for the kernels: profiles/coset_bytes.md.
+// SMALLEST bad index, whatever the launch geometry.  The ITEMS instantiations (k_g1_decode_be<false, true> for the proofs, k_fr_decode_be<true>;
+// kzg_retrieve_blobs_bytes_tolerant) name EVERY refused item instead: atomicOr of a COSET_ITEM_* bit into one status word per item, N words
+// behind the bad words in ctx->cb[1], read with them at the one synchronisation; the commitments keep the one word.  The other
+// instantiations compile as they did.  Plain vector loads and stores and those two vector atomics only; integer VALU work throughout, no
+// MFMA.  The compiler's figures for the kernels: profiles/coset_bytes.md, profiles/retrieve_tolerant.md.
 #include "engine.h"
 #include "byte_stager.h"
 #include "g1_decode.h"
@@ -21,7 +25,10 @@
 
 namespace kzg {
 
-template <bool WIRE>
+// ITEMS (the tolerant retriever, kzg_retrieve_blobs_bytes_tolerant): a refusal ORs its COSET_ITEM_* bit into the status word of its ITEM
+// (point first + i; value (first + i) >> log_per_item) in place of the atomicMin on `bad`: every refused item is named, not the smallest
+// only.  A vector atomic OR of a constant bit: the l value lanes of an item and its proof lane may meet in one word in any order.
+template <bool WIRE, bool ITEMS = false>
 __global__ void __launch_bounds__(256)
 k_g1_decode_be(const uint4* __restrict__ bytes, uint4* __restrict__ out, uint4* __restrict__ out_copy, uint8_t* __restrict__ out_inf, uint32_t n, uint32_t first,
                uint32_t* __restrict__ bad) {
@@ -38,7 +45,8 @@ k_g1_decode_be(const uint4* __restrict__ bytes, uint4* __restrict__ out, uint4* 
         if (WIRE) g1_point_to_wire_words(o, x, y);
         else g1_point_to_device_words(o, x, y);
     } else if (kind != G1_DECODE_IDENTITY) {
-        atomicMin(bad, (first + i) << 2 | kind);                    // first + i < 2^28
+        if (ITEMS) atomicOr(bad + first + i, kind == G1_BAD_NOT_ON_CURVE ? COSET_ITEM_PROOF_OFF_CURVE : COSET_ITEM_PROOF_BYTES);   // bad: the n_points status words
+        else atomicMin(bad, (first + i) << 2 | kind);               // first + i < 2^28
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) out[4 * (size_t)i + k] = make_uint4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
@@ -49,8 +57,9 @@ k_g1_decode_be(const uint4* __restrict__ bytes, uint4* __restrict__ out, uint4* 
     if (WIRE) out_inf[i] = kind == G1_DECODE_OK ? 0 : 1;
 }
 
+template <bool ITEMS = false>
 __global__ void __launch_bounds__(256)
-k_fr_decode_be(const uint4* __restrict__ bytes, uint4* __restrict__ out, uint32_t n, uint32_t first, uint32_t* __restrict__ bad) {
+k_fr_decode_be(const uint4* __restrict__ bytes, uint4* __restrict__ out, uint32_t n, uint32_t first, uint32_t* __restrict__ bad, int log_per_item) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint4 q0 = bytes[2 * (size_t)i], q1 = bytes[2 * (size_t)i + 1];
@@ -59,10 +68,20 @@ k_fr_decode_be(const uint4* __restrict__ bytes, uint4* __restrict__ out, uint32_
     if (!fr_decode_be_to_wire(o, raw)) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = 0;
-        atomicMin(bad, (first + i) << 2);                           // first + i < 2^28; the one kind
+        if (ITEMS) atomicOr(bad + ((first + i) >> log_per_item), COSET_ITEM_VALUE);   // bad: the status words, one per item of 2^log_per_item values
+        else atomicMin(bad, (first + i) << 2);                      // first + i < 2^28; the one kind
     }
     out[2 * (size_t)i] = make_uint4(o[0], o[1], o[2], o[3]);
     out[2 * (size_t)i + 1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+
+// weights[i] = 0 where item i was refused by the decode (status word not zero): the item then enters every sum of the batch equation with weight 0
+__global__ void __launch_bounds__(256)
+k_mask_refused_weights(uint4* __restrict__ weights, const uint32_t* __restrict__ status, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || status[i] == 0u) return;
+    weights[2 * (size_t)i] = make_uint4(0, 0, 0, 0);
+    weights[2 * (size_t)i + 1] = make_uint4(0, 0, 0, 0);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -78,7 +97,8 @@ int32_t coset_bytes_enqueue(kzg_ctx* ctx, CosetBytesDecode* job, ByteStager* in_
     const size_t M = job->n_points[0], N = job->n_points[1], V = job->n_values;
     if (M > ((size_t)1 << 28) || N > ((size_t)1 << 28) || V > ((size_t)1 << 28)) return KZG_ERR_TOO_LARGE;
     KZG_HIP_TRY(ctx, ctx->cb[0].reserve(std::max<size_t>(V * 32, 32)));
-    KZG_HIP_TRY(ctx, ctx->cb[1].reserve((M + N) * 32 + 16));
+    const bool items = job->item_status;                            // N status words behind the bad words
+    KZG_HIP_TRY(ctx, ctx->cb[1].reserve((M + N) * 32 + 16 + (items ? N * 4 : 0)));
     { const int32_t rc = msm_pinned_out(ctx, ws); if (rc != KZG_OK) return rc; }
     char* d_pts = ctx->cb[1].as<char>();
     uint32_t* d_bad = reinterpret_cast<uint32_t*>(d_pts + (M + N) * 32);
@@ -89,6 +109,9 @@ int32_t coset_bytes_enqueue(kzg_ctx* ctx, CosetBytesDecode* job, ByteStager* in_
     ByteStager& stager = in_use ? *in_use : own;
     hipError_t e = in_use ? hipSuccess : own.init(st, ws.pinned_out);
     if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0xFF, 16, st);
+    job->d_status = items ? d_bad + 4 : nullptr;
+    if (e == hipSuccess && items && N) e = hipMemsetAsync(job->d_status, 0, N * 4, st);
+    const int log_per_item = __builtin_ctzll(std::max<size_t>(job->values_per_item, 1));
     for (int a = 0; a < 2 && e == hipSuccess; ++a) {
         const size_t n = job->n_points[a];
         if (n == 0) continue;
@@ -99,7 +122,9 @@ int32_t coset_bytes_enqueue(kzg_ctx* ctx, CosetBytesDecode* job, ByteStager* in_
             const dim3 grid((cnt + 255) / 256), block(256);
             const uint4* src = reinterpret_cast<const uint4*>(d_bytes + lo);
             uint4* copy = job->d_points_copy[a] ? job->d_points_copy[a] + 4 * p0 : nullptr;
-            if (job->wire_points)
+            if (items && a == 1)
+                hipLaunchKernelGGL((k_g1_decode_be<false, true>), grid, block, 0, st, src, job->d_points[a] + 4 * p0, copy, static_cast<uint8_t*>(nullptr), cnt, (uint32_t)p0, job->d_status);
+            else if (job->wire_points)
                 hipLaunchKernelGGL(k_g1_decode_be<true>, grid, block, 0, st, src, job->d_points[a] + 4 * p0, copy, job->d_inf[a] + p0, cnt, (uint32_t)p0, d_bad + a);
             else
                 hipLaunchKernelGGL(k_g1_decode_be<false>, grid, block, 0, st, src, job->d_points[a] + 4 * p0, copy, static_cast<uint8_t*>(nullptr), cnt, (uint32_t)p0, d_bad + a);
@@ -110,8 +135,9 @@ int32_t coset_bytes_enqueue(kzg_ctx* ctx, CosetBytesDecode* job, ByteStager* in_
         e = stager.push(job->ys_be, V * 32, d_bytes, COSET_BYTES_LAUNCH, [&](size_t lo, size_t hi) {
             const size_t v0 = lo / 32;
             const uint32_t cnt = (uint32_t)((hi - lo) / 32);
-            hipLaunchKernelGGL(k_fr_decode_be, dim3((cnt + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint4*>(d_bytes + lo), job->d_ys + 2 * v0, cnt, (uint32_t)v0,
-                               d_bad + 2);
+            const uint4* src = reinterpret_cast<const uint4*>(d_bytes + lo);
+            if (items) hipLaunchKernelGGL(k_fr_decode_be<true>, dim3((cnt + 255) / 256), dim3(256), 0, st, src, job->d_ys + 2 * v0, cnt, (uint32_t)v0, job->d_status, log_per_item);
+            else hipLaunchKernelGGL(k_fr_decode_be<false>, dim3((cnt + 255) / 256), dim3(256), 0, st, src, job->d_ys + 2 * v0, cnt, (uint32_t)v0, d_bad + 2, 0);
         });
     }
     if (e != hipSuccess) {
@@ -125,6 +151,10 @@ int32_t coset_bytes_collect(kzg_ctx* ctx, CosetBytesDecode* job) {
     const uint32_t* d_bad = reinterpret_cast<const uint32_t*>(ctx->cb[1].as<char>() + (job->n_points[0] + job->n_points[1]) * 32);
     uint32_t h_bad[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
     hipError_t e = hipMemcpyAsync(h_bad, d_bad, 12, hipMemcpyDeviceToHost, ctx->stream);
+    if (job->item_status) {
+        job->status.assign(job->n_points[1], 0);
+        if (e == hipSuccess && job->n_points[1]) e = hipMemcpyAsync(job->status.data(), job->d_status, job->n_points[1] * 4, hipMemcpyDeviceToHost, ctx->stream);
+    }
     const hipError_t es = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return set_error(ctx, e, "decoding serialized coset items");
@@ -140,6 +170,13 @@ int32_t coset_bytes_status(kzg_ctx* ctx, const char* who, const char* array, uin
     ctx->last_error = std::string(who) + ": " + array + " " + std::to_string(index) +
                       (off_curve ? " has no point on the curve" : " is not a canonical encoding (flag bits, or an integer not below the modulus)");
     return off_curve ? KZG_ERR_NOT_ON_CURVE : KZG_ERR_DESERIALIZE;
+}
+
+int32_t coset_mask_refused_weights(kzg_ctx* ctx, uint4* d_weights, const uint32_t* d_status, size_t count) {
+    if (count == 0) return KZG_OK;
+    hipLaunchKernelGGL(k_mask_refused_weights, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, d_weights, d_status, (uint32_t)count);
+    KZG_HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
 }
 
 }  // namespace kzg

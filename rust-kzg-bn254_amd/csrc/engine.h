@@ -363,8 +363,14 @@ int32_t coset_interpolate_rlc_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* 
 // per non-empty group the XYZZ wire words of sum r_i pi_i and sum (r_i C_{c_i} + r_i w^(k_i l) pi_i) -> out_xyzz, 2 x 16 u64 each (synchronised)
 int32_t locate_upload_plan(kzg_ctx* ctx, const LocatePlan& plan);
 int32_t coset_group_coeffs_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, const LocatePlan& plan, size_t n, size_t l);
+// its two halves, for a caller that sums the SAME items under more than one plan (kzg_retrieve_blobs_bytes_tolerant): the per-item rows
+// r_i w^(-k_i t) IFFT_l(ys_i)_t over d_ys, which do not depend on the partition (transformed: l > 1024 and d_ys already holds IFFT_l(ys_i), as
+// coset_interpolate_rlc_device leaves it), then the segment sums of a plan (which may cover a subset of the items) -> ctx->ml[0].  Enqueued.
+int32_t coset_item_rows_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, size_t count, size_t n, size_t l, bool transformed);
+int32_t coset_seg_sums_device(kzg_ctx* ctx, const uint4* d_rows, const LocatePlan& plan, size_t l);
+// n_proofs: the proofs in front of the commitments in d_points (0: plan.count, a plan over all items; a subset plan names items below n_proofs)
 int32_t locate_point_sums_device(kzg_ctx* ctx, const uint4* d_points, const uint64_t* d_ci, const uint4* d_w, const uint4* d_w2, const LocatePlan& plan,
-                                 uint64_t* out_xyzz);
+                                 uint64_t* out_xyzz, size_t n_proofs = 0);
 // the one-sum form (the header batch): per non-empty group the XYZZ wire words (16 u64) of sum [w_i] P_i over plan.count device-format points and
 // wire weights in the caller's order; the plan uploaded by locate_upload_plan (synchronised)
 int32_t locate_group_sums_g1_device(kzg_ctx* ctx, const uint4* d_points, const uint4* d_w, const LocatePlan& plan, uint64_t* out_xyzz);
@@ -388,7 +394,14 @@ int32_t coset_r_powers_device_bytes(kzg_ctx* ctx, const uint8_t* commitments_be,
 // leave in the device format of curve.h (d_points, and a second copy at d_points_copy when that is not null) or, with wire_points, as wire points
 // with one identity byte each (d_inf); values leave as wire scalars.  bad[a] = index << 2 | kind (G1_BAD_* of g1_decode.h; 0 for a value >= r) of
 // the SMALLEST refused index of array a (0 commitments, 1 proofs, 2 values), or 0xFFFFFFFF.
+// item_status (the tolerant retriever): refused proofs ([1]) and values do NOT reach bad[1] / bad[2]; every item gets a word of COSET_ITEM_* bits
+// instead (d_status, behind the bad words in cb[1]; `status` on the host after the collect), values_per_item values to an item.
+constexpr uint32_t COSET_ITEM_PROOF_BYTES = 1, COSET_ITEM_PROOF_OFF_CURVE = 2, COSET_ITEM_VALUE = 4;
 struct CosetBytesDecode {
+    bool item_status = false;
+    size_t values_per_item = 1;                         // a power of two
+    uint32_t* d_status = nullptr;                       // (set by the enqueue)
+    std::vector<uint32_t> status;                       // (set by the collect)
     const uint8_t* points_be[2] = {nullptr, nullptr};
     size_t n_points[2] = {0, 0};
     uint4* d_points[2] = {nullptr, nullptr};
@@ -409,6 +422,8 @@ int32_t coset_bytes_collect(kzg_ctx* ctx, CosetBytesDecode* job);    // drains t
 // the status of a bad word (KZG_OK for 0xFFFFFFFF): KZG_ERR_DESERIALIZE / KZG_ERR_NOT_ON_CURVE, the element's index / per_item to *bad_index (may be
 // null), a line with the array's name for kzg_ctx_last_error
 int32_t coset_bytes_status(kzg_ctx* ctx, const char* who, const char* array, uint32_t bad_word, size_t per_item, uint64_t* bad_index);
+// d_weights[i] = 0 for every item whose status word is not zero (enqueued on ctx->stream)
+int32_t coset_mask_refused_weights(kzg_ctx* ctx, uint4* d_weights, const uint32_t* d_status, size_t count);
 // Serialized blob headers decoded on the device (headerbytes.hip).  Called under ctx->mu with the device set and slot 0 idle; count <= 2^20.  Per
 // header 32 B of gnark-compressed commitment and 64 B each of length commitment and length proof (g2_decode.h's format and the identity 0x40 || 63
 // zeros), staged through ONE ByteStager (byte_stager.h) into ws.bases_wire (G2) and ctx->cb[1] (G1), where they stay.  The G2 elements

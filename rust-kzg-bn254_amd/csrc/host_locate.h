@@ -63,6 +63,17 @@ inline int32_t locate_plan(const uint64_t* group_indices, size_t count, size_t n
     return KZG_OK;
 }
 
+// The plan over a SUBSET of the items (the second level of kzg_retrieve_blobs_bytes_tolerant: the items of the bad blobs only).  Chosen item
+// j is items[j] (an item of the call, any order, none twice) in group groups[j] < n_groups.  The plan has n_sel lanes -- count, offsets, segments
+// and partial slots are those of locate_plan over the n_sel group indices -- and perm names the ITEMS, so the kernels, which read values, weights
+// and points through perm, touch the chosen items only.  n_sel = 0 gives a plan without segments: nothing to launch.
+inline int32_t locate_subset_plan(const uint32_t* items, const uint64_t* groups, size_t n_sel, size_t n_groups, LocatePlan* plan) {
+    const int32_t rc = locate_plan(groups, n_sel, n_groups, plan);
+    if (rc != KZG_OK) return rc;
+    for (uint32_t& p : plan->perm) p = items[p];
+    return KZG_OK;
+}
+
 // ceil(log2 n) for n >= 1
 inline unsigned locate_log2_ceil(size_t n) {
     unsigned k = 0;

@@ -205,6 +205,10 @@ struct RecoverBatchPlan {
     // partial patterns x splits x 9 x 2 m.  rows = patterns = 1 with one index row, else `group`.
     size_t w_item = 0, w_pat = 0, w_miss = 0, w_flag = 0, w_zdom = 0, w_zsinv = 0, w_part = 0, w_end = 0;
     size_t blob_pattern(size_t b) const { return pattern_of[index_rows == 1 ? 0 : b]; }
+    // the items a blob HOLDS where the values lie (the stride between two blobs' values is held x l); 0: count, every held item is used.
+    // recover_selected_plan sets it: count of the held items are used and item_of names positions below held
+    size_t held = 0;
+    size_t value_stride() const { return held ? held : count; }
 };
 
 inline void recover_batch_layout(RecoverBatchPlan* p) {
@@ -297,6 +301,90 @@ inline size_t recover_batch_stage(const RecoverBatchPlan& p, size_t b0, size_t g
     }
     *words = p.w_miss + P * p.n_missing;
     return P;
+}
+
+// ---- kzg_retrieve_blobs_bytes_tolerant: a blob HOLDS `count` chunks and is recovered from the first use_count good ones ------------------
+// The status of an item of that call (out_item_status); the decode refusals in the order the entries report them, a proof before a value
+constexpr uint8_t RETRIEVE_ITEM_GOOD = 0, RETRIEVE_ITEM_BAD_EQUATION = 1, RETRIEVE_ITEM_PROOF_BYTES = 2, RETRIEVE_ITEM_PROOF_OFF_CURVE = 3,
+                  RETRIEVE_ITEM_VALUE = 4;
+
+// The host table of the call: that of kzg_retrieve_blobs_bytes's recovery half (recover_bytes_check) in its order, with the rows that speak of
+// the cosets a blob is recovered FROM applied to use_count: 1 <= use_count <= count beside the range of count, the degree bound and out_len
+// against use_count x l, the cost cap against m - use_count missing cosets.  The held indices are checked as before (below m, distinct per row).
+inline int32_t retrieve_tolerant_check(bool any_null, const uint64_t* coset_indices, size_t index_rows, size_t blobs, size_t count, size_t use_count,
+                                       size_t n, size_t chunk_len, size_t degree_bound, bool eval_form, size_t out_len) {
+    if (any_null || blobs == 0) return KZG_ERR_INVALID_ARG;
+    if (index_rows != 1 && index_rows != blobs) return KZG_ERR_INVALID_ARG;
+    const int32_t rc = recover_shape_check(count, n, chunk_len);
+    if (rc != KZG_OK) return rc;
+    if (use_count == 0 || use_count > count) return KZG_ERR_INVALID_ARG;
+    const size_t l = chunk_len, m = n / l;
+    std::vector<uint64_t> seen((m + 63) / 64);
+    for (size_t r = 0; r < index_rows; ++r) {
+        std::fill(seen.begin(), seen.end(), 0);
+        for (size_t i = 0; i < count; ++i) {
+            const uint64_t k = coset_indices[r * count + i];
+            if (k >= m) return KZG_ERR_INVALID_ARG;
+            uint64_t& word = seen[k >> 6];
+            const uint64_t bit = (uint64_t)1 << (k & 63);
+            if (word & bit) return KZG_ERR_INVALID_ARG;
+            word |= bit;
+        }
+    }
+    if (degree_bound > use_count * l) return KZG_ERR_INVALID_ARG;
+    const size_t bound = degree_bound ? degree_bound : use_count * l;
+    if (out_len != 0 && (eval_form ? out_len != n : (out_len < bound || out_len > n))) return KZG_ERR_INVALID_ARG;
+    const int32_t rs = recover_batch_size_check(blobs, use_count, n, l);
+    if (rs != KZG_OK) return rs;
+    if (blobs > RECOVER_BYTES_MAX_VALUES / (count * l)) return KZG_ERR_TOO_LARGE;
+    return KZG_OK;
+}
+
+// The choice: blob b is recovered from its first use_count items of status RETRIEVE_ITEM_GOOD, in item order.  chosen: blobs x use_count
+// positions below count, ascending per blob; blob_status[b] = 1 and the positions 0 .. use_count - 1 (never read: recover_selected_plan gives
+// such a blob an empty item map) when the blob has fewer.  Returns the number of blobs that are not recovered.
+inline size_t retrieve_choose(const uint8_t* item_status, size_t blobs, size_t count, size_t use_count, std::vector<uint32_t>* chosen,
+                              std::vector<uint8_t>* blob_status) {
+    chosen->resize(blobs * use_count);
+    blob_status->assign(blobs, 0);
+    size_t unrecovered = 0;
+    for (size_t b = 0; b < blobs; ++b) {
+        uint32_t* row = chosen->data() + b * use_count;
+        size_t got = 0;
+        for (size_t j = 0; j < count && got < use_count; ++j)
+            if (item_status[b * count + j] == RETRIEVE_ITEM_GOOD) row[got++] = (uint32_t)j;
+        if (got < use_count) {
+            for (size_t j = 0; j < use_count; ++j) row[j] = (uint32_t)j;
+            (*blob_status)[b] = 1;
+            ++unrecovered;
+        }
+    }
+    return unrecovered;
+}
+
+// The plan of the recovery from the chosen items, the values staying where the verifier's front end left them: `count` items per blob are held
+// (plan.held), use_count of them are used (plan.count).  Patterns, missing lists, grouping and layout are those of recover_batch_plan on the
+// chosen cosets as its rows; item_of names the position of a coset's item in the HELD layout, which is what k_recover_scatter indexes.  A blob
+// of blob_status 1 gets an item map without items: no value of it is read, its work row is zero (the caller reports the zero row and flag 0).
+// One index row for all blobs, every blob recovered and every blob with the same choice is planned as ONE row, as recover_batch_plan would be
+// given it: one pattern, one upload, later groups reuse the first group's vanishing values.
+inline void recover_selected_plan(const uint64_t* coset_indices, size_t index_rows, size_t blobs, size_t count, size_t use_count, const uint32_t* chosen,
+                                  const uint8_t* blob_status, size_t n, size_t chunk_len, size_t degree_bound, bool eval_form, size_t out_len, size_t group_bytes,
+                                  RecoverBatchPlan* plan) {
+    bool one_row = index_rows == 1;
+    for (size_t b = 0; b < blobs && one_row; ++b)
+        one_row = !blob_status[b] && std::equal(chosen, chosen + use_count, chosen + b * use_count);
+    const size_t rows = one_row ? 1 : blobs;
+    std::vector<uint64_t> cosets(rows * use_count);
+    for (size_t r = 0; r < rows; ++r)
+        for (size_t j = 0; j < use_count; ++j) cosets[r * use_count + j] = coset_indices[(index_rows == 1 ? 0 : r) * count + chosen[r * use_count + j]];
+    recover_batch_plan(cosets.data(), rows, blobs, use_count, n, chunk_len, degree_bound, eval_form, out_len, group_bytes, plan);
+    plan->held = count;
+    const size_t m = plan->m;
+    for (size_t r = 0; r < rows; ++r) {
+        uint32_t* item_of = plan->item_of.data() + r * m;
+        for (size_t j = 0; j < use_count; ++j) item_of[cosets[r * use_count + j]] = blob_status[r] ? RECOVER_NO_ITEM : chosen[r * use_count + j];
+    }
 }
 
 }  // namespace kzg

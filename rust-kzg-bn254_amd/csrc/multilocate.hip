@@ -214,16 +214,23 @@ int32_t locate_upload_plan(kzg_ctx* ctx, const LocatePlan& plan) {
 // locate_upload_plan -> ctx->ml[0]: segs x l canonical wire coefficients A_{g,t}, segment-major.  count > 0.
 int32_t coset_group_coeffs_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, const LocatePlan& plan, size_t n, size_t l) {
     RoctxRange range("kzg:coset_group_coeffs");
+    const int32_t rc = coset_item_rows_device(ctx, d_ys, d_ks, d_weights, plan.count, n, l, false);
+    return rc != KZG_OK ? rc : coset_seg_sums_device(ctx, d_ys, plan, l);
+}
+
+// The first half: row i of d_ys, the l wire values of item i, becomes r_i w^(-k_i t) IFFT_l(ys_i)_t, canonical wire words.  The rows depend on
+// the items alone, not on how a plan groups them.  transformed (l > 1024 only): d_ys already holds IFFT_l(ys_i), 1 / l included -- what the
+// ntt_run per coset of coset_interpolate_rlc_device leaves when the batch equation has run over the same buffer; the loop below makes the same
+// calls, so only the twist is left to do.  count > 0.
+int32_t coset_item_rows_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, size_t count, size_t n, size_t l, bool transformed) {
     hipStream_t st = ctx->stream;
-    const size_t count = plan.count, S = plan.segs.size();
     const int log_n = __builtin_ctzll(n), log_l = __builtin_ctzll(l);
     NttTables nt;
     int32_t rc = ntt_get_tables(ctx, log_n, true, &nt);
     if (rc != KZG_OK) return rc;
     MvTables tb{nt.lo, nt.hi, nt.lo_len, nt.hi_len, nt.lo_bits};
-    KZG_HIP_TRY(ctx, ctx->ml[0].reserve(S * l * 32));
     if (l > MV_LDS_MAX_L) {
-        for (size_t i = 0; i < count; ++i) {
+        for (size_t i = 0; i < count && !transformed; ++i) {
             rc = ntt_run(ctx, d_ys + 2 * i * l, l, true, st, &ctx->mv_ntt);
             if (rc != KZG_OK) return rc;
         }
@@ -240,24 +247,35 @@ int32_t coset_group_coeffs_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_k
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_coset_interp<2, true>), dim3(groups), dim3(256), lds, st, a);
     }
     KZG_HIP_TRY(ctx, hipGetLastError());
+    return KZG_OK;
+}
+
+// The second half: the rows of each segment of the plan (uploaded by locate_upload_plan; perm may name a subset of the items) added up ->
+// ctx->ml[0]: segs x l canonical wire coefficients, segment-major.  plan.segs is not empty.
+int32_t coset_seg_sums_device(kzg_ctx* ctx, const uint4* d_rows, const LocatePlan& plan, size_t l) {
+    const size_t S = plan.segs.size();
+    const int log_l = __builtin_ctzll(l);
+    KZG_HIP_TRY(ctx, ctx->ml[0].reserve(S * l * 32));
     const uint32_t* d_plan = ctx->ml[1].as<uint32_t>();
     const int log_cb = std::min(log_l, 8);
-    hipLaunchKernelGGL(k_coset_seg_sum, dim3((unsigned)(S << (log_l - log_cb))), dim3(256), 0, st, d_ys, d_plan, d_plan + 2 * count, log_l, log_cb, ctx->ml[0].as<uint4>());
+    hipLaunchKernelGGL(k_coset_seg_sum, dim3((unsigned)(S << (log_l - log_cb))), dim3(256), 0, ctx->stream, d_rows, d_plan, d_plan + 2 * plan.count, log_l, log_cb, ctx->ml[0].as<uint4>());
     KZG_HIP_TRY(ctx, hipGetLastError());
     return KZG_OK;
 }
 
 // d_points: count proofs then the commitments (device format); d_ci / d_w / d_w2 per item (caller order); the plan uploaded by
 // locate_upload_plan -> out_xyzz: per segment the XYZZ wire words (16 u64 each) of sum r_i pi_i and of sum (r_i C_{c_i} + r_i w^(k_i l) pi_i).
-// Synchronised on return.  count > 0.
-int32_t locate_point_sums_device(kzg_ctx* ctx, const uint4* d_points, const uint64_t* d_ci, const uint4* d_w, const uint4* d_w2, const LocatePlan& plan, uint64_t* out_xyzz) {
+// Synchronised on return.  count > 0.  n_proofs: where the commitments begin in d_points (0: at plan.count; a plan over a subset of the items
+// has fewer lanes than there are proofs).
+int32_t locate_point_sums_device(kzg_ctx* ctx, const uint4* d_points, const uint64_t* d_ci, const uint4* d_w, const uint4* d_w2, const LocatePlan& plan, uint64_t* out_xyzz,
+                                 size_t n_proofs) {
     RoctxRange range("kzg:locate_point_sums");
     const size_t N = plan.count, S = plan.segs.size(), n_part = plan.part_off.back();
     KZG_HIP_TRY(ctx, ctx->ml[2].reserve(2 * n_part * 4 * NL * 4));
     KZG_HIP_TRY(ctx, ctx->ml[3].reserve(S * 2 * 128));
     const uint32_t* d_plan = ctx->ml[1].as<uint32_t>();
     LocateArgs a;
-    a.points = d_points; a.n_proofs = (uint32_t)N; a.count = (uint32_t)N;
+    a.points = d_points; a.n_proofs = (uint32_t)(n_proofs ? n_proofs : N); a.count = (uint32_t)N;
     a.perm = d_plan; a.seg_of = d_plan + N; a.seg_off = d_plan + 2 * N; a.part_off = d_plan + 2 * N + S + 1;
     a.ci = d_ci; a.w = d_w; a.w2 = d_w2;
     a.partial = ctx->ml[2].as<int32_t>(); a.n_part = (uint32_t)n_part;

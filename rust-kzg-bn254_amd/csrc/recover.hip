@@ -198,7 +198,7 @@ k_recover_vanish_fold(const int32_t* __restrict__ partial, uint32_t rows, uint32
 }
 
 // ---- 2. D_i = ys z(w^(l k)) on a present coset k = i mod m (entry j = i / m of its item), 0 on a missing one ------------------------------
-// Blob blockIdx.y: its count l values, its row of n work values, the item map of its index row (item_stride = 0: one row for all) and the
+// Blob blockIdx.y: its count l values (count: the items the blob HOLDS, of which the item map may use fewer), its row of n work values, the item map of its index row (item_stride = 0: one row for all) and the
 // zdom of its pattern.  BE: the values are 32-byte big-endian integers, decoded on load by the steps of fr_decode_be_to_wire; one >= r counts
 // as zero and reports its index in the call, first_value + its place in the group (< 2^28: host_recover.h), through atomicMin on the call's
 // one word.
@@ -330,7 +330,8 @@ static int32_t recover_gpow_tables(kzg_ctx* ctx, int log_n, RcPow* fwd, RcPow* i
 static int32_t recover_run_group(kzg_ctx* ctx, const RecoverBatchPlan& plan, size_t b0, size_t g, bool fresh, const NttTables& tb, const RcPow& gp,
                                  const RcPow& gpi, const RecoverIo& io, uint32_t* d_bad) {
     hipStream_t st = ctx->stream;
-    const size_t n = plan.n, l = plan.l, m = plan.m, count = plan.count, out_len = plan.out_len;
+    const size_t n = plan.n, l = plan.l, m = plan.m, out_len = plan.out_len;
+    const size_t count = plan.value_stride();                        // the items a blob holds where the values lie (plan.count of them are used)
     uint32_t* small = ctx->rc[1].as<uint32_t>();
     int32_t* zdom = ctx->rc[1].as<int32_t>() + plan.w_zdom;
     int32_t* zsinv = ctx->rc[1].as<int32_t>() + plan.w_zsinv;

@@ -689,6 +689,91 @@ def retrieve_blobs_bytes(commitments_be, coset_indices, ys_be, proofs_be, n: int
     return True, out.tobytes(), consistent.astype(bool)
 
 
+def retrieve_blobs_bytes_tolerant(commitments_be, coset_indices, ys_be, proofs_be, n: int, chunk_len: int, srs, use_count=None, g2_tau_l=None,
+                                  degree_bound=None, eval_form: bool = True, out_len=None, r_powers=None, ctx=None, return_checks=False, return_r_powers=False):
+    """The retriever's call that survives bad chunks (`kzg_retrieve_blobs_bytes_tolerant`): arguments as `retrieve_blobs_bytes`, a blob
+    holding `count` chunks of which the first `use_count` (default: count) good ones, in item order, recover it.  Returns (item_status,
+    blob_ok, polys_be, consistent): item_status (B, count) uint8 -- 0 good, 1 fails its equation, 2 proof bytes not canonical, 3 proof x
+    off the curve, 4 a value >= r; blob_ok (B,) bool, False for a blob with fewer than use_count good items (its row is zero bytes and its
+    flag False); polys_be and consistent as `KZG.recover_from_cosets_batch_bytes` gives them for the chosen chunks.  The batch equation runs
+    once; only after a reject are the bad items located, on the device-resident items, blobs first and then the items of the bad blobs.
+    A commitment that does not decode raises as in `retrieve_blobs_bytes`.  `return_checks=True` appends the number of pairing checks, `return_r_powers=True` the
+    (B * count, 4) weights used (zero at every refused item)."""
+    n, l = int(n), int(chunk_len)
+    idx = np.ascontiguousarray(coset_indices, dtype=np.uint64)
+    if l <= 0 or len(commitments_be) == 0 or len(commitments_be) % 32 != 0 or idx.ndim not in (1, 2) or idx.shape[-1] == 0:
+        raise InvalidInputLength()
+    blobs, count = len(commitments_be) // 32, int(idx.shape[-1])
+    if idx.ndim == 2 and idx.shape[0] != blobs:
+        raise GenericError("coset indices must have the shape (count,) or (B, count)")
+    if g2_tau_l is None and l != 1:
+        raise GenericError("g2_tau_l = None (consts::G2_TAU) is [tau]_2: chunks of more than one point need [tau^l]_2")
+    use = count if use_count is None else int(use_count)
+    cm = _u8_arg(commitments_be, blobs * 32, "commitments")
+    ys = _u8_arg(ys_be, blobs * count * l * 32, "values")
+    pf = _u8_arg(proofs_be, blobs * count * 32, "proofs")
+    rp = None if r_powers is None else np.ascontiguousarray(_lib.as_u64(r_powers, 0)).reshape(-1, 4)
+    if rp is not None and len(rp) != blobs * count:
+        raise GenericError("length's of the input are not the same")
+    bound = 0 if not degree_bound else int(degree_bound)
+    rows = n if not out_len else int(out_len)
+    if rows <= 0 or bound < 0 or use < 0:
+        raise GenericError("out_len is for coefficients, between the degree bound and n")
+    ctx = ctx or getattr(srs, "ctx", None) or _lib.default_context()
+    out = np.zeros(blobs * rows * 32, dtype=np.uint8)
+    consistent = np.zeros(blobs, dtype=np.int32)
+    item_status = np.zeros(blobs * count, dtype=np.uint8)
+    blob_status = np.zeros(blobs, dtype=np.uint8)
+    bad_items, unrecovered, checks, bad, arr = _lib.sz(0), _lib.sz(0), _lib.sz(0), C.c_uint64(0), _lib.i32(-1)
+    used = np.zeros((blobs * count, 4), dtype=np.uint64)
+    rc = _lib.load().kzg_retrieve_blobs_bytes_tolerant(ctx.handle, srs.handle, cm[1], _lib.ptr(idx), 1 if idx.ndim == 1 else blobs, ys[1], pf[1], blobs, count, use, n, l,
+                                                       bound, 1 if eval_form else 0, rows, None if rp is None else _lib.ptr(rp), _g2_arg(g2_tau_l),
+                                                       item_status.ctypes.data_as(_lib.u8p), blob_status.ctypes.data_as(_lib.u8p), C.byref(bad_items),
+                                                       C.byref(unrecovered), C.byref(checks), out.ctypes.data_as(_lib.u8p),
+                                                       consistent.ctypes.data_as(C.POINTER(C.c_int32)), _lib.ptr(used), C.byref(bad), C.byref(arr))
+    if rc in (_lib.ERR_DESERIALIZE, _lib.ERR_NOT_ON_CURVE):
+        helpers.raise_for_decode(rc, _ARRAYS[arr.value] if 0 <= arr.value < 3 else "element", bad.value, ctx)
+    if rc == _lib.ERR_INVALID_ARG:
+        raise GenericError("the shape, use_count, the coset indices (distinct, below n / chunk length), the degree bound or out_len is not valid, the SRS is "
+                           "not this context's monomial one, or slot 0 is in flight")
+    _raise_for(rc, ctx)
+    assert int(bad_items.value) == int((item_status != 0).sum()) and int(unrecovered.value) == int(blob_status.sum())
+    res = (item_status.reshape(blobs, count), blob_status == 0, out.tobytes(), consistent.astype(bool))
+    if return_checks:
+        res += (int(checks.value),)
+    return res + (used,) if return_r_powers else res
+
+
+def locate_bad_multiproofs_bytes(commitments_be, commitment_indices, coset_indices, ys_be, proofs_be, n: int, chunk_len: int, srs, g2_tau_l=None,
+                                 r_powers=None, ctx=None, groups="commitment", n_groups=None, return_r_powers=False):
+    """`locate_bad_multiproofs` on serialized items, the decode inside the call (`kzg_verify_multiproof_batch_locate_bytes`): the items go
+    up once as bytes and nothing decoded returns to the host.  Returns (good, pairing_checks), with `return_r_powers=True` also the weights
+    used; they are those of `locate_bad_multiproofs` on the decoded items.  DeserializationError / NotOnCurveError as
+    `verify_multiproof_batch_bytes` raises them."""
+    cm, ci, ki, ys, pf, count, l = _bytes_args(commitments_be, commitment_indices, coset_indices, ys_be, proofs_be, chunk_len)
+    if g2_tau_l is None and l != 1:
+        raise GenericError("g2_tau_l = None (consts::G2_TAU) is [tau]_2: chunks of more than one point need [tau^l]_2")
+    gi, n_groups = _group_args(groups, n_groups, ci, len(cm[0]) // 32, count)
+    ctx = ctx or getattr(srs, "ctx", None) or _lib.default_context()
+    rp = None if r_powers is None else np.ascontiguousarray(_lib.as_u64(r_powers, 0)).reshape(-1, 4)
+    if rp is not None and len(rp) != count:
+        raise GenericError("length's of the input are not the same")
+    opt = lambda a: _lib.ptr(a) if count else None                                     # noqa: E731
+    good = np.zeros(max(n_groups, 1), np.uint8)
+    out_rp = np.zeros((count, 4), dtype=np.uint64)
+    n_bad, checks, bad, arr = _lib.sz(0), _lib.sz(0), C.c_uint64(0), _lib.i32(-1)
+    rc = _lib.load().kzg_verify_multiproof_batch_locate_bytes(ctx.handle, srs.handle, cm[1], len(cm[0]) // 32, opt(ci), opt(ki), ys[1], pf[1], count, int(n), l,
+                                                              None if rp is None or count == 0 else _lib.ptr(rp), _g2_arg(g2_tau_l), opt(gi), n_groups,
+                                                              good.ctypes.data_as(_lib.u8p), C.byref(n_bad), C.byref(checks), opt(out_rp), C.byref(bad),
+                                                              C.byref(arr))
+    if rc in (_lib.ERR_DESERIALIZE, _lib.ERR_NOT_ON_CURVE):
+        helpers.raise_for_decode(rc, _ARRAYS[arr.value] if 0 <= arr.value < 3 else "element", bad.value, ctx)
+    _raise_for(rc, ctx)
+    good = good[:n_groups].astype(bool)
+    assert int(n_bad.value) == int((~good).sum())
+    return (good, int(checks.value), out_rp) if return_r_powers else (good, int(checks.value))
+
+
 # ---- locating the bad items of a rejected batch ----------------------------------------------------------------------------------
 pairings_verify = helpers.pairings_verify          # e(a1, a2) == e(b1, b2): the check of one pair of group sums against ([tau^l]_2, G2)
 
