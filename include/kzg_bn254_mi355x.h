@@ -27,7 +27,7 @@
  *   KZG_ROCTX=1                           roctx ranges around the host phases (rocprofv3 --marker-trace)
  *   KZG_NTT_TILE_LOG=10 / 11              one tile size of the Fr NTT at every transform size
  *   KZG_EXCHANGE_TIMEOUT_S, KZG_RCCL_LIB  the _rccl entries: seconds to wait for a collective (60); the RCCL to dlopen
- * Per-context settings are calls (kzg_ctx_set_msm_window, kzg_ctx_set_reduction_lanes, kzg_ctx_set_transcript_device, kzg_ctx_set_encode_group_bytes, kzg_ctx_set_recover_group_bytes).  Entry points marked MEASUREMENT ONLY below
+ * Per-context settings are calls (kzg_ctx_set_msm_window, kzg_ctx_set_reduction_lanes, kzg_ctx_set_transcript_device, kzg_ctx_set_locate_pairings, kzg_ctx_set_encode_group_bytes, kzg_ctx_set_recover_group_bytes).  Entry points marked MEASUREMENT ONLY below
  * (kzg_ctx_set_profiling, kzg_ctx_get_msm_profile*, kzg_ctx_measure_valu_rates) exist for bench.py's roofline figures; a host binding can leave them out.
  */
 #ifndef KZG_BN254_MI355X_H
@@ -795,6 +795,19 @@ int32_t kzg_coset_group_sums(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* commitm
  * choosing there is no such guarantee.
  * This entry always pays for the group sums: a caller who expects good batches calls kzg_verify_multiproof_batch first and this one
  * only after a reject.  count = 0 -> every group good, no device work, no pairing check.
+ * Pairing checks of a located batch on the DEVICE (kzg_ctx_set_locate_pairings(ctx, 1); mode 0, the default, is everything above,
+ * unchanged).  The root is still tested on the host, so a good batch costs exactly one check and no further GPU work.  After a failing
+ * root over S > 1 non-empty groups the equation e(lhs_g, [tau^l]_2) e(-rhs_g, G2) = 1 of EVERY such group is evaluated as one batch of
+ * S two-pair checks on the device (the group sums made affine with one inversion per 256; kzg_pairings_product_verify_batch's kernel),
+ * and the verdicts are out_group_ok.  A failing root over S = 1 names that group without another check.  *out_pairing_checks counts every
+ * equation evaluated, on the host or on the device: 1 if the root holds or S <= 1, else 1 + S.  kzg_retrieve_blobs_bytes_tolerant runs
+ * such a pass over the blobs and one over the decodable items of all bad blobs together: 1 (the batch equation) + on a reject
+ * [1 + blobs, or 1 for a single blob] + [1 + I, or 1 for I = 1, nothing for I = 0] for I such items.  Leaf tests are exact where the
+ * search's "a range that holds is all good" is statistical: the two modes give the same map except with the cancellation probability of
+ * csrc/host_locate.h's note 3 (two bad groups cancelling inside a range that the search tests and mode 1 never forms).  The device pass
+ * takes the time of one check per 64 x (SIMDs of the device) groups, about 24 ms (profiles/pairing_device.md), where the search pays
+ * about 0.5 ms per check and the work between them: measured, mode 1 wins from three bad chunks among 64 x 513 on and loses at one.  Header locate (variable G2 points, 3 + lengths pairs per
+ * group) keeps the host search in both modes.
  * Errors: those of kzg_coset_group_sums in its order (NULL g2_tau_l_mont with chunk_len != 1 where the batch entry reports it), then
  * g2_tau_l_mont off the twist -> KZG_ERR_G2_TAU_NOT_ON_CURVE. */
 int32_t kzg_verify_multiproof_batch_locate(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments,
@@ -985,6 +998,37 @@ int32_t kzg_verify_length_proof(const uint64_t commitment_xy[8], const uint64_t 
 /* host only: prod_k e(g1s[k], g2s[k]) == 1 (EIP-197's predicate), any count; identity inputs contribute 1.
  * G1 off the curve -> KZG_ERR_G1_NOT_ON_CURVE, G2 off the twist -> KZG_ERR_G2_TAU_NOT_ON_CURVE (every G1 input is tested first). */
 int32_t kzg_pairings_product_verify(const uint64_t* g1s_xy, const uint64_t* g2s, size_t count, int32_t* out_ok);
+/* ---- batches of pairing checks on the device (csrc/pairing.hip, csrc/pairing_dev.h, csrc/fq12.h) ----------------------------------
+ * n_checks independent instances of the predicate above in ONE launch: check i covers the pairs [pair_offsets[i], pair_offsets[i + 1])
+ * of the two arrays (pair_offsets: n_checks + 1 entries, the first 0, never decreasing), and out_ok[i] (n_checks bytes) is exactly what
+ * kzg_pairings_product_verify returns for that slice: identity inputs contribute 1, an empty slice gives 1, a check whose Miller loop
+ * meets T = +-Q in an addition step (a G2 point outside the order-r subgroup) gives 0.  One check is one lane's work: the optimal-ate
+ * Miller loop of its pairs with a shared squaring, one final exponentiation to the host's exponent, the is-one test.  The on-curve
+ * tests run on the device.  Errors, decided in this order, the first three before the context is dereferenced:
+ *   a null ctx, pair_offsets or (with n_checks > 0) output; offsets that do not start at 0 or that decrease; a null point array with pairs
+ *                                                                                   -> KZG_ERR_INVALID_ARG
+ *   n_checks > 2^20, more than 64 pairs in one check, more than 2^20 pairs in all  -> KZG_ERR_TOO_LARGE
+ *   a G1 point off the curve (every G1 input is tested first)                      -> KZG_ERR_G1_NOT_ON_CURVE
+ *   a G2 point off the twist                                                       -> KZG_ERR_G2_TAU_NOT_ON_CURVE
+ * the last two with the first such pair in *bad_index (may be NULL).  No output is written on an error.  n_checks = 0 -> KZG_OK.
+ * Synchronous; its buffers are its own (no slot is used).  A lone check takes the time of a full wave of 64 (profiles/pairing_device.md):
+ * the batch form pays from a few dozen checks on. */
+int32_t kzg_pairings_product_verify_batch(kzg_ctx* ctx, const uint64_t* g1s_xy, const uint64_t* g2s, const uint64_t* pair_offsets, size_t n_checks, uint8_t* out_ok,
+                                          uint64_t* bad_index);
+/* The same call returning the VALUE of every check: out_gt_mont = n_checks x 12 x 4 u64, the final-exponentiated product as the twelve
+ * coefficients of Fq[w] / (w^12 - 18 w^6 + 82) (csrc/host_pairing.h's flat order) in Montgomery wire words; all zero for a check with a
+ * degenerate addition step (no GT element).  Arguments and errors as above. */
+int32_t kzg_pairings_product_gt_batch(kzg_ctx* ctx, const uint64_t* g1s_xy, const uint64_t* g2s, const uint64_t* pair_offsets, size_t n_checks, uint64_t* out_gt_mont,
+                                      uint64_t* bad_index);
+/* host only: that value for ONE product of `count` pairs, computed as kzg_pairings_product_verify computes its verdict (chunks of Miller
+ * loops, one final exponentiation).  The two GT entries are the parity surface of the device pairing: equal bit for bit.  Errors as
+ * kzg_pairings_product_verify. */
+int32_t kzg_pairings_product_gt(const uint64_t* g1s_xy, const uint64_t* g2s, size_t count, uint64_t* out_gt_mont);
+/* Where the located coset verifiers (kzg_verify_multiproof_batch_locate, kzg_verify_multiproof_batch_locate_bytes,
+ * kzg_retrieve_blobs_bytes_tolerant) evaluate pairing checks after a failing root check: 0 (default) = the binary search of
+ * csrc/host_locate.h on the host, 1 = the equation of EVERY group as one batch on the device (kzg_pairings_product_verify_batch's
+ * kernel).  See "pairing checks of a located batch" at kzg_verify_multiproof_batch_locate.  Another mode -> KZG_ERR_INVALID_ARG. */
+int32_t kzg_ctx_set_locate_pairings(kzg_ctx* ctx, int32_t mode);
 /* n wire points on the device: each the identity, or on the twist AND in the order-r subgroup.  The first that is not ->
  * KZG_ERR_NOT_ON_CURVE with *bad_index (may be NULL).  n = 0 -> KZG_OK; n > 2^28 -> KZG_ERR_TOO_LARGE.  Synchronous, slot 0. */
 int32_t kzg_g2_check_subgroup(kzg_ctx* ctx, const uint64_t* g2_mont, size_t n_points, uint64_t* bad_index);

@@ -761,6 +761,18 @@ inline bool pairings_product_verify(const std::vector<G1Affine>& g1s, const std:
     detail::check(kzg_pairings_product_verify(g1s.empty() ? nullptr : g1s.data()->xy.data(), g2s.empty() ? nullptr : g2s.data()->w.data(), g1s.size(), &ok));
     return ok != 0;
 }
+// offsets.size() - 1 such checks in one launch on the device (kzg_pairings_product_verify_batch): check i covers the pairs
+// [offsets[i], offsets[i + 1]); offsets[0] = 0, never decreasing, offsets.back() = the number of pairs.  One verdict per check.
+inline std::vector<bool> pairings_product_verify_batch(const Context& ctx, const std::vector<G1Affine>& g1s, const std::vector<G2Affine>& g2s,
+                                                       const std::vector<uint64_t>& offsets) {
+    if (g1s.size() != g2s.size() || offsets.empty() || offsets.back() != g1s.size()) throw KzgError::GenericError("length's of the input are not the same");
+    const size_t n = offsets.size() - 1;
+    std::vector<uint8_t> ok(n ? n : 1, 0);
+    detail::check(kzg_pairings_product_verify_batch(ctx.handle(), g1s.empty() ? nullptr : g1s.data()->xy.data(), g2s.empty() ? nullptr : g2s.data()->w.data(), offsets.data(), n,
+                                                    ok.data(), nullptr),
+                  ctx.handle());
+    return std::vector<bool>(ok.begin(), ok.begin() + n);
+}
 // {d: [tau^(srs_order - d)]_1} for the claimed lengths in `lens`, read from a device-resident G1 SRS: the `shifts` of verify_length_proof_batch
 inline std::map<uint64_t, G1Affine> header_shifts(const SRS& srs, uint64_t srs_order, const std::vector<uint64_t>& lens) {
     std::map<uint64_t, G1Affine> out;

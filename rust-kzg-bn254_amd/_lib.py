@@ -234,6 +234,10 @@ PROTOTYPES = {
     "kzg_msm_g2_batch_info": (i32, [sz, C.c_uint32, sz, C.c_uint32, vp]),
     "kzg_verify_length_proof": (i32, [u64p, u64p, u64p, u64p, C.POINTER(i32)]),
     "kzg_pairings_product_verify": (i32, [u64p, u64p, sz, C.POINTER(i32)]),
+    "kzg_pairings_product_verify_batch": (i32, [vp, u64p, u64p, u64p, sz, u8p, u64p]),
+    "kzg_pairings_product_gt_batch": (i32, [vp, u64p, u64p, u64p, sz, u64p, u64p]),
+    "kzg_pairings_product_gt": (i32, [u64p, u64p, sz, u64p]),
+    "kzg_ctx_set_locate_pairings": (i32, [vp, i32]),
     "kzg_g2_check_subgroup": (i32, [vp, u64p, sz, C.POINTER(C.c_uint64)]),
     "kzg_compute_header_batch_weights": (i32, [u64p, u64p, u64p, u64p, sz, u64p, u64p, sz, u64p]),
     "kzg_verify_length_proof_batch": (i32, [vp, u64p, u64p, u64p, u64p, sz, u64p, u64p, sz, u64p, C.POINTER(i32), C.POINTER(C.c_uint64)]),
@@ -346,6 +350,13 @@ class Context:
         measurement hook)."""
         if load().kzg_ctx_set_transcript_device(self.handle, mode) != OK:
             raise ValueError("mode must be 0, 1 or 2")
+
+    def set_locate_pairings(self, mode=0):
+        """Where the located coset verifiers (`verifier.locate_bad_multiproofs`, `locate_bad_multiproofs_bytes`,
+        `retrieve_blobs_bytes_tolerant`) evaluate pairing checks after a failing root check: 0 (default) the host's binary search, 1 every
+        group's equation as one batch on the device (`kzg_ctx_set_locate_pairings`)."""
+        if load().kzg_ctx_set_locate_pairings(self.handle, mode) != OK:
+            raise ValueError("mode must be 0 or 1")
 
     def set_encode_group_bytes(self, nbytes=0):
         """The device-workspace budget of a group of `KZG.encode_cosets_batch` on this context, in bytes; 0 = the default (4 GiB).  A group

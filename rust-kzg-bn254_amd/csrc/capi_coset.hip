@@ -426,6 +426,61 @@ void xyzz_to_affine_many(const kzg_host::Xyzz* p, size_t count, uint64_t* out_xy
     });
 }
 
+// The located pass over the segments' pairs by the context's mode (kzg_ctx_set_locate_pairings).  Mode 0: group_search, as it always was.
+// Mode 1: the root [0, S) on the host, so that a batch whose root holds costs one check and no device work; after a failing root over more
+// than one segment EVERY segment's own equation e(L_j, [tau^l]_2) e(-R_j, G2) = 1 goes to the device as one batch (pairing.hip; the sums to
+// affine with one inversion per 256), and the verdicts are seg_ok: 1 + S checks.  A failing root over ONE segment names it without another check.
+// locked: the caller holds ctx->mu (the batch works in the context's buffers, so it is taken here otherwise).
+int32_t group_locate(kzg_ctx* ctx, bool locked, const GroupSums& gs, const kzg_host::G2& g2_tau_l, uint8_t* seg_ok, size_t* bad, size_t* checks) {
+    using namespace kzg_host;
+    if (ctx->locate_pairings.load() == 0) { *checks = group_search(gs, g2_tau_l, seg_ok, bad); return KZG_OK; }
+    const size_t S = gs.lhs.size();
+    *bad = 0; *checks = 0;
+    if (S == 0) return KZG_OK;
+    std::vector<Xyzz> sums(2 * S);                                                       // L_0 .. L_(S-1), then -R_0 .. -R_(S-1)
+    Xyzz tl = xyzz_inf(), tr = xyzz_inf();
+    for (size_t j = 0; j < S; ++j) {
+        sums[j] = gs.lhs[j];
+        sums[S + j] = gs.rhs[j];
+        sums[S + j].y = neg(sums[S + j].y);
+        tl = xyzz_add(tl, gs.lhs[j]); tr = xyzz_add(tr, gs.rhs[j]);
+    }
+    {
+        uint64_t a[8], b[8];
+        xyzz_to_affine(tl, a, nullptr);
+        xyzz_to_affine(tr, b, nullptr);
+        *checks = 1;
+        if (pairings_verify_pooled(g1_from_wire(a), g2_tau_l, g1_from_wire(b), g2_generator())) { memset(seg_ok, 1, S); return KZG_OK; }
+    }
+    if (S == 1) { seg_ok[0] = 0; *bad = 1; return KZG_OK; }
+    std::vector<uint64_t> xy(16 * S);
+    std::vector<uint8_t> inf(2 * S);
+    xyzz_to_affine_many(sums.data(), 2 * S, xy.data(), inf.data());
+    uint64_t q_tau[16], q_gen[16];
+    g2_to_wire(g2_tau_l, q_tau);
+    g2_to_wire(g2_generator(), q_gen);
+    std::unique_lock<std::mutex> lk(ctx->mu, std::defer_lock);
+    if (!locked) { lk.lock(); KZG_HIP_TRY(ctx, hipSetDevice(ctx->device)); }
+    const size_t slice = PAIRING_RUN_MAX_PAIRS / 2;                                    // two pairs per check
+    std::vector<uint64_t> g1s, g2s, offs;
+    for (size_t lo = 0; lo < S; lo += slice) {
+        const size_t m = std::min(slice, S - lo);
+        g1s.assign(16 * m, 0); g2s.resize(32 * m); offs.resize(m + 1);
+        for (size_t j = 0; j < m; ++j) {
+            if (!inf[lo + j]) memcpy(&g1s[16 * j], &xy[8 * (lo + j)], 64);
+            if (!inf[S + lo + j]) memcpy(&g1s[16 * j + 8], &xy[8 * (S + lo + j)], 64);
+            memcpy(&g2s[32 * j], q_tau, 128); memcpy(&g2s[32 * j + 16], q_gen, 128);
+            offs[j] = 2 * j;
+        }
+        offs[m] = 2 * m;
+        const int32_t rc = pairing_batch_run(ctx, g1s.data(), g2s.data(), offs.data(), m, 2 * m, seg_ok + lo, nullptr, nullptr);
+        if (rc != KZG_OK) return rc;
+    }
+    for (size_t j = 0; j < S; ++j) *bad += seg_ok[j] ? 0 : 1;
+    *checks += S;
+    return KZG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -659,7 +714,9 @@ int32_t kzg_verify_multiproof_batch_locate(kzg_ctx* ctx, kzg_srs* srs, const uin
     const size_t S = gs.plan.segs.size();
     std::vector<uint8_t> seg_ok(S, 1);
     size_t bad = 0;
-    const size_t checks = group_search(gs, g2_tau_l, seg_ok.data(), &bad);
+    size_t checks = 0;
+    rc = group_locate(ctx, false, gs, g2_tau_l, seg_ok.data(), &bad, &checks);
+    if (rc != KZG_OK) return rc;
     memset(out_group_ok, 1, n_groups);
     for (size_t j = 0; j < S; ++j) out_group_ok[gs.plan.segs[j]] = seg_ok[j];
     *out_bad_groups = bad;
@@ -706,7 +763,9 @@ int32_t kzg_verify_multiproof_batch_locate_bytes(kzg_ctx* ctx, kzg_srs* srs, con
     const size_t S = gs.plan.segs.size();
     std::vector<uint8_t> seg_ok(S, 1);
     size_t bad = 0;
-    const size_t checks = group_search(gs, g2_tau_l, seg_ok.data(), &bad);
+    size_t checks = 0;
+    rc = group_locate(ctx, false, gs, g2_tau_l, seg_ok.data(), &bad, &checks);
+    if (rc != KZG_OK) return rc;
     if (n_groups) memset(out_group_ok, 1, n_groups);
     for (size_t j = 0; j < S; ++j) out_group_ok[gs.plan.segs[j]] = seg_ok[j];
     *out_bad_groups = bad;
@@ -766,7 +825,10 @@ int32_t kzg_retrieve_blobs_bytes_tolerant(kzg_ctx* ctx, kzg_srs* srs, const uint
         if (rc != KZG_OK) return rc;
         std::vector<uint8_t> blob_ok(blobs, 1);                                          // (count > 0: every blob is a segment, segment b = blob b)
         size_t bad_blobs = 0;
-        checks += group_search(gs, g2_tau_l, blob_ok.data(), &bad_blobs);
+        size_t level_checks = 0;
+        rc = group_locate(ctx, true, gs, g2_tau_l, blob_ok.data(), &bad_blobs, &level_checks);
+        if (rc != KZG_OK) return rc;
+        checks += level_checks;
         std::vector<uint32_t> items;
         for (size_t b = 0; b < blobs; ++b)
             if (!blob_ok[b])
@@ -779,7 +841,9 @@ int32_t kzg_retrieve_blobs_bytes_tolerant(kzg_ctx* ctx, kzg_srs* srs, const uint
             if (rc != KZG_OK) return rc;
             std::vector<uint8_t> item_ok(items.size(), 1);                               // (segment j = chosen item j)
             size_t bad_items = 0;
-            checks += group_search(gs, g2_tau_l, item_ok.data(), &bad_items);
+            rc = group_locate(ctx, true, gs, g2_tau_l, item_ok.data(), &bad_items, &level_checks);
+            if (rc != KZG_OK) return rc;
+            checks += level_checks;
             for (size_t j = 0; j < items.size(); ++j) if (!item_ok[j]) status[items[j]] = RETRIEVE_ITEM_BAD_EQUATION;
         }
     }

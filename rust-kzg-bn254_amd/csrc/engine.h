@@ -148,6 +148,9 @@ struct kzg_ctx {
     kzg::NttWorkspace rc_ntt;                  // its `data` also stages the uploaded coset values (dead before the first transform) and the compacted rows of out_len < n (after the last)
     kzg::DeviceBuffer pc[4];                   // kzg_prove_cosets / kzg_coset_quotients (provecosets.hip): the referenced polynomials' coefficients | a group's quotient rows | its heads block, then its twisted remainders | its items' polynomial slots and coset indices
     kzg::NttWorkspace pc_ntt;                  // the inverse transforms of eval-form polynomials, the l-point transforms of the values
+    kzg::DeviceBuffer pr[4];                   // batched pairing checks (pairing.hip; host_pairing_batch.h PairingBatchPlan): wire points | device-format points, offsets, flags | GT words, verdicts | the constants of the device pairing
+    bool pr_consts_ready = false;              // pr[3] holds them (uploaded at the context's first batch)
+    std::atomic<int> locate_pairings{0};       // kzg_ctx_set_locate_pairings: 0 = the located coset verifiers search on the host, 1 = they evaluate every group's equation on the device
 };
 
 struct kzg_srs {
@@ -374,6 +377,12 @@ int32_t locate_point_sums_device(kzg_ctx* ctx, const uint4* d_points, const uint
 // the one-sum form (the header batch): per non-empty group the XYZZ wire words (16 u64) of sum [w_i] P_i over plan.count device-format points and
 // wire weights in the caller's order; the plan uploaded by locate_upload_plan (synchronised)
 int32_t locate_group_sums_g1_device(kzg_ctx* ctx, const uint4* d_points, const uint4* d_w, const LocatePlan& plan, uint64_t* out_xyzz);
+// batched pairing checks (pairing.hip).  Called under ctx->mu with the device set and the arguments passed through pairing_batch_check_args (host_pairing_batch.h):
+// check i is prod e(g1s[k], g2s[k]) over k in [pair_offsets[i], pair_offsets[i + 1]); out_ok: a verdict byte per check, out_gt: 48 u64 per check (the flat GT value,
+// zeros for a degenerate check); either may be null; host arrays, written only with KZG_OK.  A point off its curve: the host entry's errors, *bad_index = the pair.
+constexpr size_t PAIRING_RUN_MAX_PAIRS = (size_t)1 << 20;        // the most pairs of one call: kzg_host::PAIRING_BATCH_MAX_PAIRS (pairing.hip asserts the two agree)
+int32_t pairing_batch_run(kzg_ctx* ctx, const uint64_t* g1s_xy, const uint64_t* g2s, const uint64_t* pair_offsets, size_t n_checks, size_t total, uint8_t* out_ok,
+                          uint64_t* out_gt, uint64_t* bad_index);
 // hashing on the device (fsdevice.hip).  Called under ctx->mu with the device set.
 // count messages of row_len bytes each (host, stride row_len) -> count SHA-256 digests (host); synchronised on return
 int32_t sha256_rows_run(kzg_ctx* ctx, const uint8_t* msgs, size_t row_len, size_t count, uint8_t* out_digests);

@@ -70,6 +70,67 @@ def pairings_product_verify(g1s, g2s) -> bool:
     return bool(ok.value)
 
 
+def _pairing_batch_args(g1s, g2s, offsets):
+    p1 = np.ascontiguousarray(_lib.as_u64(g1s, 8)).reshape(-1, 8)
+    p2 = np.ascontiguousarray(_lib.as_u64(g2s, 16)).reshape(-1, 16)
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1))
+    if len(p1) != len(p2) or len(off) == 0 or int(off[-1]) != len(p1):
+        raise InvalidInputLength()
+    return p1, p2, off
+
+
+def _raise_for_pair(rc, bad, ctx):
+    if rc == _lib.ERR_G1_NOT_ON_CURVE:
+        raise NotOnCurveError("G1 point %d not on curve" % bad.value)
+    if rc == _lib.ERR_G2_TAU_NOT_ON_CURVE:
+        raise NotOnCurveError("G2 point %d not on curve" % bad.value)
+    _raise_for(rc, ctx)
+
+
+def pairings_product_verify_batch(g1s, g2s, offsets, ctx=None) -> np.ndarray:
+    """`len(offsets) - 1` independent pairing-product checks in one launch on the device (`kzg_pairings_product_verify_batch`): check i
+    covers the pairs offsets[i] .. offsets[i + 1] (offsets[0] = 0, never decreasing, offsets[-1] = the number of pairs) and entry i of the
+    returned bool array is what `pairings_product_verify` returns for that slice.  An empty slice gives True."""
+    p1, p2, off = _pairing_batch_args(g1s, g2s, offsets)
+    ctx = ctx or _lib.default_context()
+    n = len(off) - 1
+    ok = np.zeros(max(n, 1), dtype=np.uint8)
+    bad = C.c_uint64(0)
+    rc = _lib.load().kzg_pairings_product_verify_batch(ctx.handle, _lib.ptr(p1) if len(p1) else None, _lib.ptr(p2) if len(p2) else None, _lib.ptr(off), n,
+                                                       ok.ctypes.data_as(_lib.u8p), C.byref(bad))
+    _raise_for_pair(rc, bad, ctx)
+    return ok[:n].astype(bool)
+
+
+def pairings_product_gt_batch(g1s, g2s, offsets, ctx=None) -> np.ndarray:
+    """The value of every check of `pairings_product_verify_batch` (`kzg_pairings_product_gt_batch`): (n_checks, 12, 4) uint64, the
+    final-exponentiated product as twelve Montgomery coefficients in the host's flat order; zeros where the Miller loop was degenerate."""
+    p1, p2, off = _pairing_batch_args(g1s, g2s, offsets)
+    ctx = ctx or _lib.default_context()
+    n = len(off) - 1
+    gt = np.zeros((max(n, 1), 12, 4), dtype=np.uint64)
+    bad = C.c_uint64(0)
+    rc = _lib.load().kzg_pairings_product_gt_batch(ctx.handle, _lib.ptr(p1) if len(p1) else None, _lib.ptr(p2) if len(p2) else None, _lib.ptr(off), n, _lib.ptr(gt),
+                                                   C.byref(bad))
+    _raise_for_pair(rc, bad, ctx)
+    return gt[:n]
+
+
+def pairings_product_gt(g1s, g2s) -> np.ndarray:
+    """prod_k e(g1s[k], g2s[k]) as the host computes it (`kzg_pairings_product_gt`): (12, 4) uint64; the parity reference of
+    `pairings_product_gt_batch`."""
+    p1 = np.ascontiguousarray(_lib.as_u64(g1s, 8)).reshape(-1, 8)
+    p2 = np.ascontiguousarray(_lib.as_u64(g2s, 16)).reshape(-1, 16)
+    if len(p1) != len(p2):
+        raise InvalidInputLength()
+    gt = np.zeros((12, 4), dtype=np.uint64)
+    rc = _lib.load().kzg_pairings_product_gt(_lib.ptr(p1) if len(p1) else None, _lib.ptr(p2) if len(p2) else None, len(p1), _lib.ptr(gt))
+    if rc == _lib.ERR_G2_TAU_NOT_ON_CURVE:
+        raise NotOnCurveError("G2 point not on curve")
+    _raise_for(rc)
+    return gt
+
+
 def header_shifts(srs, srs_order: int, lens) -> dict:
     """{d: [tau^(srs_order - d)]_1 for d in lens}, read from a device-resident G1 SRS (`kzg_srs_download` of point srs_order - d): the
     `shifts` argument of verify_length_proof_batch.  d = srs_order gives the generator."""
