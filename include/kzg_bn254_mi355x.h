@@ -602,6 +602,50 @@ int32_t kzg_commit_and_prove_blob(kzg_ctx* ctx, const kzg_srs* srs, const uint8_
                                   uint64_t out_commitment_xy_mont[8], uint8_t* out_commitment_is_infinity,
                                   uint64_t out_proof_xy_mont[8], uint8_t* out_proof_is_infinity,
                                   uint64_t* out_z_mont, uint64_t* out_y_mont);
+/* ---- the batched prover: many proofs in one call (no counterpart in the reference, which proves one polynomial per call) ------------------
+ * A proof is the commitment of the quotient's evaluations over the Lagrange basis (kzg.rs:176-177), so the proofs of `count` polynomials of
+ * one length are ONE bucket problem, as the commitments of kzg_commit_eval_form_batch are; in front of it one fused kernel (one workgroup per
+ * polynomial of up to 2^12 evaluations) computes y = f(z) and the quotient row with one inversion per polynomial, z on the domain included
+ * (kzg.rs:237-260 without a search for the index: the lane that meets the zero denominator knows it).  Polynomials of more than 2^12
+ * evaluations take the single-proof path inside the call.  The SRS handle is not const: the Lagrange basis of each length and its per-bit
+ * tables are attached on first use, as for the batched commitments.  SLOTS: the batched MSM runs on the context's slots; a kzg_*_begin in
+ * flight gives KZG_ERR_INVALID_ARG.  The work goes through GROUPS of rows whose device workspace fits kzg_ctx_set_prove_group_bytes
+ * (0 = 256 MiB; a group is never smaller than one row); the results do not depend on it.
+ *
+ * kzg_compute_proof_batch: KZG::compute_proof (kzg.rs:128-178, :215-234, :237-260) for row b of evals_mont (count x n wire elements) at
+ * zs_mont[b]: out_proofs_xy_mont[b] (8 words; the identity as zeros with out_is_infinity[b] = 1) and out_ys_mont[b] = f_b(z_b) equal
+ * kzg_compute_proof on that row, bit for bit.  out_is_infinity and out_ys_mont may be NULL.  There is NO n_roots argument: the roots-length
+ * check of kzg.rs:135-139 has no batch counterpart (the domain is the canonical one of n points).  Checks, in this order: a null handle, an
+ * SRS of another context, out_proofs_xy_mont NULL: KZG_ERR_INVALID_ARG; count = 0: KZG_OK, nothing written; evals_mont or zs_mont NULL:
+ * KZG_ERR_INVALID_ARG; n = 0 or no power of two: KZG_ERR_INVALID_INPUT_LENGTH (helpers.rs:485-487); n > 2^28 or count x n > 2^40:
+ * KZG_ERR_TOO_LARGE; n > the SRS: KZG_ERR_SRS_CAPACITY_EXCEEDED (kzg.rs:89-94).  _device: the evaluations are resident (complete before the call). */
+int32_t kzg_compute_proof_batch(kzg_ctx* ctx, kzg_srs* srs, const uint64_t* evals_mont, size_t n, size_t count, const uint64_t* zs_mont,
+                                uint64_t* out_proofs_xy_mont, uint8_t* out_is_infinity, uint64_t* out_ys_mont);
+int32_t kzg_compute_proof_batch_device(kzg_ctx* ctx, kzg_srs* srs, const void* d_evals_mont, size_t n, size_t count, const uint64_t* zs_mont,
+                                       uint64_t* out_proofs_xy_mont, uint8_t* out_is_infinity, uint64_t* out_ys_mont);
+/* kzg_compute_blob_proof_batch: KZG::compute_blob_proof (kzg.rs:288-309) for `count` blobs of any mix of lengths: blob b is blob_lens[b] bytes
+ * at blobs[b] with the commitment commitments_xy_mont[b].  Row b of every output equals kzg_compute_blob_proof on blob b (with the roots of its
+ * own padded length), bit for bit; out_is_infinity, out_zs_mont, out_ys_mont may be NULL.  The blobs are sorted into length classes (one per
+ * log2 of the padded length); per class and group the bytes go up once, bytes -> Fr (helpers::to_fr_array) runs on the device beside the
+ * transcripts on the host pool (exactly helpers::compute_challenge's bytes, helpers.rs:411-455), then the fused kernel and the batched MSM.
+ * ERRORS are those of the single call, checked per blob BEFORE any device work in this order: a length without bytes KZG_ERR_INVALID_ARG;
+ * more than 2^28 elements KZG_ERR_TOO_LARGE (polynomial.rs:42-46); a commitment off the curve KZG_ERR_G1_NOT_ON_CURVE (kzg.rs:295); an empty
+ * blob KZG_ERR_ZERO_LENGTH (helpers.rs:554-558: no roots of unity exist for it, where the single call compares lengths, kzg.rs:135-139); a
+ * padded length beyond the SRS KZG_ERR_SRS_CAPACITY_EXCEEDED (kzg.rs:89-94).  The call returns the status of the FIRST failing blob in index
+ * order and writes its index to *out_bad_index (may be NULL; untouched on success).  In front of them: a null handle, an SRS of another
+ * context, out_proofs_xy_mont NULL: KZG_ERR_INVALID_ARG; count = 0: KZG_OK, nothing written; blobs, blob_lens or commitments_xy_mont NULL:
+ * KZG_ERR_INVALID_ARG. */
+int32_t kzg_compute_blob_proof_batch(kzg_ctx* ctx, kzg_srs* srs, const uint8_t* const* blobs, const size_t* blob_lens, const uint64_t* commitments_xy_mont,
+                                     size_t count, uint64_t* out_proofs_xy_mont, uint8_t* out_is_infinity, uint64_t* out_zs_mont, uint64_t* out_ys_mont,
+                                     size_t* out_bad_index);
+/* kzg_commit_and_prove_blob_batch: the same with the commitments computed by the call (KZG::commit_blob, kzg.rs:182-185, as one batched MSM
+ * per group over the same Lagrange basis, then kzg.rs:288-309): row b equals kzg_commit_and_prove_blob on blob b, bit for bit.
+ * out_commitments_xy_mont (count x 8) is required; out_commitment_is_infinity and the optional outputs above may be NULL. */
+int32_t kzg_commit_and_prove_blob_batch(kzg_ctx* ctx, kzg_srs* srs, const uint8_t* const* blobs, const size_t* blob_lens, size_t count,
+                                        uint64_t* out_commitments_xy_mont, uint8_t* out_commitment_is_infinity, uint64_t* out_proofs_xy_mont,
+                                        uint8_t* out_proof_is_infinity, uint64_t* out_zs_mont, uint64_t* out_ys_mont, size_t* out_bad_index);
+/* the device-workspace budget of a group of the batched prover, in bytes; 0 = the default (256 MiB) */
+int32_t kzg_ctx_set_prove_group_bytes(kzg_ctx* ctx, size_t bytes);
 /* The same as a STREAM (round 6): KZG::commit_blob + KZG::compute_blob_proof (kzg.rs:182-185, :288-309) of many blobs with up to
  * KZG_BLOB_JOBS of them in flight per context.  One call above is bound by ITS transcript -- SHA-256 over the whole blob is one
  * sequential stream, 14-15 ms per 32 MiB on a core with SHA extensions, against ~2.9 ms of GPU work -- but the transcripts of different

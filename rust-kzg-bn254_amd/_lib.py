@@ -269,6 +269,11 @@ PROTOTYPES = {
     "kzg_encode_cosets_batch_bytes": (i32, [vp, vp, u8p, sz, sz, i32, sz, sz, u8p, u8p, u8p, C.POINTER(C.c_uint64)]),
     "kzg_disperse_blobs_bytes": (i32, [vp, vp, vp, vp, C.c_uint64, C.c_uint64, u8p, sz, sz, sz, sz, C.c_uint64, u8p, u8p, u8p, u8p, u8p,
                                        C.POINTER(C.c_uint64)]),
+    "kzg_compute_proof_batch": (i32, [vp, vp, u64p, sz, sz, u64p, u64p, u8p, u64p]),
+    "kzg_compute_proof_batch_device": (i32, [vp, vp, vp, sz, sz, u64p, u64p, u8p, u64p]),
+    "kzg_compute_blob_proof_batch": (i32, [vp, vp, C.POINTER(C.c_char_p), C.POINTER(sz), u64p, sz, u64p, u8p, u64p, u64p, C.POINTER(sz)]),
+    "kzg_commit_and_prove_blob_batch": (i32, [vp, vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, u64p, u8p, u64p, u8p, u64p, u64p, C.POINTER(sz)]),
+    "kzg_ctx_set_prove_group_bytes": (i32, [vp, sz]),
 }
 
 _lib = None
@@ -368,6 +373,13 @@ class Context:
         """The device-workspace budget of a group of `KZG.recover_from_cosets_batch` on this context, in bytes; 0 = the default (4 GiB).
         A group is never smaller than one blob (same results whatever the budget; `helpers.recover_batch_info` tells the grouping)."""
         if nbytes < 0 or load().kzg_ctx_set_recover_group_bytes(self.handle, int(nbytes)) != OK:
+            raise ValueError("the budget is a byte count >= 0")
+
+    def set_prove_group_bytes(self, nbytes=0):
+        """The device-workspace budget of a group of rows of the batched prover (`KZG.compute_proof_batch`, `compute_blob_proof_batch`,
+        `commit_and_prove_blob_batch`) on this context, in bytes; 0 = the default (256 MiB).  A group is never smaller than one row (same
+        results whatever the budget)."""
+        if nbytes < 0 or load().kzg_ctx_set_prove_group_bytes(self.handle, int(nbytes)) != OK:
             raise ValueError("the budget is a byte count >= 0")
 
     def set_g2_batch_group(self, max_blobs=0):

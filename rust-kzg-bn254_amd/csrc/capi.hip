@@ -369,6 +369,7 @@ void kzg_ctx_destroy(kzg_ctx* ctx) {
     for (auto& b : ctx->pc) b.release();
     ctx->pc_ntt.release();
     for (auto& b : ctx->pr) b.release();
+    for (auto& b : ctx->pb) b.release();
     ctx->rccl_buf.release();
     if (ctx->rccl_pinned) { (void)hipHostFree(ctx->rccl_pinned); ctx->rccl_pinned = nullptr; ctx->rccl_pinned_bytes = 0; }
     if (ctx->vb_pinned) { (void)hipHostFree(ctx->vb_pinned); ctx->vb_pinned = nullptr; ctx->vb_pinned_bytes = 0; }

@@ -15,6 +15,7 @@
 #include "host_encode.h"   // EncodePlan
 #include "host_locate.h"   // LocatePlan
 #include "host_prove_cosets.h"   // ProveCosetsPlan
+#include "host_prove_batch.h"    // ProveBatchPlan, the group budget
 
 namespace kzg_host { struct G1; struct G2; }   // host_pairing.h
 namespace kzg {
@@ -150,6 +151,8 @@ struct kzg_ctx {
     kzg::NttWorkspace pc_ntt;                  // the inverse transforms of eval-form polynomials, the l-point transforms of the values
     kzg::DeviceBuffer pr[4];                   // batched pairing checks (pairing.hip; host_pairing_batch.h PairingBatchPlan): wire points | device-format points, offsets, flags | GT words, verdicts | the constants of the device pairing
     bool pr_consts_ready = false;              // pr[3] holds them (uploaded at the context's first batch)
+    kzg::DeviceBuffer pb[4];                   // the batched prover (provebatch.hip), for a group of one length class: packed blob bytes, descriptors | rows of evaluations | quotient rows | zs, ys, prep records
+    size_t prove_group_bytes = 0;              // kzg_ctx_set_prove_group_bytes: the workspace budget of such a group, 0 = PROVE_GROUP_BYTES_DEFAULT (host_prove_batch.h)
     std::atomic<int> locate_pairings{0};       // kzg_ctx_set_locate_pairings: 0 = the located coset verifiers search on the host, 1 = they evaluate every group's equation on the device
 };
 
@@ -496,6 +499,14 @@ int32_t vb_evaluate_setup(kzg_ctx* ctx, size_t packed_len, size_t nb);
 int32_t vb_evaluate_enqueue(kzg_ctx* ctx, const uint8_t* packed, const VbBlob* meta, size_t nb, size_t b0, size_t b1, const uint64_t* zs,
                             uint8_t* small_pinned);
 int32_t vb_evaluate_finish(kzg_ctx* ctx, size_t nb, uint64_t* ys_out, uint8_t* fallback_out);
+// the batched prover (provebatch.hip), one launch sequence per group of rows of one length class n = 2^log_n <= 2^PROVE_BATCH_MAX_LOG; the caller holds
+// ctx->mu, has set the device and found every slot idle.  prove_batch_rows_from_bytes: `rows` blobs packed in host memory (blob r at meta[r].off, 32-byte
+// aligned, zero-filled to its last whole element) -> rows x n wire elements in ctx->pb[1] (helpers::to_fr_array, zero padding to n), enqueued on ctx->stream.
+// prove_batch_rows_run: rows x n wire evaluations on the device (written on ctx->stream or complete) and `rows` points (host, wire) -> y_b = f_b(z_b) and the
+// proof of every row, its quotient's commitment over `basis`, the cached Lagrange basis of n points; out_inf / out_ys may be null.
+int32_t prove_batch_rows_from_bytes(kzg_ctx* ctx, const uint8_t* packed, size_t packed_bytes, const VbBlob* meta, size_t rows, int log_n, const void** d_rows);
+int32_t prove_batch_rows_run(kzg_ctx* ctx, kzg_srs* basis, const void* d_rows, int log_n, size_t rows, const uint64_t* zs, uint64_t* out_xy, uint8_t* out_inf,
+                             uint64_t* out_ys);
 // Lagrange-sharded proofs (lagrange.hip; the host folds lag_fold_y / lag_fold_proof: host_lagrange.h)
 int32_t lag_begin(kzg_ctx* ctx, const kzg_srs* shard, size_t base, const void* evals, bool on_device, size_t len, size_t n, const uint64_t z[4], int slot, int commit_slot);
 int32_t lag_partial_y(kzg_ctx* ctx, int slot, uint64_t out[8]);

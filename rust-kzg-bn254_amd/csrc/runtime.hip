@@ -76,7 +76,7 @@ void host_parallel_for(size_t n, const std::function<void(size_t)>& job) { kzg_h
 KZG_BOUND_CHECK_EXPORTS(runtime)
 // The variant library's totals over every translation unit: counts[site] summed, first[site] = the operand limbs kept by the first
 // translation unit (in the order below) whose counter of that site fired.  Not declared in include/kzg_bn254_mi355x.h.
-#define KZG_BC_UNITS(X) X(msm) X(ntt) X(poly) X(vbeval) X(lagrange) X(srs) X(g1fft) X(capi) X(capi_srs) X(capi_verify) X(capi_coset) X(runtime) X(blobstream) X(multi) X(ubench) X(multiproof) X(multiverify) X(multilocate) X(recover) X(g2msm) X(g2batch) X(g2decode) X(capi_g2) X(fsdevice) X(cosetbytes) X(capi_bytes) X(provecosets) X(capi_prove) X(pairing)
+#define KZG_BC_UNITS(X) X(msm) X(ntt) X(poly) X(vbeval) X(lagrange) X(srs) X(g1fft) X(capi) X(capi_srs) X(capi_verify) X(capi_coset) X(runtime) X(blobstream) X(multi) X(ubench) X(multiproof) X(multiverify) X(multilocate) X(recover) X(g2msm) X(g2batch) X(g2decode) X(capi_g2) X(fsdevice) X(cosetbytes) X(capi_bytes) X(provecosets) X(capi_prove) X(pairing) X(provebatch) X(capi_provebatch)
 #define KZG_BC_DECLARE(name) extern "C" int kzg_bc_read_##name(unsigned long long*, int32_t*); extern "C" int kzg_bc_reset_##name();
 KZG_BC_UNITS(KZG_BC_DECLARE)
 extern "C" int kzg_bc_sites() { return kzg::KZG_SITES; }

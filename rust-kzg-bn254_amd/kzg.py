@@ -1017,6 +1017,80 @@ class KZG:
         self._raise_proof_status(ctx, rc, blob, srs)
         return com, out, z, y
 
+    # ---- the batched prover: many proofs in one call (no counterpart in the reference; same values as that many single calls) ----------
+    def compute_proof_batch(self, polynomials, zs, srs, want_y=False):
+        """`compute_proof` of every (polynomial, z) pair in ONE call (`kzg_compute_proof_batch`): `polynomials` is a list of
+        PolynomialEvalForm of one length n (or a (count, n, 4) array of wire evaluations), `zs` one point per polynomial.  Returns a
+        (count, 8) array of wire points (the identity as zeros), row b bit-identical to `compute_proof(polynomials[b], zs[b], srs)` on a
+        KZG whose roots have that length; with want_y also the (count, 4) values f_b(z_b).  One fused kernel computes the values and the
+        quotients (one workgroup per polynomial of up to 4 096 evaluations, points on the domain included), one batched MSM the proofs."""
+        if isinstance(polynomials, np.ndarray):
+            if polynomials.ndim != 3 or polynomials.shape[2] != 4:
+                raise GenericError("compute_proof_batch takes a (count, n, 4) array")
+            data = np.ascontiguousarray(polynomials, dtype=np.uint64)
+            count, n = int(data.shape[0]), int(data.shape[1])
+        else:
+            rows = [_lib.as_u64(p.evaluations() if hasattr(p, "evaluations") else p, 4).reshape(-1, 4) for p in polynomials]
+            count = len(rows)
+            n = len(rows[0]) if rows else 0
+            if any(len(r) != n for r in rows):
+                raise GenericError("batched proofs need polynomials of one length")
+            data = np.ascontiguousarray(np.stack(rows), dtype=np.uint64) if count and n else np.zeros((count, 0, 4), dtype=np.uint64)
+        z = np.ascontiguousarray(np.stack([_lib.as_u64(v, 0).reshape(4) for v in zs]), dtype=np.uint64) if len(zs) else np.zeros((0, 4), dtype=np.uint64)
+        if len(z) != count:
+            raise GenericError("one point per polynomial")
+        out = np.zeros((count, 8), dtype=np.uint64); inf = np.zeros(max(count, 1), dtype=np.uint8); y = np.zeros((count, 4), dtype=np.uint64)
+        if count == 0:
+            return (out, y) if want_y else out
+        if n > len(srs):
+            raise SrsCapacityExceeded(n, len(srs))
+        ctx = self._ctx()
+        rc = _lib.load().kzg_compute_proof_batch(ctx.handle, srs.handle, _lib.ptr(data) if data.size else None, n, count, _lib.ptr(z), _lib.ptr(out),
+                                                 inf.ctypes.data_as(_lib.u8p), _lib.ptr(y))
+        if rc == _lib.ERR_SRS_CAPACITY_EXCEEDED:
+            raise SrsCapacityExceeded(n, len(srs))
+        ctx.check_device(rc)
+        if rc != _lib.OK:
+            raise GenericError(_lib.status_message(rc))
+        return (out, y) if want_y else out
+
+    def _blob_proof_batch(self, blobs, commitments, srs):
+        ctx = self._ctx()
+        blobs = list(blobs)
+        count = len(blobs)
+        ptrs, lens, keep = _lib.blob_args(blobs)
+        com = np.zeros((count, 8), dtype=np.uint64); out = np.zeros((count, 8), dtype=np.uint64); inf = np.zeros(max(count, 1), dtype=np.uint8)
+        z = np.zeros((count, 4), dtype=np.uint64); y = np.zeros((count, 4), dtype=np.uint64)
+        bad = C.c_size_t(0)
+        lib = _lib.load()
+        if commitments is None:
+            rc = lib.kzg_commit_and_prove_blob_batch(ctx.handle, srs.handle, ptrs, lens, count, _lib.ptr(com), None, _lib.ptr(out), inf.ctypes.data_as(_lib.u8p),
+                                                     _lib.ptr(z), _lib.ptr(y), C.byref(bad))
+        else:
+            rows = [_lib.as_u64(c, 0).reshape(8) for c in commitments]
+            if len(rows) != count:
+                raise GenericError("one commitment per blob")
+            com = np.ascontiguousarray(np.stack(rows), dtype=np.uint64) if count else com
+            rc = lib.kzg_compute_blob_proof_batch(ctx.handle, srs.handle, ptrs, lens, _lib.ptr(com), count, _lib.ptr(out), inf.ctypes.data_as(_lib.u8p), _lib.ptr(z),
+                                                  _lib.ptr(y), C.byref(bad))
+        del keep
+        if rc != _lib.OK:
+            self._raise_proof_status(ctx, rc, blobs[bad.value] if bad.value < count else blobs[0], srs)
+        return com, out, z, y
+
+    def compute_blob_proof_batch(self, blobs, commitments, srs, want_zy=False):
+        """`compute_blob_proof` of every (blob, commitment) pair in ONE call (`kzg_compute_blob_proof_batch`), the blobs of any mix of
+        lengths: a (count, 8) array of proofs, row b bit-identical to `compute_blob_proof(blobs[b], commitments[b], srs)`; with want_zy also
+        the (count, 4) challenges and values.  Raises what the single method raises, for the first failing blob in index order."""
+        _, out, z, y = self._blob_proof_batch(blobs, list(commitments), srs)
+        return (out, z, y) if want_zy else out
+
+    def commit_and_prove_blob_batch(self, blobs, srs):
+        """`commit_and_prove_blob` of every blob in ONE call (`kzg_commit_and_prove_blob_batch`): (commitments (count, 8), proofs (count, 8),
+        zs (count, 4), ys (count, 4)), row b bit-identical to the single method on blobs[b] -- what `verifier.verify_blob_kzg_proof_batch`
+        takes."""
+        return self._blob_proof_batch(blobs, None, srs)
+
     # the same as a stream (`kzg_commit_and_prove_blob_begin` / `_end`): up to _lib.BLOB_JOBS blobs in flight, their transcript hashes side by side
     def commit_and_prove_blob_begin(self, blob, srs, job, commitment=None):
         """Starts job `job` (0 .. BLOB_JOBS-1): the transcript prefix on a host thread of the library, upload + bytes -> Fr + commitment on the
