@@ -799,7 +799,60 @@ int32_t kzg_verify_multiproof_batch(kzg_ctx* ctx, const kzg_srs* srs, const uint
                                     const uint64_t* commitment_indices, const uint64_t* coset_indices, const uint64_t* ys_mont,
                                     const uint64_t* proofs_xy_mont, size_t count, size_t n, size_t chunk_len,
                                     const uint64_t* r_powers_mont, const uint64_t* g2_tau_l_mont, int32_t* out_ok);
-/* One proof: the batch of one item with weight 1 (ys: chunk_len x 4 u64).  Errors as above. */
+/* ---- batches of MIXED shapes: one call, one product of pairings ----------------------------------------------------------------
+ * A batch has n_classes shape classes; class s is the pair (n_s, l_s) = (class_n[s], class_chunk_len[s]) with m_s = n_s / l_s cosets and
+ * w_s the primitive n_s-th root of the library; the rules for a class are those of n / chunk_len above.  Item i has the class
+ * s_i = class_indices[i], a commitment row c_i, a coset k_i < m_{s_i}, l_{s_i} values and a proof.  Only the G2 side of the equation
+ * depends on the chunk length, and the interpolation polynomials of all shapes add into one coefficient vector:
+ *     A_t = sum_{i : l_{s_i} > t} r_i w_{s_i}^(-k_i t) IFFT_{l_{s_i}}(ys_i)_t          t < l_max          (GPU, kzg_coset_interpolate_rlc_mixed)
+ *     L_d = sum_{i : l_{s_i} = d} r_i pi_i                                             one per DISTINCT chunk length d
+ *     R   = sum_i r_i C_{c_i} - sum_t A_t [tau^t]_1 + sum_i r_i w_{s_i}^(k_i l_{s_i}) pi_i
+ *     accept <=> prod_d e(L_d, [tau^d]_2) e(-R, G2) = 1
+ * 1 + (distinct chunk lengths that have items) pairs whatever the item count; two classes of equal l and different n share a pair.  For one
+ * class this is the equation of kzg_verify_multiproof_batch (whose transcript differs: a batch of ONE shape belongs there, see README).
+ * Common arguments: class_n, class_chunk_len: n_classes u64 each; class_indices: count u64; ys_mont is RAGGED: item i's l_{s_i} values
+ * follow item i - 1's, in the caller's item order, with no padding.  Items may come in any order; classes may be empty or repeated.
+ *
+ * kzg_coset_interpolate_rlc_mixed: out = the l_max coefficients A_t with r_i = weights[i], canonical wire words; l_max is the largest
+ * class_chunk_len over ALL classes, empty ones included.  Equal inputs give equal bits whatever the item order, the class numbering or the
+ * launch geometry.  count = 0 -> zeros.  Errors, in this order: a null pointer -> KZG_ERR_INVALID_ARG; n_classes = 0 with count > 0 ->
+ * KZG_ERR_INVALID_ARG; n_classes > 512 -> KZG_ERR_TOO_LARGE; every class, in class order, by the table of kzg_coset_interpolate_rlc
+ * (KZG_ERR_NOT_POWER_OF_TWO / KZG_ERR_DOMAIN / KZG_ERR_INVALID_ARG); a class index >= n_classes or a coset index >= m_{s_i} ->
+ * KZG_ERR_INVALID_ARG; sum_i l_{s_i} > 2^28 -> KZG_ERR_TOO_LARGE. */
+int32_t kzg_coset_interpolate_rlc_mixed(kzg_ctx* ctx, const uint64_t* class_n, const uint64_t* class_chunk_len, size_t n_classes,
+                                        const uint64_t* class_indices, const uint64_t* coset_indices, const uint64_t* ys_mont,
+                                        const uint64_t* weights_mont, size_t count, uint64_t* out_coeffs_mont);
+/* The Fiat-Shamir weights [r^0 .. r^(count-1)] of a batch of mixed shapes.  Host only.  The item digest d_i is the one of
+ * kzg_compute_multiproof_r_powers over c_i, k_i, the item's OWN l_{s_i} values and its proof; then
+ *   r = SHA-256("KZGBN254_COSETMIXED__V1_" || u64be(n_classes) || n_classes x (u64be(n_s) || u64be(l_s)) || u64be(n_commitments) ||
+ *               u64be(count) || count x u64be(s_i) || n_commitments x ark-compressed C || d_0 || .. || d_(count-1)) mod r
+ * (the tag 24 bytes; encodings and the reduction as there).  count = 0 writes nothing.  A null pointer, a class index >= n_classes or a
+ * chunk length 0 -> KZG_ERR_INVALID_ARG; sum_i l_{s_i} > 2^28 -> KZG_ERR_TOO_LARGE.  Points are serialised as given, not validated. */
+int32_t kzg_compute_multiproof_r_powers_mixed(const uint64_t* commitments_xy_mont, size_t n_commitments, const uint64_t* commitment_indices,
+                                              const uint64_t* class_n, const uint64_t* class_chunk_len, size_t n_classes,
+                                              const uint64_t* class_indices, const uint64_t* coset_indices, const uint64_t* ys_mont,
+                                              const uint64_t* proofs_xy_mont, size_t count, uint64_t* out_r_powers_mont);
+/* The mixed equation above: values, indices and weights go up once in the caller's order, the interpolation kernels (one launch for the
+ * classes of l <= 512, one for l = 1024, one transform per coset above that) and a row sum leave the l_max coefficients on the device, ONE
+ * MSM over srs[0 .. l_max), one variable-base MSM per distinct chunk length over the proofs (uploaded sorted by chunk length), one over
+ * the second copy of the proofs and the commitments, and ONE pooled product of pairings on the host.  g2_tau_l_mont: n_classes G2 wire
+ * points, entry s = [tau^{l_s}]_2, checked to be on the twist (classes that have items only); never NULL (there is no consts::G2_TAU
+ * shortcut).  r_powers_mont = NULL derives the weights of kzg_compute_multiproof_r_powers_mixed on the host pool before the context is
+ * taken.  *out_ok = 1 iff the equation holds; a failed equation is *out_ok = 0 with KZG_OK.  count = 0 -> *out_ok = 1, no device work.
+ * Every chunk length kzg_verify_multiproof_batch accepts is accepted; the entry is refused while a kzg_*_begin is in flight.
+ * Errors, in this order: (1) a null pointer, srs of another context or a Lagrange-basis handle -> KZG_ERR_INVALID_ARG; (2) n_classes = 0
+ * with count > 0 -> KZG_ERR_INVALID_ARG; (3) n_classes > 512 -> KZG_ERR_TOO_LARGE; (4) every class, in class order, by the table of
+ * kzg_verify_multiproof_batch for (n, chunk_len); (5) l_max > kzg_srs_len(srs) -> KZG_ERR_SRS_CAPACITY_EXCEEDED; (6) a class index >=
+ * n_classes, a coset index >= m_{s_i} or a commitment index >= n_commitments -> KZG_ERR_INVALID_ARG; (7) sum_i l_{s_i} > 2^28 ->
+ * KZG_ERR_TOO_LARGE; (8) two classes of equal chunk length whose G2 points differ bit-wise -> KZG_ERR_INVALID_ARG; (9) a commitment or
+ * proof off the curve -> KZG_ERR_G1_NOT_ON_CURVE; (10) a G2 entry of a class that has items off the twist, in class order ->
+ * KZG_ERR_G2_TAU_NOT_ON_CURVE. */
+int32_t kzg_verify_multiproof_batch_mixed(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments,
+                                          const uint64_t* commitment_indices, const uint64_t* class_n, const uint64_t* class_chunk_len,
+                                          size_t n_classes, const uint64_t* class_indices, const uint64_t* coset_indices,
+                                          const uint64_t* ys_mont, const uint64_t* proofs_xy_mont, size_t count,
+                                          const uint64_t* r_powers_mont, const uint64_t* g2_tau_l_mont, int32_t* out_ok);
+/* One proof: the batch of one item with weight 1 (ys: chunk_len x 4 u64).  Errors as kzg_verify_multiproof_batch. */
 int32_t kzg_verify_multiproof(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t commitment_xy_mont[8], const uint64_t proof_xy_mont[8],
                               uint64_t coset_index, const uint64_t* ys_mont, size_t n, size_t chunk_len,
                               const uint64_t* g2_tau_l_mont, int32_t* out_ok);

@@ -13,4 +13,4 @@ from .polynomial import PolynomialCoeffForm, PolynomialEvalForm  # noqa: F401
 from .srs import SRS  # noqa: F401
 from .g2srs import G2SRS  # noqa: F401
 from .verifier import (verify_blob_kzg_proof, verify_blob_kzg_proof_batch, verify_length_proof, verify_length_proof_batch,  # noqa: F401
-                       verify_multiproof, verify_multiproof_batch, verify_proof)
+                       verify_multiproof, verify_multiproof_batch, verify_multiproof_batch_mixed, verify_proof)

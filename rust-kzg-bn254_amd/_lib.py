@@ -209,6 +209,9 @@ PROTOTYPES = {
     "kzg_compute_multiproof_r_powers_device": (i32, [vp, u64p, sz, u64p, u64p, u64p, u64p, sz, sz, sz, u64p]),
     "kzg_verify_multiproof_batch": (i32, [vp, vp, u64p, sz, u64p, u64p, u64p, u64p, sz, sz, sz, u64p, u64p, C.POINTER(i32)]),
     "kzg_verify_multiproof": (i32, [vp, vp, u64p, u64p, C.c_uint64, u64p, sz, sz, u64p, C.POINTER(i32)]),
+    "kzg_coset_interpolate_rlc_mixed": (i32, [vp, u64p, u64p, sz, u64p, u64p, u64p, u64p, sz, u64p]),
+    "kzg_compute_multiproof_r_powers_mixed": (i32, [u64p, sz, u64p, u64p, u64p, sz, u64p, u64p, u64p, u64p, sz, u64p]),
+    "kzg_verify_multiproof_batch_mixed": (i32, [vp, vp, u64p, sz, u64p, u64p, u64p, sz, u64p, u64p, u64p, u64p, sz, u64p, u64p, C.POINTER(i32)]),
     "kzg_coset_group_sums": (i32, [vp, vp, u64p, sz, u64p, u64p, u64p, u64p, sz, sz, sz, u64p, u64p, sz, u64p, u8p, u64p, u8p]),
     "kzg_verify_multiproof_batch_locate": (i32, [vp, vp, u64p, sz, u64p, u64p, u64p, u64p, sz, sz, sz, u64p, u64p, u64p, sz, u8p, C.POINTER(sz),
                                                  C.POINTER(sz)]),

@@ -1,7 +1,8 @@
 // capi_coset.hip — the coset-proof verifiers of the C-ABI (the proofs: kzg_compute_multiproofs): the weights of the batch transcript, the
 // interpolation entry, the batch equation on wire words and on serialized bytes (two front ends, coset_stage_words and coset_stage_bytes, leave the items
 // of a call on the device; one tail, coset_batch_tail, runs it), the retriever's call on top of the bytes front end (verify, then recover.hip on the
-// value bytes the front end left on the device), the group sums and the search for the bad groups.  Host scalars: host_coset_verify.h.
+// value bytes the front end left on the device), the group sums and the search for the bad groups, and the three entries for batches of MIXED blob
+// shapes (their own stage and tail: ragged values, a plan from host_coset_mixed.h, a product of several pairings).  Host scalars: host_coset_verify.h.
 #include "engine.h"
 #include "host_curve.h"
 #include "host_fiat_shamir.h"
@@ -19,13 +20,7 @@ using kzg_host::multiproof_r_powers_host;
 
 namespace {
 
-// the domain / chunk table of kzg_compute_multiproofs, in the documented order
-int32_t coset_domain_check(size_t n, size_t chunk_len) {
-    if (n == 0 || (n & (n - 1)) != 0) return KZG_ERR_NOT_POWER_OF_TWO;
-    if (n > ((size_t)1 << 24)) return KZG_ERR_DOMAIN;
-    if (n == 1 || chunk_len == 0 || (chunk_len & (chunk_len - 1)) != 0 || chunk_len > n / 2) return KZG_ERR_INVALID_ARG;
-    return KZG_OK;
-}
+using kzg_host::coset_domain_check;   // the domain / chunk table of kzg_compute_multiproofs, in the documented order (host_coset_mixed.h: the mixed checks run it per class)
 
 // the upload alone: values -> ctx->mv[0], weights | indices -> ctx->mv[1] (weights == nullptr: their place is left for the caller to fill on the
 // device; ys == nullptr: room only); room for the l coefficients in ctx->mv[2].  Enqueued on ctx->stream; the caller holds ctx->mu
@@ -481,6 +476,50 @@ int32_t group_locate(kzg_ctx* ctx, bool locked, const GroupSums& gs, const kzg_h
     return KZG_OK;
 }
 
+// ---- batches of mixed shapes (host_coset_mixed.h, multiverify.hip coset_interpolate_rlc_mixed_device) ----------------------------------------
+// The plan of one call and where its items lie on the device.  Values, coset indices and weights go up ONCE in the caller's order; the kernels
+// reach an item through the plan's permutation.  ctx->mv[0]: the ragged values; ctx->mv[1]: N weights | N coset indices | the plan's tables
+// (`aux`: perm | val_off | workgroup classes of the two launches | MixedClassDev per class | MixedRow per row); ctx->mv[2]: l_max coefficients.
+struct MixedStage {
+    kzg_host::MixedPlan plan;
+    std::vector<uint32_t> aux;                   // (in use until the stream is drained)
+    uint4* d_ys = nullptr; uint4* d_w = nullptr; uint64_t* d_k = nullptr;
+    MixedDevTables t{};
+};
+
+// enqueued on ctx->stream; the caller holds ctx->mu and has set the device
+int32_t mixed_upload(kzg_ctx* ctx, const uint64_t* ys, const uint64_t* coset_indices, const uint64_t* weights, MixedStage* m) {
+    const kzg_host::MixedPlan& p = m->plan;
+    const size_t N = p.count;
+    std::vector<uint32_t>& aux = m->aux;
+    aux.clear();
+    const size_t at_perm = 0, at_off = N, at_wg0 = 2 * N, at_wg1 = at_wg0 + p.wg_class[0].size(), at_cls = at_wg1 + p.wg_class[1].size(),
+                 at_rows = at_cls + 8 * p.cls.size(), words = at_rows + 2 * p.rows.size();
+    static_assert(sizeof(kzg_host::MixedClassDev) == 32 && sizeof(kzg_host::MixedRow) == 8, "the tables go up as u32 words");
+    aux.resize(words);
+    if (N) { memcpy(&aux[at_perm], p.perm.data(), N * 4); memcpy(&aux[at_off], p.val_off.data(), N * 4); }
+    if (!p.wg_class[0].empty()) memcpy(&aux[at_wg0], p.wg_class[0].data(), p.wg_class[0].size() * 4);
+    if (!p.wg_class[1].empty()) memcpy(&aux[at_wg1], p.wg_class[1].data(), p.wg_class[1].size() * 4);
+    if (!p.cls.empty()) memcpy(&aux[at_cls], p.cls.data(), p.cls.size() * 32);
+    if (!p.rows.empty()) memcpy(&aux[at_rows], p.rows.data(), p.rows.size() * 8);
+    KZG_HIP_TRY(ctx, ctx->mv[0].reserve(std::max<size_t>(p.total_values * 32, 32)));
+    KZG_HIP_TRY(ctx, ctx->mv[1].reserve(N * 40 + words * 4 + 64));
+    KZG_HIP_TRY(ctx, ctx->mv[2].reserve(std::max<size_t>(p.l_max * 32, 32)));
+    m->d_ys = ctx->mv[0].as<uint4>();
+    m->d_w = ctx->mv[1].as<uint4>();
+    m->d_k = reinterpret_cast<uint64_t*>(ctx->mv[1].as<uint8_t>() + N * 32);
+    const uint32_t* d_aux = reinterpret_cast<const uint32_t*>(ctx->mv[1].as<uint8_t>() + N * 40);
+    m->t.perm = d_aux + at_perm; m->t.val_off = d_aux + at_off; m->t.wg_class[0] = d_aux + at_wg0; m->t.wg_class[1] = d_aux + at_wg1;
+    m->t.classes = d_aux + at_cls; m->t.rows = d_aux + at_rows;
+    if (N) {
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(m->d_ys, ys, p.total_values * 32, hipMemcpyHostToDevice, ctx->stream));
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(m->d_w, weights, N * 32, hipMemcpyHostToDevice, ctx->stream));
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(m->d_k, coset_indices, N * 8, hipMemcpyHostToDevice, ctx->stream));
+        KZG_HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint32_t*>(d_aux), aux.data(), words * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return KZG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -553,6 +592,150 @@ int32_t kzg_verify_multiproof_batch(kzg_ctx* ctx, const kzg_srs* srs, const uint
                 "host scalars + proof / commitment MSMs %.3f ms, point sums + pairing %.3f ms, call %.3f ms\n", count, chunk_len, n_commitments, st.rp_path, st.ms[0], st.ms[1],
                 ms_between(t.start, t.interpolated), ms_between(t.interpolated, t.coeff_msm), ms_between(t.coeff_msm, t.point_msms), ms_between(t.point_msms, Clock::now()),
                 ms_between(t0, Clock::now()));
+    return KZG_OK;
+}
+
+// ---- batches of mixed shapes ------------------------------------------------------------------------------------------------------------
+int32_t kzg_compute_multiproof_r_powers_mixed(const uint64_t* commitments_xy_mont, size_t n_commitments, const uint64_t* commitment_indices, const uint64_t* class_n,
+                                              const uint64_t* class_chunk_len, size_t n_classes, const uint64_t* class_indices, const uint64_t* coset_indices,
+                                              const uint64_t* ys_mont, const uint64_t* proofs_xy_mont, size_t count, uint64_t* out_r_powers_mont) {
+    if (count == 0) return KZG_OK;
+    if (!commitment_indices || !class_n || !class_chunk_len || !class_indices || !coset_indices || !ys_mont || !proofs_xy_mont || !out_r_powers_mont ||
+        (n_commitments && !commitments_xy_mont))
+        return KZG_ERR_INVALID_ARG;
+    size_t total = 0;
+    for (size_t i = 0; i < count; ++i) {
+        if (class_indices[i] >= n_classes || class_chunk_len[class_indices[i]] == 0) return KZG_ERR_INVALID_ARG;
+        if (class_chunk_len[class_indices[i]] > kzg_host::MIXED_MAX_VALUES) return KZG_ERR_TOO_LARGE;
+        total += (size_t)class_chunk_len[class_indices[i]];
+        if (total > kzg_host::MIXED_MAX_VALUES) return KZG_ERR_TOO_LARGE;
+    }
+    std::vector<uint32_t> off;
+    kzg_host::mixed_value_offsets(class_chunk_len, class_indices, count, &off);
+    kzg_host::multiproof_r_powers_mixed_host(commitments_xy_mont, n_commitments, commitment_indices, class_n, class_chunk_len, n_classes, class_indices, coset_indices,
+                                             ys_mont, off.data(), proofs_xy_mont, count, out_r_powers_mont, host_parallel_for);
+    return KZG_OK;
+}
+
+int32_t kzg_coset_interpolate_rlc_mixed(kzg_ctx* ctx, const uint64_t* class_n, const uint64_t* class_chunk_len, size_t n_classes, const uint64_t* class_indices,
+                                        const uint64_t* coset_indices, const uint64_t* ys_mont, const uint64_t* weights_mont, size_t count, uint64_t* out_coeffs_mont) {
+    const bool bad = !ctx || !out_coeffs_mont || (n_classes && (!class_n || !class_chunk_len)) || (count && (!class_indices || !coset_indices || !ys_mont || !weights_mont));
+    size_t l_max = 0, total = 0;
+    int32_t rc = kzg_host::mixed_checks(bad, class_n, class_chunk_len, n_classes, SIZE_MAX, 0, nullptr, class_indices, coset_indices, count, nullptr, &l_max, &total);
+    if (rc != KZG_OK) return rc;
+    if (l_max == 0) return KZG_OK;                                                       // (no class: no coefficient)
+    MixedStage m;
+    kzg_host::mixed_plan(class_n, class_chunk_len, n_classes, class_indices, count, &m.plan);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = mixed_upload(ctx, ys_mont, coset_indices, weights_mont, &m);
+    if (rc == KZG_OK) rc = coset_interpolate_rlc_mixed_device(ctx, m.plan, m.d_ys, m.d_k, m.d_w, m.t, ctx->mv[2].as<uint4>());
+    if (rc != KZG_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }            // (the plan's tables are in flight)
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(out_coeffs_mont, ctx->mv[2].p, l_max * 32, hipMemcpyDeviceToHost, ctx->stream));
+    KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return KZG_OK;
+}
+
+// The batch equation for items of mixed shapes: class s is (n_s, l_s), item i has the class s_i.  With the weights r_i,
+//     A_t = sum_{i : l_{s_i} > t} r_i w_{s_i}^(-k_i t) IFFT_{l_{s_i}}(ys_i)_t   (t < l_max),      L_d = sum_{i : l_{s_i} = d} r_i pi_i   per DISTINCT chunk length d,
+//     R = sum_i r_i C_{c_i} - sum_t A_t [tau^t]_1 + sum_i r_i w_{s_i}^(k_i l_{s_i}) pi_i,         accept <=> prod_d e(L_d, [tau^d]_2) e(-R, G2) = 1:
+// 1 + (distinct chunk lengths that have items) pairs whatever the item count; only the G2 side depends on the chunk length.  The bases hold the
+// proofs sorted by chunk length (the plan's permutation, which is sorted by class and by length at once): each L_d is a contiguous variable-base
+// MSM, and the second copy of the proofs with the commitments behind it is ONE MSM for the two point sums of R.
+int32_t kzg_verify_multiproof_batch_mixed(kzg_ctx* ctx, const kzg_srs* srs, const uint64_t* commitments_xy_mont, size_t n_commitments, const uint64_t* commitment_indices,
+                                          const uint64_t* class_n, const uint64_t* class_chunk_len, size_t n_classes, const uint64_t* class_indices,
+                                          const uint64_t* coset_indices, const uint64_t* ys_mont, const uint64_t* proofs_xy_mont, size_t count,
+                                          const uint64_t* r_powers_mont, const uint64_t* g2_tau_l_mont, int32_t* out_ok) {
+    using namespace kzg_host;
+    const bool bad = !ctx || !srs || !out_ok || (n_classes && (!class_n || !class_chunk_len || !g2_tau_l_mont)) ||
+                     (count && (!commitments_xy_mont || !commitment_indices || !class_indices || !coset_indices || !ys_mont || !proofs_xy_mont)) ||
+                     srs->ctx != ctx || srs->lagrange_of != 0;
+    size_t l_max = 0, total = 0;
+    int32_t rc = mixed_checks(bad, class_n, class_chunk_len, n_classes, bad ? 0 : srs->n, n_commitments, commitment_indices, class_indices, coset_indices, count,
+                              g2_tau_l_mont, &l_max, &total);
+    if (rc != KZG_OK) return rc;
+    if (count == 0) { *out_ok = 1; return KZG_OK; }
+    const bool trace = opts().vb_trace != 0;
+    const auto t0 = Clock::now();
+    const size_t N = count, M = n_commitments;
+    MixedStage m;
+    mixed_plan(class_n, class_chunk_len, n_classes, class_indices, N, &m.plan);
+    const MixedPlan& p = m.plan;
+    // the G2 point of every chunk length that has items, taken from the first class of that length (the others carry the same bits); a point off the
+    // twist is reported behind an off-curve G1 point, for the first class in class order that has items
+    std::vector<G2> g2s(p.lens.size() + 1);
+    for (size_t d = 0; d < p.lens.size(); ++d) g2s[d] = g2_from_wire(g2_tau_l_mont + 16 * p.lens[d].g2_class);
+    g2s[p.lens.size()] = g2_generator();
+    bool g2_ok = true;
+    for (size_t s = 0; s < n_classes && g2_ok; ++s)
+        if (p.cls[s].count) g2_ok = g2_on_curve(g2_from_wire(g2_tau_l_mont + 16 * s));
+    // the weights: supplied, or derived on the host pool BEFORE ctx->mu is taken (threads that share a context overlap there)
+    const auto t_plan = Clock::now();
+    std::vector<uint64_t> derived;
+    if (!r_powers_mont) {
+        RoctxRange range("kzg:multiproof_verify_mixed:r_powers (host)");
+        derived.resize(4 * N);
+        multiproof_r_powers_mixed_host(commitments_xy_mont, M, commitment_indices, class_n, class_chunk_len, n_classes, class_indices, coset_indices, ys_mont,
+                                       p.val_off.data(), proofs_xy_mont, N, derived.data(), host_parallel_for);
+        r_powers_mont = derived.data();
+    }
+    const auto t_rp = Clock::now();
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    KZG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (slot0_refused(ctx, true)) return KZG_ERR_INVALID_ARG;
+    rc = mixed_upload(ctx, ys_mont, coset_indices, r_powers_mont, &m);
+    if (rc != KZG_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    // the points, validated on their way into the device format: proofs by chunk length | the same again | commitments (synchronised)
+    KZG_HIP_TRY(ctx, ctx->msm.bases.reserve((2 * N + M) * 64));
+    uint4* d_bases = ctx->msm.bases.as<uint4>();
+    {
+        std::vector<uint64_t> twice(2 * N * 8);
+        for (size_t j = 0; j < N; ++j) {
+            memcpy(twice.data() + 8 * j, proofs_xy_mont + 8 * (size_t)p.perm[j], 64);
+            memcpy(twice.data() + 8 * (N + j), proofs_xy_mont + 8 * (size_t)p.perm[j], 64);
+        }
+        rc = coset_upload_points(ctx, twice.data(), 2 * N, commitments_xy_mont, M, d_bases, d_bases + 4 * 2 * N);
+        if (rc != KZG_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    }
+    if (!g2_ok) return KZG_ERR_G2_TAU_NOT_ON_CURVE;
+    const auto t_up = Clock::now();
+    // 1. the l_max coefficients A_t (left on the device), 2. their MSM over srs[0 .. l_max)
+    rc = coset_interpolate_rlc_mixed_device(ctx, p, m.d_ys, m.d_k, m.d_w, m.t, ctx->mv[2].as<uint4>());
+    if (rc != KZG_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (trace) KZG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const auto t_interp = Clock::now();
+    uint64_t interp_xy[8];
+    uint8_t interp_inf = 0;
+    rc = msm_srs_locked(ctx, srs, 0, ctx->mv[2].p, true, l_max, interp_xy, &interp_inf, nullptr);
+    if (rc != KZG_OK) return rc;
+    const auto t_msm = Clock::now();
+    // 3. host scalars in the order of the bases, 4. one MSM per distinct chunk length over the first copy, one over the second copy and the commitments
+    std::vector<uint64_t> class_m(n_classes), scalars((2 * N + M) * 4);
+    for (size_t s = 0; s < n_classes; ++s) class_m[s] = class_n[s] / class_chunk_len[s];
+    coset_batch_scalars_mixed(class_m.data(), n_classes, class_indices, coset_indices, commitment_indices, r_powers_mont, p.perm.data(), N, M, scalars.data(),
+                              host_parallel_for);
+    KZG_HIP_TRY(ctx, ctx->msm.scalars.reserve((2 * N + M) * 32 + 32));
+    const uint4* d_scalars = ctx->msm.scalars.as<uint4>();
+    KZG_HIP_TRY(ctx, hipMemcpyAsync(ctx->msm.scalars.p, scalars.data(), (2 * N + M) * 32, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<G1> g1s(p.lens.size() + 1);
+    uint64_t sum_xy[8];
+    uint8_t inf = 0;
+    for (size_t d = 0; d < p.lens.size() && rc == KZG_OK; ++d) {
+        rc = msm_run_batch(ctx, d_bases + 4 * p.lens[d].first, d_scalars + 2 * p.lens[d].first, p.lens[d].count, 1, sum_xy, &inf);
+        if (rc == KZG_OK) g1s[d] = g1_from_wire(sum_xy);
+    }
+    if (rc == KZG_OK) rc = msm_run_batch(ctx, d_bases + 4 * N, d_scalars + 2 * N, N + M, 1, sum_xy, &inf);
+    if (rc != KZG_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }            // (`scalars` is in use until the stream is drained)
+    lk.unlock();
+    const auto t_pts = Clock::now();
+    // 5. ONE pooled product of 1 + (distinct chunk lengths) pairings
+    g1s[p.lens.size()] = g1_neg(g1_add(g1_from_wire(sum_xy), g1_neg(g1_from_wire(interp_xy))));
+    *out_ok = pairings_product_is_one(g1s.data(), g2s.data(), (int)g1s.size(), host_parallel_for) ? 1 : 0;
+    if (trace)
+        fprintf(stderr, "kzg_verify_multiproof_batch_mixed N=%zu classes=%zu lengths=%zu l_max=%zu M=%zu: r_powers%s %.3f ms, plan + upload %.3f ms, interpolation kernels %.3f ms, "
+                "coefficient MSM %.3f ms, host scalars + proof / commitment MSMs %.3f ms, point sums + pairings %.3f ms, call %.3f ms\n", N, n_classes, p.lens.size(), l_max, M,
+                derived.empty() ? " (supplied)" : " (host)", ms_between(t_plan, t_rp), ms_between(t0, t_plan) + ms_between(t_rp, t_up), ms_between(t_up, t_interp), ms_between(t_interp, t_msm),
+                ms_between(t_msm, t_pts), ms_between(t_pts, Clock::now()), ms_between(t0, Clock::now()));
     return KZG_OK;
 }
 

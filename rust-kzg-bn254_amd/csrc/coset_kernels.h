@@ -6,10 +6,12 @@
 //   SEG = true    the same weighted, twisted entry is written back per ITEM as a canonical wire word, in place of the value it came
 //                 from; nothing is summed here, so no sum can cross a segment boundary (multilocate.hip k_coset_seg_sum adds the rows
 //                 of each segment).
+// k_coset_interp_mixed, below them, is the ragged form of SEG = false: classes of different (n, l) in one launch, a workgroup per class.
 // Device code only; every lazy-reduction bound is written at its site.
 #pragma once
 #include "engine.h"
 #include "field29.h"
+#include "host_coset_mixed.h"   // the class descriptor and the limits of the ragged form (pure host header)
 
 namespace kzg {
 
@@ -212,6 +214,156 @@ constexpr uint32_t MV_MAX_GROUPS = 1024;              // workgroups of k_coset_i
 inline size_t mv_interp_lds_bytes(uint32_t E, size_t l) {
     const size_t cpt = E / l;
     return ((size_t)NL * E + (size_t)NL * cpt + (size_t)NL * (l / 2 > 1 ? l / 2 : 1) + cpt) * 4;
+}
+
+// ---- the ragged form: classes of different (n, l) in ONE launch (host_coset_mixed.h plans it; multiverify.hip launches it) ------------------
+// A workgroup serves exactly ONE class, which it finds through wg_class[blockIdx.x]; it takes that class's tiles with the stride of the
+// workgroups the class was given.  l, n, the cosets per tile, the tile count and the LDS carve-up are therefore uniform across the workgroup:
+// every __syncthreads() below has the same trip count on all lanes, and the per-lane accumulators keep one meaning across tiles, column
+// t = p & (l - 1).  Values, coset indices and weights stay in the caller's item order: slot j of the class is item perm[first + j], whose values
+// start at val_off[item].  One table set, that of the largest domain present: w_s = w_max^(n_max / n_s), so an exponent of class s is
+// shifted left by log n_max - log n_s before mv_root_pow -- for the stage twiddles and for the twist k t alike (the product k t in 64 bits
+// before it is masked, as above).
+static_assert(NL == 9, "host_coset_mixed.h sizes the LDS and the partial rows with 9 limb planes");
+static_assert(MV_MAX_GROUPS == kzg_host::MIXED_MAX_GROUPS && MV_LDS_MAX_L == kzg_host::MIXED_LDS_MAX_L, "host_coset_mixed.h plans with the limits of this file");
+struct MvMixedArgs {
+    const uint4* ys;                          // ragged: the items' values one after the other, caller's order
+    const uint64_t* ks;                       // count coset indices (< n_s / l_s, checked by the host), caller's order
+    const uint4* weights;                     // count wire weights, caller's order
+    const uint32_t* perm;                     // the items sorted by class
+    const uint32_t* val_off;                  // per item (caller's index): its first value, in elements (total <= 2^28)
+    const kzg_host::MixedClassDev* classes;   // per class
+    const uint32_t* wg_class;                 // gridDim entries: the class of each workgroup of this launch
+    int log_n_max;
+    MvTables tb;                              // inverse tables of the n_max-point domain
+    int32_t* partial;                         // plane rows: class s, workgroup g of it at row_off + g * 9 * l_s
+};
+
+// dynamic LDS, sized for the largest class of the launch and carved per class:
+// x 9 x E | scale 9 x (E / l) | stage twiddles 9 x max(l / 2, 1) | coset index E / l | value offset E / l
+template <int EPT>
+__global__ void __launch_bounds__(256)
+k_coset_interp_mixed(MvMixedArgs a) {
+    extern __shared__ int32_t mv_lds[];
+    constexpr uint32_t E = 256u * EPT;
+    const kzg_host::MixedClassDev d = a.classes[a.wg_class[blockIdx.x]];
+    const int log_l = (int)d.log_l, log_n = (int)d.log_n, up = a.log_n_max - log_n;
+    const uint32_t tid = threadIdx.x, l = 1u << log_l, cpt = E >> log_l, half = l >> 1, ntw = half ? half : 1u;
+    const uint32_t n_mask = (1u << log_n) - 1u, wg = blockIdx.x - d.wg_first;
+    int32_t* x = mv_lds;
+    int32_t* sc = x + NL * E;
+    int32_t* tw = sc + NL * cpt;
+    uint32_t* kk = reinterpret_cast<uint32_t*>(tw + NL * ntw);
+    uint32_t* vo = kk + cpt;
+    for (uint32_t q = tid; q < half; q += 256) {                    // w_l^-q = w_n^(-q m) = w_max^(-(q m) 2^up): q 2^(log n_max - log l) < n_max / 2
+        Fr w;
+        mv_root_pow(w, a.tb, q << (a.log_n_max - log_l));
+        mv_planes_store(tw, ntw, q, w);
+    }
+    Fr acc[EPT];
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) fe_set_zero(acc[e]);
+    uint32_t pending = 0;
+#pragma unroll 1
+    for (uint32_t tile = wg; tile < d.tiles; tile += d.wg_count) {
+        const uint32_t first = tile * cpt;
+        // per coset: r_i / l in internal form (zero past the end), k_i, where its values start
+        for (uint32_t c = tid; c < cpt; c += 256) {
+            const uint32_t j = first + c;
+            Fr s;
+            uint32_t k = 0, off = kzg_host::MIXED_NO_ITEM;
+            fe_set_zero(s);
+            if (j < d.count) {
+                const uint32_t i = a.perm[d.first + j];
+                Fr t;
+                mv_load_words(t, a.weights + 2 * (size_t)i);
+                Fr kin;
+#pragma unroll
+                for (int q = 0; q < NL; ++q) kin.l[q] = (int32_t)FrParams::K_IN[q];
+                fe_mul(s, t, kin);                                   // wire -> internal: (-m, 2m)
+                if (log_l) {
+                    Fr ninv;
+#pragma unroll
+                    for (int q = 0; q < NL; ++q) ninv.l[q] = (int32_t)FrParams::NINV[log_l * NL + q];
+                    fe_mul(s, s, ninv);
+                }
+                k = (uint32_t)a.ks[i];
+                off = a.val_off[i];
+            }
+            mv_planes_store(sc, cpt, c, s);
+            kk[c] = k;
+            vo[c] = off;
+        }
+        __syncthreads();                                             // the fill reads vo
+        // values: coset c of the tile at [c l, (c + 1) l), entry j at the bit-reversed position
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+            const uint32_t p = tid + 256u * e, c = p >> log_l, j = p & (l - 1), off = vo[c];
+            Fr v;
+            fe_set_zero(v);
+            if (off != kzg_host::MIXED_NO_ITEM) mv_load_words(v, a.ys + 2 * ((size_t)off + j));
+            const uint32_t rj = log_l ? __brev(j) >> (32 - log_l) : 0u;
+            mv_planes_store(x, E, (c << log_l) + rj, v);
+        }
+        __syncthreads();
+        // log l decimation-in-time stages, the bounds of k_coset_interp: inputs < 2^256 < 5.3 m; stage 0 (every twiddle 1) adds and subtracts
+        // them: < 10.6 m; from stage 1 on b w is in (-m, 2m), so a value grows by 2 m per stage: < 10.6 m + 9 * 2 m = 28.6 m (log l <= 10), and
+        // |b w| < 58 m^2 < 169 m^2.  Every value is stored normalised.
+#pragma unroll 1
+        for (int s = 0; s < log_l; ++s) {
+            const uint32_t h = 1u << s;
+#pragma unroll 1
+            for (uint32_t bi = tid; bi < E / 2; bi += 256) {
+                const uint32_t q = bi & (h - 1), base = ((bi >> s) << (s + 1)) + q;
+                Fr u, v, r0, r1;
+                mv_planes_load(u, x, E, base);
+                mv_planes_load(v, x, E, base + h);
+                if (s != 0) {
+                    Fr w;
+                    mv_planes_load(w, tw, ntw, q << (log_l - 1 - s));
+                    fe_mul(v, v, w);
+                }
+                fe_add(r0, u, v);
+                fe_sub(r1, u, v);
+                fe_norm(r0);
+                fe_norm(r1);
+                mv_planes_store(x, E, base, r0);
+                mv_planes_store(x, E, base + h, r1);
+            }
+            __syncthreads();
+        }
+        // entry t of coset c times r_i l^-1 w_s^(-k_i t), summed per lane across the tiles of this class.  The lazy rule of k_coset_interp: every
+        // 32nd sum is reduced (|acc| < 2 m + 32 * 2 m = 66 m < 169 m), the others normalised.
+        const bool reduce = ++pending == 32;
+        if (reduce) pending = 0;
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+            const uint32_t p = tid + 256u * e, c = p >> log_l, t = p & (l - 1);
+            Fr v, s;
+            mv_planes_load(v, x, E, p);
+            mv_planes_load(s, sc, cpt, c);
+            const uint32_t ex = (uint32_t)(((uint64_t)kk[c] * (uint64_t)t) & (uint64_t)n_mask) << up;   // < n_s 2^up = n_max
+            if (ex != 0) {
+                Fr w;
+                mv_root_pow(w, a.tb, ex);
+                fe_mul(s, s, w);
+            }
+            fe_mul(v, v, s);                                         // |v s| < 28.6 m * 2 m; the product is normalised, in (-m, 2m)
+            mv_lazy_add(acc[e], v, reduce);
+        }
+        __syncthreads();                                             // the next tile overwrites x, sc, kk, vo
+    }
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+        fe_reduce(acc[e]);                                           // |acc| < 66 m -> (-m, 2m), normalised
+        mv_planes_store(x, E, tid + 256u * e, acc[e]);
+    }
+    __syncthreads();
+    mv_fold(x, E, l, tid);
+    int32_t* row = a.partial + d.row_off + (size_t)wg * NL * l;
+    for (uint32_t t = tid; t < l; t += 256)
+#pragma unroll
+        for (int j = 0; j < NL; ++j) row[(size_t)j * l + t] = x[j * E + t];
 }
 
 }  // namespace kzg

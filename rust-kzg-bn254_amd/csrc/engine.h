@@ -16,6 +16,7 @@
 #include "host_locate.h"   // LocatePlan
 #include "host_prove_cosets.h"   // ProveCosetsPlan
 #include "host_prove_batch.h"    // ProveBatchPlan, the group budget
+#include "host_coset_mixed.h"    // MixedPlan
 
 namespace kzg_host { struct G1; struct G2; }   // host_pairing.h
 namespace kzg {
@@ -364,6 +365,11 @@ struct EncodeBytesIo {
 int32_t multiproof_encode_batch_bytes(kzg_ctx* ctx, kzg_srs* srs, bool eval_form, const EncodeBatchPlan& plan, const EncodeBytesIo& io);
 // verification of coset proofs (multiverify.hip): d_out[t] = sum_i weights[i] w^(-ks[i] t) IFFT_l(ys_i)[t], enqueued on ctx->stream (d_ys is scratch when l > 1024)
 int32_t coset_interpolate_rlc_device(kzg_ctx* ctx, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights, size_t count, size_t n, size_t l, uint4* d_out);
+// the same for items of mixed shapes (host_coset_mixed.h MixedPlan): d_out[t] = the sum over the items with l > t, t < l_max.  The plan's tables on the
+// device: perm, val_off (u32 per item), the class of each workgroup of the two launches, MixedClassDev per class, MixedRow per row
+struct MixedDevTables { const uint32_t *perm, *val_off, *wg_class[2]; const void *classes, *rows; };
+int32_t coset_interpolate_rlc_mixed_device(kzg_ctx* ctx, const kzg_host::MixedPlan& p, uint4* d_ys, const uint64_t* d_ks, const uint4* d_weights,
+                                           const MixedDevTables& t, uint4* d_out);
 // locating the bad groups of a batch (multilocate.hip; LocatePlan: host_locate.h).  Called under ctx->mu with the device set, count > 0.
 // the plan's arrays -> ctx->ml[1] (enqueued); the coefficients A_{g,t} of every non-empty group -> ctx->ml[0], d_ys overwritten (enqueued);
 // per non-empty group the XYZZ wire words of sum r_i pi_i and sum (r_i C_{c_i} + r_i w^(k_i l) pi_i) -> out_xyzz, 2 x 16 u64 each (synchronised)

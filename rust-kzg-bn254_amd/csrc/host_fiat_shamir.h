@@ -22,6 +22,7 @@ using ParallelFor = void (*)(size_t n, const std::function<void(size_t)>& job); 
 const char RC_BATCH_DOMAIN[] = "EIGENDA_RCKZGBATCH___V1_";       // primitives/src/consts.rs:11 (24 bytes)
 const char COSET_ITEM_DOMAIN[] = "KZGBN254_COSETITEM___V1_";     // 24 bytes each; this library's own transcript (the reference has no coset proofs)
 const char COSET_BATCH_DOMAIN[] = "KZGBN254_COSETBATCH__V1_";
+const char COSET_MIXED_DOMAIN[] = "KZGBN254_COSETMIXED__V1_";    // the batch level of a batch of mixed shapes (the item level is COSET_ITEM_DOMAIN's)
 const char HEADER_ITEM_DOMAIN[] = "KZGBN254_HEADERITEM__V1_";    // 24 bytes each; this library's own transcript for batches of blob headers
 const char HEADER_BATCH_DOMAIN[] = "KZGBN254_HEADERBATCH_V1_";
 
@@ -144,6 +145,44 @@ inline void multiproof_r_powers_host(const uint64_t* commitments, size_t n_commi
             put_u64be(item.data() + 24, commitment_indices[i]);
             put_u64be(item.data() + 32, coset_indices[i]);
             for (size_t t = 0; t < l; ++t) fr_wire_to_be_bytes(ys + 4 * (i * l + t), item.data() + 40 + 32 * t);
+            g1_serialize_compressed_ark(g1_from_wire(proofs + 8 * i), item.data() + 40 + 32 * l);
+            Sha256 sh;
+            sha256_init(sh);
+            sha256_update(sh, item.data(), item.size());
+            sha256_final(sh, data.data() + head + 32 * i);
+        }
+    };
+    if (jobs > 1) parallel_for(jobs, body); else if (jobs == 1) body(0);
+    hash_to_r_powers(data, count, out);
+}
+
+// The transcript of a batch of MIXED shapes (kzg_compute_multiproof_r_powers_mixed): class s is (n_s, l_s), item i has class s_i and its own
+// l_{s_i} values at ys + 4 value_offsets[i] (ragged, the caller's order).  The item digest is the one above, over the item's own values;
+// the batch level is COSET_MIXED_DOMAIN || u64be(n_classes) || n_classes x (u64be(n_s) || u64be(l_s)) || u64be(n_commitments) ||
+// u64be(count) || count x u64be(s_i) || the commitments || the digests.
+inline void multiproof_r_powers_mixed_host(const uint64_t* commitments, size_t n_commitments, const uint64_t* commitment_indices, const uint64_t* class_n,
+                                           const uint64_t* class_chunk_len, size_t n_classes, const uint64_t* class_indices, const uint64_t* coset_indices,
+                                           const uint64_t* ys, const uint32_t* value_offsets, const uint64_t* proofs, size_t count, uint64_t* out,
+                                           ParallelFor parallel_for) {
+    const size_t head = 24 + 8 + 16 * n_classes + 16 + 8 * count + 32 * n_commitments;
+    std::vector<uint8_t> data(head + 32 * count, 0);
+    uint8_t* p = data.data();
+    memcpy(p, COSET_MIXED_DOMAIN, 24); p += 24;
+    put_u64be(p, (uint64_t)n_classes); p += 8;
+    for (size_t s = 0; s < n_classes; ++s) { put_u64be(p, class_n[s]); put_u64be(p + 8, class_chunk_len[s]); p += 16; }
+    put_u64be(p, (uint64_t)n_commitments); put_u64be(p + 8, (uint64_t)count); p += 16;
+    for (size_t i = 0; i < count; ++i) { put_u64be(p, class_indices[i]); p += 8; }
+    for (size_t c = 0; c < n_commitments; ++c) { g1_serialize_compressed_ark(g1_from_wire(commitments + 8 * c), p); p += 32; }
+    const size_t per = 16, jobs = (count + per - 1) / per;
+    auto body = [&](size_t j) {
+        std::vector<uint8_t> item;
+        for (size_t i = j * per; i < std::min(count, (j + 1) * per); ++i) {
+            const size_t l = (size_t)class_chunk_len[class_indices[i]];
+            item.resize(24 + 16 + 32 * l + 32);
+            memcpy(item.data(), COSET_ITEM_DOMAIN, 24);
+            put_u64be(item.data() + 24, commitment_indices[i]);
+            put_u64be(item.data() + 32, coset_indices[i]);
+            for (size_t t = 0; t < l; ++t) fr_wire_to_be_bytes(ys + 4 * ((size_t)value_offsets[i] + t), item.data() + 40 + 32 * t);
             g1_serialize_compressed_ark(g1_from_wire(proofs + 8 * i), item.data() + 40 + 32 * l);
             Sha256 sh;
             sha256_init(sh);

@@ -566,6 +566,39 @@ def coset_interpolate_rlc(ys, coset_indices, weights, n: int, ctx=None) -> np.nd
     return out
 
 
+def coset_interpolate_rlc_mixed(classes, class_indices, coset_indices, ys, weights, ctx=None) -> np.ndarray:
+    """A_t = sum over the items i with l_i > t of weights[i] w_i^(-k_i t) IFFT_{l_i}(ys[i])_t for t < l_max (`kzg_coset_interpolate_rlc_mixed`, GPU):
+    items of mixed shapes in one call.  `classes` is a sequence of (n, l); item i has the class `class_indices[i]` and the coset
+    `coset_indices[i]` of that class's domain; `ys` is a sequence of (l_i, 4) arrays or one flat (sum l_i, 4) array in item order.  Returns
+    (l_max, 4), l_max the largest l over ALL classes; the same bits whatever the item order or the class numbering."""
+    cn = np.ascontiguousarray([int(c[0]) for c in classes], dtype=np.uint64)
+    cl = np.ascontiguousarray([int(c[1]) for c in classes], dtype=np.uint64)
+    si = np.ascontiguousarray([int(v) for v in class_indices], dtype=np.uint64)
+    ks = np.ascontiguousarray([int(v) for v in coset_indices], dtype=np.uint64)
+    if isinstance(ys, np.ndarray) and ys.ndim == 2:
+        flat = np.ascontiguousarray(_lib.as_u64(ys, 0))
+    else:
+        rows = [np.ascontiguousarray(_lib.as_u64(y, 0)).reshape(-1, 4) for y in ys]
+        if len(rows) != len(si):
+            raise InvalidInputLength()
+        flat = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros((0, 4), np.uint64)
+    ws = np.ascontiguousarray(_lib.as_u64(weights, 0)).reshape(-1, 4)
+    count = len(si)
+    if len(ks) != count or len(ws) != count or flat.ndim != 2 or flat.shape[1] != 4:
+        raise InvalidInputLength()
+    if all(int(s) < len(cl) for s in si) and len(flat) != sum(int(cl[int(s)]) for s in si):
+        raise InvalidInputLength()
+    ctx = ctx or _lib.default_context()
+    out = np.zeros((int(cl.max()) if len(cl) and int(cl.max()) <= (1 << 23) else 0, 4), dtype=np.uint64)   # (a longer chunk is refused by the call)
+    opt = lambda a: _lib.ptr(a) if len(a) else None                              # noqa: E731
+    rc = _lib.load().kzg_coset_interpolate_rlc_mixed(ctx.handle, opt(cn), opt(cl), len(cn), opt(si), opt(ks), opt(flat), opt(ws), count,
+                                                     _lib.ptr(out) if len(out) else _lib.ptr(np.zeros((1, 4), np.uint64)))
+    ctx.check_device(rc)
+    if rc != _lib.OK:
+        raise GenericError(_lib.status_message(rc))
+    return out
+
+
 def sha256_rows(rows, ctx=None) -> np.ndarray:
     """SHA-256 of every row of a 2-D uint8 array (`kzg_sha256_rows`, GPU: one lane per row): (count, row_len) -> (count, 32)."""
     rows = np.ascontiguousarray(rows, dtype=np.uint8)
